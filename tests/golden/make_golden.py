@@ -1,7 +1,7 @@
 """Generates the golden fixtures of tests/golden/*.npz from the oracle (oracle/pqp_oracle.py) and the synthetic
 generator.  The reference holds no vectors for this path, so these are produced here, by the
 build's own restatement, and pinned by the KKT certificate stored next to them.
-Run from the repo root:  python tests/golden/make_golden.py"""
+Run from the repo root:  python tests/golden/make_golden.py   (reference_pieces.npz: python tests/golden/make_golden.py reference)"""
 import os
 import sys
 
@@ -116,9 +116,20 @@ def make_smoother_fixture(name):
     print(name, sorted(out)[:6], "...")
 
 
+def make_reference_fixture(name):
+    """What the reference's std-only pieces compute on the tests' fixed inputs (tests/ref_pieces.py; needs oracle/_ref: `make -C oracle ref`)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_pieces as RP
+    out = RP.record()
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+    print(name, len(out), "arrays")
+
+
 if __name__ == "__main__":
     if "smoothers" in sys.argv[1:]:
         make_smoother_fixture("smoothers"); sys.exit(0)
+    if "reference" in sys.argv[1:]:
+        make_reference_fixture("reference_pieces"); sys.exit(0)
     make_smoother_fixture("smoothers")
     make_line_fixture("line_a", 3)
     make("path_n8", 8, 4, "varied")

@@ -1,7 +1,6 @@
 """The CPU restatement of the corridor-bounds step (oracle/corridor_oracle.py) against what can be pinned here:
-the reference's own tk::spline compiled from /root/reference (oracle/_ref, bit for bit), and analytic known answers
+the reference's own tk::spline bit for bit (its values recorded in tests/golden/reference_pieces.npz, see tests/ref_pieces.py), and analytic known answers
 for the restated grid_map lookups and the clearance search."""
-import ctypes as C
 import math
 import os
 
@@ -10,30 +9,21 @@ import pytest
 
 import corridor_oracle as K
 import corridor_util as U
+import ref_pieces as RP
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SPLINE = os.path.join(ROOT, "oracle", "_ref", "libref_spline.so")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SPLINE), reason="oracle/_ref not built (needs /root/reference: `make -C oracle ref`)")
 def test_spline_restatement_is_the_reference_bit_for_bit():
-    lib = C.CDLL(REF_SPLINE)
-    lib.ref_spline_new.restype = C.c_void_p; lib.ref_spline_new.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    lib.ref_spline_eval.restype = C.c_double; lib.ref_spline_eval.argtypes = [C.c_void_p, C.c_double]
-    lib.ref_spline_deriv.restype = C.c_double; lib.ref_spline_deriv.argtypes = [C.c_void_p, C.c_int, C.c_double]
-    lib.ref_spline_free.argtypes = [C.c_void_p]
-    rng = np.random.default_rng(0)
-    for _ in range(12):
-        n = int(rng.integers(3, 60))
-        x = np.cumsum(rng.uniform(0.2, 3.0, n)); y = np.cumsum(rng.normal(size=n))
+    ref = RP.reference()
+    for c in range(RP.SPLINE_CASES):
+        x, y, t, want = ref[f"spline{c}_x"], ref[f"spline{c}_y"], ref[f"spline{c}_t"], ref[f"spline{c}_value"]
         sp = K.spline_fit(x, y)
-        h = lib.ref_spline_new(n, x.ctypes.data, y.ctypes.data)
-        for t in np.concatenate([x, rng.uniform(x[0] - 3, x[-1] + 3, 120)]):      # knots, interior, both extrapolations
-            t = float(t)
-            assert K.spline_eval(sp, t) == lib.ref_spline_eval(h, t)
+        for v, w in zip(t, want):                                  # knots, interior, both extrapolations
+            v = float(v)
+            assert K.spline_eval(sp, v) == w[0]
             for order in (1, 2, 3):
-                assert K.spline_deriv(sp, order, t) == lib.ref_spline_deriv(h, order, t)
-        lib.ref_spline_free(h)
+                assert K.spline_deriv(sp, order, v) == w[order]
 
 
 def test_spline_interpolates_and_is_c2():

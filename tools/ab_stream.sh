@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of library builds on the lane-per-QP (stream) kernel's lines in ONE GPU call:  LIBS="name=path ..." tools/ab_stream.sh <tag>
 tag=$1; o=gpurun_out/${tag}; mkdir -p gpurun_out; root=$PWD
-Q="--no-cpu-baseline --no-secondary --pmc off --sustain 0"
+Q="--full --no-cpu-baseline --no-secondary --pmc off --sustain 0"          # --full: the line keeps solved / out_sha1 / kkt_solves
 line() { python -c "
 import json,sys
 ls=[l for l in sys.stdin.readlines() if l.startswith('{\"metric\"')]

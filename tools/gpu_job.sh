@@ -14,7 +14,7 @@ o=gpurun_out/${tag}; mkdir -p gpurun_out
 export TMPDIR=/tmp
 root=$PWD
 F='RCCL\|HIP version\|ROCm version\|Hostname\|Librccl\|amdgpu.ids'
-Q="--no-cpu-baseline --no-secondary --pmc off --sustain 0"
+Q="--full --no-cpu-baseline --no-secondary --pmc off --sustain 0"          # --full: the line keeps solved / out_sha1 / kkt_solves
 line() { python -c "
 import json,sys
 ls=[l for l in sys.stdin.readlines() if l.startswith('{\"metric\"')]
@@ -26,12 +26,12 @@ for sec in "$@"; do case $sec in
 tests)
   (timeout 1800 python -m pytest tests -m gpu -q -x 2>&1 | grep -v "$F" | tail -15) > ${o}_pytest.log 2>&1; tail -5 ${o}_pytest.log ;;
 bench)
-  (time timeout 900 python bench.py > ${o}_bench_n1.json) 2> ${o}_bench_n1.err
-  timeout 300 python bench.py --steps 20 --warmup 3 > ${o}_bench_driver_style.json 2> /dev/null
-  timeout 600 python bench.py --config 3 --batch 65536 --steps 40 --no-cpu-baseline > ${o}_bench_stream_65536.json 2> /dev/null
-  timeout 300 python bench.py --config 2 --steps 40 --no-cpu-baseline > ${o}_bench_config2.json 2> /dev/null
-  timeout 300 python bench.py --config 3 --steps 100 --no-cpu-baseline > ${o}_bench_config3_shard.json 2> /dev/null
-  timeout 300 python bench.py --config 4 --steps 200 --no-cpu-baseline > ${o}_bench_config4.json 2> /dev/null
+  (time timeout 900 python bench.py --full > ${o}_bench_n1.json) 2> ${o}_bench_n1.err
+  timeout 300 python bench.py --full --steps 20 --warmup 3 > ${o}_bench_driver_style.json 2> /dev/null
+  timeout 600 python bench.py --full --config 3 --batch 65536 --steps 40 --no-cpu-baseline > ${o}_bench_stream_65536.json 2> /dev/null
+  timeout 300 python bench.py --full --config 2 --steps 40 --no-cpu-baseline > ${o}_bench_config2.json 2> /dev/null
+  timeout 300 python bench.py --full --config 3 --steps 100 --no-cpu-baseline > ${o}_bench_config3_shard.json 2> /dev/null
+  timeout 300 python bench.py --full --config 4 --steps 200 --no-cpu-baseline > ${o}_bench_config4.json 2> /dev/null
   for f in n1 driver_style stream_65536 config2 config3_shard config4; do cat ${o}_bench_$f.json | line $f; done | tee ${o}_bench_summary.txt
   (cd /tmp && rm -rf /tmp/rp1 && rocprofv3 --kernel-trace --stats -f csv -d /tmp/rp1 -- python $root/bench.py $Q > ${root}/${o}_bench_n1_under_rocprof.json 2> /dev/null)
   cp $(find /tmp/rp1 -name "*kernel_stats.csv" | head -1) ${o}_bench_n1_kernel_stats.csv; head -3 ${o}_bench_n1_kernel_stats.csv ;;

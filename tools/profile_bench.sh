@@ -7,7 +7,7 @@ tag=$1; shift
 out=$GRAFT_REPO_ROOT/gpurun_out/prof/$tag; mkdir -p $out
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
-cmd="python $root/bench.py --no-cpu-baseline --steps 20 --warmup 3 $*"
+cmd="python $root/bench.py --full --no-cpu-baseline --steps 20 --warmup 3 $*"
 rocprofv3 --kernel-trace --stats -f csv -d $out/stats -- $cmd > $out/stats.log 2>&1
 i=0
 for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_FLAT SQ_LDS_BANK_CONFLICT" \
