@@ -455,6 +455,22 @@ int pqp_corridor_bounds(pqp_handle* h, int batch, int n, int m, const double* re
                         const double* spline_ext, const float* dist, int n_maps, const int32_t* map_of, const pqp_grid_geometry* geom,
                         const pqp_corridor_params* prm, double* bounds, int32_t* n_valid);
 
+/* ---- the obstacle distance layer from an occupancy grid --------------------------------------------------------------------------
+ * cv::distanceTransform(obstacle, dist, CV_DIST_L2, CV_DIST_MASK_PRECISE); dist *= resolution   (src/test/demo.cpp:104-113), for n_maps maps
+ * in one call: an exact Euclidean distance transform, in the layout the map-reading entry points take.
+ * grid [n_maps][cols][rows] uint8, the layout of dist; a cell is an obstacle iff its byte is 0 (the reference's OCCUPY = 0, FREE = 255)
+ * dist [n_maps][cols][rows] float, ready for pqp_corridor_bounds / pqp_dp_corridor / pqp_clearance_device / pqp_optimize_path_device
+ * geom as for pqp_corridor_bounds (2 x 2 up to 2^30 cells per map, resolution > 0); only rows, cols and resolution are read.
+ * Every cell gets, bit for bit, fl32(fl32(sqrt(d2)) * fl32(resolution)) with d2 the least (dr)^2 + (dc)^2 to an obstacle cell of its map
+ * (0 on an obstacle; cells outside the map are not obstacles) and sqrt correctly rounded.  A map without any obstacle cell gets
+ * d2 = rows^2 + cols^2 everywhere (hypot(rows, cols) cells: finite, beyond every distance inside the map): our choice, OpenCV's value for
+ * that case is not pinned.
+ * The _device form takes device pointers, allocates nothing and is asynchronous on the handle's stream (it can be enqueued right in front
+ * of pqp_optimize_path_device); the host form copies in, runs, copies out and synchronises.  PQP_ERR_INVALID: a null pointer,
+ * n_maps < 1, a bad geometry or a resolution that is not positive (NaN included). */
+int pqp_distance_layer_device(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist);
+int pqp_distance_layer(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist);
+
 /* ---- reference states from the reference line's spline + the vehicle's initial error -------------------
  * ReferencePathImpl::buildReferenceFromSpline(delta_s_smaller, delta_s_larger)  src/data_struct/reference_path_impl.cpp:314-338
  *   (called with output_spacing / 2, output_spacing = 0.15, 0.3 at path_optimizer.cpp:119; dynamic = FLAGS_enable_dynamic_segmentation)

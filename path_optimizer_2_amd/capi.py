@@ -68,6 +68,7 @@ EXPORTS = [
     "pqp_post_smooth", "pqp_post_smooth_device", "pqp_corridor_default_params", "pqp_corridor_bounds", "pqp_corridor_bounds_device",
     "pqp_reference_states", "pqp_reference_states_device", "pqp_spline_fit", "pqp_spline_fit_device", "pqp_dp_default_params",
     "pqp_dp_corridor", "pqp_dp_corridor_device", "pqp_segment_raw_reference", "pqp_segment_raw_reference_device", "pqp_bspline_resample", "pqp_bspline_resample_device", "pqp_reference_length", "pqp_reference_length_device", "pqp_offsets_to_points", "pqp_offsets_to_points_device",
+    "pqp_distance_layer", "pqp_distance_layer_device",
 ]
 
 _lib = None
@@ -175,6 +176,8 @@ def load_library(path=None, with_torch=None):
                                     vp, vp, vp, vp, vp]
     for name in ("pqp_path_solve_var_device", "pqp_path_solve_var"):
         getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    for name in ("pqp_distance_layer", "pqp_distance_layer_device"):
+        getattr(lib, name).argtypes = [vp, C.c_int, C.POINTER(PqpGridGeometry), vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -290,6 +293,15 @@ class PqpError(RuntimeError):
     pass
 
 
+def _occupancy(grid, who):
+    """uint8 occupancy grids [n_maps][rows][cols] (0 = obstacle).  A bool mask is refused: which of its values would mean obstacle is easy
+    to get backwards."""
+    grid = np.asarray(grid)
+    if grid.dtype != np.uint8:
+        raise TypeError(f"{who}: grid must be uint8 with 0 = obstacle, not {grid.dtype}")
+    return grid[None] if grid.ndim == 2 else grid
+
+
 class Handle:
     """Thin RAII wrapper over pqp_handle (one per GPU)."""
 
@@ -365,20 +377,37 @@ class Handle:
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  Returns dict(out [B][n_max][7], n_out, status, stage, iters)."""
+        dist = np.asarray(dist, dtype=np.float32)
+        if dist.ndim == 2:
+            dist = dist[None]
+        return self._chain(points, n_points, start, target, np.transpose(dist, (0, 2, 1)), np.float32, None, geom, map_of, smoother, cfg, start_k)
+
+    def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None):
+        """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
+        device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
+        no host round trip between the two.  Returns what optimize_path returns."""
+        grid = _occupancy(grid, "optimize_path_on_grid")
+        build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
+                                                                                      C.c_void_p(d_dist.data_ptr())))
+        return self._chain(points, n_points, start, target, np.transpose(grid, (0, 2, 1)), np.uint8, build, geom, map_of, smoother, cfg, start_k)
+
+    def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k):
+        """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
+        them on the handle's stream (None: they are the layer)"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
         t = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        dist = np.asarray(dist, dtype=np.float32)
-        if dist.ndim == 2:
-            dist = dist[None]
-        d_dist = t(np.transpose(dist, (0, 2, 1)), np.float32)              # the ABI's column-major layer
+        d_layer = t(layer_cm, layer_dtype)
+        d_dist = d_layer if build is None else torch.empty(d_layer.shape, dtype=torch.float32, device=dev)
         B, p_max = points.shape[0], points.shape[1]
         d_pts, d_np, d_st, d_tg = t(points, np.float64), t(n_points, np.int32), t(start, np.float64), t(target, np.float64)
         d_map, d_k = t(map_of, np.int32), t(start_k, np.float64)
         out = torch.zeros((B, cfg.n_max, 7), dtype=torch.float64, device=dev)
         ints = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4)]
         torch.cuda.synchronize(dev)
+        if build is not None:
+            build(d_layer, d_dist)
         p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
         self._check(self.lib.pqp_optimize_path_device(self._h, smoother._h if smoother is not None else None, C.byref(cfg), B, p_max, p(d_pts), p(d_np),
                                                       p(d_st), p(d_tg), p(d_dist), p(d_map), C.byref(geom), p(d_k), p(out), p(ints[0]), p(ints[1]),
@@ -387,6 +416,17 @@ class Handle:
         if smoother is not None:
             smoother.sync()
         return dict(out=out.cpu().numpy(), n_out=ints[0].cpu().numpy(), status=ints[1].cpu().numpy(), stage=ints[2].cpu().numpy(), iters=ints[3].cpu().numpy())
+
+    def distance_layer(self, grid, geom):
+        """pqp_distance_layer (host arrays): grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, in the orientation corridor_bounds takes
+        its layer -> the float32 distance layer [n_maps][rows][cols] (2-D in, 2-D out)."""
+        two_d = np.ndim(grid) == 2
+        grid = _occupancy(grid, "distance_layer")
+        cm = np.ascontiguousarray(np.transpose(grid, (0, 2, 1)))          # the ABI's column-major [n_maps][cols][rows]
+        out = np.empty(cm.shape, dtype=np.float32)
+        self._check(self.lib.pqp_distance_layer(self._h, cm.shape[0], C.byref(geom), _ptr(cm), _ptr(out)))
+        out = np.transpose(out, (0, 2, 1))
+        return out[0] if two_d else out
 
     def corridor_params(self, **over):
         p = PqpCorridorParams()

@@ -11,6 +11,7 @@
 // No CPU fallback: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -245,6 +246,7 @@ __global__ void constrain_angle_kernel(int count, const double* __restrict__ in,
 
 #include "pqp_smoother_kernels.inc"
 #include "pqp_corridor_kernels.inc"
+#include "pqp_distance_kernels.inc"
 
 // =========================================================================================================
 // C ABI
@@ -1334,6 +1336,43 @@ int pqp_corridor_bounds(pqp_handle* h, int batch, int n, int m, const double* re
         return rc;
     PQP_HIP(hipMemcpyAsync(bounds, h->c_buf[5].p, b_bnd, hipMemcpyDeviceToHost, h->stream));
     PQP_HIP(hipMemcpyAsync(n_valid, h->c_buf[6].p, b_nv, hipMemcpyDeviceToHost, h->stream));
+    PQP_HIP(hipStreamSynchronize(h->stream));
+    return PQP_OK;
+}
+
+// ---- the obstacle distance layer from an occupancy grid (src/test/demo.cpp:104-113) ------------------------------------------------
+int pqp_distance_layer_device(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist) {
+    if (!h || !grid || !dist || n_maps < 1 || !geometry_ok(geom))
+        return fail(PQP_ERR_INVALID, "pqp_distance_layer: bad argument (n_maps >= 1; a map of 2 x 2 to 2^30 cells, resolution > 0)");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::DistanceArgs a;
+    a.grid = grid; a.out = reinterpret_cast<int32_t*>(dist); a.n_maps = n_maps; a.rows = geom->rows; a.cols = geom->cols;
+    const pqp::edt::Shape sh = pqp::edt::shape_of(geom->rows, geom->cols);
+    a.site_bits = sh.site_bits; a.empty_d2 = sh.empty_d2; a.res = (float)geom->resolution;
+    const long long lines = (long long)n_maps * geom->cols, lanes = (long long)n_maps * geom->rows;
+    h->next_event_pair();
+    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(pqp::distance_lines_kernel, dim3((unsigned)std::min((lines + 3) / 4, 1ll << 20)), dim3(256), 0, h->stream, a);
+    PQP_HIP(hipGetLastError());
+    const unsigned blocks = (unsigned)std::min((lanes + 63) / 64, 1ll << 20);
+    if (sh.wide) hipLaunchKernelGGL(pqp::distance_envelope_kernel<int64_t>, dim3(blocks), dim3(64), 0, h->stream, a);
+    else hipLaunchKernelGGL(pqp::distance_envelope_kernel<int32_t>, dim3(blocks), dim3(64), 0, h->stream, a);
+    PQP_HIP(hipGetLastError());
+    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return PQP_OK;
+}
+
+int pqp_distance_layer(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist) {
+    if (!h || !grid || !dist || n_maps < 1 || !geometry_ok(geom))
+        return fail(PQP_ERR_INVALID, "pqp_distance_layer: bad argument (n_maps >= 1; a map of 2 x 2 to 2^30 cells, resolution > 0)");
+    PQP_HIP(hipSetDevice(h->device));
+    const size_t cells = (size_t)n_maps * geom->rows * geom->cols;
+    int rc;
+    if ((rc = h->c_buf[0].ensure(cells)) || (rc = h->c_buf[1].ensure(cells * 4))) return rc;
+    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, grid, cells, hipMemcpyHostToDevice, h->stream));
+    if ((rc = pqp_distance_layer_device(h, n_maps, geom, h->c_buf[0].as<uint8_t>(), h->c_buf[1].as<float>()))) return rc;
+    PQP_HIP(hipMemcpyAsync(dist, h->c_buf[1].p, cells * 4, hipMemcpyDeviceToHost, h->stream));
     PQP_HIP(hipStreamSynchronize(h->stream));
     return PQP_OK;
 }

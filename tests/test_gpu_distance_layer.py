@@ -1,0 +1,167 @@
+"""pqp_distance_layer on the GPU: bit for bit the restatement of cv::distanceTransform(..., CV_DIST_L2, CV_DIST_MASK_PRECISE) * resolution
+(tests/distance_util.py; reference src/test/demo.cpp:104-113) on the reference's own map and on random maps, many maps in one launch,
+the device form in front of the map-reading steps on one stream, and bad arguments.  Run with -m gpu on an MI355X."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import corridor_util as U
+import distance_util as D
+from path_optimizer_2_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def handle(hip_lib):
+    h = capi.Handle(capi.default_params(), device=0, max_batch=64, max_n=128)
+    yield h
+    h.close()
+
+
+def _geom(rows, cols, res=0.2):
+    return capi.PqpGridGeometry(rows, cols, res, rows * res, cols * res, 0.0, 0.0)
+
+
+def _same(got, want):
+    return got.shape == want.shape and np.array_equal(np.asarray(got, np.float32).view(np.int32), np.asarray(want, np.float32).view(np.int32))
+
+
+def test_reference_map_bit_for_bit(handle):
+    g, res = D.reference_map()
+    got = handle.distance_layer(g, _geom(*g.shape, res))
+    want = D.distance_layer(g, res)
+    assert _same(got, want)
+    assert want.max() == np.float32(np.float32(77.0) * np.float32(0.2))
+
+
+def _special_maps(rows, cols):
+    chk = np.where((np.indices((rows, cols)).sum(axis=0) % 2) == 0, 0, 255).astype(np.uint8)
+    corner = np.full((rows, cols), 255, np.uint8)
+    corner[-1, -1] = 0
+    return {"all_obstacle": np.zeros((rows, cols), np.uint8), "no_obstacle": np.full((rows, cols), 255, np.uint8), "corner": corner, "checkerboard": chk}
+
+
+@pytest.mark.parametrize("shape", [(2, 2), (2, 1000), (1000, 2), (333, 517), (1024, 1024), (4096, 64)])
+def test_random_and_special_maps_bit_for_bit(handle, shape):
+    rng = np.random.default_rng(shape[0] * 7 + shape[1])
+    maps = {f"density {d}": np.where(rng.uniform(size=shape) < d, 0, rng.integers(1, 256, size=shape)).astype(np.uint8) for d in (0.001, 0.35, 0.99)}
+    maps.update(_special_maps(*shape))
+    for name, g in maps.items():
+        got = handle.distance_layer(g, _geom(*shape))
+        assert _same(got, D.distance_layer(g, 0.2)), name
+
+
+def test_squared_distances_beyond_2_31(handle):
+    g = np.full((60000, 3), 255, np.uint8)
+    g[0, :] = 0
+    got = handle.distance_layer(g, _geom(60000, 3))
+    want = np.broadcast_to(np.arange(60000, dtype=np.float32)[:, None] * np.float32(0.2), g.shape)
+    assert _same(got, want)
+
+
+def test_many_maps_in_one_call_and_nothing_written_beyond_them(handle):
+    import torch
+    rng = np.random.default_rng(64)
+    rows, cols, n = 97, 131, 64
+    maps = np.stack([np.where(rng.uniform(size=(rows, cols)) < rng.uniform(0.0, 0.5), 0, 255).astype(np.uint8) for _ in range(n)])
+    maps[5] = 255                                              # one map without obstacle among them
+    geom = _geom(rows, cols)
+    dev = torch.device("cuda", 0)
+    cells, pad = rows * cols, 4096
+    d_grid = torch.from_numpy(np.ascontiguousarray(np.transpose(maps, (0, 2, 1)))).to(dev)
+    d_buf = torch.full((n * cells + 2 * pad,), float("nan"), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    rc = handle.lib.pqp_distance_layer_device(handle._h, n, C.byref(geom), C.c_void_p(d_grid.data_ptr()), C.c_void_p(d_buf.data_ptr() + 4 * pad))
+    assert rc == 0
+    handle.sync()
+    buf = d_buf.cpu().numpy()
+    assert np.isnan(buf[:pad]).all() and np.isnan(buf[pad + n * cells:]).all()
+    body = buf[pad:pad + n * cells]
+    assert not np.isnan(body).any()
+    got = np.transpose(body.reshape(n, cols, rows), (0, 2, 1))
+    for k in range(n):
+        alone = handle.distance_layer(maps[k], geom)
+        assert _same(got[k], alone), k
+        assert _same(alone, D.distance_layer(maps[k], 0.2)), k
+
+
+def test_device_layer_feeds_corridor_bounds_on_the_same_stream(handle):
+    import torch
+    c = U.build(3, n=60)
+    sc, dist = c["scene"], c["dist"]
+    occ = D.occupancy_of(dist)
+    layer = D.distance_layer(occ, sc["resolution"])
+    geom = capi.PqpGridGeometry(sc["rows"], sc["cols"], sc["resolution"], sc["length"][0], sc["length"][1], sc["pos"][0], sc["pos"][1])
+    want, nv_want = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], layer, geom)
+    dev = torch.device("cuda", 0)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    d_grid = t(occ.T, np.uint8)
+    d_dist = torch.full((sc["cols"], sc["rows"]), float("nan"), dtype=torch.float32, device=dev)
+    d_ref, d_tab, d_ext = t(c["ref"][None], np.float64), t(c["tab"][None], np.float64), t(c["ext"][None], np.float64)
+    n, m = c["ref"].shape[0], c["tab"].shape[1]
+    d_bounds = torch.zeros((1, n, 6), dtype=torch.float64, device=dev)
+    d_nv = torch.zeros(1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    p = lambda x: C.c_void_p(x.data_ptr())
+    prm = handle.corridor_params()
+    assert handle.lib.pqp_distance_layer_device(handle._h, 1, C.byref(geom), p(d_grid), p(d_dist)) == 0
+    assert handle.lib.pqp_corridor_bounds_device(handle._h, 1, n, m, p(d_ref), None, p(d_tab), p(d_ext), p(d_dist), None, C.byref(geom), C.byref(prm),
+                                                 p(d_bounds), p(d_nv)) == 0
+    handle.sync()
+    assert _same(d_dist.cpu().numpy().T, layer)
+    assert np.array_equal(d_bounds.cpu().numpy(), want) and d_nv.cpu().numpy()[0] == nv_want[0]
+
+
+def test_optimize_path_on_grid_equals_optimize_path_on_the_layer(hip_lib):
+    from test_gpu_chain import _scenarios, _smoother_params
+    B = 24
+    sc = _scenarios(B)
+    occ = D.occupancy_of(sc["dist"])
+    layer = D.distance_layer(occ, sc["geom"].resolution)
+    h = capi.Handle(capi.production_params(), max_batch=B, max_n=256)
+    hs = capi.Handle(_smoother_params(), max_batch=B, max_n=128)
+    try:
+        want = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], layer, sc["geom"], map_of=sc["map_of"], smoother=hs)
+        got = h.optimize_path_on_grid(sc["pts"], sc["n_pts"], sc["start"], sc["target"], occ, sc["geom"], map_of=sc["map_of"], smoother=hs)
+    finally:
+        h.close()
+        hs.close()
+    assert (want["stage"] == 0).sum() >= B // 2, want["stage"]
+    for k in ("n_out", "status", "stage", "iters"):
+        assert np.array_equal(got[k], want[k]), k
+    assert np.array_equal(got["out"], want["out"])
+
+
+def test_bad_arguments_launch_nothing(handle):
+    import torch
+    lib, h = handle.lib, handle._h
+    dev = torch.device("cuda", 0)
+    d_grid = torch.zeros((8, 8), dtype=torch.uint8, device=dev)
+    d_dist = torch.full((8, 8), float("nan"), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    p = lambda x: C.c_void_p(x.data_ptr())
+    good = _geom(8, 8)
+    bad = [(None, 1, good, p(d_grid), p(d_dist)), (h, 0, good, p(d_grid), p(d_dist)), (h, 1, None, p(d_grid), p(d_dist)),
+           (h, 1, good, None, p(d_dist)), (h, 1, good, p(d_grid), None), (h, 1, _geom(1, 8), p(d_grid), p(d_dist)),
+           (h, 1, _geom(8, 1), p(d_grid), p(d_dist)), (h, 1, _geom(1 << 15, 1 << 15), p(d_grid), p(d_dist)),
+           (h, 1, _geom(8, 8, 0.0), p(d_grid), p(d_dist)), (h, 1, _geom(8, 8, -0.2), p(d_grid), p(d_dist)),
+           (h, 1, _geom(8, 8, float("nan")), p(d_grid), p(d_dist))]
+    for k, args in enumerate(bad):
+        geom = args[2]
+        assert lib.pqp_distance_layer_device(args[0], args[1], None if geom is None else C.byref(geom), args[3], args[4]) == -1, k          # PQP_ERR_INVALID
+        assert lib.pqp_distance_layer(args[0], args[1], None if geom is None else C.byref(geom), None, None) == -1, k          # PQP_ERR_INVALID
+    handle.sync()
+    assert torch.isnan(d_dist).all().item()
+
+
+def test_synth_layers_agree_within_one_ulp(handle):
+    """make_scene's layer multiplies in float64 before its one rounding; the ABI rounds the square root to float first (MatrixXf *= double
+    multiplies in float).  The two differ by at most one float ulp: documented here, not a gate on either."""
+    from path_optimizer_2_amd.synth import make_scene
+    for seed in range(4):
+        s = make_scene(seed=seed)
+        got = handle.distance_layer(D.occupancy_of(s["dist"]), _geom(s["rows"], s["cols"], s["resolution"]))
+        ulps = np.abs(got.view(np.int32).astype(np.int64) - s["dist"].view(np.int32).astype(np.int64))
+        assert ulps.max() <= 1, ulps.max()
