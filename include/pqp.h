@@ -636,6 +636,45 @@ int pqp_post_smooth_var_device(pqp_handle* h, int batch, int m_max, const int32_
 int pqp_spline_fit_var_device(pqp_handle* h, int batch, int m_max, const int32_t* m_of, const double* s, const double* x, const double* y,
                               double* spline, double* spline_ext);
 
+/* ---- vehicle footprints of planned states against the distance layer ----------------------------------------------------------------
+ * CollisionChecker (src/tools/collision_checker.cpp:9-58) with CarGeometry's six-circle footprint (src/tools/car_geometry.cpp:38-72) and
+ * local2Global (src/tools/tools.cpp:50-55), for many states of many scenarios per call.  PathOptimizer builds such a checker from its map
+ * (path_optimizer.cpp:29); the path QP's collision rows are soft, so a SOLVED path may still put a corner of the car into an obstacle. */
+typedef struct pqp_car_geometry {        /* CollisionChecker ctor (collision_checker.cpp:9-14): car_(car_width, fabs(rear_length), front_length) */
+    double width;                        /* 2.0   FLAGS_car_width     planning_flags.cpp:10 */
+    double rear_length;                  /* -1.0  FLAGS_rear_length   planning_flags.cpp:18 (the flag's sign; the checker takes fabs) */
+    double front_length;                 /* 3.9   FLAGS_front_length  planning_flags.cpp:20 */
+} pqp_car_geometry;
+typedef enum pqp_footprint_mode {
+    PQP_FOOTPRINT_CIRCLES = 0,           /* isSingleStateCollisionFree          collision_checker.cpp:17-39: the six circles */
+    PQP_FOOTPRINT_BOUNDING_FIRST = 1     /* isSingleStateCollisionFreeImproved  collision_checker.cpp:41-58: the bounding circle, the six when it is not clear */
+} pqp_footprint_mode;
+void pqp_car_default_geometry(pqp_car_geometry* c);
+/* Pure host: CarGeometry::setCircles (car_geometry.cpp:38-57) in the vehicle frame, in the reference's expression order.
+ * circles [7][3] = x, y, r of rr, rl, fr, fl, fm, rm (getCircles' order), then the bounding circle (getBoundingCircle).
+ * PQP_ERR_INVALID: a null pointer or a geometry that is not finite. */
+int pqp_car_circles(const pqp_car_geometry* c, double* circles);
+/* states [batch][n][stride]  x, y, heading at offsets 0, 1, 2 (stride = PQP_OUT_STRIDE reads pqp_optimize_path_device's `out` in place)
+ * n_of [batch] or NULL       states of each scenario (<= n), e.g. the chain's n_out; NULL: all have n
+ * dist / map_of / geom       the distance layer(s), as for pqp_corridor_bounds; pqp_footprint_check takes n_maps after dist, as it does
+ * car, mode                  the footprint and pqp_footprint_mode
+ * free_out [batch][n]        1 when the state is collision-free in `mode`, else 0; a circle whose centre is outside the map is a collision
+ *                            (:32-35, :56-57), so is a state that is not finite; 0 at index n_of[b] and beyond
+ * first_collision [batch]    the first colliding index below n_of[b], n_of[b] when there is none (the convention of n_valid)
+ * margin [batch][n] or NULL  min over the six circles of Map::getObstacleDistance(centre) - r (Map.cpp:16-22: 0 outside the map), whatever
+ *                            the mode; 0 at index n_of[b] and beyond
+ * In BOUNDING_FIRST mode a state can be free where CIRCLES says collision (the corner circles poke out of the bounding circle and the
+ * layer is interpolated): each mode gives the reference's own answer.
+ * The _device form takes device pointers and is asynchronous on the handle's stream (enqueue it right behind pqp_optimize_path_device);
+ * it checks null pointers and sizes only.  The host form copies in, runs, copies out and synchronises; PQP_ERR_INVALID, with nothing
+ * launched, also for a map_of value outside [0, n_maps), stride < 3, a car geometry that is not finite or a bad mode. */
+int pqp_footprint_check_device(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist,
+                               const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
+                               int32_t* first_collision, double* margin);
+int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist, int n_maps,
+                        const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
+                        int32_t* first_collision, double* margin);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,13 @@ class PqpChainConfig(C.Structure):
                 ("corridor", PqpCorridorParams), ("dp", PqpDpParams), ("smoothing_method", C.c_int32)]
 
 
+class PqpCarGeometry(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("width", "rear_length", "front_length")]
+
+
+FOOTPRINT_CIRCLES, FOOTPRINT_BOUNDING_FIRST = 0, 1      # pqp_footprint_mode
+
+
 class PqpSizes(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "state", "control", "precise", "slack", "vars", "cons", "nnz_a", "nnz_p")]
 
@@ -69,6 +76,7 @@ EXPORTS = [
     "pqp_reference_states", "pqp_reference_states_device", "pqp_spline_fit", "pqp_spline_fit_device", "pqp_dp_default_params",
     "pqp_dp_corridor", "pqp_dp_corridor_device", "pqp_segment_raw_reference", "pqp_segment_raw_reference_device", "pqp_bspline_resample", "pqp_bspline_resample_device", "pqp_reference_length", "pqp_reference_length_device", "pqp_offsets_to_points", "pqp_offsets_to_points_device",
     "pqp_distance_layer", "pqp_distance_layer_device",
+    "pqp_car_default_geometry", "pqp_car_circles", "pqp_footprint_check", "pqp_footprint_check_device",
 ]
 
 _lib = None
@@ -178,6 +186,13 @@ def load_library(path=None, with_torch=None):
         getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     for name in ("pqp_distance_layer", "pqp_distance_layer_device"):
         getattr(lib, name).argtypes = [vp, C.c_int, C.POINTER(PqpGridGeometry), vp, vp]
+    lib.pqp_car_default_geometry.argtypes = [C.POINTER(PqpCarGeometry)]
+    lib.pqp_car_default_geometry.restype = None
+    lib.pqp_car_circles.argtypes = [C.POINTER(PqpCarGeometry), vp]
+    lib.pqp_footprint_check_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpCarGeometry),
+                                               C.c_int, vp, vp, vp]
+    lib.pqp_footprint_check.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpCarGeometry),
+                                        C.c_int, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -200,6 +215,27 @@ def production_params(lib=None, **over):
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def car_default_geometry(lib=None, **over):
+    """pqp_car_default_geometry: the reference's flags (car_width 2.0, rear_length -1.0, front_length 3.9), with `over` applied."""
+    lib = lib or load_library()
+    c = PqpCarGeometry()
+    lib.pqp_car_default_geometry(C.byref(c))
+    for k, v in over.items():
+        setattr(c, k, v)
+    return c
+
+
+def car_circles(car=None, lib=None):
+    """pqp_car_circles (pure host): [7][3] x, y, r in the vehicle frame of rr, rl, fr, fl, fm, rm and the bounding circle."""
+    lib = lib or load_library()
+    car = car if car is not None else car_default_geometry(lib)
+    out = np.zeros((7, 3))
+    rc = lib.pqp_car_circles(C.byref(car), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise PqpError(f"pqp error {rc}: {lib.pqp_last_error().decode()}")
+    return out
 
 
 def _ptr(a):
@@ -373,27 +409,34 @@ class Handle:
             setattr(c, k, v)
         return c
 
-    def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None):
+    def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
-        smoother QPs run on (None: this one).  Returns dict(out [B][n_max][7], n_out, status, stage, iters)."""
+        smoother QPs run on (None: this one).  Returns dict(out [B][n_max][7], n_out, status, stage, iters).
+        check_footprint: pqp_footprint_check_device right behind the chain on the same stream, on its `out` (stride 7) and `n_out` and the same
+        layers (car: PqpCarGeometry, None: the reference's; footprint_mode: pqp_footprint_mode); adds free [B][n_max], first_collision [B]
+        and margin [B][n_max] to the dict."""
         dist = np.asarray(dist, dtype=np.float32)
         if dist.ndim == 2:
             dist = dist[None]
-        return self._chain(points, n_points, start, target, np.transpose(dist, (0, 2, 1)), np.float32, None, geom, map_of, smoother, cfg, start_k)
+        return self._chain(points, n_points, start, target, np.transpose(dist, (0, 2, 1)), np.float32, None, geom, map_of, smoother, cfg, start_k,
+                           (car, footprint_mode) if check_footprint else None)
 
-    def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None):
+    def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
+                              check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
-        no host round trip between the two.  Returns what optimize_path returns."""
+        no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
                                                                                       C.c_void_p(d_dist.data_ptr())))
-        return self._chain(points, n_points, start, target, np.transpose(grid, (0, 2, 1)), np.uint8, build, geom, map_of, smoother, cfg, start_k)
+        return self._chain(points, n_points, start, target, np.transpose(grid, (0, 2, 1)), np.uint8, build, geom, map_of, smoother, cfg, start_k,
+                           (car, footprint_mode) if check_footprint else None)
 
-    def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k):
+    def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
-        them on the handle's stream (None: they are the layer)"""
+        them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -412,10 +455,21 @@ class Handle:
         self._check(self.lib.pqp_optimize_path_device(self._h, smoother._h if smoother is not None else None, C.byref(cfg), B, p_max, p(d_pts), p(d_np),
                                                       p(d_st), p(d_tg), p(d_dist), p(d_map), C.byref(geom), p(d_k), p(out), p(ints[0]), p(ints[1]),
                                                       p(ints[2]), p(ints[3])))
+        if footprint is not None:           # behind the chain on the handle's stream: reads out / n_out where they are
+            car, mode = footprint
+            car = car if car is not None else car_default_geometry(self.lib)
+            free = torch.zeros((B, cfg.n_max), dtype=torch.uint8, device=dev)
+            first = torch.zeros(B, dtype=torch.int32, device=dev)
+            margin = torch.zeros((B, cfg.n_max), dtype=torch.float64, device=dev)
+            self._check(self.lib.pqp_footprint_check_device(self._h, B, cfg.n_max, 7, p(out), p(ints[0]), p(d_dist), p(d_map), C.byref(geom),
+                                                            C.byref(car), int(mode), p(free), p(first), p(margin)))
         self.sync()
         if smoother is not None:
             smoother.sync()
-        return dict(out=out.cpu().numpy(), n_out=ints[0].cpu().numpy(), status=ints[1].cpu().numpy(), stage=ints[2].cpu().numpy(), iters=ints[3].cpu().numpy())
+        res = dict(out=out.cpu().numpy(), n_out=ints[0].cpu().numpy(), status=ints[1].cpu().numpy(), stage=ints[2].cpu().numpy(), iters=ints[3].cpu().numpy())
+        if footprint is not None:
+            res.update(free=free.cpu().numpy(), first_collision=first.cpu().numpy(), margin=margin.cpu().numpy())
+        return res
 
     def distance_layer(self, grid, geom):
         """pqp_distance_layer (host arrays): grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, in the orientation corridor_bounds takes
@@ -427,6 +481,30 @@ class Handle:
         self._check(self.lib.pqp_distance_layer(self._h, cm.shape[0], C.byref(geom), _ptr(cm), _ptr(out)))
         out = np.transpose(out, (0, 2, 1))
         return out[0] if two_d else out
+
+    def footprint_check(self, states, n_of, dist, geom, map_of=None, car=None, mode=FOOTPRINT_CIRCLES, margin=False):
+        """pqp_footprint_check (host arrays): states [B][n][stride >= 3] (x, y, heading first; the chain's `out` as it is), n_of [B] or None,
+        dist [n_maps][rows][cols] float32 (converted to the ABI's column-major order here), geom = PqpGridGeometry, car = PqpCarGeometry
+        (None: the reference's), mode = FOOTPRINT_CIRCLES / FOOTPRINT_BOUNDING_FIRST.  Returns dict(free [B][n] uint8, first_collision [B]
+        [, margin [B][n]])."""
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        dist = np.asarray(dist, dtype=np.float32)
+        if dist.ndim == 2:
+            dist = dist[None]
+        dist_cm = np.ascontiguousarray(np.transpose(dist, (0, 2, 1)))        # [n_maps][cols][rows]
+        B, n, stride = states.shape
+        no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
+        mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
+        car = car if car is not None else car_default_geometry(self.lib)
+        free = np.zeros((B, n), dtype=np.uint8)
+        first = np.zeros(B, dtype=np.int32)
+        mg = np.zeros((B, n)) if margin else None
+        self._check(self.lib.pqp_footprint_check(self._h, B, n, stride, _ptr(states), _ptr(no), _ptr(dist_cm), dist.shape[0], _ptr(mo), C.byref(geom),
+                                                 C.byref(car), int(mode), _ptr(free), _ptr(first), _ptr(mg)))
+        res = dict(free=free, first_collision=first)
+        if margin:
+            res["margin"] = mg
+        return res
 
     def corridor_params(self, **over):
         p = PqpCorridorParams()

@@ -1,0 +1,102 @@
+// pqp_footprint_kernels.inc — included by pqp_kernels.hip after pqp_corridor_kernels.inc.  Vehicle footprints of planned states against
+// the obstacle distance layer (pqp_footprint_check):
+//   CollisionChecker::isSingleStateCollisionFree          src/tools/collision_checker.cpp:17-39
+//   CollisionChecker::isSingleStateCollisionFreeImproved  src/tools/collision_checker.cpp:41-58
+//   CarGeometry::getCircles / getBoundingCircle           src/tools/car_geometry.cpp:59-72 (the circles themselves: pqp_car_circles, host)
+//   local2Global                                          src/tools/tools.cpp:50-55
+//   Map::getObstacleDistance / isInside                   src/tools/Map.cpp:16-26   (obstacle_distance of pqp_corridor_kernels.inc)
+// One workgroup of 256 lanes per scenario, one state per lane, striding over the scenario's states.  A state takes one sincos and six
+// map samples; the six samples' 24 cell loads are independent of each other, so they are in flight together (the layer, <= a few MB,
+// sits in L2).  first_collision: one ballot per wavefront and stride step, then the least of the four wavefronts' indices through LDS -
+// no atomics, the same answer every run, any n.
+
+namespace pqp {
+
+constexpr int kFootprintThreads = 256;
+
+struct FootprintArgs {
+    int batch, n, stride;
+    const double* states;            // [batch][n][stride]  x, y, heading at offsets 0, 1, 2
+    const int32_t* n_of;             // [batch] states per scenario (<= n), or nullptr: all have n
+    const float* dist;               // [n_maps][cols][rows]  as for CorridorArgs
+    const int32_t* map_of;           // [batch] or nullptr: map 0
+    pqp_grid_geometry g;
+    double cx[7], cy[7], cr[7];      // vehicle frame: rr, rl, fr, fl, fm, rm, then the bounding circle (pqp_car_circles)
+    uint8_t* free_out;               // [batch][n]
+    int32_t* first_collision;        // [batch]
+    double* margin;                  // [batch][n] or nullptr
+};
+
+// GridMap::isInside (checkIfPositionWithinMap), the test obstacle_distance opens with
+__device__ __forceinline__ bool map_is_inside(const pqp_grid_geometry& g, double px, double py) {
+#pragma clang fp contract(off)
+    const double tx = -(px - g.pos_x - 0.5 * g.length_x), ty = -(py - g.pos_y - 0.5 * g.length_y);
+    return tx >= 0.0 && ty >= 0.0 && tx < g.length_x && ty < g.length_y;
+}
+
+// MODE: pqp_footprint_mode.  In BOUNDING_FIRST mode the six samples are taken only where the bounding circle is not clear (or where the
+// margin is asked for): lanes of one wavefront diverge there.
+template <int MODE>
+__global__ void __launch_bounds__(kFootprintThreads) footprint_check_kernel(const FootprintArgs a) {
+#pragma clang fp contract(off)
+    __shared__ int wave_first[kFootprintThreads / 64];
+    const int b = blockIdx.x, wave = threadIdx.x >> 6;
+    const int nb = a.n_of ? min(max(a.n_of[b], 0), a.n) : a.n;
+    const float* __restrict__ dist = a.dist + (size_t)(a.map_of ? a.map_of[b] : 0) * a.g.rows * a.g.cols;
+    const double* st = a.states + (size_t)b * a.n * a.stride;
+    int first = INT_MAX;                                                     // wave-uniform: the wavefront's first colliding index
+    for (int base = 0; base < a.n; base += kFootprintThreads) {
+        const int i = base + (int)threadIdx.x;
+        bool collide = false;
+        double mg = 0.0;
+        if (i < nb) {
+            const double x = st[(size_t)i * a.stride], y = st[(size_t)i * a.stride + 1], heading = st[(size_t)i * a.stride + 2];
+            double sh, ch;
+            sincos(heading, &sh, &ch);
+            // local2Global(current, circle): x cos - y sin + ref.x, x sin + y cos + ref.y  (tools.cpp:51-52)
+            auto gx = [&](int k) { return a.cx[k] * ch - a.cy[k] * sh + x; };
+            auto gy = [&](int k) { return a.cx[k] * sh + a.cy[k] * ch + y; };
+            bool bound_in = true, exact = true;
+            if (MODE == PQP_FOOTPRINT_BOUNDING_FIRST) {
+                const double bx = gx(6), by = gy(6);
+                bound_in = map_is_inside(a.g, bx, by);
+                exact = bound_in && obstacle_distance(dist, a.g, bx, by) < a.cr[6];          // :49-53: the big circle is not clear
+            }
+            bool six = false;
+            if (exact || a.margin) {
+                double d[6];
+                bool in[6];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    const double px = gx(k), py = gy(k);
+                    in[k] = map_is_inside(a.g, px, py);
+                    d[k] = obstacle_distance(dist, a.g, px, py);                             // Map::getObstacleDistance: 0 outside
+                }
+                mg = d[0] - a.cr[0];
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    six = six || !in[k] || d[k] < a.cr[k];                                    // :28-35
+                    const double v = d[k] - a.cr[k];
+                    mg = v < mg ? v : mg;
+                }
+            }
+            collide = MODE == PQP_FOOTPRINT_BOUNDING_FIRST ? (!bound_in || (exact && six)) : six;
+        }
+        if (i < a.n) {
+            a.free_out[(size_t)b * a.n + i] = (i < nb && !collide) ? 1 : 0;
+            if (a.margin) a.margin[(size_t)b * a.n + i] = mg;
+        }
+        const uint64_t hit = __ballot(collide);
+        if (hit && first == INT_MAX) first = base + wave * 64 + __builtin_ctzll(hit);
+    }
+    if ((threadIdx.x & 63) == 0) wave_first[wave] = first;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int f = nb;
+#pragma unroll
+        for (int w = 0; w < kFootprintThreads / 64; ++w) f = min(f, wave_first[w]);
+        a.first_collision[b] = f;
+    }
+}
+
+}  // namespace pqp

@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -247,6 +249,7 @@ __global__ void constrain_angle_kernel(int count, const double* __restrict__ in,
 #include "pqp_smoother_kernels.inc"
 #include "pqp_corridor_kernels.inc"
 #include "pqp_distance_kernels.inc"
+#include "pqp_footprint_kernels.inc"
 
 // =========================================================================================================
 // C ABI
@@ -1373,6 +1376,99 @@ int pqp_distance_layer(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom,
     PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, grid, cells, hipMemcpyHostToDevice, h->stream));
     if ((rc = pqp_distance_layer_device(h, n_maps, geom, h->c_buf[0].as<uint8_t>(), h->c_buf[1].as<float>()))) return rc;
     PQP_HIP(hipMemcpyAsync(dist, h->c_buf[1].p, cells * 4, hipMemcpyDeviceToHost, h->stream));
+    PQP_HIP(hipStreamSynchronize(h->stream));
+    return PQP_OK;
+}
+
+// ---- vehicle footprints against the distance layer (collision_checker.cpp:17-58, car_geometry.cpp:38-72) ----------------------------
+void pqp_car_default_geometry(pqp_car_geometry* c) {
+    if (!c) return;
+    c->width = 2.0;                 // planning_flags.cpp:10
+    c->rear_length = -1.0;          // :18
+    c->front_length = 3.9;          // :20
+}
+
+static bool car_ok(const pqp_car_geometry* c) {
+    return c && std::isfinite(c->width) && std::isfinite(c->rear_length) && std::isfinite(c->front_length);
+}
+
+int pqp_car_circles(const pqp_car_geometry* c, double* circles) {
+    if (!car_ok(c) || !circles) return fail(PQP_ERR_INVALID, "pqp_car_circles: bad argument (a finite car geometry)");
+    // CollisionChecker's car_(FLAGS_car_width, fabs(FLAGS_rear_length), FLAGS_front_length) -> CarGeometry(width, back_length, front_length)
+    const double width = c->width, back_length = std::fabs(c->rear_length), front_length = c->front_length;
+    const double length = front_length + back_length;
+    const double fl_x = front_length, fl_y = width / 2.0, fr_x = front_length, fr_y = -width / 2.0;
+    const double rl_x = -back_length, rl_y = width / 2.0, rr_x = -back_length, rr_y = -width / 2.0;
+    // CarGeometry::setCircles, car_geometry.cpp:38-57, term by term
+    const double bounding_x = (front_length - back_length) / 2.0;
+    const double bounding_r = std::sqrt(std::pow(length / 2, 2) + std::pow(width / 2, 2));
+    const double small_circle_shift = width / 4.0;
+    const double small_circle_radius = std::sqrt(2 * std::pow(small_circle_shift, 2));
+    const double large_circle_radius = std::sqrt(std::pow(width, 2) + std::pow((length - width) / 2.0, 2)) / 2;
+    const double v[7][3] = {{rr_x + small_circle_shift, rr_y + small_circle_shift, small_circle_radius},
+                            {rl_x + small_circle_shift, rl_y - small_circle_shift, small_circle_radius},
+                            {fr_x - small_circle_shift, fr_y + small_circle_shift, small_circle_radius},
+                            {fl_x - small_circle_shift, fl_y - small_circle_shift, small_circle_radius},
+                            {bounding_x + (length - width) / 4, 0, large_circle_radius},
+                            {bounding_x - (length - width) / 4, 0, large_circle_radius},
+                            {bounding_x, 0, bounding_r}};
+    std::memcpy(circles, v, sizeof(v));
+    return PQP_OK;
+}
+
+int pqp_footprint_check_device(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist,
+                               const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
+                               int32_t* first_collision, double* margin) {
+    if (!h || !states || !dist || !free_out || !first_collision || batch < 1 || n < 1 || n > (1 << 30) || stride < 3 || !geometry_ok(geom) ||
+        !car_ok(car) || (mode != PQP_FOOTPRINT_CIRCLES && mode != PQP_FOOTPRINT_BOUNDING_FIRST))
+        return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument (stride >= 3; a finite car geometry; mode CIRCLES or BOUNDING_FIRST; "
+                                     "a map layer of 2 x 2 to 2^30 cells)");
+    PQP_HIP(hipSetDevice(h->device));
+    double circles[7][3];
+    int rc;
+    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
+    pqp::FootprintArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.states = states; a.n_of = n_of; a.dist = dist; a.map_of = map_of; a.g = *geom;
+    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
+    a.free_out = free_out; a.first_collision = first_collision; a.margin = margin;
+    h->next_event_pair();
+    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
+    if (mode == PQP_FOOTPRINT_CIRCLES)
+        hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_CIRCLES>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_BOUNDING_FIRST>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
+    PQP_HIP(hipGetLastError());
+    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    return PQP_OK;
+}
+
+int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist, int n_maps,
+                        const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
+                        int32_t* first_collision, double* margin) {
+    if (!h || !states || !dist || !free_out || !first_collision || batch < 1 || n < 1 || n > (1 << 30) || stride < 3 || n_maps < 1 ||
+        !geometry_ok(geom) || !car_ok(car) || (mode != PQP_FOOTPRINT_CIRCLES && mode != PQP_FOOTPRINT_BOUNDING_FIRST))
+        return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument");
+    if (map_of)
+        for (int b = 0; b < batch; ++b)
+            if (map_of[b] < 0 || map_of[b] >= n_maps) return fail(PQP_ERR_INVALID, "pqp_footprint_check: map_of outside [0, n_maps)");
+    PQP_HIP(hipSetDevice(h->device));
+    const size_t b_st = (size_t)batch * n * stride * 8, b_of = (size_t)batch * 4, b_map = (size_t)n_maps * geom->rows * geom->cols * 4;
+    const size_t b_free = (size_t)batch * n, b_first = (size_t)batch * 4, b_mg = (size_t)batch * n * 8;
+    const size_t sizes[7] = {b_st, b_of, b_map, b_of, b_free, b_first, b_mg};
+    int rc;
+    for (int k = 0; k < 7; ++k) if ((rc = h->c_buf[k].ensure(sizes[k]))) return rc;
+    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, states, b_st, hipMemcpyHostToDevice, h->stream));
+    if (n_of) PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, n_of, b_of, hipMemcpyHostToDevice, h->stream));
+    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, dist, b_map, hipMemcpyHostToDevice, h->stream));
+    if (map_of) PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, map_of, b_of, hipMemcpyHostToDevice, h->stream));
+    if ((rc = pqp_footprint_check_device(h, batch, n, stride, h->c_buf[0].as<double>(), n_of ? h->c_buf[1].as<int32_t>() : nullptr,
+                                         h->c_buf[2].as<float>(), map_of ? h->c_buf[3].as<int32_t>() : nullptr, geom, car, mode,
+                                         h->c_buf[4].as<uint8_t>(), h->c_buf[5].as<int32_t>(), margin ? h->c_buf[6].as<double>() : nullptr)))
+        return rc;
+    PQP_HIP(hipMemcpyAsync(free_out, h->c_buf[4].p, b_free, hipMemcpyDeviceToHost, h->stream));
+    PQP_HIP(hipMemcpyAsync(first_collision, h->c_buf[5].p, b_first, hipMemcpyDeviceToHost, h->stream));
+    if (margin) PQP_HIP(hipMemcpyAsync(margin, h->c_buf[6].p, b_mg, hipMemcpyDeviceToHost, h->stream));
     PQP_HIP(hipStreamSynchronize(h->stream));
     return PQP_OK;
 }
