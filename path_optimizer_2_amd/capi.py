@@ -338,6 +338,14 @@ def _occupancy(grid, who):
     return grid[None] if grid.ndim == 2 else grid
 
 
+def _column_major(maps, dtype):
+    """one map [rows][cols] or many [n_maps][rows][cols] -> the ABI's column-major [n_maps][cols][rows], contiguous, as dtype"""
+    maps = np.asarray(maps, dtype=dtype)
+    if maps.ndim == 2:
+        maps = maps[None]
+    return np.ascontiguousarray(np.transpose(maps, (0, 2, 1)))
+
+
 class Handle:
     """Thin RAII wrapper over pqp_handle (one per GPU)."""
 
@@ -417,10 +425,7 @@ class Handle:
         check_footprint: pqp_footprint_check_device right behind the chain on the same stream, on its `out` (stride 7) and `n_out` and the same
         layers (car: PqpCarGeometry, None: the reference's; footprint_mode: pqp_footprint_mode); adds free [B][n_max], first_collision [B]
         and margin [B][n_max] to the dict."""
-        dist = np.asarray(dist, dtype=np.float32)
-        if dist.ndim == 2:
-            dist = dist[None]
-        return self._chain(points, n_points, start, target, np.transpose(dist, (0, 2, 1)), np.float32, None, geom, map_of, smoother, cfg, start_k,
+        return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None)
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
@@ -431,7 +436,7 @@ class Handle:
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
                                                                                       C.c_void_p(d_dist.data_ptr())))
-        return self._chain(points, n_points, start, target, np.transpose(grid, (0, 2, 1)), np.uint8, build, geom, map_of, smoother, cfg, start_k,
+        return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None)
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None):
@@ -475,8 +480,7 @@ class Handle:
         """pqp_distance_layer (host arrays): grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, in the orientation corridor_bounds takes
         its layer -> the float32 distance layer [n_maps][rows][cols] (2-D in, 2-D out)."""
         two_d = np.ndim(grid) == 2
-        grid = _occupancy(grid, "distance_layer")
-        cm = np.ascontiguousarray(np.transpose(grid, (0, 2, 1)))          # the ABI's column-major [n_maps][cols][rows]
+        cm = _column_major(_occupancy(grid, "distance_layer"), np.uint8)
         out = np.empty(cm.shape, dtype=np.float32)
         self._check(self.lib.pqp_distance_layer(self._h, cm.shape[0], C.byref(geom), _ptr(cm), _ptr(out)))
         out = np.transpose(out, (0, 2, 1))
@@ -488,10 +492,7 @@ class Handle:
         (None: the reference's), mode = FOOTPRINT_CIRCLES / FOOTPRINT_BOUNDING_FIRST.  Returns dict(free [B][n] uint8, first_collision [B]
         [, margin [B][n]])."""
         states = np.ascontiguousarray(states, dtype=np.float64)
-        dist = np.asarray(dist, dtype=np.float32)
-        if dist.ndim == 2:
-            dist = dist[None]
-        dist_cm = np.ascontiguousarray(np.transpose(dist, (0, 2, 1)))        # [n_maps][cols][rows]
+        dist_cm = _column_major(dist, np.float32)
         B, n, stride = states.shape
         no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
         mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
@@ -499,7 +500,7 @@ class Handle:
         free = np.zeros((B, n), dtype=np.uint8)
         first = np.zeros(B, dtype=np.int32)
         mg = np.zeros((B, n)) if margin else None
-        self._check(self.lib.pqp_footprint_check(self._h, B, n, stride, _ptr(states), _ptr(no), _ptr(dist_cm), dist.shape[0], _ptr(mo), C.byref(geom),
+        self._check(self.lib.pqp_footprint_check(self._h, B, n, stride, _ptr(states), _ptr(no), _ptr(dist_cm), dist_cm.shape[0], _ptr(mo), C.byref(geom),
                                                  C.byref(car), int(mode), _ptr(free), _ptr(first), _ptr(mg)))
         res = dict(free=free, first_collision=first)
         if margin:
@@ -517,10 +518,7 @@ class Handle:
         """pqp_dp_corridor (host arrays) -> (layers_s [B][max_layers], lb, ub, count [B], vehicle_l [B])."""
         spline = np.ascontiguousarray(spline, dtype=np.float64); spline_ext = np.ascontiguousarray(spline_ext, dtype=np.float64)
         length = np.ascontiguousarray(length, dtype=np.float64); start = np.ascontiguousarray(start, dtype=np.float64)
-        dist = np.asarray(dist, dtype=np.float32)
-        if dist.ndim == 2:
-            dist = dist[None]
-        dist_cm = np.ascontiguousarray(np.transpose(dist, (0, 2, 1)))
+        dist_cm = _column_major(dist, np.float32)
         B, m = spline.shape[0], spline.shape[2]
         ls = np.zeros((B, max_layers)); lb = np.zeros((B, max_layers)); ub = np.zeros((B, max_layers))
         count = np.zeros(B, dtype=np.int32); vl = np.zeros(B)
@@ -529,7 +527,7 @@ class Handle:
             prm = PqpDpParams()
             self.lib.pqp_dp_default_params(C.byref(prm))
         self._check(self.lib.pqp_dp_corridor(self._h, B, m, max_layers, _ptr(spline), _ptr(spline_ext), _ptr(length), _ptr(start), _ptr(dist_cm),
-                                             dist.shape[0], _ptr(mo), C.byref(geom), C.byref(prm), _ptr(ls), _ptr(lb), _ptr(ub), _ptr(count), _ptr(vl)))
+                                             dist_cm.shape[0], _ptr(mo), C.byref(geom), C.byref(prm), _ptr(ls), _ptr(lb), _ptr(ub), _ptr(count), _ptr(vl)))
         return ls, lb, ub, count, vl
 
     def spline_fit(self, s, x, y):
@@ -605,10 +603,7 @@ class Handle:
         ref = np.ascontiguousarray(ref, dtype=np.float64)
         spline = np.ascontiguousarray(spline, dtype=np.float64)
         spline_ext = np.ascontiguousarray(spline_ext, dtype=np.float64)
-        dist = np.asarray(dist, dtype=np.float32)
-        if dist.ndim == 2:
-            dist = dist[None]
-        dist_cm = np.ascontiguousarray(np.transpose(dist, (0, 2, 1)))        # [n_maps][cols][rows]
+        dist_cm = _column_major(dist, np.float32)
         B, n = ref.shape[0], ref.shape[1]
         m = spline.shape[2]
         bounds = np.zeros((B, n, 6))
@@ -616,7 +611,7 @@ class Handle:
         mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
         prm = prm or self.corridor_params()
         no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
-        self._check(self.lib.pqp_corridor_bounds(self._h, B, n, m, _ptr(ref), _ptr(no), _ptr(spline), _ptr(spline_ext), _ptr(dist_cm), dist.shape[0],
+        self._check(self.lib.pqp_corridor_bounds(self._h, B, n, m, _ptr(ref), _ptr(no), _ptr(spline), _ptr(spline_ext), _ptr(dist_cm), dist_cm.shape[0],
                                                  _ptr(mo), C.byref(geom), C.byref(prm), _ptr(bounds), _ptr(n_valid)))
         return bounds, n_valid
 

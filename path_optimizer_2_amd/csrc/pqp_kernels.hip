@@ -274,6 +274,10 @@ std::atomic<unsigned long long> g_alloc_generation{0};
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     int ensure(size_t need) {
         if (need <= bytes) return PQP_OK;
         g_alloc_generation.fetch_add(1, std::memory_order_relaxed);
@@ -289,9 +293,18 @@ struct DevBuf {
         PQP_HIP(hipStreamSynchronize(nullptr));
         return PQP_OK;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// one CU's LDS on gfx950: the most dynamic LDS a workgroup can have
+constexpr size_t kLdsPerCu = 160 * 1024;
+
+// `bytes` of dynamic LDS for kernel `fn`: PQP_ERR_CAPACITY (message `who`) beyond one CU's LDS, the opt-in beyond the 48 KiB any kernel may use
+int lds_opt_in(const void* fn, size_t bytes, const char* who) {
+    if (bytes > kLdsPerCu) return fail(PQP_ERR_CAPACITY, who);
+    if (bytes > 48 * 1024) PQP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return PQP_OK;
+}
 }  // namespace
 
 struct pqp_handle {
@@ -299,16 +312,27 @@ struct pqp_handle {
     pqp_params prm;
     hipStream_t stream = nullptr;
     // HIP events around the dominant kernel of every call, on the stream it is launched on: a ring of the last kEvRing launches,
-    // read back (after the work is done) by pqp_last_kernel_ms / pqp_kernel_ms_history without putting a sync between launches
-    static constexpr int kEvRing = 256;
-    hipEvent_t evs0[kEvRing] = {}, evs1[kEvRing] = {};
+    // read back (after the work is done) by pqp_last_kernel_ms / pqp_kernel_ms_history without putting a sync between launches.
+    // One slot more than the history: the one launch_timed records into, which a launch that fails may leave half recorded.
+    static constexpr int kEvRing = 256, kEvSlots = kEvRing + 1;
+    hipEvent_t evs0[kEvSlots] = {}, evs1[kEvSlots] = {};
     long long ev_count = 0;          // launches recorded so far
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;      // the pair of the launch being recorded
-    bool timed = false;
+    bool timed = false;              // the last of them is what pqp_last_kernel_ms reports
     static constexpr int kMarks = 8;
     static constexpr int kChainMarks = 2;      // + two events of pqp_optimize_path_device's own
     hipEvent_t marks[kMarks + kChainMarks] = {};   // pqp_mark / pqp_wait_mark: ordering between the streams of two handles
-    void next_event_pair() { if (capturing) return; ev0 = evs0[ev_count % kEvRing]; ev1 = evs1[ev_count % kEvRing]; ev_count += 1; }
+    // the launches of one call between the next pair of the ring's events, which count only once the launches were accepted: a call that
+    // fails leaves the timing of the previous one.  No events inside a graph capture.
+    template <class F> int launch_timed(F&& launch) {
+        if (capturing) return launch();
+        const int slot = (int)(ev_count % kEvSlots);
+        PQP_HIP(hipEventRecord(evs0[slot], stream));
+        if (const int rc = launch()) return rc;
+        PQP_HIP(hipEventRecord(evs1[slot], stream));
+        ev_count += 1;
+        timed = true;
+        return PQP_OK;
+    }
     // PQP_OPT_CHAIN_GRAPH: pqp_optimize_path_device captured as hipGraphs (pqp_chain.inc).  capturing: the handle's stream is in capture
     // mode - no timing events, the path solve resets its ticket counter inside the graph
     bool capturing = false;
@@ -336,12 +360,56 @@ struct pqp_handle {
     int stream_order_batch = 0, stream_order_n = 0;    // shape the map being read was built for (0: none)
     int num_cu = 0;
     int blocks_per_cu[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // occupancy of the solve kernel variants [log2(nw)][cert]
-    DevBuf s_ref, s_lin, s_bounds, s_scal;      // staging for the host-pointer entry points
-    DevBuf s_out, s_status, s_iters, s_info, s_a, s_p, s_l, s_u, s_idx;
-    // smoother QPs: banded problem data + shared sparsity (cached per type and size) + staging
-    DevBuf b_pband, b_q, b_aval, b_lo, b_up, b_x, b_y, b_acol, b_trow, b_tslot, b_in[5], b_out[3], c_buf[12];
+    static constexpr int kStage = 12;
+    DevBuf stage[kStage];                       // device copies of the arrays of a host-pointer entry point (Staging), in argument order
+    // smoother QPs: banded problem data + shared sparsity (cached per type and size)
+    DevBuf b_pband, b_q, b_aval, b_lo, b_up, b_x, b_y, b_acol, b_trow, b_tslot;
     int b_struct_type = -1, b_struct_n = -1;
 };
+
+namespace {
+int hip_ok(hipError_t e, const char* what) { return e == hipSuccess ? PQP_OK : fail(PQP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+// The host-pointer form of an entry point: device copies of its arrays from the handle's pool, in argument order.  in() copies a host array in
+// (nullptr stays nullptr); out() hands out a device array, first set to the byte `fill` if that is not negative, which run() copies back when
+// the host pointer is not null.  The first failure is kept and every later step skipped.  What was enqueued reads or writes the caller's
+// memory, so no return leaves it queued: run() synchronises after the copies back, the destructor on any other return.
+class Staging {
+  public:
+    explicit Staging(pqp_handle* h) : h_(h) { rc_ = hip_ok(hipSetDevice(h->device), "hipSetDevice"); }
+    ~Staging() { if (pending_) (void)hipStreamSynchronize(h_->stream); }
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    template <class T> T* in(const T* host, size_t count) { return host ? static_cast<T*>(take(count * sizeof(T), host, nullptr, -1)) : nullptr; }
+    template <class T> T* out(T* host, size_t count, int fill = -1) { return static_cast<T*>(take(count * sizeof(T), nullptr, host, fill)); }
+    // the device form on the staged arrays, then the copies back
+    template <class F> int run(F&& device_form) {
+        if (rc_ || (rc_ = device_form())) return rc_;
+        for (int k = 0; k < n_back_ && !rc_; ++k)
+            rc_ = hip_ok(hipMemcpyAsync(back_[k].host, back_[k].dev, back_[k].bytes, hipMemcpyDeviceToHost, h_->stream), "hipMemcpyAsync(device to host)");
+        if (!rc_ && !(rc_ = hip_ok(hipStreamSynchronize(h_->stream), "hipStreamSynchronize"))) pending_ = false;
+        return rc_;
+    }
+
+  private:
+    void* take(size_t bytes, const void* src, void* host_out, int fill) {
+        if (rc_) return nullptr;
+        if (used_ == pqp_handle::kStage) { rc_ = fail(PQP_ERR_INVALID, "staging: more arrays than the handle's pool holds"); return nullptr; }
+        DevBuf& b = h_->stage[used_++];
+        if ((rc_ = b.ensure(bytes))) return nullptr;
+        pending_ = true;
+        if (src) rc_ = hip_ok(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h_->stream), "hipMemcpyAsync(host to device)");
+        else if (fill >= 0) rc_ = hip_ok(hipMemsetAsync(b.p, fill, bytes, h_->stream), "hipMemsetAsync");
+        if (host_out) back_[n_back_++] = {host_out, b.p, bytes};
+        return rc_ ? nullptr : b.p;
+    }
+    struct Back { void* host; const void* dev; size_t bytes; };
+    pqp_handle* h_;
+    int rc_ = PQP_OK, used_ = 0, n_back_ = 0;
+    bool pending_ = false;
+    Back back_[pqp_handle::kStage];
+};
+}  // namespace
 
 extern "C" {
 
@@ -367,7 +435,7 @@ int pqp_create(pqp_handle** out, const pqp_params* params, int device, int max_b
     auto build = [&]() -> int {
         PQP_HIP(hipDeviceGetAttribute(&h->num_cu, hipDeviceAttributeMultiprocessorCount, device));
         PQP_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        for (int k = 0; k < pqp_handle::kEvRing; ++k) { PQP_HIP(hipEventCreate(&h->evs0[k])); PQP_HIP(hipEventCreate(&h->evs1[k])); }
+        for (int k = 0; k < pqp_handle::kEvSlots; ++k) { PQP_HIP(hipEventCreate(&h->evs0[k])); PQP_HIP(hipEventCreate(&h->evs1[k])); }
         for (int k = 0; k < pqp_handle::kMarks + pqp_handle::kChainMarks; ++k) PQP_HIP(hipEventCreateWithFlags(&h->marks[k], hipEventDisableTiming));
         int rc;
         if ((rc = h->ticket.ensure(8)) || (rc = h->cost_hist.ensure(2 * pqp::kCostBins * 4))) return rc;
@@ -394,17 +462,10 @@ int pqp_destroy(pqp_handle* h) {
     g_alloc_generation.fetch_add(1, std::memory_order_relaxed);
     for (auto& g : h->chain_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
     h->chain_graphs.clear();
-    for (DevBuf* b : {&h->sm_act[0], &h->sm_act[1], &h->stream_ws, &h->stream_key, &h->stream_hist, &h->stream_order, &h->chain_d, &h->chain_i, &h->wscale, &h->ticket, &h->cost_key, &h->cost_hist, &h->order, &h->wx, &h->wy, &h->wye, &h->wrho, &h->wsave, &h->s_ref, &h->s_lin, &h->s_bounds, &h->s_scal, &h->s_out,
-                      &h->s_status, &h->s_iters, &h->s_info, &h->s_a, &h->s_p, &h->s_l, &h->s_u, &h->s_idx, &h->b_pband, &h->b_q, &h->b_aval,
-                      &h->b_lo, &h->b_up, &h->b_x, &h->b_y, &h->b_acol, &h->b_trow, &h->b_tslot, &h->b_in[0], &h->b_in[1], &h->b_in[2],
-                      &h->b_in[3], &h->b_in[4], &h->b_out[0], &h->b_out[1], &h->b_out[2], &h->c_buf[0], &h->c_buf[1], &h->c_buf[2],
-                      &h->c_buf[3], &h->c_buf[4], &h->c_buf[5], &h->c_buf[6], &h->c_buf[7], &h->c_buf[8], &h->c_buf[9], &h->c_buf[10],
-                      &h->c_buf[11]})
-        b->release();
-    for (int k = 0; k < pqp_handle::kEvRing; ++k) { if (h->evs0[k]) (void)hipEventDestroy(h->evs0[k]); if (h->evs1[k]) (void)hipEventDestroy(h->evs1[k]); }
+    for (int k = 0; k < pqp_handle::kEvSlots; ++k) { if (h->evs0[k]) (void)hipEventDestroy(h->evs0[k]); if (h->evs1[k]) (void)hipEventDestroy(h->evs1[k]); }
     for (int k = 0; k < pqp_handle::kMarks + pqp_handle::kChainMarks; ++k) if (h->marks[k]) (void)hipEventDestroy(h->marks[k]);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;           // (its DevBufs free themselves)
     return PQP_OK;
 }
 
@@ -488,73 +549,52 @@ int pqp_path_sizes(const pqp_params* params, int n, const double* s, pqp_sizes* 
 int pqp_path_pattern(pqp_handle* h, int n, int precise, int32_t* rows, int32_t* colptr, int32_t* pcols) {
     if (!h || !rows || !colptr || !pcols || n < 2 || precise < 0 || precise > n)
         return fail(PQP_ERR_INVALID, "pqp_path_pattern: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
     pqp::RefIndex R{n, precise};
-    const size_t total = (size_t)R.nnz_a() + R.vars() + 1 + R.nnz_p();
-    int rc;
-    if ((rc = h->s_idx.ensure(total * 4))) return rc;
-    int32_t* d_rows = h->s_idx.as<int32_t>();
-    int32_t* d_colptr = d_rows + R.nnz_a();
-    int32_t* d_pcols = d_colptr + R.vars() + 1;
-    PQP_HIP(hipMemsetAsync(d_rows, 0xff, total * 4, h->stream));
-    hipLaunchKernelGGL(pqp::path_pattern_kernel, dim3((n + 127) / 128), dim3(128), 0, h->stream, R, d_rows, d_colptr, d_pcols);
-    PQP_HIP(hipGetLastError());
-    PQP_HIP(hipMemcpyAsync(rows, d_rows, (size_t)R.nnz_a() * 4, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(colptr, d_colptr, (size_t)(R.vars() + 1) * 4, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(pcols, d_pcols, (size_t)R.nnz_p() * 4, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    int32_t* d_rows = st.out(rows, R.nnz_a(), 0xff);
+    int32_t* d_colptr = st.out(colptr, R.vars() + 1, 0xff);
+    int32_t* d_pcols = st.out(pcols, R.nnz_p(), 0xff);
+    return st.run([&]() -> int {
+        hipLaunchKernelGGL(pqp::path_pattern_kernel, dim3((n + 127) / 128), dim3(128), 0, h->stream, R, d_rows, d_colptr, d_pcols);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+static bool assemble_ok(pqp_handle* h, int batch, int n, int precise, const double* ref, const double* bounds, const double* scal, const double* a_val,
+                        const double* p_val, const double* lower, const double* upper) {
+    return h && ref && bounds && scal && a_val && p_val && lower && upper && batch >= 1 && n >= 2 && precise >= 0 && precise <= n;
 }
 
 int pqp_path_assemble_device(pqp_handle* h, int batch, int n, int precise, const double* ref, const double* lin,
                              const double* bounds, const double* scal, double* a_val, double* p_val, double* lower,
                              double* upper) {
-    if (!h || !ref || !bounds || !scal || !a_val || !p_val || !lower || !upper || batch < 1 || n < 2 || precise < 0 || precise > n)
-        return fail(PQP_ERR_INVALID, "pqp_path_assemble: bad argument");
+    if (!assemble_ok(h, batch, n, precise, ref, bounds, scal, a_val, p_val, lower, upper)) return fail(PQP_ERR_INVALID, "pqp_path_assemble: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     pqp::RefIndex R{n, precise};
     const size_t lds = ((size_t)R.nnz_a() + R.nnz_p() + 2 * (size_t)R.cons()) * 8;
     const int stage = lds <= 150 * 1024 ? 1 : 0;
-    if (stage && lds > 64 * 1024)
-        PQP_HIP(hipFuncSetAttribute((const void*)pqp::path_assemble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    int rc;
+    if (stage && (rc = lds_opt_in((const void*)pqp::path_assemble_kernel, lds, "pqp_path_assemble: LDS"))) return rc;
     const int grid = batch < 4096 ? batch : 4096;
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::path_assemble_kernel, dim3(grid), dim3(256), stage ? lds : 0, h->stream, R, batch, ref, lin, bounds,
-                       scal, h->prm, a_val, p_val, lower, upper, stage);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::path_assemble_kernel, dim3(grid), dim3(256), stage ? lds : 0, h->stream, R, batch, ref, lin, bounds,
+                           scal, h->prm, a_val, p_val, lower, upper, stage);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_path_assemble(pqp_handle* h, int batch, int n, int precise, const double* ref, const double* lin,
                       const double* bounds, const double* scal, double* a_val, double* p_val, double* lower, double* upper) {
-    if (!h || !ref || !bounds || !scal || !a_val || !p_val || !lower || !upper || batch < 1 || n < 2 || precise < 0 || precise > n)
-        return fail(PQP_ERR_INVALID, "pqp_path_assemble: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
+    if (!assemble_ok(h, batch, n, precise, ref, bounds, scal, a_val, p_val, lower, upper)) return fail(PQP_ERR_INVALID, "pqp_path_assemble: bad argument");
     pqp::RefIndex R{n, precise};
     const size_t bn = (size_t)batch * n;
-    int rc;
-    if ((rc = h->s_ref.ensure(bn * 5 * 8)) || (rc = h->s_bounds.ensure(bn * 6 * 8)) || (rc = h->s_scal.ensure((size_t)batch * 6 * 8)) ||
-        (rc = h->s_a.ensure((size_t)batch * R.nnz_a() * 8)) || (rc = h->s_p.ensure((size_t)batch * R.nnz_p() * 8)) ||
-        (rc = h->s_l.ensure((size_t)batch * R.cons() * 8)) || (rc = h->s_u.ensure((size_t)batch * R.cons() * 8)))
-        return rc;
-    if (lin && (rc = h->s_lin.ensure(bn * 3 * 8))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->s_ref.p, ref, bn * 5 * 8, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->s_bounds.p, bounds, bn * 6 * 8, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->s_scal.p, scal, (size_t)batch * 6 * 8, hipMemcpyHostToDevice, h->stream));
-    if (lin) PQP_HIP(hipMemcpyAsync(h->s_lin.p, lin, bn * 3 * 8, hipMemcpyHostToDevice, h->stream));
-    rc = pqp_path_assemble_device(h, batch, n, precise, h->s_ref.as<double>(), lin ? h->s_lin.as<double>() : nullptr,
-                                  h->s_bounds.as<double>(), h->s_scal.as<double>(), h->s_a.as<double>(), h->s_p.as<double>(),
-                                  h->s_l.as<double>(), h->s_u.as<double>());
-    if (rc) return rc;
-    PQP_HIP(hipMemcpyAsync(a_val, h->s_a.p, (size_t)batch * R.nnz_a() * 8, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(p_val, h->s_p.p, (size_t)batch * R.nnz_p() * 8, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(lower, h->s_l.p, (size_t)batch * R.cons() * 8, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(upper, h->s_u.p, (size_t)batch * R.cons() * 8, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    const double *d_ref = st.in(ref, bn * 5), *d_lin = st.in(lin, bn * 3), *d_bounds = st.in(bounds, bn * 6), *d_scal = st.in(scal, (size_t)batch * 6);
+    double *d_a = st.out(a_val, (size_t)batch * R.nnz_a()), *d_p = st.out(p_val, (size_t)batch * R.nnz_p());
+    double *d_l = st.out(lower, (size_t)batch * R.cons()), *d_u = st.out(upper, (size_t)batch * R.cons());
+    return st.run([&]() -> int { return pqp_path_assemble_device(h, batch, n, precise, d_ref, d_lin, d_bounds, d_scal, d_a, d_p, d_l, d_u); });
 }
 
 extern "C" hipError_t pqp_stream_launch(const pqp::lq::Args* a, int waves, void* stream);
@@ -596,11 +636,8 @@ static int path_stream_impl(pqp_handle* h, int batch, int n, const int32_t* n_of
         a.hist = h->stream_hist.as<int32_t>();
         a.order_next = h->stream_order.as<int32_t>() + (size_t)((h->stream_solves + 1) & 1) * batch;
     }
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    PQP_HIP(pqp_stream_launch(&a, waves, (void*)h->stream));      // path_stream_kernel lives in its own translation unit (pqp_path_stream.hip)
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    // (path_stream_kernel lives in its own translation unit, pqp_path_stream.hip)
+    if ((rc = h->launch_timed([&]() -> int { PQP_HIP(pqp_stream_launch(&a, waves, (void*)h->stream)); return PQP_OK; }))) return rc;
     if (ordered) { h->stream_solves += 1; h->stream_order_batch = batch; h->stream_order_n = n; }
     h->stream_last_batch = batch; h->stream_last_n = n;
     h->warm_batch = batch; h->warm_n = n;
@@ -636,10 +673,13 @@ static int stream_batch_auto(int n) {
 }
 extern "C" int pqp_stream_batch_default(int n) { return n < 2 ? 0 : stream_batch_auto(n); }
 
+static bool path_solve_ok(pqp_handle* h, int batch, int n, const double* ref, const double* bounds, const double* scal, int passes, const double* out) {
+    return h && ref && bounds && scal && out && batch >= 1 && n >= 2 && passes >= 0;
+}
+
 static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* ref, const double* lin, const double* bounds,
                            const double* scal, int passes, int warm, double* out, int32_t* status, int32_t* iters, double* info) {
-    if (!h || !ref || !bounds || !scal || !out || batch < 1 || n < 2 || passes < 0)
-        return fail(PQP_ERR_INVALID, "pqp_path_solve: bad argument");
+    if (!path_solve_ok(h, batch, n, ref, bounds, scal, passes, out)) return fail(PQP_ERR_INVALID, "pqp_path_solve: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     // lane-per-QP kernel: large batches of a caller that keeps no warm state (PQP_OPT_STREAM_BATCH), and every path of more than 512
     // waypoints (the lane-per-waypoint kernel's workgroup ends there; a reference path of 80 m at 0.15 m spacing has 530:
@@ -699,7 +739,7 @@ static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of,
         case 4: fn = pqp_path_solve_fn_nw4(cert); break;
         default: fn = pqp_path_solve_fn_nw8(cert); break;
     }
-    if (lds > 64 * 1024) PQP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if ((rc = lds_opt_in(fn, lds, "pqp_path_solve: LDS"))) return rc;
     // persistent workgroups: as many as the chip holds at once (a surplus one would only wait for a free slot), each with its own
     // save area; they draw the QPs from the ticket counter
     int& per_cu = h->blocks_per_cu[2 * lg + (cert ? 1 : 0)];
@@ -740,20 +780,20 @@ static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of,
         a.cost_hist = h->cost_hist.as<int32_t>();
         a.order_next = order_write;
     }
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    void* kargs[] = {(void*)&a};
-    hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(64 * nw), kargs, lds, h->stream);
-    if (le == hipSuccess) le = hipGetLastError();
-    if (le != hipSuccess) {
-        h->hist_batch = 0; h->hist_n = 0;          // (the histogram may have been cleared for a launch that never ran)
-        return fail(PQP_ERR_HIP, std::string("hipLaunchKernel(path_solve_kernel): ") + hipGetErrorString(le));
-    }
-    h->ticket_next = a.ticket_base + (unsigned long long)batch + (unsigned long long)grid;
-    if (h->opt_order_by_cost) { h->hist_batch = batch; h->hist_n = n; }
-    h->solves += 1;
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
+    rc = h->launch_timed([&]() -> int {
+        void* kargs[] = {(void*)&a};
+        hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(64 * nw), kargs, lds, h->stream);
+        if (le == hipSuccess) le = hipGetLastError();
+        if (le != hipSuccess) {
+            h->hist_batch = 0; h->hist_n = 0;          // (the histogram may have been cleared for a launch that never ran)
+            return fail(PQP_ERR_HIP, std::string("hipLaunchKernel(path_solve_kernel): ") + hipGetErrorString(le));
+        }
+        h->ticket_next = a.ticket_base + (unsigned long long)batch + (unsigned long long)grid;
+        if (h->opt_order_by_cost) { h->hist_batch = batch; h->hist_n = n; }
+        h->solves += 1;
+        return PQP_OK;
+    });
+    if (rc) return rc;
     h->warm_batch = batch; h->warm_n = n;
     h->warm_stored = h->opt_store_warm != 0 || h->opt_carry != 0;
     h->last_path_kernel = PQP_KERNEL_LANE_PER_WAYPOINT;
@@ -773,30 +813,14 @@ int pqp_path_solve_var_device(pqp_handle* h, int batch, int n_max, const int32_t
     return path_solve_impl(h, batch, n_max, n_of, ref, lin, bounds, scal, passes, warm, out, status, iters, info);
 }
 
-static int path_solve_host_body(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* ref, const double* lin, const double* bounds,
-                                const double* scal, int passes, int warm, double* out, int32_t* status, int32_t* iters, double* info,
-                                std::vector<int32_t>& counts);
-
 static int path_solve_host(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* ref, const double* lin, const double* bounds,
                            const double* scal, int passes, int warm, double* out, int32_t* status, int32_t* iters, double* info) {
-    if (!h || !ref || !bounds || !scal || !out || batch < 1 || n < 2 || passes < 0)
-        return fail(PQP_ERR_INVALID, "pqp_path_solve: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    std::vector<int32_t> counts;            // outlives every copy enqueued from it: an early error return synchronises first
-    const int rc = path_solve_host_body(h, batch, n, n_of, ref, lin, bounds, scal, passes, warm, out, status, iters, info, counts);
-    if (rc != PQP_OK) (void)hipStreamSynchronize(h->stream);
-    return rc;
-}
-
-static int path_solve_host_body(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* ref, const double* lin, const double* bounds,
-                                const double* scal, int passes, int warm, double* out, int32_t* status, int32_t* iters, double* info,
-                                std::vector<int32_t>& counts) {
-    const size_t bn = (size_t)batch * n;
-    int rc;
+    if (!path_solve_ok(h, batch, n, ref, bounds, scal, passes, out)) return fail(PQP_ERR_INVALID, "pqp_path_solve: bad argument");
     // A box with lower > upper bound: OSQP refuses such data at setup (OsqpEigen's initSolver() fails and BaseSolver::solve returns
     // false, base_solver.cpp:76-80).  The host-pointer entry points see the data anyway: such a QP is not launched (waypoint count 0)
     // and comes back PQP_STATUS_PRIMAL_INFEASIBLE.  (The device-pointer entry points do not validate: there the row would be
     // pinned to its upper bound.)
+    std::vector<int32_t> counts;            // declared before the staging: outlives the copy enqueued from it
     bool any_invalid = false;
     for (int q = 0; q < batch; ++q) {
         const int cnt = n_of ? n_of[q] : n;
@@ -813,29 +837,15 @@ static int path_solve_host_body(pqp_handle* h, int batch, int n, const int32_t* 
         if (bad) counts[q] = -1;
     }
     if (any_invalid) n_of = counts.data();
-    if (n_of) {
-        if ((rc = h->c_buf[11].ensure((size_t)batch * 4))) return rc;
-        PQP_HIP(hipMemcpyAsync(h->c_buf[11].p, n_of, (size_t)batch * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if ((rc = h->s_ref.ensure(bn * 5 * 8)) || (rc = h->s_bounds.ensure(bn * 6 * 8)) || (rc = h->s_scal.ensure((size_t)batch * 6 * 8)) ||
-        (rc = h->s_out.ensure(bn * 7 * 8)) || (rc = h->s_status.ensure((size_t)batch * 4)) || (rc = h->s_iters.ensure((size_t)batch * 4)) ||
-        (rc = h->s_info.ensure((size_t)batch * PQP_INFO_STRIDE * 8)))
-        return rc;
-    if (lin && (rc = h->s_lin.ensure(bn * 3 * 8))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->s_ref.p, ref, bn * 5 * 8, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->s_bounds.p, bounds, bn * 6 * 8, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->s_scal.p, scal, (size_t)batch * 6 * 8, hipMemcpyHostToDevice, h->stream));
-    if (lin) PQP_HIP(hipMemcpyAsync(h->s_lin.p, lin, bn * 3 * 8, hipMemcpyHostToDevice, h->stream));
-    if (n_of) PQP_HIP(hipMemsetAsync(h->s_out.p, 0, bn * 7 * 8, h->stream));        // rows beyond a QP's own count are not written
-    rc = path_solve_impl(h, batch, n, n_of ? h->c_buf[11].as<int32_t>() : nullptr, h->s_ref.as<double>(), lin ? h->s_lin.as<double>() : nullptr,
-                         h->s_bounds.as<double>(), h->s_scal.as<double>(), passes, warm, h->s_out.as<double>(), h->s_status.as<int32_t>(),
-                         h->s_iters.as<int32_t>(), h->s_info.as<double>());
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const double *d_ref = st.in(ref, bn * 5), *d_lin = st.in(lin, bn * 3), *d_bounds = st.in(bounds, bn * 6), *d_scal = st.in(scal, (size_t)batch * 6);
+    double* d_out = st.out(out, bn * 7, n_of ? 0 : -1);           // (rows beyond a QP's own count are not written)
+    int32_t *d_status = st.out(status, batch), *d_iters = st.out(iters, batch);
+    double* d_info = st.out(info, (size_t)batch * PQP_INFO_STRIDE);
+    const int rc = st.run([&]() -> int { return path_solve_impl(h, batch, n, d_n_of, d_ref, d_lin, d_bounds, d_scal, passes, warm, d_out, d_status, d_iters, d_info); });
     if (rc) return rc;
-    PQP_HIP(hipMemcpyAsync(out, h->s_out.p, bn * 7 * 8, hipMemcpyDeviceToHost, h->stream));
-    if (status) PQP_HIP(hipMemcpyAsync(status, h->s_status.p, (size_t)batch * 4, hipMemcpyDeviceToHost, h->stream));
-    if (iters) PQP_HIP(hipMemcpyAsync(iters, h->s_iters.p, (size_t)batch * 4, hipMemcpyDeviceToHost, h->stream));
-    if (info) PQP_HIP(hipMemcpyAsync(info, h->s_info.p, (size_t)batch * PQP_INFO_STRIDE * 8, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
     if (any_invalid && status)
         for (int q = 0; q < batch; ++q)
             if (counts[q] < 0) status[q] = PQP_STATUS_PRIMAL_INFEASIBLE;
@@ -857,20 +867,17 @@ int pqp_path_get_solution(pqp_handle* h, int batch, int n, int precise, double* 
     if (!h || batch < 1 || n < 2 || precise < 0 || precise > n) return fail(PQP_ERR_INVALID, "pqp_path_get_solution: bad argument");
     if (h->warm_batch != batch || h->warm_n != n || !h->warm_stored)
         return fail(PQP_ERR_INVALID, "pqp_path_get_solution: no solve of that shape on this handle (or PQP_OPT_STORE_WARM is off)");
-    PQP_HIP(hipSetDevice(h->device));
     pqp::RefIndex R{n, precise};
-    int rc;
-    if ((rc = h->s_a.ensure((size_t)batch * R.vars() * 8)) || (rc = h->s_l.ensure((size_t)batch * R.cons() * 8))) return rc;
-    PQP_HIP(hipMemsetAsync(h->s_a.p, 0, (size_t)batch * R.vars() * 8, h->stream));
-    PQP_HIP(hipMemsetAsync(h->s_l.p, 0, (size_t)batch * R.cons() * 8, h->stream));
-    const int total = batch * n;
-    hipLaunchKernelGGL(pqp::path_gather_solution, dim3((total + 255) / 256), dim3(256), 0, h->stream, R, batch, h->wx.as<double>(),
-                       h->wy.as<double>(), h->wye.as<double>(), x ? h->s_a.as<double>() : nullptr, y ? h->s_l.as<double>() : nullptr);
-    PQP_HIP(hipGetLastError());
-    if (x) PQP_HIP(hipMemcpyAsync(x, h->s_a.p, (size_t)batch * R.vars() * 8, hipMemcpyDeviceToHost, h->stream));
-    if (y) PQP_HIP(hipMemcpyAsync(y, h->s_l.p, (size_t)batch * R.cons() * 8, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    double* d_x = st.out(x, (size_t)batch * R.vars(), 0);
+    double* d_y = st.out(y, (size_t)batch * R.cons(), 0);
+    return st.run([&]() -> int {
+        const int total = batch * n;
+        hipLaunchKernelGGL(pqp::path_gather_solution, dim3((total + 255) / 256), dim3(256), 0, h->stream, R, batch, h->wx.as<double>(),
+                           h->wy.as<double>(), h->wye.as<double>(), x ? d_x : nullptr, y ? d_y : nullptr);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_constrain_angle_device(pqp_handle* h, int count, const double* in, double* out) {
@@ -890,8 +897,9 @@ int pqp_last_kernel_ms(pqp_handle* h, float* ms) {
     if (!h || !ms) return fail(PQP_ERR_INVALID, "pqp_last_kernel_ms: null argument");
     if (!h->timed) return fail(PQP_ERR_INVALID, "pqp_last_kernel_ms: nothing was launched yet");
     PQP_HIP(hipSetDevice(h->device));
-    PQP_HIP(hipEventSynchronize(h->ev1));
-    PQP_HIP(hipEventElapsedTime(ms, h->ev0, h->ev1));
+    const long long idx = (h->ev_count - 1) % pqp_handle::kEvSlots;
+    PQP_HIP(hipEventSynchronize(h->evs1[idx]));
+    PQP_HIP(hipEventElapsedTime(ms, h->evs0[idx], h->evs1[idx]));
     return PQP_OK;
 }
 
@@ -902,7 +910,7 @@ int pqp_kernel_ms_history(pqp_handle* h, float* ms, int count) {
     PQP_HIP(hipSetDevice(h->device));
     PQP_HIP(hipStreamSynchronize(h->stream));
     for (int k = 0; k < count; ++k) {          // oldest of the requested launches first
-        const long long idx = (h->ev_count - count + k) % pqp_handle::kEvRing;
+        const long long idx = (h->ev_count - count + k) % pqp_handle::kEvSlots;
         PQP_HIP(hipEventElapsedTime(ms + k, h->evs0[idx], h->evs1[idx]));
     }
     return PQP_OK;
@@ -976,11 +984,10 @@ int sm_solve(pqp_handle* h, int type, int batch, int n, int32_t* status, int32_t
     // the row data of A, the index lists and q staged in LDS once per QP (256-lane kernels: always - two of them still share a CU's LDS up
     // to 80 KB each; 512-lane kernels: when it fits; 1024-lane kernels: never)
     const size_t lds0 = (size_t)pqp::BqLayout{sh.nv, sh.nc, sh.bw}.total(false) * 8, lds1 = (size_t)pqp::BqLayout{sh.nv, sh.nc, sh.bw}.total(true) * 8;
-    if (lds0 > 160 * 1024) return fail(PQP_ERR_CAPACITY, "smoother QP too large for one CU's LDS");
     const int nbb = pqp::BqLayout{sh.nv, sh.nc, sh.bw}.nbb();
     const int threads = 64 * ((nbb + 63) / 64);        // one lane per (padded) variable
     if (threads > 1024) return fail(PQP_ERR_CAPACITY, "smoother QP has more than 1024 variables");
-    const bool stage = threads <= 512 && lds1 <= 160 * 1024;
+    const bool stage = threads <= 512 && lds1 <= kLdsPerCu;
     const size_t lds = stage ? lds1 : lds0;
     const void* fn = nullptr;
 #define PQP_BQ_PICK(BB) fn = (threads <= 256 && stage) ? (const void*)pqp::banded_solve_kernel<BB, 256, true> : threads <= 512 ? (stage ? (const void*)pqp::banded_solve_kernel<BB, 512, true> : (const void*)pqp::banded_solve_kernel<BB, 512, false>) : (const void*)pqp::banded_solve_kernel<BB, 1024, false>
@@ -991,22 +998,21 @@ int sm_solve(pqp_handle* h, int type, int batch, int n, int32_t* status, int32_t
         default: return fail(PQP_ERR_INVALID, "unsupported smoother block size");
     }
 #undef PQP_BQ_PICK
-    if (lds > 64 * 1024) PQP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    void* kargs[] = {(void*)&a};
-    PQP_HIP(hipLaunchKernel(fn, dim3(batch), dim3(threads), kargs, lds, h->stream));
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in(fn, lds, "smoother QP too large for one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        void* kargs[] = {(void*)&a};
+        PQP_HIP(hipLaunchKernel(fn, dim3(batch), dim3(threads), kargs, lds, h->stream));
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 // does the generic banded core hold a smoother QP of this size (its vectors, factor rows and row data in one CU's LDS, one lane per padded variable)?
 bool sm_generic_fits(int type, int n) {
     const SmShape sh = sm_shape(type, n);
     const pqp::BqLayout lay{sh.nv, sh.nc, sh.bw};
-    return (size_t)lay.total(false) * 8 <= 160 * 1024 && 64 * ((lay.nbb() + 63) / 64) <= 1024;
+    return (size_t)lay.total(false) * 8 <= kLdsPerCu && 64 * ((lay.nbb() + 63) / 64) <= 1024;
 }
 
 int sm_alloc(pqp_handle* h, int type, int batch, int n) {
@@ -1020,11 +1026,16 @@ int sm_alloc(pqp_handle* h, int type, int batch, int n) {
 }
 }  // namespace
 
+static bool tension2_ok(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list, const double* k_list,
+                        const double* s_list, const double* out_x, const double* out_y, const double* out_s) {
+    return h && x_list && y_list && angle_list && k_list && s_list && out_x && out_y && out_s && batch >= 1 && n >= 3;
+}
+
 // TensionSmoother2::osqpSmooth (tension_smoother_2.cpp:20-72), device pointers, all lists [batch][n]; n_of [batch] (device) or nullptr
 static int smooth_tension2_impl(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* x_list, const double* y_list,
                                 const double* angle_list, const double* k_list, const double* s_list, double* out_x, double* out_y, double* out_s,
                                 int32_t* status, int32_t* iters, double* info) {
-    if (!h || !x_list || !y_list || !angle_list || !k_list || !s_list || !out_x || !out_y || !out_s || batch < 1 || n < 3)
+    if (!tension2_ok(h, batch, n, x_list, y_list, angle_list, k_list, s_list, out_x, out_y, out_s))
         return fail(PQP_ERR_INVALID, "pqp_smooth_tension2: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     int rc;
@@ -1036,15 +1047,13 @@ static int smooth_tension2_impl(pqp_handle* h, int batch, int n, const int32_t* 
         hipLaunchKernelGGL(pqp::tension2_stage_kernel, dim3((batch * n + 255) / 256), dim3(256), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, k_list,
                            s_list, h->b_aval.as<double>());
         PQP_HIP(hipGetLastError());
-        h->next_event_pair();
-        if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-        hipLaunchKernelGGL(pqp::tension2_exact_kernel, dim3((batch + 63) / 64), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list,
-                           h->prm.tension2_deviation_weight, h->prm.tension2_curvature_weight, h->prm.tension2_curvature_rate_weight, h->b_aval.as<double>(),
-                           h->b_pband.as<double>(), out_x, out_y, out_s, status, iters, info);
-        PQP_HIP(hipGetLastError());
-        if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-        h->timed = true;
-        return PQP_OK;
+        return h->launch_timed([&]() -> int {
+            hipLaunchKernelGGL(pqp::tension2_exact_kernel, dim3((batch + 63) / 64), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list,
+                               h->prm.tension2_deviation_weight, h->prm.tension2_curvature_weight, h->prm.tension2_curvature_rate_weight, h->b_aval.as<double>(),
+                               h->b_pband.as<double>(), out_x, out_y, out_s, status, iters, info);
+            PQP_HIP(hipGetLastError());
+            return PQP_OK;
+        });
     }
     if ((rc = sm_alloc(h, SM_TENSION2, batch, n))) return rc;
     const int total = batch * n;
@@ -1071,12 +1080,16 @@ int pqp_smooth_tension2_var_device(pqp_handle* h, int batch, int n_max, const in
     return smooth_tension2_impl(h, batch, n_max, n_of, x_list, y_list, angle_list, k_list, s_list, out_x, out_y, out_s, status, iters, info);
 }
 
+static bool tension_ok(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list, const double* clearance,
+                       const double* out_x, const double* out_y, const double* out_s) {
+    return h && x_list && y_list && angle_list && clearance && out_x && out_y && out_s && batch >= 1 && n >= 4;
+}
+
 // TensionSmoother::osqpSmooth (tension_smoother.cpp:49-100); clearance[batch][n] = Map::getObstacleDistance at each point; n_of [batch]
 // (device) or nullptr
 static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* x_list, const double* y_list, const double* angle_list,
                                const double* clearance, double* out_x, double* out_y, double* out_s, int32_t* status, int32_t* iters, double* info) {
-    if (!h || !x_list || !y_list || !angle_list || !clearance || !out_x || !out_y || !out_s || batch < 1 || n < 4)
-        return fail(PQP_ERR_INVALID, "pqp_smooth_tension: bad argument");
+    if (!tension_ok(h, batch, n, x_list, y_list, angle_list, clearance, out_x, out_y, out_s)) return fail(PQP_ERR_INVALID, "pqp_smooth_tension: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     int rc;
     // The generic block-cyclic-reduction core keeps a QP's vectors, factor rows and row data in one compute unit's LDS: in TensionSmoother's
@@ -1088,8 +1101,6 @@ static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n
     if (h->prm.polish == 1 || !generic_fits) {
         // exact optima asked for (or the only kernel that holds the QP): the box QP in the lateral shifts alone, one wavefront per scenario (tension_exact_kernel)
         if (!status) return fail(PQP_ERR_INVALID, "pqp_smooth_tension: status is null");
-        h->next_event_pair();
-        if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
         const double wk = h->prm.cartesian_curvature_weight, wdk = h->prm.cartesian_curvature_rate_weight, wdev = h->prm.cartesian_deviation_weight, tol = h->prm.polish_tol;
         // PQP_OPT_CARRY_CYCLES: the active set every line ended with is kept on the handle; a solve of the shape of the previous one starts from it
         signed char* act_io = nullptr;
@@ -1101,24 +1112,22 @@ static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n
             carry = (h->sm_act_batch[0] == batch && h->sm_act_n[0] == n && before == h->sm_act[0].p) ? 1 : 0;
             h->sm_act_batch[0] = batch; h->sm_act_n[0] = n;
         }
-        if (n <= 64) hipLaunchKernelGGL(pqp::tension_exact_kernel<1>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        else if (n <= 128) hipLaunchKernelGGL(pqp::tension_exact_kernel<2>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        else if (n <= 256) hipLaunchKernelGGL(pqp::tension_exact_kernel<4>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        else if (n <= 384) hipLaunchKernelGGL(pqp::tension_exact_kernel<6>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        else if (n <= 512) hipLaunchKernelGGL(pqp::tension_exact_kernel<8>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        // (twelve / sixteen points per lane: the lane state no longer fits the registers - 1.8 / 3.3 KB of scratch per lane - but lines that long are
-        //  rare, a point per metre of reference line, and the recursion down the lanes, not the spills, is what their time goes to)
-        else if (n <= 768) hipLaunchKernelGGL(pqp::tension_exact_kernel<12>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        else if (n <= 1024) hipLaunchKernelGGL(pqp::tension_exact_kernel<16>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-        else {
-            // any longer line (the reference has no cap: tension_smoother.cpp:49-100): the same kernel with its arrays in HBM (SmHbm)
-            if ((rc = h->b_pband.ensure((size_t)batch * pqp::kTensionExactArrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
-            hipLaunchKernelGGL(pqp::tension_exact_kernel<0>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, h->b_pband.as<double>());
-        }
-        PQP_HIP(hipGetLastError());
-        if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-        h->timed = true;
-        return PQP_OK;
+        // any line longer than 1024 points (the reference has no cap: tension_smoother.cpp:49-100): the same kernel with its arrays in HBM (SmHbm)
+        if (n > 1024 && (rc = h->b_pband.ensure((size_t)batch * pqp::kTensionExactArrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
+        return h->launch_timed([&]() -> int {
+            if (n <= 64) hipLaunchKernelGGL(pqp::tension_exact_kernel<1>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            else if (n <= 128) hipLaunchKernelGGL(pqp::tension_exact_kernel<2>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            else if (n <= 256) hipLaunchKernelGGL(pqp::tension_exact_kernel<4>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            else if (n <= 384) hipLaunchKernelGGL(pqp::tension_exact_kernel<6>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            else if (n <= 512) hipLaunchKernelGGL(pqp::tension_exact_kernel<8>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            // (twelve / sixteen points per lane: the lane state no longer fits the registers - 1.8 / 3.3 KB of scratch per lane - but lines that long are
+            //  rare, a point per metre of reference line, and the recursion down the lanes, not the spills, is what their time goes to)
+            else if (n <= 768) hipLaunchKernelGGL(pqp::tension_exact_kernel<12>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            else if (n <= 1024) hipLaunchKernelGGL(pqp::tension_exact_kernel<16>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
+            else hipLaunchKernelGGL(pqp::tension_exact_kernel<0>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, h->b_pband.as<double>());
+            PQP_HIP(hipGetLastError());
+            return PQP_OK;
+        });
     }
     if ((rc = sm_alloc(h, SM_TENSION, batch, n))) return rc;
     const int total = batch * n;
@@ -1144,47 +1153,46 @@ int pqp_smooth_tension_var_device(pqp_handle* h, int batch, int n_max, const int
     return smooth_tension_impl(h, batch, n_max, n_of, x_list, y_list, angle_list, clearance, out_x, out_y, out_s, status, iters, info);
 }
 
+static bool post_smooth_ok(pqp_handle* h, int batch, int m, const double* layers_s, const double* lb, const double* ub, const double* vehicle_l,
+                           const double* out_l) {
+    return h && layers_s && lb && ub && vehicle_l && out_l && batch >= 1 && m >= 4;
+}
+
 // ReferencePathSmoother::postSmooth QP (reference_path_smoother.cpp:526-558): out_l[batch][m] = the lateral offsets l_i
 static int post_smooth_impl(pqp_handle* h, int batch, int m, const int32_t* m_of, const double* layers_s, const double* lb, const double* ub,
                             const double* vehicle_l, double* out_l, int32_t* status, int32_t* iters, double* info) {
-    if (!h || !layers_s || !lb || !ub || !vehicle_l || !out_l || batch < 1 || m < 4) return fail(PQP_ERR_INVALID, "pqp_post_smooth: bad argument (m >= 4, reference_path_smoother.cpp:528)");
+    if (!post_smooth_ok(h, batch, m, layers_s, lb, ub, vehicle_l, out_l)) return fail(PQP_ERR_INVALID, "pqp_post_smooth: bad argument (m >= 4, reference_path_smoother.cpp:528)");
     PQP_HIP(hipSetDevice(h->device));
+    int rc;
     // (beyond what the generic core holds in a CU's LDS also a handle in the reference's ADMM setting gets the exact kernel's optimum, as in smooth_tension_impl)
     if (h->prm.polish == 1 || !sm_generic_fits(SM_POST, m)) {
         // exact optima asked for: the box QP in the offsets alone, one wavefront per scenario (post_exact_kernel)
         if (!status) return fail(PQP_ERR_INVALID, "pqp_post_smooth: status is null");
-        h->next_event_pair();
-        if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
         const double tol = h->prm.polish_tol;
         signed char* act_io = nullptr;          // PQP_OPT_CARRY_CYCLES, as in smooth_tension_impl
         int carry = 0;
         if (h->opt_carry) {
             const void* before = h->sm_act[1].p;
-            int rc_a;
-            if ((rc_a = h->sm_act[1].ensure((size_t)batch * m))) return rc_a;
+            if ((rc = h->sm_act[1].ensure((size_t)batch * m))) return rc;
             act_io = h->sm_act[1].as<signed char>();
             carry = (h->sm_act_batch[1] == batch && h->sm_act_n[1] == m && before == h->sm_act[1].p) ? 1 : 0;
             h->sm_act_batch[1] = batch; h->sm_act_n[1] = m;
         }
-        if (m <= 64) hipLaunchKernelGGL(pqp::post_exact_kernel<1>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else if (m <= 128) hipLaunchKernelGGL(pqp::post_exact_kernel<2>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else if (m <= 256) hipLaunchKernelGGL(pqp::post_exact_kernel<4>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else if (m <= 384) hipLaunchKernelGGL(pqp::post_exact_kernel<6>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else if (m <= 512) hipLaunchKernelGGL(pqp::post_exact_kernel<8>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else if (m <= 768) hipLaunchKernelGGL(pqp::post_exact_kernel<12>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else if (m <= 1024) hipLaunchKernelGGL(pqp::post_exact_kernel<16>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-        else {
-            // any longer corridor (reference_path_smoother.cpp:526-580 has no cap): the same kernel with its arrays in HBM (SmHbm)
-            int rc_w;
-            if ((rc_w = h->b_pband.ensure((size_t)batch * pqp::kPostExactArrays * (64 * (((size_t)m + 63) / 64)) * 8))) return rc_w;
-            hipLaunchKernelGGL(pqp::post_exact_kernel<0>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, h->b_pband.as<double>());
-        }
-        PQP_HIP(hipGetLastError());
-        if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-        h->timed = true;
-        return PQP_OK;
+        // any corridor longer than 1024 layers (reference_path_smoother.cpp:526-580 has no cap): the same kernel with its arrays in HBM (SmHbm)
+        if (m > 1024 && (rc = h->b_pband.ensure((size_t)batch * pqp::kPostExactArrays * (64 * (((size_t)m + 63) / 64)) * 8))) return rc;
+        return h->launch_timed([&]() -> int {
+            if (m <= 64) hipLaunchKernelGGL(pqp::post_exact_kernel<1>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else if (m <= 128) hipLaunchKernelGGL(pqp::post_exact_kernel<2>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else if (m <= 256) hipLaunchKernelGGL(pqp::post_exact_kernel<4>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else if (m <= 384) hipLaunchKernelGGL(pqp::post_exact_kernel<6>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else if (m <= 512) hipLaunchKernelGGL(pqp::post_exact_kernel<8>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else if (m <= 768) hipLaunchKernelGGL(pqp::post_exact_kernel<12>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else if (m <= 1024) hipLaunchKernelGGL(pqp::post_exact_kernel<16>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
+            else hipLaunchKernelGGL(pqp::post_exact_kernel<0>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, h->b_pband.as<double>());
+            PQP_HIP(hipGetLastError());
+            return PQP_OK;
+        });
     }
-    int rc;
     if ((rc = sm_alloc(h, SM_POST, batch, m))) return rc;
     const int total = batch * m;
     hipLaunchKernelGGL(pqp::post_assemble_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l,
@@ -1207,63 +1215,37 @@ int pqp_post_smooth_var_device(pqp_handle* h, int batch, int m_max, const int32_
     return post_smooth_impl(h, batch, m_max, m_of, layers_s, lb, ub, vehicle_l, out_l, status, iters, info);
 }
 
-// host-pointer conveniences: nin input lists of [batch][n] (+ optional [batch] scalar list), nout output lists
-static int sm_host_call(pqp_handle* h, int which, int batch, int n, const double* const* in, int nin, const double* scalar_in, double* const* out,
-                        int nout, int32_t* status, int32_t* iters) {
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t bytes = (size_t)batch * n * 8;
-    int rc;
-    for (int k = 0; k < nin; ++k) {
-        if ((rc = h->b_in[k].ensure(bytes))) return rc;
-        PQP_HIP(hipMemcpyAsync(h->b_in[k].p, in[k], bytes, hipMemcpyHostToDevice, h->stream));
-    }
-    if (scalar_in) {
-        if ((rc = h->b_in[4].ensure((size_t)batch * 8))) return rc;
-        PQP_HIP(hipMemcpyAsync(h->b_in[4].p, scalar_in, (size_t)batch * 8, hipMemcpyHostToDevice, h->stream));
-    }
-    for (int k = 0; k < nout; ++k) if ((rc = h->b_out[k].ensure(bytes))) return rc;
-    if ((rc = h->s_status.ensure((size_t)batch * 4)) || (rc = h->s_iters.ensure((size_t)batch * 4))) return rc;
-    double* i0 = h->b_in[0].as<double>(); double* i1 = h->b_in[1].as<double>(); double* i2 = h->b_in[2].as<double>(); double* i3 = h->b_in[3].as<double>();
-    double* o0 = h->b_out[0].as<double>(); double* o1 = h->b_out[1].as<double>(); double* o2 = h->b_out[2].as<double>();
-    if (which == SM_TENSION2) {
-        if ((rc = h->b_in[4].ensure(bytes))) return rc;
-        PQP_HIP(hipMemcpyAsync(h->b_in[4].p, in[4], bytes, hipMemcpyHostToDevice, h->stream));
-        rc = pqp_smooth_tension2_device(h, batch, n, i0, i1, i2, i3, h->b_in[4].as<double>(), o0, o1, o2, h->s_status.as<int32_t>(), h->s_iters.as<int32_t>(), nullptr);
-    } else if (which == SM_TENSION) {
-        rc = pqp_smooth_tension_device(h, batch, n, i0, i1, i2, i3, o0, o1, o2, h->s_status.as<int32_t>(), h->s_iters.as<int32_t>(), nullptr);
-    } else {
-        rc = pqp_post_smooth_device(h, batch, n, i0, i1, i2, h->b_in[4].as<double>(), o0, h->s_status.as<int32_t>(), h->s_iters.as<int32_t>(), nullptr);
-    }
-    if (rc) return rc;
-    for (int k = 0; k < nout; ++k) PQP_HIP(hipMemcpyAsync(out[k], h->b_out[k].p, bytes, hipMemcpyDeviceToHost, h->stream));
-    if (status) PQP_HIP(hipMemcpyAsync(status, h->s_status.p, (size_t)batch * 4, hipMemcpyDeviceToHost, h->stream));
-    if (iters) PQP_HIP(hipMemcpyAsync(iters, h->s_iters.p, (size_t)batch * 4, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
-}
-
 int pqp_smooth_tension2(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list, const double* k_list,
                         const double* s_list, double* out_x, double* out_y, double* out_s, int32_t* status, int32_t* iters) {
-    if (!h || !x_list || !y_list || !angle_list || !k_list || !s_list || !out_x || !out_y || !out_s || batch < 1 || n < 3)
-        return fail(PQP_ERR_INVALID, "pqp_smooth_tension2: bad argument");
-    const double* in[5] = {x_list, y_list, angle_list, k_list, s_list};
-    double* out[3] = {out_x, out_y, out_s};
-    return sm_host_call(h, SM_TENSION2, batch, n, in, 4, nullptr, out, 3, status, iters);
+    if (!tension2_ok(h, batch, n, x_list, y_list, angle_list, k_list, s_list, out_x, out_y, out_s)) return fail(PQP_ERR_INVALID, "pqp_smooth_tension2: bad argument");
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double *d_x = st.in(x_list, bn), *d_y = st.in(y_list, bn), *d_angle = st.in(angle_list, bn), *d_k = st.in(k_list, bn), *d_s = st.in(s_list, bn);
+    double *o_x = st.out(out_x, bn), *o_y = st.out(out_y, bn), *o_s = st.out(out_s, bn);
+    int32_t *d_status = st.out(status, batch), *d_iters = st.out(iters, batch);
+    return st.run([&]() -> int { return pqp_smooth_tension2_device(h, batch, n, d_x, d_y, d_angle, d_k, d_s, o_x, o_y, o_s, d_status, d_iters, nullptr); });
 }
+
 int pqp_smooth_tension(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list, const double* clearance,
                        double* out_x, double* out_y, double* out_s, int32_t* status, int32_t* iters) {
-    if (!h || !x_list || !y_list || !angle_list || !clearance || !out_x || !out_y || !out_s || batch < 1 || n < 4)
-        return fail(PQP_ERR_INVALID, "pqp_smooth_tension: bad argument");
-    const double* in[4] = {x_list, y_list, angle_list, clearance};
-    double* out[3] = {out_x, out_y, out_s};
-    return sm_host_call(h, SM_TENSION, batch, n, in, 4, nullptr, out, 3, status, iters);
+    if (!tension_ok(h, batch, n, x_list, y_list, angle_list, clearance, out_x, out_y, out_s)) return fail(PQP_ERR_INVALID, "pqp_smooth_tension: bad argument");
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double *d_x = st.in(x_list, bn), *d_y = st.in(y_list, bn), *d_angle = st.in(angle_list, bn), *d_clr = st.in(clearance, bn);
+    double *o_x = st.out(out_x, bn), *o_y = st.out(out_y, bn), *o_s = st.out(out_s, bn);
+    int32_t *d_status = st.out(status, batch), *d_iters = st.out(iters, batch);
+    return st.run([&]() -> int { return pqp_smooth_tension_device(h, batch, n, d_x, d_y, d_angle, d_clr, o_x, o_y, o_s, d_status, d_iters, nullptr); });
 }
+
 int pqp_post_smooth(pqp_handle* h, int batch, int m, const double* layers_s, const double* lb, const double* ub, const double* vehicle_l, double* out_l,
                     int32_t* status, int32_t* iters) {
-    if (!h || !layers_s || !lb || !ub || !vehicle_l || !out_l || batch < 1 || m < 4) return fail(PQP_ERR_INVALID, "pqp_post_smooth: bad argument");
-    const double* in[3] = {layers_s, lb, ub};
-    double* out[1] = {out_l};
-    return sm_host_call(h, SM_POST, batch, m, in, 3, vehicle_l, out, 1, status, iters);
+    if (!post_smooth_ok(h, batch, m, layers_s, lb, ub, vehicle_l, out_l)) return fail(PQP_ERR_INVALID, "pqp_post_smooth: bad argument");
+    const size_t bm = (size_t)batch * m;
+    Staging st(h);
+    const double *d_s = st.in(layers_s, bm), *d_lb = st.in(lb, bm), *d_ub = st.in(ub, bm), *d_vl = st.in(vehicle_l, batch);
+    double* o_l = st.out(out_l, bm);
+    int32_t *d_status = st.out(status, batch), *d_iters = st.out(iters, batch);
+    return st.run([&]() -> int { return pqp_post_smooth_device(h, batch, m, d_s, d_lb, d_ub, d_vl, o_l, d_status, d_iters, nullptr); });
 }
 
 // ---- corridor bounds from the distance map -----------------------------------------------------------
@@ -1281,71 +1263,64 @@ static bool geometry_ok(const pqp_grid_geometry* g) {
     return g && g->rows >= 2 && g->cols >= 2 && g->resolution > 0.0 && (long long)g->rows * g->cols < (1ll << 30);
 }
 
+static bool corridor_ok(pqp_handle* h, int batch, int n, int m, const double* ref, const double* spline, const double* spline_ext, const float* dist,
+                        const pqp_grid_geometry* geom, const pqp_corridor_params* prm, const double* bounds, const int32_t* n_valid) {
+    return h && ref && spline && spline_ext && dist && prm && bounds && n_valid && batch >= 1 && n >= 1 && m >= 3 && geometry_ok(geom) &&
+           prm->delta_s > 0.0 && prm->smaller_ds > 0.0;
+}
+
 int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* spline,
                                const double* spline_ext, const float* dist, const int32_t* map_of, const pqp_grid_geometry* geom,
                                const pqp_corridor_params* prm, double* bounds, int32_t* n_valid) {
-    if (!h || !ref || !spline || !spline_ext || !dist || !geom || !prm || !bounds || !n_valid || batch < 1 || n < 1 || m < 3 ||
-        !geometry_ok(geom) || !(prm->delta_s > 0.0) || !(prm->smaller_ds > 0.0))
+    if (!corridor_ok(h, batch, n, m, ref, spline, spline_ext, dist, geom, prm, bounds, n_valid))
         return fail(PQP_ERR_INVALID, "pqp_corridor_bounds: bad argument (m >= 3 knots: spline.cpp:164; a map layer of 2 x 2 to 2^30 cells)");
     PQP_HIP(hipSetDevice(h->device));
     pqp::CorridorArgs a;
     a.batch = batch; a.n = n; a.m = m; a.ref = ref; a.spl = spline; a.spl_ext = spline_ext; a.dist = dist; a.map_of = map_of; a.n_of = n_of;
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
-    int threads = 64 * ((3 * n + 63) / 64);
-    if (threads > 1024) threads = 1024;
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
     // a whole scenario's probes in LDS when they fit (9 m + 33 n doubles), tiles of waypoints otherwise: any path length
     a.tile = n;
-    if (pqp::CorridorLds{m, n}.total_bytes() > 160 * 1024) {
-        const long long room = 160 * 1024 - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
+    if (pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu) {
+        const long long room = (long long)kLdsPerCu - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
         if (room < 16 * per_waypoint) return fail(PQP_ERR_CAPACITY, "pqp_corridor_bounds: the line's spline table (9 m doubles) does not leave room for the probes in one CU's LDS");
         a.tile = (int)(room / per_waypoint);
     }
     const size_t lds = pqp::CorridorLds{m, a.tile}.total_bytes();
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_corridor_bounds: scenario too large for one CU's LDS (about 9 m + 31 n doubles)");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::corridor_bounds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    threads = 512;                   // the sample loops are strided; 512 lanes per scenario keep the most gathers in flight per CU (measured at batch
+    const int rc = lds_opt_in((const void*)pqp::corridor_bounds_kernel, lds, "pqp_corridor_bounds: scenario too large for one CU's LDS (about 9 m + 31 n doubles)");
+    if (rc) return rc;
+    const int threads = 512;         // the sample loops are strided; 512 lanes per scenario keep the most gathers in flight per CU (measured at batch
                                      // 1024 x n = 80: 1024 lanes 142 us - two scenarios per CU -, 512: 121, 256: 120, 128: 146)
-    hipLaunchKernelGGL(pqp::corridor_bounds_kernel, dim3(batch), dim3(threads), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::corridor_bounds_kernel, dim3(batch), dim3(threads), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_corridor_bounds(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* spline,
                         const double* spline_ext, const float* dist, int n_maps, const int32_t* map_of, const pqp_grid_geometry* geom,
                         const pqp_corridor_params* prm, double* bounds, int32_t* n_valid) {
-    if (!h || !ref || !spline || !spline_ext || !dist || !geom || !prm || !bounds || !n_valid || batch < 1 || n < 1 || m < 3 || n_maps < 1)
+    if (!corridor_ok(h, batch, n, m, ref, spline, spline_ext, dist, geom, prm, bounds, n_valid) || n_maps < 1)
         return fail(PQP_ERR_INVALID, "pqp_corridor_bounds: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_ref = (size_t)batch * n * PQP_REF_STRIDE * 8, b_spl = (size_t)batch * 9 * m * 8, b_ext = (size_t)batch * 4 * 8;
-    const size_t b_map = (size_t)n_maps * geom->rows * geom->cols * 4, b_of = (size_t)batch * 4;
-    const size_t b_bnd = (size_t)batch * n * PQP_BOUNDS_STRIDE * 8, b_nv = (size_t)batch * 4;
-    const size_t sizes[7] = {b_ref, b_spl, b_ext, b_map, b_of, b_bnd, b_nv};
-    int rc;
-    for (int k = 0; k < 7; ++k) if ((rc = h->c_buf[k].ensure(sizes[k]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, ref, b_ref, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, spline, b_spl, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, spline_ext, b_ext, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, dist, b_map, hipMemcpyHostToDevice, h->stream));
-    if (map_of) PQP_HIP(hipMemcpyAsync(h->c_buf[4].p, map_of, b_of, hipMemcpyHostToDevice, h->stream));
-    if (n_of) PQP_HIP(hipMemcpyAsync(h->c_buf[6].p, n_of, b_nv, hipMemcpyHostToDevice, h->stream));     // n_valid is written after n_of is read
-    if ((rc = pqp_corridor_bounds_device(h, batch, n, m, h->c_buf[0].as<double>(), n_of ? h->c_buf[6].as<int32_t>() : nullptr,
-                                         h->c_buf[1].as<double>(), h->c_buf[2].as<double>(),
-                                         h->c_buf[3].as<float>(), map_of ? h->c_buf[4].as<int32_t>() : nullptr, geom, prm,
-                                         h->c_buf[5].as<double>(), h->c_buf[6].as<int32_t>())))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(bounds, h->c_buf[5].p, b_bnd, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(n_valid, h->c_buf[6].p, b_nv, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_ref = st.in(ref, bn * PQP_REF_STRIDE);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4);
+    const float* d_dist = st.in(dist, (size_t)n_maps * geom->rows * geom->cols);
+    const int32_t* d_map_of = st.in(map_of, batch);
+    double* d_bounds = st.out(bounds, bn * PQP_BOUNDS_STRIDE);
+    int32_t* d_n_valid = st.out(n_valid, batch);
+    return st.run([&]() -> int { return pqp_corridor_bounds_device(h, batch, n, m, d_ref, d_n_of, d_spl, d_ext, d_dist, d_map_of, geom, prm, d_bounds, d_n_valid); });
 }
 
 // ---- the obstacle distance layer from an occupancy grid (src/test/demo.cpp:104-113) ------------------------------------------------
+static bool distance_layer_ok(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, const float* dist) {
+    return h && grid && dist && n_maps >= 1 && geometry_ok(geom);
+}
+
 int pqp_distance_layer_device(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist) {
-    if (!h || !grid || !dist || n_maps < 1 || !geometry_ok(geom))
+    if (!distance_layer_ok(h, n_maps, geom, grid, dist))
         return fail(PQP_ERR_INVALID, "pqp_distance_layer: bad argument (n_maps >= 1; a map of 2 x 2 to 2^30 cells, resolution > 0)");
     PQP_HIP(hipSetDevice(h->device));
     pqp::DistanceArgs a;
@@ -1353,31 +1328,25 @@ int pqp_distance_layer_device(pqp_handle* h, int n_maps, const pqp_grid_geometry
     const pqp::edt::Shape sh = pqp::edt::shape_of(geom->rows, geom->cols);
     a.site_bits = sh.site_bits; a.empty_d2 = sh.empty_d2; a.res = (float)geom->resolution;
     const long long lines = (long long)n_maps * geom->cols, lanes = (long long)n_maps * geom->rows;
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::distance_lines_kernel, dim3((unsigned)std::min((lines + 3) / 4, 1ll << 20)), dim3(256), 0, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    const unsigned blocks = (unsigned)std::min((lanes + 63) / 64, 1ll << 20);
-    if (sh.wide) hipLaunchKernelGGL(pqp::distance_envelope_kernel<int64_t>, dim3(blocks), dim3(64), 0, h->stream, a);
-    else hipLaunchKernelGGL(pqp::distance_envelope_kernel<int32_t>, dim3(blocks), dim3(64), 0, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::distance_lines_kernel, dim3((unsigned)std::min((lines + 3) / 4, 1ll << 20)), dim3(256), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        const unsigned blocks = (unsigned)std::min((lanes + 63) / 64, 1ll << 20);
+        if (sh.wide) hipLaunchKernelGGL(pqp::distance_envelope_kernel<int64_t>, dim3(blocks), dim3(64), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::distance_envelope_kernel<int32_t>, dim3(blocks), dim3(64), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_distance_layer(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist) {
-    if (!h || !grid || !dist || n_maps < 1 || !geometry_ok(geom))
+    if (!distance_layer_ok(h, n_maps, geom, grid, dist))
         return fail(PQP_ERR_INVALID, "pqp_distance_layer: bad argument (n_maps >= 1; a map of 2 x 2 to 2^30 cells, resolution > 0)");
-    PQP_HIP(hipSetDevice(h->device));
     const size_t cells = (size_t)n_maps * geom->rows * geom->cols;
-    int rc;
-    if ((rc = h->c_buf[0].ensure(cells)) || (rc = h->c_buf[1].ensure(cells * 4))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, grid, cells, hipMemcpyHostToDevice, h->stream));
-    if ((rc = pqp_distance_layer_device(h, n_maps, geom, h->c_buf[0].as<uint8_t>(), h->c_buf[1].as<float>()))) return rc;
-    PQP_HIP(hipMemcpyAsync(dist, h->c_buf[1].p, cells * 4, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    const uint8_t* d_grid = st.in(grid, cells);
+    float* d_dist = st.out(dist, cells);
+    return st.run([&]() -> int { return pqp_distance_layer_device(h, n_maps, geom, d_grid, d_dist); });
 }
 
 // ---- vehicle footprints against the distance layer (collision_checker.cpp:17-58, car_geometry.cpp:38-72) ----------------------------
@@ -1416,11 +1385,16 @@ int pqp_car_circles(const pqp_car_geometry* c, double* circles) {
     return PQP_OK;
 }
 
+static bool footprint_ok(pqp_handle* h, int batch, int n, int stride, const double* states, const float* dist, const pqp_grid_geometry* geom,
+                         const pqp_car_geometry* car, int mode, const uint8_t* free_out, const int32_t* first_collision) {
+    return h && states && dist && free_out && first_collision && batch >= 1 && n >= 1 && n <= (1 << 30) && stride >= 3 && geometry_ok(geom) &&
+           car_ok(car) && (mode == PQP_FOOTPRINT_CIRCLES || mode == PQP_FOOTPRINT_BOUNDING_FIRST);
+}
+
 int pqp_footprint_check_device(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist,
                                const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
                                int32_t* first_collision, double* margin) {
-    if (!h || !states || !dist || !free_out || !first_collision || batch < 1 || n < 1 || n > (1 << 30) || stride < 3 || !geometry_ok(geom) ||
-        !car_ok(car) || (mode != PQP_FOOTPRINT_CIRCLES && mode != PQP_FOOTPRINT_BOUNDING_FIRST))
+    if (!footprint_ok(h, batch, n, stride, states, dist, geom, car, mode, free_out, first_collision))
         return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument (stride >= 3; a finite car geometry; mode CIRCLES or BOUNDING_FIRST; "
                                      "a map layer of 2 x 2 to 2^30 cells)");
     PQP_HIP(hipSetDevice(h->device));
@@ -1431,301 +1405,241 @@ int pqp_footprint_check_device(pqp_handle* h, int batch, int n, int stride, cons
     a.batch = batch; a.n = n; a.stride = stride; a.states = states; a.n_of = n_of; a.dist = dist; a.map_of = map_of; a.g = *geom;
     for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
     a.free_out = free_out; a.first_collision = first_collision; a.margin = margin;
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    if (mode == PQP_FOOTPRINT_CIRCLES)
-        hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_CIRCLES>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
-    else
-        hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_BOUNDING_FIRST>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    return h->launch_timed([&]() -> int {
+        if (mode == PQP_FOOTPRINT_CIRCLES)
+            hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_CIRCLES>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
+        else
+            hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_BOUNDING_FIRST>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist, int n_maps,
                         const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
                         int32_t* first_collision, double* margin) {
-    if (!h || !states || !dist || !free_out || !first_collision || batch < 1 || n < 1 || n > (1 << 30) || stride < 3 || n_maps < 1 ||
-        !geometry_ok(geom) || !car_ok(car) || (mode != PQP_FOOTPRINT_CIRCLES && mode != PQP_FOOTPRINT_BOUNDING_FIRST))
+    if (!footprint_ok(h, batch, n, stride, states, dist, geom, car, mode, free_out, first_collision) || n_maps < 1)
         return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument");
     if (map_of)
         for (int b = 0; b < batch; ++b)
             if (map_of[b] < 0 || map_of[b] >= n_maps) return fail(PQP_ERR_INVALID, "pqp_footprint_check: map_of outside [0, n_maps)");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_st = (size_t)batch * n * stride * 8, b_of = (size_t)batch * 4, b_map = (size_t)n_maps * geom->rows * geom->cols * 4;
-    const size_t b_free = (size_t)batch * n, b_first = (size_t)batch * 4, b_mg = (size_t)batch * n * 8;
-    const size_t sizes[7] = {b_st, b_of, b_map, b_of, b_free, b_first, b_mg};
-    int rc;
-    for (int k = 0; k < 7; ++k) if ((rc = h->c_buf[k].ensure(sizes[k]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, states, b_st, hipMemcpyHostToDevice, h->stream));
-    if (n_of) PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, n_of, b_of, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, dist, b_map, hipMemcpyHostToDevice, h->stream));
-    if (map_of) PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, map_of, b_of, hipMemcpyHostToDevice, h->stream));
-    if ((rc = pqp_footprint_check_device(h, batch, n, stride, h->c_buf[0].as<double>(), n_of ? h->c_buf[1].as<int32_t>() : nullptr,
-                                         h->c_buf[2].as<float>(), map_of ? h->c_buf[3].as<int32_t>() : nullptr, geom, car, mode,
-                                         h->c_buf[4].as<uint8_t>(), h->c_buf[5].as<int32_t>(), margin ? h->c_buf[6].as<double>() : nullptr)))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(free_out, h->c_buf[4].p, b_free, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(first_collision, h->c_buf[5].p, b_first, hipMemcpyDeviceToHost, h->stream));
-    if (margin) PQP_HIP(hipMemcpyAsync(margin, h->c_buf[6].p, b_mg, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_states = st.in(states, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const float* d_dist = st.in(dist, (size_t)n_maps * geom->rows * geom->cols);
+    const int32_t* d_map_of = st.in(map_of, batch);
+    uint8_t* d_free = st.out(free_out, bn);
+    int32_t* d_first = st.out(first_collision, batch);
+    double* d_margin = margin ? st.out(margin, bn) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_footprint_check_device(h, batch, n, stride, d_states, d_n_of, d_dist, d_map_of, geom, car, mode, d_free, d_first, d_margin);
+    });
 }
 
 // ---- reference states + initial error ----------------------------------------------------------------
+static bool reference_states_ok(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext, const double* max_s,
+                                const double* start, double ds_small, double ds_large, const double* ref, const int32_t* count, const double* init_err) {
+    return h && spline && spline_ext && max_s && ref && count && batch >= 1 && n_max >= 1 && m >= 3 && ds_small > 0.0 && ds_large >= ds_small &&
+           (!init_err || start);
+}
+
 int pqp_reference_states_device(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext,
                                 const double* max_s, const double* start, double ds_small, double ds_large, int dynamic, double* ref,
                                 int32_t* count, double* init_err) {
-    if (!h || !spline || !spline_ext || !max_s || !ref || !count || batch < 1 || n_max < 1 || m < 3 || !(ds_small > 0.0) ||
-        !(ds_large >= ds_small) || (init_err && !start))
+    if (!reference_states_ok(h, batch, n_max, m, spline, spline_ext, max_s, start, ds_small, ds_large, ref, count, init_err))
         return fail(PQP_ERR_INVALID, "pqp_reference_states: bad argument (0 < ds_small <= ds_large: reference_path_impl.cpp:315)");
     PQP_HIP(hipSetDevice(h->device));
     pqp::RefStatesArgs a;
     a.batch = batch; a.n_max = n_max; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.max_s = max_s; a.start = start;
     a.ds_small = ds_small; a.ds_large = ds_large; a.dynamic = dynamic ? 1 : 0; a.ref = ref; a.count = count; a.init_err = init_err;
     a.lx = a.ly = a.ls = a.langle = a.lk = nullptr;
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
     const size_t lds = ((size_t)9 * m + n_max) * 8;
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_reference_states: 9 m + n_max doubles exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::reference_states_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_reference_states: 9 m + n_max doubles exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 // ---- raw reference line -> the smoother QPs' input lists (ReferencePathSmoother::segmentRawReference) ------------------------------
+static bool segment_ok(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext, const double* max_s, double delta_s,
+                       const double* x, const double* y, const double* s, const double* angle, const double* k, const int32_t* count) {
+    return h && spline && spline_ext && max_s && x && y && s && angle && k && count && batch >= 1 && n_max >= 1 && m >= 3 && delta_s > 0.0;
+}
+
 int pqp_segment_raw_reference_device(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext,
                                      const double* max_s, double delta_s, double* x, double* y, double* s, double* angle, double* k,
                                      int32_t* count) {
-    if (!h || !spline || !spline_ext || !max_s || !x || !y || !s || !angle || !k || !count || batch < 1 || n_max < 1 || m < 3 || !(delta_s > 0.0))
+    if (!segment_ok(h, batch, n_max, m, spline, spline_ext, max_s, delta_s, x, y, s, angle, k, count))
         return fail(PQP_ERR_INVALID, "pqp_segment_raw_reference: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     pqp::RefStatesArgs a;
     a.batch = batch; a.n_max = n_max; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.max_s = max_s; a.start = nullptr;
     a.ds_small = delta_s; a.ds_large = delta_s; a.dynamic = 2; a.ref = nullptr; a.count = count; a.init_err = nullptr;
     a.lx = x; a.ly = y; a.ls = s; a.langle = angle; a.lk = k;
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
     const size_t lds = ((size_t)9 * m + n_max) * 8;
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_segment_raw_reference: 9 m + n_max doubles exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::reference_states_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_segment_raw_reference: 9 m + n_max doubles exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_segment_raw_reference(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext, const double* max_s,
                               double delta_s, double* x, double* y, double* s, double* angle, double* k, int32_t* count) {
-    if (!h || !spline || !spline_ext || !max_s || !x || !y || !s || !angle || !k || !count || batch < 1 || n_max < 1 || m < 3)
+    if (!segment_ok(h, batch, n_max, m, spline, spline_ext, max_s, delta_s, x, y, s, angle, k, count))
         return fail(PQP_ERR_INVALID, "pqp_segment_raw_reference: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_spl = (size_t)batch * 9 * m * 8, b_ext = (size_t)batch * 4 * 8, b_s = (size_t)batch * 8;
-    const size_t b_list = (size_t)batch * n_max * 8, b_cnt = (size_t)batch * 4;
-    const size_t sizes[5] = {5 * b_list, b_spl, b_ext, b_s, b_cnt};
-    int rc;
-    for (int j = 0; j < 5; ++j) if ((rc = h->c_buf[j].ensure(sizes[j]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, spline, b_spl, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, spline_ext, b_ext, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, max_s, b_s, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemsetAsync(h->c_buf[0].p, 0, 5 * b_list, h->stream));
-    double* l = h->c_buf[0].as<double>();
     const size_t bn = (size_t)batch * n_max;
-    if ((rc = pqp_segment_raw_reference_device(h, batch, n_max, m, h->c_buf[1].as<double>(), h->c_buf[2].as<double>(), h->c_buf[3].as<double>(),
-                                               delta_s, l, l + bn, l + 2 * bn, l + 3 * bn, l + 4 * bn, h->c_buf[4].as<int32_t>())))
-        return rc;
-    double* outs[5] = {x, y, s, angle, k};
-    for (int j = 0; j < 5; ++j) PQP_HIP(hipMemcpyAsync(outs[j], l + j * bn, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(count, h->c_buf[4].p, b_cnt, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4), *d_max_s = st.in(max_s, batch);
+    double *d_x = st.out(x, bn, 0), *d_y = st.out(y, bn, 0), *d_s = st.out(s, bn, 0), *d_angle = st.out(angle, bn, 0), *d_k = st.out(k, bn, 0);
+    int32_t* d_count = st.out(count, batch);
+    return st.run([&]() -> int { return pqp_segment_raw_reference_device(h, batch, n_max, m, d_spl, d_ext, d_max_s, delta_s, d_x, d_y, d_s, d_angle, d_k, d_count); });
 }
 
 int pqp_reference_states(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext, const double* max_s,
                          const double* start, double ds_small, double ds_large, int dynamic, double* ref, int32_t* count,
                          double* init_err) {
-    if (!h || !spline || !spline_ext || !max_s || !ref || !count || batch < 1 || n_max < 1 || m < 3)
+    if (!reference_states_ok(h, batch, n_max, m, spline, spline_ext, max_s, start, ds_small, ds_large, ref, count, init_err))
         return fail(PQP_ERR_INVALID, "pqp_reference_states: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_spl = (size_t)batch * 9 * m * 8, b_ext = (size_t)batch * 4 * 8, b_s = (size_t)batch * 8, b_st = (size_t)batch * 3 * 8;
-    const size_t b_ref = (size_t)batch * n_max * PQP_REF_STRIDE * 8, b_cnt = (size_t)batch * 4, b_err = (size_t)batch * 2 * 8;
-    const size_t sizes[7] = {b_ref, b_spl, b_ext, b_s, b_st, b_err, b_cnt};
-    int rc;
-    for (int k = 0; k < 7; ++k) if ((rc = h->c_buf[k].ensure(sizes[k]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, spline, b_spl, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, spline_ext, b_ext, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, max_s, b_s, hipMemcpyHostToDevice, h->stream));
-    if (start) PQP_HIP(hipMemcpyAsync(h->c_buf[4].p, start, b_st, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemsetAsync(h->c_buf[0].p, 0, b_ref, h->stream));
-    if ((rc = pqp_reference_states_device(h, batch, n_max, m, h->c_buf[1].as<double>(), h->c_buf[2].as<double>(), h->c_buf[3].as<double>(),
-                                          start ? h->c_buf[4].as<double>() : nullptr, ds_small, ds_large, dynamic, h->c_buf[0].as<double>(),
-                                          h->c_buf[6].as<int32_t>(), (init_err && start) ? h->c_buf[5].as<double>() : nullptr)))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(ref, h->c_buf[0].p, b_ref, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(count, h->c_buf[6].p, b_cnt, hipMemcpyDeviceToHost, h->stream));
-    if (init_err && start) PQP_HIP(hipMemcpyAsync(init_err, h->c_buf[5].p, b_err, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4), *d_max_s = st.in(max_s, batch);
+    const double* d_start = st.in(start, (size_t)batch * 3);
+    double* d_ref = st.out(ref, (size_t)batch * n_max * PQP_REF_STRIDE, 0);
+    int32_t* d_count = st.out(count, batch);
+    double* d_err = init_err ? st.out(init_err, (size_t)batch * 2) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_reference_states_device(h, batch, n_max, m, d_spl, d_ext, d_max_s, d_start, ds_small, ds_large, dynamic, d_ref, d_count, d_err);
+    });
 }
 
 // ---- lateral offsets on a line -> points with chord-length abscissae (tail of ReferencePathSmoother::postSmooth) ---------------------
+static bool offsets_ok(pqp_handle* h, int batch, int m_spline, int m, const double* spline, const double* spline_ext, const double* at_s, const double* l,
+                       const double* x, const double* y, const double* s) {
+    return h && spline && spline_ext && at_s && l && x && y && s && batch >= 1 && m_spline >= 3 && m >= 1;
+}
+
 int pqp_offsets_to_points_device(pqp_handle* h, int batch, int m_spline, int m, const double* spline, const double* spline_ext, const double* at_s,
                                  const double* l, const int32_t* m_of, double* x, double* y, double* s) {
-    if (!h || !spline || !spline_ext || !at_s || !l || !x || !y || !s || batch < 1 || m_spline < 3 || m < 1)
-        return fail(PQP_ERR_INVALID, "pqp_offsets_to_points: bad argument");
+    if (!offsets_ok(h, batch, m_spline, m, spline, spline_ext, at_s, l, x, y, s)) return fail(PQP_ERR_INVALID, "pqp_offsets_to_points: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     pqp::OffsetsArgs a;
     a.batch = batch; a.m_spl = m_spline; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.at_s = at_s; a.l = l; a.m_of = m_of;
     a.x = x; a.y = y; a.s = s;
     const size_t lds = ((size_t)9 * m_spline + 2 * (size_t)m) * 8;
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_offsets_to_points: 9 m_spline + 2 m doubles exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::offsets_to_points_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::offsets_to_points_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::offsets_to_points_kernel, lds, "pqp_offsets_to_points: 9 m_spline + 2 m doubles exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::offsets_to_points_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_offsets_to_points(pqp_handle* h, int batch, int m_spline, int m, const double* spline, const double* spline_ext, const double* at_s,
                           const double* l, const int32_t* m_of, double* x, double* y, double* s) {
-    if (!h || !spline || !spline_ext || !at_s || !l || !x || !y || !s || batch < 1 || m_spline < 3 || m < 1)
-        return fail(PQP_ERR_INVALID, "pqp_offsets_to_points: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_spl = (size_t)batch * 9 * m_spline * 8, b_ext = (size_t)batch * 4 * 8, b_list = (size_t)batch * m * 8, b_n = (size_t)batch * 4;
-    const size_t sizes[6] = {3 * b_list, b_spl, b_ext, b_list, b_list, b_n};
-    int rc;
-    for (int j = 0; j < 6; ++j) if ((rc = h->c_buf[j].ensure(sizes[j]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, spline, b_spl, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, spline_ext, b_ext, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, at_s, b_list, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[4].p, l, b_list, hipMemcpyHostToDevice, h->stream));
-    if (m_of) PQP_HIP(hipMemcpyAsync(h->c_buf[5].p, m_of, b_n, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemsetAsync(h->c_buf[0].p, 0, 3 * b_list, h->stream));
-    double* o = h->c_buf[0].as<double>();
-    const size_t bn = (size_t)batch * m;
-    if ((rc = pqp_offsets_to_points_device(h, batch, m_spline, m, h->c_buf[1].as<double>(), h->c_buf[2].as<double>(), h->c_buf[3].as<double>(),
-                                           h->c_buf[4].as<double>(), m_of ? h->c_buf[5].as<int32_t>() : nullptr, o, o + bn, o + 2 * bn)))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(x, o, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(y, o + bn, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(s, o + 2 * bn, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    if (!offsets_ok(h, batch, m_spline, m, spline, spline_ext, at_s, l, x, y, s)) return fail(PQP_ERR_INVALID, "pqp_offsets_to_points: bad argument");
+    const size_t bm = (size_t)batch * m;
+    Staging st(h);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m_spline), *d_ext = st.in(spline_ext, (size_t)batch * 4);
+    const double *d_at_s = st.in(at_s, bm), *d_l = st.in(l, bm);
+    const int32_t* d_m_of = st.in(m_of, batch);
+    double *d_x = st.out(x, bm, 0), *d_y = st.out(y, bm, 0), *d_s = st.out(s, bm, 0);
+    return st.run([&]() -> int { return pqp_offsets_to_points_device(h, batch, m_spline, m, d_spl, d_ext, d_at_s, d_l, d_m_of, d_x, d_y, d_s); });
 }
 
 // ---- length of the reference line up to the target state (PathOptimizer::setReferencePathLength) ---------------------------------
+static bool reference_length_ok(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length, const double* target,
+                                const double* length_out) {
+    return h && spline && spline_ext && length && target && length_out && batch >= 1 && m >= 3;
+}
+
 int pqp_reference_length_device(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length,
                                 const double* target, double* length_out) {
-    if (!h || !spline || !spline_ext || !length || !target || !length_out || batch < 1 || m < 3)
-        return fail(PQP_ERR_INVALID, "pqp_reference_length: bad argument");
+    if (!reference_length_ok(h, batch, m, spline, spline_ext, length, target, length_out)) return fail(PQP_ERR_INVALID, "pqp_reference_length: bad argument");
     PQP_HIP(hipSetDevice(h->device));
     pqp::RefLengthArgs a;
     a.batch = batch; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.length = length; a.target = target; a.length_out = length_out;
     const size_t lds = (size_t)9 * m * 8;
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_reference_length: 9 m doubles exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::reference_length_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::reference_length_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::reference_length_kernel, lds, "pqp_reference_length: 9 m doubles exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::reference_length_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_reference_length(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length,
                          const double* target, double* length_out) {
-    if (!h || !spline || !spline_ext || !length || !target || !length_out || batch < 1 || m < 3)
-        return fail(PQP_ERR_INVALID, "pqp_reference_length: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_spl = (size_t)batch * 9 * m * 8, b_ext = (size_t)batch * 4 * 8, b_s = (size_t)batch * 8, b_t = (size_t)batch * 3 * 8;
-    const size_t sizes[5] = {b_s, b_spl, b_ext, b_s, b_t};
-    int rc;
-    for (int j = 0; j < 5; ++j) if ((rc = h->c_buf[j].ensure(sizes[j]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, spline, b_spl, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, spline_ext, b_ext, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, length, b_s, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[4].p, target, b_t, hipMemcpyHostToDevice, h->stream));
-    if ((rc = pqp_reference_length_device(h, batch, m, h->c_buf[1].as<double>(), h->c_buf[2].as<double>(), h->c_buf[3].as<double>(),
-                                          h->c_buf[4].as<double>(), h->c_buf[0].as<double>())))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(length_out, h->c_buf[0].p, b_s, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    if (!reference_length_ok(h, batch, m, spline, spline_ext, length, target, length_out)) return fail(PQP_ERR_INVALID, "pqp_reference_length: bad argument");
+    Staging st(h);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4);
+    const double *d_length = st.in(length, batch), *d_target = st.in(target, (size_t)batch * 3);
+    double* d_out = st.out(length_out, batch);
+    return st.run([&]() -> int { return pqp_reference_length_device(h, batch, m, d_spl, d_ext, d_length, d_target, d_out); });
 }
 
 // ---- input points -> dense raw reference line (ReferencePathSmoother::bSpline) --------------------------------------------------
+static bool bspline_ok(pqp_handle* h, int batch, int p_max, int n_max, const double* points, const int32_t* n_points, const double* x, const double* y,
+                       const double* s, const int32_t* count) {
+    return h && points && n_points && x && y && s && count && batch >= 1 && p_max >= 4 && n_max >= 2;
+}
+
 int pqp_bspline_resample_device(pqp_handle* h, int batch, int p_max, int n_max, const double* points, const int32_t* n_points, double* x,
                                 double* y, double* s, int32_t* count) {
-    if (!h || !points || !n_points || !x || !y || !s || !count || batch < 1 || p_max < 4 || n_max < 2)
+    if (!bspline_ok(h, batch, p_max, n_max, points, n_points, x, y, s, count))
         return fail(PQP_ERR_INVALID, "pqp_bspline_resample: bad argument (at least 4 input points: reference_path_smoother.cpp:33)");
     PQP_HIP(hipSetDevice(h->device));
     pqp::BsplineArgs a;
     a.batch = batch; a.p_max = p_max; a.n_max = n_max; a.pts = points; a.n_pts = n_points; a.x = x; a.y = y; a.s = s; a.count = count;
     const size_t lds = ((size_t)3 * p_max + 6 + (size_t)3 * n_max) * 8;
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_bspline_resample: 3 p_max + 3 n_max doubles exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::bspline_resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::bspline_resample_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::bspline_resample_kernel, lds, "pqp_bspline_resample: 3 p_max + 3 n_max doubles exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::bspline_resample_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_bspline_resample(pqp_handle* h, int batch, int p_max, int n_max, const double* points, const int32_t* n_points, double* x, double* y,
                          double* s, int32_t* count) {
-    if (!h || !points || !n_points || !x || !y || !s || !count || batch < 1 || p_max < 4 || n_max < 2)
-        return fail(PQP_ERR_INVALID, "pqp_bspline_resample: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_pts = (size_t)batch * p_max * 2 * 8, b_n = (size_t)batch * 4, b_list = (size_t)batch * n_max * 8;
-    const size_t sizes[4] = {3 * b_list, b_pts, b_n, b_n};
-    int rc;
-    for (int j = 0; j < 4; ++j) if ((rc = h->c_buf[j].ensure(sizes[j]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, points, b_pts, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, n_points, b_n, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemsetAsync(h->c_buf[0].p, 0, 3 * b_list, h->stream));
-    double* l = h->c_buf[0].as<double>();
+    if (!bspline_ok(h, batch, p_max, n_max, points, n_points, x, y, s, count)) return fail(PQP_ERR_INVALID, "pqp_bspline_resample: bad argument");
     const size_t bn = (size_t)batch * n_max;
-    if ((rc = pqp_bspline_resample_device(h, batch, p_max, n_max, h->c_buf[1].as<double>(), h->c_buf[2].as<int32_t>(), l, l + bn, l + 2 * bn,
-                                          h->c_buf[3].as<int32_t>())))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(x, l, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(y, l + bn, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(s, l + 2 * bn, b_list, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(count, h->c_buf[3].p, b_n, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    Staging st(h);
+    const double* d_pts = st.in(points, (size_t)batch * p_max * 2);
+    const int32_t* d_n_pts = st.in(n_points, batch);
+    double *d_x = st.out(x, bn, 0), *d_y = st.out(y, bn, 0), *d_s = st.out(s, bn, 0);
+    int32_t* d_count = st.out(count, batch);
+    return st.run([&]() -> int { return pqp_bspline_resample_device(h, batch, p_max, n_max, d_pts, d_n_pts, d_x, d_y, d_s, d_count); });
 }
 
 // ---- spline fit ---------------------------------------------------------------------------------------
+static bool spline_fit_ok(pqp_handle* h, int batch, int m, const double* s, const double* x, const double* y, const double* spline, const double* spline_ext) {
+    return h && s && x && y && spline && spline_ext && batch >= 1 && m >= 3;
+}
+
 static int spline_fit_impl(pqp_handle* h, int batch, int m, const int32_t* m_of, const double* s, const double* x, const double* y, double* spline,
                            double* spline_ext) {
-    if (!h || !s || !x || !y || !spline || !spline_ext || batch < 1 || m < 3)
-        return fail(PQP_ERR_INVALID, "pqp_spline_fit: bad argument (m >= 3: spline.cpp:164)");
+    if (!spline_fit_ok(h, batch, m, s, x, y, spline, spline_ext)) return fail(PQP_ERR_INVALID, "pqp_spline_fit: bad argument (m >= 3: spline.cpp:164)");
     PQP_HIP(hipSetDevice(h->device));
     pqp::SplineFitArgs a;
     a.m_of = m_of;
     a.batch = batch; a.m = m; a.s = s; a.vx = x; a.vy = y; a.spl = spline; a.spl_ext = spline_ext;
     const size_t lds = (size_t)7 * m * 8;
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_spline_fit: 7 m doubles exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::spline_fit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::spline_fit_kernel, dim3(2 * batch), dim3(64), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::spline_fit_kernel, lds, "pqp_spline_fit: 7 m doubles exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::spline_fit_kernel, dim3(2 * batch), dim3(64), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_spline_fit_device(pqp_handle* h, int batch, int m, const double* s, const double* x, const double* y, double* spline,
@@ -1740,22 +1654,12 @@ int pqp_spline_fit_var_device(pqp_handle* h, int batch, int m_max, const int32_t
 }
 
 int pqp_spline_fit(pqp_handle* h, int batch, int m, const double* s, const double* x, const double* y, double* spline, double* spline_ext) {
-    if (!h || !s || !x || !y || !spline || !spline_ext || batch < 1 || m < 3) return fail(PQP_ERR_INVALID, "pqp_spline_fit: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_in = (size_t)batch * m * 8, b_spl = (size_t)batch * 9 * m * 8, b_ext = (size_t)batch * 4 * 8;
-    const size_t sizes[5] = {b_in, b_in, b_in, b_spl, b_ext};
-    int rc;
-    for (int k = 0; k < 5; ++k) if ((rc = h->c_buf[k].ensure(sizes[k]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, s, b_in, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, x, b_in, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, y, b_in, hipMemcpyHostToDevice, h->stream));
-    if ((rc = pqp_spline_fit_device(h, batch, m, h->c_buf[0].as<double>(), h->c_buf[1].as<double>(), h->c_buf[2].as<double>(),
-                                    h->c_buf[3].as<double>(), h->c_buf[4].as<double>())))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(spline, h->c_buf[3].p, b_spl, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(spline_ext, h->c_buf[4].p, b_ext, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    if (!spline_fit_ok(h, batch, m, s, x, y, spline, spline_ext)) return fail(PQP_ERR_INVALID, "pqp_spline_fit: bad argument");
+    const size_t bm = (size_t)batch * m;
+    Staging st(h);
+    const double *d_s = st.in(s, bm), *d_x = st.in(x, bm), *d_y = st.in(y, bm);
+    double *d_spl = st.out(spline, 9 * bm), *d_ext = st.out(spline_ext, (size_t)batch * 4);
+    return st.run([&]() -> int { return pqp_spline_fit_device(h, batch, m, d_s, d_x, d_y, d_spl, d_ext); });
 }
 
 // ---- layered DP corridor search ------------------------------------------------------------------------
@@ -1764,61 +1668,51 @@ void pqp_dp_default_params(pqp_dp_params* p) {
     p->lateral_range = 10.0; p->longitudinal_spacing = 1.5; p->lateral_spacing = 0.6; p->car_width = 2.0;      // planning_flags.cpp:38-42,10
 }
 
+static bool dp_ok(pqp_handle* h, int batch, int m, int max_layers, const double* spline, const double* spline_ext, const double* length, const double* start,
+                  const float* dist, const pqp_grid_geometry* geom, const pqp_dp_params* prm, const double* layers_s, const double* lb, const double* ub,
+                  const int32_t* count, const double* vehicle_l) {
+    return h && spline && spline_ext && length && start && dist && prm && layers_s && lb && ub && count && vehicle_l && batch >= 1 && m >= 3 &&
+           max_layers >= 2 && geometry_ok(geom) && prm->lateral_spacing > 0.0 && prm->longitudinal_spacing > 0.0 &&
+           !(2.0 * prm->lateral_range / prm->lateral_spacing + 1.0 > 64.0);
+}
+
 int pqp_dp_corridor_device(pqp_handle* h, int batch, int m, int max_layers, const double* spline, const double* spline_ext,
                            const double* length, const double* start, const float* dist, const int32_t* map_of,
                            const pqp_grid_geometry* geom, const pqp_dp_params* prm, double* layers_s, double* lb, double* ub,
                            int32_t* count, double* vehicle_l) {
-    if (!h || !spline || !spline_ext || !length || !start || !dist || !geom || !prm || !layers_s || !lb || !ub || !count || !vehicle_l ||
-        batch < 1 || m < 3 || max_layers < 2 || !geometry_ok(geom) || !(prm->lateral_spacing > 0.0) || !(prm->longitudinal_spacing > 0.0) ||
-        2.0 * prm->lateral_range / prm->lateral_spacing + 1.0 > 64.0)
+    if (!dp_ok(h, batch, m, max_layers, spline, spline_ext, length, start, dist, geom, prm, layers_s, lb, ub, count, vehicle_l))
         return fail(PQP_ERR_INVALID, "pqp_dp_corridor: bad argument (at most 64 lateral samples per layer)");
     PQP_HIP(hipSetDevice(h->device));
     pqp::DpArgs a;
     a.batch = batch; a.m = m; a.max_layers = max_layers; a.spl = spline; a.spl_ext = spline_ext; a.length = length; a.start = start;
     a.dist = dist; a.map_of = map_of; a.g = *geom; a.p = *prm; a.layers_s = layers_s; a.lb = lb; a.ub = ub; a.count = count; a.vehicle_l = vehicle_l;
     const size_t lds = pqp::DpLds{m, max_layers, pqp::dp_lateral_samples(prm->lateral_range, prm->lateral_spacing)}.total_bytes();
-    if (lds > 160 * 1024) return fail(PQP_ERR_CAPACITY, "pqp_dp_corridor: 9 m + 17 max_layers doubles (+ the edge table) exceed one CU's LDS");
-    if (lds > 48 * 1024) PQP_HIP(hipFuncSetAttribute((const void*)pqp::dp_corridor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->next_event_pair();
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(pqp::dp_corridor_kernel, dim3(batch), dim3(pqp::kDpThreads), lds, h->stream, a);
-    PQP_HIP(hipGetLastError());
-    if (!h->capturing) PQP_HIP(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    return PQP_OK;
+    const int rc = lds_opt_in((const void*)pqp::dp_corridor_kernel, lds, "pqp_dp_corridor: 9 m + 17 max_layers doubles (+ the edge table) exceed one CU's LDS");
+    if (rc) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::dp_corridor_kernel, dim3(batch), dim3(pqp::kDpThreads), lds, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
 }
 
 int pqp_dp_corridor(pqp_handle* h, int batch, int m, int max_layers, const double* spline, const double* spline_ext, const double* length,
                     const double* start, const float* dist, int n_maps, const int32_t* map_of, const pqp_grid_geometry* geom,
                     const pqp_dp_params* prm, double* layers_s, double* lb, double* ub, int32_t* count, double* vehicle_l) {
-    if (!h || !spline || !spline_ext || !length || !start || !dist || !geom || !prm || !layers_s || !lb || !ub || !count || !vehicle_l ||
-        batch < 1 || m < 3 || max_layers < 2 || n_maps < 1)
+    if (!dp_ok(h, batch, m, max_layers, spline, spline_ext, length, start, dist, geom, prm, layers_s, lb, ub, count, vehicle_l) || n_maps < 1)
         return fail(PQP_ERR_INVALID, "pqp_dp_corridor: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
-    const size_t b_spl = (size_t)batch * 9 * m * 8, b_ext = (size_t)batch * 4 * 8, b_len = (size_t)batch * 8, b_st = (size_t)batch * 3 * 8;
-    const size_t b_map = (size_t)n_maps * geom->rows * geom->cols * 4, b_of = (size_t)batch * 4, b_out = (size_t)batch * max_layers * 8;
-    const size_t sizes[11] = {b_spl, b_ext, b_len, b_st, b_map, b_of, b_out, b_out, b_out, b_of, b_len};
-    int rc;
-    for (int k = 0; k < 11; ++k) if ((rc = h->c_buf[k].ensure(sizes[k]))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->c_buf[0].p, spline, b_spl, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[1].p, spline_ext, b_ext, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[2].p, length, b_len, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[3].p, start, b_st, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->c_buf[4].p, dist, b_map, hipMemcpyHostToDevice, h->stream));
-    if (map_of) PQP_HIP(hipMemcpyAsync(h->c_buf[5].p, map_of, b_of, hipMemcpyHostToDevice, h->stream));
-    for (int k = 6; k < 9; ++k) PQP_HIP(hipMemsetAsync(h->c_buf[k].p, 0, b_out, h->stream));
-    if ((rc = pqp_dp_corridor_device(h, batch, m, max_layers, h->c_buf[0].as<double>(), h->c_buf[1].as<double>(), h->c_buf[2].as<double>(),
-                                     h->c_buf[3].as<double>(), h->c_buf[4].as<float>(), map_of ? h->c_buf[5].as<int32_t>() : nullptr, geom, prm,
-                                     h->c_buf[6].as<double>(), h->c_buf[7].as<double>(), h->c_buf[8].as<double>(), h->c_buf[9].as<int32_t>(),
-                                     h->c_buf[10].as<double>())))
-        return rc;
-    PQP_HIP(hipMemcpyAsync(layers_s, h->c_buf[6].p, b_out, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(lb, h->c_buf[7].p, b_out, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(ub, h->c_buf[8].p, b_out, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(count, h->c_buf[9].p, b_of, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipMemcpyAsync(vehicle_l, h->c_buf[10].p, b_len, hipMemcpyDeviceToHost, h->stream));
-    PQP_HIP(hipStreamSynchronize(h->stream));
-    return PQP_OK;
+    const size_t bl = (size_t)batch * max_layers;
+    Staging st(h);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4);
+    const double *d_length = st.in(length, batch), *d_start = st.in(start, (size_t)batch * 3);
+    const float* d_dist = st.in(dist, (size_t)n_maps * geom->rows * geom->cols);
+    const int32_t* d_map_of = st.in(map_of, batch);
+    double *d_ls = st.out(layers_s, bl, 0), *d_lb = st.out(lb, bl, 0), *d_ub = st.out(ub, bl, 0);
+    int32_t* d_count = st.out(count, batch);
+    double* d_vl = st.out(vehicle_l, batch);
+    return st.run([&]() -> int {
+        return pqp_dp_corridor_device(h, batch, m, max_layers, d_spl, d_ext, d_length, d_start, d_dist, d_map_of, geom, prm, d_ls, d_lb, d_ub, d_count, d_vl);
+    });
 }
 
 }  // extern "C"

@@ -492,6 +492,24 @@ def test_argument_errors(handle):
     with pytest.raises(capi.PqpError):
         prm = capi.PqpDpParams(10.0, 1.5, 0.1, 2.0)                                                # 201 lateral samples: more than one wavefront
         handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([10.0]), np.zeros((1, 3)), c["dist"], g, prm=prm)
+    # a geometry with negative rows is refused before the host forms size a buffer from it
+    neg = capi.PqpGridGeometry(-1, g.cols, g.resolution, g.length_x, g.length_y, g.pos_x, g.pos_y)
+    with pytest.raises(capi.PqpError, match="pqp error -1:"):
+        handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], neg)
+    with pytest.raises(capi.PqpError, match="pqp error -1:"):
+        handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([10.0]), np.zeros((1, 3)), c["dist"], neg)
+    # a launch refused for its LDS leaves the timing of the previous launch (fresh handle: nothing else in its ring)
+    fresh = capi.Handle(capi.default_params(), device=0, max_batch=1, max_n=8)
+    try:
+        s = np.arange(8.0)[None]
+        fresh.spline_fit(s, s, np.zeros_like(s))
+        ms = fresh.last_kernel_ms()
+        with pytest.raises(capi.PqpError, match="pqp error -4:"):
+            fresh.reference_states(c["tab"][None], c["ext"][None], np.array([10.0]), 20480)        # 9 m + 20480 doubles > 160 KiB
+        assert fresh.last_kernel_ms() == ms
+        assert fresh.kernel_ms_history(1)[0] == np.float32(ms)
+    finally:
+        fresh.close()
     # a batch of one and a line shorter than one step are fine
     ref, count, _ = handle.reference_states(c["tab"][None], c["ext"][None], np.array([0.1]), 8)
     assert count[0] == 1 and ref[0, 0, 0] == 0.0
