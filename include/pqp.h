@@ -513,7 +513,8 @@ int pqp_reference_length(pqp_handle* h, int batch, int m, const double* spline, 
  * point spacing > 10 m / > 5 m / else), sampled at t = 0, 1/length, 2/length, ... while t < 1 and at t = 1 (about one point per
  * metre); s = accumulated chord length.  The spline itself is the third-party tinyspline (not in the reference tree): its clamped
  * knot vector and de Boor evaluation are restated, see oracle/corridor_oracle.py.
- * points [batch][p_max][2], n_points [batch] (fewer than 4: count = 0, the reference's "Few reference points")
+ * points [batch][p_max][2], n_points [batch] (fewer than 4: count = 0, the reference's "Few reference points"; no more points than the
+ * degree: count = 0 as well, tinyspline refuses such a spline and the reference throws)
  *   ->  x, y, s [batch][n_max] = x_list_, y_list_, s_list_;  count [batch] = points the loop produces (when it exceeds n_max only
  * n_max were written).  pqp_spline_fit of (s, x, y) then gives the splines pqp_segment_raw_reference samples. */
 int pqp_bspline_resample_device(pqp_handle* h, int batch, int p_max, int n_max, const double* points, const int32_t* n_points, double* x,

@@ -462,19 +462,23 @@ __global__ void __launch_bounds__(64) bspline_resample_kernel(const BsplineArgs 
         }
         const double average_length = length / (double)(n - 1);
         const int degree = average_length > 10.0 ? 3 : (average_length > 5.0 ? 4 : 5);
-        const int order = degree + 1, n_knots = n + order;
-        const double fac = 1.0 / (double)(n_knots - 2 * degree - 1);
-        for (int i = 0; i < n_knots; ++i) knots[i] = i < order ? 0.0 : (i < n_knots - order ? (double)(i - degree) * fac : 1.0);
-        const double delta_t = 1.0 / length;
         int cnt = 0;
-        double tmp_t = 0.0;
-        while (tmp_t < 1.0 && cnt < (1 << 20)) {
-            if (cnt < a.n_max) t_of[cnt] = tmp_t;
+        // tinyspline refuses a degree that is not below the number of control points (the reference's bSpline throws there): no line, as
+        // for fewer than 4 points - de Boor would read control points that are not there
+        if (n > degree) {
+            const int order = degree + 1, n_knots = n + order;
+            const double fac = 1.0 / (double)(n_knots - 2 * degree - 1);
+            for (int i = 0; i < n_knots; ++i) knots[i] = i < order ? 0.0 : (i < n_knots - order ? (double)(i - degree) * fac : 1.0);
+            const double delta_t = 1.0 / length;
+            double tmp_t = 0.0;
+            while (tmp_t < 1.0 && cnt < (1 << 20)) {
+                if (cnt < a.n_max) t_of[cnt] = tmp_t;
+                cnt += 1;
+                tmp_t += delta_t;
+            }
+            if (cnt < a.n_max) t_of[cnt] = 1.0;
             cnt += 1;
-            tmp_t += delta_t;
         }
-        if (cnt < a.n_max) t_of[cnt] = 1.0;
-        cnt += 1;
         cnt_sh = cnt; deg_sh = degree;
         a.count[qp] = cnt;
     }
@@ -494,7 +498,7 @@ __global__ void __launch_bounds__(64) bspline_resample_kernel(const BsplineArgs 
         a.y[(size_t)qp * a.n_max + i] = oy;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && cnt > 0) {
         double acc = 0.0;
         a.s[(size_t)qp * a.n_max] = 0.0;
         for (int i = 1; i < cnt; ++i) {

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <mutex>
 #include <new>
 #include <string>
 
@@ -299,10 +300,28 @@ struct DevBuf {
 // one CU's LDS on gfx950: the most dynamic LDS a workgroup can have
 constexpr size_t kLdsPerCu = 160 * 1024;
 
-// `bytes` of dynamic LDS for kernel `fn`: PQP_ERR_CAPACITY (message `who`) beyond one CU's LDS, the opt-in beyond the 48 KiB any kernel may use
+// the static LDS of kernel `fn`: its __shared__ variables, padded to the alignment of the dynamic LDS that follows them (the compiler's
+// "LDS Size" remark; 16 bytes for a single int in front of an aligned(16) array).  Looked up once per kernel.
+int static_lds(const void* fn, size_t* out) {
+    static std::mutex mu;
+    static std::vector<std::pair<const void*, size_t>> known;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const auto& k : known)
+        if (k.first == fn) { *out = k.second; return PQP_OK; }
+    hipFuncAttributes fa{};
+    PQP_HIP(hipFuncGetAttributes(&fa, fn));
+    known.emplace_back(fn, fa.sharedSizeBytes);
+    *out = fa.sharedSizeBytes;
+    return PQP_OK;
+}
+
+// `bytes` of dynamic LDS for kernel `fn`: PQP_ERR_CAPACITY (message `who`) when they and the kernel's static LDS exceed one CU's LDS, the
+// opt-in beyond the 48 KiB any kernel may use.  The attribute takes the dynamic bytes alone (the runtime adds the static ones to it).
 int lds_opt_in(const void* fn, size_t bytes, const char* who) {
-    if (bytes > kLdsPerCu) return fail(PQP_ERR_CAPACITY, who);
-    if (bytes > 48 * 1024) PQP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    size_t fixed = 0;
+    if (const int rc = static_lds(fn, &fixed)) return rc;
+    if (bytes > kLdsPerCu - fixed) return fail(PQP_ERR_CAPACITY, who);
+    if (fixed + bytes > 48 * 1024) PQP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return PQP_OK;
 }
 }  // namespace
@@ -1280,8 +1299,10 @@ int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const dou
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
     // a whole scenario's probes in LDS when they fit (9 m + 33 n doubles), tiles of waypoints otherwise: any path length
     a.tile = n;
-    if (pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu) {
-        const long long room = (long long)kLdsPerCu - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
+    size_t fixed = 0;
+    if (const int rc = static_lds((const void*)pqp::corridor_bounds_kernel, &fixed)) return rc;
+    if (pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu - fixed) {
+        const long long room = (long long)(kLdsPerCu - fixed) - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
         if (room < 16 * per_waypoint) return fail(PQP_ERR_CAPACITY, "pqp_corridor_bounds: the line's spline table (9 m doubles) does not leave room for the probes in one CU's LDS");
         a.tile = (int)(room / per_waypoint);
     }

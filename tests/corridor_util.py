@@ -1,4 +1,7 @@
-"""Test helper: scenes for the corridor-bounds step -> oracle objects and the flat ABI arrays."""
+"""Test helper: scenes for the corridor-bounds step -> oracle objects and the flat ABI arrays; spline-table comparisons and the LDS
+budgets of the line-geometry kernels."""
+import os
+
 import numpy as np
 
 import corridor_oracle as K
@@ -18,3 +21,92 @@ def build(seed, n=40, **kw):
         ref[i] = (s, (dx * ddy - dy * ddx) / (dx * dx + dy * dy) ** 1.5, np.arctan2(dy, dx), K.spline_eval(sx, s), K.spline_eval(sy, s))
     tab, ext = K.pack_spline(sx, sy)
     return dict(scene=sc, sx=sx, sy=sy, geom=g, ref=ref, tab=tab, ext=ext, dist=sc["dist"])
+
+
+SPLINE_TOL = 1e-13      # of the largest coefficient of a table row: the device solves the moment equations by a Thomas recurrence of its own (FMA
+                        # contraction allowed), the reference by a row-normalised band LU - same spline, different round-off (measured: < 1e-15)
+
+
+def ref_spline_lib():
+    """the reference's own tk::spline, compiled from where it lies (oracle/_ref, built by oracle/Makefile; travels to the GPU box prebuilt)"""
+    import ctypes as C
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_spline.so")
+    if not os.path.exists(path):
+        return None
+    lib = C.CDLL(path)
+    lib.ref_spline_new.restype = C.c_void_p; lib.ref_spline_new.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+    lib.ref_spline_deriv.restype = C.c_double; lib.ref_spline_deriv.argtypes = [C.c_void_p, C.c_int, C.c_double]
+    lib.ref_spline_eval.restype = C.c_double; lib.ref_spline_eval.argtypes = [C.c_void_p, C.c_double]
+    lib.ref_spline_free.argtypes = [C.c_void_p]
+    return lib
+
+
+def rows_close(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    scale = max(float(np.abs(want).max()), 1e-300)
+    err = float(np.abs(got - want).max()) / scale
+    assert err <= SPLINE_TOL, (what, err)
+    return err
+
+
+def tab_close(tab, ext, want_tab, want_ext=None):
+    """a device spline table against a restatement / golden one: knots and values exact, coefficient rows to SPLINE_TOL of the row's largest"""
+    assert np.array_equal(np.asarray(tab)[[0, 1, 5]], np.asarray(want_tab)[[0, 1, 5]])
+    for r in (2, 3, 4, 6, 7, 8):
+        rows_close(tab[r], want_tab[r], ("row", r))
+    if want_ext is not None:
+        assert np.abs(np.asarray(ext) - np.asarray(want_ext)).max() <= SPLINE_TOL * max(1.0, float(np.abs(want_ext).max()))
+
+
+# ---- LDS budgets of the line-geometry kernels (pqp_corridor_kernels.inc, launchers in pqp_kernels.hip) -----------------------------
+LDS_PER_CU = 160 * 1024
+# static LDS of each kernel as the compiler reports it ("LDS Size"): its __shared__ variables padded to the 16-byte alignment of the
+# dynamic array behind them.  The launchers count it against LDS_PER_CU (tests/test_kernel_resources.py pins these numbers).
+STATIC_LDS = {"spline_fit_kernel": 0, "reference_states_kernel": 16, "reference_length_kernel": 0, "offsets_to_points_kernel": 0,
+              "bspline_resample_kernel": 16, "dp_corridor_kernel": 0, "corridor_bounds_kernel": 16}
+
+
+def dp_lateral_samples(rng=10.0, spacing=0.6):
+    nlat, c = 0, -rng
+    while c <= rng and nlat < 64:
+        c += spacing
+        nlat += 1
+    return nlat
+
+
+def dp_lds_bytes(m, lmax, nlat):
+    """DpLds::total_bytes()"""
+    parent = 9 * m + lmax + 2 * 64 * 2 + 8 + lmax + 64 + 8 * lmax + 33 * nlat + 2 * nlat * nlat
+    return parent * 8 + ((lmax * nlat + 7) // 8) * 8 + lmax * 4
+
+
+def dynamic_lds(kernel, **a):
+    """dynamic LDS bytes the launcher of `kernel` asks for"""
+    if kernel == "spline_fit_kernel":
+        return 7 * a["m"] * 8
+    if kernel == "reference_states_kernel":
+        return (9 * a["m"] + a["n_max"]) * 8
+    if kernel == "reference_length_kernel":
+        return 9 * a["m"] * 8
+    if kernel == "offsets_to_points_kernel":
+        return (9 * a["m_spline"] + 2 * a["m"]) * 8
+    if kernel == "bspline_resample_kernel":
+        return (3 * a["p_max"] + 6 + 3 * a["n_max"]) * 8
+    if kernel == "dp_corridor_kernel":
+        return dp_lds_bytes(a["m"], a["max_layers"], a["nlat"])
+    raise KeyError(kernel)
+
+
+def fits(kernel, **a):
+    return STATIC_LDS[kernel] + dynamic_lds(kernel, **a) <= LDS_PER_CU
+
+
+def largest(kernel, var, **a):
+    """the largest value of argument `var` (the others fixed) whose launch fits one CU's LDS"""
+    lo, hi = 1, 1
+    while fits(kernel, **{**a, var: hi}):
+        lo, hi = hi, hi * 2
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(kernel, **{**a, var: mid}) else (lo, mid)
+    return lo

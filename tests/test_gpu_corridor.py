@@ -9,6 +9,7 @@ import pytest
 
 import corridor_oracle as K
 import corridor_util as U
+from corridor_util import SPLINE_TOL, ref_spline_lib as _ref_spline_lib, rows_close as _rows_close, tab_close as _tab_close
 from path_optimizer_2_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -269,41 +270,6 @@ def test_pipeline_spline_to_path_on_the_device(handle):
         solved += 1
     assert solved >= 2
     hp.close()
-
-
-SPLINE_TOL = 1e-13      # of the largest coefficient of a table row: the device solves the moment equations by a Thomas recurrence of its own (FMA
-                        # contraction allowed), the reference by a row-normalised band LU - same spline, different round-off (measured: < 1e-15)
-
-
-def _ref_spline_lib():
-    """the reference's own tk::spline, compiled from where it lies (oracle/_ref, built by oracle/Makefile; travels to the GPU box prebuilt)"""
-    import ctypes as C
-    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_spline.so")
-    if not os.path.exists(path):
-        return None
-    lib = C.CDLL(path)
-    lib.ref_spline_new.restype = C.c_void_p; lib.ref_spline_new.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-    lib.ref_spline_deriv.restype = C.c_double; lib.ref_spline_deriv.argtypes = [C.c_void_p, C.c_int, C.c_double]
-    lib.ref_spline_eval.restype = C.c_double; lib.ref_spline_eval.argtypes = [C.c_void_p, C.c_double]
-    lib.ref_spline_free.argtypes = [C.c_void_p]
-    return lib
-
-
-def _rows_close(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    scale = max(float(np.abs(want).max()), 1e-300)
-    err = float(np.abs(got - want).max()) / scale
-    assert err <= SPLINE_TOL, (what, err)
-    return err
-
-
-def _tab_close(tab, ext, want_tab, want_ext=None):
-    """a device spline table against a restatement / golden one: knots and values exact, coefficient rows to SPLINE_TOL of the row's largest"""
-    assert np.array_equal(np.asarray(tab)[[0, 1, 5]], np.asarray(want_tab)[[0, 1, 5]])
-    for r in (2, 3, 4, 6, 7, 8):
-        _rows_close(tab[r], want_tab[r], ("row", r))
-    if want_ext is not None:
-        assert np.abs(np.asarray(ext) - np.asarray(want_ext)).max() <= SPLINE_TOL * max(1.0, float(np.abs(want_ext).max()))
 
 
 def test_spline_fit_matches_the_reference_build(handle):

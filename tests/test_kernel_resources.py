@@ -86,3 +86,11 @@ def test_exact_smoother_kernels_live_in_registers(kernels, name, tag):
 def test_kernels_around_the_qps_do_not_use_scratch(kernels):
     for name in ("corridor_bounds_kernel", "reference_states_kernel", "spline_fit_kernel", "dp_corridor_kernel"):
         assert _find(kernels, name)["ScratchSize"] == 0, name
+
+
+@pytest.mark.parametrize("name", sorted(__import__("corridor_util").STATIC_LDS))
+def test_static_lds_of_the_line_kernels(kernels, name):
+    """the static LDS (__shared__ variables, padded to the 16-byte alignment of the dynamic array behind them) of the line-geometry kernels:
+    lds_opt_in() counts it against one CU's 160 KiB, and tests/test_gpu_line_geometry.py sizes its edge cases from these numbers"""
+    import corridor_util as U
+    assert _find(kernels, name)["LDS Size"] == U.STATIC_LDS[name]
