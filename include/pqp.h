@@ -22,6 +22,7 @@
  *   ReferencePathSmoother::postSmooth src/reference_path_smoother/reference_path_smoother.cpp:526-636 (QP part) pqp_post_smooth
  *   ReferencePath::updateBounds -> ReferencePathImpl::updateBoundsImproved
  *                                     src/data_struct/reference_path.cpp:61, reference_path_impl.cpp:177-312    pqp_corridor_bounds
+ *   ReferencePath::updateBoundsOnInputStates    reference_path.cpp:89-91, reference_path_impl.cpp:118-175   pqp_corridor_bounds_on_states
  *   ReferencePathImpl::buildReferenceFromSpline  reference_path_impl.cpp:314-338, PathOptimizer::processInitState path_optimizer.cpp:73-85
  *                                                                                                         pqp_reference_states
  *   ReferencePathSmoother::postSmooth (tail)    reference_path_smoother.cpp:559-573                         pqp_offsets_to_points
@@ -454,6 +455,24 @@ int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const dou
 int pqp_corridor_bounds(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* spline,
                         const double* spline_ext, const float* dist, int n_maps, const int32_t* map_of, const pqp_grid_geometry* geom,
                         const pqp_corridor_params* prm, double* bounds, int32_t* n_valid);
+/* ReferencePath::updateBoundsOnInputStates (src/data_struct/reference_path.cpp:89-91 -> reference_path_impl.cpp:118-175): the corridor of
+ * every waypoint recomputed from the states of a path that was already solved - the second pass PathOptimizer::optimizePath has commented
+ * out (src/path_optimizer.cpp:147-151).  The front and rear circle centres of waypoint i sit at
+ *   ref.xy + (L - L cos(d_heading_i)) (cos, sin)(ref.heading)        L = prm->front_length / prm->rear_length
+ * and are projected on the line from the flag's length (Newton guess s + L, :139-150); the centre circle, the clearance walk and the
+ * blocked rule are pqp_corridor_bounds' (the first waypoint whose front or rear interval is empty ends the scenario; its row is written).
+ *   states [batch][n][stride]  d_heading at offset 4 (stride >= 5; stride = PQP_OUT_STRIDE reads a path solve's or the chain's `out` in place)
+ *   n_of   [batch]             states of each scenario, e.g. the previous pass's n_valid or the chain's n_out (<= n: CHECK_LE, :119), or NULL
+ *   ref, spline, spline_ext, dist, map_of, geom, prm, bounds, n_valid   as for pqp_corridor_bounds (ref = the reference states)
+ * A d_heading that is not finite gives NaN front / rear rows for that waypoint (never blocked), as the reference's arithmetic does.
+ * The host form also refuses (PQP_ERR_INVALID, nothing launched) a map_of value outside [0, n_maps) and an n_of outside [0, n]; with n_of its
+ * rows beyond a scenario's states come back as zeros. */
+int pqp_corridor_bounds_on_states_device(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* states,
+                                         int stride, const double* spline, const double* spline_ext, const float* dist, const int32_t* map_of,
+                                         const pqp_grid_geometry* geom, const pqp_corridor_params* prm, double* bounds, int32_t* n_valid);
+int pqp_corridor_bounds_on_states(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* states, int stride,
+                                  const double* spline, const double* spline_ext, const float* dist, int n_maps, const int32_t* map_of,
+                                  const pqp_grid_geometry* geom, const pqp_corridor_params* prm, double* bounds, int32_t* n_valid);
 
 /* ---- the obstacle distance layer from an occupancy grid --------------------------------------------------------------------------
  * cv::distanceTransform(obstacle, dist, CV_DIST_L2, CV_DIST_MASK_PRECISE); dist *= resolution   (src/test/demo.cpp:104-113), for n_maps maps
@@ -597,6 +616,19 @@ typedef enum pqp_chain_stage {
     PQP_CHAIN_CAPACITY = 9               /* a line needs more points / samples / layers / waypoints than pqp_chain_config allows */
 } pqp_chain_stage;
 typedef enum pqp_smoothing_method { PQP_SMOOTHING_TENSION2 = 0, PQP_SMOOTHING_TENSION = 1 } pqp_smoothing_method;
+/* what follows the first path QP (pqp_chain_config.second_pass)
+ *   RELINEARISE       PathOptimizer::optimizePath as it stands (path_optimizer.cpp:141-156): BaseSolver::solve, then
+ *                     updateProblemFormulationAndSolve around its result - one pqp_path_solve with passes = 1
+ *   BOUNDS_ON_STATES  the lines commented out there (:147-151): BaseSolver::solve (passes = 0); a scenario whose solve is not SOLVED stops
+ *                     at PQP_CHAIN_PATH_QP_FAILED ("Pre solving failed!"); the others get pqp_corridor_bounds_on_states on that path
+ *                     (n_of = its waypoint count) and a second cold solve (passes = 0) around it (lin = its l, d_heading, k) on the new
+ *                     bounds.  The post_solver's waypoint count is left undefined by the commented reference (it keeps the first count
+ *                     after the bounds were cut): here it is the new n_valid, which is also n_out; below 2 the stage is PQP_CHAIN_BLOCKED.
+ *                     isBlocked() holds when either bounds pass was blocked (blocked_bound_ is never reset, reference_path_impl.cpp:167,222).
+ *                     iters counts both solves.  Refused (PQP_ERR_INVALID, nothing enqueued) on a path handle with
+ *                     rough_constraints_far_away: the reference's post_solver would see s = 0 on every input state (getOptimizedPath never
+ *                     sets s, base_solver.cpp:266-289), so its precise-planning count would differ from the one computed here. */
+typedef enum pqp_second_pass { PQP_SECOND_PASS_RELINEARISE = 0, PQP_SECOND_PASS_BOUNDS_ON_STATES = 1 } pqp_second_pass;
 typedef struct pqp_chain_config {
     int32_t raw_max, sample_max, layer_max, n_max;   /* capacities per scenario: raw-line points (bSpline, about one per metre), 1 m samples of
                                                         the smoother QP, DP layers (1.5 m), waypoints of the path.  No upper bounds (the reference
@@ -612,6 +644,7 @@ typedef struct pqp_chain_config {
                                             reference_path_smoother.cpp:18-29).  TENSION: the clearance of the raw line's samples is looked up on
                                             the device (tension_smoother.cpp:168); on a smoother handle without polish = 1 (the reference's ADMM on the 3n-variable
                                             formulation) sample_max is bounded by what one CU's LDS holds (about 190) */
+    int32_t second_pass;                 /* PQP_SECOND_PASS_RELINEARISE (pqp_second_pass) */
 } pqp_chain_config;
 void pqp_chain_default_config(pqp_chain_config* c);
 int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_config* cfg, int batch, int p_max, const double* points,

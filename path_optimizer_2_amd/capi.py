@@ -51,7 +51,7 @@ class PqpDpParams(C.Structure):
 class PqpChainConfig(C.Structure):
     _fields_ = [("raw_max", C.c_int32), ("sample_max", C.c_int32), ("layer_max", C.c_int32), ("n_max", C.c_int32), ("output_spacing", C.c_double),
                 ("dynamic_segmentation", C.c_int32), ("max_steering_angle", C.c_double), ("smoothed_length_margin", C.c_double),
-                ("corridor", PqpCorridorParams), ("dp", PqpDpParams), ("smoothing_method", C.c_int32)]
+                ("corridor", PqpCorridorParams), ("dp", PqpDpParams), ("smoothing_method", C.c_int32), ("second_pass", C.c_int32)]
 
 
 class PqpCarGeometry(C.Structure):
@@ -73,6 +73,7 @@ EXPORTS = [
     "pqp_path_assemble_device", "pqp_path_solve", "pqp_path_solve_device", "pqp_path_solve_var_device", "pqp_path_solve_var", "pqp_path_get_solution",
     "pqp_last_kernel_ms", "pqp_last_path_kernel", "pqp_stream_batch_default", "pqp_kernel_ms_history", "pqp_smooth_tension2", "pqp_smooth_tension2_device", "pqp_smooth_tension", "pqp_smooth_tension_device",
     "pqp_post_smooth", "pqp_post_smooth_device", "pqp_corridor_default_params", "pqp_corridor_bounds", "pqp_corridor_bounds_device",
+    "pqp_corridor_bounds_on_states", "pqp_corridor_bounds_on_states_device",
     "pqp_reference_states", "pqp_reference_states_device", "pqp_spline_fit", "pqp_spline_fit_device", "pqp_dp_default_params",
     "pqp_dp_corridor", "pqp_dp_corridor_device", "pqp_segment_raw_reference", "pqp_segment_raw_reference_device", "pqp_bspline_resample", "pqp_bspline_resample_device", "pqp_reference_length", "pqp_reference_length_device", "pqp_offsets_to_points", "pqp_offsets_to_points_device",
     "pqp_distance_layer", "pqp_distance_layer_device",
@@ -164,6 +165,10 @@ def load_library(path=None, with_torch=None):
                                                C.POINTER(PqpCorridorParams), vp, vp]
     lib.pqp_corridor_bounds.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry),
                                         C.POINTER(PqpCorridorParams), vp, vp]
+    lib.pqp_corridor_bounds_on_states_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(PqpGridGeometry),
+                                                         C.POINTER(PqpCorridorParams), vp, vp]
+    lib.pqp_corridor_bounds_on_states.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry),
+                                                  C.POINTER(PqpCorridorParams), vp, vp]
     for name in ("pqp_reference_states", "pqp_reference_states_device"):
         getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp]
     for name in ("pqp_offsets_to_points", "pqp_offsets_to_points_device"):
@@ -263,6 +268,7 @@ def path_interval(value, n):
 
 KERNEL_NONE, KERNEL_LANE_PER_WAYPOINT, KERNEL_LANE_PER_QP = 0, 1, 2      # pqp_last_path_kernel
 SMOOTHING_TENSION2, SMOOTHING_TENSION = 0, 1
+SECOND_PASS_RELINEARISE, SECOND_PASS_BOUNDS_ON_STATES = 0, 1      # pqp_second_pass (pqp_chain_config.second_pass)
 
 
 class MultiHandle:
@@ -421,7 +427,9 @@ class Handle:
                       car=None, footprint_mode=FOOTPRINT_CIRCLES):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
-        smoother QPs run on (None: this one).  Returns dict(out [B][n_max][7], n_out, status, stage, iters).
+        smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
+        runs the reference's commented-out second pass (corridor bounds on the first path's states, then a solve around it) in place of the
+        re-linearised one.  Returns dict(out [B][n_max][7], n_out, status, stage, iters).
         check_footprint: pqp_footprint_check_device right behind the chain on the same stream, on its `out` (stride 7) and `n_out` and the same
         layers (car: PqpCarGeometry, None: the reference's; footprint_mode: pqp_footprint_mode); adds free [B][n_max], first_collision [B]
         and margin [B][n_max] to the dict."""
@@ -613,6 +621,28 @@ class Handle:
         no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
         self._check(self.lib.pqp_corridor_bounds(self._h, B, n, m, _ptr(ref), _ptr(no), _ptr(spline), _ptr(spline_ext), _ptr(dist_cm), dist_cm.shape[0],
                                                  _ptr(mo), C.byref(geom), C.byref(prm), _ptr(bounds), _ptr(n_valid)))
+        return bounds, n_valid
+
+    def corridor_bounds_on_states(self, ref, states, spline, spline_ext, dist, geom, map_of=None, prm=None, n_of=None):
+        """pqp_corridor_bounds_on_states (host arrays): ReferencePath::updateBoundsOnInputStates.  ref [B][n][5] (the reference states),
+        states [B][n][stride >= 5] with d_heading at offset 4 (a solve's `out` as it is), n_of [B] states per scenario (<= n) or None;
+        spline, spline_ext, dist, geom, map_of, prm as for corridor_bounds.  Returns (bounds [B][n][6], n_valid [B])."""
+        ref = np.ascontiguousarray(ref, dtype=np.float64)
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        spline = np.ascontiguousarray(spline, dtype=np.float64)
+        spline_ext = np.ascontiguousarray(spline_ext, dtype=np.float64)
+        dist_cm = _column_major(dist, np.float32)
+        B, n = ref.shape[0], ref.shape[1]
+        if states.ndim != 3 or states.shape[:2] != (B, n):
+            raise ValueError(f"states must be [{B}][{n}][stride], got {states.shape}")
+        m = spline.shape[2]
+        bounds = np.zeros((B, n, 6))
+        n_valid = np.zeros(B, dtype=np.int32)
+        mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
+        prm = prm or self.corridor_params()
+        no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
+        self._check(self.lib.pqp_corridor_bounds_on_states(self._h, B, n, m, _ptr(ref), _ptr(no), _ptr(states), states.shape[2], _ptr(spline), _ptr(spline_ext),
+                                                           _ptr(dist_cm), dist_cm.shape[0], _ptr(mo), C.byref(geom), C.byref(prm), _ptr(bounds), _ptr(n_valid)))
         return bounds, n_valid
 
     def sizes(self, n, s=None):

@@ -16,6 +16,10 @@
 //   buildReferenceFromSpline(ds / 2, ds)         :119, reference_path_impl.cpp:314-338 pqp_reference_states_device
 //   updateBounds                                 :120, reference_path_impl.cpp:177-312 pqp_corridor_bounds_device
 //   optimizePath                                 :124-161                              pqp_path_solve_var_device (passes = 1)
+//   ... or, second_pass = PQP_SECOND_PASS_BOUNDS_ON_STATES, the lines commented out there (:141-151):
+//   BaseSolver::solve                            :142                                  pqp_path_solve_var_device (passes = 0)
+//   updateBoundsOnInputStates                    :147, reference_path_impl.cpp:118-175 pqp_corridor_bounds_on_states_device, chain_scal_kernel
+//   BaseSolver post_solver(..., *final_path).solve   :149-150                          chain_lin_kernel, pqp_path_solve_var_device (passes = 0, lin)
 namespace pqp {
 
 struct ChainScalArgs {
@@ -69,6 +73,34 @@ __global__ void chain_status_kernel(const ChainStatusArgs a) {
     a.n_out[b] = (stage == PQP_CHAIN_OK) ? a.n_valid[b] : 0;
 }
 
+// second_pass = BOUNDS_ON_STATES, between the bounds on the first path and the second solve: the post_solver's linearisation point (its
+// input_path_ = the first path: l, d_heading, k at offsets 3, 4, 5 of `out`, base_solver.cpp:266-289) and its waypoint count - the new
+// n_valid, or 0 where the first solve is not SOLVED ("Pre solving failed!": no second pass, path_optimizer.cpp:142-146)
+__global__ void chain_lin_kernel(int batch, int n_max, const double* __restrict__ out, const int32_t* __restrict__ status1,
+                                 const int32_t* __restrict__ n_valid2, double* __restrict__ lin, int32_t* __restrict__ n_of2) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= batch * n_max) return;
+    const double* o = out + (size_t)idx * PQP_OUT_STRIDE;
+    double* l = lin + (size_t)idx * PQP_LIN_STRIDE;
+    l[0] = o[3]; l[1] = o[4]; l[2] = o[5];
+    const int b = idx / n_max;
+    if (idx - b * n_max == 0) n_of2[b] = status1[b] == PQP_STATUS_SOLVED ? n_valid2[b] : 0;
+}
+
+// ... and after the second solve: what chain_status_kernel reads as the path QP's waypoint count and status - the first solve's where it
+// failed, the second's otherwise - and the iterations of both solves (a QP either solve skipped counts 0 there)
+__global__ void chain_second_pass_kernel(int batch, const int32_t* __restrict__ status1, const int32_t* __restrict__ n_valid1,
+                                         const int32_t* __restrict__ status2, const int32_t* __restrict__ n_valid2, const int32_t* __restrict__ iters1,
+                                         const int32_t* __restrict__ iters2, int32_t* __restrict__ status, int32_t* __restrict__ n_valid,
+                                         int32_t* __restrict__ iters) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const bool first_ok = status1[b] == PQP_STATUS_SOLVED;
+    status[b] = first_ok ? status2[b] : status1[b];
+    n_valid[b] = first_ok ? n_valid2[b] : n_valid1[b];
+    if (iters) iters[b] = iters1[b] + iters2[b];
+}
+
 // Map::getObstacleDistance at the points of the raw line: the clearance input of the TensionSmoother QP (tension_smoother.cpp:168;
 // src/tools/Map.cpp:16-22).  One thread per point; the layer (<= 2 MB) is L2-resident.
 __global__ void clearance_kernel(int batch, int n, const int32_t* __restrict__ n_of, const double* __restrict__ x, const double* __restrict__ y,
@@ -99,6 +131,9 @@ struct ChainWs {
         *ps, *fin_tab, *fin_ext, *fin_len, *max_s, *ref, *err, *bounds, *scal;
     int32_t *raw_count, *raw_fit, *sample_count, *sample_fit, *sm_status, *sm_iters, *layer_count, *layer_fit, *ps_status, *ps_iters, *ref_count, *ref_fit,
         *n_valid, *qp_status;
+    // second_pass = BOUNDS_ON_STATES only
+    double* lin;
+    int32_t *n_valid2, *n_of2, *qp_status2, *iters1, *iters2, *n_valid_out, *status_out;
 };
 }  // namespace
 
@@ -112,6 +147,7 @@ void pqp_chain_default_config(pqp_chain_config* c) {
     c->max_steering_angle = 35.0 * 3.14159265358979323846 / 180.0;      // :22
     c->smoothed_length_margin = 3.0;               // tension_smoother.cpp:40
     c->smoothing_method = PQP_SMOOTHING_TENSION2;  // planning_flags.cpp:27
+    c->second_pass = PQP_SECOND_PASS_RELINEARISE;  // path_optimizer.cpp:150 as it stands
     pqp_corridor_default_params(&c->corridor);
     pqp_dp_default_params(&c->dp);
 }
@@ -149,7 +185,9 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
     const size_t B = (size_t)batch;
     const size_t nd = B * (3 * R + 9 * R + 4 + 1 + 6 * S + 3 * S + 9 * S + 4 + 1 + 3 * L + 1 + L + 3 * L + 9 * L + 4 + 1 + 1 + (size_t)N * 5 + 2 + (size_t)N * 6 + 6);
     const size_t ni = B * 14;
-    if ((rc = h->chain_d.ensure(nd * 8)) || (rc = h->chain_i.ensure(ni * 4))) return rc;
+    const bool second = cfg.second_pass == PQP_SECOND_PASS_BOUNDS_ON_STATES;
+    const size_t nd2 = second ? B * (size_t)N * 3 : 0, ni2 = second ? B * 7 : 0;          // (behind the workspace of the plain chain)
+    if ((rc = h->chain_d.ensure((nd + nd2) * 8)) || (rc = h->chain_i.ensure((ni + ni2) * 4))) return rc;
     ChainWs w;
     {
         double* p = h->chain_d.as<double>();
@@ -165,6 +203,11 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
         w.raw_count = takei(); w.raw_fit = takei(); w.sample_count = takei(); w.sample_fit = takei(); w.sm_status = takei(); w.sm_iters = takei();
         w.layer_count = takei(); w.layer_fit = takei(); w.ps_status = takei(); w.ps_iters = takei(); w.ref_count = takei(); w.ref_fit = takei();
         w.n_valid = takei(); w.qp_status = takei();
+        w.lin = nullptr; w.n_valid2 = w.n_of2 = w.qp_status2 = w.iters1 = w.iters2 = w.n_valid_out = w.status_out = nullptr;
+        if (second) {
+            w.lin = take((size_t)N * 3);
+            w.n_valid2 = takei(); w.n_of2 = takei(); w.qp_status2 = takei(); w.iters1 = takei(); w.iters2 = takei(); w.n_valid_out = takei(); w.status_out = takei();
+        }
     }
     const dim3 gb((batch + 255) / 256), tb(256);
     auto clamp = [&](const int32_t* in, int lo, int hi, int32_t* o) {
@@ -211,8 +254,33 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
     pqp::ChainScalArgs sa{batch, N, w.ref, w.ref_fit, w.n_valid, w.err, target, start_k, cfg.max_steering_angle, w.scal};
     hipLaunchKernelGGL(pqp::chain_scal_kernel, gb, tb, 0, h->stream, sa);
     // ---- PathOptimizer::optimizePath ---------------------------------------------------------------------------------------------------
-    if ((rc = pqp_path_solve_var_device(h, batch, N, w.n_valid, w.ref, nullptr, w.bounds, w.scal, /*passes=*/1, 0, out, w.qp_status, iters, nullptr))) return rc;
-    pqp::ChainStatusArgs st{batch, N, R, S, L, cfg.smoothing_method == PQP_SMOOTHING_TENSION ? 4 : 3, n_points, w.raw_count, w.sample_count, w.sm_status, w.layer_count, w.ps_status, w.ref_count, w.n_valid, w.qp_status,
+    const int32_t *qp_n = w.n_valid, *qp_st = w.qp_status;          // what chain_status_kernel reads
+    if (!second) {
+        if ((rc = pqp_path_solve_var_device(h, batch, N, w.n_valid, w.ref, nullptr, w.bounds, w.scal, /*passes=*/1, 0, out, w.qp_status, iters, nullptr))) return rc;
+    } else {
+        // solver.solve(final_path) (:142), cold
+        if ((rc = pqp_path_solve_var_device(h, batch, N, w.n_valid, w.ref, nullptr, w.bounds, w.scal, /*passes=*/0, 0, out, w.qp_status, w.iters1, nullptr))) return rc;
+        // reference_path_->updateBoundsOnInputStates(*grid_map_, *final_path) (:147) on the first path's states (its n_valid of them).  The
+        // bounds of the first pass are no longer read: the new ones take their place
+        if ((rc = pqp_corridor_bounds_on_states_device(h, batch, N, L, w.ref, w.n_valid, out, PQP_OUT_STRIDE, w.fin_tab, w.fin_ext, dist, map_of, geom,
+                                                       &cfg.corridor, w.bounds, w.n_valid2))) return rc;
+        // the post_solver reads isBlocked() again: with count = the reference states before either cut, n_valid2 < count holds when either
+        // pass was blocked (n_valid2 <= n_valid <= count), which is blocked_bound_ never being reset (reference_path_impl.cpp:167,222)
+        pqp::ChainScalArgs sa2{batch, N, w.ref, w.ref_fit, w.n_valid2, w.err, target, start_k, cfg.max_steering_angle, w.scal};
+        hipLaunchKernelGGL(pqp::chain_scal_kernel, gb, tb, 0, h->stream, sa2);
+        hipLaunchKernelGGL(pqp::chain_lin_kernel, dim3((batch * N + 255) / 256), tb, 0, h->stream, batch, N, (const double*)out, (const int32_t*)w.qp_status,
+                           (const int32_t*)w.n_valid2, w.lin, w.n_of2);
+        PQP_HIP(hipGetLastError());
+        // BaseSolver post_solver(*reference_path_, *vehicle_state_, *final_path); post_solver.solve(final_path) (:149-150): a cold solve
+        // around the first path, on the new bounds and the new n_valid waypoints (a scenario that keeps fewer than 2 is left alone: BLOCKED)
+        if ((rc = pqp_path_solve_var_device(h, batch, N, w.n_of2, w.ref, w.lin, w.bounds, w.scal, /*passes=*/0, 0, out, w.qp_status2, w.iters2, nullptr))) return rc;
+        hipLaunchKernelGGL(pqp::chain_second_pass_kernel, gb, tb, 0, h->stream, batch, (const int32_t*)w.qp_status, (const int32_t*)w.n_valid,
+                           (const int32_t*)w.qp_status2, (const int32_t*)w.n_valid2, (const int32_t*)w.iters1, (const int32_t*)w.iters2, w.status_out,
+                           w.n_valid_out, iters);
+        PQP_HIP(hipGetLastError());
+        qp_n = w.n_valid_out; qp_st = w.status_out;
+    }
+    pqp::ChainStatusArgs st{batch, N, R, S, L, cfg.smoothing_method == PQP_SMOOTHING_TENSION ? 4 : 3, n_points, w.raw_count, w.sample_count, w.sm_status, w.layer_count, w.ps_status, w.ref_count, qp_n, qp_st,
                             w.err, stage ? stage : w.ref_fit /* scratch */, status, n_out};
     hipLaunchKernelGGL(pqp::chain_status_kernel, gb, tb, 0, h->stream, st);
     PQP_HIP(hipGetLastError());
@@ -233,7 +301,7 @@ static std::vector<unsigned char> chain_key(pqp_handle* h, pqp_handle* hs, const
     for (int i = 0; i < n_ptrs; ++i) put(&ptrs[i], sizeof(void*));
     // (the structs field by field where they have padding: raw bytes of padding are not part of the value)
     put_int(cfg.raw_max); put_int(cfg.sample_max); put_int(cfg.layer_max); put_int(cfg.n_max); put(&cfg.output_spacing, 8); put_int(cfg.dynamic_segmentation);
-    put(&cfg.max_steering_angle, 8); put(&cfg.smoothed_length_margin, 8); put_int(cfg.smoothing_method);
+    put(&cfg.max_steering_angle, 8); put(&cfg.smoothed_length_margin, 8); put_int(cfg.smoothing_method); put_int(cfg.second_pass);
     pqp_corridor_params cp; std::memset(&cp, 0, sizeof(cp)); pqp_dp_params dp; std::memset(&dp, 0, sizeof(dp)); pqp_grid_geometry gg; std::memset(&gg, 0, sizeof(gg));
     // (copy member-wise into zeroed storage: assignment of the whole struct may copy padding, field copies do not matter here because the
     //  structs below are compared as bytes only after this same normalisation on both sides)
@@ -261,6 +329,12 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
     const int R = cfg.raw_max, S = cfg.sample_max, L = cfg.layer_max, N = cfg.n_max;
     if (cfg.smoothing_method != PQP_SMOOTHING_TENSION2 && cfg.smoothing_method != PQP_SMOOTHING_TENSION)
         return fail(PQP_ERR_INVALID, "pqp_optimize_path: smoothing_method is neither TENSION2 nor TENSION (\"No such smoother!\", reference_path_smoother.cpp:25-28)");
+    if (cfg.second_pass != PQP_SECOND_PASS_RELINEARISE && cfg.second_pass != PQP_SECOND_PASS_BOUNDS_ON_STATES)
+        return fail(PQP_ERR_INVALID, "pqp_optimize_path: second_pass is neither RELINEARISE nor BOUNDS_ON_STATES");
+    // (the reference's post_solver would see s = 0 on every input state - getOptimizedPath never sets s, base_solver.cpp:266-289 - and so
+    //  another precise-planning count than the one the path solve computes from the reference states: pqp.h, pqp_second_pass)
+    if (cfg.second_pass == PQP_SECOND_PASS_BOUNDS_ON_STATES && h->prm.rough_constraints_far_away)
+        return fail(PQP_ERR_INVALID, "pqp_optimize_path: second_pass = BOUNDS_ON_STATES with rough_constraints_far_away on the path handle");
     // (no upper bounds here - the reference has none: every step below checks what it can hold, the smoother QPs and the path QP of any size go
     //  to the kernels that keep their state in HBM; what remains are the steps that stage a line's spline table in a CU's LDS, ~2000 knots)
     if (R < 8 || S < 4 || L < 4 || N < 2) return fail(PQP_ERR_CAPACITY, "pqp_optimize_path: capacities out of range (raw_max >= 8, sample_max >= 4, layer_max >= 4, n_max >= 2)");
@@ -281,7 +355,7 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
         // Only a body whose path solve ran on the lane-per-waypoint kernel touches the ticket counter (the graph resets it and leaves it at
         // ticket_after) and counts a solve launch; a body that went to path_stream_kernel leaves both alone - plain pqp_path_solve* calls on the
         // handle between two replays keep their counter
-        if (e.lane_launch) { h->ticket_next = e.ticket_after; h->solves += 1; }
+        if (e.lane_launch) { h->ticket_next = e.ticket_after; h->solves += e.lane_launches; }
         h->last_path_kernel = e.path_kernel;         // (pqp_last_path_kernel: the kernel the replayed body's path solve runs on)
         // no timing events inside a graph: pqp_last_kernel_ms / pqp_kernel_ms_history have nothing newer than the last plain launch to report
         h->timed = false; hs->timed = false;
@@ -337,6 +411,7 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
     g->exec = exec;
     g->path_kernel = h->last_path_kernel;
     g->lane_launch = h->solves != solves_before;     // the body's path solve ran on the lane-per-waypoint kernel (ticket counter, launch parity)
+    g->lane_launches = h->solves - solves_before;    // (two with second_pass = BOUNDS_ON_STATES)
     g->ticket_after = h->ticket_next;
     h->solves = solves_before;                       // (the capture counted a launch that only happens now)
     const int rl = launch(g->exec);

@@ -356,7 +356,7 @@ struct pqp_handle {
     // mode - no timing events, the path solve resets its ticket counter inside the graph
     bool capturing = false;
     int opt_chain_graph = 0;
-    struct ChainGraph { std::vector<unsigned char> key; hipGraphExec_t exec = nullptr; bool failed = false; bool lane_launch = false; int path_kernel = 0; unsigned long long ticket_after = 0; };
+    struct ChainGraph { std::vector<unsigned char> key; hipGraphExec_t exec = nullptr; bool failed = false; bool lane_launch = false; long long lane_launches = 0; int path_kernel = 0; unsigned long long ticket_after = 0; };
     std::vector<ChainGraph> chain_graphs;
     int warm_batch = 0, warm_n = 0;
     bool warm_stored = false;                   // the last solve wrote its final iterate to wx / wy / wye
@@ -1288,6 +1288,25 @@ static bool corridor_ok(pqp_handle* h, int batch, int n, int m, const double* re
            prm->delta_s > 0.0 && prm->smaller_ds > 0.0;
 }
 
+// the waypoints kernel `fn` (corridor_bounds_kernel / states_bounds_kernel) holds in LDS at a time: a whole scenario's probes when they fit
+// (9 m + 33 n doubles), tiles of waypoints otherwise: any path length.  Sets *lds to the dynamic LDS of that tile and opts in to it.
+static int corridor_tile(const void* fn, int m, int n, int* tile, size_t* lds, const char* who) {
+    *tile = n;
+    size_t fixed = 0;
+    if (const int rc = static_lds(fn, &fixed)) return rc;
+    if (pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu - fixed) {
+        const long long room = (long long)(kLdsPerCu - fixed) - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
+        if (room < 16 * per_waypoint) return fail(PQP_ERR_CAPACITY, std::string(who) + ": the line's spline table (9 m doubles) does not leave room for the probes in one CU's LDS");
+        *tile = (int)(room / per_waypoint);
+    }
+    *lds = pqp::CorridorLds{m, *tile}.total_bytes();
+    return lds_opt_in(fn, *lds, (std::string(who) + ": scenario too large for one CU's LDS (about 9 m + 31 n doubles)").c_str());
+}
+
+// the sample loops are strided; 512 lanes per scenario keep the most gathers in flight per CU (measured at batch 1024 x n = 80: 1024 lanes
+// 142 us - two scenarios per CU -, 512: 121, 256: 120, 128: 146)
+constexpr int kCorridorThreads = 512;
+
 int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* spline,
                                const double* spline_ext, const float* dist, const int32_t* map_of, const pqp_grid_geometry* geom,
                                const pqp_corridor_params* prm, double* bounds, int32_t* n_valid) {
@@ -1297,22 +1316,10 @@ int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const dou
     pqp::CorridorArgs a;
     a.batch = batch; a.n = n; a.m = m; a.ref = ref; a.spl = spline; a.spl_ext = spline_ext; a.dist = dist; a.map_of = map_of; a.n_of = n_of;
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
-    // a whole scenario's probes in LDS when they fit (9 m + 33 n doubles), tiles of waypoints otherwise: any path length
-    a.tile = n;
-    size_t fixed = 0;
-    if (const int rc = static_lds((const void*)pqp::corridor_bounds_kernel, &fixed)) return rc;
-    if (pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu - fixed) {
-        const long long room = (long long)(kLdsPerCu - fixed) - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
-        if (room < 16 * per_waypoint) return fail(PQP_ERR_CAPACITY, "pqp_corridor_bounds: the line's spline table (9 m doubles) does not leave room for the probes in one CU's LDS");
-        a.tile = (int)(room / per_waypoint);
-    }
-    const size_t lds = pqp::CorridorLds{m, a.tile}.total_bytes();
-    const int rc = lds_opt_in((const void*)pqp::corridor_bounds_kernel, lds, "pqp_corridor_bounds: scenario too large for one CU's LDS (about 9 m + 31 n doubles)");
-    if (rc) return rc;
-    const int threads = 512;         // the sample loops are strided; 512 lanes per scenario keep the most gathers in flight per CU (measured at batch
-                                     // 1024 x n = 80: 1024 lanes 142 us - two scenarios per CU -, 512: 121, 256: 120, 128: 146)
+    size_t lds = 0;
+    if (const int rc = corridor_tile((const void*)pqp::corridor_bounds_kernel, m, n, &a.tile, &lds, "pqp_corridor_bounds")) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::corridor_bounds_kernel, dim3(batch), dim3(threads), lds, h->stream, a);
+        hipLaunchKernelGGL(pqp::corridor_bounds_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1333,6 +1340,57 @@ int pqp_corridor_bounds(pqp_handle* h, int batch, int n, int m, const double* re
     double* d_bounds = st.out(bounds, bn * PQP_BOUNDS_STRIDE);
     int32_t* d_n_valid = st.out(n_valid, batch);
     return st.run([&]() -> int { return pqp_corridor_bounds_device(h, batch, n, m, d_ref, d_n_of, d_spl, d_ext, d_dist, d_map_of, geom, prm, d_bounds, d_n_valid); });
+}
+
+// ---- corridor bounds on the states of a solved path (ReferencePathImpl::updateBoundsOnInputStates) ----------------------------------
+static bool corridor_states_ok(pqp_handle* h, int batch, int n, int m, const double* ref, const double* states, int stride, const double* spline,
+                               const double* spline_ext, const float* dist, const pqp_grid_geometry* geom, const pqp_corridor_params* prm,
+                               const double* bounds, const int32_t* n_valid) {
+    return corridor_ok(h, batch, n, m, ref, spline, spline_ext, dist, geom, prm, bounds, n_valid) && states && stride >= 5;
+}
+
+int pqp_corridor_bounds_on_states_device(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* states,
+                                         int stride, const double* spline, const double* spline_ext, const float* dist, const int32_t* map_of,
+                                         const pqp_grid_geometry* geom, const pqp_corridor_params* prm, double* bounds, int32_t* n_valid) {
+    if (!corridor_states_ok(h, batch, n, m, ref, states, stride, spline, spline_ext, dist, geom, prm, bounds, n_valid))
+        return fail(PQP_ERR_INVALID, "pqp_corridor_bounds_on_states: bad argument (stride >= 5; m >= 3 knots; a map layer of 2 x 2 to 2^30 cells)");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::CorridorArgs a;
+    a.batch = batch; a.n = n; a.m = m; a.ref = ref; a.spl = spline; a.spl_ext = spline_ext; a.dist = dist; a.map_of = map_of; a.n_of = n_of;
+    a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
+    size_t lds = 0;
+    if (const int rc = corridor_tile((const void*)pqp::states_bounds_kernel, m, n, &a.tile, &lds, "pqp_corridor_bounds_on_states")) return rc;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::states_bounds_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a, states, stride);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_corridor_bounds_on_states(pqp_handle* h, int batch, int n, int m, const double* ref, const int32_t* n_of, const double* states, int stride,
+                                  const double* spline, const double* spline_ext, const float* dist, int n_maps, const int32_t* map_of,
+                                  const pqp_grid_geometry* geom, const pqp_corridor_params* prm, double* bounds, int32_t* n_valid) {
+    if (!corridor_states_ok(h, batch, n, m, ref, states, stride, spline, spline_ext, dist, geom, prm, bounds, n_valid) || n_maps < 1)
+        return fail(PQP_ERR_INVALID, "pqp_corridor_bounds_on_states: bad argument");
+    if (map_of)
+        for (int b = 0; b < batch; ++b)
+            if (map_of[b] < 0 || map_of[b] >= n_maps) return fail(PQP_ERR_INVALID, "pqp_corridor_bounds_on_states: map_of outside [0, n_maps)");
+    if (n_of)       // CHECK_LE(input_sl_states.size(), reference_states_.size()) (reference_path_impl.cpp:119)
+        for (int b = 0; b < batch; ++b)
+            if (n_of[b] < 0 || n_of[b] > n) return fail(PQP_ERR_INVALID, "pqp_corridor_bounds_on_states: n_of outside [0, n] (more states than reference states)");
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_ref = st.in(ref, bn * PQP_REF_STRIDE);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const double* d_states = st.in(states, bn * stride);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4);
+    const float* d_dist = st.in(dist, (size_t)n_maps * geom->rows * geom->cols);
+    const int32_t* d_map_of = st.in(map_of, batch);
+    double* d_bounds = st.out(bounds, bn * PQP_BOUNDS_STRIDE, n_of ? 0 : -1);      // (rows beyond a scenario's states are not written)
+    int32_t* d_n_valid = st.out(n_valid, batch);
+    return st.run([&]() -> int {
+        return pqp_corridor_bounds_on_states_device(h, batch, n, m, d_ref, d_n_of, d_states, stride, d_spl, d_ext, d_dist, d_map_of, geom, prm, d_bounds, d_n_valid);
+    });
 }
 
 // ---- the obstacle distance layer from an occupancy grid (src/test/demo.cpp:104-113) ------------------------------------------------
