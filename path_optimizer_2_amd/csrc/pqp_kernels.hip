@@ -20,6 +20,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "pqp_defaults.hpp"
 #include "pqp_path_lane.hpp"
@@ -429,6 +430,44 @@ class Staging {
     Back back_[pqp_handle::kStage];
 };
 }  // namespace
+
+// PQP_OPT_CARRY_CYCLES for an exact smoother kernel (slot 0: TensionSmoother, 1: postSmooth): the active set every scenario ended with is kept
+// on the handle; a solve of the shape of the previous one (and the buffer still where it was) starts from it (carry = 1)
+static int sm_carry_slot(pqp_handle* h, int slot, int batch, int n, signed char*& act_io, int& carry) {
+    act_io = nullptr;
+    carry = 0;
+    if (!h->opt_carry) return PQP_OK;
+    const void* before = h->sm_act[slot].p;
+    int rc;
+    if ((rc = h->sm_act[slot].ensure((size_t)batch * n))) return rc;
+    act_io = h->sm_act[slot].as<signed char>();
+    carry = (h->sm_act_batch[slot] == batch && h->sm_act_n[slot] == n && before == h->sm_act[slot].p) ? 1 : 0;
+    h->sm_act_batch[slot] = batch; h->sm_act_n[slot] = n;
+    return PQP_OK;
+}
+
+// One launch of an exact smoother kernel (tension_exact_kernel / post_exact_kernel) on n elements per scenario: launch(K, ws) with K = the fewest
+// chunks of 64 per lane that hold them (SmRegs<K>), or K = 0 beyond 1024 with `arrays` workspace arrays per scenario in HBM (SmHbm, ws).
+// (twelve / sixteen per lane: the lane state no longer fits the registers - S2 1.8 / 3.3 KB of scratch per lane - but lines that long are rare,
+//  a point per metre of reference line, and the recursion down the lanes, not the spills, is what their time goes to)
+template <class F>
+static int sm_exact_launch(pqp_handle* h, int batch, int n, int arrays, F&& launch) {
+    int rc;
+    if (n > 1024 && (rc = h->b_pband.ensure((size_t)batch * arrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
+    double* ws = n > 1024 ? h->b_pband.as<double>() : nullptr;
+    return h->launch_timed([&]() -> int {
+        if (n <= 64) launch(std::integral_constant<int, 1>(), ws);
+        else if (n <= 128) launch(std::integral_constant<int, 2>(), ws);
+        else if (n <= 256) launch(std::integral_constant<int, 4>(), ws);
+        else if (n <= 384) launch(std::integral_constant<int, 6>(), ws);
+        else if (n <= 512) launch(std::integral_constant<int, 8>(), ws);
+        else if (n <= 768) launch(std::integral_constant<int, 12>(), ws);
+        else if (n <= 1024) launch(std::integral_constant<int, 16>(), ws);
+        else launch(std::integral_constant<int, 0>(), ws);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
 
 extern "C" {
 
@@ -1121,31 +1160,13 @@ static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n
         // exact optima asked for (or the only kernel that holds the QP): the box QP in the lateral shifts alone, one wavefront per scenario (tension_exact_kernel)
         if (!status) return fail(PQP_ERR_INVALID, "pqp_smooth_tension: status is null");
         const double wk = h->prm.cartesian_curvature_weight, wdk = h->prm.cartesian_curvature_rate_weight, wdev = h->prm.cartesian_deviation_weight, tol = h->prm.polish_tol;
-        // PQP_OPT_CARRY_CYCLES: the active set every line ended with is kept on the handle; a solve of the shape of the previous one starts from it
-        signed char* act_io = nullptr;
-        int carry = 0;
-        if (h->opt_carry) {
-            const void* before = h->sm_act[0].p;
-            if ((rc = h->sm_act[0].ensure((size_t)batch * n))) return rc;
-            act_io = h->sm_act[0].as<signed char>();
-            carry = (h->sm_act_batch[0] == batch && h->sm_act_n[0] == n && before == h->sm_act[0].p) ? 1 : 0;
-            h->sm_act_batch[0] = batch; h->sm_act_n[0] = n;
-        }
-        // any line longer than 1024 points (the reference has no cap: tension_smoother.cpp:49-100): the same kernel with its arrays in HBM (SmHbm)
-        if (n > 1024 && (rc = h->b_pband.ensure((size_t)batch * pqp::kTensionExactArrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
-        return h->launch_timed([&]() -> int {
-            if (n <= 64) hipLaunchKernelGGL(pqp::tension_exact_kernel<1>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            else if (n <= 128) hipLaunchKernelGGL(pqp::tension_exact_kernel<2>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            else if (n <= 256) hipLaunchKernelGGL(pqp::tension_exact_kernel<4>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            else if (n <= 384) hipLaunchKernelGGL(pqp::tension_exact_kernel<6>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            else if (n <= 512) hipLaunchKernelGGL(pqp::tension_exact_kernel<8>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            // (twelve / sixteen points per lane: the lane state no longer fits the registers - 1.8 / 3.3 KB of scratch per lane - but lines that long are
-            //  rare, a point per metre of reference line, and the recursion down the lanes, not the spills, is what their time goes to)
-            else if (n <= 768) hipLaunchKernelGGL(pqp::tension_exact_kernel<12>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            else if (n <= 1024) hipLaunchKernelGGL(pqp::tension_exact_kernel<16>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, nullptr);
-            else hipLaunchKernelGGL(pqp::tension_exact_kernel<0>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk, wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, h->b_pband.as<double>());
-            PQP_HIP(hipGetLastError());
-            return PQP_OK;
+        signed char* act_io;
+        int carry;
+        if ((rc = sm_carry_slot(h, 0, batch, n, act_io, carry))) return rc;
+        // (any line longer than 1024 points - the reference has no cap: tension_smoother.cpp:49-100 - runs with its arrays in HBM)
+        return sm_exact_launch(h, batch, n, pqp::kTensionExactArrays, [&](auto K, double* ws) {
+            hipLaunchKernelGGL(pqp::tension_exact_kernel<K>, dim3(batch), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance, wk, wdk,
+                               wdev, tol, out_x, out_y, out_s, status, iters, info, act_io, carry, ws);
         });
     }
     if ((rc = sm_alloc(h, SM_TENSION, batch, n))) return rc;
@@ -1188,28 +1209,13 @@ static int post_smooth_impl(pqp_handle* h, int batch, int m, const int32_t* m_of
         // exact optima asked for: the box QP in the offsets alone, one wavefront per scenario (post_exact_kernel)
         if (!status) return fail(PQP_ERR_INVALID, "pqp_post_smooth: status is null");
         const double tol = h->prm.polish_tol;
-        signed char* act_io = nullptr;          // PQP_OPT_CARRY_CYCLES, as in smooth_tension_impl
-        int carry = 0;
-        if (h->opt_carry) {
-            const void* before = h->sm_act[1].p;
-            if ((rc = h->sm_act[1].ensure((size_t)batch * m))) return rc;
-            act_io = h->sm_act[1].as<signed char>();
-            carry = (h->sm_act_batch[1] == batch && h->sm_act_n[1] == m && before == h->sm_act[1].p) ? 1 : 0;
-            h->sm_act_batch[1] = batch; h->sm_act_n[1] = m;
-        }
-        // any corridor longer than 1024 layers (reference_path_smoother.cpp:526-580 has no cap): the same kernel with its arrays in HBM (SmHbm)
-        if (m > 1024 && (rc = h->b_pband.ensure((size_t)batch * pqp::kPostExactArrays * (64 * (((size_t)m + 63) / 64)) * 8))) return rc;
-        return h->launch_timed([&]() -> int {
-            if (m <= 64) hipLaunchKernelGGL(pqp::post_exact_kernel<1>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else if (m <= 128) hipLaunchKernelGGL(pqp::post_exact_kernel<2>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else if (m <= 256) hipLaunchKernelGGL(pqp::post_exact_kernel<4>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else if (m <= 384) hipLaunchKernelGGL(pqp::post_exact_kernel<6>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else if (m <= 512) hipLaunchKernelGGL(pqp::post_exact_kernel<8>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else if (m <= 768) hipLaunchKernelGGL(pqp::post_exact_kernel<12>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else if (m <= 1024) hipLaunchKernelGGL(pqp::post_exact_kernel<16>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, nullptr);
-            else hipLaunchKernelGGL(pqp::post_exact_kernel<0>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status, iters, info, act_io, carry, h->b_pband.as<double>());
-            PQP_HIP(hipGetLastError());
-            return PQP_OK;
+        signed char* act_io;
+        int carry;
+        if ((rc = sm_carry_slot(h, 1, batch, m, act_io, carry))) return rc;
+        // (any corridor longer than 1024 layers - reference_path_smoother.cpp:526-580 has no cap - runs with its arrays in HBM)
+        return sm_exact_launch(h, batch, m, pqp::kPostExactArrays, [&](auto K, double* ws) {
+            hipLaunchKernelGGL(pqp::post_exact_kernel<K>, dim3(batch), dim3(64), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l, tol, out_l, status,
+                               iters, info, act_io, carry, ws);
         });
     }
     if ((rc = sm_alloc(h, SM_POST, batch, m))) return rc;

@@ -386,19 +386,22 @@ struct SmRegs {
     __device__ __forceinline__ int chunks() const { return K; }
     template <class A> __device__ __forceinline__ void bind(A&, int) const {}
     __device__ __forceinline__ void sync() const {}
-    // element i + e (e = -3 .. 3) of an array; 0 beyond the ends.  (Run with every lane enabled.)
-    __device__ __forceinline__ double at(const Vec& v, int k, int e) const {
-        const int src = lane + e;
-        const double same = __shfl(v[k], src & 63);
-        const double nxt = k + 1 < K ? __shfl(v[k + 1 < K ? k + 1 : k], src & 63) : 0.0;
-        const double prv = k > 0 ? __shfl(v[k > 0 ? k - 1 : k], src & 63) : 0.0;
-        return src > 63 ? nxt : (src < 0 ? prv : same);
+    // element i + E (E = -3 .. 3) of an array; 0 beyond the ends.  E = +1, +2, -1, -2: one shuffle and one lane read.  (Run with every lane enabled.)
+    template <int E> __device__ __forceinline__ double at(const Vec& v, int k) const {
+        static_assert(E != 0 && E >= -3 && E <= 3, "neighbours up to three away");
+        const int kn = k + 1 < K ? k + 1 : k, kp = k > 0 ? k - 1 : k;
+        if constexpr (E == 1) { const double t = __shfl_down(v[k], 1); const double w = k + 1 < K ? readlane_f64(v[kn], 0) : 0.0; return lane == 63 ? w : t; }
+        if constexpr (E == 2) { const double t = __shfl_down(v[k], 2); const double w = k + 1 < K ? __shfl(v[kn], (lane + 2) & 63) : 0.0; return lane >= 62 ? w : t; }
+        if constexpr (E == -1) { const double t = __shfl_up(v[k], 1); const double w = k > 0 ? readlane_f64(v[kp], 63) : 0.0; return lane == 0 ? w : t; }
+        if constexpr (E == -2) { const double t = __shfl_up(v[k], 2); const double w = k > 0 ? __shfl(v[kp], (lane + 62) & 63) : 0.0; return lane < 2 ? w : t; }
+        if constexpr (E == 3 || E == -3) {
+            const int src = lane + E;
+            const double same = __shfl(v[k], src & 63);
+            const double nxt = k + 1 < K ? __shfl(v[kn], src & 63) : 0.0;
+            const double prv = k > 0 ? __shfl(v[kp], src & 63) : 0.0;
+            return src > 63 ? nxt : (src < 0 ? prv : same);
+        }
     }
-    // the same for e = +1, +2, -1, -2 with one shuffle and one lane read
-    __device__ __forceinline__ double nx1(const Vec& v, int k) const { const double t = __shfl_down(v[k], 1); const double w = k + 1 < K ? readlane_f64(v[k + 1 < K ? k + 1 : k], 0) : 0.0; return lane == 63 ? w : t; }
-    __device__ __forceinline__ double nx2(const Vec& v, int k) const { const double t = __shfl_down(v[k], 2); const double w = k + 1 < K ? __shfl(v[k + 1 < K ? k + 1 : k], (lane + 2) & 63) : 0.0; return lane >= 62 ? w : t; }
-    __device__ __forceinline__ double pv1(const Vec& v, int k) const { const double t = __shfl_up(v[k], 1); const double w = k > 0 ? readlane_f64(v[k > 0 ? k - 1 : k], 63) : 0.0; return lane == 0 ? w : t; }
-    __device__ __forceinline__ double pv2(const Vec& v, int k) const { const double t = __shfl_up(v[k], 2); const double w = k > 0 ? __shfl(v[k > 0 ? k - 1 : k], (lane + 62) & 63) : 0.0; return lane < 2 ? w : t; }
 };
 struct SmHbm {
     static constexpr bool kHbm = true;
@@ -413,16 +416,177 @@ struct SmHbm {
     __device__ __forceinline__ int chunks() const { return kc; }
     __device__ __forceinline__ void bind(Vec& v, int slot) const { v.p = base + (size_t)slot * npad + lane; }
     __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ double at(const Vec& v, int k, int e) const { const int i = lane + 64 * k + e; return (i >= 0 && i < npad) ? v.p[64 * k + e] : 0.0; }
-    __device__ __forceinline__ double nx1(const Vec& v, int k) const { return at(v, k, 1); }
-    __device__ __forceinline__ double nx2(const Vec& v, int k) const { return at(v, k, 2); }
-    __device__ __forceinline__ double pv1(const Vec& v, int k) const { return at(v, k, -1); }
-    __device__ __forceinline__ double pv2(const Vec& v, int k) const { return at(v, k, -2); }
+    template <int E> __device__ __forceinline__ double at(const Vec& v, int k) const { const int i = lane + 64 * k + E; return (i >= 0 && i < npad) ? v.p[64 * k + E] : 0.0; }
 };
 template <int K> struct SmStoreOf { typedef SmRegs<K> type; };
 template <> struct SmStoreOf<0> { typedef SmHbm type; };
 // arrays of the workspace (SmHbm): doubles per element
 constexpr int kPostExactArrays = 25, kTensionExactArrays = 44;
+
+// ---- what the exact kernels of S3 (BW = 2: pentadiagonal) and S2 (BW = 3: heptadiagonal, a linear term) share ---------------------------
+// A symmetric band is held as its diagonal p, the sub-diagonals q, r, t (H[i+1][i], H[i+2][i], H[i+3][i]) and the same shifted to row i
+// (q_m1 = H[i][i-1], r_m2 = H[i][i-2], t_m3 = H[i][i-3]); t and t_m3 only for BW = 3.  The sums keep the order each kernel had on its own.
+// (H x + lin)_i, lin only with kLin
+template <int BW, bool kLin, class St, class Vec = typename St::Vec>
+__device__ __forceinline__ double band_gradient(const St& st, int k, const Vec& x, const Vec& p, const Vec& q, const Vec& r, const Vec& t, const Vec& q_m1,
+                                                const Vec& r_m2, const Vec& t_m3, const Vec& lin) {
+    double g = p[k] * x[k];
+    if constexpr (kLin) g = lin[k] + g;
+    g += q[k] * st.template at<1>(x, k);
+    g += r[k] * st.template at<2>(x, k);
+    if constexpr (BW == 3) g += t[k] * st.template at<3>(x, k);
+    g += q_m1[k] * st.template at<-1>(x, k);
+    g += r_m2[k] * st.template at<-2>(x, k);
+    if constexpr (BW == 3) g += t_m3[k] * st.template at<-3>(x, k);
+    return g;
+}
+
+// LDL^T of the band with diagonal pm and sub-diagonals qm, rm, tm (tm only for BW = 3), forward and back substitution: x (written, not read) =
+// the solution on the first nq elements, 0 beyond.  The recursion runs down the lanes through v_readlane, a chunk at a time.  L's columns and z: slots slot .. slot + BW.
+template <int BW, class St, class Vec = typename St::Vec>
+__device__ __forceinline__ void band_ldl_solve(const St& st, int nq, const Vec& pm, const Vec& qm, const Vec& rm, const Vec& tm, const Vec& rhs, Vec& x,
+                                               int slot) {
+    static_assert(BW == 2 || BW == 3, "penta- or heptadiagonal");
+    const int KC = st.chunks(), lane = st.lane;
+    Vec l1, l2, l3, z;
+    st.bind(l1, slot); st.bind(l2, slot + 1); st.bind(z, slot + BW);
+    if constexpr (BW == 3) st.bind(l3, slot + 2);
+    {
+        double d1 = 0.0, d2 = 0.0, d3 = 0.0;           // d_{i-1}, d_{i-2}, d_{i-3}
+        double a1 = 0.0;                               // l1_{i-1}
+        double b1 = 0.0, b2 = 0.0;                     // l2_{i-1}, l2_{i-2}
+        double c1 = 0.0, c2 = 0.0, c3 = 0.0;           // l3_{i-1}, l3_{i-2}, l3_{i-3}
+        double y1 = 0.0, y2 = 0.0, y3 = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const double pk = pm[k], qk = qm[k], rk = rm[k], bk = rhs[k];
+            double tk = 0.0;
+            if constexpr (BW == 3) tk = tm[k];
+            double l1k = 0.0, l2k = 0.0, l3k = 0.0, zk = 0.0;
+            const int cnt = nq - 64 * k < 64 ? nq - 64 * k : 64;
+            for (int l = 0; l < cnt; ++l) {
+                const double pi = readlane_f64(pk, l), qi = readlane_f64(qk, l), ri = readlane_f64(rk, l), bi = readlane_f64(bk, l);
+                double di = pi - a1 * a1 * d1 - b2 * b2 * d2, l1n = qi - b1 * a1 * d1, l2n = ri, yi = bi - a1 * y1 - b2 * y2, ti = 0.0;
+                if constexpr (BW == 3) { ti = readlane_f64(tk, l); di -= c3 * c3 * d3; l1n -= c2 * b2 * d2; l2n -= c1 * a1 * d1; yi -= c3 * y3; }
+                const double inv = rcp(di);
+                const double l1i = l1n * inv, l2i = l2n * inv, l3i = ti * inv;
+                // (selects, not a branch around four moves: two scalar branches per step cost more than eight v_cndmask - +6 % at 80 points, +23 % at 200)
+                { const bool me = lane == l; l1k = me ? l1i : l1k; l2k = me ? l2i : l2k; l3k = me ? l3i : l3k; zk = me ? yi * inv : zk; }
+                d3 = d2; d2 = d1; d1 = di;
+                a1 = l1i;
+                b2 = b1; b1 = l2i;
+                c3 = c2; c2 = c1; c1 = l3i;
+                y3 = y2; y2 = y1; y1 = yi;
+            }
+            l1[k] = l1k; l2[k] = l2k; z[k] = zk;
+            if constexpr (BW == 3) l3[k] = l3k;
+        }
+    }
+    {
+        double x1 = 0.0, x2 = 0.0, x3 = 0.0;
+#pragma unroll
+        for (int k = KC - 1; k >= 0; --k) {
+            const double zk = z[k], l1k = l1[k], l2k = l2[k];
+            double l3k = 0.0;
+            if constexpr (BW == 3) l3k = l3[k];
+            double xk = 0.0;
+            const int cnt = nq - 64 * k < 64 ? nq - 64 * k : 64;
+            for (int l = cnt - 1; l >= 0; --l) {
+                double xi = readlane_f64(zk, l) - readlane_f64(l1k, l) * x1 - readlane_f64(l2k, l) * x2;
+                if constexpr (BW == 3) xi -= readlane_f64(l3k, l) * x3;
+                xk = lane == l ? xi : xk;
+                x3 = x2; x2 = x1; x1 = xi;
+            }
+            x[k] = lane + 64 * k < nq ? xk : 0.0;
+        }
+    }
+}
+
+// workspace slots (SmHbm) of the arrays the rounds use; tm only for BW = 3, the LDL^T's BW + 1 from ldl on
+struct SmRoundSlots { int fix, frd, rhs, pm, qm, rm, tm, ldl, viol; };
+struct SmRounds { bool ok, nonfinite; int factors; };
+
+// Primal-dual active-set rounds of the box QP  minimise 1/2 x^T H x (+ lin^T x)  over lo <= x <= up  from the set act (-1 at lo, 1 at up,
+// 0 free), x the first guess on entry and the last solve on exit.  Each round: one LDL^T with the active elements REMOVED from the system (their
+// values pinned, their coupling moved to the right-hand side), then the KKT test of the box QP - free elements inside their box, active ones
+// pushed against it - to tol relative to 1 + |x|_inf.  Every element that violates it changes sides; once the largest violation has not
+// shrunk by 30 % in three rounds (or from the start: conservative) only those within loose(round) of the largest move.
+template <int BW, bool kLin, class St, class Loose, class Vec = typename St::Vec, class ActVec = typename St::ActVec>
+__device__ __forceinline__ SmRounds band_active_set_rounds(const St& st, int nq, const Vec& p, const Vec& q, const Vec& r, const Vec& t, const Vec& q_m1,
+                                                           const Vec& r_m2, const Vec& t_m3, const Vec& lin, const Vec& lo, const Vec& up, ActVec& act,
+                                                           Vec& x, double tol, int max_rounds, bool conservative, Loose loose, SmRoundSlots sl) {
+    const int KC = st.chunks(), lane = st.lane;
+    auto real = [&](int k) { return lane + 64 * k < nq; };
+    auto pinned = [&](int k) { return real(k) && lo[k] == up[k]; };
+    SmRounds res{false, false, 0};
+    bool nonfinite = false;
+    int stall = 0;
+    double best = 1e300;
+    for (int round = 0; round < max_rounds; ++round) {
+        Vec fix, frd, rhs, pm, qm, rm, tm;
+        st.bind(fix, sl.fix); st.bind(frd, sl.frd); st.bind(rhs, sl.rhs); st.bind(pm, sl.pm); st.bind(qm, sl.qm); st.bind(rm, sl.rm);
+        if constexpr (BW == 3) st.bind(tm, sl.tm);
+#pragma unroll
+        for (int k = 0; k < KC; ++k) { fix[k] = act[k] < 0 ? lo[k] : (act[k] > 0 ? up[k] : 0.0); frd[k] = act[k] == 0 ? 1.0 : 0.0; }
+        st.sync();
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const bool fr = act[k] == 0;
+            // (the shuffles run with every lane enabled, none behind a condition: a disabled lane's value is not readable)
+            const bool f1 = st.template at<1>(frd, k) != 0.0, f2 = st.template at<2>(frd, k) != 0.0, f3 = BW == 3 && st.template at<3>(frd, k) != 0.0;
+            double s = q[k] * st.template at<1>(fix, k) + r[k] * st.template at<2>(fix, k);
+            if constexpr (BW == 3) s += t[k] * st.template at<3>(fix, k);
+            s += q_m1[k] * st.template at<-1>(fix, k);
+            s += r_m2[k] * st.template at<-2>(fix, k);
+            if constexpr (BW == 3) s += t_m3[k] * st.template at<-3>(fix, k);
+            double coupled = -s;
+            if constexpr (kLin) coupled = -lin[k] - s;
+            rhs[k] = fr ? coupled : fix[k];
+            pm[k] = fr ? p[k] : 1.0; qm[k] = (fr && f1) ? q[k] : 0.0; rm[k] = (fr && f2) ? r[k] : 0.0;
+            if constexpr (BW == 3) tm[k] = (fr && f3) ? t[k] : 0.0;
+        }
+        band_ldl_solve<BW>(st, nq, pm, qm, rm, tm, rhs, x, sl.ldl);
+        res.factors += 1;
+        st.sync();
+        Vec viol;
+        st.bind(viol, sl.viol);
+        double vloc = 0.0, sloc = 0.0;
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+            const double xk = x[k];
+            const double g = band_gradient<BW, kLin>(st, k, x, p, q, r, t, q_m1, r_m2, t_m3, lin);
+            double v = 0.0;
+            if (real(k) && !pinned(k)) {
+                if (act[k] == 0) v = fmax(fmax(lo[k] - xk, xk - up[k]), 0.0);
+                else v = act[k] < 0 ? fmax(-g, 0.0) : fmax(g, 0.0);
+            }
+            if (real(k) && !(fabs(xk) <= 1e300 && fabs(g) <= 1e300)) nonfinite = true;
+            viol[k] = v; vloc = fmax(vloc, v); sloc = fmax(sloc, real(k) ? fabs(xk) : 0.0);       // (S3: H's smallest eigenvalue is >= 1, a gradient that is off by tol moves the optimum by <= tol)
+        }
+        if (__ballot(nonfinite) != 0ull) { res.nonfinite = true; break; }
+        const double vmax = wave_max(vloc), scale = 1.0 + wave_max(sloc);
+        if (vmax <= tol * scale) { res.ok = true; break; }
+        // (when the violation stops shrinking only the worst offenders move, as in the generic core's polish)
+        if (vmax < 0.7 * best) { best = vmax; stall = 0; } else { stall += 1; }
+        if (stall >= 3) conservative = true;
+        const double thr = conservative ? fmax(tol * scale, loose(round) * vmax) : tol * scale;
+#pragma unroll
+        for (int k = 0; k < KC; ++k)
+            if (real(k) && !pinned(k) && viol[k] >= thr && viol[k] > 0.0) {
+                if (act[k] == 0) act[k] = (lo[k] - x[k] > x[k] - up[k]) ? -1 : 1;
+                else act[k] = 0;
+            }
+    }
+    return res;
+}
+
+// lane 0: a scenario's status, iters (0) and info (f[3] = interior-point iterations, f[5] = f[6] = factorisations)
+__device__ __forceinline__ void sm_exact_report(int b, bool ok, bool nonfinite, int factors, int ipm_its, int32_t* status, int32_t* iters, double* info) {
+    if (threadIdx.x != 0) return;
+    status[b] = ok ? PQP_STATUS_SOLVED : (nonfinite ? PQP_STATUS_NUMERICAL : PQP_STATUS_MAX_ITER);
+    if (iters) iters[b] = 0;
+    if (info) { double* f = info + (size_t)b * PQP_INFO_STRIDE; for (int k = 0; k < PQP_INFO_STRIDE; ++k) f[k] = 0.0; f[3] = (double)ipm_its; f[4] = ok ? 1.0 : 0.0; f[5] = (double)factors; f[6] = (double)factors; }
+}
 
 // K: layers per lane (m <= 64 K; the host picks the smallest of 1, 2, 4, 6, 8, 12, 16: up to 1024 layers; 16: 19 spilled registers), or 0: any m,
 // the arrays in the workspace `ws` (kPostExactArrays * 64 ceil(m / 64) doubles per scenario).
@@ -448,7 +612,6 @@ __global__ void __launch_bounds__(64) post_exact_kernel(int batch, int m, const 
     st.bind(sv, 0); st.bind(ih, 1); st.bind(wb, 2); st.bind(al, 3); st.bind(be, 4); st.bind(ga, 5); st.bind(p, 6); st.bind(q, 7); st.bind(r, 8); st.bind(lo, 9); st.bind(up, 10); st.bind(a, 11); st.bind(q_p1, 12); st.bind(r_p2, 13);
     typename St::ActVec act;
     st.bind(act, 14);
-    auto pinned = [&](int k) { return real(k) && lo[k] == up[k]; };
 #pragma unroll
     for (int k = 0; k < KC; ++k) sv[k] = real(k) ? ls[row + lane + 64 * k] : 0.0;
     bool bad_s = false, bad_box = false;
@@ -456,7 +619,7 @@ __global__ void __launch_bounds__(64) post_exact_kernel(int batch, int m, const 
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
         const int i = lane + 64 * k;
-        const double s_next = st.nx1(sv, k);
+        const double s_next = st.template at<1>(sv, k);
         const bool has_b = i + 1 < mq;                   // l'_i exists for i <= mq - 2
         const double h = s_next - sv[k];
         bad_s = bad_s || (has_b && !(h > 0.0));
@@ -476,14 +639,14 @@ __global__ void __launch_bounds__(64) post_exact_kernel(int batch, int m, const 
     for (int k = 0; k < KC; ++k) {
         const int i = lane + 64 * k;
         const bool has_c = i + 2 < mq;                   // l''_i for i <= mq - 3
-        const double ih_next = st.nx1(ih, k), ihk = ih[k];
+        const double ih_next = st.template at<1>(ih, k), ihk = ih[k];
         al[k] = has_c ? ihk * ihk : 0.0; be[k] = has_c ? -(ih_next + ihk) * ihk : 0.0; ga[k] = has_c ? ih_next * ihk : 0.0;   // l''_i = al l_i + be l_{i+1} + ga l_{i+2}
     }
     st.sync();
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
         const int i = lane + 64 * k;
-        const double wb_p = st.pv1(wb, k), be_p = st.pv1(be, k), ga_p = st.pv1(ga, k), ga_pp = st.pv2(ga, k);
+        const double wb_p = st.template at<-1>(wb, k), be_p = st.template at<-1>(be, k), ga_p = st.template at<-1>(ga, k), ga_pp = st.template at<-2>(ga, k);
         const double alk = al[k];
         p[k] = 1.0 + wb_p + wb[k] + 1000.0 * (ga_pp * ga_pp + be_p * be_p + alk * alk);
         q[k] = -wb[k] + 1000.0 * (be_p * ga_p + alk * be[k]);
@@ -503,112 +666,23 @@ __global__ void __launch_bounds__(64) post_exact_kernel(int batch, int m, const 
     }
     st.sync();
 #pragma unroll
-    for (int k = 0; k < KC; ++k) { q_p1[k] = st.pv1(q, k); r_p2[k] = st.pv2(r, k); }
+    for (int k = 0; k < KC; ++k) { q_p1[k] = st.template at<-1>(q, k); r_p2[k] = st.template at<-2>(r, k); }
     if (__ballot(bad_box) != 0ull) {                     // an inverted box: the rows l_i >= lb_i, l_i <= ub_i have no common point
         for (int i = lane; i < m; i += 64) out_l[row + i] = 0.0;
         if (lane == 0) { status[b] = PQP_STATUS_PRIMAL_INFEASIBLE; if (iters) iters[b] = 0; }
         return;
     }
-    const int max_rounds = 4 * mq + 24;
-    int round = 0, stall = 0, factors = 0;
-    bool ok = false, conservative = false, nonfinite = false;
-    double best = 1e300;
-    for (; round < max_rounds; ++round) {
-        // ---- the system with the active offsets pinned: their rows and columns leave the matrix, their values go to the right-hand side
-        Vec fix, frd, rhs, pm, qm, rm;
-        st.bind(fix, 15); st.bind(frd, 16); st.bind(rhs, 17); st.bind(pm, 18); st.bind(qm, 19); st.bind(rm, 20);
-#pragma unroll
-        for (int k = 0; k < KC; ++k) { fix[k] = act[k] < 0 ? lo[k] : (act[k] > 0 ? up[k] : 0.0); frd[k] = act[k] == 0 ? 1.0 : 0.0; }
-        st.sync();
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const bool fr = act[k] == 0;
-            const bool fr_n1 = st.nx1(frd, k) != 0.0, fr_n2 = st.nx2(frd, k) != 0.0;
-            // (the shuffles run with every lane enabled: a disabled lane's value is not readable)
-            const double coupled = -(q[k] * st.nx1(fix, k) + r[k] * st.nx2(fix, k) + q_p1[k] * st.pv1(fix, k) + r_p2[k] * st.pv2(fix, k));
-            rhs[k] = fr ? coupled : fix[k];
-            pm[k] = fr ? p[k] : 1.0; qm[k] = (fr && fr_n1) ? q[k] : 0.0; rm[k] = (fr && fr_n2) ? r[k] : 0.0;
-        }
-        // ---- LDL^T of the pentadiagonal matrix and the two substitutions, down and up the lanes ----------------------------------------------
-        Vec l1, l2, z;
-        st.bind(l1, 21); st.bind(l2, 22); st.bind(z, 23);
-        {
-            double d_p = 0.0, d_pp = 0.0, l1_p = 0.0, l2_p = 0.0, l2_pp = 0.0, y_p = 0.0, y_pp = 0.0;
-#pragma unroll
-            for (int k = 0; k < KC; ++k) {
-                const double pk = pm[k], qk = qm[k], rk = rm[k], bk = rhs[k];
-                double l1k = 0.0, l2k = 0.0, zk = 0.0;
-                const int cnt = mq - 64 * k < 64 ? mq - 64 * k : 64;
-                for (int l = 0; l < cnt; ++l) {
-                    const double pi = readlane_f64(pk, l), qi = readlane_f64(qk, l), ri = readlane_f64(rk, l), bi = readlane_f64(bk, l);
-                    const double di = pi - l1_p * l1_p * d_p - l2_pp * l2_pp * d_pp;
-                    const double inv = rcp(di);
-                    const double l1i = (qi - l2_p * l1_p * d_p) * inv, l2i = ri * inv;
-                    const double yi = bi - l1_p * y_p - l2_pp * y_pp;
-                    { const bool me = lane == l; l1k = me ? l1i : l1k; l2k = me ? l2i : l2k; zk = me ? yi * inv : zk; }       // (selects: see tension_exact_kernel)
-                    d_pp = d_p; d_p = di; l2_pp = l2_p; l2_p = l2i; l1_p = l1i; y_pp = y_p; y_p = yi;
-                }
-                l1[k] = l1k; l2[k] = l2k; z[k] = zk;
-            }
-        }
-        factors += 1;
-        {
-            double x_n = 0.0, x_nn = 0.0;
-#pragma unroll
-            for (int k = KC - 1; k >= 0; --k) {
-                const double zk = z[k], l1k = l1[k], l2k = l2[k];
-                double ak = a[k];
-                const int cnt = mq - 64 * k < 64 ? mq - 64 * k : 64;
-                for (int l = cnt - 1; l >= 0; --l) {
-                    const double xi = readlane_f64(zk, l) - readlane_f64(l1k, l) * x_n - readlane_f64(l2k, l) * x_nn;
-                    ak = lane == l ? xi : ak;
-                    x_nn = x_n; x_n = xi;
-                }
-                a[k] = real(k) ? ak : 0.0;
-            }
-        }
-        st.sync();
-        // ---- KKT test of the box QP: g = H l; free offsets inside their box, pinned ones pushed against it ----------------------------------
-        Vec viol;
-        st.bind(viol, 24);
-        double vloc = 0.0, sloc = 0.0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const double ak = a[k];
-            const double g = p[k] * ak + q[k] * st.nx1(a, k) + r[k] * st.nx2(a, k) + q_p1[k] * st.pv1(a, k) + r_p2[k] * st.pv2(a, k);
-            double v = 0.0;
-            if (real(k) && !pinned(k)) {
-                if (act[k] == 0) v = fmax(fmax(lo[k] - ak, ak - up[k]), 0.0);
-                else v = act[k] < 0 ? fmax(-g, 0.0) : fmax(g, 0.0);
-            }
-            if (real(k) && !(fabs(ak) <= 1e300 && fabs(g) <= 1e300)) nonfinite = true;
-            viol[k] = v; vloc = fmax(vloc, v); sloc = fmax(sloc, real(k) ? fabs(ak) : 0.0);       // (the Hessian's smallest eigenvalue is >= 1: a gradient that is off by tol moves the optimum by <= tol)
-        }
-        if (__ballot(nonfinite) != 0ull) { nonfinite = true; break; }
-        const double vmax = wave_max(vloc), scale = 1.0 + wave_max(sloc);
-        if (vmax <= tol * scale) { ok = true; break; }
-        // ---- primal-dual active-set step; when the violation stops shrinking only the worst offenders move (as the generic core's polish)
-        if (vmax < 0.7 * best) { best = vmax; stall = 0; } else { stall += 1; }
-        if (stall >= 3) conservative = true;
-        const double thr = conservative ? fmax(tol * scale, 0.9 * vmax) : tol * scale;
-#pragma unroll
-        for (int k = 0; k < KC; ++k)
-            if (real(k) && !pinned(k) && viol[k] >= thr && viol[k] > 0.0) {
-                if (act[k] == 0) act[k] = (lo[k] - a[k] > a[k] - up[k]) ? -1 : 1;
-                else act[k] = 0;
-            }
-    }
+    // (no linear term, no t: the dummies p, q are not read)
+    const SmRounds rs = band_active_set_rounds<2, false>(st, mq, p, q, r, q, q_p1, r_p2, q_p1, p, lo, up, act, a, tol, 4 * mq + 24, false,
+                                                         [](int) { return 0.9; }, SmRoundSlots{15, 16, 17, 18, 19, 20, -1, 21, 24});
+    const bool ok = rs.ok, nonfinite = rs.nonfinite;
 #pragma unroll
     for (int k = 0; k < KC; ++k) if (lane + 64 * k < m) out_l[row + lane + 64 * k] = (real(k) && !nonfinite) ? a[k] : 0.0;
     if (act_io && ok) {
 #pragma unroll
         for (int k = 0; k < KC; ++k) if (real(k)) act_io[row + lane + 64 * k] = (signed char)act[k];
     }
-    if (lane == 0) {
-        status[b] = ok ? PQP_STATUS_SOLVED : (nonfinite ? PQP_STATUS_NUMERICAL : PQP_STATUS_MAX_ITER);
-        if (iters) iters[b] = 0;
-        if (info) { double* f = info + (size_t)b * PQP_INFO_STRIDE; for (int k = 0; k < PQP_INFO_STRIDE; ++k) f[k] = 0.0; f[4] = ok ? 1.0 : 0.0; f[5] = (double)factors; f[6] = (double)factors; }
-    }
+    sm_exact_report(b, ok, nonfinite, rs.factors, 0, status, iters, info);
 }
 
 // ---- S2, exact: TensionSmoother's QP as a box QP in the lateral shifts alone, one wavefront per scenario --------------------------------
@@ -678,17 +752,17 @@ __global__ void __launch_bounds__(64) tension_exact_kernel(int batch, int n, con
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
         bad_box = bad_box || (real(k) && lo[k] > up[k]);
-        const double c1 = st.at(cs, k, 1), s1 = st.at(sn, k, 1), c2 = st.at(cs, k, 2), s2 = st.at(sn, k, 2), c3 = st.at(cs, k, 3), s3 = st.at(sn, k, 3);
+        const double c1 = st.template at<1>(cs, k), s1 = st.template at<1>(sn, k), c2 = st.template at<2>(cs, k), s2 = st.template at<2>(sn, k), c3 = st.template at<3>(cs, k), s3 = st.template at<3>(sn, k);
         p[k] = real(k) ? h0[k] + w_dev : 1.0;
         q[k] = h1[k] * (c1 * cs[k] + s1 * sn[k]);
         r[k] = h2[k] * (c2 * cs[k] + s2 * sn[k]);
         t[k] = h3[k] * (c3 * cs[k] + s3 * sn[k]);
         // gradient: c_i (H X)_i + s_i (H Y)_i; the rows of H annihilate constants, so the coordinates enter relative to point i
         double hx = 0.0, hy = 0.0;
-        hx += h1[k] * (st.at(X, k, 1) - X[k]) + h2[k] * (st.at(X, k, 2) - X[k]) + h3[k] * (st.at(X, k, 3) - X[k]);
-        hy += h1[k] * (st.at(Y, k, 1) - Y[k]) + h2[k] * (st.at(Y, k, 2) - Y[k]) + h3[k] * (st.at(Y, k, 3) - Y[k]);
-        hx += st.at(h1, k, -1) * (st.at(X, k, -1) - X[k]) + st.at(h2, k, -2) * (st.at(X, k, -2) - X[k]) + st.at(h3, k, -3) * (st.at(X, k, -3) - X[k]);
-        hy += st.at(h1, k, -1) * (st.at(Y, k, -1) - Y[k]) + st.at(h2, k, -2) * (st.at(Y, k, -2) - Y[k]) + st.at(h3, k, -3) * (st.at(Y, k, -3) - Y[k]);
+        hx += h1[k] * (st.template at<1>(X, k) - X[k]) + h2[k] * (st.template at<2>(X, k) - X[k]) + h3[k] * (st.template at<3>(X, k) - X[k]);
+        hy += h1[k] * (st.template at<1>(Y, k) - Y[k]) + h2[k] * (st.template at<2>(Y, k) - Y[k]) + h3[k] * (st.template at<3>(Y, k) - Y[k]);
+        hx += st.template at<-1>(h1, k) * (st.template at<-1>(X, k) - X[k]) + st.template at<-2>(h2, k) * (st.template at<-2>(X, k) - X[k]) + st.template at<-3>(h3, k) * (st.template at<-3>(X, k) - X[k]);
+        hy += st.template at<-1>(h1, k) * (st.template at<-1>(Y, k) - Y[k]) + st.template at<-2>(h2, k) * (st.template at<-2>(Y, k) - Y[k]) + st.template at<-3>(h3, k) * (st.template at<-3>(Y, k) - Y[k]);
         lin[k] = real(k) ? cs[k] * hx + sn[k] * hy : 0.0;
     }
     if (__ballot(bad_box) != 0ull) {                     // a negative clearance: the box on d is empty
@@ -700,60 +774,8 @@ __global__ void __launch_bounds__(64) tension_exact_kernel(int batch, int n, con
     st.bind(q_m1, 17); st.bind(r_m2, 18); st.bind(t_m3, 19);
     st.sync();
 #pragma unroll
-    for (int k = 0; k < KC; ++k) { q_m1[k] = st.at(q, k, -1); r_m2[k] = st.at(r, k, -2); t_m3[k] = st.at(t, k, -3); }
-    // ---- LDL^T of a heptadiagonal matrix (diagonals pm, qm, rm, tm) and the two substitutions, down and up the lanes -------------------------
-    auto ldl_solve = [&](const Vec& pm, const Vec& qm, const Vec& rm, const Vec& tm, const Vec& rhs, Vec& x) {
-        Vec l1, l2, l3, z;
-        st.bind(l1, 20); st.bind(l2, 21); st.bind(l3, 22); st.bind(z, 23);
-        {
-            double d1 = 0.0, d2 = 0.0, d3 = 0.0;           // d_{i-1}, d_{i-2}, d_{i-3}
-            double a1 = 0.0;                               // l1_{i-1}
-            double b1 = 0.0, b2 = 0.0;                     // l2_{i-1}, l2_{i-2}
-            double c1 = 0.0, c2 = 0.0, c3 = 0.0;           // l3_{i-1}, l3_{i-2}, l3_{i-3}
-            double y1 = 0.0, y2 = 0.0, y3 = 0.0;
-#pragma unroll
-            for (int k = 0; k < KC; ++k) {
-                const double pk = pm[k], qk = qm[k], rk = rm[k], tk = tm[k], bk = rhs[k];
-                double l1k = 0.0, l2k = 0.0, l3k = 0.0, zk = 0.0;
-                const int cnt = nq - 64 * k < 64 ? nq - 64 * k : 64;
-                for (int l = 0; l < cnt; ++l) {
-                    const double pi = readlane_f64(pk, l), qi = readlane_f64(qk, l), ri = readlane_f64(rk, l), ti = readlane_f64(tk, l), bi = readlane_f64(bk, l);
-                    const double di = pi - a1 * a1 * d1 - b2 * b2 * d2 - c3 * c3 * d3;
-                    const double inv = rcp(di);
-                    const double l1i = (qi - b1 * a1 * d1 - c2 * b2 * d2) * inv;
-                    const double l2i = (ri - c1 * a1 * d1) * inv;
-                    const double l3i = ti * inv;
-                    const double yi = bi - a1 * y1 - b2 * y2 - c3 * y3;
-                    // (selects, not a branch around four moves: two scalar branches per step cost more than eight v_cndmask - +6 % at 80 points, +23 % at 200)
-                    { const bool me = lane == l; l1k = me ? l1i : l1k; l2k = me ? l2i : l2k; l3k = me ? l3i : l3k; zk = me ? yi * inv : zk; }
-                    d3 = d2; d2 = d1; d1 = di;
-                    a1 = l1i;
-                    b2 = b1; b1 = l2i;
-                    c3 = c2; c2 = c1; c1 = l3i;
-                    y3 = y2; y2 = y1; y1 = yi;
-                }
-                l1[k] = l1k; l2[k] = l2k; l3[k] = l3k; z[k] = zk;
-            }
-        }
-        {
-            double x1 = 0.0, x2 = 0.0, x3 = 0.0;
-#pragma unroll
-            for (int k = KC - 1; k >= 0; --k) {
-                const double zk = z[k], l1k = l1[k], l2k = l2[k], l3k = l3[k];
-                double xk = x[k];
-                const int cnt = nq - 64 * k < 64 ? nq - 64 * k : 64;
-                for (int l = cnt - 1; l >= 0; --l) {
-                    const double xi = readlane_f64(zk, l) - readlane_f64(l1k, l) * x1 - readlane_f64(l2k, l) * x2 - readlane_f64(l3k, l) * x3;
-                    xk = lane == l ? xi : xk;
-                    x3 = x2; x2 = x1; x1 = xi;
-                }
-                x[k] = xk;
-            }
-        }
-    };
-    auto gradient = [&](int k) {
-        return lin[k] + p[k] * d[k] + q[k] * st.at(d, k, 1) + r[k] * st.at(d, k, 2) + t[k] * st.at(d, k, 3) + q_m1[k] * st.at(d, k, -1) + r_m2[k] * st.at(d, k, -2) + t_m3[k] * st.at(d, k, -3);
-    };
+    for (int k = 0; k < KC; ++k) { q_m1[k] = st.template at<-1>(q, k); r_m2[k] = st.template at<-2>(r, k); t_m3[k] = st.template at<-3>(t, k); }
+    auto gradient = [&](int k) { return band_gradient<3, true>(st, k, d, p, q, r, t, q_m1, r_m2, t_m3, lin); };
     auto narrow = [&](int k) { return real(k) && !pinned(k) && up[k] - lo[k] < 1e-3; };
     int factors = 0, ipm_its = 0;
     // ---- the first active set, from the cold start: primal-dual interior-point iterations on the box QP ----------------------------------------
@@ -812,15 +834,14 @@ __global__ void __launch_bounds__(64) tension_exact_kernel(int batch, int n, con
 #pragma unroll
                 for (int k = 0; k < KC; ++k) {
                     const bool f = fre[k] != 0.0;
-                    const bool f1 = st.at(fre, k, 1) != 0.0, f2 = st.at(fre, k, 2) != 0.0, f3 = st.at(fre, k, 3) != 0.0;
+                    const bool f1 = st.template at<1>(fre, k) != 0.0, f2 = st.template at<2>(fre, k) != 0.0, f3 = st.template at<3>(fre, k) != 0.0;
                     const double il = rcp(tl[k]), iu = rcp(tu[k]);
                     itl[k] = il; itu[k] = iu;
                     pm[k] = f ? p[k] + zl[k] * il + zu[k] * iu : 1.0;
                     qm[k] = (f && f1) ? q[k] : 0.0; rm[k] = (f && f2) ? r[k] : 0.0; tm[k] = (f && f3) ? t[k] : 0.0;
                     rhs[k] = f ? -g[k] + smu * (il - iu) : 0.0;
-                    dd[k] = 0.0;
                 }
-                ldl_solve(pm, qm, rm, tm, rhs, dd);
+                band_ldl_solve<3>(st, nq, pm, qm, rm, tm, rhs, dd, 20);
                 factors += 1; ipm_its += 1;
                 Vec dzl, dzu;
                 st.bind(dzl, 38); st.bind(dzu, 39);
@@ -857,63 +878,16 @@ __global__ void __launch_bounds__(64) tension_exact_kernel(int batch, int n, con
                 if (narrow(k)) act[k] = gk > 0.0 ? -1 : 1;
             }
         }
-        const int max_rounds = attempt == 0 ? 3 : 6 * nq + 40;
-        int round = 0, stall = 0;
         // (after the interior start the set is a box or two off: moving only the worst offenders from the first round on ends in at most 4 rounds
         //  where the full moves the cold-start rule needs wander for 10-20 on one line in 3 500 - tools/active_set_sweep.py, tools/tension_fuzz.py)
-        bool conservative = attempt == 1;
-        double best = 1e300;
-        for (; round < max_rounds; ++round) {
-            Vec fix, frd, rhs, pm, qm, rm, tm;
-            st.bind(fix, 40); st.bind(frd, 41); st.bind(rhs, 36); st.bind(pm, 32); st.bind(qm, 33); st.bind(rm, 34); st.bind(tm, 35);
-#pragma unroll
-            for (int k = 0; k < KC; ++k) { fix[k] = act[k] < 0 ? lo[k] : (act[k] > 0 ? up[k] : 0.0); frd[k] = act[k] == 0 ? 1.0 : 0.0; }
-            st.sync();
-#pragma unroll
-            for (int k = 0; k < KC; ++k) {
-                const bool fr = act[k] == 0;
-                const bool f1 = st.at(frd, k, 1) != 0.0, f2 = st.at(frd, k, 2) != 0.0, f3 = st.at(frd, k, 3) != 0.0;
-                const double coupled = -lin[k] - (q[k] * st.at(fix, k, 1) + r[k] * st.at(fix, k, 2) + t[k] * st.at(fix, k, 3) + q_m1[k] * st.at(fix, k, -1) +
-                                                 r_m2[k] * st.at(fix, k, -2) + t_m3[k] * st.at(fix, k, -3));
-                rhs[k] = fr ? coupled : fix[k];
-                pm[k] = fr ? p[k] : 1.0; qm[k] = (fr && f1) ? q[k] : 0.0; rm[k] = (fr && f2) ? r[k] : 0.0; tm[k] = (fr && f3) ? t[k] : 0.0;
-            }
-            ldl_solve(pm, qm, rm, tm, rhs, d);
-            factors += 1;
-#pragma unroll
-            for (int k = 0; k < KC; ++k) if (!real(k)) d[k] = 0.0;
-            st.sync();
-            // ---- KKT test of the box QP: g = H d + lin ---------------------------------------------------------------------------------------------
-            Vec viol;
-            st.bind(viol, 42);
-            double vloc = 0.0, sloc = 0.0;
-#pragma unroll
-            for (int k = 0; k < KC; ++k) {
-                const double gk = gradient(k), dk = d[k];
-                double v = 0.0;
-                if (real(k) && !pinned(k)) {
-                    if (act[k] == 0) v = fmax(fmax(lo[k] - dk, dk - up[k]), 0.0);
-                    else v = act[k] < 0 ? fmax(-gk, 0.0) : fmax(gk, 0.0);
-                }
-                if (real(k) && !(fabs(dk) <= 1e300 && fabs(gk) <= 1e300)) nonfinite = true;
-                viol[k] = v; vloc = fmax(vloc, v); sloc = fmax(sloc, real(k) ? fabs(dk) : 0.0);
-            }
-            if (__ballot(nonfinite) != 0ull) { nonfinite = true; break; }
-            const double vmax = wave_max(vloc), scale = 1.0 + wave_max(sloc);
-            if (vmax <= tol * scale) { ok = true; break; }
-            if (vmax < 0.7 * best) { best = vmax; stall = 0; } else { stall += 1; }
-            if (stall >= 3) conservative = true;
-            // (half of the largest violation, not the generic core's 0.9: the first solve - no box active, a Hessian of condition 1e8 - activates about four times the boxes
-            //  the optimum holds, and releasing them one at a time took 20 / 28 / 55 rounds at 48 / 80 / 200 points where this takes 16 / 21 / 32; 0.25 cycles on 1 line in 100)
-            // (1 line in 1000 cycles with 0.5 - tools/active_set_sweep.py -; from round 40 + n / 4 on, far beyond what a converging line needs, single moves end it)
-            const double thr = conservative ? fmax(tol * scale, ((attempt == 1 || round >= 40 + nq / 4) ? 0.9 : 0.5) * vmax) : tol * scale;
-#pragma unroll
-            for (int k = 0; k < KC; ++k)
-                if (real(k) && !pinned(k) && viol[k] >= thr && viol[k] > 0.0) {
-                    if (act[k] == 0) act[k] = (lo[k] - d[k] > d[k] - up[k]) ? -1 : 1;
-                    else act[k] = 0;
-                }
-        }
+        // (half of the largest violation, not the generic core's 0.9: the first solve - no box active, a Hessian of condition 1e8 - activates about four times the boxes
+        //  the optimum holds, and releasing them one at a time took 20 / 28 / 55 rounds at 48 / 80 / 200 points where this takes 16 / 21 / 32; 0.25 cycles on 1 line in 100)
+        // (1 line in 1000 cycles with 0.5 - tools/active_set_sweep.py -; from round 40 + n / 4 on, far beyond what a converging line needs, single moves end it)
+        // (slots 32-36: the interior start's pm, qm, rm, tm, rhs, dead by now)
+        const SmRounds rs = band_active_set_rounds<3, true>(st, nq, p, q, r, t, q_m1, r_m2, t_m3, lin, lo, up, act, d, tol, attempt == 0 ? 3 : 6 * nq + 40,
+                                                            attempt == 1, [&](int round) { return (attempt == 1 || round >= 40 + nq / 4) ? 0.9 : 0.5; },
+                                                            SmRoundSlots{40, 41, 36, 32, 33, 34, 35, 20, 42});
+        ok = rs.ok; nonfinite = rs.nonfinite; factors += rs.factors;
     }
     // ---- x = X + c d, y = Y + s d, the chord lengths in the reference's order (tension_smoother.cpp:85-98); the tail repeats the last point
     Vec gx, gy, seg, sc;
@@ -926,7 +900,7 @@ __global__ void __launch_bounds__(64) tension_exact_kernel(int batch, int n, con
     st.sync();
 #pragma unroll
     for (int k = 0; k < KC; ++k) {
-        const double px = st.at(gx, k, -1), py = st.at(gy, k, -1), cx = gx[k], cy = gy[k];
+        const double px = st.template at<-1>(gx, k), py = st.template at<-1>(gy, k), cx = gx[k], cy = gy[k];
         const int i = lane + 64 * k;
         seg[k] = (i >= 1 && i < nq) ? sqrt((cx - px) * (cx - px) + (cy - py) * (cy - py)) : 0.0;
     }
@@ -949,11 +923,7 @@ __global__ void __launch_bounds__(64) tension_exact_kernel(int batch, int n, con
         if (i < n) { ox[row + i] = i < nq ? gx[k] : lx; oy[row + i] = i < nq ? gy[k] : ly; os[row + i] = i < nq ? sc[k] : acc; }
         if (act_io && ok && real(k)) act_io[row + i] = (signed char)act[k];
     }
-    if (lane == 0) {
-        status[b] = ok ? PQP_STATUS_SOLVED : (nonfinite ? PQP_STATUS_NUMERICAL : PQP_STATUS_MAX_ITER);
-        if (iters) iters[b] = 0;
-        if (info) { double* f = info + (size_t)b * PQP_INFO_STRIDE; for (int k = 0; k < PQP_INFO_STRIDE; ++k) f[k] = 0.0; f[3] = (double)ipm_its; f[4] = ok ? 1.0 : 0.0; f[5] = (double)factors; f[6] = (double)factors; }
-    }
+    sm_exact_report(b, ok, nonfinite, factors, ipm_its, status, iters, info);
 }
 
 // result lists of the tension smoothers: x, y of the solution and the cumulative chord length
