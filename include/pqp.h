@@ -266,8 +266,17 @@ int pqp_set_params(pqp_handle* h, const pqp_params* params);
  *                                      the library, or other arguments, falls back to plain launches (and a new capture).  Set it on the path handle.
  *                                      A replay runs on the path handle's stream; it is fenced against the smoother handle's stream on both sides
  *                                      (work the caller enqueues there stays ordered as with plain launches).  Value 2: no fences (-3.6 % time) -
- *                                      the caller guarantees that the smoother handle's stream carries no other work while chains are in flight. */
-typedef enum pqp_option { PQP_OPT_STORE_WARM = 1, PQP_OPT_ORDER_BY_COST = 2, PQP_OPT_RESERVE_CUS = 3, PQP_OPT_STREAM_BATCH = 4, PQP_OPT_CARRY_CYCLES = 5, PQP_OPT_CHAIN_GRAPH = 6, PQP_OPT_STREAM_STAGED = 7 } pqp_option;
+ *                                      the caller guarantees that the smoother handle's stream carries no other work while chains are in flight.
+ *   PQP_OPT_LONG_LINES (default 0)     lines of any length in the line-geometry steps (pqp_spline_fit*, pqp_reference_states, pqp_segment_raw_reference,
+ *                                      pqp_reference_length, pqp_offsets_to_points, pqp_bspline_resample, pqp_dp_corridor, pqp_corridor_bounds*).  Their kernels
+ *                                      stage a line's spline table (9 doubles per knot) and their per-element arrays in one CU's LDS, which caps the line
+ *                                      (the DP search first, at about 880 m of smoothed line).  0: those kernels only, PQP_ERR_CAPACITY past their LDS.
+ *                                      1: per launch, the LDS kernel where its LDS fits, otherwise a long form that reads the table from HBM (through the
+ *                                      caches) and keeps the per-element arrays in a workspace of the handle.  2: the long forms always (tests, measurements).
+ *                                      The long forms compute in the same order as the LDS kernels: the same bits.  Set it on the path handle for
+ *                                      pqp_optimize_path_device: every line step of the chain runs there.   */
+typedef enum pqp_option { PQP_OPT_STORE_WARM = 1, PQP_OPT_ORDER_BY_COST = 2, PQP_OPT_RESERVE_CUS = 3, PQP_OPT_STREAM_BATCH = 4, PQP_OPT_CARRY_CYCLES = 5, PQP_OPT_CHAIN_GRAPH = 6, PQP_OPT_STREAM_STAGED = 7,
+                          PQP_OPT_LONG_LINES = 8 } pqp_option;
 int pqp_set_option(pqp_handle* h, int option, int value);
 int pqp_get_stream(pqp_handle* h, void** hip_stream);   /* hipStream_t */
 /* The handle's stream is created non-blocking: work the caller enqueued on ANOTHER stream (the inputs of a *_device call produced by
@@ -632,8 +641,9 @@ typedef enum pqp_second_pass { PQP_SECOND_PASS_RELINEARISE = 0, PQP_SECOND_PASS_
 typedef struct pqp_chain_config {
     int32_t raw_max, sample_max, layer_max, n_max;   /* capacities per scenario: raw-line points (bSpline, about one per metre), 1 m samples of
                                                         the smoother QP, DP layers (1.5 m), waypoints of the path.  No upper bounds (the reference
-                                                        has none); a line of more than ~2000 spline knots exceeds the LDS staging of the corridor
-                                                        steps (PQP_ERR_CAPACITY from that step) */
+                                                        has none).  A line whose spline table does not fit the LDS staging of the line steps
+                                                        (about 880 m of smoothed line: the DP search) is refused there with
+                                                        PQP_ERR_CAPACITY unless the path handle has PQP_OPT_LONG_LINES */
     double output_spacing;               /* 0.3   FLAGS_output_spacing, planning_flags.cpp:106 */
     int32_t dynamic_segmentation;        /* 1     FLAGS_enable_dynamic_segmentation, :110 */
     double max_steering_angle;           /* 35 degrees, :22 */

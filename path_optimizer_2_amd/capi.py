@@ -253,6 +253,7 @@ def _ptr(a):
 
 
 OPT_STORE_WARM, OPT_ORDER_BY_COST, OPT_RESERVE_CUS, OPT_STREAM_BATCH, OPT_CARRY_CYCLES, OPT_CHAIN_GRAPH, OPT_STREAM_STAGED = 1, 2, 3, 4, 5, 6, 7
+OPT_LONG_LINES = 8     # line-geometry steps past their LDS: 0 refuse (default), 1 long form where the LDS form does not fit, 2 long form always
 def stream_batch_default(n, lib=None):
     """pqp_stream_batch_default: from how many QPs of n waypoints on a cold call runs on the lane-per-QP kernel (PQP_OPT_STREAM_BATCH's default)."""
     lib = lib or load_library()

@@ -310,6 +310,7 @@ static std::vector<unsigned char> chain_key(pqp_handle* h, pqp_handle* hs, const
     for (pqp_handle* x : {h, hs}) {
         pqp_params pr; std::memset(&pr, 0, sizeof(pr)); pr = x->prm; put(&pr, sizeof(pr));
         put_int(x->opt_store_warm); put_int(x->opt_order_by_cost); put_int(x->opt_reserve_cus); put_int(x->opt_stream_batch); put_int(x->opt_carry);
+        put_int(x->opt_long_lines);
         put_int(x->solves & 1); put_int(x->hist_batch); put_int(x->hist_n); put_int(x->warm_batch); put_int(x->warm_n); put_int(x->warm_stored ? 1 : 0);
         put_int(x->stream_last_batch); put_int(x->stream_last_n); put_int(x->sm_act_batch[0]); put_int(x->sm_act_n[0]); put_int(x->sm_act_batch[1]); put_int(x->sm_act_n[1]);
         put_int(x->b_struct_type); put_int(x->b_struct_n);
@@ -336,7 +337,8 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
     if (cfg.second_pass == PQP_SECOND_PASS_BOUNDS_ON_STATES && h->prm.rough_constraints_far_away)
         return fail(PQP_ERR_INVALID, "pqp_optimize_path: second_pass = BOUNDS_ON_STATES with rough_constraints_far_away on the path handle");
     // (no upper bounds here - the reference has none: every step below checks what it can hold, the smoother QPs and the path QP of any size go
-    //  to the kernels that keep their state in HBM; what remains are the steps that stage a line's spline table in a CU's LDS, ~2000 knots)
+    //  to the kernels that keep their state in HBM; the steps that stage a line's spline table in a CU's LDS take lines of any length with
+    //  PQP_OPT_LONG_LINES on the path handle, where they all run)
     if (R < 8 || S < 4 || L < 4 || N < 2) return fail(PQP_ERR_CAPACITY, "pqp_optimize_path: capacities out of range (raw_max >= 8, sample_max >= 4, layer_max >= 4, n_max >= 2)");
     if (!hs) hs = h;
     if (hs->device != h->device) return fail(PQP_ERR_INVALID, "pqp_optimize_path: the smoother handle lives on another device than the path handle");

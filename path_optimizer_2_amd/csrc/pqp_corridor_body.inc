@@ -1,6 +1,8 @@
 // pqp_corridor_body.inc — the four phases of the corridor walk, included as the body of corridor_bounds_kernel
 // (ReferencePathImpl::updateBoundsImproved) and of states_bounds_kernel (updateBoundsOnInputStates), pqp_corridor_kernels.inc.
 // In scope there: `a` (CorridorArgs); with PQP_CORRIDOR_ON_STATES = 1 also `states` and `stride`, which only phase 1 reads.
+// With PQP_CORRIDOR_LONG = 1 (long_corridor_kernel / long_states_kernel, pqp_long_line_kernels.inc; PQP_OPT_LONG_LINES) the spline table
+// stays in HBM and the LDS holds the probes of a tile alone: the Newton projection's few evaluations per task read the table through the caches.
 // (One text in two kernels rather than a __device__ function both call: such a function is simplified on its own before it is inlined,
 //  where the kernel arguments are loads through a pointer, and corridor_bounds_kernel's gfx950 code came out different.)
 #pragma clang fp contract(off)
@@ -8,7 +10,11 @@
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int qp = blockIdx.x;
     const int nq = a.n_of ? (a.n_of[qp] < a.n ? a.n_of[qp] : a.n) : a.n;
+#if defined(PQP_CORRIDOR_LONG) && PQP_CORRIDOR_LONG
+    const CorridorLds L{0, a.tile};
+#else
     const CorridorLds L{a.m, a.tile};
+#endif
     int ncoarse = (int)(a.p.search_range / a.p.delta_s);                     // 20 (:243)
     ncoarse = ncoarse > 32 ? 32 : ncoarse;
     const int nfine = (int)(a.p.delta_s / a.p.smaller_ds) - 1;               // static_cast<int>(0.3 / 0.05) = 5: steps i = 1..4 (:278)
@@ -19,12 +25,17 @@
         double acc = 0.0;
         for (int j = 0; j < ncoarse; ++j) { acc += a.p.delta_s; lds[L.acc() + j] = acc; }
     }
+#if defined(PQP_CORRIDOR_LONG) && PQP_CORRIDOR_LONG
+    const float* dist = a.dist + (size_t)(a.map_of ? a.map_of[qp] : 0) * a.g.rows * a.g.cols;
+    const double* tab = a.spl + (size_t)qp * 9 * a.m;
+#else
     {
         const double* src = a.spl + (size_t)qp * 9 * a.m;
         for (int k = threadIdx.x; k < 9 * a.m; k += blockDim.x) lds[k] = src[k];
     }
     const float* dist = a.dist + (size_t)(a.map_of ? a.map_of[qp] : 0) * a.g.rows * a.g.cols;
     const double* tab = lds;
+#endif
     const double* ext = a.spl_ext + (size_t)qp * 4;
     const SplineView sx{tab, tab + a.m, tab + 2 * a.m, tab + 3 * a.m, tab + 4 * a.m, ext[0], ext[1], a.m};
     const SplineView sy{tab, tab + 5 * a.m, tab + 6 * a.m, tab + 7 * a.m, tab + 8 * a.m, ext[2], ext[3], a.m};

@@ -250,6 +250,7 @@ __global__ void constrain_angle_kernel(int count, const double* __restrict__ in,
 
 #include "pqp_smoother_kernels.inc"
 #include "pqp_corridor_kernels.inc"
+#include "pqp_long_line_kernels.inc"
 #include "pqp_distance_kernels.inc"
 #include "pqp_footprint_kernels.inc"
 
@@ -325,6 +326,17 @@ int lds_opt_in(const void* fn, size_t bytes, const char* who) {
     if (fixed + bytes > 48 * 1024) PQP_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     return PQP_OK;
 }
+
+// PQP_OPT_LONG_LINES = `opt`: whether a launch of the LDS kernel `fn` with `bytes` of dynamic LDS goes to its long form
+// (pqp_long_line_kernels.inc) - never (0), where the LDS kernel does not fit one CU (1), always (2)
+int long_form(int opt, const void* fn, size_t bytes, bool* out) {
+    *out = opt == 2;
+    if (opt != 1) return PQP_OK;
+    size_t fixed = 0;
+    if (const int rc = static_lds(fn, &fixed)) return rc;
+    *out = bytes > kLdsPerCu - fixed;
+    return PQP_OK;
+}
 }  // namespace
 
 struct pqp_handle {
@@ -370,6 +382,8 @@ struct pqp_handle {
     long long solves = 0;                       // solve launches so far (parity selects the cost histogram being filled)
     int hist_batch = 0, hist_n = 0;             // shape of the solve whose costs cost_key / cost_hist hold (0: none)
     int opt_store_warm = 1, opt_order_by_cost = 0, opt_reserve_cus = 0, opt_stream_batch = -1, opt_carry = 0, opt_stream_staged = -1;      // (opt_stream_batch < 0: stream_batch_auto(n))
+    int opt_long_lines = 0;                            // PQP_OPT_LONG_LINES: 0 LDS forms only, 1 long form where the LDS form does not fit, 2 long forms
+    DevBuf line_ws;                                    // workspace of the long forms of the line kernels (one launch at a time on the stream)
     int stream_last_batch = 0, stream_last_n = 0;      // shape of the last path_stream_kernel launch (what its workspace still holds)
     int last_path_kernel = 0;                          // pqp_path_kernel of the last pqp_path_solve* launch (pqp_last_path_kernel)
     DevBuf sm_act[2];                                  // final active sets of the exact TensionSmoother / postSmooth kernels (PQP_OPT_CARRY_CYCLES)
@@ -544,6 +558,7 @@ int pqp_set_option(pqp_handle* h, int option, int value) {
         case PQP_OPT_STREAM_STAGED: h->opt_stream_staged = value < 0 ? -1 : (value ? 1 : 0); h->stream_last_batch = 0; return PQP_OK;      // (another layout: nothing to carry)
         case PQP_OPT_CARRY_CYCLES: h->opt_carry = value < 0 ? 0 : (value > 64 ? 64 : value); h->stream_last_batch = 0; h->sm_act_batch[0] = h->sm_act_batch[1] = 0; return PQP_OK;
         case PQP_OPT_CHAIN_GRAPH: h->opt_chain_graph = value == 2 ? 2 : (value ? 1 : 0); return PQP_OK;
+        case PQP_OPT_LONG_LINES: h->opt_long_lines = value >= 2 ? 2 : (value == 1 ? 1 : 0); return PQP_OK;
         default: return fail(PQP_ERR_INVALID, "pqp_set_option: unknown option");
     }
 }
@@ -1309,6 +1324,21 @@ static int corridor_tile(const void* fn, int m, int n, int* tile, size_t* lds, c
     return lds_opt_in(fn, *lds, (std::string(who) + ": scenario too large for one CU's LDS (about 9 m + 31 n doubles)").c_str());
 }
 
+// PQP_OPT_LONG_LINES on a corridor launch: the long kernel `long_fn` (the table in HBM, tiles of probes in LDS) where `fn` would refuse
+// the line's table (1) or always (2); *fn_out and the tile / LDS of the launch accordingly
+static int corridor_pick(int opt, const void* fn, const void* long_fn, int m, int n, const void** fn_out, int* tile, size_t* lds, const char* who) {
+    *fn_out = fn;
+    bool go_long = opt == 2;
+    if (opt == 1) {
+        size_t fixed = 0;
+        if (const int rc = static_lds(fn, &fixed)) return rc;
+        const long long room = (long long)(kLdsPerCu - fixed) - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
+        go_long = pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu - fixed && room < 16 * per_waypoint;
+    }
+    if (go_long) *fn_out = long_fn;
+    return corridor_tile(*fn_out, go_long ? 0 : m, n, tile, lds, who);
+}
+
 // the sample loops are strided; 512 lanes per scenario keep the most gathers in flight per CU (measured at batch 1024 x n = 80: 1024 lanes
 // 142 us - two scenarios per CU -, 512: 121, 256: 120, 128: 146)
 constexpr int kCorridorThreads = 512;
@@ -1323,9 +1353,12 @@ int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const dou
     a.batch = batch; a.n = n; a.m = m; a.ref = ref; a.spl = spline; a.spl_ext = spline_ext; a.dist = dist; a.map_of = map_of; a.n_of = n_of;
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
     size_t lds = 0;
-    if (const int rc = corridor_tile((const void*)pqp::corridor_bounds_kernel, m, n, &a.tile, &lds, "pqp_corridor_bounds")) return rc;
+    const void* fn = nullptr;
+    if (const int rc = corridor_pick(h->opt_long_lines, (const void*)pqp::corridor_bounds_kernel, (const void*)pqp::long_corridor_kernel, m, n, &fn, &a.tile, &lds,
+                                     "pqp_corridor_bounds")) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::corridor_bounds_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a);
+        if (fn == (const void*)pqp::long_corridor_kernel) hipLaunchKernelGGL(pqp::long_corridor_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a);
+        else hipLaunchKernelGGL(pqp::corridor_bounds_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1365,9 +1398,12 @@ int pqp_corridor_bounds_on_states_device(pqp_handle* h, int batch, int n, int m,
     a.batch = batch; a.n = n; a.m = m; a.ref = ref; a.spl = spline; a.spl_ext = spline_ext; a.dist = dist; a.map_of = map_of; a.n_of = n_of;
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
     size_t lds = 0;
-    if (const int rc = corridor_tile((const void*)pqp::states_bounds_kernel, m, n, &a.tile, &lds, "pqp_corridor_bounds_on_states")) return rc;
+    const void* fn = nullptr;
+    if (const int rc = corridor_pick(h->opt_long_lines, (const void*)pqp::states_bounds_kernel, (const void*)pqp::long_states_kernel, m, n, &fn, &a.tile, &lds,
+                                     "pqp_corridor_bounds_on_states")) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::states_bounds_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a, states, stride);
+        if (fn == (const void*)pqp::long_states_kernel) hipLaunchKernelGGL(pqp::long_states_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a, states, stride);
+        else hipLaunchKernelGGL(pqp::states_bounds_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a, states, stride);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1540,10 +1576,13 @@ int pqp_reference_states_device(pqp_handle* h, int batch, int n_max, int m, cons
     a.ds_small = ds_small; a.ds_large = ds_large; a.dynamic = dynamic ? 1 : 0; a.ref = ref; a.count = count; a.init_err = init_err;
     a.lx = a.ly = a.ls = a.langle = a.lk = nullptr;
     const size_t lds = ((size_t)9 * m + n_max) * 8;
-    const int rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_reference_states: 9 m + n_max doubles exceed one CU's LDS");
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::reference_states_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_reference_states: 9 m + n_max doubles exceed one CU's LDS");
     if (rc) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_ref_states_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1566,10 +1605,13 @@ int pqp_segment_raw_reference_device(pqp_handle* h, int batch, int n_max, int m,
     a.ds_small = delta_s; a.ds_large = delta_s; a.dynamic = 2; a.ref = nullptr; a.count = count; a.init_err = nullptr;
     a.lx = x; a.ly = y; a.ls = s; a.langle = angle; a.lk = k;
     const size_t lds = ((size_t)9 * m + n_max) * 8;
-    const int rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_segment_raw_reference: 9 m + n_max doubles exceed one CU's LDS");
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::reference_states_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_segment_raw_reference: 9 m + n_max doubles exceed one CU's LDS");
     if (rc) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_ref_states_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1617,10 +1659,13 @@ int pqp_offsets_to_points_device(pqp_handle* h, int batch, int m_spline, int m, 
     a.batch = batch; a.m_spl = m_spline; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.at_s = at_s; a.l = l; a.m_of = m_of;
     a.x = x; a.y = y; a.s = s;
     const size_t lds = ((size_t)9 * m_spline + 2 * (size_t)m) * 8;
-    const int rc = lds_opt_in((const void*)pqp::offsets_to_points_kernel, lds, "pqp_offsets_to_points: 9 m_spline + 2 m doubles exceed one CU's LDS");
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::offsets_to_points_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::offsets_to_points_kernel, lds, "pqp_offsets_to_points: 9 m_spline + 2 m doubles exceed one CU's LDS");
     if (rc) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::offsets_to_points_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_offsets_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::offsets_to_points_kernel, dim3(batch), dim3(64), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1651,10 +1696,13 @@ int pqp_reference_length_device(pqp_handle* h, int batch, int m, const double* s
     pqp::RefLengthArgs a;
     a.batch = batch; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.length = length; a.target = target; a.length_out = length_out;
     const size_t lds = (size_t)9 * m * 8;
-    const int rc = lds_opt_in((const void*)pqp::reference_length_kernel, lds, "pqp_reference_length: 9 m doubles exceed one CU's LDS");
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::reference_length_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::reference_length_kernel, lds, "pqp_reference_length: 9 m doubles exceed one CU's LDS");
     if (rc) return rc;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::reference_length_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_ref_length_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::reference_length_kernel, dim3(batch), dim3(64), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1684,10 +1732,15 @@ int pqp_bspline_resample_device(pqp_handle* h, int batch, int p_max, int n_max, 
     pqp::BsplineArgs a;
     a.batch = batch; a.p_max = p_max; a.n_max = n_max; a.pts = points; a.n_pts = n_points; a.x = x; a.y = y; a.s = s; a.count = count;
     const size_t lds = ((size_t)3 * p_max + 6 + (size_t)3 * n_max) * 8;
-    const int rc = lds_opt_in((const void*)pqp::bspline_resample_kernel, lds, "pqp_bspline_resample: 3 p_max + 3 n_max doubles exceed one CU's LDS");
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::bspline_resample_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::bspline_resample_kernel, lds, "pqp_bspline_resample: 3 p_max + 3 n_max doubles exceed one CU's LDS");
+    if (!rc && go_long) rc = h->line_ws.ensure((size_t)batch * (p_max + 6) * 8);
     if (rc) return rc;
+    double* ws = h->line_ws.as<double>();
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::bspline_resample_kernel, dim3(batch), dim3(64), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_bspline_kernel, dim3(batch), dim3(64), 0, h->stream, a, ws);
+        else hipLaunchKernelGGL(pqp::bspline_resample_kernel, dim3(batch), dim3(64), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1718,10 +1771,15 @@ static int spline_fit_impl(pqp_handle* h, int batch, int m, const int32_t* m_of,
     a.m_of = m_of;
     a.batch = batch; a.m = m; a.s = s; a.vx = x; a.vy = y; a.spl = spline; a.spl_ext = spline_ext;
     const size_t lds = (size_t)7 * m * 8;
-    const int rc = lds_opt_in((const void*)pqp::spline_fit_kernel, lds, "pqp_spline_fit: 7 m doubles exceed one CU's LDS");
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::spline_fit_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::spline_fit_kernel, lds, "pqp_spline_fit: 7 m doubles exceed one CU's LDS");
+    if (!rc && go_long) rc = h->line_ws.ensure((size_t)2 * batch * lds);
     if (rc) return rc;
+    double* ws = h->line_ws.as<double>();
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::spline_fit_kernel, dim3(2 * batch), dim3(64), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_fit_kernel, dim3(2 * batch), dim3(64), 0, h->stream, a, ws);
+        else hipLaunchKernelGGL(pqp::spline_fit_kernel, dim3(2 * batch), dim3(64), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1771,11 +1829,19 @@ int pqp_dp_corridor_device(pqp_handle* h, int batch, int m, int max_layers, cons
     pqp::DpArgs a;
     a.batch = batch; a.m = m; a.max_layers = max_layers; a.spl = spline; a.spl_ext = spline_ext; a.length = length; a.start = start;
     a.dist = dist; a.map_of = map_of; a.g = *geom; a.p = *prm; a.layers_s = layers_s; a.lb = lb; a.ub = ub; a.count = count; a.vehicle_l = vehicle_l;
-    const size_t lds = pqp::DpLds{m, max_layers, pqp::dp_lateral_samples(prm->lateral_range, prm->lateral_spacing)}.total_bytes();
-    const int rc = lds_opt_in((const void*)pqp::dp_corridor_kernel, lds, "pqp_dp_corridor: 9 m + 17 max_layers doubles (+ the edge table) exceed one CU's LDS");
+    const int nlat = pqp::dp_lateral_samples(prm->lateral_range, prm->lateral_spacing);
+    const size_t lds = pqp::DpLds{m, max_layers, nlat}.total_bytes();
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, (const void*)pqp::dp_corridor_kernel, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::dp_corridor_kernel, lds, "pqp_dp_corridor: 9 m + 17 max_layers doubles (+ the edge table) exceed one CU's LDS");
+    const size_t lds_long = pqp::DpLongLds{nlat}.total_bytes();
+    if (!rc && go_long) rc = lds_opt_in((const void*)pqp::long_dp_kernel, lds_long, "pqp_dp_corridor: the long form's cost tables exceed one CU's LDS");
+    if (!rc && go_long) rc = h->line_ws.ensure((size_t)batch * pqp::DpLongWs{max_layers, nlat}.doubles() * 8);
     if (rc) return rc;
+    double* ws = h->line_ws.as<double>();
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::dp_corridor_kernel, dim3(batch), dim3(pqp::kDpThreads), lds, h->stream, a);
+        if (go_long) hipLaunchKernelGGL(pqp::long_dp_kernel, dim3(batch), dim3(pqp::kDpThreads), lds_long, h->stream, a, ws);
+        else hipLaunchKernelGGL(pqp::dp_corridor_kernel, dim3(batch), dim3(pqp::kDpThreads), lds, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
