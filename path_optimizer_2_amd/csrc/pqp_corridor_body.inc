@@ -1,10 +1,13 @@
 // pqp_corridor_body.inc — the four phases of the corridor walk, included as the body of corridor_bounds_kernel
 // (ReferencePathImpl::updateBoundsImproved) and of states_bounds_kernel (updateBoundsOnInputStates), pqp_corridor_kernels.inc.
 // In scope there: `a` (CorridorArgs); with PQP_CORRIDOR_ON_STATES = 1 also `states` and `stride`, which only phase 1 reads.
-// With PQP_CORRIDOR_LONG = 1 (long_corridor_kernel / long_states_kernel, pqp_long_line_kernels.inc; PQP_OPT_LONG_LINES) the spline table
+// With PQP_CORRIDOR_LONG = 1 (long_corridor_kernel / long_states_kernel; PQP_OPT_LONG_LINES) the spline table
 // stays in HBM and the LDS holds the probes of a tile alone: the Newton projection's few evaluations per task read the table through the caches.
 // (One text in two kernels rather than a __device__ function both call: such a function is simplified on its own before it is inlined,
-//  where the kernel arguments are loads through a pointer, and corridor_bounds_kernel's gfx950 code came out different.)
+//  where the kernel arguments are loads through a pointer, and corridor_bounds_kernel's gfx950 code came out different.  The same was seen
+//  for the five pqp_*_body.inc of the line kernels - as a template <bool kLong> __forceinline__ function taking the arguments by reference
+//  or by value, spline_fit_kernel kept its 649 instructions with operands of commutative ones swapped, the others changed in count - but not
+//  for reference_length_kernel, whose body is such a function.)
 #pragma clang fp contract(off)
     __shared__ int first_blocked;
     extern __shared__ __attribute__((aligned(16))) double lds[];

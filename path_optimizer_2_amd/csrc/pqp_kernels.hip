@@ -250,7 +250,6 @@ __global__ void constrain_angle_kernel(int count, const double* __restrict__ in,
 
 #include "pqp_smoother_kernels.inc"
 #include "pqp_corridor_kernels.inc"
-#include "pqp_long_line_kernels.inc"
 #include "pqp_distance_kernels.inc"
 #include "pqp_footprint_kernels.inc"
 
@@ -328,7 +327,7 @@ int lds_opt_in(const void* fn, size_t bytes, const char* who) {
 }
 
 // PQP_OPT_LONG_LINES = `opt`: whether a launch of the LDS kernel `fn` with `bytes` of dynamic LDS goes to its long form
-// (pqp_long_line_kernels.inc) - never (0), where the LDS kernel does not fit one CU (1), always (2)
+// (long_*_kernel, pqp_corridor_kernels.inc) - never (0), where the LDS kernel does not fit one CU (1), always (2)
 int long_form(int opt, const void* fn, size_t bytes, bool* out) {
     *out = opt == 2;
     if (opt != 1) return PQP_OK;
@@ -478,6 +477,27 @@ static int sm_exact_launch(pqp_handle* h, int batch, int n, int arrays, F&& laun
         else if (n <= 768) launch(std::integral_constant<int, 12>(), ws);
         else if (n <= 1024) launch(std::integral_constant<int, 16>(), ws);
         else launch(std::integral_constant<int, 0>(), ws);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+// One launch of a line-geometry kernel under PQP_OPT_LONG_LINES: the LDS kernel `fn` with `lds` bytes of dynamic LDS, refused with `who` where
+// they exceed one CU's, or - by long_form() - its long form, with `ws_bytes` of the handle's workspace if it takes one.  launch(go_long, ws)
+// enqueues the one (std::false_type) or the other (std::true_type).  long_fn / long_lds / long_who: the long form's own dynamic LDS (the DP's).
+template <class F>
+static int line_launch(pqp_handle* h, const void* fn, size_t lds, const char* who, size_t ws_bytes, F&& launch, const void* long_fn = nullptr,
+                       size_t long_lds = 0, const char* long_who = nullptr) {
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, fn, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in(fn, lds, who);
+    if (!rc && go_long && long_fn) rc = lds_opt_in(long_fn, long_lds, long_who);
+    if (!rc && go_long && ws_bytes) rc = h->line_ws.ensure(ws_bytes);
+    if (rc) return rc;
+    double* ws = h->line_ws.as<double>();
+    return h->launch_timed([&]() -> int {
+        if (go_long) launch(std::true_type(), ws);
+        else launch(std::false_type(), ws);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -1327,15 +1347,10 @@ static int corridor_tile(const void* fn, int m, int n, int* tile, size_t* lds, c
 // PQP_OPT_LONG_LINES on a corridor launch: the long kernel `long_fn` (the table in HBM, tiles of probes in LDS) where `fn` would refuse
 // the line's table (1) or always (2); *fn_out and the tile / LDS of the launch accordingly
 static int corridor_pick(int opt, const void* fn, const void* long_fn, int m, int n, const void** fn_out, int* tile, size_t* lds, const char* who) {
-    *fn_out = fn;
-    bool go_long = opt == 2;
-    if (opt == 1) {
-        size_t fixed = 0;
-        if (const int rc = static_lds(fn, &fixed)) return rc;
-        const long long room = (long long)(kLdsPerCu - fixed) - (long long)pqp::CorridorLds{m, 0}.total_bytes(), per_waypoint = (long long)(pqp::CorridorLds{m, 1}.total_bytes() - pqp::CorridorLds{m, 0}.total_bytes());
-        go_long = pqp::CorridorLds{m, n}.total_bytes() > kLdsPerCu - fixed && room < 16 * per_waypoint;
-    }
-    if (go_long) *fn_out = long_fn;
+    // (what corridor_tile refuses: the table and the fewest probes `fn` runs on, a tile of 16 waypoints or all n, exceed one CU's LDS)
+    bool go_long = false;
+    if (const int rc = long_form(opt, fn, pqp::CorridorLds{m, n < 16 ? n : 16}.total_bytes(), &go_long)) return rc;
+    *fn_out = go_long ? long_fn : fn;
     return corridor_tile(*fn_out, go_long ? 0 : m, n, tile, lds, who);
 }
 
@@ -1576,15 +1591,10 @@ int pqp_reference_states_device(pqp_handle* h, int batch, int n_max, int m, cons
     a.ds_small = ds_small; a.ds_large = ds_large; a.dynamic = dynamic ? 1 : 0; a.ref = ref; a.count = count; a.init_err = init_err;
     a.lx = a.ly = a.ls = a.langle = a.lk = nullptr;
     const size_t lds = ((size_t)9 * m + n_max) * 8;
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::reference_states_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_reference_states: 9 m + n_max doubles exceed one CU's LDS");
-    if (rc) return rc;
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_ref_states_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+    return line_launch(h, (const void*)pqp::reference_states_kernel, lds, "pqp_reference_states: 9 m + n_max doubles exceed one CU's LDS", 0,
+                       [&](auto go_long, double*) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_ref_states_kernel, dim3(batch), dim3(64), 0, h->stream, a);
         else hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
     });
 }
 
@@ -1605,15 +1615,10 @@ int pqp_segment_raw_reference_device(pqp_handle* h, int batch, int n_max, int m,
     a.ds_small = delta_s; a.ds_large = delta_s; a.dynamic = 2; a.ref = nullptr; a.count = count; a.init_err = nullptr;
     a.lx = x; a.ly = y; a.ls = s; a.langle = angle; a.lk = k;
     const size_t lds = ((size_t)9 * m + n_max) * 8;
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::reference_states_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::reference_states_kernel, lds, "pqp_segment_raw_reference: 9 m + n_max doubles exceed one CU's LDS");
-    if (rc) return rc;
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_ref_states_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+    return line_launch(h, (const void*)pqp::reference_states_kernel, lds, "pqp_segment_raw_reference: 9 m + n_max doubles exceed one CU's LDS", 0,
+                       [&](auto go_long, double*) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_ref_states_kernel, dim3(batch), dim3(64), 0, h->stream, a);
         else hipLaunchKernelGGL(pqp::reference_states_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
     });
 }
 
@@ -1659,15 +1664,10 @@ int pqp_offsets_to_points_device(pqp_handle* h, int batch, int m_spline, int m, 
     a.batch = batch; a.m_spl = m_spline; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.at_s = at_s; a.l = l; a.m_of = m_of;
     a.x = x; a.y = y; a.s = s;
     const size_t lds = ((size_t)9 * m_spline + 2 * (size_t)m) * 8;
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::offsets_to_points_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::offsets_to_points_kernel, lds, "pqp_offsets_to_points: 9 m_spline + 2 m doubles exceed one CU's LDS");
-    if (rc) return rc;
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_offsets_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+    return line_launch(h, (const void*)pqp::offsets_to_points_kernel, lds, "pqp_offsets_to_points: 9 m_spline + 2 m doubles exceed one CU's LDS", 0,
+                       [&](auto go_long, double*) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_offsets_kernel, dim3(batch), dim3(64), 0, h->stream, a);
         else hipLaunchKernelGGL(pqp::offsets_to_points_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
     });
 }
 
@@ -1696,15 +1696,10 @@ int pqp_reference_length_device(pqp_handle* h, int batch, int m, const double* s
     pqp::RefLengthArgs a;
     a.batch = batch; a.m = m; a.spl = spline; a.spl_ext = spline_ext; a.length = length; a.target = target; a.length_out = length_out;
     const size_t lds = (size_t)9 * m * 8;
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::reference_length_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::reference_length_kernel, lds, "pqp_reference_length: 9 m doubles exceed one CU's LDS");
-    if (rc) return rc;
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_ref_length_kernel, dim3(batch), dim3(64), 0, h->stream, a);
+    return line_launch(h, (const void*)pqp::reference_length_kernel, lds, "pqp_reference_length: 9 m doubles exceed one CU's LDS", 0,
+                       [&](auto go_long, double*) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_ref_length_kernel, dim3(batch), dim3(64), 0, h->stream, a);
         else hipLaunchKernelGGL(pqp::reference_length_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
     });
 }
 
@@ -1732,17 +1727,10 @@ int pqp_bspline_resample_device(pqp_handle* h, int batch, int p_max, int n_max, 
     pqp::BsplineArgs a;
     a.batch = batch; a.p_max = p_max; a.n_max = n_max; a.pts = points; a.n_pts = n_points; a.x = x; a.y = y; a.s = s; a.count = count;
     const size_t lds = ((size_t)3 * p_max + 6 + (size_t)3 * n_max) * 8;
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::bspline_resample_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::bspline_resample_kernel, lds, "pqp_bspline_resample: 3 p_max + 3 n_max doubles exceed one CU's LDS");
-    if (!rc && go_long) rc = h->line_ws.ensure((size_t)batch * (p_max + 6) * 8);
-    if (rc) return rc;
-    double* ws = h->line_ws.as<double>();
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_bspline_kernel, dim3(batch), dim3(64), 0, h->stream, a, ws);
+    return line_launch(h, (const void*)pqp::bspline_resample_kernel, lds, "pqp_bspline_resample: 3 p_max + 3 n_max doubles exceed one CU's LDS", (size_t)batch * (p_max + 6) * 8,
+                       [&](auto go_long, double* ws) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_bspline_kernel, dim3(batch), dim3(64), 0, h->stream, a, ws);
         else hipLaunchKernelGGL(pqp::bspline_resample_kernel, dim3(batch), dim3(64), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
     });
 }
 
@@ -1771,17 +1759,10 @@ static int spline_fit_impl(pqp_handle* h, int batch, int m, const int32_t* m_of,
     a.m_of = m_of;
     a.batch = batch; a.m = m; a.s = s; a.vx = x; a.vy = y; a.spl = spline; a.spl_ext = spline_ext;
     const size_t lds = (size_t)7 * m * 8;
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::spline_fit_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::spline_fit_kernel, lds, "pqp_spline_fit: 7 m doubles exceed one CU's LDS");
-    if (!rc && go_long) rc = h->line_ws.ensure((size_t)2 * batch * lds);
-    if (rc) return rc;
-    double* ws = h->line_ws.as<double>();
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_fit_kernel, dim3(2 * batch), dim3(64), 0, h->stream, a, ws);
+    return line_launch(h, (const void*)pqp::spline_fit_kernel, lds, "pqp_spline_fit: 7 m doubles exceed one CU's LDS", (size_t)2 * batch * lds,
+                       [&](auto go_long, double* ws) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_fit_kernel, dim3(2 * batch), dim3(64), 0, h->stream, a, ws);
         else hipLaunchKernelGGL(pqp::spline_fit_kernel, dim3(2 * batch), dim3(64), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
     });
 }
 
@@ -1830,21 +1811,13 @@ int pqp_dp_corridor_device(pqp_handle* h, int batch, int m, int max_layers, cons
     a.batch = batch; a.m = m; a.max_layers = max_layers; a.spl = spline; a.spl_ext = spline_ext; a.length = length; a.start = start;
     a.dist = dist; a.map_of = map_of; a.g = *geom; a.p = *prm; a.layers_s = layers_s; a.lb = lb; a.ub = ub; a.count = count; a.vehicle_l = vehicle_l;
     const int nlat = pqp::dp_lateral_samples(prm->lateral_range, prm->lateral_spacing);
-    const size_t lds = pqp::DpLds{m, max_layers, nlat}.total_bytes();
-    bool go_long = false;
-    int rc = long_form(h->opt_long_lines, (const void*)pqp::dp_corridor_kernel, lds, &go_long);
-    if (!rc && !go_long) rc = lds_opt_in((const void*)pqp::dp_corridor_kernel, lds, "pqp_dp_corridor: 9 m + 17 max_layers doubles (+ the edge table) exceed one CU's LDS");
-    const size_t lds_long = pqp::DpLongLds{nlat}.total_bytes();
-    if (!rc && go_long) rc = lds_opt_in((const void*)pqp::long_dp_kernel, lds_long, "pqp_dp_corridor: the long form's cost tables exceed one CU's LDS");
-    if (!rc && go_long) rc = h->line_ws.ensure((size_t)batch * pqp::DpLongWs{max_layers, nlat}.doubles() * 8);
-    if (rc) return rc;
-    double* ws = h->line_ws.as<double>();
-    return h->launch_timed([&]() -> int {
-        if (go_long) hipLaunchKernelGGL(pqp::long_dp_kernel, dim3(batch), dim3(pqp::kDpThreads), lds_long, h->stream, a, ws);
+    const size_t lds = pqp::DpBlock<true, true>{m, max_layers, nlat}.total_bytes();
+    const size_t lds_long = pqp::DpBlock<false, true>{m, max_layers, nlat}.total_bytes();
+    return line_launch(h, (const void*)pqp::dp_corridor_kernel, lds, "pqp_dp_corridor: 9 m + 17 max_layers doubles (+ the edge table) exceed one CU's LDS",
+                       (size_t)batch * pqp::DpBlock<true, false>{m, max_layers, nlat}.doubles() * 8, [&](auto go_long, double* ws) {
+        if constexpr (go_long) hipLaunchKernelGGL(pqp::long_dp_kernel, dim3(batch), dim3(pqp::kDpThreads), lds_long, h->stream, a, ws);
         else hipLaunchKernelGGL(pqp::dp_corridor_kernel, dim3(batch), dim3(pqp::kDpThreads), lds, h->stream, a);
-        PQP_HIP(hipGetLastError());
-        return PQP_OK;
-    });
+    }, (const void*)pqp::long_dp_kernel, lds_long, "pqp_dp_corridor: the long form's cost tables exceed one CU's LDS");
 }
 
 int pqp_dp_corridor(pqp_handle* h, int batch, int m, int max_layers, const double* spline, const double* spline_ext, const double* length,

@@ -75,7 +75,7 @@ def dp_lateral_samples(rng=10.0, spacing=0.6):
 
 
 def dp_lds_bytes(m, lmax, nlat):
-    """DpLds::total_bytes()"""
+    """DpBlock<true, true>::total_bytes()"""
     parent = 9 * m + lmax + 2 * 64 * 2 + 8 + lmax + 64 + 8 * lmax + 33 * nlat + 2 * nlat * nlat
     return parent * 8 + ((lmax * nlat + 7) // 8) * 8 + lmax * 4
 

@@ -1,4 +1,5 @@
-"""PQP_OPT_LONG_LINES: the line-geometry steps and the chain on lines longer than their LDS kernels take (pqp_long_line_kernels.inc).
+"""PQP_OPT_LONG_LINES: the line-geometry steps and the chain on lines longer than their LDS kernels take (the long forms of
+pqp_corridor_kernels.inc: one source text per kernel, compiled once for the LDS and once for the long form).
 Past the LDS edge (option 1) every entry point runs and matches oracle/corridor_oracle.py as the edge tests of test_gpu_line_geometry.py
 do; where both forms run, the long form (option 2) gives the LDS form's bits; option 1 below the edge is the LDS launch; option 0 still
 refuses.  Run with -m gpu on an MI355X."""

@@ -1,5 +1,5 @@
 """PQP_OPT_LONG_LINES without a GPU: the option's value in the C header is the binding's, and the long forms of the line kernels
-(pqp_long_line_kernels.inc) keep everything in registers - no scratch - with the static LDS the launchers count on."""
+(pqp_corridor_kernels.inc: each the text of its LDS kernel, a pqp_*_body.inc with PQP_LINE_LONG = 1) keep everything in registers - no scratch - with the static LDS the launchers count on."""
 import os
 import re
 
@@ -16,7 +16,7 @@ def test_option_value_matches_the_header():
     assert m and int(m.group(1)) == capi.OPT_LONG_LINES == 8
 
 
-# kernel -> static LDS ("LDS Size"): the long DP keeps its cost tables in dynamic LDS (DpLongLds), the corridor forms their first-blocked
+# kernel -> static LDS ("LDS Size"): the long DP keeps its cost tables in dynamic LDS (DpBlock<false, true>), the corridor forms their first-blocked
 # index, reference states its count, the B-spline its count and degree
 LONG_KERNELS = {"long_fit_kernel": 0, "long_ref_states_kernel": 4, "long_ref_length_kernel": 0, "long_offsets_kernel": 0,
                 "long_bspline_kernel": 8, "long_dp_kernel": 0, "long_corridor_kernel": 16, "long_states_kernel": 16}
