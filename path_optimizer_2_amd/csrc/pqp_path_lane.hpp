@@ -294,9 +294,13 @@ struct SlotSetup {
     double Dg[6], Lc[9], Rc[9];      // factor: current diagonal block, couplings (left: rows prev, cols own; right: rows own, cols next)
 };
 
+// what the I3 phase of a polish solve leaves for the look that follows it (PathQp::look_primal); dead everywhere else
+struct LookPart { double pr, nz, w, bad; };
+
 struct Lane {
     Slot s;
     SlotSetup w;
+    LookPart look;
 };
 
 // end rows (owned by the thread holding waypoint n-1), kept in shared memory
@@ -1345,7 +1349,7 @@ struct PathQp {
                     sym3_inv(W.Dg, S.Dinv);
                     mat3_mul_sym3(W.Lc, S.Dinv, S.GL);
                     mat3t_mul_sym3(W.Rc, S.Dinv, S.GR);
-                    if (h < T) {
+                    if (h < h_last) {      // (the last level's node has no survivor to send to: with root_is_padding() that would be the padding root)
                         double* f = sh + L.fbuf() + 21 * t;
                         mat3_mul_mat3t_sym(S.GL, W.Lc, f);
                         mat3_mul_mat3_sym(S.GR, W.Rc, f + 6);
@@ -1424,7 +1428,9 @@ struct PathQp {
         });
     }
 
-    PQP_HD void iterate() {
+    // look: a polish solve (alpha == 1) that look_after_solve() follows - I3 then also leaves the lane's share of the look's primal terms, computed from
+    // the A x~ and the end rows it holds anyway, and the message of the updated y_T (see look_primal)
+    PQP_HD void iterate(bool look = false) {
         const pqp_params& prm = A.prm;
         kkt_solves_ += 1;
         const double alpha = alpha_;
@@ -1619,13 +1625,14 @@ struct PathQp {
         ctx.phase_w([&](int t, Lane& ln) {
             Slot& S = ln.s;
             // the two end rows' fields, loaded by every lane at the top of the phase (see I1); used by the lane that owns the rows at the bottom
-            double e_lo[2], e_up[2], e_z[2], e_y[2], e_rho[2], e_rinv[2], e_act[2];
+            double e_lo[2], e_up[2], e_z[2], e_y[2], e_rho[2], e_rinv[2], e_act[2], e_rb[2] = {0.0, 0.0};
             {
                 const EndRows* er = end_rows();
                 _Pragma("unroll") for (int k = 0; k < 2; ++k) {
                     e_lo[k] = er->lo[k]; e_up[k] = er->up[k]; e_z[k] = er->z[k]; e_y[k] = er->y[k];
                     e_rho[k] = er->rho[k]; e_rinv[k] = er->rinv[k]; e_act[k] = er->act[k];
                 }
+                if (look) { e_rb[0] = er->rb[0]; e_rb[1] = er->rb[1]; }
             }
             double Xp[3];
             if constexpr (D) {
@@ -1675,7 +1682,15 @@ struct PathQp {
                     er->y[k] = e_y[k] + d;
                     if (CERT) er->yp[k] = d;
                     er->z[k] = zn;
+                    e_y[k] += d; e_z[k] = zn;       // (what the end rows now hold, for the look)
                 }
+            }
+            if (look) {
+                // alpha == 1: x is x~, so zT / zI ARE the A x of residuals(), and Xp, the end rows and the updated z, y are all here
+                look_primal(S, t, zT, zI, e_z, e_y, e_rb, e_lo, e_up, e_act, ln.look);
+                double g[3];
+                back_msg(S, S.yT, g);
+                _Pragma("unroll") for (int k = 0; k < 3; ++k) sh[L.bufG() + 3 * t + k] = g[k];
             }
         });
         PQP_IT(6);       // I3
@@ -1689,8 +1704,56 @@ struct PathQp {
     //   res[4] = 1 if an iterate is not finite
     //   res[5] = worst KKT failure over the inequality rows for the current active set (only meaningful while polishing)
     // ---------------------------------------------------------------------------------------------
-    PQP_HD void residuals(double (&res)[6]) {
+    // The lane's terms of a look, in two pieces, each ONE text for residuals() and for the look fused into a polish solve:
+    //   look_primal: from A x of the lane's rows (aT, aI), x and the end rows' z, y -> ||Ax - z||, max(||Ax||, ||z||), the worst KKT failure, the guard
+    //   look_dual:   from the message gn of the next waypoint and the end rows' y -> ||Px + A^T y|| and (FULL) max(||Px||, ||A^T y||)
+    PQP_HD void look_primal(const Slot& S, int t, const double* aT, const double* aI, const double* e_z, const double* e_y, const double* e_rb,
+                            const double* e_lo, const double* e_up, const double* e_act, LookPart& P) const {
+        const bool real = S.flags & F_REAL;
+        double pr = 0.0, nz = 0.0;
+        _Pragma("unroll") for (int k = 0; k < 3; ++k) {
+            pr = fmax(pr, fmax(fabs(aT[k] - S.bT[k]), fabs(aI[k] - S.zI[k])));
+            nz = fmax(nz, fmax(fmax(fabs(aT[k]), fabs(S.bT[k])), fmax(fabs(aI[k]), fabs(S.zI[k]))));
+        }
+        double w = 0.0;
+        _Pragma("unroll") for (int k = 0; k < 3; ++k) w = fmax(w, row_violation(S, t, k, aI[k]));
+        if (S.flags & F_LAST) {
+            pr = fmax(pr, fmax(fabs(S.x[0] - e_z[0]), fabs(S.x[1] - e_z[1])));
+            nz = fmax(nz, fmax(fmax(fabs(S.x[0]), fabs(e_z[0])), fmax(fabs(S.x[1]), fabs(e_z[1]))));
+            _Pragma("unroll") for (int k = 0; k < 2; ++k) w = fmax(w, end_violation_of(e_rb[k], e_lo[k], e_up[k], e_act[k], e_y[k], S.x[k]));
+        }
+        double xsum = 0.0;
+        _Pragma("unroll") for (int k = 0; k < 6; ++k) xsum += S.x[k];
+        P.pr = real ? pr : 0.0;
+        P.nz = real ? nz : 0.0;
+        P.w = w;
+        P.bad = (fabs(xsum) <= 1e300) ? 0.0 : 1.0;   // NaN / Inf guard: a sum of six iterates is finite iff (up to overflow near 1e300) each of them is
+    }
+    template <bool FULL>
+    PQP_HD void look_dual(const Slot& S, const double* gn, const double* e_y, double& du_out, double& nd_out) const {
         const pqp_params& prm = A.prm;
+        const bool real = S.flags & F_REAL;
+        const double cf = coef_front(prm, S.flags), cr = coef_rear(prm, S.flags);
+        double ye0 = 0.0, ye1 = 0.0;
+        if (S.flags & F_LAST) { ye0 = e_y[0]; ye1 = e_y[1]; }
+        double aty[6];
+        aty[0] = -S.yT[0] + gn[0] + S.yI[1] + S.yI[2] + ye0;
+        aty[1] = -S.yT[1] + gn[1] + cf * S.yI[1] + cr * S.yI[2] + ye1;
+        aty[2] = -S.yT[2] + gn[2] + S.yI[0];
+        aty[3] = S.a[5] * S.yT[2];
+        aty[4] = S.yI[1];
+        aty[5] = S.yI[2];
+        const bool colreal[6] = {real, real, real, (S.flags & F_PREV) != 0, real, real && (S.flags & F_PRECISE)};
+        double du = 0.0, nd = 0.0;
+        _Pragma("unroll") for (int k = 0; k < 6; ++k) {
+            const double px = cost_diag(prm, S.flags, k) * S.x[k];
+            du = fmax(du, colreal[k] ? fabs(px + aty[k]) : 0.0);
+            if (FULL) nd = fmax(nd, colreal[k] ? fmax(fabs(px), fabs(aty[k])) : 0.0);
+        }
+        du_out = du; nd_out = nd;
+    }
+
+    PQP_HD void residuals(double (&res)[6]) {
         ctx.phase([&](int t, Lane& ln) {
             double g[3];
             back_msg(ln.s, ln.s.yT, g);
@@ -1703,45 +1766,43 @@ struct PathQp {
             double Xp[3], gn[3];
             { const double* xp_ = nb(t > 0, L.xres(), 3, t - 1); _Pragma("unroll") for (int k = 0; k < 3; ++k) Xp[k] = xp_[k]; }
             { const double* gn_ = nb(t + 1 < T, L.bufG(), 3, t + 1); _Pragma("unroll") for (int k = 0; k < 3; ++k) gn[k] = gn_[k]; }
-            const bool real = S.flags & F_REAL;
-            const double cf = coef_front(prm, S.flags), cr = coef_rear(prm, S.flags);
             double aT[3], aI[3];
             rows_of(S, Xp, S.x, aT, aI);
-            double pr = 0.0, nz = 0.0;
-            _Pragma("unroll") for (int k = 0; k < 3; ++k) {
-                pr = fmax(pr, fmax(fabs(aT[k] - S.bT[k]), fabs(aI[k] - S.zI[k])));
-                nz = fmax(nz, fmax(fmax(fabs(aT[k]), fabs(S.bT[k])), fmax(fabs(aI[k]), fabs(S.zI[k]))));
-            }
-            double ye0 = 0.0, ye1 = 0.0, w = 0.0;
-            _Pragma("unroll") for (int k = 0; k < 3; ++k) w = fmax(w, row_violation(S, t, k, aI[k]));
-            if (S.flags & F_LAST) {
-                pr = fmax(pr, fmax(fabs(S.x[0] - e_z[0]), fabs(S.x[1] - e_z[1])));
-                nz = fmax(nz, fmax(fmax(fabs(S.x[0]), fabs(e_z[0])), fmax(fabs(S.x[1]), fabs(e_z[1]))));
-                ye0 = e_y[0]; ye1 = e_y[1];
-                _Pragma("unroll") for (int k = 0; k < 2; ++k) w = fmax(w, end_violation_of(e_rb[k], e_lo[k], e_up[k], e_act[k], e_y[k], S.x[k]));
-            }
-            double aty[6];
-            aty[0] = -S.yT[0] + gn[0] + S.yI[1] + S.yI[2] + ye0;
-            aty[1] = -S.yT[1] + gn[1] + cf * S.yI[1] + cr * S.yI[2] + ye1;
-            aty[2] = -S.yT[2] + gn[2] + S.yI[0];
-            aty[3] = S.a[5] * S.yT[2];
-            aty[4] = S.yI[1];
-            aty[5] = S.yI[2];
-            const bool colreal[6] = {real, real, real, (S.flags & F_PREV) != 0, real, real && (S.flags & F_PRECISE)};
-            double du = 0.0, nd = 0.0, xsum = 0.0;
-            _Pragma("unroll") for (int k = 0; k < 6; ++k) {
-                const double px = cost_diag(prm, S.flags, k) * S.x[k];
-                du = fmax(du, colreal[k] ? fabs(px + aty[k]) : 0.0);
-                nd = fmax(nd, colreal[k] ? fmax(fabs(px), fabs(aty[k])) : 0.0);
-                xsum += S.x[k];
-            }
-            v[0] = real ? pr : 0.0;
-            v[1] = du;
-            v[2] = real ? nz : 0.0;
-            v[3] = nd;
-            v[4] = (fabs(xsum) <= 1e300) ? 0.0 : 1.0;   // NaN / Inf guard: a sum of six iterates is finite iff (up to overflow near 1e300) each of them is
-            v[5] = w;
+            LookPart P;
+            look_primal(S, t, aT, aI, e_z, e_y, e_rb, e_lo, e_up, e_act, P);
+            look_dual<true>(S, gn, e_y, v[1], v[3]);
+            v[0] = P.pr;
+            v[2] = P.nz;
+            v[4] = P.bad;
+            v[5] = P.w;
         });
+    }
+
+    // The look after a polish solve that ran as iterate(true): the primal terms are in the lanes, the messages of the updated y_T in bufG; what is left
+    // is the barrier every look needs behind a solve, the dual terms and the reduction.  FULL: the six values of residuals() (bit for bit); the lazy
+    // look reduces only the four its policy reads, into a type of its own - the two norms it leaves out cannot be read stale.
+    // (gn comes from LDS in every context: the end rows' y is an LDS load of the same phase, so the round trip is paid once either way, and the DPP
+    //  form would add the message's six products to every lane to save three loads that wait for nothing of their own)
+    struct LazyLook { double pr, du, bad, viol; };
+    template <int K>
+    PQP_HD void look_after_solve_(double (&v)[K]) {
+        sync_after_iterate();
+        ctx.template reduce_max<K>(v, [&](int t, Lane& ln, double (&u)[K]) {
+            const Slot& S = ln.s;
+            double e_y[2], gn[3];
+            { const EndRows* er = end_rows(); e_y[0] = er->y[0]; e_y[1] = er->y[1]; }
+            { const double* gn_ = nb(t + 1 < T, L.bufG(), 3, t + 1); _Pragma("unroll") for (int k = 0; k < 3; ++k) gn[k] = gn_[k]; }
+            double du, nd;
+            look_dual<K == 6>(S, gn, e_y, du, nd);
+            if constexpr (K == 6) { u[0] = ln.look.pr; u[1] = du; u[2] = ln.look.nz; u[3] = nd; u[4] = ln.look.bad; u[5] = ln.look.w; }
+            else { u[0] = ln.look.pr; u[1] = du; u[2] = ln.look.bad; u[3] = ln.look.w; }
+        });
+    }
+    PQP_HD void look_after_solve(double (&res)[6]) { look_after_solve_<6>(res); }
+    PQP_HD void look_after_solve(LazyLook& lz) {
+        double v[4];
+        look_after_solve_<4>(v);
+        lz.pr = v[0]; lz.du = v[1]; lz.bad = v[2]; lz.viol = v[3];
     }
 
     // ---------------------------------------------------------------------------------------------
@@ -2009,6 +2070,9 @@ struct PathQp {
 #define PQP_TIC(m)
 #define PQP_TOC(k)
 #endif
+#ifndef PQP_LOOK_HOOK
+#define PQP_LOOK_HOOK(k, v)      // (tests/emu/look_emu.cpp: compares every fused look with residuals() on the same state)
+#endif
         for (;;) {
             // (the last pass of the call - the reference stops after a solve that fails - writes the output record)
             if (op == COLD_END_PASS) i1 = (status != PQP_STATUS_SOLVED || pass == A.passes) ? 1 : 0;
@@ -2047,7 +2111,8 @@ struct PathQp {
             const long long tic_hot_ = (PQP_TIMING_MASK & 0x02) ? ctx.clock() : 0;      // category 1: the whole hot loop (iterate + residuals + policy)
 #endif
             for (;;) {
-                { PQP_TIC(0x10); iterate(); PQP_TOC(4); }
+                // (a polish solve that a look follows - known before the solve - prepares it in its last phase: iterate(true) / look_after_solve())
+                { PQP_TIC(0x10); iterate(polish_mode && refine_left <= 1); PQP_TOC(4); }
                 bool want_res, check = false, adapt = false;
                 if (!polish_mode) {
                     it += 1;
@@ -2064,8 +2129,30 @@ struct PathQp {
                     if (!polish_mode && it >= prm.max_iter) { sync_after_iterate(); op = COLD_END_PASS; i0 = 0; break; }
                     continue;
                 }
+                // polish_lazy = k: the first look of a round comes after one solve.  Its point is not accurate enough for the acceptance
+                // test, but rows that fail by far more than the solve's own residual fail at the refined point too: during the first
+                // k full rounds of an attempt (where many rows move at once) they move now and the round is over; otherwise the
+                // remaining refinement solves follow.  (Unbounded k: the late rounds, which move single rows, cycle on unrefined points.)
+                if (polish_mode && lazy_look) {
+                    LazyLook lz;
+                    { PQP_TIC(0x20); look_after_solve(lz); PQP_TOC(5); }
+                    PQP_LOOK_HOOK(4, lz);
+                    res[0] = lz.pr; res[1] = lz.du;      // (the info record's two residuals are those of the QP's last look, whichever kind it was)
+                    lazy_look = false;
+                    const double tol = prm.polish_tol, viol = lz.viol;
+                    const double noise = 10.0 * fmax(lz.pr, lz.du);
+                    // (viol > 10 tol already says that the point fails the acceptance test - viol is never negative -, so the test's two norms are not needed here)
+                    if (lz.bad == 0.0 && viol > fmax(10.0 * tol, noise) && round + 1 < max_rounds && round < prm.polish_lazy && !conservative) {
+                        round += 1;
+                        refine_left = 1; lazy_look = true;
+                        op = COLD_REFACTOR; i0 = RF_POLISH_UPDATE; d0 = fmax(fmax(tol, noise), kFullMoveShare * viol); break;
+                    }
+                    // (nothing moves: the point is only looked at again, and only ever accepted, fully refined)
+                    refine_left = prm.polish_refine_iter > 1 ? prm.polish_refine_iter - 1 : 1; continue;
+                }
+                if (polish_mode) { PQP_TIC(0x20); look_after_solve(res); PQP_TOC(5); PQP_LOOK_HOOK(6, res); }
                 // (no barrier between the solve and the residuals: residuals() publishes into buffers the tail of iterate() does not touch - ShLayout::xres)
-                { PQP_TIC(0x20); residuals(res); PQP_TOC(5); }
+                else { PQP_TIC(0x20); residuals(res); PQP_TOC(5); }
                 if (!polish_mode) {
                     bool start_polish = false;
                     if (res[4] != 0.0) { status = PQP_STATUS_NUMERICAL; op = COLD_END_PASS; i0 = 2; break; }      // (i0 = 2: a zero output record)
@@ -2126,21 +2213,7 @@ struct PathQp {
                     const double viol = res[5];
                     const bool solve_ok = res[4] == 0.0 && res[0] <= tol * (1.0 + res[2]) && res[1] <= tol * (1.0 + res[3]);
                     const bool ok = solve_ok && viol <= tol;
-                    // polish_lazy = k: the first look of a round comes after one solve.  Its point is not accurate enough for the acceptance
-                    // test, but rows that fail by far more than the solve's own residual fail at the refined point too: during the first
-                    // k full rounds of an attempt (where many rows move at once) they move now and the round is over; otherwise the
-                    // remaining refinement solves follow.  (Unbounded k: the late rounds, which move single rows, cycle on unrefined points.)
-                    if (lazy_look) {
-                        lazy_look = false;
-                        const double noise = 10.0 * fmax(res[0], res[1]);
-                        if (res[4] == 0.0 && !ok && viol > fmax(10.0 * tol, noise) && round + 1 < max_rounds && round < prm.polish_lazy && !conservative) {
-                            round += 1;
-                            refine_left = 1; lazy_look = true;
-                            op = COLD_REFACTOR; i0 = RF_POLISH_UPDATE; d0 = fmax(fmax(tol, noise), kFullMoveShare * viol); break;
-                        }
-                        // (nothing moves: the point is only looked at again, and only ever accepted, fully refined)
-                        refine_left = prm.polish_refine_iter > 1 ? prm.polish_refine_iter - 1 : 1; continue;
-                    }
+                    // (the lazy look of a round was handled above)
                     // the refinement solves start from the ADMM iterate; from a distant one the budgeted number of them may leave the
                     // polished point short of the accuracy the KKT test needs: up to 3 more pairs of solves instead of throwing the
                     // attempt away

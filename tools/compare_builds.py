@@ -1,5 +1,6 @@
 """Two builds of the library on the same batches: how far apart are their paths?  (Run on the GPU box; each build in a process of its own.)
-Usage: python tools/compare_builds.py <libA> <libB> [batch n profile]...   - prints max / p99 / median |A - B| over (l, d_heading) and the statuses"""
+Usage: python tools/compare_builds.py <libA> <libB> [batch:n:profile[:variant]]...   - prints max / p99 / median |A - B| over (l, d_heading) and the statuses
+(variant v > 0: synth.jitter_batch's v-th planning cycle of the batch, as bench.py cycles them)"""
 import os, subprocess, sys, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,11 +8,11 @@ CHILD = r'''
 import sys, numpy as np
 sys.path.insert(0, %r)
 from path_optimizer_2_amd import capi
-from path_optimizer_2_amd.synth import make_batch
+from path_optimizer_2_amd.synth import jitter_batch, make_batch
 out = {}
 for spec in sys.argv[2:]:
-    batch, n, profile = spec.split(":")
-    b = make_batch(int(batch), int(n), profile)
+    batch, n, profile, variant = (spec.split(":") + ["0"])[:4]
+    b = jitter_batch(make_batch(int(batch), int(n), profile), int(variant))
     h = capi.Handle(capi.production_params(), device=0, max_batch=int(batch), max_n=int(n))
     h.set_option(capi.OPT_STORE_WARM, 0)
     r = h.solve(b["ref"], b["bounds"], b["scal"], passes=1)
