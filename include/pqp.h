@@ -719,6 +719,67 @@ int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const doubl
                         const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
                         int32_t* first_collision, double* margin);
 
+/* ---- scores of candidate paths and each group's best ------------------------------------------------------------------------------
+ * A planner launches many candidates per vehicle and drives one of them.  Behind pqp_optimize_path_device and pqp_footprint_check_device,
+ * on the same stream, this scores every candidate and leaves the winner of every group - its index and its waypoints - so that only the
+ * winners cross to the host.  The reference plans one path per call and has no counterpart; with the default weights the score is twice
+ * the path QP's own objective without its slack terms (OSQP minimises 1/2 x'Px, P's diagonal 20 on k and 100 on dk,
+ * base_solver.cpp:123-147), so "best" means what the solver means.  A group lives on one GPU. */
+#define PQP_SCORE_STRIDE 8
+typedef struct pqp_select_params {
+    double weight_kappa;      /* 20   the path QP's own weight on k      (base_solver.cpp:124, pqp_params.weight_kappa)  */
+    double weight_dkappa;     /* 100  on dk                              (base_solver.cpp:125) */
+    double weight_offset;     /* 0    on l                               (base_solver.cpp:123: weight_l is 0) */
+    double weight_length;     /* 0    on the path's length in metres */
+    double weight_clearance;  /* 0    on sum_i max(0, clearance_want - margin_i)^2 */
+    double clearance_want;    /* 0.6  FLAGS_expected_safety_margin, planning_flags.cpp:95 */
+    int32_t per_waypoint;     /* 0    1: the three sums over waypoints and the clearance sum are divided by the path's count */
+    int32_t require_free;     /* 1    with first_collision given, a path that collides cannot win */
+} pqp_select_params;
+void pqp_select_default_params(pqp_select_params* p);          /* pure host */
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   paths [batch][n][stride]          stride >= 7, columns as PQP_OUT_STRIDE documents: x, y, heading, l, d_heading, k, dk;
+ *                                     stride = PQP_OUT_STRIDE reads pqp_optimize_path_device's `out` where it is
+ *   n_of [batch] or NULL              waypoints of each candidate, e.g. the chain's n_out, clamped to [0, n]; NULL: all have n.
+ *                                     "count" below is this clamped value
+ *   status, stage [batch] or NULL     what the chain wrote (pqp_status, pqp_chain_stage)
+ *   first_collision [batch] or NULL   what the footprint check wrote
+ *   margin [batch][n] or NULL         what the footprint check wrote
+ *   group_start [groups + 1]          the candidates of group g are the rows group_start[g] .. group_start[g + 1] - 1: ascending, the first 0,
+ *                                     the last `batch`; empty groups are allowed
+ * A candidate is eligible when all of these hold: its count is at least 2; status is absent or PQP_STATUS_SOLVED; stage is absent or
+ * PQP_CHAIN_OK; first_collision is absent, or require_free is 0, or first_collision[b] equals its count; its score is finite.
+ * Outputs, fully overwritten:
+ *   terms [batch][PQP_SCORE_STRIDE]   0 score, 1 sum k_i^2, 2 sum_{i < count - 1} dk_i^2, 3 sum l_i^2,
+ *                                     4 length sum_{i < count - 1} sqrt(dx^2 + dy^2) of the chords between successive waypoints,
+ *                                     5 the least margin over the path (0 when margin is NULL; NaN when one of them is NaN),
+ *                                     6 the clearance sum sum_i max(0, clearance_want - margin_i)^2 (0 when margin is NULL),
+ *                                     7 eligible as 1.0 / 0.0.  Sums without a range run over i < count.  Entries 1, 2, 3 and 6 are stored
+ *                                     after the per_waypoint division, and
+ *                                     score = weight_kappa t1 + weight_dkappa t2 + weight_offset t3 + weight_length t4 + weight_clearance t6.
+ *                                     A candidate that is not eligible still gets its terms; one with a count below 2 gets eight zeros.
+ *                                     The order of a candidate's additions depends on its count alone: the same candidate gives the same
+ *                                     bits in any batch, at any position, in any group.
+ *   best [groups]                     the row of the group's eligible candidate with the least score, the lowest row among equal scores;
+ *                                     -1 when the group has none
+ *   best_paths [groups][n][7], best_n [groups]   both or neither (NULL): the winner's seven columns and its count, zeros beyond the
+ *                                     count; a group without a winner is all zeros with best_n 0
+ * The _device form is asynchronous on the handle's stream (two launches: the scores, then the groups) and checks null pointers and sizes
+ * only; with groups = 0 it scores the candidates and launches nothing else.  It cannot see group_start, so the kernel clamps every
+ * group boundary to [0, batch] and takes a descending pair for an empty group: no array makes it read outside `paths`.  What a damaged
+ * array yields follows from that rule alone: a group that starts at a value above batch, and the group of a descending pair, are empty
+ * (best -1, zeros); a group that ends at a value above batch runs to the last row; a negative boundary counts as 0; every other group
+ * is what its own two boundaries say.
+ * The host form copies in, runs, copies out and synchronises; PQP_ERR_INVALID, with nothing launched and the outputs untouched, for
+ * stride < 7, groups < 0, a group_start that is not ascending from 0 to batch (so, batch being at least 1, it needs one group or more),
+ * a parameter that is not finite, or best_paths without best_n or the reverse. */
+int pqp_select_paths_device(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                            const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                            const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n);
+int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                     const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                     const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,14 @@ class PqpCarGeometry(C.Structure):
 FOOTPRINT_CIRCLES, FOOTPRINT_BOUNDING_FIRST = 0, 1      # pqp_footprint_mode
 
 
+class PqpSelectParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("weight_kappa", "weight_dkappa", "weight_offset", "weight_length", "weight_clearance", "clearance_want")] + \
+               [("per_waypoint", C.c_int32), ("require_free", C.c_int32)]
+
+
+SCORE_STRIDE = 8      # PQP_SCORE_STRIDE
+
+
 class PqpSizes(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "state", "control", "precise", "slack", "vars", "cons", "nnz_a", "nnz_p")]
 
@@ -78,6 +86,7 @@ EXPORTS = [
     "pqp_dp_corridor", "pqp_dp_corridor_device", "pqp_segment_raw_reference", "pqp_segment_raw_reference_device", "pqp_bspline_resample", "pqp_bspline_resample_device", "pqp_reference_length", "pqp_reference_length_device", "pqp_offsets_to_points", "pqp_offsets_to_points_device",
     "pqp_distance_layer", "pqp_distance_layer_device",
     "pqp_car_default_geometry", "pqp_car_circles", "pqp_footprint_check", "pqp_footprint_check_device",
+    "pqp_select_default_params", "pqp_select_paths", "pqp_select_paths_device",
 ]
 
 _lib = None
@@ -198,6 +207,10 @@ def load_library(path=None, with_torch=None):
                                                C.c_int, vp, vp, vp]
     lib.pqp_footprint_check.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpCarGeometry),
                                         C.c_int, vp, vp, vp]
+    lib.pqp_select_default_params.argtypes = [C.POINTER(PqpSelectParams)]
+    lib.pqp_select_default_params.restype = None
+    for name in ("pqp_select_paths", "pqp_select_paths_device"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(PqpSelectParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -230,6 +243,17 @@ def car_default_geometry(lib=None, **over):
     for k, v in over.items():
         setattr(c, k, v)
     return c
+
+
+def select_default_params(lib=None, **over):
+    """pqp_select_default_params: the path QP's own weights on k and dk (20, 100), nothing else weighted, clearance_want 0.6,
+    require_free 1, with `over` applied."""
+    lib = lib or load_library()
+    p = PqpSelectParams()
+    lib.pqp_select_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
 
 
 def car_circles(car=None, lib=None):
@@ -345,6 +369,13 @@ def _occupancy(grid, who):
     return grid[None] if grid.ndim == 2 else grid
 
 
+def _check_group_start(group_start, batch):
+    """what pqp_select_paths refuses on the host and the device form cannot see"""
+    gs = np.asarray(group_start)
+    if gs.ndim != 1 or gs.size < 1 or gs[0] != 0 or gs[-1] != batch or (np.diff(gs) < 0).any():
+        raise ValueError(f"group_start must ascend from 0 to the batch ({batch})")
+
+
 def _column_major(maps, dtype):
     """one map [rows][cols] or many [n_maps][rows][cols] -> the ABI's column-major [n_maps][cols][rows], contiguous, as dtype"""
     maps = np.asarray(maps, dtype=dtype)
@@ -425,7 +456,7 @@ class Handle:
         return c
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
-                      car=None, footprint_mode=FOOTPRINT_CIRCLES):
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -433,24 +464,40 @@ class Handle:
         re-linearised one.  Returns dict(out [B][n_max][7], n_out, status, stage, iters).
         check_footprint: pqp_footprint_check_device right behind the chain on the same stream, on its `out` (stride 7) and `n_out` and the same
         layers (car: PqpCarGeometry, None: the reference's; footprint_mode: pqp_footprint_mode); adds free [B][n_max], first_collision [B]
-        and margin [B][n_max] to the dict."""
+        and margin [B][n_max] to the dict.
+        select: group_start [groups + 1] - pqp_select_paths_device behind the chain (and behind the footprint check, whose first_collision
+        and margin it then reads) on the same stream; adds terms [B][8], best [groups], best_paths [groups][n_max][7] and best_n [groups]
+        (select_params: PqpSelectParams, None: select_default_params()).  winners_only (with select): out, free and margin stay on the
+        device and are not in the dict - only per-candidate scalars and the winners cross to the host."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None)
+                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
-                              check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES):
+                              check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
+                              winners_only=False):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
-        no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device)."""
+        no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
+        select / select_params / winners_only: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
                                                                                       C.c_void_p(d_dist.data_ptr())))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None)
+                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only))
 
-    def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None):
+    def _selection(self, select, select_params, winners_only):
+        if select is None:
+            if winners_only or select_params is not None:
+                raise ValueError("select_params / winners_only need select=group_start")
+            return None
+        return (np.ascontiguousarray(select, dtype=np.int32), select_params if select_params is not None else select_default_params(self.lib),
+                bool(winners_only))
+
+    def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
+               selection=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
-        them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None"""
+        them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
+        selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -462,6 +509,15 @@ class Handle:
         d_map, d_k = t(map_of, np.int32), t(start_k, np.float64)
         out = torch.zeros((B, cfg.n_max, 7), dtype=torch.float64, device=dev)
         ints = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4)]
+        if selection is not None:
+            group_start, sel_prm, winners_only = selection
+            _check_group_start(group_start, B)
+            groups = group_start.size - 1           # (one or more: group_start runs from 0 to B)
+            d_start = t(group_start, np.int32)
+            terms = torch.zeros((B, SCORE_STRIDE), dtype=torch.float64, device=dev)
+            best = torch.zeros(groups, dtype=torch.int32, device=dev)
+            best_paths = torch.zeros((groups, cfg.n_max, 7), dtype=torch.float64, device=dev)
+            best_n = torch.zeros(groups, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -477,12 +533,25 @@ class Handle:
             margin = torch.zeros((B, cfg.n_max), dtype=torch.float64, device=dev)
             self._check(self.lib.pqp_footprint_check_device(self._h, B, cfg.n_max, 7, p(out), p(ints[0]), p(d_dist), p(d_map), C.byref(geom),
                                                             C.byref(car), int(mode), p(free), p(first), p(margin)))
+        if selection is not None:           # behind both: reads out, n_out, status, stage (and first_collision, margin) where they are
+            self._check(self.lib.pqp_select_paths_device(self._h, C.byref(sel_prm), B, cfg.n_max, 7, p(out), p(ints[0]), p(ints[1]), p(ints[2]),
+                                                         p(first) if footprint is not None else None, p(margin) if footprint is not None else None,
+                                                         groups, p(d_start), p(terms), p(best), p(best_paths), p(best_n)))
         self.sync()
         if smoother is not None:
             smoother.sync()
-        res = dict(out=out.cpu().numpy(), n_out=ints[0].cpu().numpy(), status=ints[1].cpu().numpy(), stage=ints[2].cpu().numpy(), iters=ints[3].cpu().numpy())
+        host = lambda x: x.cpu().numpy()
+        everything = selection is None or not selection[2]          # winners_only: out, free and margin stay on the device
+        res = dict(out=host(out)) if everything else {}
+        res.update(n_out=host(ints[0]), status=host(ints[1]), stage=host(ints[2]), iters=host(ints[3]))
         if footprint is not None:
-            res.update(free=free.cpu().numpy(), first_collision=first.cpu().numpy(), margin=margin.cpu().numpy())
+            if everything:
+                res.update(free=host(free))
+            res.update(first_collision=host(first))
+            if everything:
+                res.update(margin=host(margin))
+        if selection is not None:
+            res.update(terms=host(terms), best=host(best), best_paths=host(best_paths), best_n=host(best_n))
         return res
 
     def distance_layer(self, grid, geom):
@@ -515,6 +584,27 @@ class Handle:
         if margin:
             res["margin"] = mg
         return res
+
+    def select_paths(self, paths, group_start, n_of=None, status=None, stage=None, first_collision=None, margin=None, prm=None):
+        """pqp_select_paths (host arrays): paths [B][n][stride >= 7] (the chain's `out` as it is), group_start [groups + 1] (ascending, 0 ..
+        B), the optional per-candidate arrays the chain and the footprint check wrote, prm = PqpSelectParams (None: the defaults).  Returns
+        dict(terms [B][8], best [groups], best_paths [groups][n][7], best_n [groups])."""
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        B, n, stride = paths.shape
+        gs = np.ascontiguousarray(group_start, dtype=np.int32).ravel()
+        _check_group_start(gs, B)
+        groups = gs.size - 1
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        no, stt, stg, fc = i32(n_of), i32(status), i32(stage), i32(first_collision)
+        mg = None if margin is None else np.ascontiguousarray(margin, dtype=np.float64)
+        prm = prm if prm is not None else select_default_params(self.lib)
+        terms = np.zeros((B, SCORE_STRIDE))
+        best = np.zeros(groups, dtype=np.int32)
+        best_paths = np.zeros((groups, n, 7))
+        best_n = np.zeros(groups, dtype=np.int32)
+        self._check(self.lib.pqp_select_paths(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(stt), _ptr(stg), _ptr(fc), _ptr(mg),
+                                              groups, _ptr(gs), _ptr(terms), _ptr(best), _ptr(best_paths), _ptr(best_n)))
+        return dict(terms=terms, best=best, best_paths=best_paths, best_n=best_n)
 
     def corridor_params(self, **over):
         p = PqpCorridorParams()

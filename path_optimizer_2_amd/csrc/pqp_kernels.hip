@@ -252,6 +252,7 @@ __global__ void constrain_angle_kernel(int count, const double* __restrict__ in,
 #include "pqp_corridor_kernels.inc"
 #include "pqp_distance_kernels.inc"
 #include "pqp_footprint_kernels.inc"
+#include "pqp_select_kernels.inc"
 
 // =========================================================================================================
 // C ABI
@@ -1570,6 +1571,79 @@ int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const doubl
     double* d_margin = margin ? st.out(margin, bn) : nullptr;
     return st.run([&]() -> int {
         return pqp_footprint_check_device(h, batch, n, stride, d_states, d_n_of, d_dist, d_map_of, geom, car, mode, d_free, d_first, d_margin);
+    });
+}
+
+// ---- scores of candidate paths and each group's best ----------------------------------------------------------------------------------
+void pqp_select_default_params(pqp_select_params* p) {
+    if (!p) return;
+    pqp_params d;
+    pqp::default_params(&d);
+    p->weight_kappa = d.weight_kappa;          // base_solver.cpp:124
+    p->weight_dkappa = d.weight_dkappa;        // :125
+    p->weight_offset = 0.0;                    // :123: weight_l is 0
+    p->weight_length = 0.0;
+    p->weight_clearance = 0.0;
+    p->clearance_want = d.expected_safety_margin;      // FLAGS_expected_safety_margin, planning_flags.cpp:95
+    p->per_waypoint = 0;
+    p->require_free = 1;
+}
+
+static bool select_ok(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, int groups,
+                      const int32_t* group_start, const double* terms, const int32_t* best, const double* best_paths, const int32_t* best_n) {
+    return h && prm && paths && group_start && terms && best && batch >= 1 && n >= 1 && n <= (1 << 30) && stride >= 7 && groups >= 0 &&
+           (best_paths != nullptr) == (best_n != nullptr);
+}
+
+int pqp_select_paths_device(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                            const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                            const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n) {
+    if (!select_ok(h, prm, batch, n, stride, paths, groups, group_start, terms, best, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, "pqp_select_paths: bad argument (stride >= 7; groups >= 0; best_paths and best_n both or neither)");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::SelectArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.groups = groups; a.paths = paths; a.n_of = n_of; a.status = status; a.stage = stage;
+    a.first_collision = first_collision; a.margin = margin; a.group_start = group_start; a.prm = *prm; a.terms = terms; a.best = best;
+    a.best_paths = best_paths; a.best_n = best_n;
+    constexpr int per_block = pqp::kSelectThreads / 64;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::path_score_kernel, dim3((unsigned)((batch + per_block - 1) / per_block)), dim3(pqp::kSelectThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        if (groups > 0) {
+            hipLaunchKernelGGL(pqp::group_select_kernel, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(pqp::kSelectThreads), 0, h->stream, a);
+            PQP_HIP(hipGetLastError());
+        }
+        return PQP_OK;
+    });
+}
+
+int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                     const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                     const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n) {
+    if (!select_ok(h, prm, batch, n, stride, paths, groups, group_start, terms, best, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, "pqp_select_paths: bad argument (stride >= 7; groups >= 0; best_paths and best_n both or neither)");
+    for (const double v : {prm->weight_kappa, prm->weight_dkappa, prm->weight_offset, prm->weight_length, prm->weight_clearance, prm->clearance_want})
+        if (!std::isfinite(v)) return fail(PQP_ERR_INVALID, "pqp_select_paths: a parameter that is not finite");
+    if (group_start[0] != 0 || group_start[groups] != batch) return fail(PQP_ERR_INVALID, "pqp_select_paths: group_start must run from 0 to batch");
+    for (int g = 0; g < groups; ++g)
+        if (group_start[g + 1] < group_start[g]) return fail(PQP_ERR_INVALID, "pqp_select_paths: group_start must be ascending");
+    // (from here on groups >= 1: group_start runs from 0 to batch >= 1)
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_status = st.in(status, batch);
+    const int32_t* d_stage = st.in(stage, batch);
+    const int32_t* d_first = st.in(first_collision, batch);
+    const double* d_margin = st.in(margin, bn);
+    const int32_t* d_start = st.in(group_start, (size_t)groups + 1);
+    double* d_terms = st.out(terms, (size_t)batch * PQP_SCORE_STRIDE);
+    int32_t* d_best = st.out(best, groups);
+    double* d_best_paths = best_paths ? st.out(best_paths, (size_t)groups * n * 7) : nullptr;
+    int32_t* d_best_n = best_n ? st.out(best_n, groups) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_select_paths_device(h, prm, batch, n, stride, d_paths, d_n_of, d_status, d_stage, d_first, d_margin, groups, d_start, d_terms,
+                                       d_best, d_best_paths, d_best_n);
     });
 }
 
