@@ -27,6 +27,7 @@
  *                                                                                                         pqp_reference_states
  *   ReferencePathSmoother::postSmooth (tail)    reference_path_smoother.cpp:559-573                         pqp_offsets_to_points
  *   PathOptimizer::setReferencePathLength       path_optimizer.cpp:87-104                                   pqp_reference_length
+ *   getProjection + global2Local      src/tools/tools.cpp:57-126                                           pqp_project_points
  *   ReferencePathSmoother::bSpline              reference_path_smoother.cpp:490-521                         pqp_bspline_resample
  *   ReferencePathSmoother::segmentRawReference  reference_path_smoother.cpp:48-85                           pqp_segment_raw_reference
  *   tk::spline::set_points            src/tools/spline.cpp:161-249                                         pqp_spline_fit
@@ -779,6 +780,53 @@ int pqp_select_paths_device(pqp_handle* h, const pqp_select_params* prm, int bat
 int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
                      const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
                      const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n);
+
+/* ---- points onto their reference line: Cartesian to Frenet -------------------------------------------------------------------------
+ * Where does a point sit relative to a line?  The reference answers with getProjection / getProjectionByNewton (src/tools/tools.cpp:66-126)
+ * and takes the signed offset from global2Local(projection, point).y (tools.cpp:57-64), as in processInitState (path_optimizer.cpp:73-85)
+ * and graphSearchDp (reference_path_smoother.cpp:148-165).  This does it for many points per line in one launch - obstacle corners, agents,
+ * goal candidates, last cycle's waypoints - and is the inverse of pqp_offsets_to_points.
+ * Inputs:
+ *   spline [batch][9][m], spline_ext [batch][4], length [batch]   as for pqp_reference_length: the tables pqp_spline_fit writes
+ *   points [batch][q_max][stride]     x, y at offsets 0, 1 (stride >= 2); with has_heading a heading at offset 2 (stride >= 3):
+ *                                     stride = PQP_OUT_STRIDE then reads a path solve's or the chain's `out` in place
+ *   q_of [batch] or NULL              the points of each line, clamped to [0, q_max]; NULL: all have q_max
+ * Outputs, fully overwritten: proj [batch][q_max][PQP_PROJ_STRIDE] and flags [batch][q_max]; rows beyond a line's count are eight zeros
+ * with flag 0.  A row:
+ *   0 s          exactly getProjection(xs, ys, x, y, length, 0.0).s: the scan at 0, 1, 2, ... <= length, the first strict minimum wins, the end
+ *                point takes over only when it is strictly closer, Newton from min(best, length) with at most 20 steps until |ds| < 1e-5,
+ *                then min(cur, length).  As in the reference s is NOT clamped at 0 (tk::spline extrapolates to the left,
+ *                spline.cpp:251-272): PQP_PROJ_BEFORE_START says when s < 0.  Bit for bit what pqp_reference_length returns for a target
+ *                behind the line's end.
+ *                One consequence of the end-point rule to know: on a line whose length is no integer the end sample lies less than a metre
+ *                behind the last grid sample, and a point nearer to it than to every grid sample - roughly, a point that belongs to the
+ *                line's last metre - is handed to the end without a Newton step: s = length, PQP_PROJ_AT_END, and t says how far before
+ *                the end the point lies.  To project a path onto the line through its own points, let `length` run a metre or two past
+ *                the last knot (the spline extrapolates to the right as well, spline.cpp:262-266).
+ *   1 l, 2 t     global2Local((x_p, y_p, heading_p), point).y and .x: l is positive to the left, the sign of vehicle_l and of
+ *                initial_offset; t is the distance along the tangent, non-zero only where the projection was clipped (or not converged)
+ *   3 d_heading  constrainAngle(point.heading - heading_p) as path_optimizer.cpp:83, or 0 without has_heading
+ *   4 x_p, 5 y_p, 6 heading_p   the line's state at s, heading_p = getHeading (tools.cpp:32-36)
+ *   7 k_p        getCurvature at s (tools.cpp:38-44)
+ * flags: PQP_PROJ_AT_END s == length; PQP_PROJ_BEFORE_START s < 0; PQP_PROJ_NOT_CONVERGED the 20th Newton step was still >= 1e-5 (the
+ * row is still the reference's); PQP_PROJ_NOT_FINITE see below.
+ * Edge cases:
+ *   length <= 0 or NaN     s = 0 and the other columns from the line's state at 0.  The reference returns a bare State{xs(0), ys(0)} there,
+ *                          without a heading (tools.cpp:72-74); filling the row from the line is this library's choice.
+ *   a point (x, y, or the heading that is read) or a Newton iterate that is not finite: eight NaNs and PQP_PROJ_NOT_FINITE alone; its
+ *                          neighbours are untouched.  So is every point of a line whose length is infinite or 2^20 m (1049 km) and more:
+ *                          the scan's floor(length) + 1 steps would not end, or would hold the GPU for a long time.
+ * The _device form is asynchronous on the handle's stream (one launch), allocates nothing and checks null pointers and sizes only; it has
+ * no knot-count cap and needs neither PQP_OPT_LONG_LINES nor a workspace: the kernel reads the table where it lies.  The host form copies
+ * in, runs, copies out and synchronises.  PQP_ERR_INVALID, with nothing launched and the outputs untouched: a null pointer (q_of apart),
+ * batch < 1, m < 2, q_max < 1 or q_max > 256 * 65535, stride < 2, or stride < 3 with has_heading. */
+#define PQP_PROJ_STRIDE 8
+#define PQP_PROJECT_TILE_SAMPLES 1024      /* coarse samples the kernel holds in LDS at a time (16 bytes each, and the end sample behind them) */
+enum { PQP_PROJ_AT_END = 1, PQP_PROJ_BEFORE_START = 2, PQP_PROJ_NOT_CONVERGED = 4, PQP_PROJ_NOT_FINITE = 8 };
+int pqp_project_points_device(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length,
+                              int q_max, int stride, int has_heading, const double* points, const int32_t* q_of, double* proj, int32_t* flags);
+int pqp_project_points(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length, int q_max,
+                       int stride, int has_heading, const double* points, const int32_t* q_of, double* proj, int32_t* flags);
 
 #ifdef __cplusplus
 }

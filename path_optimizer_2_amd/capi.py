@@ -67,6 +67,9 @@ class PqpSelectParams(C.Structure):
 
 
 SCORE_STRIDE = 8      # PQP_SCORE_STRIDE
+PROJ_STRIDE = 8       # PQP_PROJ_STRIDE: s, l, t, d_heading, x_p, y_p, heading_p, k_p
+PROJECT_TILE_SAMPLES = 1024      # PQP_PROJECT_TILE_SAMPLES
+PROJ_AT_END, PROJ_BEFORE_START, PROJ_NOT_CONVERGED, PROJ_NOT_FINITE = 1, 2, 4, 8
 
 
 class PqpSizes(C.Structure):
@@ -87,6 +90,7 @@ EXPORTS = [
     "pqp_distance_layer", "pqp_distance_layer_device",
     "pqp_car_default_geometry", "pqp_car_circles", "pqp_footprint_check", "pqp_footprint_check_device",
     "pqp_select_default_params", "pqp_select_paths", "pqp_select_paths_device",
+    "pqp_project_points", "pqp_project_points_device",
 ]
 
 _lib = None
@@ -211,6 +215,8 @@ def load_library(path=None, with_torch=None):
     lib.pqp_select_default_params.restype = None
     for name in ("pqp_select_paths", "pqp_select_paths_device"):
         getattr(lib, name).argtypes = [vp, C.POINTER(PqpSelectParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    for name in ("pqp_project_points", "pqp_project_points_device"):
+        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -669,6 +675,22 @@ class Handle:
         out = np.zeros(B)
         self._check(self.lib.pqp_reference_length(self._h, B, m, _ptr(spline), _ptr(spline_ext), _ptr(length), _ptr(target), _ptr(out)))
         return out
+
+    def project_points(self, spline, spline_ext, length, points, q_of=None, has_heading=None):
+        """pqp_project_points (host arrays): spline [B][9][m], spline_ext [B][4], length [B], points [B][q_max][stride] with x, y (and a heading
+        when has_heading; None: stride >= 3) in front, q_of [B] or None -> (proj [B][q_max][8] = s, l, t, d_heading, x_p, y_p, heading_p, k_p,
+        flags [B][q_max] of PROJ_*)."""
+        spline = np.ascontiguousarray(spline, dtype=np.float64); spline_ext = np.ascontiguousarray(spline_ext, dtype=np.float64)
+        length = np.ascontiguousarray(length, dtype=np.float64); points = np.ascontiguousarray(points, dtype=np.float64)
+        qo = None if q_of is None else np.ascontiguousarray(q_of, dtype=np.int32)
+        B, m = spline.shape[0], spline.shape[2]
+        q_max, stride = points.shape[1], points.shape[2]
+        if has_heading is None:
+            has_heading = stride >= 3
+        proj = np.zeros((B, q_max, PROJ_STRIDE)); flags = np.zeros((B, q_max), dtype=np.int32)
+        self._check(self.lib.pqp_project_points(self._h, B, m, _ptr(spline), _ptr(spline_ext), _ptr(length), q_max, stride, 1 if has_heading else 0,
+                                                _ptr(points), _ptr(qo), _ptr(proj), _ptr(flags)))
+        return proj, flags
 
     def bspline_resample(self, points, n_points, n_max):
         """pqp_bspline_resample (host arrays): points [B][p_max][2], n_points [B].  Returns dict(x, y, s: [B][n_max], count [B])."""

@@ -253,6 +253,7 @@ __global__ void constrain_angle_kernel(int count, const double* __restrict__ in,
 #include "pqp_distance_kernels.inc"
 #include "pqp_footprint_kernels.inc"
 #include "pqp_select_kernels.inc"
+#include "pqp_project_kernels.inc"
 
 // =========================================================================================================
 // C ABI
@@ -1644,6 +1645,46 @@ int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int
     return st.run([&]() -> int {
         return pqp_select_paths_device(h, prm, batch, n, stride, d_paths, d_n_of, d_status, d_stage, d_first, d_margin, groups, d_start, d_terms,
                                        d_best, d_best_paths, d_best_n);
+    });
+}
+
+// ---- points onto their reference line: Cartesian to Frenet (getProjection + global2Local, tools.cpp:57-126) -------------------------------
+static const char* const kProjectBad =
+    "pqp_project_points: bad argument (batch >= 1, m >= 2, 1 <= q_max <= 256 * 65535, stride >= 2, stride >= 3 with has_heading)";
+
+static bool project_ok(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length, int q_max, int stride,
+                       int has_heading, const double* points, const double* proj, const int32_t* flags) {
+    return h && spline && spline_ext && length && points && proj && flags && batch >= 1 && m >= 2 && q_max >= 1 &&
+           q_max <= pqp::kProjectThreads * 65535 && stride >= (has_heading ? 3 : 2);
+}
+
+int pqp_project_points_device(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length, int q_max,
+                              int stride, int has_heading, const double* points, const int32_t* q_of, double* proj, int32_t* flags) {
+    if (!project_ok(h, batch, m, spline, spline_ext, length, q_max, stride, has_heading, points, proj, flags)) return fail(PQP_ERR_INVALID, kProjectBad);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::ProjectArgs a;
+    a.batch = batch; a.m = m; a.q_max = q_max; a.stride = stride; a.has_heading = has_heading ? 1 : 0; a.spl = spline; a.spl_ext = spline_ext;
+    a.length = length; a.points = points; a.q_of = q_of; a.proj = proj; a.flags = flags;
+    const dim3 grid((unsigned)batch, (unsigned)((q_max + pqp::kProjectThreads - 1) / pqp::kProjectThreads));
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::project_points_kernel, grid, dim3(pqp::kProjectThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_project_points(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length, int q_max,
+                       int stride, int has_heading, const double* points, const int32_t* q_of, double* proj, int32_t* flags) {
+    if (!project_ok(h, batch, m, spline, spline_ext, length, q_max, stride, has_heading, points, proj, flags)) return fail(PQP_ERR_INVALID, kProjectBad);
+    const size_t rows = (size_t)batch * q_max;
+    Staging st(h);
+    const double *d_spl = st.in(spline, (size_t)batch * 9 * m), *d_ext = st.in(spline_ext, (size_t)batch * 4), *d_length = st.in(length, batch);
+    const double* d_points = st.in(points, rows * stride);
+    const int32_t* d_q_of = st.in(q_of, batch);
+    double* d_proj = st.out(proj, rows * PQP_PROJ_STRIDE);
+    int32_t* d_flags = st.out(flags, rows);
+    return st.run([&]() -> int {
+        return pqp_project_points_device(h, batch, m, d_spl, d_ext, d_length, q_max, stride, has_heading, d_points, d_q_of, d_proj, d_flags);
     });
 }
 
