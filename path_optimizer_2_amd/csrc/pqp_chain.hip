@@ -1,4 +1,4 @@
-// pqp_chain.inc — included by pqp_kernels.hip.  PathOptimizer::solve (reference src/path_optimizer.cpp:34-71) for a batch of scenarios
+// pqp_chain.hip — PathOptimizer::solve (reference src/path_optimizer.cpp:34-71) for a batch of scenarios
 // as ONE device-resident call: input points -> optimised paths, nothing copied to the host between the steps, every scenario with its
 // own point / sample / layer / waypoint counts.
 //
@@ -20,6 +20,28 @@
 //   BaseSolver::solve                            :142                                  pqp_path_solve_var_device (passes = 0)
 //   updateBoundsOnInputStates                    :147, reference_path_impl.cpp:118-175 pqp_corridor_bounds_on_states_device, chain_scal_kernel
 //   BaseSolver post_solver(..., *final_path).solve   :149-150                          chain_lin_kernel, pqp_path_solve_var_device (passes = 0, lin)
+// The steps are the `_device` entry points of the other translation units; this one holds the chain's own small kernels and its graph capture.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <atomic>
+#include <mutex>
+#include <new>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "pqp_defaults.hpp"
+#include "pqp_path_lane.hpp"
+#include "pqp_line_device.hpp"
+#include "pqp_internal.hpp"
+
+using namespace pqp_internal;
+
 namespace pqp {
 
 struct ChainScalArgs {
@@ -120,6 +142,16 @@ __global__ void chain_clamp_kernel(int batch, const int32_t* __restrict__ in, in
     if (b >= batch) return;
     const int v = in[b];
     out[b] = v < lo ? lo : (v > hi ? hi : v);
+}
+
+// dst[b] = src[b][count[b] - 1] + add: the length of a line from its abscissa list (the hand-over between the chain's steps)
+__global__ void gather_last_kernel(int batch, int stride, const int32_t* __restrict__ count, const double* __restrict__ src, double add,
+                                   double* __restrict__ dst) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    int c = count[b];
+    c = c < 1 ? 1 : (c > stride ? stride : c);
+    dst[b] = src[(size_t)b * stride + c - 1] + add;
 }
 
 }  // namespace pqp

@@ -1,4 +1,4 @@
-// pqp_corridor_kernels.inc — included by pqp_kernels.hip.  Corridor bounds of every waypoint from the obstacle distance map
+// pqp_corridor_kernels.inc — included by pqp_lines.hip (SplineView, obstacle_distance ...: pqp_line_device.hpp).  Corridor bounds of every waypoint from the obstacle distance map
 // (SURVEY.md §8f rank 1): the step that produces the `bounds` input of the path QP.
 //   ReferencePathImpl::updateBoundsImproved            src/data_struct/reference_path_impl.cpp:177-230
 //   ReferencePathImpl::getClearanceWithDirectionStrict src/data_struct/reference_path_impl.cpp:232-312
@@ -43,41 +43,6 @@ struct RefStatesArgs {
     double *lx, *ly, *ls, *langle, *lk;          // [batch][n_max] each (only when dynamic == 2)
 };
 
-struct SplineView {
-    const double *x, *y, *a, *b, *c;
-    double b0, c0;
-    int m;
-};
-
-__device__ __forceinline__ int spline_segment(const SplineView& s, double v) {      // std::lower_bound - 1, clamped at 0
-    int lo = 0, hi = s.m;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s.x[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1 > 0 ? lo - 1 : 0;
-}
-
-__device__ __forceinline__ void spline_eval3(const SplineView& s, double v, double& f, double& d1, double& d2) {
-#pragma clang fp contract(off)
-    const int n = s.m;
-    const int idx = spline_segment(s, v);
-    const double h = v - s.x[idx];
-    if (v < s.x[0]) {
-        f = (s.b0 * h + s.c0) * h + s.y[0];
-        d1 = 2.0 * s.b0 * h + s.c0;
-        d2 = 2.0 * s.b0 * h;                       // sic: the reference's left-extrapolated second derivative (spline.cpp:288)
-    } else if (v > s.x[n - 1]) {
-        f = (s.b[n - 1] * h + s.c[n - 1]) * h + s.y[n - 1];
-        d1 = 2.0 * s.b[n - 1] * h + s.c[n - 1];
-        d2 = 2.0 * s.b[n - 1];
-    } else {
-        f = ((s.a[idx] * h + s.b[idx]) * h + s.c[idx]) * h + s.y[idx];
-        d1 = (3.0 * s.a[idx] * h + 2.0 * s.b[idx]) * h + s.c[idx];
-        d2 = 6.0 * s.a[idx] * h + 2.0 * s.b[idx];
-    }
-}
-
 // The long forms of the line-geometry kernels (PQP_OPT_LONG_LINES, pqp.h).  The LDS kernels below stage a line's spline table (9 doubles per
 // knot) and their per-element arrays in one CU's LDS, which caps the line they take (DESIGN.md 8.3).  Each of them has a long form (long_*_kernel)
 // with what does not fit moved out of the LDS and nothing else changed - the same expressions in the same order, so the same bits:
@@ -90,60 +55,6 @@ __device__ __forceinline__ void spline_eval3(const SplineView& s, double v, doub
 // pqp_corridor_body.inc, which says why an included text), reference_length_body<kLong> for the one pair where a function gives the same code.
 // The __global__ functions keep names of their own, the long ones such that no other kernel's name is a substring of theirs:
 // tests/test_kernel_resources.py finds kernels by substring.
-// a / b, correctly rounded, from y = 1 / b rounded to nearest: the quotient by the reciprocal, corrected twice with the exact residual a - b q
-// (fused multiply-add).  After the first correction q is within half an ulp and a bit of a / b, and the second one then rounds to the nearest
-// double (Markstein's theorem; 520 M random and cell-boundary cases against `/` with 13 divisors: 0 mismatches already after one correction).
-// Five instructions where the IEEE division sequence (two scalings, rcp, Newton steps, fix-ups) takes ~15: a map sample divides four times by the
-// cell size, and the kernels around the map are bound by VALU issue (DESIGN.md 8.0).  Differs from `/` only in the sign of a zero quotient.
-__device__ __forceinline__ double exact_div(double a, double b, double y) {
-    double q = a * y;
-    q = fma(fma(-b, q, a), y, q);
-    return fma(fma(-b, q, a), y, q);
-}
-
-// grid_map_core 1.6.x: isInside, getIndex, getPosition, atPositionLinearInterpolated, nearest fallback (restated from the
-// published sources; oracle/corridor_oracle.py carries the same restatement and the notes on its border behaviour)
-__device__ __forceinline__ double obstacle_distance(const float* __restrict__ dist, const pqp_grid_geometry& g, double px, double py) {
-#pragma clang fp contract(off)
-    const double tx = -(px - g.pos_x - 0.5 * g.length_x), ty = -(py - g.pos_y - 0.5 * g.length_y);
-    if (!(tx >= 0.0 && ty >= 0.0 && tx < g.length_x && ty < g.length_y)) return 0.0;
-    const double inv_res = 1.0 / g.resolution;           // (the same for every sample of the kernel: hoisted by the compiler)
-    const int i0x = -(int)exact_div(px - 0.5 * g.length_x - g.pos_x, g.resolution, inv_res);
-    const int i0y = -(int)exact_div(py - 0.5 * g.length_y - g.pos_y, g.resolution, inv_res);
-    const double ox = 0.5 * g.length_x - 0.5 * g.resolution, oy = 0.5 * g.length_y - 0.5 * g.resolution;
-    const double cx = (g.pos_x + ox) + g.resolution * (double)(-i0x), cy = (g.pos_y + oy) + g.resolution * (double)(-i0y);
-    const bool dirx = px >= cx, diry = py >= cy;
-    const int i1x = dirx ? i0x - 1 : i0x + 1;          // indices[1] = (i1x, i0y), indices[2] = (i0x, i2y), indices[3] = (i1x, i2y)
-    const int i2y = diry ? i0y - 1 : i0y + 1;
-    // idxShift: which of the four cells is f[0] (the one whose centre is the interpolation origin), f[1] (+x), f[2] (+y), f[3]
-    int fx[4], fy[4];
-    const int ax = dirx ? i0x : i1x, bx = dirx ? i1x : i0x;       // ax: cell at relative x = 0, bx: at relative x = 1
-    const int ay = diry ? i0y : i2y, by = diry ? i2y : i0y;
-    fx[0] = ax; fy[0] = ay; fx[1] = bx; fy[1] = ay; fx[2] = ax; fy[2] = by; fx[3] = bx; fy[3] = by;
-    // (32-bit: the entry points refuse maps of 2^30 cells and more; the indices are within one cell of the map, the point being inside it)
-    const int end_lin = g.rows * g.cols;
-    int lin[4];
-    float f[4];
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        lin[k] = fy[k] * g.rows + fx[k];                              // column-major linear index; negative = huge size_t upstream
-        const bool in = lin[k] >= 0 && lin[k] < end_lin;
-        ok = ok && in;
-        lin[k] = in ? lin[k] : 0;
-    }
-    // all four cells in flight at once (a cell outside the layer reads cell 0 instead of branching around the load: four dependent
-    // round trips to L2 per sample became one)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) f[k] = dist[lin[k]];
-    if (!ok) return (double)dist[i0y * g.rows + i0x];                // INTER_NEAREST fallback of GridMap::atPosition
-    const double qx = (g.pos_x + ox) + g.resolution * (double)(-ax), qy = (g.pos_y + oy) + g.resolution * (double)(-ay);
-    const double rx = exact_div(px - qx, g.resolution, inv_res), ry = exact_div(py - qy, g.resolution, inv_res);
-    const double ux = 1.0 - rx, uy = 1.0 - ry;
-    const double v = (double)f[0] * ux * uy + (double)f[1] * rx * uy + (double)f[2] * ux * ry + (double)f[3] * rx * ry;
-    return (double)(float)v;
-}
-
 // Layout of the kernel's dynamic LDS in doubles; n = waypoints held at a time (CorridorArgs::tile), tasks = (waypoint, circle)
 struct CorridorLds {
     int m, n;
@@ -197,14 +108,6 @@ __global__ void __launch_bounds__(1024) long_states_kernel(const CorridorArgs a,
 //   ReferencePathImpl::buildReferenceFromSpline  src/data_struct/reference_path_impl.cpp:314-338   (sequential in s: the next
 //       step length depends on the curvature just computed -> one lane per scenario walks its own line)
 //   PathOptimizer::processInitState              src/path_optimizer.cpp:73-85
-// getCurvature (tools.cpp:38-44): (x' y'' - y' x'') / pow(x'^2 + y'^2, 1.5).  v * sqrt(v) is within an ulp of pow(v, 1.5), as
-// libm's pow is of ocml's; the walk below evaluates it at every step, where a double-precision pow would dominate.
-__device__ __forceinline__ double curvature_of(double dx, double dy, double ddx, double ddy) {
-#pragma clang fp contract(off)
-    const double v = dx * dx + dy * dy;
-    return (dx * ddy - dy * ddx) / (v * sqrt(v));
-}
-
 // One wavefront per scenario: the spline table is staged in LDS, lane 0 walks s (it only needs the curvature at each step),
 // then all lanes evaluate the states of the walk's abscissae in parallel and write them coalesced.
 // Long form: the walk's abscissae go straight to their output column (s of a reference state / the `s` list), where the lanes read them back.
@@ -265,77 +168,6 @@ __global__ void __launch_bounds__(64) long_bspline_kernel(const BsplineArgs a, d
 #define PQP_LINE_LONG 1
 #include "pqp_bspline_body.inc"
 #undef PQP_LINE_LONG
-}
-
-// getProjection (src/tools/tools.cpp:66-96) with getProjectionByNewton (:98-126): the abscissa of the point of the line nearest to
-// (tx, ty) - a 1 m grid search from 0, the end point, then Newton on the squared distance (20 steps, |ds| < 1e-5), clipped to the length.
-__device__ __forceinline__ double spline_projection(const SplineView& sx, const SplineView& sy, double tx, double ty, double length) {
-#pragma clang fp contract(off)
-    if (!(length > 0.0)) return 0.0;                  // max_s <= start_s: the state at start_s, whose s stays 0 (:71-74)
-    double tmp = 0.0, best_s = 0.0, best = 1.7976931348623157e308;
-    while (tmp <= length) {
-        double x, y, d1, d2;
-        spline_eval3(sx, tmp, x, d1, d2); spline_eval3(sy, tmp, y, d1, d2);
-        const double d = sqrt((x - tx) * (x - tx) + (y - ty) * (y - ty));
-        if (d < best) { best = d; best_s = tmp; }
-        tmp += 1.0;
-    }
-    double xe, ye, d1, d2;
-    spline_eval3(sx, length, xe, d1, d2); spline_eval3(sy, length, ye, d1, d2);
-    if (sqrt((xe - tx) * (xe - tx) + (ye - ty) * (ye - ty)) < best) return length;
-    double cur = fmin(best_s, length), prev = cur;
-    for (int it = 0; it < 20; ++it) {
-        double x, dx, ddx, y, dy, ddy;
-        spline_eval3(sx, cur, x, dx, ddx); spline_eval3(sy, cur, y, dy, ddy);
-        const double j = (x - tx) * dx + (y - ty) * dy;
-        const double h = dx * dx + (x - tx) * ddx + dy * dy + (y - ty) * ddy;
-        cur -= j / h;
-        if (fabs(cur - prev) < 1e-5) break;
-        prev = cur;
-    }
-    return fmin(cur, length);
-}
-
-// The same projection computed by a whole wavefront (every lane of it calls this, every lane gets the result): the coarse scan at 1 m
-// steps - up to 40 spline evaluations in a row for one lane - is one evaluation per lane; the first minimum wins as in the serial scan
-// (its abscissae 0, 1, 2, ... are exact in both forms), the Newton iterations run redundantly on all lanes.
-__device__ __forceinline__ double spline_projection_wave(const SplineView& sx, const SplineView& sy, double tx, double ty, double length) {
-#pragma clang fp contract(off)
-    if (!(length > 0.0)) return 0.0;
-    const int lane = threadIdx.x & 63;
-    double best_s = 0.0, best = 1.7976931348623157e308;
-    for (int base = 0; (double)base <= length; base += 64) {
-        const int k = base + lane;
-        const double tmp = (double)k;
-        double d = 1.7976931348623157e308;
-        if (tmp <= length) {
-            double x, y, d1, d2;
-            spline_eval3(sx, tmp, x, d1, d2); spline_eval3(sy, tmp, y, d1, d2);
-            d = sqrt((x - tx) * (x - tx) + (y - ty) * (y - ty));
-        }
-        int kk = k;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            const double od = __shfl_xor(d, off, 64);
-            const int ok = __shfl_xor(kk, off, 64);
-            if (od < d || (od == d && ok < kk)) { d = od; kk = ok; }
-        }
-        if (d < best) { best = d; best_s = (double)kk; }
-    }
-    double xe, ye, d1, d2;
-    spline_eval3(sx, length, xe, d1, d2); spline_eval3(sy, length, ye, d1, d2);
-    if (sqrt((xe - tx) * (xe - tx) + (ye - ty) * (ye - ty)) < best) return length;
-    double cur = fmin(best_s, length), prev = cur;
-    for (int it = 0; it < 20; ++it) {
-        double x, dx, ddx, y, dy, ddy;
-        spline_eval3(sx, cur, x, dx, ddx); spline_eval3(sy, cur, y, dy, ddy);
-        const double j = (x - tx) * dx + (y - ty) * dy;
-        const double h = dx * dx + (x - tx) * ddx + dy * dy + (y - ty) * ddy;
-        cur -= j / h;
-        if (fabs(cur - prev) < 1e-5) break;
-        prev = cur;
-    }
-    return fmin(cur, length);
 }
 
 // PathOptimizer::setReferencePathLength (src/path_optimizer.cpp:87-104): when the target state lies behind the end of the reference
@@ -435,16 +267,6 @@ __global__ void __launch_bounds__(64) long_fit_kernel(const SplineFitArgs a, dou
 #define PQP_LINE_LONG 1
 #include "pqp_spline_fit_body.inc"
 #undef PQP_LINE_LONG
-}
-
-// dst[b] = src[b][count[b] - 1] + add: the length of a line from its abscissa list (the hand-over between the chain's steps)
-__global__ void gather_last_kernel(int batch, int stride, const int32_t* __restrict__ count, const double* __restrict__ src, double add,
-                                   double* __restrict__ dst) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    int c = count[b];
-    c = c < 1 ? 1 : (c > stride ? stride : c);
-    dst[b] = src[(size_t)b * stride + c - 1] + add;
 }
 
 // Layered DP corridor search between the smoother QP and the postSmooth QP (SURVEY.md 8f rank 4):

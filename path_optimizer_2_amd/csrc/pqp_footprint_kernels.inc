@@ -1,4 +1,4 @@
-// pqp_footprint_kernels.inc — included by pqp_kernels.hip after pqp_corridor_kernels.inc.  Vehicle footprints of planned states against
+// pqp_footprint_kernels.inc — included by pqp_maps.hip.  Vehicle footprints of planned states against
 // the obstacle distance layer (pqp_footprint_check):
 //   CollisionChecker::isSingleStateCollisionFree          src/tools/collision_checker.cpp:17-39
 //   CollisionChecker::isSingleStateCollisionFreeImproved  src/tools/collision_checker.cpp:41-58

@@ -1,0 +1,242 @@
+// pqp_internal.hpp — host side only: what the translation units of libpqp_hip.so share behind the C ABI of include/pqp.h.  The handle, its
+// device buffers, launch timing and host staging, the error message of pqp_last_error, and the launch helpers that several kernel families use.
+// Everything here lives in a namespace of hidden visibility: the library exports the entry points of pqp.h (and its kernels' host stubs), nothing of this.
+// The state behind it - the thread-local error message, the allocation generation, the cache of static_lds - is defined once, in pqp_kernels.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <atomic>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/pqp.h"
+
+namespace pqp_internal __attribute__((visibility("hidden"))) {
+
+// sets the calling thread's message (pqp_last_error) and returns `code`
+int fail(int code, const std::string& msg);
+#define PQP_HIP(call)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (call);                                                                        \
+        if (e_ != hipSuccess) return ::pqp_internal::fail(PQP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+// every (re)allocation of a device buffer of the library: captured hipGraphs of the chain hold device pointers and are only replayed
+// while this has not moved (pqp_chain.hip)
+extern std::atomic<unsigned long long> g_alloc_generation;
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int ensure(size_t need) {
+        if (need <= bytes) return PQP_OK;
+        g_alloc_generation.fetch_add(1, std::memory_order_relaxed);
+        if (p) (void)hipFree(p);
+        p = nullptr; bytes = 0;
+        PQP_HIP(hipMalloc(&p, need));
+        bytes = need;
+        // No call ever reads uninitialised device memory (warm state of skipped QPs, info rows).  hipMemset runs on the NULL stream and
+        // may return before the fill has executed; the handles' streams are non-blocking, i.e. NOT ordered behind the NULL stream, so a
+        // fill still queued there could land on the buffer milliseconds later, after kernels of the handle have written it (seen: a
+        // whole smoother batch solved on zeroed problem data).  Allocation is rare: wait for the fill.
+        PQP_HIP(hipMemset(p, 0, need));
+        PQP_HIP(hipStreamSynchronize(nullptr));
+        return PQP_OK;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// one CU's LDS on gfx950: the most dynamic LDS a workgroup can have
+constexpr size_t kLdsPerCu = 160 * 1024;
+
+// the static LDS of kernel `fn`: its __shared__ variables, padded to the alignment of the dynamic LDS that follows them (the compiler's
+// "LDS Size" remark; 16 bytes for a single int in front of an aligned(16) array).  Looked up once per kernel.
+int static_lds(const void* fn, size_t* out);
+
+// `bytes` of dynamic LDS for kernel `fn`: PQP_ERR_CAPACITY (message `who`) when they and the kernel's static LDS exceed one CU's LDS, the
+// opt-in beyond the 48 KiB any kernel may use.  The attribute takes the dynamic bytes alone (the runtime adds the static ones to it).
+int lds_opt_in(const void* fn, size_t bytes, const char* who);
+
+// PQP_OPT_LONG_LINES = `opt`: whether a launch of the LDS kernel `fn` with `bytes` of dynamic LDS goes to its long form
+// (long_*_kernel, pqp_corridor_kernels.inc) - never (0), where the LDS kernel does not fit one CU (1), always (2)
+int long_form(int opt, const void* fn, size_t bytes, bool* out);
+
+}  // namespace pqp_internal
+
+struct pqp_handle {
+    using DevBuf = pqp_internal::DevBuf;
+    int device = 0;
+    pqp_params prm;
+    hipStream_t stream = nullptr;
+    // HIP events around the dominant kernel of every call, on the stream it is launched on: a ring of the last kEvRing launches,
+    // read back (after the work is done) by pqp_last_kernel_ms / pqp_kernel_ms_history without putting a sync between launches.
+    // One slot more than the history: the one launch_timed records into, which a launch that fails may leave half recorded.
+    static constexpr int kEvRing = 256, kEvSlots = kEvRing + 1;
+    hipEvent_t evs0[kEvSlots] = {}, evs1[kEvSlots] = {};
+    long long ev_count = 0;          // launches recorded so far
+    bool timed = false;              // the last of them is what pqp_last_kernel_ms reports
+    static constexpr int kMarks = 8;
+    static constexpr int kChainMarks = 2;      // + two events of pqp_optimize_path_device's own
+    hipEvent_t marks[kMarks + kChainMarks] = {};   // pqp_mark / pqp_wait_mark: ordering between the streams of two handles
+    // the launches of one call between the next pair of the ring's events, which count only once the launches were accepted: a call that
+    // fails leaves the timing of the previous one.  No events inside a graph capture.
+    template <class F> int launch_timed(F&& launch) {
+        if (capturing) return launch();
+        const int slot = (int)(ev_count % kEvSlots);
+        PQP_HIP(hipEventRecord(evs0[slot], stream));
+        if (const int rc = launch()) return rc;
+        PQP_HIP(hipEventRecord(evs1[slot], stream));
+        ev_count += 1;
+        timed = true;
+        return PQP_OK;
+    }
+    // PQP_OPT_CHAIN_GRAPH: pqp_optimize_path_device captured as hipGraphs (pqp_chain.hip).  capturing: the handle's stream is in capture
+    // mode - no timing events, the path solve resets its ticket counter inside the graph
+    bool capturing = false;
+    int opt_chain_graph = 0;
+    struct ChainGraph { std::vector<unsigned char> key; hipGraphExec_t exec = nullptr; bool failed = false; bool lane_launch = false; long long lane_launches = 0; int path_kernel = 0; unsigned long long ticket_after = 0; };
+    std::vector<ChainGraph> chain_graphs;
+    int warm_batch = 0, warm_n = 0;
+    bool warm_stored = false;                   // the last solve wrote its final iterate to wx / wy / wye
+    DevBuf wx, wy, wye, wrho, wsave, wscale;    // warm state (lane layout) + polish save area, parked Ruiz vectors (per workgroup slot)
+    // work distribution of the solve kernel: ticket counter (never reset: a launch uses batch + grid tickets), cost bins of the
+    // last solve and the ticket -> QP order derived from them
+    DevBuf ticket, cost_key, cost_hist, order;
+    DevBuf chain_d, chain_i;                    // workspace of pqp_optimize_path_device
+    unsigned long long ticket_next = 0;
+    long long solves = 0;                       // solve launches so far (parity selects the cost histogram being filled)
+    int hist_batch = 0, hist_n = 0;             // shape of the solve whose costs cost_key / cost_hist hold (0: none)
+    int opt_store_warm = 1, opt_order_by_cost = 0, opt_reserve_cus = 0, opt_stream_batch = -1, opt_carry = 0, opt_stream_staged = -1;      // (opt_stream_batch < 0: stream_batch_auto(n))
+    int opt_long_lines = 0;                            // PQP_OPT_LONG_LINES: 0 LDS forms only, 1 long form where the LDS form does not fit, 2 long forms
+    DevBuf line_ws;                                    // workspace of the long forms of the line kernels (one launch at a time on the stream)
+    int stream_last_batch = 0, stream_last_n = 0;      // shape of the last path_stream_kernel launch (what its workspace still holds)
+    int last_path_kernel = 0;                          // pqp_path_kernel of the last pqp_path_solve* launch (pqp_last_path_kernel)
+    DevBuf sm_act[2];                                  // final active sets of the exact TensionSmoother / postSmooth kernels (PQP_OPT_CARRY_CYCLES)
+    int sm_act_batch[2] = {0, 0}, sm_act_n[2] = {0, 0};
+    DevBuf stream_ws;                           // workspace of path_stream_kernel
+    DevBuf stream_key, stream_hist, stream_order;      // PQP_OPT_ORDER_BY_COST on that kernel: phase keys, key histogram, two slot -> QP maps
+    long long stream_solves = 0;                // ordered launches so far (parity selects the map being read)
+    int stream_order_batch = 0, stream_order_n = 0;    // shape the map being read was built for (0: none)
+    int num_cu = 0;
+    int blocks_per_cu[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // occupancy of the solve kernel variants [log2(nw)][cert]
+    static constexpr int kStage = 12;
+    DevBuf stage[kStage];                       // device copies of the arrays of a host-pointer entry point (Staging), in argument order
+    // smoother QPs: banded problem data + shared sparsity (cached per type and size)
+    DevBuf b_pband, b_q, b_aval, b_lo, b_up, b_x, b_y, b_acol, b_trow, b_tslot;
+    int b_struct_type = -1, b_struct_n = -1;
+};
+
+namespace pqp_internal __attribute__((visibility("hidden"))) {
+
+inline int hip_ok(hipError_t e, const char* what) { return e == hipSuccess ? PQP_OK : fail(PQP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+// The host-pointer form of an entry point: device copies of its arrays from the handle's pool, in argument order.  in() copies a host array in
+// (nullptr stays nullptr); out() hands out a device array, first set to the byte `fill` if that is not negative, which run() copies back when
+// the host pointer is not null.  The first failure is kept and every later step skipped.  What was enqueued reads or writes the caller's
+// memory, so no return leaves it queued: run() synchronises after the copies back, the destructor on any other return.
+class Staging {
+  public:
+    explicit Staging(pqp_handle* h) : h_(h) { rc_ = hip_ok(hipSetDevice(h->device), "hipSetDevice"); }
+    ~Staging() { if (pending_) (void)hipStreamSynchronize(h_->stream); }
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    template <class T> T* in(const T* host, size_t count) { return host ? static_cast<T*>(take(count * sizeof(T), host, nullptr, -1)) : nullptr; }
+    template <class T> T* out(T* host, size_t count, int fill = -1) { return static_cast<T*>(take(count * sizeof(T), nullptr, host, fill)); }
+    // the device form on the staged arrays, then the copies back
+    template <class F> int run(F&& device_form) {
+        if (rc_ || (rc_ = device_form())) return rc_;
+        for (int k = 0; k < n_back_ && !rc_; ++k)
+            rc_ = hip_ok(hipMemcpyAsync(back_[k].host, back_[k].dev, back_[k].bytes, hipMemcpyDeviceToHost, h_->stream), "hipMemcpyAsync(device to host)");
+        if (!rc_ && !(rc_ = hip_ok(hipStreamSynchronize(h_->stream), "hipStreamSynchronize"))) pending_ = false;
+        return rc_;
+    }
+
+  private:
+    void* take(size_t bytes, const void* src, void* host_out, int fill) {
+        if (rc_) return nullptr;
+        if (used_ == pqp_handle::kStage) { rc_ = fail(PQP_ERR_INVALID, "staging: more arrays than the handle's pool holds"); return nullptr; }
+        DevBuf& b = h_->stage[used_++];
+        if ((rc_ = b.ensure(bytes))) return nullptr;
+        pending_ = true;
+        if (src) rc_ = hip_ok(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, h_->stream), "hipMemcpyAsync(host to device)");
+        else if (fill >= 0) rc_ = hip_ok(hipMemsetAsync(b.p, fill, bytes, h_->stream), "hipMemsetAsync");
+        if (host_out) back_[n_back_++] = {host_out, b.p, bytes};
+        return rc_ ? nullptr : b.p;
+    }
+    struct Back { void* host; const void* dev; size_t bytes; };
+    pqp_handle* h_;
+    int rc_ = PQP_OK, used_ = 0, n_back_ = 0;
+    bool pending_ = false;
+    Back back_[pqp_handle::kStage];
+};
+
+// PQP_OPT_CARRY_CYCLES for an exact smoother kernel (slot 0: TensionSmoother, 1: postSmooth): the active set every scenario ended with is kept
+// on the handle; a solve of the shape of the previous one (and the buffer still where it was) starts from it (carry = 1)
+inline int sm_carry_slot(pqp_handle* h, int slot, int batch, int n, signed char*& act_io, int& carry) {
+    act_io = nullptr;
+    carry = 0;
+    if (!h->opt_carry) return PQP_OK;
+    const void* before = h->sm_act[slot].p;
+    int rc;
+    if ((rc = h->sm_act[slot].ensure((size_t)batch * n))) return rc;
+    act_io = h->sm_act[slot].as<signed char>();
+    carry = (h->sm_act_batch[slot] == batch && h->sm_act_n[slot] == n && before == h->sm_act[slot].p) ? 1 : 0;
+    h->sm_act_batch[slot] = batch; h->sm_act_n[slot] = n;
+    return PQP_OK;
+}
+
+// One launch of an exact smoother kernel (tension_exact_kernel / post_exact_kernel) on n elements per scenario: launch(K, ws) with K = the fewest
+// chunks of 64 per lane that hold them (SmRegs<K>), or K = 0 beyond 1024 with `arrays` workspace arrays per scenario in HBM (SmHbm, ws).
+// (twelve / sixteen per lane: the lane state no longer fits the registers - S2 1.8 / 3.3 KB of scratch per lane - but lines that long are rare,
+//  a point per metre of reference line, and the recursion down the lanes, not the spills, is what their time goes to)
+template <class F>
+int sm_exact_launch(pqp_handle* h, int batch, int n, int arrays, F&& launch) {
+    int rc;
+    if (n > 1024 && (rc = h->b_pband.ensure((size_t)batch * arrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
+    double* ws = n > 1024 ? h->b_pband.as<double>() : nullptr;
+    return h->launch_timed([&]() -> int {
+        if (n <= 64) launch(std::integral_constant<int, 1>(), ws);
+        else if (n <= 128) launch(std::integral_constant<int, 2>(), ws);
+        else if (n <= 256) launch(std::integral_constant<int, 4>(), ws);
+        else if (n <= 384) launch(std::integral_constant<int, 6>(), ws);
+        else if (n <= 512) launch(std::integral_constant<int, 8>(), ws);
+        else if (n <= 768) launch(std::integral_constant<int, 12>(), ws);
+        else if (n <= 1024) launch(std::integral_constant<int, 16>(), ws);
+        else launch(std::integral_constant<int, 0>(), ws);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+// One launch of a line-geometry kernel under PQP_OPT_LONG_LINES: the LDS kernel `fn` with `lds` bytes of dynamic LDS, refused with `who` where
+// they exceed one CU's, or - by long_form() - its long form, with `ws_bytes` of the handle's workspace if it takes one.  launch(go_long, ws)
+// enqueues the one (std::false_type) or the other (std::true_type).  long_fn / long_lds / long_who: the long form's own dynamic LDS (the DP's).
+template <class F>
+int line_launch(pqp_handle* h, const void* fn, size_t lds, const char* who, size_t ws_bytes, F&& launch, const void* long_fn = nullptr,
+                size_t long_lds = 0, const char* long_who = nullptr) {
+    bool go_long = false;
+    int rc = long_form(h->opt_long_lines, fn, lds, &go_long);
+    if (!rc && !go_long) rc = lds_opt_in(fn, lds, who);
+    if (!rc && go_long && long_fn) rc = lds_opt_in(long_fn, long_lds, long_who);
+    if (!rc && go_long && ws_bytes) rc = h->line_ws.ensure(ws_bytes);
+    if (rc) return rc;
+    double* ws = h->line_ws.as<double>();
+    return h->launch_timed([&]() -> int {
+        if (go_long) launch(std::true_type(), ws);
+        else launch(std::false_type(), ws);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+// a distance-map layer the kernels can index with 32 bits (obstacle_distance, pqp_line_device.hpp)
+inline bool geometry_ok(const pqp_grid_geometry* g) {
+    return g && g->rows >= 2 && g->cols >= 2 && g->resolution > 0.0 && (long long)g->rows * g->cols < (1ll << 30);
+}
+
+}  // namespace pqp_internal

@@ -1,0 +1,228 @@
+// pqp_maps.hip — the entry points of include/pqp.h around the obstacle distance map and the planned paths: the distance layer from an
+// occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
+// group's best (pqp_select_kernels.inc).  Their kernels, launchers and entry points.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <atomic>
+#include <mutex>
+#include <new>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "pqp_defaults.hpp"
+#include "pqp_path_lane.hpp"
+#include "pqp_wave.hpp"
+#include "pqp_line_device.hpp"
+#include "pqp_internal.hpp"
+
+using namespace pqp_internal;
+
+#include "pqp_distance_kernels.inc"
+#include "pqp_footprint_kernels.inc"
+#include "pqp_select_kernels.inc"
+
+extern "C" {
+
+// ---- the obstacle distance layer from an occupancy grid (src/test/demo.cpp:104-113) ------------------------------------------------
+static bool distance_layer_ok(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, const float* dist) {
+    return h && grid && dist && n_maps >= 1 && geometry_ok(geom);
+}
+
+int pqp_distance_layer_device(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist) {
+    if (!distance_layer_ok(h, n_maps, geom, grid, dist))
+        return fail(PQP_ERR_INVALID, "pqp_distance_layer: bad argument (n_maps >= 1; a map of 2 x 2 to 2^30 cells, resolution > 0)");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::DistanceArgs a;
+    a.grid = grid; a.out = reinterpret_cast<int32_t*>(dist); a.n_maps = n_maps; a.rows = geom->rows; a.cols = geom->cols;
+    const pqp::edt::Shape sh = pqp::edt::shape_of(geom->rows, geom->cols);
+    a.site_bits = sh.site_bits; a.empty_d2 = sh.empty_d2; a.res = (float)geom->resolution;
+    const long long lines = (long long)n_maps * geom->cols, lanes = (long long)n_maps * geom->rows;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::distance_lines_kernel, dim3((unsigned)std::min((lines + 3) / 4, 1ll << 20)), dim3(256), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        const unsigned blocks = (unsigned)std::min((lanes + 63) / 64, 1ll << 20);
+        if (sh.wide) hipLaunchKernelGGL(pqp::distance_envelope_kernel<int64_t>, dim3(blocks), dim3(64), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::distance_envelope_kernel<int32_t>, dim3(blocks), dim3(64), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_distance_layer(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom, const uint8_t* grid, float* dist) {
+    if (!distance_layer_ok(h, n_maps, geom, grid, dist))
+        return fail(PQP_ERR_INVALID, "pqp_distance_layer: bad argument (n_maps >= 1; a map of 2 x 2 to 2^30 cells, resolution > 0)");
+    const size_t cells = (size_t)n_maps * geom->rows * geom->cols;
+    Staging st(h);
+    const uint8_t* d_grid = st.in(grid, cells);
+    float* d_dist = st.out(dist, cells);
+    return st.run([&]() -> int { return pqp_distance_layer_device(h, n_maps, geom, d_grid, d_dist); });
+}
+
+// ---- vehicle footprints against the distance layer (collision_checker.cpp:17-58, car_geometry.cpp:38-72) ----------------------------
+void pqp_car_default_geometry(pqp_car_geometry* c) {
+    if (!c) return;
+    c->width = 2.0;                 // planning_flags.cpp:10
+    c->rear_length = -1.0;          // :18
+    c->front_length = 3.9;          // :20
+}
+
+static bool car_ok(const pqp_car_geometry* c) {
+    return c && std::isfinite(c->width) && std::isfinite(c->rear_length) && std::isfinite(c->front_length);
+}
+
+int pqp_car_circles(const pqp_car_geometry* c, double* circles) {
+    if (!car_ok(c) || !circles) return fail(PQP_ERR_INVALID, "pqp_car_circles: bad argument (a finite car geometry)");
+    // CollisionChecker's car_(FLAGS_car_width, fabs(FLAGS_rear_length), FLAGS_front_length) -> CarGeometry(width, back_length, front_length)
+    const double width = c->width, back_length = std::fabs(c->rear_length), front_length = c->front_length;
+    const double length = front_length + back_length;
+    const double fl_x = front_length, fl_y = width / 2.0, fr_x = front_length, fr_y = -width / 2.0;
+    const double rl_x = -back_length, rl_y = width / 2.0, rr_x = -back_length, rr_y = -width / 2.0;
+    // CarGeometry::setCircles, car_geometry.cpp:38-57, term by term
+    const double bounding_x = (front_length - back_length) / 2.0;
+    const double bounding_r = std::sqrt(std::pow(length / 2, 2) + std::pow(width / 2, 2));
+    const double small_circle_shift = width / 4.0;
+    const double small_circle_radius = std::sqrt(2 * std::pow(small_circle_shift, 2));
+    const double large_circle_radius = std::sqrt(std::pow(width, 2) + std::pow((length - width) / 2.0, 2)) / 2;
+    const double v[7][3] = {{rr_x + small_circle_shift, rr_y + small_circle_shift, small_circle_radius},
+                            {rl_x + small_circle_shift, rl_y - small_circle_shift, small_circle_radius},
+                            {fr_x - small_circle_shift, fr_y + small_circle_shift, small_circle_radius},
+                            {fl_x - small_circle_shift, fl_y - small_circle_shift, small_circle_radius},
+                            {bounding_x + (length - width) / 4, 0, large_circle_radius},
+                            {bounding_x - (length - width) / 4, 0, large_circle_radius},
+                            {bounding_x, 0, bounding_r}};
+    std::memcpy(circles, v, sizeof(v));
+    return PQP_OK;
+}
+
+static bool footprint_ok(pqp_handle* h, int batch, int n, int stride, const double* states, const float* dist, const pqp_grid_geometry* geom,
+                         const pqp_car_geometry* car, int mode, const uint8_t* free_out, const int32_t* first_collision) {
+    return h && states && dist && free_out && first_collision && batch >= 1 && n >= 1 && n <= (1 << 30) && stride >= 3 && geometry_ok(geom) &&
+           car_ok(car) && (mode == PQP_FOOTPRINT_CIRCLES || mode == PQP_FOOTPRINT_BOUNDING_FIRST);
+}
+
+int pqp_footprint_check_device(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist,
+                               const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
+                               int32_t* first_collision, double* margin) {
+    if (!footprint_ok(h, batch, n, stride, states, dist, geom, car, mode, free_out, first_collision))
+        return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument (stride >= 3; a finite car geometry; mode CIRCLES or BOUNDING_FIRST; "
+                                     "a map layer of 2 x 2 to 2^30 cells)");
+    PQP_HIP(hipSetDevice(h->device));
+    double circles[7][3];
+    int rc;
+    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
+    pqp::FootprintArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.states = states; a.n_of = n_of; a.dist = dist; a.map_of = map_of; a.g = *geom;
+    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
+    a.free_out = free_out; a.first_collision = first_collision; a.margin = margin;
+    return h->launch_timed([&]() -> int {
+        if (mode == PQP_FOOTPRINT_CIRCLES)
+            hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_CIRCLES>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
+        else
+            hipLaunchKernelGGL(pqp::footprint_check_kernel<PQP_FOOTPRINT_BOUNDING_FIRST>, dim3(batch), dim3(pqp::kFootprintThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const double* states, const int32_t* n_of, const float* dist, int n_maps,
+                        const int32_t* map_of, const pqp_grid_geometry* geom, const pqp_car_geometry* car, int mode, uint8_t* free_out,
+                        int32_t* first_collision, double* margin) {
+    if (!footprint_ok(h, batch, n, stride, states, dist, geom, car, mode, free_out, first_collision) || n_maps < 1)
+        return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument");
+    if (map_of)
+        for (int b = 0; b < batch; ++b)
+            if (map_of[b] < 0 || map_of[b] >= n_maps) return fail(PQP_ERR_INVALID, "pqp_footprint_check: map_of outside [0, n_maps)");
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_states = st.in(states, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const float* d_dist = st.in(dist, (size_t)n_maps * geom->rows * geom->cols);
+    const int32_t* d_map_of = st.in(map_of, batch);
+    uint8_t* d_free = st.out(free_out, bn);
+    int32_t* d_first = st.out(first_collision, batch);
+    double* d_margin = margin ? st.out(margin, bn) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_footprint_check_device(h, batch, n, stride, d_states, d_n_of, d_dist, d_map_of, geom, car, mode, d_free, d_first, d_margin);
+    });
+}
+
+// ---- scores of candidate paths and each group's best ----------------------------------------------------------------------------------
+void pqp_select_default_params(pqp_select_params* p) {
+    if (!p) return;
+    pqp_params d;
+    pqp::default_params(&d);
+    p->weight_kappa = d.weight_kappa;          // base_solver.cpp:124
+    p->weight_dkappa = d.weight_dkappa;        // :125
+    p->weight_offset = 0.0;                    // :123: weight_l is 0
+    p->weight_length = 0.0;
+    p->weight_clearance = 0.0;
+    p->clearance_want = d.expected_safety_margin;      // FLAGS_expected_safety_margin, planning_flags.cpp:95
+    p->per_waypoint = 0;
+    p->require_free = 1;
+}
+
+static bool select_ok(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, int groups,
+                      const int32_t* group_start, const double* terms, const int32_t* best, const double* best_paths, const int32_t* best_n) {
+    return h && prm && paths && group_start && terms && best && batch >= 1 && n >= 1 && n <= (1 << 30) && stride >= 7 && groups >= 0 &&
+           (best_paths != nullptr) == (best_n != nullptr);
+}
+
+int pqp_select_paths_device(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                            const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                            const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n) {
+    if (!select_ok(h, prm, batch, n, stride, paths, groups, group_start, terms, best, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, "pqp_select_paths: bad argument (stride >= 7; groups >= 0; best_paths and best_n both or neither)");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::SelectArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.groups = groups; a.paths = paths; a.n_of = n_of; a.status = status; a.stage = stage;
+    a.first_collision = first_collision; a.margin = margin; a.group_start = group_start; a.prm = *prm; a.terms = terms; a.best = best;
+    a.best_paths = best_paths; a.best_n = best_n;
+    constexpr int per_block = pqp::kSelectThreads / 64;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::path_score_kernel, dim3((unsigned)((batch + per_block - 1) / per_block)), dim3(pqp::kSelectThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        if (groups > 0) {
+            hipLaunchKernelGGL(pqp::group_select_kernel, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(pqp::kSelectThreads), 0, h->stream, a);
+            PQP_HIP(hipGetLastError());
+        }
+        return PQP_OK;
+    });
+}
+
+int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                     const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                     const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n) {
+    if (!select_ok(h, prm, batch, n, stride, paths, groups, group_start, terms, best, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, "pqp_select_paths: bad argument (stride >= 7; groups >= 0; best_paths and best_n both or neither)");
+    for (const double v : {prm->weight_kappa, prm->weight_dkappa, prm->weight_offset, prm->weight_length, prm->weight_clearance, prm->clearance_want})
+        if (!std::isfinite(v)) return fail(PQP_ERR_INVALID, "pqp_select_paths: a parameter that is not finite");
+    if (group_start[0] != 0 || group_start[groups] != batch) return fail(PQP_ERR_INVALID, "pqp_select_paths: group_start must run from 0 to batch");
+    for (int g = 0; g < groups; ++g)
+        if (group_start[g + 1] < group_start[g]) return fail(PQP_ERR_INVALID, "pqp_select_paths: group_start must be ascending");
+    // (from here on groups >= 1: group_start runs from 0 to batch >= 1)
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_status = st.in(status, batch);
+    const int32_t* d_stage = st.in(stage, batch);
+    const int32_t* d_first = st.in(first_collision, batch);
+    const double* d_margin = st.in(margin, bn);
+    const int32_t* d_start = st.in(group_start, (size_t)groups + 1);
+    double* d_terms = st.out(terms, (size_t)batch * PQP_SCORE_STRIDE);
+    int32_t* d_best = st.out(best, groups);
+    double* d_best_paths = best_paths ? st.out(best_paths, (size_t)groups * n * 7) : nullptr;
+    int32_t* d_best_n = best_n ? st.out(best_n, groups) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_select_paths_device(h, prm, batch, n, stride, d_paths, d_n_of, d_status, d_stage, d_first, d_margin, groups, d_start, d_terms,
+                                       d_best, d_best_paths, d_best_n);
+    });
+}
+
+}  // extern "C"

@@ -8,7 +8,7 @@
 // pqp_multi_gather_paths below: the result slabs the shards keep in device memory, gathered over RCCL (xGMI) so that every GPU holds every
 // path - the one exchange step north_star names, and the only place this library touches RCCL (dlopen'ed on first use: a caller that never
 // gathers needs no librccl).  The one-process-per-GPU counterpart is path_optimizer_2_amd/shard.py (torch.distributed).
-// Plain host C++ over the entry points of pqp_kernels.hip + the HIP runtime's memory API; part of libpqp_hip.so.
+// Plain host C++ over the path-QP entry points of pqp_kernels.hip + the HIP runtime's memory API; part of libpqp_hip.so.
 // The reference has no counterpart (one path per call, single-threaded: base_solver.cpp:56-95).
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>

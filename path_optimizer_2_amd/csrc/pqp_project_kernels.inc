@@ -1,19 +1,19 @@
-// pqp_project_kernels.inc — included by pqp_kernels.hip after pqp_select_kernels.inc.  Many points onto their reference line: Cartesian to
+// pqp_project_kernels.inc — included by pqp_lines.hip after pqp_corridor_kernels.inc.  Many points onto their reference line: Cartesian to
 // Frenet (pqp_project_points), the inverse of pqp_offsets_to_points.
 //   getProjection / getProjectionByNewton      src/tools/tools.cpp:66-126
 //   getHeading, getCurvature, global2Local     src/tools/tools.cpp:32-44, 57-64
 //   the signed offset and the heading error    src/path_optimizer.cpp:73-85, src/reference_path_smoother/reference_path_smoother.cpp:148-165
-// spline_projection (pqp_corridor_kernels.inc) is the same search for ONE point of a line.  Its 1 m coarse scan evaluates the spline at
+// spline_projection_wave (pqp_line_device.hpp) is the same search for ONE point of a line.  Its 1 m coarse scan evaluates the spline at
 // 0, 1, 2, ... <= length whatever the point is, so here a workgroup makes those evaluations once - one sample per lane, spline_eval3 on the
 // table where it lies (HBM through L2: ~log2(m) knots per evaluation, no knot-count cap, no workspace) - and leaves them in LDS, 16 bytes per
 // sample, kProjectTile samples at a time with the end sample behind them.  Then every lane owns one point and scans the samples: all
 // lanes read the same address, a broadcast without a bank conflict.  A lane carries its running minimum from tile to tile, so the first
-// strict minimum wins across tile borders as in the serial scan; the end compare and the Newton steps are spline_projection's, word for word.
+// strict minimum wins across tile borders as in the serial scan; the end compare and the Newton steps are spline_projection_wave's, word for word.
 //
 // The scan compares sqrt(dx*dx + dy*dy) as the reference does, but takes the square root only of a candidate: with d2 the squared distance
 // of a sample and best2 that of the minimum so far, d2 >= best2 implies sqrt(d2) >= sqrt(best2) (a correctly rounded square root is
 // monotone), which the reference's strict `<` rejects; only d2 < best2 needs the root and the reference's own compare.  The first minimum,
-// hence s, is bit for bit what spline_projection returns.
+// hence s, is bit for bit what spline_projection_wave returns.
 
 namespace pqp {
 

@@ -1,4 +1,4 @@
-// pqp_select_kernels.inc — included by pqp_kernels.hip after pqp_footprint_kernels.inc.  Scores of candidate paths and each group's best
+// pqp_select_kernels.inc — included by pqp_maps.hip after pqp_footprint_kernels.inc.  Scores of candidate paths and each group's best
 // (pqp_select_paths).  The reference plans one path per call and has nothing to rank; the default weights are the path QP's own
 //   weight_kappa 20, weight_dkappa 100, weight_l 0          src/solver/base_solver.cpp:123-147 (the diagonal of P)
 //   clearance_want 0.6                                       src/config/planning_flags.cpp:95 (FLAGS_expected_safety_margin)

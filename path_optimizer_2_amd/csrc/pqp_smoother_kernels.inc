@@ -1,4 +1,4 @@
-// pqp_smoother_kernels.inc — included by pqp_kernels.hip.  GPU side of the reference-line smoothing QPs
+// pqp_smoother_kernels.inc — included by pqp_smoothers.hip.  GPU side of the reference-line smoothing QPs
 // (SURVEY.md §8a rows S1-S3): per-type assemble kernels (values in the point-interleaved order that makes the reduced
 // KKT banded), the generic banded ADMM solve kernel (pqp_banded_qp.hpp) and the per-type finish kernels - the reference's
 // formulation and iteration, what a handle with polish = 0 runs -, and the exact kernels for handles that ask for optima:
@@ -11,7 +11,7 @@ namespace pqp {
 template <int K, bool MAX>
 __device__ __forceinline__ void wg_reduce_dyn(double (&v)[K], double* red) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = MAX ? wave_max(v[k]) : wave_sum(v[k]);        // DPP, wave-uniform (pqp_kernels.hip)
+    for (int k = 0; k < K; ++k) v[k] = MAX ? wave_max(v[k]) : wave_sum(v[k]);        // DPP, wave-uniform (pqp_wave.hpp)
     const int nw = (blockDim.x + 63) >> 6;
     if (nw > 1) {
         const int w = threadIdx.x >> 6;

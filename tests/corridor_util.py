@@ -58,7 +58,7 @@ def tab_close(tab, ext, want_tab, want_ext=None):
         assert np.abs(np.asarray(ext) - np.asarray(want_ext)).max() <= SPLINE_TOL * max(1.0, float(np.abs(want_ext).max()))
 
 
-# ---- LDS budgets of the line-geometry kernels (pqp_corridor_kernels.inc, launchers in pqp_kernels.hip) -----------------------------
+# ---- LDS budgets of the line-geometry kernels (pqp_corridor_kernels.inc, launchers in pqp_lines.hip) -----------------------------
 LDS_PER_CU = 160 * 1024
 # static LDS of each kernel as the compiler reports it ("LDS Size"): its __shared__ variables padded to the 16-byte alignment of the
 # dynamic array behind them.  The launchers count it against LDS_PER_CU (tests/test_kernel_resources.py pins these numbers).

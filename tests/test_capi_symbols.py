@@ -63,3 +63,47 @@ def test_stream_batch_default_is_the_measured_crossover(hip_lib):
     assert f(200) == 30000 and f(256) == 49152
     assert f(300) == 14400 and f(512) == 24576
     assert all(f(n) > 8192 for n in range(2, 129))
+
+
+PQP_ERR_INVALID = -1        # include/pqp.h
+
+
+def _refused_calls(lib):
+    """One argument-validating entry point per translation unit of the library, each refused for its arguments before it touches a device:
+    (the name its message carries - the entry point's, which the host and the `_device` form share -, the call)."""
+    sizes = capi.PqpSizes()
+    return [
+        ("pqp_corridor_bounds", lambda: lib.pqp_corridor_bounds_device(None, 1, 1, 3, None, None, None, None, None, None, None, None, None, None)),       # pqp_lines.hip
+        ("pqp_post_smooth", lambda: lib.pqp_post_smooth_device(None, 1, 4, None, None, None, None, None, None, None, None)),                              # pqp_smoothers.hip
+        ("pqp_footprint_check", lambda: lib.pqp_footprint_check_device(None, 1, 1, 3, None, None, None, None, None, None, 0, None, None, None)),           # pqp_maps.hip
+        ("pqp_optimize_path", lambda: lib.pqp_optimize_path_device(None, None, None, 1, 4, None, None, None, None, None, None, None, None, None, None,
+                                                                    None, None, None)),                                                                   # pqp_chain.hip
+        ("pqp_path_sizes", lambda: lib.pqp_path_sizes(None, 1, None, C.byref(sizes))),                                                                   # pqp_kernels.hip
+    ]
+
+
+def test_last_error_is_one_thread_local_message_across_translation_units(hip_lib):
+    """pqp_last_error's message is one thread-local object of the library, whichever translation unit an entry point lives in: a refusal in
+    any of them is what pqp_last_error reports next (a second definition in another object would leave the previous unit's message there),
+    and another thread's refusal does not show in this thread's message."""
+    import threading
+    for name, call in _refused_calls(hip_lib):
+        assert call() == PQP_ERR_INVALID, name
+        msg = hip_lib.pqp_last_error().decode()
+        assert msg.startswith(name + ":"), (name, msg)
+    calls = _refused_calls(hip_lib)
+    (first_name, first_call), (other_name, other_call) = calls[0], calls[1]
+    assert first_call() == PQP_ERR_INVALID
+    seen = {}
+
+    def other():
+        seen["before"] = hip_lib.pqp_last_error().decode()         # a thread that has made no call has no message
+        seen["rc"] = other_call()
+        seen["after"] = hip_lib.pqp_last_error().decode()
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen["rc"] == PQP_ERR_INVALID and seen["before"] == "" and seen["after"].startswith(other_name + ":"), seen
+    mine = hip_lib.pqp_last_error().decode()
+    assert mine.startswith(first_name + ":") and other_name not in mine, mine

@@ -256,7 +256,7 @@ def test_clearance_lookup_on_the_device(hip_lib):
 
 
 def test_chain_replayed_as_a_hip_graph_is_bit_identical(hip_lib):
-    """PQP_OPT_CHAIN_GRAPH: the chain's ~25 launches on two streams captured once per argument set and replayed (csrc/pqp_chain.inc).  Same
+    """PQP_OPT_CHAIN_GRAPH: the chain's ~25 launches on two streams captured once per argument set and replayed (csrc/pqp_chain.hip).  Same
     device buffers call after call, their CONTENTS moving like planning cycles: every call's result equals the plainly launched chain's bit for bit -
     through the plain first calls, the two captures (one per parity of the cost-order double buffer) and the replays - and other arguments fall
     back to plain launches."""
@@ -363,3 +363,59 @@ def test_chain_graph_on_the_lane_per_qp_kernel_leaves_the_ticket_counter_alone(h
     for k in range(6):
         for a, b_ in zip(results[0][k], results[1][k]):
             np.testing.assert_array_equal(a, b_)
+
+
+def test_chain_graph_is_not_replayed_after_the_smoother_handle_reallocates(hip_lib):
+    """The library's allocation generation is one counter, whichever translation unit a buffer grows in: a captured chain holds device pointers of
+    both handles' workspaces, and a smoother call that makes the smoother handle reallocate (pqp_smoothers.hip) must keep pqp_optimize_path_device
+    (pqp_chain.hip) from replaying it.  Replay, grow the smoother handle's buffers, call the chain again: bit for bit a fresh pair's plain chain."""
+    import torch
+    B = 4
+    sc = _scenarios(B, seed=7)
+    dev = torch.device("cuda", 0)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    p = lambda x: capi.C.c_void_p(x.data_ptr())
+    d_pts, d_np, d_st, d_tg, d_map = t(sc["pts"], np.float64), t(sc["n_pts"], np.int32), t(sc["start"], np.float64), t(sc["target"], np.float64), t(sc["map_of"], np.int32)
+    d_dist = t(np.transpose(sc["dist"], (0, 2, 1)), np.float32)
+
+    def pair(graph):
+        h = capi.Handle(capi.production_params(), device=0, max_batch=B, max_n=256)
+        hs = capi.Handle(_smoother_params(), device=0, max_batch=B, max_n=128)
+        h.set_option(capi.OPT_CHAIN_GRAPH, graph); hs.set_option(capi.OPT_CHAIN_GRAPH, graph)
+        out = torch.zeros((B, 256, 7), dtype=torch.float64, device=dev)
+        ints = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4)]          # n_out, status, stage, iters
+        cfg = h.chain_config()                                                            # default-sized scenarios: n_max = 256
+
+        def run():
+            h._check(h.lib.pqp_optimize_path_device(h._h, hs._h, capi.C.byref(cfg), B, sc["pts"].shape[1], p(d_pts), p(d_np), p(d_st), p(d_tg), p(d_dist), p(d_map),
+                                                    capi.C.byref(sc["geom"]), None, p(out), *(p(x) for x in ints)))
+            h.sync(); hs.sync()
+            return [out.cpu().numpy().copy()] + [x.cpu().numpy().copy() for x in ints]
+        return h, hs, run
+
+    h0, hs0, run0 = pair(0)
+    want = run0()
+    h0.close(); hs0.close()
+    assert (want[3] == 0).sum() >= B // 2          # most scenarios give a path
+    h, hs, run = pair(1)
+    # until the chain replays: a call launched as a graph records no timing events (pqp_last_kernel_ms has nothing to report), and of three such
+    # calls in a row at most two are captures (one per parity of the path handle's solve count), so the third is a replay
+    ms, in_a_row = capi.C.c_float(), 0
+    for _ in range(12):
+        got = run()
+        for a, b_ in zip(want, got):
+            np.testing.assert_array_equal(a, b_)
+        in_a_row = in_a_row + 1 if h.lib.pqp_last_kernel_ms(h._h, capi.C.byref(ms)) != 0 else 0
+        if in_a_row == 3:
+            break
+    assert in_a_row == 3, "the chain never replayed"
+    # the smoother handle reallocates: a batch larger than anything it has seen
+    n = 32
+    s = np.tile(np.arange(n, dtype=np.float64), (64, 1))
+    y = 0.3 * np.sin(0.2 * s) + 0.01 * np.arange(64)[:, None]
+    sm = hs.smooth_tension2(s.copy(), y, np.arctan(0.06 * np.cos(0.2 * s)), np.zeros_like(s), s.copy())
+    assert (sm["status"] == 1).all(), sm["status"]
+    got = run()
+    for a, b_ in zip(want, got):
+        np.testing.assert_array_equal(a, b_)
+    h.close(); hs.close()
