@@ -379,8 +379,9 @@ def test_smallest_and_largest_paths(hip_lib, n):
     h = capi.Handle(_polished(), max_batch=2, max_n=n)
     r = h.solve(b["ref"], b["bounds"], b["scal"], passes=1)
     assert (r["status"] == 1).all()
-    ref = O.solve_path(b["ref"][0], b["bounds"][0], b["scal"][0], st=ORACLE_TIGHT)
-    assert np.abs(r["out"][0][:, 3:5] - ref[-1]["out"][:, 3:5]).max() < (5e-6 if n <= 300 else 5e-5)
+    for q in range(2):
+        ref = O.solve_path(b["ref"][q], b["bounds"][q], b["scal"][q], st=ORACLE_TIGHT)
+        assert np.abs(r["out"][q][:, 3:5] - ref[-1]["out"][:, 3:5]).max() < (5e-6 if n <= 300 else 5e-5), q
     h.close()
 
 
