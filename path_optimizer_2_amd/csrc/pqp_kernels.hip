@@ -624,7 +624,7 @@ static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of,
     while (64 * nw < n) { nw *= 2; lg += 1; }           // one waypoint per lane: T = 64 * nw >= n threads per QP
     const int T_lanes = 64 * nw;
     const bool save_lds = nw <= pqp::kSaveLdsMaxNw;
-    const size_t lds = (size_t)pqp::ShLayout{T_lanes}.total(save_lds, save_lds) * 8;
+    const size_t lds = (size_t)pqp::ShLayout{T_lanes}.total(save_lds) * 8;
     // two variants of every kernel: with and without OSQP's primal infeasibility certificate (prm.eps_prim_inf > 0)
     const bool cert = h->prm.eps_prim_inf > 0.0 && h->prm.prim_inf_after <= 0;
     const void* fn = nullptr;

@@ -285,8 +285,6 @@ struct Slot {
     double Dinv[6], GL[9], GR[9];
     // per-iteration scratch that crosses a phase boundary
     double r[3], rv, rsf, rsr, xt[6];
-    // contexts with kCstAcc: the halves of the pass constants that live in the accumulator half of the register file (see PathQp::acc_get)
-    int acc[24];
 };
 // setup-time state (dead inside the ADMM loop)
 struct SlotSetup {
@@ -314,6 +312,10 @@ struct EndRows {
                             // previous late infeasibility check
 };
 
+// Up to this many wavefronts per QP the polish save area, the parked Ruiz vectors and the dual snapshot live in LDS (Ctx::kSaveLds); beyond,
+// in the workgroup slot's global memory.  4 is what fits (256 lanes: 157 KB).  One rule for the kernels, the launcher and the host emulation.
+constexpr int kSaveLdsMaxNw = 4;
+
 // shared-memory layout in doubles, T = threads per QP = padded number of waypoints.  The per-iteration exchange
 // buffers and the factor-time exchange buffer are never live at the same time and share one region.
 struct ShLayout {
@@ -335,19 +337,17 @@ struct ShLayout {
     PQP_HD int red() const { return 26 * T + 32; }          // reduction scratch [8][16]
     PQP_HD int poison() const { return 26 * T + 32 + 15; }  // (a column of the reduction scratch no wavefront uses) 1.0: the scenario of this QP is not a number (F_BADIN)
                                                             // - zeroed in load(), set in assemble(), read once per pass behind it
-    // per-waypoint pass constants that are read once per iteration (kCstLds contexts keep them here instead of in registers):
-    // [12][T] sig(6) lo(2) up(2) idsf idsr, one array per constant (unit stride over the lanes: conflict-free)
     // 24 zeros (written once per workgroup): where a lane has no neighbour its read is redirected here, so the reads of a phase
     // need no exec-mask change and no select (a conditional LDS read costs two scalar instructions around every ds_read)
     PQP_HD int zero() const { return 26 * T + 32 + 128; }
-    PQP_HD int cst() const { return 26 * T + 32 + 128 + 24; }
-    // contexts with kSaveLds (T <= 256) keep the polish save area here instead of in global memory: [T][PQP_SAVE_STRIDE]
+    // Contexts with kSaveLds (T <= 256) keep three regions here that the others keep in the workgroup slot's global memory.  The Ruiz vectors
+    // parked between the passes: [12][T] D(6) E(6), one array per element (unit stride over the lanes: conflict-free)
+    PQP_HD int scale() const { return 26 * T + 32 + 128 + 24; }
+    // ... the polish save area: [T][PQP_SAVE_STRIDE]
     PQP_HD int save() const { return 38 * T + 32 + 128 + 24; }
     // ... and the dual iterate of the previous late infeasibility check, [T][6] (prim_inf_after)
     PQP_HD int ysnap() const { return (38 + PQP_SAVE_STRIDE) * T + 32 + 128 + 24; }
-    // (contexts whose save area lives in global memory park their scaling vectors there too: without pass constants in LDS the constants
-    //  region is then unused and not allocated - 26 T doubles = 27 KB per QP at 128 waypoints)
-    PQP_HD int total(bool save_in_lds = false, bool cst_in_lds = true) const { return (save_in_lds ? 44 + PQP_SAVE_STRIDE : (cst_in_lds ? 38 : 26)) * T + 32 + 128 + 24; }
+    PQP_HD int total(bool save_in_lds) const { return (save_in_lds ? 44 + PQP_SAVE_STRIDE : 26) * T + 32 + 128 + 24; }
     // y_k - y_{k-1} of the last iteration, [T][6] (infeasibility certificate): lives in the part of the factor-time buffer
     // the iteration does not use; every iteration rewrites it, and a check never follows a factorisation directly
     PQP_HD int yprev() const { return 12 * T; }
@@ -500,15 +500,8 @@ PQP_HD void record_cost(const PathSolveArgs& a, int qp, int cost, int at_least_b
 #endif
 }
 
-// uniform (per-QP) solver scalars; handed by value across the hot / cold boundary
-struct Uni {
-    double rho, cscale, kap, alpha;
-    int kkt_solves;
-    int factors;
-    int polishing;
-    int cert;
-};
-// cold operations (rare, register-hungry): executed out of line on a memory-resident copy of the lane state
+// cold operations (rare, register-hungry): they run inline on the same lane state as the ADMM loop; PathQp::run() issues all of them from
+// one call site, which keeps the kernel's code size down
 enum ColdOp : int {
     COLD_BEGIN_PASS = 0,     // i0 = pass index, i1 = have_warm: [load, warm-load], assemble, Ruiz, start rows, factor
     COLD_REFACTOR = 1,       // i0 = RefactorKind, d0 = parameter: penalty change + factor
@@ -521,14 +514,13 @@ enum RefactorKind : int { RF_RESCALE = 0 /* d0 = ratio */, RF_POLISH_BEGIN = 1, 
 // =======================================================================================================
 // The solver.  Ctx provides:
 //   int  T()                              threads per QP (power of two, >= 64)
-//   double* sh()                          shared scratch of ShLayout(T).total() doubles
+//   double* sh()                          shared scratch of ShLayout(T).total(kSaveLds) doubles
 //   template<F> void phase(F f)           run f(t, Lane&) for every thread, then synchronise the workgroup
 //   template<F> void phase_w(F f)         the same, but only the lanes of one wavefront need to see each other's LDS writes
 //   template<int K,F> void reduce_max/sum(double (&out)[K], F f)   f(t, Lane&, double (&v)[K])
-//   void cold(PathQp&, op, i0, i1, d0)    run do_cold() (possibly out of line)
-//   static constexpr bool kCstLds         12 per-waypoint pass constants live in LDS (ShLayout::cst) instead of in Slot fields
-//   static constexpr bool kParkScale      the Ruiz vectors D, E are parked (LDS or PathSolveArgs::wscale) between the passes
-//   static constexpr bool kSaveLds        the polish save area (and the parked D, E) live in LDS: ShLayout::total(true) doubles
+//   void cold(PathQp&, op, i0, i1, d0)    run do_cold() on the same lane state
+//   static constexpr bool kSaveLds        the polish save area, the parked Ruiz vectors D, E and the dual snapshot live in LDS (ShLayout::save,
+//                                         scale, ysnap) instead of in the workgroup slot's global memory (PathSolveArgs::wsave, wscale)
 // =======================================================================================================
 // CERT: compile the primal infeasibility certificate in.  It is a template parameter because its mere presence in the kernel
 // (one more cold operation + six LDS stores per iteration) costs the ADMM iteration 12 % through register allocation;
@@ -688,9 +680,7 @@ struct PathQp {
                 // (the QP's verdict lives in one LDS word - zeroed in load(), read by residuals() - not in a lane field of the ADMM loop)
                 if (!(mark == 0.0) || !ds_ok || (S.flags & F_BADIN)) sh[L.poison()] = 1.0;
             }
-            if constexpr (kAcc) { acc_set(S, C_LO, lo0); acc_set(S, C_LO + 1, lo1); acc_set(S, C_UP, up0); acc_set(S, C_UP + 1, up1); }
-            else if constexpr (kCst) { cst_set(t, C_LO, lo0); cst_set(t, C_LO + 1, lo1); cst_set(t, C_UP, up0); cst_set(t, C_UP + 1, up1); }
-            else { S.lo[0] = lo0; S.up[0] = up0; S.lo[1] = lo1; S.up[1] = up1; }
+            S.lo[0] = lo0; S.up[0] = up0; S.lo[1] = lo1; S.up[1] = up1;
             if (S.flags & F_LAST) {                                         // :250-259
                 EndRows* er = end_rows();
                 double elo = -kInfty, eup = kInfty;
@@ -708,28 +698,10 @@ struct PathQp {
         });
     }
 
-    // the box of inequality row k (0: curvature, 1: front, 2: rear) as assembled ...
-    // Pass constants of a waypoint that the iteration reads once: in registers (Slot fields) or, in contexts with kCstLds, in LDS -
-    // 24 registers less in the ADMM loop, which is what lets two wavefronts share a SIMD.
-    static constexpr bool kCst = Ctx::kCstLds;
-    // ... or (kCstAcc, the device) in the ACCUMULATOR half of the register file, by their own v_accvgpr_write / _read at the one definition and the one
-    // use per solve: gfx950 gives a one-wavefront-per-SIMD kernel 256 + 256 registers but VALU operands come from the first 256 only, and the compiler,
-    // left to park what does not fit, shuffles hundreds of registers between the halves around every phase (tools/isa_mix.py).  What is used once
-    // per solve is parked by hand: one read per use, no shuffles.
-    static constexpr bool kAcc = Ctx::kCstAcc;
-    enum : int { C_SIG = 0, C_LO = 6, C_UP = 8, C_IDSF = 10, C_IDSR = 11 };
-    PQP_HD double cst_get(int t, int c) const { return sh[L.cst() + c * T + t]; }
-    PQP_HD void cst_set(int t, int c, double v) const { sh[L.cst() + c * T + t] = v; }
-    PQP_HD double acc_get(const Slot& S, int c) const { return Ctx::acc_read(S.acc[2 * c], S.acc[2 * c + 1]); }
-    PQP_HD void acc_set(Slot& S, int c, double v) const { Ctx::acc_write(v, S.acc[2 * c], S.acc[2 * c + 1]); }
-    PQP_HD double sig_of(const Slot& S, int t, int k) const { if constexpr (kAcc) return acc_get(S, C_SIG + k); else if constexpr (kCst) return cst_get(t, C_SIG + k); else return S.sig[k]; }
-    PQP_HD void set_sig(Slot& S, int t, int k, double v) const { if constexpr (kAcc) acc_set(S, C_SIG + k, v); else if constexpr (kCst) cst_set(t, C_SIG + k, v); else S.sig[k] = v; }
-    PQP_HD double idsf_of(const Slot& S, int t) const { if constexpr (kAcc) return acc_get(S, C_IDSF); else if constexpr (kCst) return cst_get(t, C_IDSF); else return S.idsf; }
-    PQP_HD double idsr_of(const Slot& S, int t) const { if constexpr (kAcc) return acc_get(S, C_IDSR); else if constexpr (kCst) return cst_get(t, C_IDSR); else return S.idsr; }
-    PQP_HD double lo_of(const Slot& S, int t, int j) const { if constexpr (kAcc) return acc_get(S, C_LO + j); else if constexpr (kCst) return cst_get(t, C_LO + j); else return S.lo[j]; }
-    PQP_HD double up_of(const Slot& S, int t, int j) const { if constexpr (kAcc) return acc_get(S, C_UP + j); else if constexpr (kCst) return cst_get(t, C_UP + j); else return S.up[j]; }
-    PQP_HD double raw_lo(const Slot& S, int t, int k) const { return k == 0 ? ((S.flags & F_REAL) ? -kap : 0.0) : lo_of(S, t, k - 1); }
-    PQP_HD double raw_up(const Slot& S, int t, int k) const { return k == 0 ? ((S.flags & F_REAL) ? kap : 0.0) : up_of(S, t, k - 1); }
+    // the box of inequality row k (0: curvature, uniform per QP; 1: front, 2: rear, the lane's Slot::lo / up) as assembled ...
+    // (t, the lane's index, is not used by these: it stays in the signatures that the emulation's probe and the callers below share)
+    PQP_HD double raw_lo(const Slot& S, int t, int k) const { return k == 0 ? ((S.flags & F_REAL) ? -kap : 0.0) : S.lo[k - 1]; }
+    PQP_HD double raw_up(const Slot& S, int t, int k) const { return k == 0 ? ((S.flags & F_REAL) ? kap : 0.0) : S.up[k - 1]; }
     // ... and as the iteration sees it: while polishing, an active row is pinned to its bound, an inactive row is free
     PQP_HD double box_lo(const Slot& S, int t, int k) const {
         const double lo = raw_lo(S, t, k), up = raw_up(S, t, k);
@@ -757,18 +729,16 @@ struct PathQp {
     // only rebuilds the metrics; any positive diagonal scaling is a valid metric, OSQP's own update path re-equilibrates
     PQP_HD void ruiz(bool reuse = false) {
         if (!reuse) ruiz_equilibrate();
-        // kParkScale: D, E are only read here, once per pass - between the passes they live in the workgroup slot's memory instead
-        // of in 24 registers of the ADMM loop
-        if constexpr (Ctx::kParkScale) {
-            ctx.phase([&](int t, Lane& ln) {
-                double* w = scale_slot(t);
-                const int ws = scale_stride();
-                if (!reuse) { _Pragma("unroll") for (int k = 0; k < 6; ++k) { w[k * ws] = ln.w.D[k]; w[(6 + k) * ws] = ln.w.E[k]; } }
-                double d[6], e[6];
-                _Pragma("unroll") for (int k = 0; k < 6; ++k) { d[k] = reuse ? w[k * ws] : ln.w.D[k]; e[k] = reuse ? w[(6 + k) * ws] : ln.w.E[k]; }
-                _Pragma("unroll") for (int k = 0; k < 6; ++k) { ln.w.D[k] = d[k]; ln.w.E[k] = e[k]; }
-            });
-        }
+        // D, E are only read here, once per pass - between the passes they are parked in the workgroup slot's memory (scale_slot) instead
+        // of in 24 registers of the ADMM loop (+2 %, profiles/r02b_variants.txt)
+        ctx.phase([&](int t, Lane& ln) {
+            double* w = scale_slot(t);
+            const int ws = scale_stride();
+            if (!reuse) { _Pragma("unroll") for (int k = 0; k < 6; ++k) { w[k * ws] = ln.w.D[k]; w[(6 + k) * ws] = ln.w.E[k]; } }
+            double d[6], e[6];
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) { d[k] = reuse ? w[k * ws] : ln.w.D[k]; e[k] = reuse ? w[(6 + k) * ws] : ln.w.E[k]; }
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) { ln.w.D[k] = d[k]; ln.w.E[k] = e[k]; }
+        });
         ruiz_metrics();
     }
     // scaling < 0: |scaling| passes of the same equilibration on ONE interior waypoint's blocks as if every waypoint carried them (the path
@@ -920,7 +890,7 @@ struct PathQp {
             Slot& S = ln.s;
             const SlotSetup& W = ln.w;
             const bool real = S.flags & F_REAL, precise = S.flags & F_PRECISE;
-            _Pragma("unroll") for (int k = 0; k < 6; ++k) set_sig(S, t, k, prm.sigma * rcp(c * W.D[k] * W.D[k]));
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) S.sig[k] = prm.sigma * rcp(c * W.D[k] * W.D[k]);
             _Pragma("unroll") for (int k = 0; k < 3; ++k) S.rhoT[k] = real ? rho_now * kRhoEqFactor * W.E[k] * W.E[k] * ic : 0.0;
             int fl = S.flags & ~((7 * F_FREE0) | (7 * F_EQ0));      // the active-set bits of a previous polish survive
             _Pragma("unroll") for (int k = 0; k < 3; ++k) {
@@ -988,19 +958,18 @@ struct PathQp {
     //      change sides (primal-dual active-set rounds) or, when that stalls, the ADMM state is restored.
     // ---------------------------------------------------------------------------------------------
     static constexpr int kSaveStride = PQP_SAVE_STRIDE;   // x6 yT3 yI3 zI3 rhoI3 (+2 pad) | best polished point: x6 yT3 yI3
-    static constexpr int kPolishRounds = 40; // active-set correction rounds per polish attempt
 
     PQP_HD double* save_slot(int t) const {
         if constexpr (Ctx::kSaveLds) return sh + L.save() + t * kSaveStride;
         else return A.wsave + ((size_t)slot * T + t) * kSaveStride;
     }
-    // parked Ruiz vectors of lane t, D(6) E(6): element k at scale_slot(t)[k * scale_stride()] - the (otherwise unused) constants region
-    // of the LDS layout, one array per element, or the workgroup slot's global memory
+    // parked Ruiz vectors of lane t, D(6) E(6): element k at scale_slot(t)[k * scale_stride()] - one array per element in LDS, or the
+    // lane's 18 doubles of the workgroup slot's global memory (whose last six are the dual snapshot, snap_slot)
     PQP_HD double* scale_slot(int t) const {
-        if constexpr (Ctx::kSaveLds && !Ctx::kCstLds) return sh + L.cst() + t;
+        if constexpr (Ctx::kSaveLds) return sh + L.scale() + t;
         else return A.wscale + ((size_t)slot * T + t) * 18;
     }
-    PQP_HD int scale_stride() const { return (Ctx::kSaveLds && !Ctx::kCstLds) ? T : 1; }
+    PQP_HD int scale_stride() const { return Ctx::kSaveLds ? T : 1; }
 
     // how badly inequality row k fails the KKT test at the polished point: violation of its true box when it is
     // treated as inactive, wrong-signed multiplier when it is treated as active (0 for rows that do not exist)
@@ -1049,7 +1018,7 @@ struct PathQp {
                 if (act_up) fl |= (F_ACTUP0 << k);
             }
             S.flags = keep_set ? S.flags : fl;      // keep_set: start from the active set of the previous pass
-            _Pragma("unroll") for (int k = 0; k < 6; ++k) set_sig(S, t, k, sig_of(S, t, k) * sgain);
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) S.sig[k] *= sgain;
             if (S.flags & F_LAST) {
                 EndRows* er = end_rows();
                 const EndVals e = end_vals();
@@ -1228,7 +1197,7 @@ struct PathQp {
                 S.rinvI[k] = r > 0.0 ? rcp(r) : 0.0;
                 S.rhoT[k] *= itgain;
             }
-            _Pragma("unroll") for (int k = 0; k < 6; ++k) set_sig(S, t, k, sig_of(S, t, k) * isgain);
+            _Pragma("unroll") for (int k = 0; k < 6; ++k) S.sig[k] *= isgain;
             if (S.flags & F_LAST) {
                 EndRows* er = end_rows();
                 double e_rb[2], e_sz[2], e_sy[2], e_by[2];
@@ -1275,25 +1244,24 @@ struct PathQp {
             double re0 = 0.0, re1 = 0.0;
             if (S.flags & F_LAST) { re0 = end_rows()->rho[0]; re1 = end_rows()->rho[1]; }
             const double rK = S.rhoI[0], rF = S.rhoI[1], rR = S.rhoI[2];
-            const double dsf = cost_diag(prm, S.flags, 4) + sig_of(S, t, 4) + rF, dsr = cost_diag(prm, S.flags, 5) + sig_of(S, t, 5) + rR;
+            const double dsf = cost_diag(prm, S.flags, 4) + S.sig[4] + rF, dsr = cost_diag(prm, S.flags, 5) + S.sig[5] + rR;
             const double idsf = rcp(dsf), idsr = rcp(dsr);
-            if constexpr (kAcc) { acc_set(S, C_IDSF, idsf); acc_set(S, C_IDSR, idsr); }
-            else if constexpr (kCst) { cst_set(t, C_IDSF, idsf); cst_set(t, C_IDSR, idsr); } else { S.idsf = idsf; S.idsr = idsr; }
+            S.idsf = idsf; S.idsr = idsr;
             S.cF = rF * idsf; S.cR = rR * idsr;
             const double gf = rF - rF * S.cF, gr = rR - rR * S.cR;
             const double ds = S.a[5];
             S.tu = S.rhoT[2] * ds;
-            const double du = cost_diag(prm, S.flags, 3) + sig_of(S, t, 3) + S.tu * ds;
+            const double du = cost_diag(prm, S.flags, 3) + S.sig[3] + S.tu * ds;
             S.idu = rcp(du);
             S.tudc = S.tu * S.idu;
             const double gu = S.rhoT[2] - S.tu * S.tudc;
             const double cf = coef_front(prm, S.flags), cr = coef_rear(prm, S.flags);
-            W.Dg[0] = cost_diag(prm, S.flags, 0) + sig_of(S, t, 0) + S.rhoT[0] + gf + gr + re0;
+            W.Dg[0] = cost_diag(prm, S.flags, 0) + S.sig[0] + S.rhoT[0] + gf + gr + re0;
             W.Dg[1] = gf * cf + gr * cr;
             W.Dg[2] = 0.0;
-            W.Dg[3] = cost_diag(prm, S.flags, 1) + sig_of(S, t, 1) + S.rhoT[1] + gf * cf * cf + gr * cr * cr + re1;
+            W.Dg[3] = cost_diag(prm, S.flags, 1) + S.sig[1] + S.rhoT[1] + gf * cf * cf + gr * cr * cr + re1;
             W.Dg[4] = 0.0;
-            W.Dg[5] = cost_diag(prm, S.flags, 2) + sig_of(S, t, 2) + gu + rK;
+            W.Dg[5] = cost_diag(prm, S.flags, 2) + S.sig[2] + gu + rK;
             const double r0 = S.rhoT[0], r1 = S.rhoT[1];
             const double a00 = S.a[0], a01 = S.a[1], a10 = S.a[2], a11 = S.a[3], a12 = S.a[4];
             const double gup = (S.flags & F_PREV) ? gu : 0.0;
@@ -1451,17 +1419,17 @@ struct PathQp {
             const double e_rho0 = er1->rho[0], e_rho1 = er1->rho[1], e_z0 = er1->z[0], e_z1 = er1->z[1], e_y0 = er1->y[0], e_y1 = er1->y[1];
             const bool last1 = S.flags & F_LAST;
             const double we0 = last1 ? e_rho0 * e_z0 - e_y0 : 0.0, we1 = last1 ? e_rho1 * e_z1 - e_y1 : 0.0;
-            S.rv = sig_of(S, t, 3) * S.x[3] + S.a[5] * wT[2];
-            S.rsf = sig_of(S, t, 4) * S.x[4] + wI[1];
-            S.rsr = sig_of(S, t, 5) * S.x[5] + wI[2];
+            S.rv = S.sig[3] * S.x[3] + S.a[5] * wT[2];
+            S.rsf = S.sig[4] * S.x[4] + wI[1];
+            S.rsr = S.sig[5] * S.x[5] + wI[2];
             const double tud = S.tudc * S.rv;
             double g[3];
             back_msg(S, wT, g);
             g[2] -= tud;
             const double eF = S.cF * S.rsf, eR = S.cR * S.rsr;
-            S.r[0] = sig_of(S, t, 0) * S.x[0] - wT[0] + wI[1] + wI[2] + we0 - eF - eR;
-            S.r[1] = sig_of(S, t, 1) * S.x[1] - wT[1] + cf * wI[1] + cr * wI[2] + we1 - cf * eF - cr * eR;
-            S.r[2] = sig_of(S, t, 2) * S.x[2] - wT[2] + wI[0] + tud;
+            S.r[0] = S.sig[0] * S.x[0] - wT[0] + wI[1] + wI[2] + we0 - eF - eR;
+            S.r[1] = S.sig[1] * S.x[1] - wT[1] + cf * wI[1] + cr * wI[2] + we1 - cf * eF - cr * eR;
+            S.r[2] = S.sig[2] * S.x[2] - wT[2] + wI[0] + tud;
             _Pragma("unroll") for (int k = 0; k < 3; ++k) sh[L.bufG() + 3 * t + k] = g[k];
             if constexpr (D) { _Pragma("unroll") for (int k = 0; k < 3; ++k) gm[k] = g[k]; }
         });
@@ -1620,8 +1588,10 @@ struct PathQp {
         PQP_IT(5);       // backward levels 8 .. 1 (DPP)
         // I3: back-substitute v, sf, sr; z~ = A x~; relaxed updates, projection, dual update.  Wave-local: a lane reads the X~ of the
         // previous one; the first lane of a wavefront reads the last lane of the previous wavefront, which wrote its X~ before
-        // the last workgroup barrier of the backward pass.  iterate() therefore ENDS WITHOUT A BARRIER: the next iterate() may
-        // follow directly, anything else (residuals, cold operations) must synchronise first - sync_after_iterate().
+        // the last workgroup barrier of the backward pass.  iterate() therefore ENDS WITHOUT A BARRIER.  The invariant that allows it: after a
+        // solve's last workgroup barrier only xbuf is read (here), and residuals() writes only bufP (ShLayout::xres) and bufG before its own
+        // first barrier - so the next iterate() and residuals() may follow directly.  Anything else (the look after a polish solve, cold
+        // operations) must synchronise first - sync_after_iterate().
         ctx.phase_w([&](int t, Lane& ln) {
             Slot& S = ln.s;
             // the two end rows' fields, loaded by every lane at the top of the phase (see I1); used by the lane that owns the rows at the bottom
@@ -1644,8 +1614,8 @@ struct PathQp {
             double xt[6];
             xt[0] = S.xt[0]; xt[1] = S.xt[1]; xt[2] = S.xt[2];
             xt[3] = (S.rv - S.tu * (((S.flags & F_PREV) ? Xp[2] : 0.0) - xt[2])) * S.idu;
-            xt[4] = (S.rsf - S.rhoI[1] * (xt[0] + cf * xt[1])) * idsf_of(S, t);
-            xt[5] = (S.rsr - S.rhoI[2] * (xt[0] + cr * xt[1])) * idsr_of(S, t);
+            xt[4] = (S.rsf - S.rhoI[1] * (xt[0] + cf * xt[1])) * S.idsf;
+            xt[5] = (S.rsr - S.rhoI[2] * (xt[0] + cr * xt[1])) * S.idsr;
             double zT[3], zI[3];
             rows_of(S, Xp, xt, zT, zI);
             _Pragma("unroll") for (int k = 0; k < 6; ++k) S.x[k] = alpha * xt[k] + (1.0 - alpha) * S.x[k];
@@ -1833,7 +1803,7 @@ struct PathQp {
             LateCertIn in;
             _Pragma("unroll") for (int k = 0; k < 3; ++k) { in.y[k] = S.yT[k]; in.y[3 + k] = S.yI[k]; in.b[k] = S.bT[k]; }
             _Pragma("unroll") for (int k = 0; k < 6; ++k) in.a[k] = S.a[k];
-            in.flags = S.flags; in.lo0 = lo_of(S, t, 0); in.lo1 = lo_of(S, t, 1); in.up0 = up_of(S, t, 0); in.up1 = up_of(S, t, 1);
+            in.flags = S.flags; in.lo0 = S.lo[0]; in.lo1 = S.lo[1]; in.up0 = S.up[0]; in.up1 = S.up[1];
             res = ctx.late_certificate(sh, t, snap_slot(t), have, in, A.prm.front_length, A.prm.rear_length, kap, A.prm.eps_prim_inf, cscale);
         });
         return res;
@@ -1846,8 +1816,8 @@ struct PathQp {
             double* pc = sh + L.stageC() + 3 * t;
             _Pragma("unroll") for (int k = 0; k < 6; ++k) pa[k] = S.a[k];
             _Pragma("unroll") for (int k = 0; k < 3; ++k) pa[6 + k] = S.bT[k];
-            pb[0] = (double)S.flags; pb[1] = lo_of(S, t, 0); pb[2] = lo_of(S, t, 1);
-            pc[0] = up_of(S, t, 0); pc[1] = up_of(S, t, 1); pc[2] = 0.0;
+            pb[0] = (double)S.flags; pb[1] = S.lo[0]; pb[2] = S.lo[1];
+            pc[0] = S.up[0]; pc[1] = S.up[1]; pc[2] = 0.0;
         });
         return ctx.certificate(sh, T, A.prm.front_length, A.prm.rear_length, kap, A.prm.eps_prim_inf, cscale);
     }
@@ -1957,11 +1927,8 @@ struct PathQp {
         });
     }
 
-    PQP_HD Uni get_uni() const { return Uni{rho, cscale, kap, alpha_, kkt_solves_, factors_, polishing_ ? 1 : 0, (cert_ ? 1 : 0) | (snap_valid_ ? 2 : 0)}; }
-    PQP_HD void set_uni(const Uni& u) { rho = u.rho; cscale = u.cscale; kap = u.kap; alpha_ = u.alpha; kkt_solves_ = u.kkt_solves; factors_ = u.factors; polishing_ = u.polishing != 0; cert_ = (u.cert & 1) != 0; snap_valid_ = (u.cert & 2) != 0; }
-
-    // The cold side of the solver.  On the device this runs inside a __noinline__ function on a copy of the lane
-    // state that lives in memory (DevCtx::cold), so its register needs never leak into the ADMM loop.
+    // The cold side of the solver: everything that is not the ADMM loop, one operation per call.  It runs inline on the same lane state as the
+    // loop, in every context (Ctx::cold); run() calls it from one place, so the kernel holds one copy of this code.
     PQP_HD void do_cold(int op, int i0, int i1, double d0) {
         const pqp_params& prm = A.prm;
         if (op == COLD_BEGIN_PASS) {
@@ -2020,8 +1987,9 @@ struct PathQp {
 
     // ---------------------------------------------------------------------------------------------
     // the whole path: (warm) solve + `passes` re-linearised warm re-solves.
-    // Hot side: one loop around iterate() / residuals() / the KKT test.  Everything else is a cold operation, issued
-    // from ONE call site (the lane state crosses the hot/cold boundary through memory there, once per operation).
+    // Hot side: one loop around iterate() / residuals() / the KKT test.  Everything else is a cold operation (do_cold), which runs inline
+    // on the same lane state and is issued from ONE call site: the loop only records which operation is due, so the kernel's code holds
+    // each of them once.
     //   mode ADMM  : OSQP iterations; every check_termination iterations residuals -> stop / adapt rho / start a polish
     //   mode POLISH: polish_refine_iter solves, then the KKT test -> accept / next active-set round / give up
     // ---------------------------------------------------------------------------------------------

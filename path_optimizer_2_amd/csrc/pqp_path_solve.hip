@@ -95,30 +95,13 @@ __device__ __noinline__ bool dev_late_certificate(double* sh, int t, double* sna
 // workgroup barriers (for a one-wave workgroup the barrier is only a wait on outstanding LDS traffic).
 template <int NW>
 struct DevCtx {
-    // kSaveLds: up to 256 lanes the polish save area fits beside the exchange buffers (72 KB per QP at T = 128, two QPs per CU)
-    // kCstLds: pass constants in LDS instead of in registers (no gain at one wavefront per SIMD); kParkScale: the Ruiz vectors are parked
-    // between the passes (+2 %, profiles/r02b_variants.txt)
-    static constexpr bool kCstLds = false, kParkScale = true, kSaveLds = NW <= kSaveLdsMaxNw;
+    // kSaveLds: up to 256 lanes the polish save area, the parked Ruiz vectors and the dual snapshot fit beside the exchange buffers (72 KB per
+    // QP at T = 128, two QPs per CU); the 512-lane kernel keeps them in its workgroup slot's global memory
+    static constexpr bool kSaveLds = NW <= kSaveLdsMaxNw;
     static constexpr bool kFinalRefine = NW >= 4;      // pqp_params::polish_final_refine is honoured: the contexts of paths beyond 128 waypoints
     // DPP moves: the value of the lane H below / above in the same row of 16 lanes, of the previous row's last lane; 0 where
     // there is no such lane.  Must run with every lane enabled (a disabled source lane reads as "no lane").  (profiles/r02j_dpp_exchanges.txt)
     static constexpr bool kDpp = true;
-    // kCstAcc: twelve pass constants of a waypoint that a solve reads once live in the accumulator registers, written and read by hand
-#ifdef PQP_CST_ACC
-    static constexpr bool kCstAcc = true;
-#else
-    static constexpr bool kCstAcc = false;
-#endif
-    __device__ __forceinline__ static void acc_write(double v, int& lo, int& hi) {
-        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(lo) : "v"(__double2loint(v)));
-        asm volatile("v_accvgpr_write_b32 %0, %1" : "=a"(hi) : "v"(__double2hiint(v)));
-    }
-    __device__ __forceinline__ static double acc_read(int lo, int hi) {
-        int l, h;
-        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(l) : "a"(lo));
-        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(h) : "a"(hi));
-        return __hiloint2double(h, l);
-    }
     template <int CTRL, int ROW_MASK>
     __device__ __forceinline__ static double dpp0(double v) {
         const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);

@@ -51,8 +51,4 @@ __device__ __forceinline__ double wave_sum(double x) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
 }
 
-// Up to this many wavefronts per QP the polish save area (and the parked Ruiz vectors) live in LDS; beyond, in the workgroup slot's global
-// memory.  4 is what fits (256 lanes: 157 KB).
-constexpr int kSaveLdsMaxNw = 4;
-
 }  // namespace pqp

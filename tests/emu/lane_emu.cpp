@@ -33,19 +33,17 @@ static int g_carry_tails = 0;
 extern "C" void pqp_emu_set_carry(int32_t* cost_key, int32_t* cost_hist, int carry_tails) { g_cost_key = cost_key; g_cost_hist = cost_hist; g_carry_tails = carry_tails; }
 
 namespace {
-#ifndef PQP_EMU_DIET
-#define PQP_EMU_DIET 0
-#endif
+// SAVE_LDS: Ctx::kSaveLds by the device's rule (path_solve_of below) - up to 256 lanes the polish save area, the parked Ruiz vectors and the dual
+// snapshot live in the shared array, at 512 lanes in PathSolveArgs::wsave / wscale, as in the 512-lane kernel
+template <bool SAVE_LDS>
 struct HostCtx {
-    // default: the device contexts' setting (Ruiz vectors parked, save area in the shared array up to 256 lanes); PQP_EMU_DIET: pass
-    // constants in the shared array too, everything parked in global memory
-    static constexpr bool kCstLds = PQP_EMU_DIET != 0, kParkScale = true, kSaveLds = PQP_EMU_DIET == 0, kDpp = false, kCstAcc = false;
+    static constexpr bool kSaveLds = SAVE_LDS, kDpp = false;
     static constexpr bool kFinalRefine = true;      // (the device: contexts of more than 128 lanes per QP; the parameter is 0 below that)
     template <class... A> static void join(A&...) {}      // (the device: a scheduling fence behind a batch of LDS loads)
     int T_;
     std::vector<pqp::Lane> lanes;
     std::vector<double> shm;
-    explicit HostCtx(int T) : T_(T), lanes(T), shm(pqp::ShLayout{T}.total(true), poison_value()) { poison_lanes(lanes); }
+    explicit HostCtx(int T) : T_(T), lanes(T), shm(pqp::ShLayout{T}.total(kSaveLds), poison_value()) { poison_lanes(lanes); }
     int T() const { return T_; }
     double* sh() { return shm.data(); }
     template <class F> void phase(F f) { for (int t = 0; t < T_; ++t) f(t, lanes[t]); }
@@ -112,6 +110,24 @@ struct HostCtx {
 extern "C" void pqp_emu_default_params(pqp_params* p) { pqp::default_params(p); }
 extern "C" void pqp_emu_production_params(pqp_params* p) { pqp::production_params(p); }
 
+namespace {
+// every QP of the batch on a fresh context, by the kernel variant the launcher would pick for it (with or without the certificate)
+template <bool SAVE_LDS>
+void path_solve_of(const pqp::PathSolveArgs& a, const pqp_params* prm, int T, int32_t* status, int32_t* iters) {
+    using Ctx = HostCtx<SAVE_LDS>;
+    for (int q = 0; q < a.batch; ++q) {
+        if (pqp::PathQp<Ctx, true>::count_of(a, q) < 2) {
+            if (status) status[q] = PQP_STATUS_UNSOLVED;
+            if (iters) iters[q] = 0;
+            continue;
+        }
+        Ctx ctx(T);
+        if (prm->eps_prim_inf > 0.0 && prm->prim_inf_after <= 0) { pqp::PathQp<Ctx, true> s(ctx, a, q); s.run(); }
+        else { pqp::PathQp<Ctx, false> s(ctx, a, q); s.run(); }
+    }
+}
+}  // namespace
+
 extern "C" int pqp_emu_path_solve(const pqp_params* prm, int batch, int n, const double* ref, const double* lin,
                                   const double* bounds, const double* scal, int passes, int warm, double* out,
                                   int32_t* status, int32_t* iters, double* info, double* wx, double* wy,
@@ -124,44 +140,29 @@ extern "C" int pqp_emu_path_solve(const pqp_params* prm, int batch, int n, const
     a.ref = ref; a.lin = lin; a.bounds = bounds; a.scal = scal; a.out = out;
     a.status = status; a.iters = iters; a.info = info;
     a.wx = wx; a.wy = wy; a.wye = wye; a.wrho = wrho;
-    std::vector<double> wsave((size_t)batch * T * PQP_SAVE_STRIDE, 0.0);
+    // the global form of the save area and the parked vectors (512 lanes), one slot per QP; poisoned like the shared array
+    std::vector<double> wsave((size_t)batch * T * PQP_SAVE_STRIDE, poison_value());
     a.wsave = wsave.data();
-    std::vector<double> wscale((size_t)batch * T * 18, 0.0);
+    std::vector<double> wscale((size_t)batch * T * 18, poison_value());
     a.wscale = wscale.data();
     a.store_warm = 1;
     a.prm = *prm;
     pqp::resolve_path_params(&a.prm, n);          // (as the launcher does)
     a.n_of = g_n_of;
     a.cost_key = g_cost_key; a.cost_hist = g_cost_hist; a.carry_tails = g_cost_key ? g_carry_tails : 0; a.carry_k = a.carry_tails;
-    for (int q = 0; q < batch; ++q) {
-        if (pqp::PathQp<HostCtx, true>::count_of(a, q) < 2) {
-            if (status) status[q] = PQP_STATUS_UNSOLVED;
-            if (iters) iters[q] = 0;
-            continue;
-        }
-        HostCtx ctx(T);
-        if (prm->eps_prim_inf > 0.0 && prm->prim_inf_after <= 0) { pqp::PathQp<HostCtx, true> s(ctx, a, q); s.run(); }       // the two variants the launcher picks from
-        else { pqp::PathQp<HostCtx, false> s(ctx, a, q); s.run(); }
-    }
+    if (T <= 64 * pqp::kSaveLdsMaxNw) path_solve_of<true>(a, prm, T, status, iters);       // the device's rule (DevCtx::kSaveLds)
+    else path_solve_of<false>(a, prm, T, status, iters);
     return 0;
 }
 
 // Debug probe: run load/assemble/ruiz/factor (+ iterations) and dump per-waypoint state.
 //   dump [n][64]: a(6) bT(3) lo(3) up(3) D(6) E(6) sig(6) rhoT(3) rhoI(3)  = 39 used
-extern "C" int pqp_emu_probe(const pqp_params* prm, int n, const double* ref, const double* bounds, const double* scal,
-                             double* dump, double* endrows, double* cscale, int do_iters, double* xout) {
-    int T = 64;
-    while (T < n) T *= 2;
-    pqp::PathSolveArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.batch = 1; a.n = n; a.ref = ref; a.bounds = bounds; a.scal = scal; a.prm = *prm;
-    pqp::resolve_path_params(&a.prm, n);
-    std::vector<double> wsave((size_t)T * PQP_SAVE_STRIDE, 0.0);
-    a.wsave = wsave.data();
-    std::vector<double> wscale((size_t)T * 18, 0.0);
-    a.wscale = wscale.data();
-    HostCtx ctx(T);
-    pqp::PathQp<HostCtx> s(ctx, a, 0);
+namespace {
+template <bool SAVE_LDS>
+void probe_of(const pqp::PathSolveArgs& a, int T, double* dump, double* endrows, double* cscale, int do_iters, double* xout) {
+    const int n = a.n;
+    HostCtx<SAVE_LDS> ctx(T);
+    pqp::PathQp<HostCtx<SAVE_LDS>> s(ctx, a, 0);
     s.load();
     s.end_rows()->y[0] = s.end_rows()->y[1] = 0.0;
     s.assemble();
@@ -188,6 +189,23 @@ extern "C" int pqp_emu_probe(const pqp_params* prm, int n, const double* ref, co
     }
     std::memcpy(endrows, s.end_rows(), sizeof(pqp::EndRows));
     *cscale = s.cscale;
+}
+}  // namespace
+
+extern "C" int pqp_emu_probe(const pqp_params* prm, int n, const double* ref, const double* bounds, const double* scal,
+                             double* dump, double* endrows, double* cscale, int do_iters, double* xout) {
+    int T = 64;
+    while (T < n) T *= 2;
+    pqp::PathSolveArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.batch = 1; a.n = n; a.ref = ref; a.bounds = bounds; a.scal = scal; a.prm = *prm;
+    pqp::resolve_path_params(&a.prm, n);
+    std::vector<double> wsave((size_t)T * PQP_SAVE_STRIDE, poison_value());
+    a.wsave = wsave.data();
+    std::vector<double> wscale((size_t)T * 18, poison_value());
+    a.wscale = wscale.data();
+    if (T <= 64 * pqp::kSaveLdsMaxNw) probe_of<true>(a, T, dump, endrows, cscale, do_iters, xout);
+    else probe_of<false>(a, T, dump, endrows, cscale, do_iters, xout);
     return 0;
 }
 

@@ -23,7 +23,7 @@ def _load():
     if _lib is None:
         deps = [SRC] + EU._DEPS
         if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DPQP_EMU_DIET=0", "-o", LIB, SRC], check=True)
+            subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", LIB, SRC], check=True)
         _lib = C.CDLL(LIB)
     return _lib
 

@@ -3,7 +3,9 @@ host emulation) and test_gpu_path_widths.py (the device).  Plain data and functi
 
 pqp_path_solve.hip is compiled once per workgroup width (NW = 1 / 2 / 4 / 8 wavefronts per QP: up to 64 / 128 / 256 / 512 waypoints), each with a
 certificate form and a plain form: eight register allocations of one kernel.  NW >= 4 compiles kFinalRefine in, NW == 8 keeps the polish save
-area and the parked Ruiz vectors in global memory per workgroup slot, wg_reduce has NW-wide loops.  The cases here put every width through
+area, the parked Ruiz vectors and the dual snapshot in global memory per workgroup slot, wg_reduce has NW-wide loops.  The host emulation picks
+that storage form by the device's rule (kSaveLdsMaxNw), so the CPU file runs the 512-lane cases on the global form too, each QP on buffers of its
+own; with PQP_EMU_POISON=1 those start as NaN like the shared array.  The cases here put every width through
   A  its first and last waypoint counts,
   B  both infeasibility forms (the certificate kernel and the late form of the plain kernel),
   C  a workgroup slot that draws several QPs in turn (LDS, save area and scale vectors inherited from the QP before),

@@ -22,7 +22,7 @@ def build(spec):
     name, _, defs = spec.partition("=")
     os.makedirs(OUT, exist_ok=True)
     lib = os.path.join(OUT, f"lib_{name}.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DPQP_EMU_DIET=0", *[f"-D{d}" for d in defs.split(",") if d], "-o", lib, SRC], check=True)
+    subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", *[f"-D{d}" for d in defs.split(",") if d], "-o", lib, SRC], check=True)
     return name, lib
 
 

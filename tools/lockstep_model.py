@@ -42,7 +42,7 @@ def build_tracing_emulation(tmp):
             shutil.copy(os.path.join(ROOT, "path_optimizer_2_amd", "csrc", f), os.path.join(tmp, "path_optimizer_2_amd", "csrc"))
     p = os.path.join(tmp, "path_optimizer_2_amd", "csrc", "pqp_path_lane.hpp")
     s = open(p).read()
-    for head, code in (("    PQP_HD void iterate() {\n", "ctx.trace(1);"), ("    PQP_HD void residuals(double (&res)[6]) {\n", "ctx.trace(2);"),
+    for head, code in (("    PQP_HD void iterate(bool look = false) {\n", "ctx.trace(1);"), ("    PQP_HD void residuals(double (&res)[6]) {\n", "ctx.trace(2);"),
                        ("    PQP_HD void factor() {\n", "ctx.trace(3);"),
                        ("    PQP_HD void do_cold(int op, int i0, int i1, double d0) {\n",
                         "ctx.trace(10 + op * 10 + (op == COLD_REFACTOR ? i0 : (op == COLD_BEGIN_PASS ? (i1 & 2 ? 1 : 0) : 0)));")):
@@ -53,7 +53,7 @@ def build_tracing_emulation(tmp):
     e = e.replace("static int g_wave_order = 1;", "static int g_wave_order = 1;\nstatic std::vector<int> g_trace;\nextern \"C\" int pqp_emu_trace(int* out, int cap) "
                   "{ int n = (int)g_trace.size(); for (int i = 0; i < n && i < cap; ++i) out[i] = g_trace[i]; g_trace.clear(); return n; }")
     e = e.replace("    static double uni(double x) { return x; }\n", "    static double uni(double x) { return x; }\n    void trace(int c) { g_trace.push_back(c); }\n")
-    e = e.replace("        HostCtx ctx(T);\n        if (prm->eps_prim_inf", "        HostCtx ctx(T);\n        g_trace.push_back(-1 - q);\n        if (prm->eps_prim_inf")
+    e = e.replace("        Ctx ctx(T);\n        if (prm->eps_prim_inf", "        Ctx ctx(T);\n        g_trace.push_back(-1 - q);\n        if (prm->eps_prim_inf")
     src = os.path.join(tmp, "tests", "emu", "lane_emu.cpp")
     open(src, "w").write(e)
     lib = os.path.join(tmp, "liblane_emu_trace.so")

@@ -9,7 +9,7 @@ root=$(cd "$(dirname "$0")/.." && pwd); cd "$root"
 out=ab/asan; mkdir -p $out
 F="-O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -fPIC -shared"
 g++ $F -std=c++17 -o $out/liblq_emu.so tests/emu/lq_emu.cpp &
-g++ $F -std=c++17 -DPQP_EMU_DIET=0 -o $out/liblane_emu.so tests/emu/lane_emu.cpp &
+g++ $F -std=c++17 -o $out/liblane_emu.so tests/emu/lane_emu.cpp &
 gcc $F -fopenmp -o $out/libpqp_oracle.so oracle/pqp_oracle.c -lm &
 wait
 tests=${@:-tests/test_lq_emulation.py tests/test_lane_emulation.py tests/test_banded_core_emulation.py tests/test_oracle_c.py tests/test_highs_pin.py}
