@@ -828,6 +828,70 @@ int pqp_project_points_device(pqp_handle* h, int batch, int m, const double* spl
 int pqp_project_points(pqp_handle* h, int batch, int m, const double* spline, const double* spline_ext, const double* length, int q_max,
                        int stride, int has_heading, const double* points, const int32_t* q_of, double* proj, int32_t* flags);
 
+/* ---- planned paths to trajectories: arc length, speed, acceleration, time --------------------------------------------------------------
+ * The reference's State carries s, v and a (include/data_struct/data_struct.hpp:14-26) and nothing fills them; getOptimizedPath adds the
+ * chords of the path up in tmp_s and drops the sum (src/solver/base_solver.cpp:268,282-284).  A controller, a simulator or a scorer by
+ * travel time needs each path as a trajectory: this gives every waypoint its arc length along the path itself, a speed that respects the
+ * path's curvature and the car's acceleration limits, and a time stamp - behind the chain, the footprint check and the selection on the
+ * same stream, reading `out` or `best_paths` where they lie.  The reference has no counterpart and no such flags: the defaults below are
+ * this library's choice. */
+#define PQP_SPEED_STRIDE 4
+typedef struct pqp_speed_params {
+    double v_max;             /* 10.0  m/s, finite, >= 0: the cap on every waypoint */
+    double a_max;             /* 1.5   m/s^2, finite, > 0: the largest acceleration */
+    double d_max;             /* 3.0   m/s^2, finite, > 0: the largest braking, as a positive number */
+    double a_lat_max;         /* 2.0   m/s^2, > 0, +inf allowed: v^2 |k| stays below it */
+} pqp_speed_params;
+void pqp_speed_default_params(pqp_speed_params* p);            /* pure host */
+enum { PQP_SPEED_START_TOO_FAST = 1, PQP_SPEED_STOPS_EARLY = 2, PQP_SPEED_NEVER_ARRIVES = 4, PQP_SPEED_EMPTY = 8, PQP_SPEED_NOT_FINITE = 16 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   paths [batch][n][stride]          x, y at offsets 0, 1 and k at offset 5, stride >= 6; stride = PQP_OUT_STRIDE reads a path solve's or the
+ *                                     chain's `out`, or pqp_select_paths' best_paths, in place
+ *   n_of [batch] or NULL              waypoints of each path, clamped to [0, n]; NULL: all have n.  "count" below is this clamped value
+ *   stop_before [batch] or NULL       e.g. the footprint check's first_collision: states at index >= stop_before[b] are not driven.  The
+ *                                     driven count is c = min(count, max(stop_before[b], 0)); when c < count the profile ends at speed 0 at
+ *                                     index c - 1 and PQP_SPEED_STOPS_EARLY is set
+ *   v_limit [batch][n] or NULL        a speed cap per waypoint (m/s, >= 0, +inf allowed)
+ *   v_start [batch]                   the vehicle's speed at waypoint 0, finite and >= 0
+ *   v_end [batch] or NULL             the speed demanded at the last driven waypoint, finite and >= 0; NaN (or NULL): free.  Not read for a
+ *                                     path that stops early
+ *   prm                               pqp_speed_params
+ * Outputs, fully overwritten: profile [batch][n][PQP_SPEED_STRIDE] = s, v, a, t and flags [batch]; rows at index >= c are zeros.
+ * The definition, in fp64, for a path with driven count c:
+ *   s   d_i = sqrt(dx^2 + dy^2) between waypoints i and i + 1; s_0 = 0, s_{i+1} = s_i + d_i - the chords, as pqp_select_paths' term 4 and
+ *       the reference's tmp_s
+ *   v   caps in v^2: cap_i = min(v_max^2, v_limit_i^2, a_lat_max / |k_i|) (a zero curvature gives no cap), then cap_0 = min(cap_0, v_start^2),
+ *       cap_{c-1} = min(cap_{c-1}, v_end^2) when v_end is a number, cap_{c-1} = 0 when the path stops early.  w is the largest sequence with
+ *       w_i <= cap_i, w_{i+1} <= w_i + 2 a_max d_i and w_i <= w_{i+1} + 2 d_max d_i - the textbook forward pass then backward pass - and
+ *       v_i = sqrt(w_i).  In closed form
+ *         w_i = min( cap_i, min_{j < i} (cap_j + 2 a_max (s_i - s_j)), min_{j > i} (cap_j + 2 d_max (s_j - s_i)) )
+ *       which is what the kernel evaluates, by scans
+ *   a   a_i = (w_{i+1} - w_i) / (2 d_i) for i < c - 1, 0 where d_i = 0, and a_{c-1} = 0
+ *   t   t_0 = 0, t_{i+1} = t_i + 2 d_i / (v_i + v_{i+1}); the step is 0 where d_i = 0, and +inf, with PQP_SPEED_NEVER_ARRIVES, where both
+ *       speeds are 0 and d_i > 0
+ *   c = 1 gives the one row (0, sqrt(cap_0), 0, 0).
+ * flags:
+ *   PQP_SPEED_START_TOO_FAST   w_0 < v_start^2: the caps or the braking limit do not allow the start speed; the row is still the definition's
+ *   PQP_SPEED_STOPS_EARLY      c < count
+ *   PQP_SPEED_NEVER_ARRIVES    see t
+ *   PQP_SPEED_EMPTY            c = 0: all zeros (together with PQP_SPEED_STOPS_EARLY when count > 0)
+ *   PQP_SPEED_NOT_FINITE       a value that is read for the driven range is not what it must be: an x, y or k below index c that is not
+ *                              finite, a v_limit below index c that is NaN or negative, a v_start that is not finite or negative, a v_end
+ *                              (of a path that does not stop early) that is infinite or negative, or an arc length that overflows.  The
+ *                              path's driven rows are NaN, this flag is set alone, and neighbouring paths are untouched
+ * The order of a path's additions depends on its driven count alone: the same path gives the same bits at any position in any batch, as
+ * pqp_select_paths promises.  (The sums are scans, so s and t agree with a sequential sum to (c - 1) ulp, not bit for bit.)
+ * The _device form is one launch, asynchronous on the handle's stream; it allocates nothing and checks pointers, sizes and prm only
+ * (the arrays are the device's: what they hold is judged by the kernel, path by path).  The host form copies in, runs, copies out and
+ * synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the outputs untouched, for a null pointer that is not optional,
+ * batch < 1, n < 1, stride < 6, or a parameter outside the ranges pqp_speed_params states. */
+int pqp_speed_profile_device(pqp_handle* h, const pqp_speed_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                             const int32_t* stop_before, const double* v_limit, const double* v_start, const double* v_end, double* profile,
+                             int32_t* flags);
+int pqp_speed_profile(pqp_handle* h, const pqp_speed_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                      const int32_t* stop_before, const double* v_limit, const double* v_start, const double* v_end, double* profile,
+                      int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,14 @@ PROJECT_TILE_SAMPLES = 1024      # PQP_PROJECT_TILE_SAMPLES
 PROJ_AT_END, PROJ_BEFORE_START, PROJ_NOT_CONVERGED, PROJ_NOT_FINITE = 1, 2, 4, 8
 
 
+class PqpSpeedParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("v_max", "a_max", "d_max", "a_lat_max")]
+
+
+SPEED_STRIDE = 4      # PQP_SPEED_STRIDE: s, v, a, t
+SPEED_START_TOO_FAST, SPEED_STOPS_EARLY, SPEED_NEVER_ARRIVES, SPEED_EMPTY, SPEED_NOT_FINITE = 1, 2, 4, 8, 16
+
+
 class PqpSizes(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "state", "control", "precise", "slack", "vars", "cons", "nnz_a", "nnz_p")]
 
@@ -91,6 +99,7 @@ EXPORTS = [
     "pqp_car_default_geometry", "pqp_car_circles", "pqp_footprint_check", "pqp_footprint_check_device",
     "pqp_select_default_params", "pqp_select_paths", "pqp_select_paths_device",
     "pqp_project_points", "pqp_project_points_device",
+    "pqp_speed_default_params", "pqp_speed_profile", "pqp_speed_profile_device",
 ]
 
 _lib = None
@@ -217,6 +226,10 @@ def load_library(path=None, with_torch=None):
         getattr(lib, name).argtypes = [vp, C.POINTER(PqpSelectParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     for name in ("pqp_project_points", "pqp_project_points_device"):
         getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.pqp_speed_default_params.argtypes = [C.POINTER(PqpSpeedParams)]
+    lib.pqp_speed_default_params.restype = None
+    for name in ("pqp_speed_profile", "pqp_speed_profile_device"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(PqpSpeedParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -257,6 +270,17 @@ def select_default_params(lib=None, **over):
     lib = lib or load_library()
     p = PqpSelectParams()
     lib.pqp_select_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def speed_default_params(lib=None, **over):
+    """pqp_speed_default_params: v_max 10 m/s, a_max 1.5, d_max 3 and a_lat_max 2 m/s^2 - this library's choice, the reference has no such
+    flags - with `over` applied."""
+    lib = lib or load_library()
+    p = PqpSpeedParams()
+    lib.pqp_speed_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p
@@ -462,7 +486,8 @@ class Handle:
         return c
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
-                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False):
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, speed=None, v_start=None,
+                      v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -474,22 +499,41 @@ class Handle:
         select: group_start [groups + 1] - pqp_select_paths_device behind the chain (and behind the footprint check, whose first_collision
         and margin it then reads) on the same stream; adds terms [B][8], best [groups], best_paths [groups][n_max][7] and best_n [groups]
         (select_params: PqpSelectParams, None: select_default_params()).  winners_only (with select): out, free and margin stay on the
-        device and are not in the dict - only per-candidate scalars and the winners cross to the host."""
+        device and are not in the dict - only per-candidate scalars and the winners cross to the host.
+        speed: PqpSpeedParams - pqp_speed_profile_device behind all of these on the same stream; adds profile [..][n_max][4] = s, v, a, t and
+        speed_flags.  Without select it runs on out / n_out for every candidate, v_start (and v_end, optional) [B], stopping before
+        first_collision when the footprint was checked.  With select it runs on best_paths / best_n, so only the winners become
+        trajectories, v_start (and v_end) [groups]; a winner's collision index is not at hand, so select_params.require_free = 0 together
+        with check_footprint is refused.  The winners' profile crosses to the host with winners_only too."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only))
+                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
+                           self._speed(speed, v_start, v_end, check_footprint, select, select_params))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False):
+                              winners_only=False, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
-        select / select_params / winners_only: as for optimize_path)."""
+        select / select_params / winners_only / speed / v_start / v_end: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
                                                                                       C.c_void_p(d_dist.data_ptr())))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only))
+                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
+                           self._speed(speed, v_start, v_end, check_footprint, select, select_params))
+
+    def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
+        if speed is None:
+            if v_start is not None or v_end is not None:
+                raise ValueError("v_start / v_end need speed=PqpSpeedParams")
+            return None
+        if v_start is None:
+            raise ValueError("speed needs v_start")
+        if select is not None and check_footprint and select_params is not None and not select_params.require_free:
+            raise ValueError("speed with select and check_footprint needs select_params.require_free: a winner's collision index is not at hand")
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel()
+        return (speed, f64(v_start), f64(v_end))
 
     def _selection(self, select, select_params, winners_only):
         if select is None:
@@ -500,10 +544,11 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None):
+               selection=None, speed=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
-        selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None"""
+        selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
+        of a speed profile behind all three, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -524,6 +569,14 @@ class Handle:
             best = torch.zeros(groups, dtype=torch.int32, device=dev)
             best_paths = torch.zeros((groups, cfg.n_max, 7), dtype=torch.float64, device=dev)
             best_n = torch.zeros(groups, dtype=torch.int32, device=dev)
+        if speed is not None:
+            sp_prm, v_start, v_end = speed
+            rows = groups if selection is not None else B
+            if v_start.size != rows or (v_end is not None and v_end.size != rows):
+                raise ValueError(f"v_start / v_end must have one entry per {'group' if selection is not None else 'candidate'} ({rows})")
+            d_vs, d_ve = t(v_start, np.float64), t(v_end, np.float64)
+            profile = torch.zeros((rows, cfg.n_max, SPEED_STRIDE), dtype=torch.float64, device=dev)
+            speed_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -543,6 +596,14 @@ class Handle:
             self._check(self.lib.pqp_select_paths_device(self._h, C.byref(sel_prm), B, cfg.n_max, 7, p(out), p(ints[0]), p(ints[1]), p(ints[2]),
                                                          p(first) if footprint is not None else None, p(margin) if footprint is not None else None,
                                                          groups, p(d_start), p(terms), p(best), p(best_paths), p(best_n)))
+        if speed is not None:               # behind all of them: the winners where the selection left them, or every candidate in `out`
+            if selection is not None:       # (an eligible winner is collision-free: require_free)
+                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), groups, cfg.n_max, 7, p(best_paths), p(best_n), None, None,
+                                                              p(d_vs), p(d_ve), p(profile), p(speed_flags)))
+            else:
+                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), B, cfg.n_max, 7, p(out), p(ints[0]),
+                                                              p(first) if footprint is not None else None, None, p(d_vs), p(d_ve), p(profile),
+                                                              p(speed_flags)))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -558,6 +619,8 @@ class Handle:
                 res.update(margin=host(margin))
         if selection is not None:
             res.update(terms=host(terms), best=host(best), best_paths=host(best_paths), best_n=host(best_n))
+        if speed is not None:
+            res.update(profile=host(profile), speed_flags=host(speed_flags))
         return res
 
     def distance_layer(self, grid, geom):
@@ -611,6 +674,25 @@ class Handle:
         self._check(self.lib.pqp_select_paths(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(stt), _ptr(stg), _ptr(fc), _ptr(mg),
                                               groups, _ptr(gs), _ptr(terms), _ptr(best), _ptr(best_paths), _ptr(best_n)))
         return dict(terms=terms, best=best, best_paths=best_paths, best_n=best_n)
+
+    def speed_profile(self, paths, v_start, n_of=None, stop_before=None, v_limit=None, v_end=None, prm=None):
+        """pqp_speed_profile (host arrays): paths [B][n][stride >= 6] (x, y first, k at offset 5; the chain's `out` or best_paths as they are),
+        v_start [B], and optionally n_of [B], stop_before [B] (e.g. first_collision), v_limit [B][n], v_end [B] (NaN: free); prm =
+        PqpSpeedParams (None: the defaults).  Returns (profile [B][n][4] = s, v, a, t, flags [B] of SPEED_*)."""
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        B, n, stride = paths.shape
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        no, sb, vl, vs, ve = i32(n_of), i32(stop_before), f64(v_limit), f64(v_start), f64(v_end)
+        for name, a, size in (("n_of", no, B), ("stop_before", sb, B), ("v_limit", vl, B * n), ("v_start", vs, B), ("v_end", ve, B)):
+            if a is not None and a.size != size:
+                raise ValueError(f"speed_profile: {name} must have {size} entries, not {a.size}")
+        prm = prm if prm is not None else speed_default_params(self.lib)
+        profile = np.zeros((B, n, SPEED_STRIDE))
+        flags = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.pqp_speed_profile(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(sb), _ptr(vl), _ptr(vs), _ptr(ve),
+                                               _ptr(profile), _ptr(flags)))
+        return profile, flags
 
     def corridor_params(self, **over):
         p = PqpCorridorParams()

@@ -1,6 +1,6 @@
 // pqp_maps.hip — the entry points of include/pqp.h around the obstacle distance map and the planned paths: the distance layer from an
 // occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
-// group's best (pqp_select_kernels.inc).  Their kernels, launchers and entry points.
+// group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc).  Their kernels, launchers and entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +26,7 @@ using namespace pqp_internal;
 #include "pqp_distance_kernels.inc"
 #include "pqp_footprint_kernels.inc"
 #include "pqp_select_kernels.inc"
+#include "pqp_speed_kernels.inc"
 
 extern "C" {
 
@@ -222,6 +223,62 @@ int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int
     return st.run([&]() -> int {
         return pqp_select_paths_device(h, prm, batch, n, stride, d_paths, d_n_of, d_status, d_stage, d_first, d_margin, groups, d_start, d_terms,
                                        d_best, d_best_paths, d_best_n);
+    });
+}
+
+// ---- planned paths to trajectories: s, v, a, t ---------------------------------------------------------------------------------------------
+void pqp_speed_default_params(pqp_speed_params* p) {
+    if (!p) return;
+    // this library's choice: the reference plans geometry only and has no such flags
+    p->v_max = 10.0;
+    p->a_max = 1.5;
+    p->d_max = 3.0;
+    p->a_lat_max = 2.0;
+}
+
+static const char* const kSpeedRefusal =
+    "pqp_speed_profile: bad argument (batch >= 1; n >= 1; stride >= 6; v_max finite and >= 0; a_max and d_max finite and > 0; a_lat_max > 0)";
+
+static bool speed_ok(pqp_handle* h, const pqp_speed_params* prm, int batch, int n, int stride, const double* paths, const double* v_start,
+                     const double* profile, const int32_t* flags) {
+    return h && prm && paths && v_start && profile && flags && batch >= 1 && n >= 1 && stride >= 6 && std::isfinite(prm->v_max) &&
+           prm->v_max >= 0.0 && std::isfinite(prm->a_max) && prm->a_max > 0.0 && std::isfinite(prm->d_max) && prm->d_max > 0.0 &&
+           prm->a_lat_max > 0.0;
+}
+
+int pqp_speed_profile_device(pqp_handle* h, const pqp_speed_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                             const int32_t* stop_before, const double* v_limit, const double* v_start, const double* v_end, double* profile,
+                             int32_t* flags) {
+    if (!speed_ok(h, prm, batch, n, stride, paths, v_start, profile, flags)) return fail(PQP_ERR_INVALID, kSpeedRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::SpeedArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.paths = paths; a.n_of = n_of; a.stop_before = stop_before; a.v_limit = v_limit;
+    a.v_start = v_start; a.v_end = v_end; a.prm = *prm; a.profile = profile; a.flags = flags;
+    constexpr int per_block = pqp::kSpeedThreads / 64;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::speed_profile_kernel, dim3((unsigned)(((long long)batch + per_block - 1) / per_block)), dim3(pqp::kSpeedThreads), 0,
+                           h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_speed_profile(pqp_handle* h, const pqp_speed_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                      const int32_t* stop_before, const double* v_limit, const double* v_start, const double* v_end, double* profile,
+                      int32_t* flags) {
+    if (!speed_ok(h, prm, batch, n, stride, paths, v_start, profile, flags)) return fail(PQP_ERR_INVALID, kSpeedRefusal);
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_stop = st.in(stop_before, batch);
+    const double* d_limit = st.in(v_limit, bn);
+    const double* d_start = st.in(v_start, batch);
+    const double* d_end = st.in(v_end, batch);
+    double* d_profile = st.out(profile, bn * PQP_SPEED_STRIDE);
+    int32_t* d_flags = st.out(flags, batch);
+    return st.run([&]() -> int {
+        return pqp_speed_profile_device(h, prm, batch, n, stride, d_paths, d_n_of, d_stop, d_limit, d_start, d_end, d_profile, d_flags);
     });
 }
 

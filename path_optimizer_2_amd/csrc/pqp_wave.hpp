@@ -41,14 +41,48 @@ __device__ __forceinline__ double dpp_sum_step(double x) {
     const int ohi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
     return x + __hiloint2double(ohi, olo);
 }
-__device__ __forceinline__ double wave_sum(double x) {
+// The six steps are a scan: after them lane i holds x_0 + ... + x_i - the rows of 16 by Kogge-Stone, then row 0's total onto row 1 and
+// row 2's onto row 3, then the total of rows 0-1 onto rows 2 and 3.  The order of lane i's additions depends on i alone.
+__device__ __forceinline__ double wave_prefix_sum(double x) {
     x = dpp_sum_step<0x111, 0xf>(x);
     x = dpp_sum_step<0x112, 0xf>(x);
     x = dpp_sum_step<0x114, 0xf>(x);
     x = dpp_sum_step<0x118, 0xf>(x);
     x = dpp_sum_step<0x142, 0xa>(x);
     x = dpp_sum_step<0x143, 0xc>(x);
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
+    return x;
+}
+// the value of lane LANE in every lane (wave-uniform)
+template <int LANE>
+__device__ __forceinline__ double wave_read(double x) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), LANE), __builtin_amdgcn_readlane(__double2loint(x), LANE));
+}
+__device__ __forceinline__ double wave_sum(double x) { return wave_read<63>(wave_prefix_sum(x)); }
+
+// the same scan for a minimum: lane i holds min(x_0 .. x_i); min is exact, so the order does not matter
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_min_step(double x) {
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+    return fmin(x, __hiloint2double(ohi, olo));
+}
+__device__ __forceinline__ double wave_prefix_min(double x) {
+    x = dpp_min_step<0x111, 0xf>(x);
+    x = dpp_min_step<0x112, 0xf>(x);
+    x = dpp_min_step<0x114, 0xf>(x);
+    x = dpp_min_step<0x118, 0xf>(x);
+    x = dpp_min_step<0x142, 0xa>(x);
+    x = dpp_min_step<0x143, 0xc>(x);
+    return x;
+}
+
+// lane i takes lane i - 1's value, lane 0 takes `first` (wave_shr:1): the step from an inclusive scan to an exclusive one, and how a
+// lane sees its left neighbour's element
+__device__ __forceinline__ double wave_shift_up(double x, double first) {
+    const int olo = __builtin_amdgcn_update_dpp(__double2loint(first), __double2loint(x), 0x138, 0xf, 0xf, false);
+    const int ohi = __builtin_amdgcn_update_dpp(__double2hiint(first), __double2hiint(x), 0x138, 0xf, 0xf, false);
+    return __hiloint2double(ohi, olo);
 }
 
 }  // namespace pqp
