@@ -892,6 +892,65 @@ int pqp_speed_profile(pqp_handle* h, const pqp_speed_params* prm, int batch, int
                       const int32_t* stop_before, const double* v_limit, const double* v_start, const double* v_end, double* profile,
                       int32_t* flags);
 
+/* ---- time-stamped trajectories at a fixed time step ------------------------------------------------------------------------------------
+ * pqp_speed_profile's time stamps sit where the waypoints are: every 0.15 to 1 m of arc, at times that follow from the speed.  A tracking
+ * controller, a simulator step, an MPC horizon or a comparison against predicted agents asks where the car is at t0 + k dt: this samples
+ * every path at those times, behind the speed profile on the same stream, reading `out` (or `best_paths`) and `profile` where they lie.
+ * Inside a segment the kinematics are the profile's own - a_i = (w_{i+1} - w_i) / (2 d_i) and t_{i+1} - t_i = 2 d_i / (v_i + v_{i+1}) are
+ * constant acceleration along the chord - so a sample is their closed form.  The reference has no counterpart (nothing fills State::v). */
+#define PQP_TRAJ_STRIDE 8          /* x, y, heading, k, s, v, a, t */
+typedef struct pqp_sample_params {
+    double dt;                /* 0.1   s, finite, > 0: the time step */
+    int32_t hold_last;        /* 0     1: rows behind the arrival repeat the last driven waypoint at rest */
+} pqp_sample_params;
+void pqp_sample_default_params(pqp_sample_params* p);          /* pure host */
+enum { PQP_TRAJ_HORIZON_SHORT = 1, PQP_TRAJ_STANDS = 2, PQP_TRAJ_ENDS_MOVING = 4, PQP_TRAJ_EMPTY = 8, PQP_TRAJ_NOT_FINITE = 16 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   paths [batch][n][stride]          x, y, heading at offsets 0, 1, 2 and k at offset 5, stride >= 6; stride = PQP_OUT_STRIDE reads `out` or
+ *                                     best_paths in place
+ *   n_of, stop_before [batch] or NULL the driven count is c = min(clamp(n_of, 0, n), max(stop_before, 0)): pqp_speed_profile's expression,
+ *                                     so the same two arrays give the same c
+ *   profile [batch][n][PQP_SPEED_STRIDE]   s, v, a, t as pqp_speed_profile wrote them, or any array of that shape
+ *   t0 [batch] or NULL (all 0)        the time of sample 0, finite and >= 0
+ *   m >= 1                            samples per path
+ *   prm                               pqp_sample_params
+ * Outputs, fully overwritten: traj [batch][m][PQP_TRAJ_STRIDE], m_of [batch], flags [batch].
+ * The definition, in fp64, for a path with driven count c; every product and sum is rounded on its own (no contraction), in this order:
+ *   tau_k = t0 + (double)k * dt
+ *   T_i = max_{j <= i} t_j, the running maximum of the t column (that column is a scan's prefix sum, monotone only up to its last bit; the
+ *       running maximum is exact and monotone, so a count and a binary search find the same segment)
+ *   sample k is on the path when tau_k <= T_{c-1}; m_of is the number of such samples - a prefix k < m_of, because tau ascends
+ *   segment  i = #{ j < c : T_j <= tau_k } - 1; with t_0 = 0 that is >= 0 (a t column that starts later puts earlier samples in segment 0)
+ *   i = c - 1: the row is waypoint c - 1 itself - its x, y, heading, k, s, v, then a = 0, t = tau_k.  Otherwise
+ *     (dx, dy) = (x_{i+1} - x_i, y_{i+1} - y_i);  d = sqrt(dx*dx + dy*dy), the profile's chord;  u = tau_k - t_i
+ *     e = min(max((v_i + (0.5 * a_i) * u) * u, 0), d);  lambda = d > 0 ? e / d : 0
+ *     x = x_i + lambda * dx;  y = y_i + lambda * dy
+ *     heading = constrain_angle(h_i + lambda * constrain_angle(h_{i+1} - h_i))     (include/tools/tools.hpp:24-35's wrap to [-pi, pi])
+ *     k = k_i + lambda * (k_{i+1} - k_i);  s = s_i + e;  v = max(v_i + a_i * u, 0);  a = a_i;  t = tau_k
+ *     (min and max as fmin and fmax)
+ *   rows k >= m_of: zeros; with hold_last the last driven waypoint's x, y, heading, k, s with v = 0, a = 0, t = tau_k
+ * flags:
+ *   PQP_TRAJ_HORIZON_SHORT   tau_{m-1} < T_{c-1}: the path is not finished inside the horizon (also an arrival time of +inf)
+ *   PQP_TRAJ_STANDS          some on-path sample has i < c - 1 and T_{i+1} = +inf: the car never leaves waypoint i (the profile's
+ *                            PQP_SPEED_NEVER_ARRIVES)
+ *   PQP_TRAJ_ENDS_MOVING     m_of < m and v_{c-1} > 0: the horizon passes the end of a path that does not end at rest
+ *   PQP_TRAJ_EMPTY           c = 0: zeros, m_of = 0; nothing of the path is read, t0 neither
+ *   PQP_TRAJ_NOT_FINITE      a value read below index c is not what it must be: an x, y, heading, k, s, v or a that is not finite, a t
+ *                            that is NaN or negative (+inf is allowed), a t0 that is not finite or negative.  All m rows are NaN,
+ *                            m_of = 0, this flag is set alone, and neighbouring paths are untouched.  A path that pqp_speed_profile
+ *                            flagged PQP_SPEED_NOT_FINITE has NaN rows and arrives here that way
+ * A sample's bits depend on its path's driven rows, t0, dt and k alone - not on the batch, the position in it, n, m or which form was
+ * called.  The _device form is one launch, asynchronous on the handle's stream; it allocates nothing and checks pointers, sizes and prm
+ * only; n and m have no cap.  The host form copies in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing
+ * launched and the outputs untouched, for a null pointer that is not optional, batch < 1, n < 1, m < 1, stride < 6, a dt that is not
+ * finite and positive, or a hold_last other than 0 / 1. */
+int pqp_sample_trajectory_device(pqp_handle* h, const pqp_sample_params* prm, int batch, int n, int stride, const double* paths,
+                                 const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* t0, int m, double* traj,
+                                 int32_t* m_of, int32_t* flags);
+int pqp_sample_trajectory(pqp_handle* h, const pqp_sample_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                          const int32_t* stop_before, const double* profile, const double* t0, int m, double* traj, int32_t* m_of,
+                          int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

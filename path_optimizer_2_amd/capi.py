@@ -80,6 +80,14 @@ SPEED_STRIDE = 4      # PQP_SPEED_STRIDE: s, v, a, t
 SPEED_START_TOO_FAST, SPEED_STOPS_EARLY, SPEED_NEVER_ARRIVES, SPEED_EMPTY, SPEED_NOT_FINITE = 1, 2, 4, 8, 16
 
 
+class PqpSampleParams(C.Structure):
+    _fields_ = [("dt", C.c_double), ("hold_last", C.c_int32)]
+
+
+TRAJ_STRIDE = 8       # PQP_TRAJ_STRIDE: x, y, heading, k, s, v, a, t
+TRAJ_HORIZON_SHORT, TRAJ_STANDS, TRAJ_ENDS_MOVING, TRAJ_EMPTY, TRAJ_NOT_FINITE = 1, 2, 4, 8, 16
+
+
 class PqpSizes(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("n", "state", "control", "precise", "slack", "vars", "cons", "nnz_a", "nnz_p")]
 
@@ -100,6 +108,7 @@ EXPORTS = [
     "pqp_select_default_params", "pqp_select_paths", "pqp_select_paths_device",
     "pqp_project_points", "pqp_project_points_device",
     "pqp_speed_default_params", "pqp_speed_profile", "pqp_speed_profile_device",
+    "pqp_sample_default_params", "pqp_sample_trajectory", "pqp_sample_trajectory_device",
 ]
 
 _lib = None
@@ -230,6 +239,10 @@ def load_library(path=None, with_torch=None):
     lib.pqp_speed_default_params.restype = None
     for name in ("pqp_speed_profile", "pqp_speed_profile_device"):
         getattr(lib, name).argtypes = [vp, C.POINTER(PqpSpeedParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.pqp_sample_default_params.argtypes = [C.POINTER(PqpSampleParams)]
+    lib.pqp_sample_default_params.restype = None
+    for name in ("pqp_sample_trajectory", "pqp_sample_trajectory_device"):
+        getattr(lib, name).argtypes = [vp, C.POINTER(PqpSampleParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -281,6 +294,16 @@ def speed_default_params(lib=None, **over):
     lib = lib or load_library()
     p = PqpSpeedParams()
     lib.pqp_speed_default_params(C.byref(p))
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def sample_default_params(lib=None, **over):
+    """pqp_sample_default_params: dt 0.1 s, hold_last 0 - this library's choice - with `over` applied."""
+    lib = lib or load_library()
+    p = PqpSampleParams()
+    lib.pqp_sample_default_params(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p
@@ -486,8 +509,8 @@ class Handle:
         return c
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
-                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, speed=None, v_start=None,
-                      v_end=None):
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, sample=None, samples=None,
+                      t0=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -504,24 +527,27 @@ class Handle:
         speed_flags.  Without select it runs on out / n_out for every candidate, v_start (and v_end, optional) [B], stopping before
         first_collision when the footprint was checked.  With select it runs on best_paths / best_n, so only the winners become
         trajectories, v_start (and v_end) [groups]; a winner's collision index is not at hand, so select_params.require_free = 0 together
-        with check_footprint is refused.  The winners' profile crosses to the host with winners_only too."""
+        with check_footprint is refused.  The winners' profile crosses to the host with winners_only too.
+        sample: PqpSampleParams (needs speed) - pqp_sample_trajectory_device behind the speed profile on the same stream, on the arrays it ran
+        on: `samples` rows per path at t0 + k dt (t0 [B], or [groups] with select; None: all 0); adds traj [..][samples][8] = x, y, heading,
+        k, s, v, a, t, traj_n (the samples on the path) and traj_flags.  The winners' samples cross to the host with winners_only too."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
-                           self._speed(speed, v_start, v_end, check_footprint, select, select_params))
+                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False, speed=None, v_start=None, v_end=None):
+                              winners_only=False, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
-        select / select_params / winners_only / speed / v_start / v_end: as for optimize_path)."""
+        select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
                                                                                       C.c_void_p(d_dist.data_ptr())))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
-                           self._speed(speed, v_start, v_end, check_footprint, select, select_params))
+                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed))
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -535,6 +561,17 @@ class Handle:
         f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64).ravel()
         return (speed, f64(v_start), f64(v_end))
 
+    def _sample(self, sample, samples, t0, speed):
+        if sample is None:
+            if samples is not None or t0 is not None:
+                raise ValueError("samples / t0 need sample=PqpSampleParams")
+            return None
+        if speed is None:
+            raise ValueError("sample needs speed=PqpSpeedParams: the samples are taken from its profile")
+        if samples is None or int(samples) < 1:
+            raise ValueError("sample needs samples >= 1")
+        return (sample, int(samples), None if t0 is None else np.ascontiguousarray(t0, dtype=np.float64).ravel())
+
     def _selection(self, select, select_params, winners_only):
         if select is None:
             if winners_only or select_params is not None:
@@ -544,11 +581,11 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None):
+               selection=None, speed=None, sampling=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
-        of a speed profile behind all three, or None"""
+        of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -577,6 +614,14 @@ class Handle:
             d_vs, d_ve = t(v_start, np.float64), t(v_end, np.float64)
             profile = torch.zeros((rows, cfg.n_max, SPEED_STRIDE), dtype=torch.float64, device=dev)
             speed_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
+        if sampling is not None:
+            sa_prm, m, t0 = sampling
+            if t0 is not None and t0.size != rows:
+                raise ValueError(f"t0 must have one entry per {'group' if selection is not None else 'candidate'} ({rows})")
+            d_t0 = t(t0, np.float64)
+            traj = torch.zeros((rows, m, TRAJ_STRIDE), dtype=torch.float64, device=dev)
+            traj_n = torch.zeros(rows, dtype=torch.int32, device=dev)
+            traj_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -604,6 +649,14 @@ class Handle:
                 self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), B, cfg.n_max, 7, p(out), p(ints[0]),
                                                               p(first) if footprint is not None else None, None, p(d_vs), p(d_ve), p(profile),
                                                               p(speed_flags)))
+        if sampling is not None:            # behind the speed profile, on the arrays it ran on
+            if selection is not None:
+                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), groups, cfg.n_max, 7, p(best_paths), p(best_n), None,
+                                                                  p(profile), p(d_t0), m, p(traj), p(traj_n), p(traj_flags)))
+            else:
+                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, p(out), p(ints[0]),
+                                                                  p(first) if footprint is not None else None, p(profile), p(d_t0), m, p(traj),
+                                                                  p(traj_n), p(traj_flags)))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -621,6 +674,8 @@ class Handle:
             res.update(terms=host(terms), best=host(best), best_paths=host(best_paths), best_n=host(best_n))
         if speed is not None:
             res.update(profile=host(profile), speed_flags=host(speed_flags))
+        if sampling is not None:
+            res.update(traj=host(traj), traj_n=host(traj_n), traj_flags=host(traj_flags))
         return res
 
     def distance_layer(self, grid, geom):
@@ -693,6 +748,30 @@ class Handle:
         self._check(self.lib.pqp_speed_profile(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(sb), _ptr(vl), _ptr(vs), _ptr(ve),
                                                _ptr(profile), _ptr(flags)))
         return profile, flags
+
+    def sample_trajectory(self, paths, profile, m, n_of=None, stop_before=None, t0=None, prm=None):
+        """pqp_sample_trajectory (host arrays): paths [B][n][stride >= 6] (x, y, heading first, k at offset 5; the chain's `out` or best_paths
+        as they are), profile [B][n][4] = s, v, a, t (speed_profile's), m samples per path at t0 + k dt, and optionally n_of [B], stop_before
+        [B] (the two speed_profile got), t0 [B] (None: all 0); prm = PqpSampleParams (None: the defaults).  Returns (traj [B][m][8] = x, y,
+        heading, k, s, v, a, t, m_of [B]: the samples on the path, flags [B] of TRAJ_*)."""
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        B, n, stride = paths.shape
+        profile = np.ascontiguousarray(profile, dtype=np.float64)
+        if profile.shape != (B, n, SPEED_STRIDE):
+            raise ValueError(f"sample_trajectory: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        m = int(m)
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        no, sb, tt = i32(n_of), i32(stop_before), None if t0 is None else np.ascontiguousarray(t0, dtype=np.float64)
+        for name, a in (("n_of", no), ("stop_before", sb), ("t0", tt)):
+            if a is not None and a.size != B:
+                raise ValueError(f"sample_trajectory: {name} must have {B} entries, not {a.size}")
+        prm = prm if prm is not None else sample_default_params(self.lib)
+        traj = np.zeros((B, max(m, 0), TRAJ_STRIDE))
+        m_of = np.zeros(B, dtype=np.int32)
+        flags = np.zeros(B, dtype=np.int32)
+        self._check(self.lib.pqp_sample_trajectory(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(sb), _ptr(profile), _ptr(tt), m,
+                                                   _ptr(traj), _ptr(m_of), _ptr(flags)))
+        return traj, m_of, flags
 
     def corridor_params(self, **over):
         p = PqpCorridorParams()

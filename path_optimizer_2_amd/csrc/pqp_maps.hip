@@ -1,6 +1,7 @@
 // pqp_maps.hip — the entry points of include/pqp.h around the obstacle distance map and the planned paths: the distance layer from an
 // occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
-// group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc).  Their kernels, launchers and entry points.
+// group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc), samples of those trajectories on a time grid
+// (pqp_sample_kernels.inc).  Their kernels, launchers and entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +28,7 @@ using namespace pqp_internal;
 #include "pqp_footprint_kernels.inc"
 #include "pqp_select_kernels.inc"
 #include "pqp_speed_kernels.inc"
+#include "pqp_sample_kernels.inc"
 
 extern "C" {
 
@@ -279,6 +281,59 @@ int pqp_speed_profile(pqp_handle* h, const pqp_speed_params* prm, int batch, int
     int32_t* d_flags = st.out(flags, batch);
     return st.run([&]() -> int {
         return pqp_speed_profile_device(h, prm, batch, n, stride, d_paths, d_n_of, d_stop, d_limit, d_start, d_end, d_profile, d_flags);
+    });
+}
+
+// ---- time-stamped trajectories at a fixed time step ------------------------------------------------------------------------------------------
+void pqp_sample_default_params(pqp_sample_params* p) {
+    if (!p) return;
+    // this library's choice, as pqp_speed_default_params: the reference has no time axis
+    p->dt = 0.1;
+    p->hold_last = 0;
+}
+
+static const char* const kSampleRefusal =
+    "pqp_sample_trajectory: bad argument (batch >= 1; n >= 1; m >= 1; stride >= 6; dt finite and > 0; hold_last 0 or 1)";
+
+static bool sample_ok(pqp_handle* h, const pqp_sample_params* prm, int batch, int n, int stride, const double* paths, const double* profile, int m,
+                      const double* traj, const int32_t* m_of, const int32_t* flags) {
+    return h && prm && paths && profile && traj && m_of && flags && batch >= 1 && n >= 1 && m >= 1 && stride >= 6 && std::isfinite(prm->dt) &&
+           prm->dt > 0.0 && (prm->hold_last == 0 || prm->hold_last == 1);
+}
+
+int pqp_sample_trajectory_device(pqp_handle* h, const pqp_sample_params* prm, int batch, int n, int stride, const double* paths,
+                                 const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* t0, int m, double* traj,
+                                 int32_t* m_of, int32_t* flags) {
+    if (!sample_ok(h, prm, batch, n, stride, paths, profile, m, traj, m_of, flags)) return fail(PQP_ERR_INVALID, kSampleRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::SampleArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.m = m; a.paths = paths; a.n_of = n_of; a.stop_before = stop_before; a.profile = profile;
+    a.t0 = t0; a.prm = *prm; a.traj = traj; a.m_of = m_of; a.flags = flags;
+    constexpr int per_block = pqp::kSampleThreads / 64;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::sample_trajectory_kernel, dim3((unsigned)(((long long)batch + per_block - 1) / per_block)), dim3(pqp::kSampleThreads),
+                           0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_sample_trajectory(pqp_handle* h, const pqp_sample_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                          const int32_t* stop_before, const double* profile, const double* t0, int m, double* traj, int32_t* m_of,
+                          int32_t* flags) {
+    if (!sample_ok(h, prm, batch, n, stride, paths, profile, m, traj, m_of, flags)) return fail(PQP_ERR_INVALID, kSampleRefusal);
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_stop = st.in(stop_before, batch);
+    const double* d_profile = st.in(profile, bn * PQP_SPEED_STRIDE);
+    const double* d_t0 = st.in(t0, batch);
+    double* d_traj = st.out(traj, (size_t)batch * m * PQP_TRAJ_STRIDE);
+    int32_t* d_m_of = st.out(m_of, batch);
+    int32_t* d_flags = st.out(flags, batch);
+    return st.run([&]() -> int {
+        return pqp_sample_trajectory_device(h, prm, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, d_t0, m, d_traj, d_m_of, d_flags);
     });
 }
 
