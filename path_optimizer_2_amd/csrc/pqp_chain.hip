@@ -39,6 +39,7 @@
 #include "pqp_path_lane.hpp"
 #include "pqp_line_device.hpp"
 #include "pqp_internal.hpp"
+#include "pqp_chain_ws.hpp"
 
 using namespace pqp_internal;
 
@@ -156,19 +157,6 @@ __global__ void gather_last_kernel(int batch, int stride, const int32_t* __restr
 
 }  // namespace pqp
 
-namespace {
-// device workspace of the chain: doubles and int32 carved out of two handle buffers
-struct ChainWs {
-    double *rx, *ry, *rs, *raw_tab, *raw_ext, *raw_len, *gx, *gy, *gs, *ga, *gk, *clr, *sx, *sy, *ss, *sm_tab, *sm_ext, *sm_len, *ls, *lb, *ub, *vl, *pl, *px, *py,
-        *ps, *fin_tab, *fin_ext, *fin_len, *max_s, *ref, *err, *bounds, *scal;
-    int32_t *raw_count, *raw_fit, *sample_count, *sample_fit, *sm_status, *sm_iters, *layer_count, *layer_fit, *ps_status, *ps_iters, *ref_count, *ref_fit,
-        *n_valid, *qp_status;
-    // second_pass = BOUNDS_ON_STATES only
-    double* lin;
-    int32_t *n_valid2, *n_of2, *qp_status2, *iters1, *iters2, *n_valid_out, *status_out;
-};
-}  // namespace
-
 extern "C" {
 
 void pqp_chain_default_config(pqp_chain_config* c) {
@@ -213,34 +201,13 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
                       int32_t* iters) {
     const int R = cfg.raw_max, S = cfg.sample_max, L = cfg.layer_max, N = cfg.n_max;
     int rc;
-    // ---- workspace ---------------------------------------------------------------------------------------------------------------
-    const size_t B = (size_t)batch;
-    const size_t nd = B * (3 * R + 9 * R + 4 + 1 + 6 * S + 3 * S + 9 * S + 4 + 1 + 3 * L + 1 + L + 3 * L + 9 * L + 4 + 1 + 1 + (size_t)N * 5 + 2 + (size_t)N * 6 + 6);
-    const size_t ni = B * 14;
+    // ---- workspace: measured and carved from the one list of its arrays (pqp_chain_ws.hpp) ------------------------------------------
     const bool second = cfg.second_pass == PQP_SECOND_PASS_BOUNDS_ON_STATES;
-    const size_t nd2 = second ? B * (size_t)N * 3 : 0, ni2 = second ? B * 7 : 0;          // (behind the workspace of the plain chain)
-    if ((rc = h->chain_d.ensure((nd + nd2) * 8)) || (rc = h->chain_i.ensure((ni + ni2) * 4))) return rc;
+    const ChainDims dims{R, S, L, N, second};
     ChainWs w;
-    {
-        double* p = h->chain_d.as<double>();
-        auto take = [&](size_t k) { double* r = p; p += B * k; return r; };
-        w.rx = take(R); w.ry = take(R); w.rs = take(R); w.raw_tab = take(9 * R); w.raw_ext = take(4); w.raw_len = take(1);
-        w.gx = take(S); w.gy = take(S); w.gs = take(S); w.ga = take(S); w.gk = take(S); w.clr = take(S);
-        w.sx = take(S); w.sy = take(S); w.ss = take(S); w.sm_tab = take(9 * S); w.sm_ext = take(4); w.sm_len = take(1);
-        w.ls = take(L); w.lb = take(L); w.ub = take(L); w.vl = take(1); w.pl = take(L);
-        w.px = take(L); w.py = take(L); w.ps = take(L); w.fin_tab = take(9 * L); w.fin_ext = take(4); w.fin_len = take(1); w.max_s = take(1);
-        w.ref = take((size_t)N * 5); w.err = take(2); w.bounds = take((size_t)N * 6); w.scal = take(6);
-        int32_t* q = h->chain_i.as<int32_t>();
-        auto takei = [&]() { int32_t* r = q; q += B; return r; };
-        w.raw_count = takei(); w.raw_fit = takei(); w.sample_count = takei(); w.sample_fit = takei(); w.sm_status = takei(); w.sm_iters = takei();
-        w.layer_count = takei(); w.layer_fit = takei(); w.ps_status = takei(); w.ps_iters = takei(); w.ref_count = takei(); w.ref_fit = takei();
-        w.n_valid = takei(); w.qp_status = takei();
-        w.lin = nullptr; w.n_valid2 = w.n_of2 = w.qp_status2 = w.iters1 = w.iters2 = w.n_valid_out = w.status_out = nullptr;
-        if (second) {
-            w.lin = take((size_t)N * 3);
-            w.n_valid2 = takei(); w.n_of2 = takei(); w.qp_status2 = takei(); w.iters1 = takei(); w.iters2 = takei(); w.n_valid_out = takei(); w.status_out = takei();
-        }
-    }
+    const ChainWsSize need = carve(w, dims, (size_t)batch, nullptr, nullptr);
+    if ((rc = h->chain.d.ensure(need.doubles * 8)) || (rc = h->chain.i.ensure(need.ints * 4))) return rc;
+    carve(w, dims, (size_t)batch, h->chain.d.as<double>(), h->chain.i.as<int32_t>());
     const dim3 gb((batch + 255) / 256), tb(256);
     auto clamp = [&](const int32_t* in, int lo, int hi, int32_t* o) {
         hipLaunchKernelGGL(pqp::chain_clamp_kernel, gb, tb, 0, h->stream, batch, in, lo, hi, o);
@@ -319,35 +286,28 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
     return PQP_OK;
 }
 
-// Everything that decides what chain_body enqueues, as bytes: a captured graph is replayed only for the identical key.  Pointers and
-// sizes of the call, the configuration, both handles' parameters and options, the host-side state the path solve's arguments depend on
-// (launch parity of the cost-order double buffer, shapes of the warm / carried state), and the library's allocation generation (a graph
-// holds device pointers of the handles' workspaces).
-static std::vector<unsigned char> chain_key(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg, int batch, int p_max, const void* const* ptrs, int n_ptrs,
-                                            const pqp_grid_geometry* geom) {
-    std::vector<unsigned char> k;
-    auto put = [&](const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; k.insert(k.end(), b, b + n); };
-    auto put_int = [&](long long v) { put(&v, sizeof(v)); };
-    put(&h, sizeof(h)); put(&hs, sizeof(hs));
-    put_int(batch); put_int(p_max);
-    for (int i = 0; i < n_ptrs; ++i) put(&ptrs[i], sizeof(void*));
-    // (the structs field by field where they have padding: raw bytes of padding are not part of the value)
-    put_int(cfg.raw_max); put_int(cfg.sample_max); put_int(cfg.layer_max); put_int(cfg.n_max); put(&cfg.output_spacing, 8); put_int(cfg.dynamic_segmentation);
-    put(&cfg.max_steering_angle, 8); put(&cfg.smoothed_length_margin, 8); put_int(cfg.smoothing_method); put_int(cfg.second_pass);
-    pqp_corridor_params cp; std::memset(&cp, 0, sizeof(cp)); pqp_dp_params dp; std::memset(&dp, 0, sizeof(dp)); pqp_grid_geometry gg; std::memset(&gg, 0, sizeof(gg));
-    // (copy member-wise into zeroed storage: assignment of the whole struct may copy padding, field copies do not matter here because the
-    //  structs below are compared as bytes only after this same normalisation on both sides)
-    cp = cfg.corridor; dp = cfg.dp; gg = *geom;
-    put(&cp, sizeof(cp)); put(&dp, sizeof(dp)); put(&gg, sizeof(gg));
-    for (pqp_handle* x : {h, hs}) {
-        pqp_params pr; std::memset(&pr, 0, sizeof(pr)); pr = x->prm; put(&pr, sizeof(pr));
-        put_int(x->opt_store_warm); put_int(x->opt_order_by_cost); put_int(x->opt_reserve_cus); put_int(x->opt_stream_batch); put_int(x->opt_carry);
-        put_int(x->opt_long_lines);
-        put_int(x->solves & 1); put_int(x->hist_batch); put_int(x->hist_n); put_int(x->warm_batch); put_int(x->warm_n); put_int(x->warm_stored ? 1 : 0);
-        put_int(x->stream_last_batch); put_int(x->stream_last_n); put_int(x->sm_act_batch[0]); put_int(x->sm_act_n[0]); put_int(x->sm_act_batch[1]); put_int(x->sm_act_n[1]);
-        put_int(x->b_struct_type); put_int(x->b_struct_n);
+// Everything that decides what chain_body enqueues, as bytes: a captured graph is replayed only for the identical key.  The call's own
+// arguments, the configuration, and of both handles the parameters, the options (whole) and what each group of host state says a captured
+// launch depends on (its key(), pqp_internal.hpp); then the library's allocation generation (a graph holds device pointers of the
+// handles' workspaces).
+static Key chain_key(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg, int batch, int p_max, const void* const* ptrs, int n_ptrs,
+                     const pqp_grid_geometry* geom) {
+    Key k;
+    k.v.reserve(1024);
+    k.put(&h, sizeof(h)); k.put(&hs, sizeof(hs));
+    k.put_int(batch); k.put_int(p_max);
+    for (int i = 0; i < n_ptrs; ++i) k.put(&ptrs[i], sizeof(void*));
+    k.bytes(*geom);
+    // (pqp_chain_config has padding behind its int members: field by field; its sub-structs have none, pqp_internal.hpp)
+    k.put_int(cfg.raw_max); k.put_int(cfg.sample_max); k.put_int(cfg.layer_max); k.put_int(cfg.n_max); k.put(&cfg.output_spacing, 8); k.put_int(cfg.dynamic_segmentation);
+    k.put(&cfg.max_steering_angle, 8); k.put(&cfg.smoothed_length_margin, 8); k.put_int(cfg.smoothing_method); k.put_int(cfg.second_pass);
+    k.bytes(cfg.corridor); k.bytes(cfg.dp);
+    for (const pqp_handle* x : {h, hs}) {
+        k.bytes(x->prm);
+        k.bytes(x->opt);
+        x->lane.key(k); x->strm.key(k); x->sm.key(k);
     }
-    put_int((long long)g_alloc_generation.load(std::memory_order_relaxed));
+    k.put_int((long long)g_alloc_generation.load(std::memory_order_relaxed));
     return k;
 }
 
@@ -376,30 +336,25 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
     if (hs->device != h->device) return fail(PQP_ERR_INVALID, "pqp_optimize_path: the smoother handle lives on another device than the path handle");
     PQP_HIP(hipSetDevice(h->device));
     auto body = [&]() { return chain_body(h, hs, cfg, batch, p_max, points, n_points, start, target, dist, map_of, geom, start_k, out, n_out, status, stage, iters); };
-    if (!h->opt_chain_graph) return body();
+    if (!h->opt.chain_graph) return body();
     // ---- PQP_OPT_CHAIN_GRAPH: the first call with a key runs plain (it sizes every workspace and uploads what is uploaded once), the second call
     //      with that key is captured and launched, later ones are replays.  The key holds the launch parity of the path handle's cost-order double
     //      buffer, so a caller sees: plain, plain (other parity), capture, capture (other parity), replays - two graphs per argument set ----
     const void* ptrs[] = {points, n_points, start, target, dist, map_of, start_k, out, n_out, status, stage, iters};
-    const std::vector<unsigned char> key = chain_key(h, hs, cfg, batch, p_max, ptrs, (int)(sizeof(ptrs) / sizeof(ptrs[0])), geom);
+    const Key key = chain_key(h, hs, cfg, batch, p_max, ptrs, (int)(sizeof(ptrs) / sizeof(ptrs[0])), geom);
     pqp_handle::ChainGraph* g = nullptr;
-    for (auto& e : h->chain_graphs) if (e.key == key) { g = &e; break; }
+    for (auto& e : h->chain.graphs) if (e.key == key) { g = &e; break; }
     auto after_replay = [&](const pqp_handle::ChainGraph& e) {
-        // the host-side state a plain run of the body leaves (everything else the body sets is the same from call to call: it is in the key).
-        // Only a body whose path solve ran on the lane-per-waypoint kernel touches the ticket counter (the graph resets it and leaves it at
-        // ticket_after) and counts a solve launch; a body that went to path_stream_kernel leaves both alone - plain pqp_path_solve* calls on the
-        // handle between two replays keep their counter
-        if (e.lane_launch) { h->ticket_next = e.ticket_after; h->solves += e.lane_launches; }
-        h->last_path_kernel = e.path_kernel;         // (pqp_last_path_kernel: the kernel the replayed body's path solve runs on)
+        h->lane.replayed(e.replay);
         // no timing events inside a graph: pqp_last_kernel_ms / pqp_kernel_ms_history have nothing newer than the last plain launch to report
-        h->timed = false; hs->timed = false;
+        h->timing.timed = false; hs->timing.timed = false;
     };
     // A replay runs as one unit on the path handle's stream; the smoother handle's stream is not part of it.  So that it stays ordered with
     // what the caller enqueues on that stream before and after - as the plain launches are, some of which run there - the graph waits for
     // the smoother stream's earlier work and the smoother stream's later work waits for the graph.
     // (The two fences cost 3.6 % of a replay, profiles/r04n_chain_fence.txt.  Option value 2: no fences - the caller guarantees that the
     //  smoother handle's stream carries no other work while chains are in flight.)
-    const bool fenced = hs != h && h->opt_chain_graph != 2;
+    const bool fenced = hs != h && h->opt.chain_graph != 2;
     auto launch = [&](hipGraphExec_t exec) -> int {
         if (fenced) { int r; if ((r = chain_mark(hs, 1)) || (r = chain_wait(h, hs, 1))) return r; }
         PQP_HIP(hipGraphLaunch(exec, h->stream));
@@ -413,24 +368,23 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
         return PQP_OK;
     }
     if (!g) {
-        if (h->chain_graphs.size() >= 16) {          // (a caller that keeps changing its buffers: stop collecting)
-            for (auto& e : h->chain_graphs) if (e.exec) (void)hipGraphExecDestroy(e.exec);
-            h->chain_graphs.clear();
+        if (h->chain.graphs.size() >= 16) {          // (a caller that keeps changing its buffers: stop collecting)
+            for (auto& e : h->chain.graphs) if (e.exec) (void)hipGraphExecDestroy(e.exec);
+            h->chain.graphs.clear();
         }
-        h->chain_graphs.emplace_back();
-        h->chain_graphs.back().key = key;
+        h->chain.graphs.emplace_back();
+        h->chain.graphs.back().key = key;
         return body();
     }
     if (g->failed) return body();
     // capture: the smoother handle's stream joins through the chain's own events and is joined back before the end
-    const long long solves_before = h->solves;
-    const unsigned long long ticket_before = h->ticket_next;
+    const pqp_handle::LanePath::Mark before = h->lane.mark();
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) { g->failed = true; return body(); }
-    h->capturing = true; hs->capturing = true;
+    h->chain.capturing = true; hs->chain.capturing = true;
     const int rc = body();
-    h->capturing = false; hs->capturing = false;
+    h->chain.capturing = false; hs->chain.capturing = false;
     e = hipStreamEndCapture(h->stream, &graph);
     hipGraphExec_t exec = nullptr;
     if (rc == PQP_OK && e == hipSuccess && graph) e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
@@ -439,15 +393,11 @@ int pqp_optimize_path_device(pqp_handle* h, pqp_handle* hs, const pqp_chain_conf
         // nothing of the captured body has run: undo its host-side bookkeeping and run it plainly
         (void)hipGetLastError();
         g->failed = true;
-        h->solves = solves_before; h->ticket_next = ticket_before;
+        h->lane.rewind(before);
         return body();
     }
     g->exec = exec;
-    g->path_kernel = h->last_path_kernel;
-    g->lane_launch = h->solves != solves_before;     // the body's path solve ran on the lane-per-waypoint kernel (ticket counter, launch parity)
-    g->lane_launches = h->solves - solves_before;    // (two with second_pass = BOUNDS_ON_STATES)
-    g->ticket_after = h->ticket_next;
-    h->solves = solves_before;                       // (the capture counted a launch that only happens now)
+    g->replay = h->lane.captured(before);           // (the capture counted launches that only happen now, with every replay)
     const int rl = launch(g->exec);
     if (rl != PQP_OK) return rl;
     after_replay(*g);

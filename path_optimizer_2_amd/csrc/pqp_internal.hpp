@@ -12,7 +12,10 @@
 
 #include "../../include/pqp.h"
 
-namespace pqp_internal __attribute__((visibility("hidden"))) {
+#ifndef PQP_HIDDEN
+#define PQP_HIDDEN __attribute__((visibility("hidden")))      // (also pqp_chain_ws.hpp, which stands alone)
+#endif
+namespace pqp_internal PQP_HIDDEN {
 
 // sets the calling thread's message (pqp_last_error) and returns `code`
 int fail(int code, const std::string& msg);
@@ -66,72 +69,190 @@ int lds_opt_in(const void* fn, size_t bytes, const char* who);
 // (long_*_kernel, pqp_corridor_kernels.inc) - never (0), where the LDS kernel does not fit one CU (1), always (2)
 int long_form(int opt, const void* fn, size_t bytes, bool* out);
 
+// Bytes that identify what a launch sequence depends on (the chain's captured graphs, pqp_chain.hip).  bytes() takes a type only where
+// every bit of it is value: no padding.
+struct Key {
+    std::vector<unsigned char> v;
+    void put(const void* p, size_t n) { const unsigned char* b = (const unsigned char*)p; v.insert(v.end(), b, b + n); }
+    void put_int(long long x) { put(&x, sizeof(x)); }
+    template <class T> void bytes(const T& x) { static_assert(std::is_trivially_copyable_v<T>); put(&x, sizeof(T)); }
+    bool operator==(const Key& o) const { return v == o.v; }
+};
+// the structs of pqp.h that go into a Key as bytes: the size of each is the sum of its members' sizes, i.e. it has no padding.  The member
+// counts below are kept by hand - C++17 cannot enumerate a struct's members - so they are a tripwire, not a derivation: any member added to
+// one of these structs changes its size and trips its line, and whoever mends the line recounts ALL members against pqp.h (an int added
+// with 4 bytes of padding passes if only the double count is bumped) and puts the struct field by field if padding has appeared
+static_assert(sizeof(pqp_params) == 29 * sizeof(double) + 18 * sizeof(int32_t), "pqp_params has padding");
+static_assert(sizeof(pqp_corridor_params) == 11 * sizeof(double), "pqp_corridor_params has padding");
+static_assert(sizeof(pqp_dp_params) == 4 * sizeof(double), "pqp_dp_params has padding");
+static_assert(sizeof(pqp_grid_geometry) == 2 * sizeof(int32_t) + 5 * sizeof(double), "pqp_grid_geometry has padding");
+
+// pqp_set_option: one int per option, nothing else - the struct goes into the chain's graph key as bytes, so every option, present or
+// future, is part of it
+struct Options {
+    int store_warm = 1, order_by_cost = 0, reserve_cus = 0;
+    int stream_batch = -1;       // (< 0: stream_batch_auto(n))
+    int carry = 0;               // PQP_OPT_CARRY_CYCLES
+    int stream_staged = -1;      // (< 0: by launch size, path_stream_impl)
+    int chain_graph = 0;         // PQP_OPT_CHAIN_GRAPH: pqp_optimize_path_device captured as hipGraphs (pqp_chain.hip); 2: without the fences
+    int long_lines = 0;          // PQP_OPT_LONG_LINES: 0 LDS forms only, 1 long form where the LDS form does not fit, 2 long forms
+};
+static_assert(std::has_unique_object_representations_v<Options>, "Options: ints only, no padding");
+
+// what a changed option leaves stale on the handle (pqp_handle::invalidate)
+enum Stale : unsigned {
+    kStaleCostOrder = 1,         // the cost histograms / order maps of both path kernels (LanePath::hist_batch, StreamPath::order_batch)
+    kStaleStreamCarry = 2,       // what the lane-per-QP kernel's workspace holds (StreamPath::last_batch)
+    kStaleSmootherCarry = 4,     // the exact smoothers' carried active sets (Smoothers::act_batch)
+};
+// every option: its id, its member, how a value is normalised, what a change invalidates.  pqp_set_option is a walk over this table.
+struct OptionRow { int id; int Options::*member; int (*normalise)(int); unsigned stale; };
+inline constexpr OptionRow kOptionTable[] = {
+    {PQP_OPT_STORE_WARM, &Options::store_warm, [](int v) { return v ? 1 : 0; }, 0},
+    {PQP_OPT_ORDER_BY_COST, &Options::order_by_cost, [](int v) { return v ? 1 : 0; }, kStaleCostOrder},
+    {PQP_OPT_RESERVE_CUS, &Options::reserve_cus, [](int v) { return v < 0 ? 0 : v; }, 0},
+    {PQP_OPT_STREAM_BATCH, &Options::stream_batch, [](int v) { return v < 0 ? -1 : v; }, 0},
+    {PQP_OPT_STREAM_STAGED, &Options::stream_staged, [](int v) { return v < 0 ? -1 : (v ? 1 : 0); }, kStaleStreamCarry},      // (another layout: nothing to carry)
+    {PQP_OPT_CARRY_CYCLES, &Options::carry, [](int v) { return v < 0 ? 0 : (v > 64 ? 64 : v); }, kStaleStreamCarry | kStaleSmootherCarry},
+    {PQP_OPT_CHAIN_GRAPH, &Options::chain_graph, [](int v) { return v == 2 ? 2 : (v ? 1 : 0); }, 0},
+    {PQP_OPT_LONG_LINES, &Options::long_lines, [](int v) { return v >= 2 ? 2 : (v == 1 ? 1 : 0); }, 0},
+};
+
 }  // namespace pqp_internal
 
+// The handle: what every launcher shares (device, parameters, stream, options, timing, marks, staging pool) and one group of state per
+// launcher that owns it.  A group that decides what a launch of pqp_optimize_path_device's body enqueues says so in key(), directly
+// under its fields: the chain's graph key is read off those (chain_key, pqp_chain.hip).  The groups are hidden like everything else
+// behind the C ABI; only the handle's own name is the ABI's.
 struct pqp_handle {
     using DevBuf = pqp_internal::DevBuf;
+    using Key = pqp_internal::Key;
     int device = 0;
+    int num_cu = 0;
     pqp_params prm;
     hipStream_t stream = nullptr;
+    pqp_internal::Options opt;
+
     // HIP events around the dominant kernel of every call, on the stream it is launched on: a ring of the last kEvRing launches,
     // read back (after the work is done) by pqp_last_kernel_ms / pqp_kernel_ms_history without putting a sync between launches.
     // One slot more than the history: the one launch_timed records into, which a launch that fails may leave half recorded.
-    static constexpr int kEvRing = 256, kEvSlots = kEvRing + 1;
-    hipEvent_t evs0[kEvSlots] = {}, evs1[kEvSlots] = {};
-    long long ev_count = 0;          // launches recorded so far
-    bool timed = false;              // the last of them is what pqp_last_kernel_ms reports
+    // (no key: events are not recorded inside a capture, and a replay clears `timed`)
+    struct PQP_HIDDEN Timing {
+        static constexpr int kEvRing = 256, kEvSlots = kEvRing + 1;
+        hipEvent_t evs0[kEvSlots] = {}, evs1[kEvSlots] = {};
+        long long ev_count = 0;          // launches recorded so far
+        bool timed = false;              // the last of them is what pqp_last_kernel_ms reports
+        // the launches of one call between the next pair of the ring's events, which count only once the launches were accepted: a call that
+        // fails leaves the timing of the previous one.  No events inside a graph capture.
+        template <class F> int launch_timed(hipStream_t stream, bool capturing, F&& launch) {
+            if (capturing) return launch();
+            const int slot = (int)(ev_count % kEvSlots);
+            PQP_HIP(hipEventRecord(evs0[slot], stream));
+            if (const int rc = launch()) return rc;
+            PQP_HIP(hipEventRecord(evs1[slot], stream));
+            ev_count += 1;
+            timed = true;
+            return PQP_OK;
+        }
+    } timing;
+    template <class F> int launch_timed(F&& launch) { return timing.launch_timed(stream, chain.capturing, launch); }
+
     static constexpr int kMarks = 8;
     static constexpr int kChainMarks = 2;      // + two events of pqp_optimize_path_device's own
     hipEvent_t marks[kMarks + kChainMarks] = {};   // pqp_mark / pqp_wait_mark: ordering between the streams of two handles
-    // the launches of one call between the next pair of the ring's events, which count only once the launches were accepted: a call that
-    // fails leaves the timing of the previous one.  No events inside a graph capture.
-    template <class F> int launch_timed(F&& launch) {
-        if (capturing) return launch();
-        const int slot = (int)(ev_count % kEvSlots);
-        PQP_HIP(hipEventRecord(evs0[slot], stream));
-        if (const int rc = launch()) return rc;
-        PQP_HIP(hipEventRecord(evs1[slot], stream));
-        ev_count += 1;
-        timed = true;
-        return PQP_OK;
-    }
-    // PQP_OPT_CHAIN_GRAPH: pqp_optimize_path_device captured as hipGraphs (pqp_chain.hip).  capturing: the handle's stream is in capture
-    // mode - no timing events, the path solve resets its ticket counter inside the graph
-    bool capturing = false;
-    int opt_chain_graph = 0;
-    struct ChainGraph { std::vector<unsigned char> key; hipGraphExec_t exec = nullptr; bool failed = false; bool lane_launch = false; long long lane_launches = 0; int path_kernel = 0; unsigned long long ticket_after = 0; };
-    std::vector<ChainGraph> chain_graphs;
-    int warm_batch = 0, warm_n = 0;
-    bool warm_stored = false;                   // the last solve wrote its final iterate to wx / wy / wye
-    DevBuf wx, wy, wye, wrho, wsave, wscale;    // warm state (lane layout) + polish save area, parked Ruiz vectors (per workgroup slot)
-    // work distribution of the solve kernel: ticket counter (never reset: a launch uses batch + grid tickets), cost bins of the
-    // last solve and the ticket -> QP order derived from them
-    DevBuf ticket, cost_key, cost_hist, order;
-    DevBuf chain_d, chain_i;                    // workspace of pqp_optimize_path_device
-    unsigned long long ticket_next = 0;
-    long long solves = 0;                       // solve launches so far (parity selects the cost histogram being filled)
-    int hist_batch = 0, hist_n = 0;             // shape of the solve whose costs cost_key / cost_hist hold (0: none)
-    int opt_store_warm = 1, opt_order_by_cost = 0, opt_reserve_cus = 0, opt_stream_batch = -1, opt_carry = 0, opt_stream_staged = -1;      // (opt_stream_batch < 0: stream_batch_auto(n))
-    int opt_long_lines = 0;                            // PQP_OPT_LONG_LINES: 0 LDS forms only, 1 long form where the LDS form does not fit, 2 long forms
-    DevBuf line_ws;                                    // workspace of the long forms of the line kernels (one launch at a time on the stream)
-    int stream_last_batch = 0, stream_last_n = 0;      // shape of the last path_stream_kernel launch (what its workspace still holds)
-    int last_path_kernel = 0;                          // pqp_path_kernel of the last pqp_path_solve* launch (pqp_last_path_kernel)
-    DevBuf sm_act[2];                                  // final active sets of the exact TensionSmoother / postSmooth kernels (PQP_OPT_CARRY_CYCLES)
-    int sm_act_batch[2] = {0, 0}, sm_act_n[2] = {0, 0};
-    DevBuf stream_ws;                           // workspace of path_stream_kernel
-    DevBuf stream_key, stream_hist, stream_order;      // PQP_OPT_ORDER_BY_COST on that kernel: phase keys, key histogram, two slot -> QP maps
-    long long stream_solves = 0;                // ordered launches so far (parity selects the map being read)
-    int stream_order_batch = 0, stream_order_n = 0;    // shape the map being read was built for (0: none)
-    int num_cu = 0;
-    int blocks_per_cu[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // occupancy of the solve kernel variants [log2(nw)][cert]
+
+    // path_solve_impl (pqp_kernels.hip): the lane-per-waypoint path kernel
+    struct PQP_HIDDEN LanePath {
+        DevBuf wx, wy, wye, wrho, wsave, wscale;    // warm state (lane layout) + polish save area, parked Ruiz vectors (per workgroup slot)
+        // work distribution of the solve kernel: ticket counter (never reset: a launch uses batch + grid tickets), cost bins of the
+        // last solve and the ticket -> QP order derived from them
+        DevBuf ticket, cost_key, cost_hist, order;
+        unsigned long long ticket_next = 0;
+        long long solves = 0;                       // solve launches so far (parity selects the cost histogram being filled)
+        int hist_batch = 0, hist_n = 0;             // shape of the solve whose costs cost_key / cost_hist hold (0: none)
+        int blocks_per_cu[8] = {0, 0, 0, 0, 0, 0, 0, 0};    // occupancy of the solve kernel variants [log2(nw)][cert]
+        // The outcome of the handle's last path solve, whichever kernel ran it.  This is the one home of these four: path_stream_impl
+        // writes them too, through solved() and nothing else (a launch of the lane-per-QP kernel keeps no warm state: stored = false).
+        int warm_batch = 0, warm_n = 0;
+        bool warm_stored = false;                   // the last solve wrote its final iterate to wx / wy / wye
+        int last_path_kernel = 0;                   // pqp_path_kernel of the last pqp_path_solve* launch (pqp_last_path_kernel)
+        void solved(int kernel, int batch, int n, bool stored) { warm_batch = batch; warm_n = n; warm_stored = stored; last_path_kernel = kernel; }
+        bool warm_is(int batch, int n) const { return warm_stored && warm_batch == batch && warm_n == n; }
+
+        // a captured launch holds: which of the two order arrays it reads (launch parity), whether it reads one at all, and the warm / carry
+        // decisions of path_solve_impl (ticket_next is not in it: a captured launch resets the device counter itself)
+        void key(Key& k) const {
+            k.put_int(solves & 1); k.put_int(hist_batch); k.put_int(hist_n); k.put_int(warm_batch); k.put_int(warm_n); k.put_int(warm_stored ? 1 : 0);
+        }
+
+        // The host bookkeeping of a chain body around its capture and its replays (pqp_optimize_path_device).  Only a body whose path solve
+        // ran on the lane-per-waypoint kernel touches the ticket counter (the graph resets it and leaves it at ticket_after) and counts solve
+        // launches; a body that went to path_stream_kernel leaves both alone - plain pqp_path_solve* calls on the handle between two replays
+        // keep their counter.
+        struct Mark { long long solves; unsigned long long ticket_next; };
+        struct Replay { long long lane_launches = 0; int path_kernel = 0; unsigned long long ticket_after = 0; };     // (lane_launches: two with second_pass = BOUNDS_ON_STATES)
+        Mark mark() const { return {solves, ticket_next}; }
+        // nothing of the captured body has run: undo its bookkeeping
+        void rewind(const Mark& m) { solves = m.solves; ticket_next = m.ticket_next; }
+        // what the capture recorded since `m`, for every replay; the launches it counted only happen then
+        Replay captured(const Mark& m) { const Replay r{solves - m.solves, last_path_kernel, ticket_next}; solves = m.solves; return r; }
+        // the host-side state a plain run of the body leaves (everything else the body sets is the same from call to call: it is in the key)
+        void replayed(const Replay& r) {
+            if (r.lane_launches) { ticket_next = r.ticket_after; solves += r.lane_launches; }
+            last_path_kernel = r.path_kernel;        // (pqp_last_path_kernel: the kernel the replayed body's path solve runs on)
+        }
+    } lane;
+
+    // path_stream_impl (pqp_kernels.hip): the lane-per-QP path kernel
+    struct PQP_HIDDEN StreamPath {
+        DevBuf ws;                                  // workspace of path_stream_kernel
+        DevBuf key_buf, hist, order;                // PQP_OPT_ORDER_BY_COST on that kernel: phase keys, key histogram, two slot -> QP maps
+        long long solves = 0;                       // ordered launches so far (parity selects the map being read)
+        int order_batch = 0, order_n = 0;           // shape the map being read was built for (0: none)
+        int last_batch = 0, last_n = 0;             // shape of the last path_stream_kernel launch (what its workspace still holds)
+        // a captured launch holds the carry decision; the ordered launches are off inside a capture, so their state decides nothing there
+        void key(Key& k) const { k.put_int(last_batch); k.put_int(last_n); }
+    } strm;
+
+    // pqp_smoothers.hip
+    struct PQP_HIDDEN Smoothers {
+        // smoother QPs: banded problem data + shared sparsity (cached per type and size)
+        DevBuf pband, q, aval, lo, up, x, y, acol, trow, tslot;
+        int struct_type = -1, struct_n = -1;
+        DevBuf act[2];                              // final active sets of the exact TensionSmoother / postSmooth kernels (PQP_OPT_CARRY_CYCLES)
+        int act_batch[2] = {0, 0}, act_n[2] = {0, 0};
+        // a captured launch holds the carry flags of the exact kernels; a structure upload cannot be captured at all (sm_upload_structure)
+        void key(Key& k) const {
+            k.put_int(act_batch[0]); k.put_int(act_n[0]); k.put_int(act_batch[1]); k.put_int(act_n[1]); k.put_int(struct_type); k.put_int(struct_n);
+        }
+    } sm;
+
+    // line_launch: workspace of the long forms of the line kernels (one launch at a time on the stream).
+    // (no key: which form runs follows from opt.long_lines and the call's sizes; a reallocation moves the allocation generation)
+    struct PQP_HIDDEN Lines { DevBuf ws; } lines;
+
+    // one captured chain: the key it was captured under, and what its replays do to the path handle's bookkeeping
+    struct ChainGraph { Key key; hipGraphExec_t exec = nullptr; bool failed = false; LanePath::Replay replay; };
+    // pqp_optimize_path_device (pqp_chain.hip).  capturing: the handle's stream is in capture mode - no timing events, the path solve
+    // resets its ticket counter inside the graph.  (no key: it is the key's user)
+    struct PQP_HIDDEN Chain {
+        DevBuf d, i;                                // workspace (pqp_chain_ws.hpp)
+        std::vector<ChainGraph> graphs;
+        bool capturing = false;
+    } chain;
+
     static constexpr int kStage = 12;
     DevBuf stage[kStage];                       // device copies of the arrays of a host-pointer entry point (Staging), in argument order
-    // smoother QPs: banded problem data + shared sparsity (cached per type and size)
-    DevBuf b_pband, b_q, b_aval, b_lo, b_up, b_x, b_y, b_acol, b_trow, b_tslot;
-    int b_struct_type = -1, b_struct_n = -1;
+                                                // (no key: the chain is a device-pointer entry point and stages nothing)
+
+    void invalidate(unsigned stale) {
+        if (stale & pqp_internal::kStaleCostOrder) { lane.hist_batch = 0; strm.order_batch = 0; }
+        if (stale & pqp_internal::kStaleStreamCarry) strm.last_batch = 0;
+        if (stale & pqp_internal::kStaleSmootherCarry) sm.act_batch[0] = sm.act_batch[1] = 0;
+    }
 };
 
-namespace pqp_internal __attribute__((visibility("hidden"))) {
+namespace pqp_internal PQP_HIDDEN {
 
 inline int hip_ok(hipError_t e, const char* what) { return e == hipSuccess ? PQP_OK : fail(PQP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 
@@ -180,13 +301,13 @@ class Staging {
 inline int sm_carry_slot(pqp_handle* h, int slot, int batch, int n, signed char*& act_io, int& carry) {
     act_io = nullptr;
     carry = 0;
-    if (!h->opt_carry) return PQP_OK;
-    const void* before = h->sm_act[slot].p;
+    if (!h->opt.carry) return PQP_OK;
+    const void* before = h->sm.act[slot].p;
     int rc;
-    if ((rc = h->sm_act[slot].ensure((size_t)batch * n))) return rc;
-    act_io = h->sm_act[slot].as<signed char>();
-    carry = (h->sm_act_batch[slot] == batch && h->sm_act_n[slot] == n && before == h->sm_act[slot].p) ? 1 : 0;
-    h->sm_act_batch[slot] = batch; h->sm_act_n[slot] = n;
+    if ((rc = h->sm.act[slot].ensure((size_t)batch * n))) return rc;
+    act_io = h->sm.act[slot].as<signed char>();
+    carry = (h->sm.act_batch[slot] == batch && h->sm.act_n[slot] == n && before == h->sm.act[slot].p) ? 1 : 0;
+    h->sm.act_batch[slot] = batch; h->sm.act_n[slot] = n;
     return PQP_OK;
 }
 
@@ -197,8 +318,8 @@ inline int sm_carry_slot(pqp_handle* h, int slot, int batch, int n, signed char*
 template <class F>
 int sm_exact_launch(pqp_handle* h, int batch, int n, int arrays, F&& launch) {
     int rc;
-    if (n > 1024 && (rc = h->b_pband.ensure((size_t)batch * arrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
-    double* ws = n > 1024 ? h->b_pband.as<double>() : nullptr;
+    if (n > 1024 && (rc = h->sm.pband.ensure((size_t)batch * arrays * (64 * (((size_t)n + 63) / 64)) * 8))) return rc;
+    double* ws = n > 1024 ? h->sm.pband.as<double>() : nullptr;
     return h->launch_timed([&]() -> int {
         if (n <= 64) launch(std::integral_constant<int, 1>(), ws);
         else if (n <= 128) launch(std::integral_constant<int, 2>(), ws);
@@ -220,12 +341,12 @@ template <class F>
 int line_launch(pqp_handle* h, const void* fn, size_t lds, const char* who, size_t ws_bytes, F&& launch, const void* long_fn = nullptr,
                 size_t long_lds = 0, const char* long_who = nullptr) {
     bool go_long = false;
-    int rc = long_form(h->opt_long_lines, fn, lds, &go_long);
+    int rc = long_form(h->opt.long_lines, fn, lds, &go_long);
     if (!rc && !go_long) rc = lds_opt_in(fn, lds, who);
     if (!rc && go_long && long_fn) rc = lds_opt_in(long_fn, long_lds, long_who);
-    if (!rc && go_long && ws_bytes) rc = h->line_ws.ensure(ws_bytes);
+    if (!rc && go_long && ws_bytes) rc = h->lines.ws.ensure(ws_bytes);
     if (rc) return rc;
-    double* ws = h->line_ws.as<double>();
+    double* ws = h->lines.ws.as<double>();
     return h->launch_timed([&]() -> int {
         if (go_long) launch(std::true_type(), ws);
         else launch(std::false_type(), ws);

@@ -329,14 +329,14 @@ int pqp_create(pqp_handle** out, const pqp_params* params, int device, int max_b
     auto build = [&]() -> int {
         PQP_HIP(hipDeviceGetAttribute(&h->num_cu, hipDeviceAttributeMultiprocessorCount, device));
         PQP_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        for (int k = 0; k < pqp_handle::kEvSlots; ++k) { PQP_HIP(hipEventCreate(&h->evs0[k])); PQP_HIP(hipEventCreate(&h->evs1[k])); }
+        for (int k = 0; k < pqp_handle::Timing::kEvSlots; ++k) { PQP_HIP(hipEventCreate(&h->timing.evs0[k])); PQP_HIP(hipEventCreate(&h->timing.evs1[k])); }
         for (int k = 0; k < pqp_handle::kMarks + pqp_handle::kChainMarks; ++k) PQP_HIP(hipEventCreateWithFlags(&h->marks[k], hipEventDisableTiming));
         int rc;
-        if ((rc = h->ticket.ensure(8)) || (rc = h->cost_hist.ensure(2 * pqp::kCostBins * 4))) return rc;
+        if ((rc = h->lane.ticket.ensure(8)) || (rc = h->lane.cost_hist.ensure(2 * pqp::kCostBins * 4))) return rc;
         if (max_batch > 0 && max_n > 0) {
             const size_t bn = (size_t)max_batch * max_n;
-            if ((rc = h->wx.ensure(bn * 6 * 8)) || (rc = h->wy.ensure(bn * 6 * 8)) || (rc = h->wye.ensure((size_t)max_batch * 2 * 8)) ||
-                (rc = h->wrho.ensure((size_t)max_batch * 8)))
+            if ((rc = h->lane.wx.ensure(bn * 6 * 8)) || (rc = h->lane.wy.ensure(bn * 6 * 8)) || (rc = h->lane.wye.ensure((size_t)max_batch * 2 * 8)) ||
+                (rc = h->lane.wrho.ensure((size_t)max_batch * 8)))
                 return rc;
         }
         return PQP_OK;
@@ -354,9 +354,9 @@ int pqp_destroy(pqp_handle* h) {
     // (captured chains of OTHER handles may hold this handle's workspaces and events - the smoother handle of a pair: their keys carry the
     //  allocation generation, so none of them is replayed after this)
     g_alloc_generation.fetch_add(1, std::memory_order_relaxed);
-    for (auto& g : h->chain_graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    h->chain_graphs.clear();
-    for (int k = 0; k < pqp_handle::kEvSlots; ++k) { if (h->evs0[k]) (void)hipEventDestroy(h->evs0[k]); if (h->evs1[k]) (void)hipEventDestroy(h->evs1[k]); }
+    for (auto& g : h->chain.graphs) if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    h->chain.graphs.clear();
+    for (int k = 0; k < pqp_handle::Timing::kEvSlots; ++k) { if (h->timing.evs0[k]) (void)hipEventDestroy(h->timing.evs0[k]); if (h->timing.evs1[k]) (void)hipEventDestroy(h->timing.evs1[k]); }
     for (int k = 0; k < pqp_handle::kMarks + pqp_handle::kChainMarks; ++k) if (h->marks[k]) (void)hipEventDestroy(h->marks[k]);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;           // (its DevBufs free themselves)
@@ -372,17 +372,13 @@ int pqp_set_params(pqp_handle* h, const pqp_params* params) {
 
 int pqp_set_option(pqp_handle* h, int option, int value) {
     if (!h) return fail(PQP_ERR_INVALID, "pqp_set_option: null handle");
-    switch (option) {
-        case PQP_OPT_STORE_WARM: h->opt_store_warm = value ? 1 : 0; return PQP_OK;
-        case PQP_OPT_ORDER_BY_COST: h->opt_order_by_cost = value ? 1 : 0; h->hist_batch = 0; h->stream_order_batch = 0; return PQP_OK;
-        case PQP_OPT_RESERVE_CUS: h->opt_reserve_cus = value < 0 ? 0 : value; return PQP_OK;
-        case PQP_OPT_STREAM_BATCH: h->opt_stream_batch = value < 0 ? -1 : value; return PQP_OK;
-        case PQP_OPT_STREAM_STAGED: h->opt_stream_staged = value < 0 ? -1 : (value ? 1 : 0); h->stream_last_batch = 0; return PQP_OK;      // (another layout: nothing to carry)
-        case PQP_OPT_CARRY_CYCLES: h->opt_carry = value < 0 ? 0 : (value > 64 ? 64 : value); h->stream_last_batch = 0; h->sm_act_batch[0] = h->sm_act_batch[1] = 0; return PQP_OK;
-        case PQP_OPT_CHAIN_GRAPH: h->opt_chain_graph = value == 2 ? 2 : (value ? 1 : 0); return PQP_OK;
-        case PQP_OPT_LONG_LINES: h->opt_long_lines = value >= 2 ? 2 : (value == 1 ? 1 : 0); return PQP_OK;
-        default: return fail(PQP_ERR_INVALID, "pqp_set_option: unknown option");
+    for (const OptionRow& row : kOptionTable) {
+        if (row.id != option) continue;
+        h->opt.*row.member = row.normalise(value);
+        h->invalidate(row.stale);
+        return PQP_OK;
     }
+    return fail(PQP_ERR_INVALID, "pqp_set_option: unknown option");
 }
 
 int pqp_get_stream(pqp_handle* h, void** s) {
@@ -500,53 +496,45 @@ static int path_stream_impl(pqp_handle* h, int batch, int n, const int32_t* n_of
                             const double* scal, int passes, double* out, int32_t* status, int32_t* iters, double* info) {
     const int waves = (batch + 63) / 64;
     int rc;
-    const void* ws_before = h->stream_ws.p;
-    if ((rc = h->stream_ws.ensure((size_t)waves * n * pqp::lq::kBlockDoubles * 64 * 8))) return rc;
+    const void* ws_before = h->strm.ws.p;
+    if ((rc = h->strm.ws.ensure((size_t)waves * n * pqp::lq::kBlockDoubles * 64 * 8))) return rc;
     pqp::lq::Args a;
     std::memset(&a, 0, sizeof(a));
     a.batch = batch; a.n = n; a.passes = passes; a.n_of = n_of; a.ref = ref; a.lin = lin; a.bounds = bounds; a.scal = scal; a.out = out;
-    a.status = status; a.iters = iters; a.info = info; a.ws = h->stream_ws.as<double>(); a.prm = h->prm;
+    a.status = status; a.iters = iters; a.info = info; a.ws = h->strm.ws.as<double>(); a.prm = h->prm;
     // Which of the kernel's two workspace layouts (pqp_path_lq_abi.hpp): a launch that leaves SIMDs idle - fewer than 768 wavefronts - waits for its loads, not for
     // HBM's throughput: the sweeps' records staged in LDS two waypoints ahead, +29 ... 33 % at 24 576 / 32 768 QPs of 80 waypoints; a launch that fills the chip
     // loses 3-4 % with them (profiles/r06au_*) and keeps the [field][lane] layout and the register prefetch.  A function of the shape alone: what PQP_OPT_CARRY_CYCLES
     // finds in the workspace was left there in the same layout.
-    a.staged = h->opt_stream_staged >= 0 ? h->opt_stream_staged : (waves < 3 * h->num_cu ? 1 : 0);
+    a.staged = h->opt.stream_staged >= 0 ? h->opt.stream_staged : (waves < 3 * h->num_cu ? 1 : 0);
     // PQP_OPT_CARRY_CYCLES: the workspace still holds, slot by slot, the optimum of the previous launch of this very shape
-    a.carry = (h->opt_carry && !lin && h->stream_last_batch == batch && h->stream_last_n == n && h->stream_ws.p == ws_before) ? 1 : 0;       // (lin == NULL: pqp.h)
+    a.carry = (h->opt.carry && !lin && h->strm.last_batch == batch && h->strm.last_n == n && h->strm.ws.p == ws_before) ? 1 : 0;       // (lin == NULL: pqp.h)
     // PQP_OPT_ORDER_BY_COST: wavefronts of QPs that ran the same phases in the handle's previous solve of the shape.  Only where it pays - batches that
     // put a wavefront on (nearly) every SIMD: below that a launch lasts as long as one wavefront's sweeps whatever its lanes do (profiles/r05g_*) - and
     // not with PQP_OPT_CARRY_CYCLES (a slot's workspace then holds the previous optimum of the QP that sat there) or inside a graph capture (host-side parity).
-    const bool ordered = h->opt_order_by_cost && !h->opt_carry && !h->capturing && waves >= 3 * h->num_cu;
+    const bool ordered = h->opt.order_by_cost && !h->opt.carry && !h->chain.capturing && waves >= 3 * h->num_cu;
     if (ordered) {
-        if ((rc = h->stream_key.ensure((size_t)batch * 4)) || (rc = h->stream_hist.ensure(((size_t)pqp::lq::kOrderBins + 1) * 4)) ||
-            (rc = h->stream_order.ensure((size_t)2 * batch * 4)))
+        if ((rc = h->strm.key_buf.ensure((size_t)batch * 4)) || (rc = h->strm.hist.ensure(((size_t)pqp::lq::kOrderBins + 1) * 4)) ||
+            (rc = h->strm.order.ensure((size_t)2 * batch * 4)))
             return rc;
-        if (h->stream_order_batch != batch || h->stream_order_n != n) {          // a shape change: stale counts, no map yet
-            PQP_HIP(hipMemsetAsync(h->stream_hist.p, 0, ((size_t)pqp::lq::kOrderBins + 1) * 4, h->stream));
+        if (h->strm.order_batch != batch || h->strm.order_n != n) {          // a shape change: stale counts, no map yet
+            PQP_HIP(hipMemsetAsync(h->strm.hist.p, 0, ((size_t)pqp::lq::kOrderBins + 1) * 4, h->stream));
             a.order = nullptr;
         } else {
-            a.order = h->stream_order.as<int32_t>() + (size_t)(h->stream_solves & 1) * batch;
+            a.order = h->strm.order.as<int32_t>() + (size_t)(h->strm.solves & 1) * batch;
         }
-        a.key_out = h->stream_key.as<int32_t>();
-        a.hist = h->stream_hist.as<int32_t>();
-        a.order_next = h->stream_order.as<int32_t>() + (size_t)((h->stream_solves + 1) & 1) * batch;
+        a.key_out = h->strm.key_buf.as<int32_t>();
+        a.hist = h->strm.hist.as<int32_t>();
+        a.order_next = h->strm.order.as<int32_t>() + (size_t)((h->strm.solves + 1) & 1) * batch;
     }
     // (path_stream_kernel lives in its own translation unit, pqp_path_stream.hip)
     if ((rc = h->launch_timed([&]() -> int { PQP_HIP(pqp_stream_launch(&a, waves, (void*)h->stream)); return PQP_OK; }))) return rc;
-    if (ordered) { h->stream_solves += 1; h->stream_order_batch = batch; h->stream_order_n = n; }
-    h->stream_last_batch = batch; h->stream_last_n = n;
-    h->warm_batch = batch; h->warm_n = n;
-    h->warm_stored = false;
-    h->last_path_kernel = PQP_KERNEL_LANE_PER_QP;
+    if (ordered) { h->strm.solves += 1; h->strm.order_batch = batch; h->strm.order_n = n; }
+    h->strm.last_batch = batch; h->strm.last_n = n;
+    h->lane.solved(PQP_KERNEL_LANE_PER_QP, batch, n, /*stored=*/false);
     return PQP_OK;
 }
 
-// PQP_OPT_STREAM_BATCH "auto": the batch size from which the lane-per-QP kernel is the faster one, by measurement on one MI355X
-// (profiles/r05a_crossover_n80.txt, r05a_crossover_n120.txt: 18.7 k QPs at 80 waypoints, ~45 k at 120).  A lone wavefront of that kernel
-// takes sweeps x n waypoint steps whatever the batch (5.5 ms at n = 80, 10.5 ms at n = 120), the lane-per-waypoint kernel's time per QP hardly
-// depends on n: the crossover grows like n^2.
-// Beyond 256 waypoints the lane-per-waypoint kernel runs two wavefronts per SIMD on half the registers and takes 4.1 ... 4.9 us per QP instead
-// of 1.0: the crossover is back at 16.7 k / 22.5 k / 32 k QPs at 300 / 400 / 512 waypoints (profiles/r05t_crossover_long_paths.txt): 64 n.
 // the lane-per-waypoint kernels, by wavefronts per QP (pqp_path_solve.hip compiled with -DPQP_NW=1 / 2 / 4 / 8); cert: with the in-loop
 // infeasibility certificate
 extern "C" {
@@ -572,19 +560,20 @@ static bool path_solve_ok(pqp_handle* h, int batch, int n, const double* ref, co
     return h && ref && bounds && scal && out && batch >= 1 && n >= 2 && passes >= 0;
 }
 
-static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* ref, const double* lin, const double* bounds,
-                           const double* scal, int passes, int warm, double* out, int32_t* status, int32_t* iters, double* info) {
-    if (!path_solve_ok(h, batch, n, ref, bounds, scal, passes, out)) return fail(PQP_ERR_INVALID, "pqp_path_solve: bad argument");
-    PQP_HIP(hipSetDevice(h->device));
+// ---- path_solve_impl in its steps: route, plan, arguments, launch, commit ---------------------------------------------------------
+
+// 1. Route: which kernel serves the call, and whether a cold call is promoted to a warm one (PQP_OPT_CARRY_CYCLES)
+struct PathRoute { bool stream; int warm, carry_tails; };
+static PathRoute path_route(const pqp_handle* h, int batch, int n, const double* lin, int warm) {
     // lane-per-QP kernel: large batches of a caller that keeps no warm state (PQP_OPT_STREAM_BATCH), and every path of more than 512
     // waypoints (the lane-per-waypoint kernel's workgroup ends there; a reference path of 80 m at 0.15 m spacing has 530:
     // reference_path_impl.cpp:321-336) - those with any batch size and without warm state
     // (warm == 1 beyond 512 waypoints: the QP around `lin` is solved cold - its optimum is unique, a warm start only saves iterations -
     //  so BaseSolver::solve + updateProblemFormulationAndSolve work at any size; and there also a handle in the reference's ADMM setting
     //  gets the exact optimum: zero residuals meet OSQP's termination test at any eps)
-    const int stream_from = h->opt_stream_batch < 0 ? stream_batch_auto(n) : h->opt_stream_batch;
-    if ((n > 512 && (!warm || lin)) || (h->prm.polish != 0 && !warm && !h->opt_store_warm && stream_from > 0 && batch >= stream_from))
-        return path_stream_impl(h, batch, n, n_of, ref, lin, bounds, scal, passes, out, status, iters, info);
+    const int stream_from = h->opt.stream_batch < 0 ? stream_batch_auto(n) : h->opt.stream_batch;
+    if ((n > 512 && (!warm || lin)) || (h->prm.polish != 0 && !warm && !h->opt.store_warm && stream_from > 0 && batch >= stream_from))
+        return {true, warm, 0};
     // PQP_OPT_CARRY_CYCLES on this kernel: a cold call (warm == 0, lin == NULL) of the shape of the handle's previous solve starts from
     // the final iterate, equilibration and active set that solve left in the warm state - the same scenarios one planning cycle later.
     // (With waypoint counts per QP the state is kept per waypoint: a path that grew or shrank by a few waypoints since the previous cycle
@@ -593,25 +582,55 @@ static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of,
     //  eps-accurate point that depends on the slot's previous QP, and pqp.h promises the cold solve's optimum to the 1e-7 of the KKT test)
     // (value k >= 2, "tails": only the QPs that were among the most expensive 1 / k of the previous launch - by the cost keys PQP_OPT_ORDER_BY_COST
     //  keeps - start from there, the others start cold: what bounds a launch is its slowest QPs)
-    int carry_tails = 0;
-    if (h->opt_carry && h->prm.polish != 0 && !warm && !lin && h->warm_stored && h->warm_batch == batch && h->warm_n == n &&
-        (h->opt_carry < 2 || (h->opt_order_by_cost && h->hist_batch == batch && h->hist_n == n))) { warm = 1; carry_tails = h->opt_carry >= 2 ? h->opt_carry : 0; }
-    if (n > 512) return fail(PQP_ERR_CAPACITY, "pqp_path_solve: warm == 1 beyond 512 waypoints needs the linearisation point (`lin`): the lane-per-QP kernel keeps no warm state");
-    if (warm && (h->warm_batch != batch || h->warm_n != n || !h->warm_stored))
-        return fail(PQP_ERR_INVALID, "pqp_path_solve: warm == 1 needs a previous solve with the same batch and n (with PQP_OPT_STORE_WARM on)");
-    const size_t bn = (size_t)batch * n;
-    int rc;
-    if (!warm) {
-        if ((rc = h->wx.ensure(bn * 6 * 8)) || (rc = h->wy.ensure(bn * 6 * 8)) || (rc = h->wye.ensure((size_t)batch * 2 * 8)) ||
-            (rc = h->wrho.ensure((size_t)batch * 8)))
-            return rc;
+    if (h->opt.carry && h->prm.polish != 0 && !warm && !lin && h->lane.warm_is(batch, n) &&
+        (h->opt.carry < 2 || (h->opt.order_by_cost && h->lane.hist_batch == batch && h->lane.hist_n == n)))
+        return {false, 1, h->opt.carry >= 2 ? h->opt.carry : 0};
+    return {false, warm, 0};
+}
+
+// 2. Plan: the kernel variant and its launch geometry for paths of n waypoints, with the workgroup slots' save area allocated
+struct PathPlan { const void* fn; int threads, grid; size_t lds; };
+static int path_plan(pqp_handle* h, int batch, int n, bool cert, PathPlan* plan) {
+    int nw = 1, lg = 0;
+    while (64 * nw < n) { nw *= 2; lg += 1; }           // one waypoint per lane: T = 64 * nw >= n threads per QP
+    const int T_lanes = 64 * nw;
+    const bool save_lds = nw <= pqp::kSaveLdsMaxNw;
+    const size_t lds = (size_t)pqp::ShLayout{T_lanes}.total(save_lds) * 8;
+    const void* fn = nullptr;
+    switch (nw) {       // (pqp_path_solve.hip, one translation unit per width)
+        case 1: fn = pqp_path_solve_fn_nw1(cert); break;
+        case 2: fn = pqp_path_solve_fn_nw2(cert); break;
+        case 4: fn = pqp_path_solve_fn_nw4(cert); break;
+        default: fn = pqp_path_solve_fn_nw8(cert); break;
     }
-    pqp::PathSolveArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.batch = batch; a.n = n; a.n_of = n_of; a.passes = passes; a.warm = warm ? 1 : 0;
-    a.ref = ref; a.lin = lin; a.bounds = bounds; a.scal = scal; a.out = out;
-    a.status = status; a.iters = iters; a.info = info;
-    a.wx = h->wx.as<double>(); a.wy = h->wy.as<double>(); a.wye = h->wye.as<double>(); a.wrho = h->wrho.as<double>();
+    int rc;
+    if ((rc = lds_opt_in(fn, lds, "pqp_path_solve: LDS"))) return rc;
+    // persistent workgroups: as many as the chip holds at once (a surplus one would only wait for a free slot), each with its own
+    // save area; they draw the QPs from the ticket counter
+    int& per_cu = h->lane.blocks_per_cu[2 * lg + (cert ? 1 : 0)];
+    if (per_cu == 0) {
+        PQP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, T_lanes, lds));
+        if (per_cu < 1) per_cu = 1;
+    }
+    const int cus = h->num_cu - h->opt.reserve_cus > 1 ? h->num_cu - h->opt.reserve_cus : 1;
+    const long long resident = (long long)per_cu * cus;
+    const int grid = (int)(batch < resident ? batch : resident);
+    if (!save_lds) {          // more than 256 lanes per QP: the save area and the parked Ruiz vectors live in the workgroup slot's global memory
+        if ((rc = h->lane.wsave.ensure((size_t)grid * T_lanes * PQP_SAVE_STRIDE * 8))) return rc;
+        if ((rc = h->lane.wscale.ensure((size_t)grid * T_lanes * 18 * 8))) return rc;
+    }
+    *plan = {fn, T_lanes, grid, lds};
+    return PQP_OK;
+}
+
+// 3. Arguments, the part that is the handle's: its buffers, parameters and options, the ticket base, the cost order.  What it enqueues
+// (the ticket reset of a capture, the clearing of a stale histogram) precedes the launch on the stream.
+static int path_args(pqp_handle* h, const PathRoute& route, pqp::PathSolveArgs& a) {
+    pqp_handle::LanePath& L = h->lane;
+    const int batch = a.batch, n = a.n;
+    int rc;
+    a.warm = route.warm ? 1 : 0;
+    a.wx = L.wx.as<double>(); a.wy = L.wy.as<double>(); a.wye = L.wye.as<double>(); a.wrho = L.wrho.as<double>();
     a.prm = h->prm;
     // Long paths: the polished point's residuals in the transition rows add up along the path - the rows are a discrete double integrator, an error of
     // 1e-9 per row in (psi, kappa) is 1e-4 in l after 300 waypoints - so an accepted point gets one more refinement solve per pass beyond 128 waypoints, three beyond 256 (each shrinks the error ~10x: 4.6e-3 -> 4.4e-4 -> 4.1e-5 -> 3.3e-6 on
@@ -620,78 +639,84 @@ static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of,
     // and 117 of 300 were 3e-5 ... 4.6e-3 off (the lane-per-QP kernel, whose roll-out satisfies the rows exactly: 5e-6).
     // ... and the production setting's intervals by path length (pqp_defaults.hpp)
     pqp::resolve_path_params(&a.prm, n);
-    int nw = 1, lg = 0;
-    while (64 * nw < n) { nw *= 2; lg += 1; }           // one waypoint per lane: T = 64 * nw >= n threads per QP
-    const int T_lanes = 64 * nw;
-    const bool save_lds = nw <= pqp::kSaveLdsMaxNw;
-    const size_t lds = (size_t)pqp::ShLayout{T_lanes}.total(save_lds) * 8;
-    // two variants of every kernel: with and without OSQP's primal infeasibility certificate (prm.eps_prim_inf > 0)
-    const bool cert = h->prm.eps_prim_inf > 0.0 && h->prm.prim_inf_after <= 0;
-    const void* fn = nullptr;
-    switch (nw) {       // (pqp_path_solve.hip, one translation unit per width)
-        case 1: fn = pqp_path_solve_fn_nw1(cert); break;
-        case 2: fn = pqp_path_solve_fn_nw2(cert); break;
-        case 4: fn = pqp_path_solve_fn_nw4(cert); break;
-        default: fn = pqp_path_solve_fn_nw8(cert); break;
-    }
-    if ((rc = lds_opt_in(fn, lds, "pqp_path_solve: LDS"))) return rc;
-    // persistent workgroups: as many as the chip holds at once (a surplus one would only wait for a free slot), each with its own
-    // save area; they draw the QPs from the ticket counter
-    int& per_cu = h->blocks_per_cu[2 * lg + (cert ? 1 : 0)];
-    if (per_cu == 0) {
-        PQP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * nw, lds));
-        if (per_cu < 1) per_cu = 1;
-    }
-    const int cus = h->num_cu - h->opt_reserve_cus > 1 ? h->num_cu - h->opt_reserve_cus : 1;
-    const long long resident = (long long)per_cu * cus;
-    const int grid = (int)(batch < resident ? batch : resident);
-    if (!save_lds) {          // more than 256 lanes per QP: the save area and the parked Ruiz vectors live in the workgroup slot's global memory
-        if ((rc = h->wsave.ensure((size_t)grid * T_lanes * PQP_SAVE_STRIDE * 8))) return rc;
-        if ((rc = h->wscale.ensure((size_t)grid * T_lanes * 18 * 8))) return rc;
-    }
-    a.wsave = h->wsave.as<double>();
-    a.wscale = h->wscale.as<double>();
-    a.store_warm = (h->opt_store_warm || h->opt_carry) ? 1 : 0;
-    a.carry_tails = carry_tails;
-    a.carry_k = h->opt_carry;
-    a.ticket = h->ticket.as<unsigned long long>();
-    a.ticket_base = h->ticket_next;
+    a.wsave = L.wsave.as<double>();
+    a.wscale = L.wscale.as<double>();
+    a.store_warm = (h->opt.store_warm || h->opt.carry) ? 1 : 0;
+    a.carry_tails = route.carry_tails;
+    a.carry_k = h->opt.carry;
+    a.ticket = L.ticket.as<unsigned long long>();
+    a.ticket_base = L.ticket_next;
     // inside a captured graph the launch cannot take its ticket base from a host counter that moves between replays: the graph resets the
     // device counter itself and every replay starts at 0 (pqp_chain.hip puts the host counter where the replay leaves the device one)
-    if (h->capturing) { PQP_HIP(hipMemsetAsync(h->ticket.p, 0, 8, h->stream)); a.ticket_base = 0; }
-    // Host-side bookkeeping of the launch (ticket base of the next launch, launch parity, shape of the cost histogram) is committed
-    // only after the launch has been accepted: a failing step below (allocation, memset, event, launch) leaves the device ticket
-    // counter and the host's idea of it in step.
-    if (h->opt_order_by_cost) {
+    if (h->chain.capturing) { PQP_HIP(hipMemsetAsync(L.ticket.p, 0, 8, h->stream)); a.ticket_base = 0; }
+    if (h->opt.order_by_cost) {
         // most expensive QPs first, by what they cost in this handle's previous solve of the same shape (a planner re-solves
         // nearly the same scenarios cycle after cycle); results do not depend on the order
-        if ((rc = h->cost_key.ensure((size_t)batch * 4)) || (rc = h->order.ensure((size_t)2 * batch * 4))) return rc;
+        if ((rc = L.cost_key.ensure((size_t)batch * 4)) || (rc = L.order.ensure((size_t)2 * batch * 4))) return rc;
         // two order arrays: the one this launch reads (written by the previous launch's last workgroup) and the one it writes
-        int32_t* order_read = h->order.as<int32_t>() + (size_t)(h->solves & 1) * batch;
-        int32_t* order_write = h->order.as<int32_t>() + (size_t)((h->solves + 1) & 1) * batch;
-        if (h->hist_batch == batch && h->hist_n == n) a.order = order_read;
-        else { h->hist_batch = 0; h->hist_n = 0; PQP_HIP(hipMemsetAsync(h->cost_hist.p, 0, (pqp::kCostBins + 1) * 4, h->stream)); }     // (a shape change: stale counts)
-        a.cost_key = h->cost_key.as<int32_t>();
-        a.cost_hist = h->cost_hist.as<int32_t>();
+        int32_t* order_read = L.order.as<int32_t>() + (size_t)(L.solves & 1) * batch;
+        int32_t* order_write = L.order.as<int32_t>() + (size_t)((L.solves + 1) & 1) * batch;
+        if (L.hist_batch == batch && L.hist_n == n) a.order = order_read;
+        else { L.hist_batch = 0; L.hist_n = 0; PQP_HIP(hipMemsetAsync(L.cost_hist.p, 0, (pqp::kCostBins + 1) * 4, h->stream)); }     // (a shape change: stale counts)
+        a.cost_key = L.cost_key.as<int32_t>();
+        a.cost_hist = L.cost_hist.as<int32_t>();
         a.order_next = order_write;
     }
+    return PQP_OK;
+}
+
+static int path_solve_impl(pqp_handle* h, int batch, int n, const int32_t* n_of, const double* ref, const double* lin, const double* bounds,
+                           const double* scal, int passes, int warm, double* out, int32_t* status, int32_t* iters, double* info) {
+    if (!path_solve_ok(h, batch, n, ref, bounds, scal, passes, out)) return fail(PQP_ERR_INVALID, "pqp_path_solve: bad argument");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp_handle::LanePath& L = h->lane;
+    // ---- 1. route ----
+    const PathRoute route = path_route(h, batch, n, lin, warm);
+    if (route.stream) return path_stream_impl(h, batch, n, n_of, ref, lin, bounds, scal, passes, out, status, iters, info);
+    if (n > 512) return fail(PQP_ERR_CAPACITY, "pqp_path_solve: warm == 1 beyond 512 waypoints needs the linearisation point (`lin`): the lane-per-QP kernel keeps no warm state");
+    if (route.warm && !L.warm_is(batch, n))
+        return fail(PQP_ERR_INVALID, "pqp_path_solve: warm == 1 needs a previous solve with the same batch and n (with PQP_OPT_STORE_WARM on)");
+    const size_t bn = (size_t)batch * n;
+    int rc;
+    if (!route.warm) {
+        if ((rc = L.wx.ensure(bn * 6 * 8)) || (rc = L.wy.ensure(bn * 6 * 8)) || (rc = L.wye.ensure((size_t)batch * 2 * 8)) ||
+            (rc = L.wrho.ensure((size_t)batch * 8)))
+            return rc;
+    }
+    // ---- 2. plan ----
+    // two variants of every kernel: with and without OSQP's primal infeasibility certificate (prm.eps_prim_inf > 0)
+    const bool cert = h->prm.eps_prim_inf > 0.0 && h->prm.prim_inf_after <= 0;
+    PathPlan plan;
+    if ((rc = path_plan(h, batch, n, cert, &plan))) return rc;
+    // ---- 3. arguments: the call's, then the handle's ----
+    pqp::PathSolveArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.batch = batch; a.n = n; a.n_of = n_of; a.passes = passes;
+    a.ref = ref; a.lin = lin; a.bounds = bounds; a.scal = scal; a.out = out;
+    a.status = status; a.iters = iters; a.info = info;
+    if ((rc = path_args(h, route, a))) return rc;
+    // ---- 4. launch, 5. commit ----
+    // Host-side bookkeeping of the launch (ticket base of the next launch, launch parity, shape of the cost histogram) is committed
+    // only after the launch has been accepted: a failing step above or here (allocation, memset, event, launch) leaves the device ticket
+    // counter and the host's idea of it in step.
+    bool accepted = false;
     rc = h->launch_timed([&]() -> int {
         void* kargs[] = {(void*)&a};
-        hipError_t le = hipLaunchKernel(fn, dim3(grid), dim3(64 * nw), kargs, lds, h->stream);
+        hipError_t le = hipLaunchKernel(plan.fn, dim3(plan.grid), dim3(plan.threads), kargs, plan.lds, h->stream);
         if (le == hipSuccess) le = hipGetLastError();
         if (le != hipSuccess) {
-            h->hist_batch = 0; h->hist_n = 0;          // (the histogram may have been cleared for a launch that never ran)
+            L.hist_batch = 0; L.hist_n = 0;          // (the histogram may have been cleared for a launch that never ran)
             return fail(PQP_ERR_HIP, std::string("hipLaunchKernel(path_solve_kernel): ") + hipGetErrorString(le));
         }
-        h->ticket_next = a.ticket_base + (unsigned long long)batch + (unsigned long long)grid;
-        if (h->opt_order_by_cost) { h->hist_batch = batch; h->hist_n = n; }
-        h->solves += 1;
+        accepted = true;
         return PQP_OK;
     });
-    if (rc) return rc;
-    h->warm_batch = batch; h->warm_n = n;
-    h->warm_stored = h->opt_store_warm != 0 || h->opt_carry != 0;
-    h->last_path_kernel = PQP_KERNEL_LANE_PER_WAYPOINT;
+    if (!accepted) return rc;
+    L.ticket_next = a.ticket_base + (unsigned long long)batch + (unsigned long long)plan.grid;
+    if (h->opt.order_by_cost) { L.hist_batch = batch; L.hist_n = n; }
+    L.solves += 1;
+    if (rc) return rc;          // (the launch is on the stream, its closing event is not: the kernel's tickets are spent, the call still fails)
+    L.solved(PQP_KERNEL_LANE_PER_WAYPOINT, batch, n, /*stored=*/h->opt.store_warm != 0 || h->opt.carry != 0);
     return PQP_OK;
 }
 
@@ -760,7 +785,7 @@ int pqp_path_solve_var(pqp_handle* h, int batch, int n_max, const int32_t* n_of,
 
 int pqp_path_get_solution(pqp_handle* h, int batch, int n, int precise, double* x, double* y) {
     if (!h || batch < 1 || n < 2 || precise < 0 || precise > n) return fail(PQP_ERR_INVALID, "pqp_path_get_solution: bad argument");
-    if (h->warm_batch != batch || h->warm_n != n || !h->warm_stored)
+    if (!h->lane.warm_is(batch, n))
         return fail(PQP_ERR_INVALID, "pqp_path_get_solution: no solve of that shape on this handle (or PQP_OPT_STORE_WARM is off)");
     pqp::RefIndex R{n, precise};
     Staging st(h);
@@ -768,8 +793,8 @@ int pqp_path_get_solution(pqp_handle* h, int batch, int n, int precise, double* 
     double* d_y = st.out(y, (size_t)batch * R.cons(), 0);
     return st.run([&]() -> int {
         const int total = batch * n;
-        hipLaunchKernelGGL(pqp::path_gather_solution, dim3((total + 255) / 256), dim3(256), 0, h->stream, R, batch, h->wx.as<double>(),
-                           h->wy.as<double>(), h->wye.as<double>(), x ? d_x : nullptr, y ? d_y : nullptr);
+        hipLaunchKernelGGL(pqp::path_gather_solution, dim3((total + 255) / 256), dim3(256), 0, h->stream, R, batch, h->lane.wx.as<double>(),
+                           h->lane.wy.as<double>(), h->lane.wye.as<double>(), x ? d_x : nullptr, y ? d_y : nullptr);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -785,28 +810,28 @@ int pqp_constrain_angle_device(pqp_handle* h, int count, const double* in, doubl
 
 int pqp_last_path_kernel(pqp_handle* h) {
     if (!h) return fail(PQP_ERR_INVALID, "pqp_last_path_kernel: null handle");
-    return h->last_path_kernel;
+    return h->lane.last_path_kernel;
 }
 
 int pqp_last_kernel_ms(pqp_handle* h, float* ms) {
     if (!h || !ms) return fail(PQP_ERR_INVALID, "pqp_last_kernel_ms: null argument");
-    if (!h->timed) return fail(PQP_ERR_INVALID, "pqp_last_kernel_ms: nothing was launched yet");
+    if (!h->timing.timed) return fail(PQP_ERR_INVALID, "pqp_last_kernel_ms: nothing was launched yet");
     PQP_HIP(hipSetDevice(h->device));
-    const long long idx = (h->ev_count - 1) % pqp_handle::kEvSlots;
-    PQP_HIP(hipEventSynchronize(h->evs1[idx]));
-    PQP_HIP(hipEventElapsedTime(ms, h->evs0[idx], h->evs1[idx]));
+    const long long idx = (h->timing.ev_count - 1) % pqp_handle::Timing::kEvSlots;
+    PQP_HIP(hipEventSynchronize(h->timing.evs1[idx]));
+    PQP_HIP(hipEventElapsedTime(ms, h->timing.evs0[idx], h->timing.evs1[idx]));
     return PQP_OK;
 }
 
 int pqp_kernel_ms_history(pqp_handle* h, float* ms, int count) {
     if (!h || !ms || count < 1) return fail(PQP_ERR_INVALID, "pqp_kernel_ms_history: bad argument");
-    if (count > pqp_handle::kEvRing || (long long)count > h->ev_count)
+    if (count > pqp_handle::Timing::kEvRing || (long long)count > h->timing.ev_count)
         return fail(PQP_ERR_INVALID, "pqp_kernel_ms_history: more launches asked for than the ring holds (256) or were made");
     PQP_HIP(hipSetDevice(h->device));
     PQP_HIP(hipStreamSynchronize(h->stream));
     for (int k = 0; k < count; ++k) {          // oldest of the requested launches first
-        const long long idx = (h->ev_count - count + k) % pqp_handle::kEvSlots;
-        PQP_HIP(hipEventElapsedTime(ms + k, h->evs0[idx], h->evs1[idx]));
+        const long long idx = (h->timing.ev_count - count + k) % pqp_handle::Timing::kEvSlots;
+        PQP_HIP(hipEventElapsedTime(ms + k, h->timing.evs0[idx], h->timing.evs1[idx]));
     }
     return PQP_OK;
 }

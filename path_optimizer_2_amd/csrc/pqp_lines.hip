@@ -85,7 +85,7 @@ int pqp_corridor_bounds_device(pqp_handle* h, int batch, int n, int m, const dou
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
     size_t lds = 0;
     const void* fn = nullptr;
-    if (const int rc = corridor_pick(h->opt_long_lines, (const void*)pqp::corridor_bounds_kernel, (const void*)pqp::long_corridor_kernel, m, n, &fn, &a.tile, &lds,
+    if (const int rc = corridor_pick(h->opt.long_lines, (const void*)pqp::corridor_bounds_kernel, (const void*)pqp::long_corridor_kernel, m, n, &fn, &a.tile, &lds,
                                      "pqp_corridor_bounds")) return rc;
     return h->launch_timed([&]() -> int {
         if (fn == (const void*)pqp::long_corridor_kernel) hipLaunchKernelGGL(pqp::long_corridor_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a);
@@ -130,7 +130,7 @@ int pqp_corridor_bounds_on_states_device(pqp_handle* h, int batch, int n, int m,
     a.g = *geom; a.p = *prm; a.bounds = bounds; a.n_valid = n_valid;
     size_t lds = 0;
     const void* fn = nullptr;
-    if (const int rc = corridor_pick(h->opt_long_lines, (const void*)pqp::states_bounds_kernel, (const void*)pqp::long_states_kernel, m, n, &fn, &a.tile, &lds,
+    if (const int rc = corridor_pick(h->opt.long_lines, (const void*)pqp::states_bounds_kernel, (const void*)pqp::long_states_kernel, m, n, &fn, &a.tile, &lds,
                                      "pqp_corridor_bounds_on_states")) return rc;
     return h->launch_timed([&]() -> int {
         if (fn == (const void*)pqp::long_states_kernel) hipLaunchKernelGGL(pqp::long_states_kernel, dim3(batch), dim3(kCorridorThreads), lds, h->stream, a, states, stride);

@@ -414,23 +414,41 @@ struct Solver {
     // different fields, so one slot holds both.  kBackChunks / kFwdChunks: copies per record (a lower bound: it sizes the wait).
     //   chunks: 0-3 transition (the first pass: 1 and 3), 4-5 boxes, 6-7 gains, 8 X0 X1, 9 X2 GK, 10 ACT LAM, 11-13 the three rows' slacks and multipliers, 14 their steps
     // (chunks of one waypoint go out in groups around a centre chunk - StagedWs::stage_group: one address, one M0 per group)
-    template <int MODE> static constexpr int back_chunks() { return 2 + 2 + ((MODE == MODE_IPM || MODE == MODE_GUESS) ? 5 : 0) + (MODE == MODE_SET ? 1 : 0); }
+    // A record's copies are written down once, as types: Chunks<CENTER, CS...> is one group (count copies), At<DI, G> that group of waypoint
+    // i + DI, Groups<...> a record's list.  stage_back / stage_fwd issue the list and back_chunks / fwd_chunks are its sum - the C of the
+    // sweeps' s_waitcnt vmcnt(C).  LinGroup is not in the lists: it goes out only on re-linearised passes (!lin0), and C must stay the lower
+    // bound that holds on both kinds of pass (too small a C only waits longer, too large a one reads a slot before its copies have landed).
+    template <int CENTER, int... CS> struct Chunks { static constexpr int count = sizeof...(CS); };
+    template <int DI, class G> struct At { using group = G; static constexpr int di = DI; };
+    template <class... E> struct Groups {
+        static constexpr int count = (0 + ... + E::group::count);
+        PQP_HD static void issue(const WS& ws, int slot, int i) { (ws.stage_group(typename E::group{}, slot, i + E::di), ...); }
+    };
+    using LinGroup = Chunks<4, 0, 2>;                                   // the transition's other half: only a re-linearised pass reads it
+    template <int MODE> static constexpr auto back_groups() {
+        using Base = At<0, Chunks<4, 1, 3, 4, 5>>;                     // transition, boxes
+        if constexpr (MODE == MODE_IPM || MODE == MODE_GUESS) return Groups<Base, At<0, Chunks<12, 9, 11, 12, 13, 14>>>{};      // GK, the rows' states and steps
+        else if constexpr (MODE == MODE_SET) return Groups<Base, At<0, Chunks<12, 10>>>{};
+        else return Groups<Base>{};
+    }
+    template <int MODE> static constexpr auto fwd_groups() {
+        using Base = At<0, Chunks<4, 1, 3, 6, 7>>;                     // transition, gains
+        if constexpr (MODE == MODE_IPM) return Groups<Base, At<1, Chunks<4, 4, 5>>, At<1, Chunks<12, 9, 11, 12, 13>>>{};        // boxes | GK, the rows' states
+        else if constexpr (MODE == MODE_SET) return Groups<Base, At<1, Chunks<8, 4, 5, 10>>>{};
+        else if constexpr (MODE == MODE_SET_GUARDED) return Groups<Base, At<1, Chunks<8, 4, 5, 8, 9, 10>>>{};
+        else return Groups<Base, At<1, Chunks<4, 4, 5>>>{};
+    }
+    template <int MODE> static constexpr int back_chunks() { return decltype(back_groups<MODE>())::count; }
+    template <int MODE> static constexpr int fwd_chunks() { return decltype(fwd_groups<MODE>())::count; }
     template <int MODE>
     PQP_HD void stage_back(int slot, int i) const {
-        if (!lin0) ws.template stage_group<4, 0, 2>(slot, i);
-        ws.template stage_group<4, 1, 3, 4, 5>(slot, i);                                                                   // transition, boxes
-        if (MODE == MODE_IPM || MODE == MODE_GUESS) ws.template stage_group<12, 9, 11, 12, 13, 14>(slot, i);              // GK, the rows' states and steps
-        if (MODE == MODE_SET) ws.template stage_group<12, 10>(slot, i);
+        if (!lin0) ws.stage_group(LinGroup{}, slot, i);
+        decltype(back_groups<MODE>())::issue(ws, slot, i);
     }
-    template <int MODE> static constexpr int fwd_chunks() { return 2 + 2 + 2 + (MODE == MODE_IPM ? 4 : 0) + ((MODE == MODE_SET || MODE == MODE_SET_GUARDED) ? 1 : 0) + (MODE == MODE_SET_GUARDED ? 2 : 0); }
     template <int MODE>
     PQP_HD void stage_fwd(int slot, int i) const {
-        if (!lin0) ws.template stage_group<4, 0, 2>(slot, i);
-        ws.template stage_group<4, 1, 3, 6, 7>(slot, i);                                                                   // transition, gains
-        if (MODE == MODE_IPM) { ws.template stage_group<4, 4, 5>(slot, i + 1); ws.template stage_group<12, 9, 11, 12, 13>(slot, i + 1); }       // boxes | GK, the rows' states
-        else if (MODE == MODE_SET) ws.template stage_group<8, 4, 5, 10>(slot, i + 1);
-        else if (MODE == MODE_SET_GUARDED) ws.template stage_group<8, 4, 5, 8, 9, 10>(slot, i + 1);
-        else ws.template stage_group<4, 4, 5>(slot, i + 1);
+        if (!lin0) ws.stage_group(LinGroup{}, slot, i);
+        decltype(fwd_groups<MODE>())::issue(ws, slot, i);
     }
     // a sweep over staged records: the one function the sweeps below call
     template <int MODE, class Body>

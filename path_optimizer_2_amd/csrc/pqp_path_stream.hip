@@ -24,7 +24,9 @@ namespace pqp {
 // (s_waitcnt vmcnt(0)) before every LDS read - the pipeline's depth would be gone.  Here the wait is staged_wait(): at most `later` records'
 // copies may still be in flight; whatever else the wavefront issued in between (its stores) only makes the wait longer, never too short.
 #pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm"      // (M0 is reserved, and named as clobbered: the compiler then restores its own uses)
+#pragma clang diagnostic ignored "-Winline-asm"      // (M0 is reserved.  It is named as clobbered, which tells the compiler the register's value is gone after the
+// statement; LLVM documents no promise to save and restore a reserved register around inline assembly - that no use of M0 of the compiler's own is live across
+// these statements is seen in the kernel's assembly, not guaranteed: ADVICE.md)
 struct StagedWs : lq::ChunkWs {
     static constexpr int kStageDepth = 2;
     const double* lds;        // the wavefront's slots [kStageDepth][kBlockDoubles][64]
@@ -37,7 +39,8 @@ struct StagedWs : lq::ChunkWs {
     // Several chunks of ONE waypoint in one statement: the instruction's 13-bit signed offset moves the source address AND the LDS destination (measured:
     // tools/probes/glds_offset_probe.hip), and a slot is laid out like a workspace block - so the chunks within -4 ... +3 of a centre chunk share one address
     // register pair and one M0: two VALU and two SALU instructions less per chunk after a group's first.
-    template <int CENTER, int... CS> __device__ __forceinline__ void stage_group(int slot, int i) const {
+    // (the group comes as its type, lq::Solver::Chunks: the sweeps' wait counts are summed over the same types)
+    template <template <int, int...> class G, int CENTER, int... CS> __device__ __forceinline__ void stage_group(G<CENTER, CS...>, int slot, int i) const {
         constexpr int n = sizeof...(CS);
         constexpr int o[] = {(CS - CENTER) * 1024 ...};
         static_assert(n >= 1 && n <= 5, "one asm string per count");

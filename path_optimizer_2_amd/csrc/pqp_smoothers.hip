@@ -41,11 +41,11 @@ SmShape sm_shape(int type, int n) {
 
 // shared sparsity of a smoother QP in the interleaved variable order: integer host logic (like pqp_path_sizes)
 int sm_upload_structure(pqp_handle* h, int type, int n) {
-    if (h->b_struct_type == type && h->b_struct_n == n) return PQP_OK;
+    if (h->sm.struct_type == type && h->sm.struct_n == n) return PQP_OK;
     // a host -> device copy from vectors that go out of scope + a synchronise: not something a capturing stream may do.  The capture of
     // pqp_optimize_path_device is abandoned cleanly (the body fails, the call falls back to plain launches and never captures these arguments again:
     // a chain whose smoothers alternate between two structure types on the generic core uploads on every call)
-    if (h->capturing) return fail(PQP_ERR_INVALID, "smoother structure upload inside a graph capture");
+    if (h->chain.capturing) return fail(PQP_ERR_INVALID, "smoother structure upload inside a graph capture");
     const SmShape sh = sm_shape(type, n);
     std::vector<int> acol((size_t)sh.nc * pqp::kRMax, -1), trow((size_t)sh.nv * pqp::kCMax, -1), tslot((size_t)sh.nv * pqp::kCMax, 0);
     auto row = [&](int r, int c0, int c1, int c2) { int* a = &acol[(size_t)r * pqp::kRMax]; a[0] = c0; a[1] = c1; a[2] = c2; };
@@ -72,12 +72,12 @@ int sm_upload_structure(pqp_handle* h, int type, int n) {
             trow[(size_t)c * pqp::kCMax + fill[c]] = r; tslot[(size_t)c * pqp::kCMax + fill[c]] = s; ++fill[c];
         }
     int rc;
-    if ((rc = h->b_acol.ensure(acol.size() * 4)) || (rc = h->b_trow.ensure(trow.size() * 4)) || (rc = h->b_tslot.ensure(tslot.size() * 4))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->b_acol.p, acol.data(), acol.size() * 4, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->b_trow.p, trow.data(), trow.size() * 4, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->b_tslot.p, tslot.data(), tslot.size() * 4, hipMemcpyHostToDevice, h->stream));
+    if ((rc = h->sm.acol.ensure(acol.size() * 4)) || (rc = h->sm.trow.ensure(trow.size() * 4)) || (rc = h->sm.tslot.ensure(tslot.size() * 4))) return rc;
+    PQP_HIP(hipMemcpyAsync(h->sm.acol.p, acol.data(), acol.size() * 4, hipMemcpyHostToDevice, h->stream));
+    PQP_HIP(hipMemcpyAsync(h->sm.trow.p, trow.data(), trow.size() * 4, hipMemcpyHostToDevice, h->stream));
+    PQP_HIP(hipMemcpyAsync(h->sm.tslot.p, tslot.data(), tslot.size() * 4, hipMemcpyHostToDevice, h->stream));
     PQP_HIP(hipStreamSynchronize(h->stream));      // the vectors go out of scope
-    h->b_struct_type = type; h->b_struct_n = n;
+    h->sm.struct_type = type; h->sm.struct_n = n;
     return PQP_OK;
 }
 
@@ -87,9 +87,9 @@ int sm_solve(pqp_handle* h, int type, int batch, int n, int32_t* status, int32_t
     pqp::BandedQpArgs a;
     std::memset(&a, 0, sizeof(a));
     a.batch = batch; a.nv = sh.nv; a.nc = sh.nc; a.bw = sh.bw; a.pbw = sh.pbw;
-    a.pband = h->b_pband.as<double>(); a.q = h->b_q.as<double>(); a.acol = h->b_acol.as<int>(); a.aval = h->b_aval.as<double>();
-    a.trow = h->b_trow.as<int>(); a.tslot = h->b_tslot.as<int>(); a.lo = h->b_lo.as<double>(); a.up = h->b_up.as<double>();
-    a.x = h->b_x.as<double>(); a.y = h->b_y.as<double>(); a.status = status; a.iters = iters; a.info = info; a.prm = h->prm;
+    a.pband = h->sm.pband.as<double>(); a.q = h->sm.q.as<double>(); a.acol = h->sm.acol.as<int>(); a.aval = h->sm.aval.as<double>();
+    a.trow = h->sm.trow.as<int>(); a.tslot = h->sm.tslot.as<int>(); a.lo = h->sm.lo.as<double>(); a.up = h->sm.up.as<double>();
+    a.x = h->sm.x.as<double>(); a.y = h->sm.y.as<double>(); a.status = status; a.iters = iters; a.info = info; a.prm = h->prm;
     pqp::resolve_banded_params(&a.prm);
     // the row data of A, the index lists and q staged in LDS once per QP (256-lane kernels: always - two of them still share a CU's LDS up
     // to 80 KB each; 512-lane kernels: when it fits; 1024-lane kernels: never)
@@ -128,9 +128,9 @@ bool sm_generic_fits(int type, int n) {
 int sm_alloc(pqp_handle* h, int type, int batch, int n) {
     const SmShape sh = sm_shape(type, n);
     int rc;
-    if ((rc = h->b_pband.ensure((size_t)batch * (sh.pbw + 1) * sh.nv * 8)) || (rc = h->b_q.ensure((size_t)batch * sh.nv * 8)) ||
-        (rc = h->b_aval.ensure((size_t)batch * sh.nc * pqp::kRMax * 8)) || (rc = h->b_lo.ensure((size_t)batch * sh.nc * 8)) ||
-        (rc = h->b_up.ensure((size_t)batch * sh.nc * 8)) || (rc = h->b_x.ensure((size_t)batch * sh.nv * 8)) || (rc = h->b_y.ensure((size_t)batch * sh.nc * 8)))
+    if ((rc = h->sm.pband.ensure((size_t)batch * (sh.pbw + 1) * sh.nv * 8)) || (rc = h->sm.q.ensure((size_t)batch * sh.nv * 8)) ||
+        (rc = h->sm.aval.ensure((size_t)batch * sh.nc * pqp::kRMax * 8)) || (rc = h->sm.lo.ensure((size_t)batch * sh.nc * 8)) ||
+        (rc = h->sm.up.ensure((size_t)batch * sh.nc * 8)) || (rc = h->sm.x.ensure((size_t)batch * sh.nv * 8)) || (rc = h->sm.y.ensure((size_t)batch * sh.nc * 8)))
         return rc;
     return sm_upload_structure(h, type, n);
 }
@@ -153,14 +153,14 @@ static int smooth_tension2_impl(pqp_handle* h, int batch, int n, const int32_t* 
         // exact optima asked for (or more points than the generic core holds: 4 n variables on at most 1024 lanes, tension_smoother_2.cpp:20-72 has
         // no cap): the QP has equality rows only - its optimum by one Riccati sweep per scenario (tension2_exact_kernel)
         if (!status) return fail(PQP_ERR_INVALID, "pqp_smooth_tension2: status is null");
-        if ((rc = h->b_pband.ensure((size_t)batch * n * 5 * 8)) || (rc = h->b_aval.ensure((size_t)batch * n * 6 * 8))) return rc;
+        if ((rc = h->sm.pband.ensure((size_t)batch * n * 5 * 8)) || (rc = h->sm.aval.ensure((size_t)batch * n * 6 * 8))) return rc;
         hipLaunchKernelGGL(pqp::tension2_stage_kernel, dim3((batch * n + 255) / 256), dim3(256), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, k_list,
-                           s_list, h->b_aval.as<double>());
+                           s_list, h->sm.aval.as<double>());
         PQP_HIP(hipGetLastError());
         return h->launch_timed([&]() -> int {
             hipLaunchKernelGGL(pqp::tension2_exact_kernel, dim3((batch + 63) / 64), dim3(64), 0, h->stream, batch, n, n_of, x_list, y_list,
-                               h->prm.tension2_deviation_weight, h->prm.tension2_curvature_weight, h->prm.tension2_curvature_rate_weight, h->b_aval.as<double>(),
-                               h->b_pband.as<double>(), out_x, out_y, out_s, status, iters, info);
+                               h->prm.tension2_deviation_weight, h->prm.tension2_curvature_weight, h->prm.tension2_curvature_rate_weight, h->sm.aval.as<double>(),
+                               h->sm.pband.as<double>(), out_x, out_y, out_s, status, iters, info);
             PQP_HIP(hipGetLastError());
             return PQP_OK;
         });
@@ -169,10 +169,10 @@ static int smooth_tension2_impl(pqp_handle* h, int batch, int n, const int32_t* 
     const int total = batch * n;
     hipLaunchKernelGGL(pqp::tension2_assemble_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list,
                        k_list, s_list, h->prm.tension2_deviation_weight, h->prm.tension2_curvature_weight, h->prm.tension2_curvature_rate_weight,
-                       h->b_pband.as<double>(), h->b_q.as<double>(), h->b_aval.as<double>(), h->b_lo.as<double>(), h->b_up.as<double>());
+                       h->sm.pband.as<double>(), h->sm.q.as<double>(), h->sm.aval.as<double>(), h->sm.lo.as<double>(), h->sm.up.as<double>());
     PQP_HIP(hipGetLastError());
     if ((rc = sm_solve(h, SM_TENSION2, batch, n, status, iters, info))) return rc;
-    hipLaunchKernelGGL(pqp::tension_finish_kernel, dim3(batch), dim3(64), (size_t)n * 8, h->stream, batch, n, n_of, 4 * n - 1, 4, h->b_x.as<double>(), out_x, out_y, out_s);
+    hipLaunchKernelGGL(pqp::tension_finish_kernel, dim3(batch), dim3(64), (size_t)n * 8, h->stream, batch, n, n_of, 4 * n - 1, 4, h->sm.x.as<double>(), out_x, out_y, out_s);
     PQP_HIP(hipGetLastError());
     return PQP_OK;
 }
@@ -225,10 +225,10 @@ static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n
     const int total = batch * n;
     hipLaunchKernelGGL(pqp::tension_assemble_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, n, n_of, x_list, y_list, angle_list, clearance,
                        h->prm.cartesian_curvature_weight, h->prm.cartesian_curvature_rate_weight, h->prm.cartesian_deviation_weight,
-                       h->b_pband.as<double>(), h->b_q.as<double>(), h->b_aval.as<double>(), h->b_lo.as<double>(), h->b_up.as<double>());
+                       h->sm.pband.as<double>(), h->sm.q.as<double>(), h->sm.aval.as<double>(), h->sm.lo.as<double>(), h->sm.up.as<double>());
     PQP_HIP(hipGetLastError());
     if ((rc = sm_solve(h, SM_TENSION, batch, n, status, iters, info))) return rc;
-    hipLaunchKernelGGL(pqp::tension_finish_kernel, dim3(batch), dim3(64), (size_t)n * 8, h->stream, batch, n, n_of, 3 * n, 3, h->b_x.as<double>(), out_x, out_y, out_s);
+    hipLaunchKernelGGL(pqp::tension_finish_kernel, dim3(batch), dim3(64), (size_t)n * 8, h->stream, batch, n, n_of, 3 * n, 3, h->sm.x.as<double>(), out_x, out_y, out_s);
     PQP_HIP(hipGetLastError());
     return PQP_OK;
 }
@@ -273,10 +273,10 @@ static int post_smooth_impl(pqp_handle* h, int batch, int m, const int32_t* m_of
     if ((rc = sm_alloc(h, SM_POST, batch, m))) return rc;
     const int total = batch * m;
     hipLaunchKernelGGL(pqp::post_assemble_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l,
-                       h->b_pband.as<double>(), h->b_q.as<double>(), h->b_aval.as<double>(), h->b_lo.as<double>(), h->b_up.as<double>());
+                       h->sm.pband.as<double>(), h->sm.q.as<double>(), h->sm.aval.as<double>(), h->sm.lo.as<double>(), h->sm.up.as<double>());
     PQP_HIP(hipGetLastError());
     if ((rc = sm_solve(h, SM_POST, batch, m, status, iters, info))) return rc;
-    hipLaunchKernelGGL(pqp::post_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, m, h->b_x.as<double>(), out_l);
+    hipLaunchKernelGGL(pqp::post_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, m, h->sm.x.as<double>(), out_l);
     PQP_HIP(hipGetLastError());
     return PQP_OK;
 }

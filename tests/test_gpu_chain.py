@@ -419,3 +419,68 @@ def test_chain_graph_is_not_replayed_after_the_smoother_handle_reallocates(hip_l
     for a, b_ in zip(want, got):
         np.testing.assert_array_equal(a, b_)
     h.close(); hs.close()
+
+
+def test_chain_graph_is_never_replayed_after_an_option_changed(hip_lib):
+    """Every option of both handles is part of the chain's graph key (csrc/pqp_internal.hpp: Options goes in as bytes).  Replay, then for each
+    option in turn: set it to another value, call once - the call must be launched plainly (it records timing events: pqp_last_kernel_ms succeeds;
+    a capture or a replay records none) and give, bit for bit below each scenario's n_out, what a fresh pair with the same options and the graph
+    option off gives - and set it back.  The fresh pair is driven through the same calls and option changes (a replay is bit-identical to plain
+    launches, above), so what PQP_OPT_CARRY_CYCLES carries from the earlier calls is the same on both sides.
+    (Not seen here: that PQP_OPT_STREAM_STAGED is in the key - both workspace layouts give the same bits and a capture is as silent as a replay.)"""
+    import torch
+    B = 4
+    sc = _scenarios(B, seed=7)
+    dev = torch.device("cuda", 0)
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    p = lambda x: capi.C.c_void_p(x.data_ptr())
+    d_pts, d_np, d_st, d_tg, d_map = t(sc["pts"], np.float64), t(sc["n_pts"], np.int32), t(sc["start"], np.float64), t(sc["target"], np.float64), t(sc["map_of"], np.int32)
+    d_dist = t(np.transpose(sc["dist"], (0, 2, 1)), np.float32)
+    # (handle, option, another value than its default, its default)
+    changes = [("path", capi.OPT_STORE_WARM, 0, 1), ("path", capi.OPT_ORDER_BY_COST, 1, 0), ("path", capi.OPT_RESERVE_CUS, 8, 0), ("path", capi.OPT_STREAM_BATCH, 1, -1),
+               ("path", capi.OPT_STREAM_STAGED, 1, -1), ("path", capi.OPT_CARRY_CYCLES, 1, 0), ("path", capi.OPT_LONG_LINES, 2, 0),
+               ("smoother", capi.OPT_CARRY_CYCLES, 1, 0), ("smoother", capi.OPT_LONG_LINES, 2, 0)]
+
+    def session(graph, warm_up):
+        """warm_up None: call until the chain replays; else: that many calls.  Then one call per changed option: (results, launched plainly)."""
+        h = capi.Handle(capi.production_params(), device=0, max_batch=B, max_n=128)
+        hs = capi.Handle(_smoother_params(), device=0, max_batch=B, max_n=128)
+        h.set_option(capi.OPT_CHAIN_GRAPH, graph); hs.set_option(capi.OPT_CHAIN_GRAPH, graph)
+        cfg = h.chain_config(raw_max=64, sample_max=48, layer_max=32, n_max=128)
+        out = torch.zeros((B, cfg.n_max, 7), dtype=torch.float64, device=dev)
+        ints = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4)]          # n_out, status, stage, iters
+        ms = capi.C.c_float()
+
+        def run():
+            h._check(h.lib.pqp_optimize_path_device(h._h, hs._h, capi.C.byref(cfg), B, sc["pts"].shape[1], p(d_pts), p(d_np), p(d_st), p(d_tg), p(d_dist), p(d_map),
+                                                    capi.C.byref(sc["geom"]), None, p(out), *(p(x) for x in ints)))
+            h.sync(); hs.sync()
+            return dict(out=out.cpu().numpy().copy(), n_out=ints[0].cpu().numpy().copy(), status=ints[1].cpu().numpy().copy(), stage=ints[2].cpu().numpy().copy())
+
+        calls, in_a_row = 0, 0
+        while (calls < 12 and in_a_row < 3) if warm_up is None else calls < warm_up:
+            run()
+            calls += 1
+            # (three calls in a row without timing events: at most two of them are captures, one per parity of the path handle's solve count)
+            in_a_row = in_a_row + 1 if h.lib.pqp_last_kernel_ms(h._h, capi.C.byref(ms)) != 0 else 0
+        if warm_up is None:
+            assert in_a_row == 3, "the chain never replayed"
+        got = []
+        for which, option, value, default in changes:
+            x = h if which == "path" else hs
+            x.set_option(option, value)
+            r = run()
+            got.append((r, h.lib.pqp_last_kernel_ms(h._h, capi.C.byref(ms)) == 0))
+            x.set_option(option, default)
+        h.close(); hs.close()
+        return calls, got
+
+    calls, with_graph = session(1, None)
+    _, plain = session(0, calls)
+    assert (plain[0][0]["stage"] == 0).sum() >= B // 2          # most scenarios give a path
+    for (which, option, value, _), (g, launched_plainly), (w, _) in zip(changes, with_graph, plain):
+        assert launched_plainly, (which, option, value)
+        for k in ("n_out", "status", "stage"):
+            np.testing.assert_array_equal(g[k], w[k], err_msg=str((which, option, k)))
+        for b in range(B):
+            np.testing.assert_array_equal(g["out"][b, :w["n_out"][b]], w["out"][b, :w["n_out"][b]], err_msg=str((which, option, b)))
