@@ -402,10 +402,10 @@ int pqp_smooth_tension2_device(pqp_handle* h, int batch, int n, const double* x_
                                int32_t* status, int32_t* iters, double* info);
 /* TensionSmoother::osqpSmooth    src/reference_path_smoother/tension_smoother.cpp:49-100; clearance = Map::getObstacleDistance
  * at each input point (the distance-map lookup itself, tension_smoother.cpp:168, stays on the caller's side; pqp_clearance_device does it).
- * n >= 4 points, no upper bound (as the reference: one point per metre of line).  Up to ~166 points a handle in the reference's ADMM setting
+ * n >= 4 points, no upper bound (as the reference: one point per metre of line).  Up to 203 points a handle in the reference's ADMM setting
  * (polish == 0) runs OSQP's iteration on the 9 x 9-block core; beyond that core's LDS capacity - and for polish == 1 at any size - the QP is
  * solved exactly (iters = 0), which meets OSQP's termination test at any eps.  The same rule holds for the other two smoothers: where the
- * generic core cannot hold the QP (TensionSmoother2: more than 256 points; postSmooth: more than ~340 layers) every handle gets the exact kernel. */
+ * generic core cannot hold the QP (TensionSmoother2 and TensionSmoother: more than 203 points; postSmooth: more than 251 layers) every handle gets the exact kernel. */
 int pqp_smooth_tension(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list,
                        const double* clearance, double* out_x, double* out_y, double* out_s, int32_t* status, int32_t* iters);
 int pqp_smooth_tension_device(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list,

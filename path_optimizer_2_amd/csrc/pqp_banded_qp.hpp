@@ -40,6 +40,10 @@ struct BandedQpArgs {
     int32_t* iters;          // [batch]
     double* info;            // [batch][PQP_INFO_STRIDE] or nullptr
     pqp_params prm;
+    // a ragged launch (the smoothers' _var entry points): n_of [batch] = points of each QP in the pattern of n_pts points, per_pt variables each;
+    // counts below n_min run as n_min (the assemble kernels' clamp).  The variables past a QP's own are its decoupled dummies.  nullptr: none.
+    const int32_t* n_of;
+    int n_pts, n_min, per_pt;
 };
 // Ctx::kStage: the row data of A, the index lists and q are copied to LDS once per QP (BqLayout::total(true) doubles of LDS); otherwise
 // they are read from global memory (L2) at every use - two dependent global round trips per ADMM iteration.
@@ -109,6 +113,12 @@ struct BandedQp {
     PQP_HD const double* aval() const { return A.aval + (size_t)qp * nc * kRMax; }
     PQP_HD const double* pband() const { return A.pband + (size_t)qp * (A.pbw + 1) * nv; }
     PQP_HD double pdiag(int j) const { return pband()[j]; }
+    // the QP's own variables: all of them, or in a ragged launch those of its own points (the leading ones; dummies follow)
+    PQP_HD int own_nv() const {
+        if (!A.n_of) return nv;
+        const int c = A.n_of[qp];
+        return nv - A.per_pt * (A.n_pts - (c < A.n_pts ? (c < A.n_min ? A.n_min : c) : A.n_pts));
+    }
 
     template <class F> PQP_HD void rows(F f) { ctx.phase([&](int t, Lane&) { for (int r = t; r < nc; r += T) f(r); }); }
     template <class F> PQP_HD void cols(F f) { ctx.phase([&](int t, Lane&) { for (int j = t; j < nv; j += T) f(j); }); }
@@ -213,12 +223,15 @@ struct BandedQp {
             });
             cols([&](int j) { D[j] = dn[j]; });
             rows([&](int r) { E[r] = en[r]; });
-            // cost scaling: c <- c / max(mean_j ||P_j||_inf, ||q||_inf)   (both after the D update, limited)
+            // cost scaling: c <- c / max(mean_j ||P_j||_inf, ||q||_inf)   (both after the D update, limited).  The mean runs over the QP's own
+            // columns: the unit-cost dummies of a ragged launch are decoupled from everything else but this mean, and with them in it a short
+            // line in a long pattern was scaled - and therefore iterated - differently from the same line launched at its own size
+            const int nvo = own_nv();
             double acc0[1], acc1[1];
             ctx.template reduce_sum<1>(acc0, [&](int t, double (&v)[1]) {
                 const double* pb = pband();
                 double s = 0.0;
-                for (int j = t; j < nv; j += T) {
+                for (int j = t; j < nvo; j += T) {
                     double m = fabs(pb[j]) * D[j] * D[j];
                     for (int d = 1; d <= A.pbw; ++d) {
                         if (j + d < nv) m = fmax(m, fabs(pb[(size_t)d * nv + j]) * D[j] * D[j + d]);
@@ -235,7 +248,7 @@ struct BandedQp {
             });
             double qn = acc1[0];
             qn = qn < kMinScaling ? 1.0 : fmin(qn, kMaxScaling);
-            double ct = fmax(acc0[0] / (double)nv, qn);
+            double ct = fmax(acc0[0] / (double)nvo, qn);
             ct = limit_scaling(ct);
             cscale = cscale / ct;
         }

@@ -81,8 +81,9 @@ int sm_upload_structure(pqp_handle* h, int type, int n) {
     return PQP_OK;
 }
 
-// assemble (already enqueued by the caller into b_pband ...) -> banded ADMM solve -> finish.  All device pointers.
-int sm_solve(pqp_handle* h, int type, int batch, int n, int32_t* status, int32_t* iters, double* info) {
+// assemble (already enqueued by the caller into b_pband ...) -> banded ADMM solve -> finish.  All device pointers.  n_of: the counts the assemble
+// kernel padded by (or nullptr)
+int sm_solve(pqp_handle* h, int type, int batch, int n, const int32_t* n_of, int32_t* status, int32_t* iters, double* info) {
     const SmShape sh = sm_shape(type, n);
     pqp::BandedQpArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -90,6 +91,7 @@ int sm_solve(pqp_handle* h, int type, int batch, int n, int32_t* status, int32_t
     a.pband = h->sm.pband.as<double>(); a.q = h->sm.q.as<double>(); a.acol = h->sm.acol.as<int>(); a.aval = h->sm.aval.as<double>();
     a.trow = h->sm.trow.as<int>(); a.tslot = h->sm.tslot.as<int>(); a.lo = h->sm.lo.as<double>(); a.up = h->sm.up.as<double>();
     a.x = h->sm.x.as<double>(); a.y = h->sm.y.as<double>(); a.status = status; a.iters = iters; a.info = info; a.prm = h->prm;
+    a.n_of = n_of; a.n_pts = n; a.n_min = type == SM_TENSION2 ? 2 : (type == SM_TENSION ? 4 : 1); a.per_pt = sh.stride;      // (n_min: the assemble kernels' clamps)
     pqp::resolve_banded_params(&a.prm);
     // the row data of A, the index lists and q staged in LDS once per QP (256-lane kernels: always - two of them still share a CU's LDS up
     // to 80 KB each; 512-lane kernels: when it fits; 1024-lane kernels: never)
@@ -150,7 +152,7 @@ static int smooth_tension2_impl(pqp_handle* h, int batch, int n, const int32_t* 
     PQP_HIP(hipSetDevice(h->device));
     int rc;
     if (h->prm.polish != 0 || !sm_generic_fits(SM_TENSION2, n)) {
-        // exact optima asked for (or more points than the generic core holds: 4 n variables on at most 1024 lanes, tension_smoother_2.cpp:20-72 has
+        // exact optima asked for (or more points than the generic core holds: 203, where its LDS ends - sm_generic_fits; tension_smoother_2.cpp:20-72 has
         // no cap): the QP has equality rows only - its optimum by one Riccati sweep per scenario (tension2_exact_kernel)
         if (!status) return fail(PQP_ERR_INVALID, "pqp_smooth_tension2: status is null");
         if ((rc = h->sm.pband.ensure((size_t)batch * n * 5 * 8)) || (rc = h->sm.aval.ensure((size_t)batch * n * 6 * 8))) return rc;
@@ -171,7 +173,7 @@ static int smooth_tension2_impl(pqp_handle* h, int batch, int n, const int32_t* 
                        k_list, s_list, h->prm.tension2_deviation_weight, h->prm.tension2_curvature_weight, h->prm.tension2_curvature_rate_weight,
                        h->sm.pband.as<double>(), h->sm.q.as<double>(), h->sm.aval.as<double>(), h->sm.lo.as<double>(), h->sm.up.as<double>());
     PQP_HIP(hipGetLastError());
-    if ((rc = sm_solve(h, SM_TENSION2, batch, n, status, iters, info))) return rc;
+    if ((rc = sm_solve(h, SM_TENSION2, batch, n, n_of, status, iters, info))) return rc;
     hipLaunchKernelGGL(pqp::tension_finish_kernel, dim3(batch), dim3(64), (size_t)n * 8, h->stream, batch, n, n_of, 4 * n - 1, 4, h->sm.x.as<double>(), out_x, out_y, out_s);
     PQP_HIP(hipGetLastError());
     return PQP_OK;
@@ -203,7 +205,7 @@ static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n
     PQP_HIP(hipSetDevice(h->device));
     int rc;
     // The generic block-cyclic-reduction core keeps a QP's vectors, factor rows and row data in one compute unit's LDS: in TensionSmoother's
-    // 9 x 9 blocks that ends near 166 points.  The reference has no such limit (tension_smoother.cpp:49-100; segmentRawReference gives a
+    // 9 x 9 blocks that ends at 203 points (sm_generic_fits; S1 also at 203, postSmooth at 251 layers).  The reference has no such limit (tension_smoother.cpp:49-100; segmentRawReference gives a
     // point per metre of line).  Beyond it, also a handle in the reference's ADMM setting gets the exact kernel's optimum: a point with
     // zero residuals meets OSQP's termination test at any eps, so it IS a valid result of that setting (iters = 0; OSQP itself would
     // stop at a less accurate one).
@@ -227,7 +229,7 @@ static int smooth_tension_impl(pqp_handle* h, int batch, int n, const int32_t* n
                        h->prm.cartesian_curvature_weight, h->prm.cartesian_curvature_rate_weight, h->prm.cartesian_deviation_weight,
                        h->sm.pband.as<double>(), h->sm.q.as<double>(), h->sm.aval.as<double>(), h->sm.lo.as<double>(), h->sm.up.as<double>());
     PQP_HIP(hipGetLastError());
-    if ((rc = sm_solve(h, SM_TENSION, batch, n, status, iters, info))) return rc;
+    if ((rc = sm_solve(h, SM_TENSION, batch, n, n_of, status, iters, info))) return rc;
     hipLaunchKernelGGL(pqp::tension_finish_kernel, dim3(batch), dim3(64), (size_t)n * 8, h->stream, batch, n, n_of, 3 * n, 3, h->sm.x.as<double>(), out_x, out_y, out_s);
     PQP_HIP(hipGetLastError());
     return PQP_OK;
@@ -275,7 +277,7 @@ static int post_smooth_impl(pqp_handle* h, int batch, int m, const int32_t* m_of
     hipLaunchKernelGGL(pqp::post_assemble_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, m, m_of, layers_s, lb, ub, vehicle_l,
                        h->sm.pband.as<double>(), h->sm.q.as<double>(), h->sm.aval.as<double>(), h->sm.lo.as<double>(), h->sm.up.as<double>());
     PQP_HIP(hipGetLastError());
-    if ((rc = sm_solve(h, SM_POST, batch, m, status, iters, info))) return rc;
+    if ((rc = sm_solve(h, SM_POST, batch, m, m_of, status, iters, info))) return rc;
     hipLaunchKernelGGL(pqp::post_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, h->stream, batch, m, h->sm.x.as<double>(), out_l);
     PQP_HIP(hipGetLastError());
     return PQP_OK;

@@ -56,11 +56,24 @@ def to_banded(P, q, A, lo, up, pos):
     return dict(nv=nv, nc=nc, bw=bw, pbw=pbw, pband=pband, q=qp, acol=acol, aval=aval, trow=trow, tslot=tslot, lo=lo.copy(), up=up.copy())
 
 
-def emu_solve(prm, b):
+def emu_solve(prm, b, stage=True):
+    """One QP (or b["batch"] QPs of one sparsity: pband, q, aval, lo, up with a leading batch axis) on the host emulation of the core, in its
+    staged form (row data, index lists and q in the shared array: the device's 256-lane and staged 512-lane kernels) or its non-staged one
+    (the 512-lane kernel past the LDS, the 1024-lane kernel)."""
     lib = E.load()
     vp = lambda a: np.ascontiguousarray(a).ctypes.data_as(C.c_void_p)
-    x = np.zeros(b["nv"]); y = np.zeros(b["nc"]); st = np.zeros(1, dtype=np.int32); it = np.zeros(1, dtype=np.int32); info = np.zeros(8)
+    batch = b.get("batch")
+    nb = batch or 1
+    x = np.zeros((nb, b["nv"])); y = np.zeros((nb, b["nc"])); st = np.zeros(nb, dtype=np.int32); it = np.zeros(nb, dtype=np.int32); info = np.zeros((nb, 8))
     arrs = {k: np.ascontiguousarray(b[k]) for k in ("pband", "q", "acol", "aval", "trow", "tslot", "lo", "up")}
-    lib.pqp_emu_banded_solve(C.byref(prm), 1, b["nv"], b["nc"], b["bw"], b["pbw"], vp(arrs["pband"]), vp(arrs["q"]), vp(arrs["acol"]),
-                             vp(arrs["aval"]), vp(arrs["trow"]), vp(arrs["tslot"]), vp(arrs["lo"]), vp(arrs["up"]), vp(x), vp(y), vp(st), vp(it), vp(info))
-    return dict(x=x, y=y, status=int(st[0]), iters=int(it[0]), info=info)
+    counts = None if b.get("n_of") is None else np.ascontiguousarray(b["n_of"], dtype=np.int32)      # a ragged launch: (n_of, n_pts, n_min, per_pt)
+    lib.pqp_emu_banded_set_counts(None if counts is None else vp(counts), *(b.get("ragged") or (0, 0, 0)))
+    assert arrs["acol"].dtype == np.int32 and arrs["trow"].dtype == np.int32 and arrs["tslot"].dtype == np.int32
+    rc = lib.pqp_emu_banded_solve_form(C.byref(prm), nb, b["nv"], b["nc"], b["bw"], b["pbw"], vp(arrs["pband"]), vp(arrs["q"]), vp(arrs["acol"]),
+                                       vp(arrs["aval"]), vp(arrs["trow"]), vp(arrs["tslot"]), vp(arrs["lo"]), vp(arrs["up"]), vp(x), vp(y), vp(st), vp(it), vp(info),
+                                       1 if stage else 0)
+    lib.pqp_emu_banded_set_counts(None, 0, 0, 0)
+    assert rc == 0
+    if batch:
+        return dict(x=x, y=y, status=st, iters=it, info=info)
+    return dict(x=x[0], y=y[0], status=int(st[0]), iters=int(it[0]), info=info[0])

@@ -211,9 +211,11 @@ extern "C" int pqp_emu_probe(const pqp_params* prm, int n, const double* ref, co
 
 // ---- the generic banded-QP core (pqp_banded_qp.hpp) on the host -----------------------------------------------------
 namespace {
-template <int B>
+// STAGE: Ctx::kStage - true as the device's 256- and staged 512-lane kernels (row data, index lists and q in the shared array, BqLayout::total(true)
+// doubles), false as its non-staged 512- and 1024-lane kernels (read from the arguments at every use; the shared array ends at total(false))
+template <int B, bool STAGE>
 struct BqHostCtx {
-    static constexpr bool kStage = true;      // as the device's 256- and 512-lane kernels: row data, index lists and q in the shared array
+    static constexpr bool kStage = STAGE;
     int T_;
     std::vector<double> shm;
     std::vector<pqp::BqLane<B>> lanes;
@@ -231,32 +233,51 @@ struct BqHostCtx {
     }
 };
 
-template <int B>
+template <int B, bool STAGE>
 void bq_run(const pqp::BandedQpArgs& a) {
     const pqp::BqLayout L{a.nv, a.nc, a.bw};
     const int T = 64 * ((L.nbb() + 63) / 64);
     for (int qp = 0; qp < a.batch; ++qp) {
-        BqHostCtx<B> ctx(T, L.total(true));
-        pqp::BandedQp<BqHostCtx<B>, B> s(ctx, a, qp);
+        BqHostCtx<B, STAGE> ctx(T, L.total(STAGE));
+        pqp::BandedQp<BqHostCtx<B, STAGE>, B> s(ctx, a, qp);
         s.run();
     }
 }
 }  // namespace
 
-extern "C" int pqp_emu_banded_solve(const pqp_params* prm, int batch, int nv, int nc, int bw, int pbw, const double* pband, const double* q,
-                                    const int* acol, const double* aval, const int* trow, const int* tslot, const double* lo,
-                                    const double* up, double* x, double* y, int32_t* status, int32_t* iters, double* info) {
+// the next pqp_emu_banded_solve_form call is a ragged launch: BandedQpArgs::n_of / n_pts / n_min / per_pt (nullptr: not ragged)
+static const int32_t* g_bq_n_of = nullptr;
+static int g_bq_n_pts = 0, g_bq_n_min = 0, g_bq_per_pt = 0;
+extern "C" void pqp_emu_banded_set_counts(const int32_t* n_of, int n_pts, int n_min, int per_pt) { g_bq_n_of = n_of; g_bq_n_pts = n_pts; g_bq_n_min = n_min; g_bq_per_pt = per_pt; }
+
+// stage != 0: the staged form, 0: the non-staged one (the device picks by size: sm_solve)
+extern "C" int pqp_emu_banded_solve_form(const pqp_params* prm, int batch, int nv, int nc, int bw, int pbw, const double* pband, const double* q,
+                                         const int* acol, const double* aval, const int* trow, const int* tslot, const double* lo,
+                                         const double* up, double* x, double* y, int32_t* status, int32_t* iters, double* info, int stage) {
     pqp::BandedQpArgs a;
     std::memset(&a, 0, sizeof(a));
     a.batch = batch; a.nv = nv; a.nc = nc; a.bw = bw; a.pbw = pbw;
     a.pband = pband; a.q = q; a.acol = acol; a.aval = aval; a.trow = trow; a.tslot = tslot; a.lo = lo; a.up = up;
     a.x = x; a.y = y; a.status = status; a.iters = iters; a.info = info; a.prm = *prm;
+    a.n_of = g_bq_n_of; a.n_pts = g_bq_n_pts; a.n_min = g_bq_n_min; a.per_pt = g_bq_per_pt;
     pqp::resolve_banded_params(&a.prm);
     switch (bw) {
-        case 3: bq_run<3>(a); break;
-        case 4: bq_run<4>(a); break;
-        case 9: bq_run<9>(a); break;
+        case 3: stage ? bq_run<3, true>(a) : bq_run<3, false>(a); break;
+        case 4: stage ? bq_run<4, true>(a) : bq_run<4, false>(a); break;
+        case 9: stage ? bq_run<9, true>(a) : bq_run<9, false>(a); break;
         default: return -1;
     }
     return 0;
+}
+
+extern "C" int pqp_emu_banded_solve(const pqp_params* prm, int batch, int nv, int nc, int bw, int pbw, const double* pband, const double* q,
+                                    const int* acol, const double* aval, const int* trow, const int* tslot, const double* lo,
+                                    const double* up, double* x, double* y, int32_t* status, int32_t* iters, double* info) {
+    return pqp_emu_banded_solve_form(prm, batch, nv, nc, bw, pbw, pband, q, acol, aval, trow, tslot, lo, up, x, y, status, iters, info, 1);
+}
+
+// the header's own layout of a QP of nv variables, nc rows and block size bw: out = nbb, total(false), total(true)   (tests/banded_cases.py restates it)
+extern "C" void pqp_emu_banded_layout(int nv, int nc, int bw, int32_t* out) {
+    const pqp::BqLayout L{nv, nc, bw};
+    out[0] = L.nbb(); out[1] = L.total(false); out[2] = L.total(true);
 }

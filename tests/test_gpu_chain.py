@@ -120,8 +120,8 @@ def test_configs0_the_demo_s_single_path(hip_lib):
 
 
 def test_capacities_beyond_the_register_kernels(hip_lib):
-    """pqp_chain_config has no upper bounds (the reference has none): 300 samples are more than TensionSmoother2's generic core holds (256),
-    400 layers more than postSmooth's (341), 600 waypoints more than the lane-per-waypoint kernel's (512 - the handle is created for them;
+    """pqp_chain_config has no upper bounds (the reference has none): 300 samples are more than TensionSmoother2's generic core holds (203),
+    400 layers more than postSmooth's (251), 600 waypoints more than the lane-per-waypoint kernel's (512 - the handle is created for them;
     a line this short still runs there).  Same paths as with the default capacities; a smoother handle in the reference's ADMM setting gets
     the exact kernels where the generic core does not fit instead of PQP_ERR_CAPACITY."""
     sc = _scenarios(3, n_maps=2, seed=33)

@@ -73,6 +73,19 @@ def test_banded_solve_kernel_registers(kernels, b, maxt, stage):
     assert r["ScratchSize"] <= 512, r         # spill slots of the setup / polish code (180-408 B today); a BqLane<9> in scratch would be 700 B
 
 
+# the other forms a size can select (tests/banded_cases.py RANGES): form -> ScratchSize in the build of the commit before this test (with it: 1316, 1240, 708, 888, 1880).  9 x 9 blocks on 512 lanes
+# (256 registers; the 256-lane form of B = 9 has 512) and every 1024-lane form (128 registers) spill lane state in the loop too; what they are held
+# to is not growing past today's value by more than the head-room the bound above has over its 408 B (a quarter).
+_SPILLING_FORMS = {(9, 512, 1): 1332, (9, 512, 0): 1288, (3, 1024, 0): 704, (4, 1024, 0): 896, (9, 1024, 0): 1908}
+
+
+@pytest.mark.parametrize("b,maxt,stage", sorted(_SPILLING_FORMS))
+def test_banded_solve_kernel_forms_that_spill_do_not_spill_more(kernels, b, maxt, stage):
+    r = _find(kernels, "banded_solve_kernel", f"ILi{b}ELi{maxt}ELb{stage}E")
+    assert r["ScratchSize"] <= _SPILLING_FORMS[(b, maxt, stage)] * 5 // 4, r
+    assert r["VGPRs"] <= (256 if maxt == 512 else 128)
+
+
 @pytest.mark.parametrize("name,tag", [("post_exact_kernel", "ILi1E"), ("post_exact_kernel", "ILi2E"), ("post_exact_kernel", "ILi4E"), ("post_exact_kernel", "ILi6E"),
                                       ("tension_exact_kernel", "ILi1E"), ("tension_exact_kernel", "ILi2E"), ("tension_exact_kernel", "ILi4E"), ("tension_exact_kernel", "ILi6E"),
                                       ("tension2_exact_kernel", ""), ("tension2_stage_kernel", "")])
