@@ -2,120 +2,84 @@
 
 Python is plumbing here (tests, bench, smoke); the product is the shared library.  There is no CPU
 fallback: if the library or a HIP device is missing, loading / pqp_create fails loudly.
+
+Nothing of the ABI is restated here: the Structure classes (pqp_grid_geometry -> PqpGridGeometry), the constants (PQP_OPT_STORE_WARM ->
+OPT_STORE_WARM), EXPORTS and every function's argtypes / restype are built from what pqp_header reads in include/pqp.h.
 """
 import ctypes as C
 import os
 
 import numpy as np
 
+from . import pqp_header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpqp_hip.so")
 
+HEADER = pqp_header.read()
+EXPORTS = list(HEADER.functions)
+globals().update({k[len("PQP_"):]: v for k, v in HEADER.constants.items()})      # OPT_*, KERNEL_*, FOOTPRINT_*, *_STRIDE, PROJ_*, SPEED_*, TRAJ_*, ...
 
-class PqpParams(C.Structure):
-    _fields_ = [
-        ("front_length", C.c_double), ("rear_length", C.c_double), ("wheel_base", C.c_double),
-        ("expected_safety_margin", C.c_double), ("precise_planning_length", C.c_double),
-        ("constraint_end_heading", C.c_int32), ("rough_constraints_far_away", C.c_int32),
-        ("weight_l", C.c_double), ("weight_kappa", C.c_double), ("weight_dkappa", C.c_double),
-        ("weight_slack", C.c_double), ("end_l_bound", C.c_double), ("end_psi_tol", C.c_double),
-        ("end_psi_max", C.c_double), ("min_clearance", C.c_double),
-        ("eps_abs", C.c_double), ("eps_rel", C.c_double), ("rho", C.c_double), ("sigma", C.c_double),
-        ("alpha", C.c_double), ("max_iter", C.c_int32), ("scaling", C.c_int32),
-        ("adaptive_rho", C.c_int32), ("adaptive_rho_interval", C.c_int32),
-        ("adaptive_rho_tolerance", C.c_double), ("check_termination", C.c_int32), ("polish", C.c_int32),
-        ("polish_refine_iter", C.c_int32), ("polish_every", C.c_int32), ("polish_warm_set", C.c_int32), ("polish_max_rounds", C.c_int32),
-        ("polish_reseed", C.c_int32), ("polish_diverge", C.c_int32), ("polish_delta", C.c_double), ("polish_tol", C.c_double),
-        ("polish_reseed_factor", C.c_double), ("eps_prim_inf", C.c_double), ("polish_patience", C.c_int32), ("prim_inf_after", C.c_int32),
-        ("polish_lazy", C.c_int32), ("polish_final_refine", C.c_int32),
-        ("tension2_deviation_weight", C.c_double), ("tension2_curvature_weight", C.c_double),
-        ("tension2_curvature_rate_weight", C.c_double), ("cartesian_curvature_weight", C.c_double),
-        ("cartesian_curvature_rate_weight", C.c_double), ("cartesian_deviation_weight", C.c_double),
-    ]
+_FIELD = {"double": C.c_double, "int32_t": C.c_int32}
+STRUCTS = {}                                                   # header name -> Structure class, in the header's order
+for _s in HEADER.structs.values():
+    STRUCTS[_s.name] = type(pqp_header.class_name(_s.name), (C.Structure,),
+                            {"_fields_": [(f, _FIELD.get(t) or STRUCTS[t]) for f, t in _s.fields], "__module__": __name__})
+globals().update({c.__name__: c for c in STRUCTS.values()})    # PqpParams, PqpSizes, PqpGridGeometry, ...
+
+_DTYPE = {"double": "float64", "float": "float32", "int32_t": "int32", "int": "int32", "uint8_t": "uint8"}      # pointee -> numpy / torch name
+_PASS = (C.c_void_p, C.Array, C._Pointer, type(C.byref(C.c_int())))
 
 
-class PqpGridGeometry(C.Structure):
-    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("resolution", C.c_double), ("length_x", C.c_double), ("length_y", C.c_double),
-                ("pos_x", C.c_double), ("pos_y", C.c_double)]
+class _DataPointer:
+    """argtype of one data-pointer parameter (const double* ref, int32_t* status, ...).  None, an int, a c_void_p and a ctypes array,
+    pointer or byref go through unchecked (device pointers look like that); a numpy array or an object with data_ptr() (a torch tensor)
+    must hold the pointee's element type, an array must be C-contiguous.  Anything else is a TypeError before the library is entered."""
+    __slots__ = ("where", "dtype")
+
+    def __init__(self, function, param):
+        self.where = f"{function}: {param.name} ({param.type})"
+        self.dtype = _DTYPE[pqp_header.pointee(param.type)[0]]
+
+    def from_param(self, v):
+        if v is None or isinstance(v, _PASS):
+            return v
+        if isinstance(v, np.ndarray):
+            if v.dtype.name != self.dtype or not v.flags["C_CONTIGUOUS"]:
+                raise TypeError(f"{self.where} wants a C-contiguous {self.dtype} array, not {v.dtype.name}"
+                                f"{'' if v.flags['C_CONTIGUOUS'] else ' (not contiguous)'}")
+            return C.c_void_p(v.ctypes.data)
+        if hasattr(v, "data_ptr"):
+            if str(v.dtype) != "torch." + self.dtype:
+                raise TypeError(f"{self.where} wants a {self.dtype} tensor, not {v.dtype}")
+            return C.c_void_p(v.data_ptr())
+        if isinstance(v, (int, np.integer)):
+            return C.c_void_p(int(v))
+        raise TypeError(f"{self.where} wants None, an address, a ctypes pointer, a numpy array or a tensor, not {type(v).__name__}")
 
 
-class PqpCorridorParams(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("front_length", "rear_length", "car_width", "safety_margin", "epsilon", "search_radius", "delta_s",
-                                         "smaller_ds", "search_range", "min_space", "projection_window")]
+_RESTYPE = {"int": C.c_int, "void": None, "const char*": C.c_char_p, "pqp_handle*": C.c_void_p}
 
 
-class PqpDpParams(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("lateral_range", "longitudinal_spacing", "lateral_spacing", "car_width")]
+def _argtype(function, param):
+    base, stars = pqp_header.pointee(param.type)
+    if stars == 0:
+        return {"int": C.c_int, "double": C.c_double}[base]
+    if stars == 2:
+        return C.POINTER(C.c_void_p)                           # pqp_handle**, pqp_multi**, void**, double* const*
+    if base in STRUCTS:
+        return C.POINTER(STRUCTS[base])
+    if base == "void" or base in HEADER.opaque:
+        return C.c_void_p
+    return _DataPointer(function, param)
 
-
-class PqpChainConfig(C.Structure):
-    _fields_ = [("raw_max", C.c_int32), ("sample_max", C.c_int32), ("layer_max", C.c_int32), ("n_max", C.c_int32), ("output_spacing", C.c_double),
-                ("dynamic_segmentation", C.c_int32), ("max_steering_angle", C.c_double), ("smoothed_length_margin", C.c_double),
-                ("corridor", PqpCorridorParams), ("dp", PqpDpParams), ("smoothing_method", C.c_int32), ("second_pass", C.c_int32)]
-
-
-class PqpCarGeometry(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("width", "rear_length", "front_length")]
-
-
-FOOTPRINT_CIRCLES, FOOTPRINT_BOUNDING_FIRST = 0, 1      # pqp_footprint_mode
-
-
-class PqpSelectParams(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("weight_kappa", "weight_dkappa", "weight_offset", "weight_length", "weight_clearance", "clearance_want")] + \
-               [("per_waypoint", C.c_int32), ("require_free", C.c_int32)]
-
-
-SCORE_STRIDE = 8      # PQP_SCORE_STRIDE
-PROJ_STRIDE = 8       # PQP_PROJ_STRIDE: s, l, t, d_heading, x_p, y_p, heading_p, k_p
-PROJECT_TILE_SAMPLES = 1024      # PQP_PROJECT_TILE_SAMPLES
-PROJ_AT_END, PROJ_BEFORE_START, PROJ_NOT_CONVERGED, PROJ_NOT_FINITE = 1, 2, 4, 8
-
-
-class PqpSpeedParams(C.Structure):
-    _fields_ = [(k, C.c_double) for k in ("v_max", "a_max", "d_max", "a_lat_max")]
-
-
-SPEED_STRIDE = 4      # PQP_SPEED_STRIDE: s, v, a, t
-SPEED_START_TOO_FAST, SPEED_STOPS_EARLY, SPEED_NEVER_ARRIVES, SPEED_EMPTY, SPEED_NOT_FINITE = 1, 2, 4, 8, 16
-
-
-class PqpSampleParams(C.Structure):
-    _fields_ = [("dt", C.c_double), ("hold_last", C.c_int32)]
-
-
-TRAJ_STRIDE = 8       # PQP_TRAJ_STRIDE: x, y, heading, k, s, v, a, t
-TRAJ_HORIZON_SHORT, TRAJ_STANDS, TRAJ_ENDS_MOVING, TRAJ_EMPTY, TRAJ_NOT_FINITE = 1, 2, 4, 8, 16
-
-
-class PqpSizes(C.Structure):
-    _fields_ = [(k, C.c_int32) for k in ("n", "state", "control", "precise", "slack", "vars", "cons", "nnz_a", "nnz_p")]
-
-
-EXPORTS = [
-    "pqp_default_params", "pqp_production_params", "pqp_last_error", "pqp_version", "pqp_create", "pqp_destroy", "pqp_set_params", "pqp_set_option",
-    "pqp_constrain_angle_device", "pqp_stream_wait", "pqp_mark", "pqp_wait_mark", "pqp_get_stream",
-    "pqp_chain_default_config", "pqp_optimize_path_device", "pqp_clearance_device", "pqp_smooth_tension2_var_device", "pqp_smooth_tension_var_device", "pqp_post_smooth_var_device", "pqp_spline_fit_var_device",
-    "pqp_shard_range", "pqp_multi_create", "pqp_multi_destroy", "pqp_multi_shards", "pqp_multi_handle", "pqp_multi_set_option", "pqp_multi_path_solve", "pqp_multi_gather_paths", "pqp_multi_gather_ranks", "pqp_sync", "pqp_path_sizes", "pqp_path_pattern", "pqp_path_assemble",
-    "pqp_path_assemble_device", "pqp_path_solve", "pqp_path_solve_device", "pqp_path_solve_var_device", "pqp_path_solve_var", "pqp_path_get_solution",
-    "pqp_last_kernel_ms", "pqp_last_path_kernel", "pqp_stream_batch_default", "pqp_kernel_ms_history", "pqp_smooth_tension2", "pqp_smooth_tension2_device", "pqp_smooth_tension", "pqp_smooth_tension_device",
-    "pqp_post_smooth", "pqp_post_smooth_device", "pqp_corridor_default_params", "pqp_corridor_bounds", "pqp_corridor_bounds_device",
-    "pqp_corridor_bounds_on_states", "pqp_corridor_bounds_on_states_device",
-    "pqp_reference_states", "pqp_reference_states_device", "pqp_spline_fit", "pqp_spline_fit_device", "pqp_dp_default_params",
-    "pqp_dp_corridor", "pqp_dp_corridor_device", "pqp_segment_raw_reference", "pqp_segment_raw_reference_device", "pqp_bspline_resample", "pqp_bspline_resample_device", "pqp_reference_length", "pqp_reference_length_device", "pqp_offsets_to_points", "pqp_offsets_to_points_device",
-    "pqp_distance_layer", "pqp_distance_layer_device",
-    "pqp_car_default_geometry", "pqp_car_circles", "pqp_footprint_check", "pqp_footprint_check_device",
-    "pqp_select_default_params", "pqp_select_paths", "pqp_select_paths_device",
-    "pqp_project_points", "pqp_project_points_device",
-    "pqp_speed_default_params", "pqp_speed_profile", "pqp_speed_profile_device",
-    "pqp_sample_default_params", "pqp_sample_trajectory", "pqp_sample_trajectory_device",
-]
 
 _lib = None
 
 
 def load_library(path=None, with_torch=None):
-    """dlopen libpqp_hip.so and declare the prototypes.  Raises OSError if it was not built.
+    """dlopen libpqp_hip.so and give every function of the header its argtypes and restype.  Raises OSError if the library was not built
+    or lacks a function the header declares.
     with_torch: import torch BEFORE the library is mapped (see below).  None = yes unless PQP_CAPI_TORCH=0: the safe default for a process that
     may use torch later; a torch-free user of the C ABI passes False (or sets PQP_CAPI_TORCH=0) and skips torch's multi-second import."""
     global _lib
@@ -137,176 +101,66 @@ def load_library(path=None, with_torch=None):
         except ImportError:
             pass
     lib = C.CDLL(path)
-    dp, ip, vp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_void_p
-    lib.pqp_default_params.argtypes = [C.POINTER(PqpParams)]
-    lib.pqp_default_params.restype = None
-    lib.pqp_production_params.argtypes = [C.POINTER(PqpParams)]
-    lib.pqp_production_params.restype = None
-    lib.pqp_last_error.restype = C.c_char_p
-    lib.pqp_version.restype = C.c_char_p
-    lib.pqp_create.argtypes = [C.POINTER(vp), C.POINTER(PqpParams), C.c_int, C.c_int, C.c_int]
-    lib.pqp_destroy.argtypes = [vp]
-    lib.pqp_set_params.argtypes = [vp, C.POINTER(PqpParams)]
-    lib.pqp_set_option.argtypes = [vp, C.c_int, C.c_int]
-    lib.pqp_stream_wait.argtypes = [vp, vp]
-    lib.pqp_mark.argtypes = [vp, C.c_int]
-    lib.pqp_constrain_angle_device.argtypes = [vp, C.c_int, vp, vp]
-    lib.pqp_wait_mark.argtypes = [vp, vp, C.c_int]
-    lib.pqp_get_stream.argtypes = [vp, C.POINTER(vp)]
-    lib.pqp_chain_default_config.argtypes = [C.POINTER(PqpChainConfig)]
-    lib.pqp_chain_default_config.restype = None
-    lib.pqp_optimize_path_device.argtypes = [vp, vp, C.POINTER(PqpChainConfig), C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(PqpGridGeometry),
-                                             vp, vp, vp, vp, vp, vp]
-    lib.pqp_clearance_device.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(PqpGridGeometry), vp]
-    lib.pqp_smooth_tension2_var_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
-    lib.pqp_smooth_tension_var_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 11
-    lib.pqp_post_smooth_var_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 9
-    lib.pqp_spline_fit_var_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 6
-    lib.pqp_shard_range.argtypes = [C.c_int, C.c_int, C.c_int, ip, ip]
-    lib.pqp_shard_range.restype = None
-    lib.pqp_multi_create.argtypes = [C.POINTER(vp), C.POINTER(PqpParams), C.c_int, ip, C.c_int, C.c_int]
-    lib.pqp_multi_destroy.argtypes = [vp]
-    lib.pqp_multi_shards.argtypes = [vp]
-    lib.pqp_multi_handle.argtypes = [vp, C.c_int]
-    lib.pqp_multi_handle.restype = vp
-    lib.pqp_multi_set_option.argtypes = [vp, C.c_int, C.c_int]
-    lib.pqp_multi_path_solve.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
-    lib.pqp_multi_gather_paths.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
-    lib.pqp_multi_gather_ranks.argtypes = [vp]
-    lib.pqp_sync.argtypes = [vp]
-    lib.pqp_path_sizes.argtypes = [C.POINTER(PqpParams), C.c_int, vp, C.POINTER(PqpSizes)]
-    lib.pqp_path_pattern.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
-    for name in ("pqp_path_assemble", "pqp_path_assemble_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    for name in ("pqp_path_solve", "pqp_path_solve_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.pqp_path_get_solution.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp]
-    lib.pqp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    lib.pqp_last_path_kernel.argtypes = [vp]
-    lib.pqp_kernel_ms_history.argtypes = [vp, vp, C.c_int]
-    lib.pqp_smooth_tension2.argtypes = [vp, C.c_int, C.c_int] + [vp] * 10
-    lib.pqp_smooth_tension2_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 11
-    lib.pqp_smooth_tension.argtypes = [vp, C.c_int, C.c_int] + [vp] * 9
-    lib.pqp_smooth_tension_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 10
-    lib.pqp_post_smooth.argtypes = [vp, C.c_int, C.c_int] + [vp] * 7
-    lib.pqp_post_smooth_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 8
-    lib.pqp_corridor_default_params.argtypes = [C.POINTER(PqpCorridorParams)]
-    lib.pqp_corridor_default_params.restype = None
-    lib.pqp_corridor_bounds_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(PqpGridGeometry),
-                                               C.POINTER(PqpCorridorParams), vp, vp]
-    lib.pqp_corridor_bounds.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry),
-                                        C.POINTER(PqpCorridorParams), vp, vp]
-    lib.pqp_corridor_bounds_on_states_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.POINTER(PqpGridGeometry),
-                                                         C.POINTER(PqpCorridorParams), vp, vp]
-    lib.pqp_corridor_bounds_on_states.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry),
-                                                  C.POINTER(PqpCorridorParams), vp, vp]
-    for name in ("pqp_reference_states", "pqp_reference_states_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_double, C.c_double, C.c_int, vp, vp, vp]
-    for name in ("pqp_offsets_to_points", "pqp_offsets_to_points_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    for name in ("pqp_reference_length", "pqp_reference_length_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    for name in ("pqp_bspline_resample", "pqp_bspline_resample_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
-    for name in ("pqp_segment_raw_reference", "pqp_segment_raw_reference_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp]
-    for name in ("pqp_spline_fit", "pqp_spline_fit_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
-    lib.pqp_dp_default_params.argtypes = [C.POINTER(PqpDpParams)]
-    lib.pqp_dp_default_params.restype = None
-    lib.pqp_dp_corridor_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpDpParams),
-                                           vp, vp, vp, vp, vp]
-    lib.pqp_dp_corridor.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpDpParams),
-                                    vp, vp, vp, vp, vp]
-    for name in ("pqp_path_solve_var_device", "pqp_path_solve_var"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
-    for name in ("pqp_distance_layer", "pqp_distance_layer_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.POINTER(PqpGridGeometry), vp, vp]
-    lib.pqp_car_default_geometry.argtypes = [C.POINTER(PqpCarGeometry)]
-    lib.pqp_car_default_geometry.restype = None
-    lib.pqp_car_circles.argtypes = [C.POINTER(PqpCarGeometry), vp]
-    lib.pqp_footprint_check_device.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpCarGeometry),
-                                               C.c_int, vp, vp, vp]
-    lib.pqp_footprint_check.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.POINTER(PqpGridGeometry), C.POINTER(PqpCarGeometry),
-                                        C.c_int, vp, vp, vp]
-    lib.pqp_select_default_params.argtypes = [C.POINTER(PqpSelectParams)]
-    lib.pqp_select_default_params.restype = None
-    for name in ("pqp_select_paths", "pqp_select_paths_device"):
-        getattr(lib, name).argtypes = [vp, C.POINTER(PqpSelectParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
-    for name in ("pqp_project_points", "pqp_project_points_device"):
-        getattr(lib, name).argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
-    lib.pqp_speed_default_params.argtypes = [C.POINTER(PqpSpeedParams)]
-    lib.pqp_speed_default_params.restype = None
-    for name in ("pqp_speed_profile", "pqp_speed_profile_device"):
-        getattr(lib, name).argtypes = [vp, C.POINTER(PqpSpeedParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    lib.pqp_sample_default_params.argtypes = [C.POINTER(PqpSampleParams)]
-    lib.pqp_sample_default_params.restype = None
-    for name in ("pqp_sample_trajectory", "pqp_sample_trajectory_device"):
-        getattr(lib, name).argtypes = [vp, C.POINTER(PqpSampleParams), C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    for f in HEADER.functions.values():
+        try:
+            fn = getattr(lib, f.name)
+        except AttributeError:
+            raise OSError(f"{path} lacks {f.name}, which include/pqp.h declares: rebuild the library") from None
+        fn.argtypes = [_argtype(f.name, p) for p in f.params]
+        fn.restype = _RESTYPE[f.ret]
     if path == LIB_PATH:
         _lib = lib
     return lib
 
 
-def default_params(lib=None, **over):
+class PqpError(RuntimeError):
+    pass
+
+
+def _raise_on(lib, rc):
+    if rc != 0:
+        raise PqpError(f"pqp error {rc}: {lib.pqp_last_error().decode()}")
+
+
+def _defaults(lib, struct, function, over):
+    """struct filled by the library's `function` (pqp_*_default_*), with `over` applied"""
     lib = lib or load_library()
-    p = PqpParams()
-    lib.pqp_default_params(C.byref(p))
+    p = struct()
+    getattr(lib, function)(C.byref(p))
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def default_params(lib=None, **over):
+    return _defaults(lib, PqpParams, "pqp_default_params", over)
 
 
 def production_params(lib=None, **over):
     """pqp_production_params: the defaults + the engine's production solver setting (1e-4 + KKT-verified polish)."""
-    lib = lib or load_library()
-    p = PqpParams()
-    lib.pqp_production_params(C.byref(p))
-    for k, v in over.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(lib, PqpParams, "pqp_production_params", over)
 
 
 def car_default_geometry(lib=None, **over):
     """pqp_car_default_geometry: the reference's flags (car_width 2.0, rear_length -1.0, front_length 3.9), with `over` applied."""
-    lib = lib or load_library()
-    c = PqpCarGeometry()
-    lib.pqp_car_default_geometry(C.byref(c))
-    for k, v in over.items():
-        setattr(c, k, v)
-    return c
+    return _defaults(lib, PqpCarGeometry, "pqp_car_default_geometry", over)
 
 
 def select_default_params(lib=None, **over):
     """pqp_select_default_params: the path QP's own weights on k and dk (20, 100), nothing else weighted, clearance_want 0.6,
     require_free 1, with `over` applied."""
-    lib = lib or load_library()
-    p = PqpSelectParams()
-    lib.pqp_select_default_params(C.byref(p))
-    for k, v in over.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(lib, PqpSelectParams, "pqp_select_default_params", over)
 
 
 def speed_default_params(lib=None, **over):
     """pqp_speed_default_params: v_max 10 m/s, a_max 1.5, d_max 3 and a_lat_max 2 m/s^2 - this library's choice, the reference has no such
     flags - with `over` applied."""
-    lib = lib or load_library()
-    p = PqpSpeedParams()
-    lib.pqp_speed_default_params(C.byref(p))
-    for k, v in over.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(lib, PqpSpeedParams, "pqp_speed_default_params", over)
 
 
 def sample_default_params(lib=None, **over):
     """pqp_sample_default_params: dt 0.1 s, hold_last 0 - this library's choice - with `over` applied."""
-    lib = lib or load_library()
-    p = PqpSampleParams()
-    lib.pqp_sample_default_params(C.byref(p))
-    for k, v in over.items():
-        setattr(p, k, v)
-    return p
+    return _defaults(lib, PqpSampleParams, "pqp_sample_default_params", over)
 
 
 def car_circles(car=None, lib=None):
@@ -314,13 +168,12 @@ def car_circles(car=None, lib=None):
     lib = lib or load_library()
     car = car if car is not None else car_default_geometry(lib)
     out = np.zeros((7, 3))
-    rc = lib.pqp_car_circles(C.byref(car), out.ctypes.data_as(C.c_void_p))
-    if rc != 0:
-        raise PqpError(f"pqp error {rc}: {lib.pqp_last_error().decode()}")
+    _raise_on(lib, lib.pqp_car_circles(C.byref(car), out))
     return out
 
 
 def _ptr(a):
+    """c_void_p of a host array or a raw address: what the typed argtypes let through unchecked (raw calls in tests and tools)"""
     if a is None:
         return None
     if isinstance(a, np.ndarray):
@@ -329,24 +182,23 @@ def _ptr(a):
     return C.c_void_p(int(a))      # raw device pointer (e.g. torch.Tensor.data_ptr())
 
 
-OPT_STORE_WARM, OPT_ORDER_BY_COST, OPT_RESERVE_CUS, OPT_STREAM_BATCH, OPT_CARRY_CYCLES, OPT_CHAIN_GRAPH, OPT_STREAM_STAGED = 1, 2, 3, 4, 5, 6, 7
-OPT_LONG_LINES = 8     # line-geometry steps past their LDS: 0 refuse (default), 1 long form where the LDS form does not fit, 2 long form always
+def _dp(x):
+    """c_void_p of a device pointer: an int, or an object with data_ptr() (a torch tensor), unchecked"""
+    if x is None:
+        return None
+    return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
+
+
 def stream_batch_default(n, lib=None):
     """pqp_stream_batch_default: from how many QPs of n waypoints on a cold call runs on the lane-per-QP kernel (PQP_OPT_STREAM_BATCH's default)."""
     lib = lib or load_library()
-    lib.pqp_stream_batch_default.restype = C.c_int
-    return int(lib.pqp_stream_batch_default(C.c_int(n)))
+    return int(lib.pqp_stream_batch_default(int(n)))
 
 
 def path_interval(value, n):
     """What pqp_params.adaptive_rho_interval / check_termination / polish_every mean for paths of n waypoints: negative values (the production
     setting) stand for "by path length" (csrc/pqp_defaults.hpp path_interval: 5 iterations up to 90 waypoints, 8 beyond)."""
     return value if value >= 0 else (5 if n <= 90 else 8)
-
-
-KERNEL_NONE, KERNEL_LANE_PER_WAYPOINT, KERNEL_LANE_PER_QP = 0, 1, 2      # pqp_last_path_kernel
-SMOOTHING_TENSION2, SMOOTHING_TENSION = 0, 1
-SECOND_PASS_RELINEARISE, SECOND_PASS_BOUNDS_ON_STATES = 0, 1      # pqp_second_pass (pqp_chain_config.second_pass)
 
 
 class MultiHandle:
@@ -357,9 +209,7 @@ class MultiHandle:
         self.params = params or default_params(self.lib)
         self._m = C.c_void_p()
         devs = (C.c_int32 * len(devices))(*devices)
-        rc = self.lib.pqp_multi_create(C.byref(self._m), C.byref(self.params), len(devices), devs, max_batch_per_shard, max_n)
-        if rc != 0:
-            raise PqpError(f"pqp error {rc}: {self.lib.pqp_last_error().decode()}")
+        _raise_on(self.lib, self.lib.pqp_multi_create(C.byref(self._m), C.byref(self.params), len(devices), devs, max_batch_per_shard, max_n))
 
     def close(self):
         if self._m:
@@ -373,8 +223,7 @@ class MultiHandle:
             pass
 
     def set_option(self, option, value):
-        if self.lib.pqp_multi_set_option(self._m, int(option), int(value)) != 0:
-            raise PqpError(self.lib.pqp_last_error().decode())
+        _raise_on(self.lib, self.lib.pqp_multi_set_option(self._m, int(option), int(value)))
 
     def solve(self, ref, bounds, scal, lin=None, passes=1, n_of=None):
         ref = np.ascontiguousarray(ref, dtype=np.float64); bounds = np.ascontiguousarray(bounds, dtype=np.float64)
@@ -383,10 +232,7 @@ class MultiHandle:
         counts = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
         batch, n = ref.shape[0], ref.shape[1]
         out = np.zeros((batch, n, 7)); status = np.zeros(batch, dtype=np.int32); iters = np.zeros(batch, dtype=np.int32); info = np.zeros((batch, 8))
-        rc = self.lib.pqp_multi_path_solve(self._m, batch, n, _ptr(counts), _ptr(ref), _ptr(lin), _ptr(bounds), _ptr(scal), passes, _ptr(out),
-                                           _ptr(status), _ptr(iters), _ptr(info))
-        if rc != 0:
-            raise PqpError(f"pqp error {rc}: {self.lib.pqp_last_error().decode()}")
+        _raise_on(self.lib, self.lib.pqp_multi_path_solve(self._m, batch, n, counts, ref, lin, bounds, scal, passes, out, status, iters, info))
         self._last = (batch, n)
         return dict(out=out, status=status, iters=iters, info=info)
 
@@ -399,18 +245,12 @@ class MultiHandle:
         for d in devices:
             torch.cuda.synchronize(int(d))
         ptrs = (C.c_void_p * len(outs))(*[t.data_ptr() for t in outs])
-        rc = self.lib.pqp_multi_gather_paths(self._m, batch, n, ptrs)
-        if rc != 0:
-            raise PqpError(f"pqp error {rc}: {self.lib.pqp_last_error().decode()}")
+        _raise_on(self.lib, self.lib.pqp_multi_gather_paths(self._m, batch, n, ptrs))
         return outs
 
     def gather_ranks(self):
         """ncclCommCount of the gather's communicator (0 before the first gather_paths)."""
         return int(self.lib.pqp_multi_gather_ranks(self._m))
-
-
-class PqpError(RuntimeError):
-    pass
 
 
 def _occupancy(grid, who):
@@ -448,8 +288,7 @@ class Handle:
         self._check(self.lib.pqp_create(C.byref(self._h), C.byref(self.params), device, max_batch, max_n))
 
     def _check(self, rc):
-        if rc != 0:
-            raise PqpError(f"pqp error {rc}: {self.lib.pqp_last_error().decode()}")
+        _raise_on(self.lib, rc)
 
     def close(self):
         if self._h:
@@ -483,7 +322,7 @@ class Handle:
         a = torch.from_numpy(np.ascontiguousarray(angles, dtype=np.float64).ravel()).to(dev)
         o = torch.empty_like(a)
         torch.cuda.synchronize(dev)
-        self._check(self.lib.pqp_constrain_angle_device(self._h, a.numel(), C.c_void_p(a.data_ptr()), C.c_void_p(o.data_ptr())))
+        self._check(self.lib.pqp_constrain_angle_device(self._h, a.numel(), a, o))
         self.sync()
         return o.cpu().numpy().reshape(np.shape(angles))
 
@@ -502,11 +341,7 @@ class Handle:
         return s.value
 
     def chain_config(self, **over):
-        c = PqpChainConfig()
-        self.lib.pqp_chain_default_config(C.byref(c))
-        for k, v in over.items():
-            setattr(c, k, v)
-        return c
+        return _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", over)
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, sample=None, samples=None,
@@ -543,8 +378,7 @@ class Handle:
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
-        build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), C.c_void_p(d_grid.data_ptr()),
-                                                                                      C.c_void_p(d_dist.data_ptr())))
+        build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed))
@@ -625,38 +459,37 @@ class Handle:
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
-        p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        self._check(self.lib.pqp_optimize_path_device(self._h, smoother._h if smoother is not None else None, C.byref(cfg), B, p_max, p(d_pts), p(d_np),
-                                                      p(d_st), p(d_tg), p(d_dist), p(d_map), C.byref(geom), p(d_k), p(out), p(ints[0]), p(ints[1]),
-                                                      p(ints[2]), p(ints[3])))
+        self._check(self.lib.pqp_optimize_path_device(self._h, smoother._h if smoother is not None else None, C.byref(cfg), B, p_max, d_pts, d_np,
+                                                      d_st, d_tg, d_dist, d_map, C.byref(geom), d_k, out, ints[0], ints[1],
+                                                      ints[2], ints[3]))
         if footprint is not None:           # behind the chain on the handle's stream: reads out / n_out where they are
             car, mode = footprint
             car = car if car is not None else car_default_geometry(self.lib)
             free = torch.zeros((B, cfg.n_max), dtype=torch.uint8, device=dev)
             first = torch.zeros(B, dtype=torch.int32, device=dev)
             margin = torch.zeros((B, cfg.n_max), dtype=torch.float64, device=dev)
-            self._check(self.lib.pqp_footprint_check_device(self._h, B, cfg.n_max, 7, p(out), p(ints[0]), p(d_dist), p(d_map), C.byref(geom),
-                                                            C.byref(car), int(mode), p(free), p(first), p(margin)))
+            self._check(self.lib.pqp_footprint_check_device(self._h, B, cfg.n_max, 7, out, ints[0], d_dist, d_map, C.byref(geom),
+                                                            C.byref(car), int(mode), free, first, margin))
         if selection is not None:           # behind both: reads out, n_out, status, stage (and first_collision, margin) where they are
-            self._check(self.lib.pqp_select_paths_device(self._h, C.byref(sel_prm), B, cfg.n_max, 7, p(out), p(ints[0]), p(ints[1]), p(ints[2]),
-                                                         p(first) if footprint is not None else None, p(margin) if footprint is not None else None,
-                                                         groups, p(d_start), p(terms), p(best), p(best_paths), p(best_n)))
+            self._check(self.lib.pqp_select_paths_device(self._h, C.byref(sel_prm), B, cfg.n_max, 7, out, ints[0], ints[1], ints[2],
+                                                         first if footprint is not None else None, margin if footprint is not None else None,
+                                                         groups, d_start, terms, best, best_paths, best_n))
         if speed is not None:               # behind all of them: the winners where the selection left them, or every candidate in `out`
             if selection is not None:       # (an eligible winner is collision-free: require_free)
-                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), groups, cfg.n_max, 7, p(best_paths), p(best_n), None, None,
-                                                              p(d_vs), p(d_ve), p(profile), p(speed_flags)))
+                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), groups, cfg.n_max, 7, best_paths, best_n, None, None,
+                                                              d_vs, d_ve, profile, speed_flags))
             else:
-                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), B, cfg.n_max, 7, p(out), p(ints[0]),
-                                                              p(first) if footprint is not None else None, None, p(d_vs), p(d_ve), p(profile),
-                                                              p(speed_flags)))
+                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), B, cfg.n_max, 7, out, ints[0],
+                                                              first if footprint is not None else None, None, d_vs, d_ve, profile,
+                                                              speed_flags))
         if sampling is not None:            # behind the speed profile, on the arrays it ran on
             if selection is not None:
-                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), groups, cfg.n_max, 7, p(best_paths), p(best_n), None,
-                                                                  p(profile), p(d_t0), m, p(traj), p(traj_n), p(traj_flags)))
+                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), groups, cfg.n_max, 7, best_paths, best_n, None,
+                                                                  profile, d_t0, m, traj, traj_n, traj_flags))
             else:
-                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, p(out), p(ints[0]),
-                                                                  p(first) if footprint is not None else None, p(profile), p(d_t0), m, p(traj),
-                                                                  p(traj_n), p(traj_flags)))
+                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, out, ints[0],
+                                                                  first if footprint is not None else None, profile, d_t0, m, traj,
+                                                                  traj_n, traj_flags))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -684,7 +517,7 @@ class Handle:
         two_d = np.ndim(grid) == 2
         cm = _column_major(_occupancy(grid, "distance_layer"), np.uint8)
         out = np.empty(cm.shape, dtype=np.float32)
-        self._check(self.lib.pqp_distance_layer(self._h, cm.shape[0], C.byref(geom), _ptr(cm), _ptr(out)))
+        self._check(self.lib.pqp_distance_layer(self._h, cm.shape[0], C.byref(geom), cm, out))
         out = np.transpose(out, (0, 2, 1))
         return out[0] if two_d else out
 
@@ -702,8 +535,8 @@ class Handle:
         free = np.zeros((B, n), dtype=np.uint8)
         first = np.zeros(B, dtype=np.int32)
         mg = np.zeros((B, n)) if margin else None
-        self._check(self.lib.pqp_footprint_check(self._h, B, n, stride, _ptr(states), _ptr(no), _ptr(dist_cm), dist_cm.shape[0], _ptr(mo), C.byref(geom),
-                                                 C.byref(car), int(mode), _ptr(free), _ptr(first), _ptr(mg)))
+        self._check(self.lib.pqp_footprint_check(self._h, B, n, stride, states, no, dist_cm, dist_cm.shape[0], mo, C.byref(geom),
+                                                 C.byref(car), int(mode), free, first, mg))
         res = dict(free=free, first_collision=first)
         if margin:
             res["margin"] = mg
@@ -726,8 +559,8 @@ class Handle:
         best = np.zeros(groups, dtype=np.int32)
         best_paths = np.zeros((groups, n, 7))
         best_n = np.zeros(groups, dtype=np.int32)
-        self._check(self.lib.pqp_select_paths(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(stt), _ptr(stg), _ptr(fc), _ptr(mg),
-                                              groups, _ptr(gs), _ptr(terms), _ptr(best), _ptr(best_paths), _ptr(best_n)))
+        self._check(self.lib.pqp_select_paths(self._h, C.byref(prm), B, n, stride, paths, no, stt, stg, fc, mg,
+                                              groups, gs, terms, best, best_paths, best_n))
         return dict(terms=terms, best=best, best_paths=best_paths, best_n=best_n)
 
     def speed_profile(self, paths, v_start, n_of=None, stop_before=None, v_limit=None, v_end=None, prm=None):
@@ -745,8 +578,8 @@ class Handle:
         prm = prm if prm is not None else speed_default_params(self.lib)
         profile = np.zeros((B, n, SPEED_STRIDE))
         flags = np.zeros(B, dtype=np.int32)
-        self._check(self.lib.pqp_speed_profile(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(sb), _ptr(vl), _ptr(vs), _ptr(ve),
-                                               _ptr(profile), _ptr(flags)))
+        self._check(self.lib.pqp_speed_profile(self._h, C.byref(prm), B, n, stride, paths, no, sb, vl, vs, ve,
+                                               profile, flags))
         return profile, flags
 
     def sample_trajectory(self, paths, profile, m, n_of=None, stop_before=None, t0=None, prm=None):
@@ -769,16 +602,12 @@ class Handle:
         traj = np.zeros((B, max(m, 0), TRAJ_STRIDE))
         m_of = np.zeros(B, dtype=np.int32)
         flags = np.zeros(B, dtype=np.int32)
-        self._check(self.lib.pqp_sample_trajectory(self._h, C.byref(prm), B, n, stride, _ptr(paths), _ptr(no), _ptr(sb), _ptr(profile), _ptr(tt), m,
-                                                   _ptr(traj), _ptr(m_of), _ptr(flags)))
+        self._check(self.lib.pqp_sample_trajectory(self._h, C.byref(prm), B, n, stride, paths, no, sb, profile, tt, m,
+                                                   traj, m_of, flags))
         return traj, m_of, flags
 
     def corridor_params(self, **over):
-        p = PqpCorridorParams()
-        self.lib.pqp_corridor_default_params(C.byref(p))
-        for k, v in over.items():
-            setattr(p, k, v)
-        return p
+        return _defaults(self.lib, PqpCorridorParams, "pqp_corridor_default_params", over)
 
     def dp_corridor(self, spline, spline_ext, length, start, dist, geom, max_layers=128, map_of=None, prm=None):
         """pqp_dp_corridor (host arrays) -> (layers_s [B][max_layers], lb, ub, count [B], vehicle_l [B])."""
@@ -790,10 +619,9 @@ class Handle:
         count = np.zeros(B, dtype=np.int32); vl = np.zeros(B)
         mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
         if prm is None:
-            prm = PqpDpParams()
-            self.lib.pqp_dp_default_params(C.byref(prm))
-        self._check(self.lib.pqp_dp_corridor(self._h, B, m, max_layers, _ptr(spline), _ptr(spline_ext), _ptr(length), _ptr(start), _ptr(dist_cm),
-                                             dist_cm.shape[0], _ptr(mo), C.byref(geom), C.byref(prm), _ptr(ls), _ptr(lb), _ptr(ub), _ptr(count), _ptr(vl)))
+            prm = _defaults(self.lib, PqpDpParams, "pqp_dp_default_params", {})
+        self._check(self.lib.pqp_dp_corridor(self._h, B, m, max_layers, spline, spline_ext, length, start, dist_cm,
+                                             dist_cm.shape[0], mo, C.byref(geom), C.byref(prm), ls, lb, ub, count, vl))
         return ls, lb, ub, count, vl
 
     def spline_fit(self, s, x, y):
@@ -801,7 +629,7 @@ class Handle:
         s = np.ascontiguousarray(s, dtype=np.float64); x = np.ascontiguousarray(x, dtype=np.float64); y = np.ascontiguousarray(y, dtype=np.float64)
         B, m = s.shape
         tab = np.zeros((B, 9, m)); ext = np.zeros((B, 4))
-        self._check(self.lib.pqp_spline_fit(self._h, B, m, _ptr(s), _ptr(x), _ptr(y), _ptr(tab), _ptr(ext)))
+        self._check(self.lib.pqp_spline_fit(self._h, B, m, s, x, y, tab, ext))
         return tab, ext
 
     def reference_states(self, spline, spline_ext, max_s, n_max, start=None, ds_small=0.15, ds_large=0.3, dynamic=True):
@@ -814,8 +642,8 @@ class Handle:
         st = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
         ref = np.zeros((B, n_max, 5)); count = np.zeros(B, dtype=np.int32)
         err = None if start is None else np.zeros((B, 2))
-        self._check(self.lib.pqp_reference_states(self._h, B, n_max, m, _ptr(spline), _ptr(spline_ext), _ptr(max_s), _ptr(st), ds_small,
-                                                  ds_large, 1 if dynamic else 0, _ptr(ref), _ptr(count), _ptr(err)))
+        self._check(self.lib.pqp_reference_states(self._h, B, n_max, m, spline, spline_ext, max_s, st, ds_small,
+                                                  ds_large, 1 if dynamic else 0, ref, count, err))
         return ref, count, err
 
     def offsets_to_points(self, spline, spline_ext, at_s, l, m_of=None):
@@ -825,7 +653,7 @@ class Handle:
         mo = None if m_of is None else np.ascontiguousarray(m_of, dtype=np.int32)
         B, ms, m = spline.shape[0], spline.shape[2], at_s.shape[1]
         x = np.zeros((B, m)); y = np.zeros((B, m)); s = np.zeros((B, m))
-        self._check(self.lib.pqp_offsets_to_points(self._h, B, ms, m, _ptr(spline), _ptr(spline_ext), _ptr(at_s), _ptr(l), _ptr(mo), _ptr(x), _ptr(y), _ptr(s)))
+        self._check(self.lib.pqp_offsets_to_points(self._h, B, ms, m, spline, spline_ext, at_s, l, mo, x, y, s))
         return x, y, s
 
     def reference_length(self, spline, spline_ext, length, target):
@@ -834,7 +662,7 @@ class Handle:
         length = np.ascontiguousarray(length, dtype=np.float64); target = np.ascontiguousarray(target, dtype=np.float64)
         B, m = spline.shape[0], spline.shape[2]
         out = np.zeros(B)
-        self._check(self.lib.pqp_reference_length(self._h, B, m, _ptr(spline), _ptr(spline_ext), _ptr(length), _ptr(target), _ptr(out)))
+        self._check(self.lib.pqp_reference_length(self._h, B, m, spline, spline_ext, length, target, out))
         return out
 
     def project_points(self, spline, spline_ext, length, points, q_of=None, has_heading=None):
@@ -849,8 +677,8 @@ class Handle:
         if has_heading is None:
             has_heading = stride >= 3
         proj = np.zeros((B, q_max, PROJ_STRIDE)); flags = np.zeros((B, q_max), dtype=np.int32)
-        self._check(self.lib.pqp_project_points(self._h, B, m, _ptr(spline), _ptr(spline_ext), _ptr(length), q_max, stride, 1 if has_heading else 0,
-                                                _ptr(points), _ptr(qo), _ptr(proj), _ptr(flags)))
+        self._check(self.lib.pqp_project_points(self._h, B, m, spline, spline_ext, length, q_max, stride, 1 if has_heading else 0,
+                                                points, qo, proj, flags))
         return proj, flags
 
     def bspline_resample(self, points, n_points, n_max):
@@ -860,8 +688,8 @@ class Handle:
         B, p_max = points.shape[0], points.shape[1]
         o = {k: np.zeros((B, n_max)) for k in ("x", "y", "s")}
         count = np.zeros(B, dtype=np.int32)
-        self._check(self.lib.pqp_bspline_resample(self._h, B, p_max, n_max, _ptr(points), _ptr(n_points), _ptr(o["x"]), _ptr(o["y"]), _ptr(o["s"]),
-                                                  _ptr(count)))
+        self._check(self.lib.pqp_bspline_resample(self._h, B, p_max, n_max, points, n_points, o["x"], o["y"], o["s"],
+                                                  count))
         o["count"] = count
         return o
 
@@ -874,8 +702,8 @@ class Handle:
         B, m = spline.shape[0], spline.shape[2]
         o = {k: np.zeros((B, n_max)) for k in ("x", "y", "s", "angle", "k")}
         count = np.zeros(B, dtype=np.int32)
-        self._check(self.lib.pqp_segment_raw_reference(self._h, B, n_max, m, _ptr(spline), _ptr(spline_ext), _ptr(max_s), delta_s,
-                                                       _ptr(o["x"]), _ptr(o["y"]), _ptr(o["s"]), _ptr(o["angle"]), _ptr(o["k"]), _ptr(count)))
+        self._check(self.lib.pqp_segment_raw_reference(self._h, B, n_max, m, spline, spline_ext, max_s, delta_s,
+                                                       o["x"], o["y"], o["s"], o["angle"], o["k"], count))
         o["count"] = count
         return o
 
@@ -893,8 +721,8 @@ class Handle:
         mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
         prm = prm or self.corridor_params()
         no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
-        self._check(self.lib.pqp_corridor_bounds(self._h, B, n, m, _ptr(ref), _ptr(no), _ptr(spline), _ptr(spline_ext), _ptr(dist_cm), dist_cm.shape[0],
-                                                 _ptr(mo), C.byref(geom), C.byref(prm), _ptr(bounds), _ptr(n_valid)))
+        self._check(self.lib.pqp_corridor_bounds(self._h, B, n, m, ref, no, spline, spline_ext, dist_cm, dist_cm.shape[0],
+                                                 mo, C.byref(geom), C.byref(prm), bounds, n_valid))
         return bounds, n_valid
 
     def corridor_bounds_on_states(self, ref, states, spline, spline_ext, dist, geom, map_of=None, prm=None, n_of=None):
@@ -915,13 +743,13 @@ class Handle:
         mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
         prm = prm or self.corridor_params()
         no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
-        self._check(self.lib.pqp_corridor_bounds_on_states(self._h, B, n, m, _ptr(ref), _ptr(no), _ptr(states), states.shape[2], _ptr(spline), _ptr(spline_ext),
-                                                           _ptr(dist_cm), dist_cm.shape[0], _ptr(mo), C.byref(geom), C.byref(prm), _ptr(bounds), _ptr(n_valid)))
+        self._check(self.lib.pqp_corridor_bounds_on_states(self._h, B, n, m, ref, no, states, states.shape[2], spline, spline_ext,
+                                                           dist_cm, dist_cm.shape[0], mo, C.byref(geom), C.byref(prm), bounds, n_valid))
         return bounds, n_valid
 
     def sizes(self, n, s=None):
         out = PqpSizes()
-        self._check(self.lib.pqp_path_sizes(C.byref(self.params), n, _ptr(s), C.byref(out)))
+        self._check(self.lib.pqp_path_sizes(C.byref(self.params), n, s, C.byref(out)))
         return {k: getattr(out, k) for k, _ in PqpSizes._fields_}
 
     def pattern(self, n, precise=None):
@@ -931,7 +759,7 @@ class Handle:
         rows = np.zeros(nnz_a, dtype=np.int32)
         colptr = np.zeros(nv + 1, dtype=np.int32)
         pcols = np.zeros(n + n - 1 + precise + n, dtype=np.int32)
-        self._check(self.lib.pqp_path_pattern(self._h, n, precise, _ptr(rows), _ptr(colptr), _ptr(pcols)))
+        self._check(self.lib.pqp_path_pattern(self._h, n, precise, rows, colptr, pcols))
         return rows, colptr, pcols
 
     def assemble(self, ref, lin, bounds, scal, precise=None):
@@ -942,8 +770,8 @@ class Handle:
         cons = 4 * n + precise + n + 2
         a_val = np.zeros((batch, nnz_a)); p_val = np.zeros((batch, nnz_p))
         lo = np.zeros((batch, cons)); up = np.zeros((batch, cons))
-        self._check(self.lib.pqp_path_assemble(self._h, batch, n, precise, _ptr(ref), _ptr(lin), _ptr(bounds),
-                                               _ptr(scal), _ptr(a_val), _ptr(p_val), _ptr(lo), _ptr(up)))
+        self._check(self.lib.pqp_path_assemble(self._h, batch, n, precise, ref, lin, bounds,
+                                               scal, a_val, p_val, lo, up))
         return a_val, p_val, lo, up
 
     def solve(self, ref, bounds, scal, lin=None, passes=1, warm=False):
@@ -951,8 +779,8 @@ class Handle:
         batch, n = ref.shape[0], ref.shape[1]
         out = np.zeros((batch, n, 7)); status = np.zeros(batch, dtype=np.int32)
         iters = np.zeros(batch, dtype=np.int32); info = np.zeros((batch, 8))
-        self._check(self.lib.pqp_path_solve(self._h, batch, n, _ptr(ref), _ptr(lin), _ptr(bounds), _ptr(scal),
-                                            passes, 1 if warm else 0, _ptr(out), _ptr(status), _ptr(iters), _ptr(info)))
+        self._check(self.lib.pqp_path_solve(self._h, batch, n, ref, lin, bounds, scal,
+                                            passes, 1 if warm else 0, out, status, iters, info))
         return dict(out=out, status=status, iters=iters, info=info)
 
     def solve_var(self, n_of, ref, bounds, scal, lin=None, passes=1, warm=False):
@@ -961,35 +789,27 @@ class Handle:
         counts = np.ascontiguousarray(n_of, dtype=np.int32)
         out = np.zeros((batch, n, 7)); status = np.zeros(batch, dtype=np.int32)
         iters = np.zeros(batch, dtype=np.int32); info = np.zeros((batch, 8))
-        self._check(self.lib.pqp_path_solve_var(self._h, batch, n, _ptr(counts), _ptr(ref), _ptr(lin), _ptr(bounds), _ptr(scal),
-                                                passes, 1 if warm else 0, _ptr(out), _ptr(status), _ptr(iters), _ptr(info)))
+        self._check(self.lib.pqp_path_solve_var(self._h, batch, n, counts, ref, lin, bounds, scal,
+                                                passes, 1 if warm else 0, out, status, iters, info))
         return dict(out=out, status=status, iters=iters, info=info)
 
     def solve_device(self, batch, n, ref, bounds, scal, out, lin=None, passes=1, warm=False, status=None,
                      iters=None, info=None):
         """Device pointers (ints or objects with data_ptr()); asynchronous on the handle's stream."""
-        def dp(x):
-            if x is None:
-                return None
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self.lib.pqp_path_solve_device(self._h, batch, n, dp(ref), dp(lin), dp(bounds), dp(scal), passes,
-                                                   1 if warm else 0, dp(out), dp(status), dp(iters), dp(info)))
+        self._check(self.lib.pqp_path_solve_device(self._h, batch, n, _dp(ref), _dp(lin), _dp(bounds), _dp(scal), passes,
+                                                   1 if warm else 0, _dp(out), _dp(status), _dp(iters), _dp(info)))
 
     def solve_var_device(self, batch, n_max, n_of, ref, bounds, scal, out, lin=None, passes=1, warm=False, status=None, iters=None, info=None):
         """pqp_path_solve_var_device: like solve_device with a waypoint count per QP (n_of: device int32 [batch])."""
-        def dp(x):
-            if x is None:
-                return None
-            return C.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else int(x))
-        self._check(self.lib.pqp_path_solve_var_device(self._h, batch, n_max, dp(n_of), dp(ref), dp(lin), dp(bounds), dp(scal), passes,
-                                                       1 if warm else 0, dp(out), dp(status), dp(iters), dp(info)))
+        self._check(self.lib.pqp_path_solve_var_device(self._h, batch, n_max, _dp(n_of), _dp(ref), _dp(lin), _dp(bounds), _dp(scal), passes,
+                                                       1 if warm else 0, _dp(out), _dp(status), _dp(iters), _dp(info)))
 
     def get_solution(self, batch, n, precise=None):
         precise = n if precise is None else precise
         nv = 3 * n + n - 1 + precise + n
         nc = 4 * n + precise + n + 2
         x = np.zeros((batch, nv)); y = np.zeros((batch, nc))
-        self._check(self.lib.pqp_path_get_solution(self._h, batch, n, precise, _ptr(x), _ptr(y)))
+        self._check(self.lib.pqp_path_get_solution(self._h, batch, n, precise, x, y))
         return x, y
 
     # ---- smoother QPs (host arrays [batch][n]) ----
@@ -997,8 +817,8 @@ class Handle:
         B, n = x.shape
         ox = np.zeros((B, n)); oy = np.zeros((B, n)); os_ = np.zeros((B, n)); st = np.zeros(B, dtype=np.int32); it = np.zeros(B, dtype=np.int32)
         c = np.ascontiguousarray
-        self._check(self.lib.pqp_smooth_tension2(self._h, B, n, _ptr(c(x)), _ptr(c(y)), _ptr(c(angle)), _ptr(c(k)), _ptr(c(s)), _ptr(ox), _ptr(oy),
-                                                 _ptr(os_), _ptr(st), _ptr(it)))
+        self._check(self.lib.pqp_smooth_tension2(self._h, B, n, c(x), c(y), c(angle), c(k), c(s), ox, oy,
+                                                 os_, st, it))
         return dict(x=ox, y=oy, s=os_, status=st, iters=it)
 
     def smooth_tension(self, x, y, angle, clearance, info=False):
@@ -1006,86 +826,56 @@ class Handle:
         ox = np.zeros((B, n)); oy = np.zeros((B, n)); os_ = np.zeros((B, n)); st = np.zeros(B, dtype=np.int32); it = np.zeros(B, dtype=np.int32)
         c = np.ascontiguousarray
         if not info:
-            self._check(self.lib.pqp_smooth_tension(self._h, B, n, _ptr(c(x)), _ptr(c(y)), _ptr(c(angle)), _ptr(c(clearance)), _ptr(ox), _ptr(oy),
-                                                    _ptr(os_), _ptr(st), _ptr(it)))
+            self._check(self.lib.pqp_smooth_tension(self._h, B, n, c(x), c(y), c(angle), c(clearance), ox, oy,
+                                                    os_, st, it))
             return dict(x=ox, y=oy, s=os_, status=st, iters=it)
-        # with the info rows (factorisations in [5]): the device entry point, torch as the memory plumbing
+        # with the info rows (factorisations in [5]): the device entry point
+        return self._on_device(self.lib.pqp_smooth_tension_device, (x, y, angle, clearance), None, ("x", "y", "s"), True, True)
+
+    def _on_device(self, function, lists, count, outs, info_rows=False, info=False):
+        """A smoother's `_device` entry point on host arrays, torch as the memory plumbing: uploads `lists` ([B][n] each, the last may be
+        [B]) and `count` [B] (None: the entry point takes none), zeroes the [B][n] outputs named in `outs`, status, iters and - with
+        info_rows - the info rows [B][8], synchronises, calls, waits and downloads.  The entry point gets the info rows only with `info`."""
         import torch
         dev = torch.device("cuda", self.device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        d = [t(a) for a in (x, y, angle, clearance)]
-        o = [torch.zeros((B, n), dtype=torch.float64, device=dev) for _ in range(3)]
-        dst, dit = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-        dinf = torch.zeros((B, 8), dtype=torch.float64, device=dev)
+        B, n = lists[0].shape
+        t = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+        d = [t(a) for a in lists]
+        d_count = [] if count is None else [t(count, np.int32)]
+        o = [torch.zeros((B, n), dtype=torch.float64, device=dev) for _ in outs]
+        st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
+        inf = torch.zeros((B, 8), dtype=torch.float64, device=dev) if info_rows else None
         torch.cuda.synchronize(dev)
-        p = lambda a: C.c_void_p(a.data_ptr())
-        self._check(self.lib.pqp_smooth_tension_device(self._h, B, n, p(d[0]), p(d[1]), p(d[2]), p(d[3]), p(o[0]), p(o[1]), p(o[2]), p(dst), p(dit), p(dinf)))
+        self._check(function(self._h, B, n, *d_count, *d, *o, st, it, inf if info else None))
         self.sync()
-        return dict(x=o[0].cpu().numpy(), y=o[1].cpu().numpy(), s=o[2].cpu().numpy(), status=dst.cpu().numpy(), iters=dit.cpu().numpy(), info=dinf.cpu().numpy())
+        r = {k: a.cpu().numpy() for k, a in zip(outs + ("status", "iters"), o + [st, it])}
+        if info:
+            r["info"] = inf.cpu().numpy()
+        return r
 
     def smooth_tension2_var(self, x, y, angle, k, s, n_of):
         """pqp_smooth_tension2_var_device (torch as the memory plumbing): lists [B][n_max], n_of [B] points per scenario."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        B, n = x.shape
-        t = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        d = [t(a) for a in (x, y, angle, k, s)]
-        d_n = t(n_of, np.int32)
-        o = [torch.zeros((B, n), dtype=torch.float64, device=dev) for _ in range(3)]
-        st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-        torch.cuda.synchronize(dev)
-        p = lambda a: C.c_void_p(a.data_ptr())
-        self._check(self.lib.pqp_smooth_tension2_var_device(self._h, B, n, p(d_n), p(d[0]), p(d[1]), p(d[2]), p(d[3]), p(d[4]), p(o[0]), p(o[1]), p(o[2]), p(st), p(it), None))
-        self.sync()
-        return dict(x=o[0].cpu().numpy(), y=o[1].cpu().numpy(), s=o[2].cpu().numpy(), status=st.cpu().numpy(), iters=it.cpu().numpy())
+        return self._on_device(self.lib.pqp_smooth_tension2_var_device, (x, y, angle, k, s), n_of, ("x", "y", "s"))
 
     def smooth_tension_var(self, x, y, angle, clearance, n_of):
         """pqp_smooth_tension_var_device (torch as the memory plumbing): lists [B][n_max], n_of [B] points per scenario."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        B, n = x.shape
-        t = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        d = [t(a) for a in (x, y, angle, clearance)]
-        d_n = t(n_of, np.int32)
-        o = [torch.zeros((B, n), dtype=torch.float64, device=dev) for _ in range(3)]
-        st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-        torch.cuda.synchronize(dev)
-        p = lambda a: C.c_void_p(a.data_ptr())
-        self._check(self.lib.pqp_smooth_tension_var_device(self._h, B, n, p(d_n), p(d[0]), p(d[1]), p(d[2]), p(d[3]), p(o[0]), p(o[1]), p(o[2]), p(st), p(it), None))
-        self.sync()
-        return dict(x=o[0].cpu().numpy(), y=o[1].cpu().numpy(), s=o[2].cpu().numpy(), status=st.cpu().numpy(), iters=it.cpu().numpy())
+        return self._on_device(self.lib.pqp_smooth_tension_var_device, (x, y, angle, clearance), n_of, ("x", "y", "s"))
 
     def post_smooth(self, layers_s, lb, ub, vehicle_l):
         B, m = layers_s.shape
         ol = np.zeros((B, m)); st = np.zeros(B, dtype=np.int32); it = np.zeros(B, dtype=np.int32)
         c = np.ascontiguousarray
-        self._check(self.lib.pqp_post_smooth(self._h, B, m, _ptr(c(layers_s)), _ptr(c(lb)), _ptr(c(ub)), _ptr(c(vehicle_l)), _ptr(ol), _ptr(st), _ptr(it)))
+        self._check(self.lib.pqp_post_smooth(self._h, B, m, c(layers_s), c(lb), c(ub), c(vehicle_l), ol, st, it))
         return dict(l=ol, status=st, iters=it)
 
     def post_smooth_var(self, layers_s, lb, ub, vehicle_l, m_of, info=False):
         """pqp_post_smooth_var_device (torch as the memory plumbing): lists [B][m_max], m_of [B] layers per scenario."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        B, m = layers_s.shape
-        t = lambda a, dt=np.float64: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        d = [t(a) for a in (layers_s, lb, ub, vehicle_l)]
-        d_m = t(m_of, np.int32)
-        ol = torch.zeros((B, m), dtype=torch.float64, device=dev)
-        st, it = (torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(2))
-        inf = torch.zeros((B, 8), dtype=torch.float64, device=dev)
-        torch.cuda.synchronize(dev)
-        p = lambda a: C.c_void_p(a.data_ptr())
-        self._check(self.lib.pqp_post_smooth_var_device(self._h, B, m, p(d_m), p(d[0]), p(d[1]), p(d[2]), p(d[3]), p(ol), p(st), p(it), p(inf) if info else None))
-        self.sync()
-        r = dict(l=ol.cpu().numpy(), status=st.cpu().numpy(), iters=it.cpu().numpy())
-        if info:
-            r["info"] = inf.cpu().numpy()
-        return r
+        return self._on_device(self.lib.pqp_post_smooth_var_device, (layers_s, lb, ub, vehicle_l), m_of, ("l",), True, info)
 
     def kernel_ms_history(self, count):
         """HIP-event durations of the last `count` launches of this handle (oldest first)."""
         ms = np.zeros(count, dtype=np.float32)
-        self._check(self.lib.pqp_kernel_ms_history(self._h, _ptr(ms), count))
+        self._check(self.lib.pqp_kernel_ms_history(self._h, ms, count))
         return ms
 
     def last_kernel_ms(self):
