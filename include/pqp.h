@@ -298,6 +298,8 @@ int pqp_path_sizes(const pqp_params* params, int n, const double* s, pqp_sizes* 
 
 /* Value-independent sparsity of A in CSC order (17N-5 slots when precise == n) and the columns of
  * the diagonal P, in the REFERENCE variable / row numbering (base_solver.cpp:154-209,127-143).
+ * P's columns are the ones the reference's sparseView keeps (base_solver.cpp:145): k_i, u_i and the slacks - and, when the handle's weight_l is not zero, l_i
+ * (pcols ascending, nnz_p = pqp_path_sizes' with the same parameters; with the default weight_l = 0 the l columns are absent as in the reference).
  * Computed by a HIP kernel.  rows[nnz_a], colptr[vars+1], pcols[nnz_p] are HOST buffers. */
 int pqp_path_pattern(pqp_handle* h, int n, int precise, int32_t* rows, int32_t* colptr, int32_t* pcols);
 

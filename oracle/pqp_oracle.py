@@ -220,9 +220,10 @@ def assemble_path_qp(ref, lin, bounds, scal, prm=None):
     return Pd, A, lo, up, sz
 
 
-def structural_pattern(n, precise):
+def structural_pattern(n, precise, with_l=False):
     """Value-independent (row, col) list of A in CSC order (col-major, rows ascending) —
-    the 17N-5 slots of SURVEY.md Appendix A generalised to P<=N — and P's diagonal columns."""
+    the 17N-5 slots of SURVEY.md Appendix A generalised to P<=N — and P's diagonal columns
+    (with_l: weight_l != 0, so that sparseView keeps the l columns too, base_solver.cpp:123,145)."""
     state, control = 3 * n, n - 1
     kappa_idx = 3 * n
     precise_idx = kappa_idx + n
@@ -258,6 +259,8 @@ def structural_pattern(n, precise):
     colptr = np.cumsum(colptr).astype(np.int32)
     pcols = []
     for i in range(n):
+        if with_l:
+            pcols.append(3 * i)
         pcols.append(3 * i + 2)
     for i in range(n - 1):
         pcols.append(state + i)

@@ -752,13 +752,17 @@ class Handle:
         self._check(self.lib.pqp_path_sizes(C.byref(self.params), n, s, C.byref(out)))
         return {k: getattr(out, k) for k, _ in PqpSizes._fields_}
 
+    def _nnz_p(self, n, precise):
+        """pqp_sizes.nnz_p: the diagonal of P has the l columns too once weight_l is not zero"""
+        return (2 * n if self.params.weight_l != 0.0 else n) + n - 1 + precise + n
+
     def pattern(self, n, precise=None):
         precise = n if precise is None else precise
         nv = 3 * n + n - 1 + precise + n
         nnz_a = 3 * n + 7 * (n - 1) + n + 6 * precise + 2 * (n - precise) + 2
         rows = np.zeros(nnz_a, dtype=np.int32)
         colptr = np.zeros(nv + 1, dtype=np.int32)
-        pcols = np.zeros(n + n - 1 + precise + n, dtype=np.int32)
+        pcols = np.zeros(self._nnz_p(n, precise), dtype=np.int32)
         self._check(self.lib.pqp_path_pattern(self._h, n, precise, rows, colptr, pcols))
         return rows, colptr, pcols
 
@@ -766,7 +770,7 @@ class Handle:
         batch, n = ref.shape[0], ref.shape[1]
         precise = n if precise is None else precise
         nnz_a = 3 * n + 7 * (n - 1) + n + 6 * precise + 2 * (n - precise) + 2
-        nnz_p = n + n - 1 + precise + n
+        nnz_p = self._nnz_p(n, precise)
         cons = 4 * n + precise + n + 2
         a_val = np.zeros((batch, nnz_a)); p_val = np.zeros((batch, nnz_p))
         lo = np.zeros((batch, cons)); up = np.zeros((batch, cons))

@@ -45,6 +45,7 @@ namespace pqp {
 // -------------------------------------------------------------------------------------------------------
 struct RefIndex {
     int n, precise;
+    int with_l;      // weight_l != 0: P's diagonal has the l_i columns too (the reference's sparseView drops them only while weight_l is an exact zero, base_solver.cpp:123,145)
     __host__ __device__ int state() const { return 3 * n; }
     __host__ __device__ int control() const { return n - 1; }
     __host__ __device__ int vars() const { return 3 * n + n - 1 + precise + n; }
@@ -57,7 +58,12 @@ struct RefIndex {
         return i < precise ? 4 * n - 1 + 2 * i + which : 4 * n - 1 + 2 * precise + (i - precise);
     }
     __host__ __device__ int nnz_a() const { return 3 * n + 7 * (n - 1) + n + 6 * precise + 2 * (n - precise) + 2; }
-    __host__ __device__ int nnz_p() const { return n + n - 1 + precise + n; }
+    __host__ __device__ int nnz_p() const { return p_states() + n - 1 + precise + n; }
+    // P's diagonal in ascending column order: per waypoint (l_i,) k_i; then u_i; then the slacks
+    __host__ __device__ int p_states() const { return with_l ? 2 * n : n; }
+    __host__ __device__ int p_kappa(int i) const { return with_l ? 2 * i + 1 : i; }
+    __host__ __device__ int p_control(int i) const { return p_states() + i; }
+    __host__ __device__ int p_slack(int i, int which) const { return p_states() + n - 1 + (i < precise ? 2 * i + which : 2 * precise + (i - precise)); }
     // CSC offset of the first entry of column 3i (state column block of waypoint i)
     __host__ __device__ int state_col_offset(int i) const {
         // per waypoint j < n-1: precise -> 5+5+4 = 14 entries, rough -> 4+3+4 = 11
@@ -117,11 +123,12 @@ __global__ void path_pattern_kernel(RefIndex R, int32_t* rows, int32_t* colptr, 
         rows[os + 2 * R.precise + li] = R.rough_idx() + li;
     }
     if (last) colptr[R.vars()] = R.nnz_a();
-    // P diagonal columns (base_solver.cpp:127-143), ascending: k_i, then u_i, then slacks
-    pcols[i] = 3 * i + 2;
-    if (has_next) pcols[n + i] = R.state() + i;
-    if (precise) { pcols[2 * n - 1 + 2 * i] = R.slack_col(i, 0); pcols[2 * n - 1 + 2 * i + 1] = R.slack_col(i, 1); }
-    else pcols[2 * n - 1 + 2 * R.precise + (i - R.precise)] = R.slack_col(i, 0);
+    // P diagonal columns (base_solver.cpp:127-143), ascending: (l_i,) k_i, then u_i, then slacks
+    if (R.with_l) pcols[2 * i] = 3 * i;
+    pcols[R.p_kappa(i)] = 3 * i + 2;
+    if (has_next) pcols[R.p_control(i)] = R.state() + i;
+    if (precise) { pcols[R.p_slack(i, 0)] = R.slack_col(i, 0); pcols[R.p_slack(i, 1)] = R.slack_col(i, 1); }
+    else pcols[R.p_slack(i, 0)] = R.slack_col(i, 0);
 }
 
 // assemble in the reference numbering.  One workgroup per QP; values are staged in LDS in their final
@@ -173,10 +180,11 @@ __global__ void __launch_bounds__(256) path_assemble_kernel(RefIndex R, int batc
             if (precise) { va[os + 2 * i] = 1.0; va[os + 2 * i + 1] = 1.0; }
             else va[os + 2 * R.precise + (i - R.precise)] = 1.0;
             // P diagonal (base_solver.cpp:123-143)
-            vp[i] = prm.weight_kappa;
-            if (has_next) vp[n + i] = prm.weight_dkappa;
-            if (precise) { vp[2 * n - 1 + 2 * i] = prm.weight_slack; vp[2 * n - 1 + 2 * i + 1] = prm.weight_slack; }
-            else vp[2 * n - 1 + 2 * R.precise + (i - R.precise)] = prm.weight_slack;
+            if (R.with_l) vp[2 * i] = prm.weight_l;
+            vp[R.p_kappa(i)] = prm.weight_kappa;
+            if (has_next) vp[R.p_control(i)] = prm.weight_dkappa;
+            if (precise) { vp[R.p_slack(i, 0)] = prm.weight_slack; vp[R.p_slack(i, 1)] = prm.weight_slack; }
+            else vp[R.p_slack(i, 0)] = prm.weight_slack;
             // bounds (base_solver.cpp:212-260)
             if (i == 0) {
                 for (int k = 0; k < 3; ++k) { vl[k] = -sc[k]; vu[k] = -sc[k]; }
@@ -431,7 +439,7 @@ int pqp_path_sizes(const pqp_params* params, int n, const double* s, pqp_sizes* 
         while (lo < hi) { const int mid = (lo + hi) / 2; if (s[mid] < params->precise_planning_length) lo = mid + 1; else hi = mid; }
         precise = lo;
     }
-    pqp::RefIndex R{n, precise};
+    pqp::RefIndex R{n, precise, params->weight_l != 0.0};
     out->n = n; out->state = 3 * n; out->control = n - 1; out->precise = precise; out->slack = precise + n;
     out->vars = R.vars(); out->cons = R.cons(); out->nnz_a = R.nnz_a(); out->nnz_p = R.nnz_p();
     return PQP_OK;
@@ -440,7 +448,7 @@ int pqp_path_sizes(const pqp_params* params, int n, const double* s, pqp_sizes* 
 int pqp_path_pattern(pqp_handle* h, int n, int precise, int32_t* rows, int32_t* colptr, int32_t* pcols) {
     if (!h || !rows || !colptr || !pcols || n < 2 || precise < 0 || precise > n)
         return fail(PQP_ERR_INVALID, "pqp_path_pattern: bad argument");
-    pqp::RefIndex R{n, precise};
+    pqp::RefIndex R{n, precise, h->prm.weight_l != 0.0};
     Staging st(h);
     int32_t* d_rows = st.out(rows, R.nnz_a(), 0xff);
     int32_t* d_colptr = st.out(colptr, R.vars() + 1, 0xff);
@@ -462,7 +470,7 @@ int pqp_path_assemble_device(pqp_handle* h, int batch, int n, int precise, const
                              double* upper) {
     if (!assemble_ok(h, batch, n, precise, ref, bounds, scal, a_val, p_val, lower, upper)) return fail(PQP_ERR_INVALID, "pqp_path_assemble: bad argument");
     PQP_HIP(hipSetDevice(h->device));
-    pqp::RefIndex R{n, precise};
+    pqp::RefIndex R{n, precise, h->prm.weight_l != 0.0};
     const size_t lds = ((size_t)R.nnz_a() + R.nnz_p() + 2 * (size_t)R.cons()) * 8;
     const int stage = lds <= 150 * 1024 ? 1 : 0;
     int rc;
@@ -479,7 +487,7 @@ int pqp_path_assemble_device(pqp_handle* h, int batch, int n, int precise, const
 int pqp_path_assemble(pqp_handle* h, int batch, int n, int precise, const double* ref, const double* lin,
                       const double* bounds, const double* scal, double* a_val, double* p_val, double* lower, double* upper) {
     if (!assemble_ok(h, batch, n, precise, ref, bounds, scal, a_val, p_val, lower, upper)) return fail(PQP_ERR_INVALID, "pqp_path_assemble: bad argument");
-    pqp::RefIndex R{n, precise};
+    pqp::RefIndex R{n, precise, h->prm.weight_l != 0.0};
     const size_t bn = (size_t)batch * n;
     Staging st(h);
     const double *d_ref = st.in(ref, bn * 5), *d_lin = st.in(lin, bn * 3), *d_bounds = st.in(bounds, bn * 6), *d_scal = st.in(scal, (size_t)batch * 6);

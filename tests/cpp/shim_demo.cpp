@@ -3,6 +3,7 @@
 // Reads a scenario (n, then n rows "s k heading x y flb fub rlb rub clb cub", then 6 scalars) from stdin, prints the
 // path "x y heading l d_heading k d_k" per line.
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "../../include/pqp_base_solver.hpp"
@@ -39,9 +40,17 @@ int main(int argc, char** argv) {
     solver.setMaxSteeringAngle(sc[5]);
     for (int a = 1; a < argc; ++a) {
         pqp_params p = solver.params();
-        double len = 0.0;
+        double len = 0.0, v = 0.0;
+        char name[64];
         if (std::sscanf(argv[a], "rough=%lf", &len) == 1) {   // FLAGS_rough_constraints_far_away with FLAGS_precise_planning_length = len
             p.rough_constraints_far_away = 1; p.precise_planning_length = len;
+        } else if (std::sscanf(argv[a], "%63[a-z_]=%lf", name, &v) == 2) {   // a car flag: FLAGS_wheel_base and its kin, base_solver.cpp:292's 0.1
+            const struct { const char* name; double pqp_params::*field; } flags[] = {
+                {"front_length", &pqp_params::front_length}, {"rear_length", &pqp_params::rear_length}, {"wheel_base", &pqp_params::wheel_base},
+                {"expected_safety_margin", &pqp_params::expected_safety_margin}, {"min_clearance", &pqp_params::min_clearance}};
+            bool known = false;
+            for (const auto& f : flags) if (std::strcmp(f.name, name) == 0) { p.*f.field = v; known = true; }
+            if (!known) return 2;
         } else {                                           // "polish": the engine's production setting
             p.eps_abs = p.eps_rel = 1e-4; p.polish = 1; p.polish_every = 25; p.adaptive_rho_interval = 25; p.polish_warm_set = 1; p.polish_refine_iter = 3;
         }

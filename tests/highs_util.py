@@ -24,16 +24,26 @@ def qp_point(o, A, lo, up, sz):
     return x
 
 
-def against_highs(ref, lin, bounds, scal, o, prm=None):
+def highs_optimum(ref, lin, bounds, scal, prm=None):
+    """HiGHS's optimum of the reference's QP around `lin`: (x, its output record, the QP)"""
     Pd, A, lo, up, sz = O.assemble_path_qp(ref, lin, bounds, scal, prm)
     A = sp.csr_matrix(A)
     xh, _, _ = H.solve_qp(Pd, np.zeros(sz["vars"]), A, lo, up)
+    return xh, O.unpack_path(xh, ref), (Pd, A, lo, up, sz)
+
+
+def against_highs(ref, lin, bounds, scal, o, prm=None, one_sided=False, l_tol=3e-4, highs=None):
+    """one_sided: the kernel's objective may lie BELOW HiGHS's (its point holds every row to 1e-7, so it is HiGHS that stopped short: 3e-7 relative
+    seen with weight_slack = 25, weight_dkappa = 250), never above it by more than the two-sided test's 1e-7.
+    l_tol: the bound on the lateral offsets, for QPs with weight_l > 0, which have no flat direction (tests/param_cases.py).
+    highs: highs_optimum() of the same QP, where several outputs are pinned to it."""
+    xh, out, (Pd, A, lo, up, sz) = highs or highs_optimum(ref, lin, bounds, scal, prm)
     x = qp_point(o, A, lo, up, sz)
     Ax = A @ x
     assert np.maximum(lo - Ax, Ax - up).max() < 1e-7                                       # the kernel's point holds every row
     f = lambda z: 0.5 * np.sum(Pd * z * z)
-    assert abs(f(x) - f(xh)) < 1e-7 * max(1.0, f(xh)), (f(x), f(xh))                       # and has HiGHS's optimal value
-    out = O.unpack_path(xh, ref)
+    gap = f(x) - f(xh)
+    assert (gap if one_sided else abs(gap)) < 1e-7 * max(1.0, f(xh)), (f(x), f(xh))        # and has HiGHS's optimal value
     d = np.abs(out - o)
     assert d[:, 4:7].max() < 2e-5, d[:, 4:7].max()                                         # heading offset, curvature, curvature rate
-    assert d[:, 3].max() < 3e-4 and d[:, 0:2].max() < 3e-4, d[:, 3].max()                  # lateral offset (and x, y): the flat direction under HiGHS's 1e-7 l^2
+    assert d[:, 3].max() < l_tol and d[:, 0:2].max() < l_tol, d[:, 3].max()                # lateral offset (and x, y): the flat direction under HiGHS's 1e-7 l^2
