@@ -953,6 +953,68 @@ int pqp_sample_trajectory(pqp_handle* h, const pqp_sample_params* prm, int batch
                           const int32_t* stop_before, const double* profile, const double* t0, int m, double* traj, int32_t* m_of,
                           int32_t* flags);
 
+/* ---- sampled trajectories against predicted moving agents -------------------------------------------------------------------------------
+ * pqp_footprint_check tests planned states against what stands still: the distance layer.  What moves - predicted vehicles, pedestrians -
+ * comes as a pose and a size per time step, and pqp_sample_trajectory puts every candidate on those time steps.  This tests every sample of
+ * every trajectory against every predicted agent of the path's scene at the same step: the six-circle footprint of pqp_car_circles against
+ * a rounded oriented rectangle, and says whether a candidate hits one, when, and which.  The reference has no counterpart (it plans one
+ * path against a static map); the footprint is its CarGeometry's six circles placed by local2Global (src/tools/tools.cpp:50-55). */
+#define PQP_AGENT_STRIDE 6         /* x, y, heading, half_length, half_width, radius */
+#define PQP_AGENT_FRAME_STRIDE 8   /* x, y, cos h, sin h, half_length, half_width, radius, reach */
+/* The check has one parameter, so it travels as itself and not in a struct: margin, in m, finite and >= 0 - the distance demanded beyond
+ * touching.  pqp_agents_default_params writes this library's choice of it, 0.0, to *margin (pure host; NULL ignored). */
+void pqp_agents_default_params(double* margin);
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   traj [batch][m][stride]           x, y, heading at offsets 0, 1, 2, stride >= 3; stride = PQP_TRAJ_STRIDE reads pqp_sample_trajectory's
+ *                                     traj in place
+ *   m_of [batch] or NULL              the samples to check: count = clamp(m_of, 0, m); NULL: all m (pass NULL with hold_last to keep
+ *                                     checking the parked car)
+ *   agents [n_scenes][a_max][m][PQP_AGENT_STRIDE]   an agent's pose and size at the same m time steps.  half_length < 0 or half_width < 0:
+ *                                     the agent is absent at that step - tested first, the rest of the row is not read.  radius rounds the
+ *                                     rectangle; a disc is half_length = half_width = 0 with a radius.  a_max = 0 is allowed (agents and
+ *                                     frames may then be NULL)
+ *   a_of [n_scenes] or NULL           agents per scene: A = clamp(a_of, 0, a_max); NULL: all a_max
+ *   scene_of [batch] or NULL (all 0)  the agent set a path is checked against (map_of's role); the host form refuses values outside
+ *                                     [0, n_scenes), the device form clamps them
+ *   car                               the footprint: the six circles (c_j, r_j) of pqp_car_circles
+ *   margin                            see above; by value in both forms
+ *   frames [n_scenes][a_max][m][PQP_AGENT_FRAME_STRIDE]   (_device form only) a workspace of the caller's, fully written by the first launch
+ * Two launches on the handle's stream.  The first turns every agent row into a frame row: x, y, half_length, half_width, radius bit for
+ * bit, (sin, cos) = sincos(heading) taken once, reach = sqrt(hl*hl + hw*hw) + radius.  An absent row becomes eight zeros with reach = -1;
+ * a present row with a value that is not finite or with a negative radius is "bad": eight zeros with reach = NaN.
+ * The second is the test.  The definition, in fp64, every product and sum rounded on its own (no contraction), in this order, for sample
+ * k < count, agent a < A and circle j < 6:
+ *   (sh, ch) = sincos(h_k);  gx = cx_j*ch - cy_j*sh + x_k;  gy = cx_j*sh + cy_j*ch + y_k      (pqp_footprint_check's expression)
+ *   dx = gx - ax;  dy = gy - ay;  u = dx*c + dy*s;  w = dy*c - dx*s
+ *   ex = fabs(u) - hl;  ey = fabs(w) - hw;  ox = fmax(ex, 0);  oy = fmax(ey, 0)
+ *   d = sqrt(ox*ox + oy*oy) + fmin(fmax(ex, ey), 0) - radius;  clear_j = d - r_j
+ *   clear(k, a) = min_j clear_j;  hit(k, a) = clear(k, a) < margin     (strict: touching at exactly `margin` is no hit; min as fmin)
+ * An absent agent is skipped.  A bad agent hits every checked sample of its scene's paths at that step, with clear = -inf.  A sample
+ * whose x, y or heading is not finite is a hit with hit_agent = -1 and clear = -inf whatever the agents are, as pqp_footprint_check
+ * takes a state that is not finite for a collision.
+ * Outputs, fully overwritten:
+ *   first_hit [batch]                 the first hit sample below count, count when there is none (the convention of first_collision); a
+ *                                     path with count = 0 therefore reports 0, as pqp_footprint_check does
+ *   hit_agent [batch]                 the lowest agent index that hits at sample first_hit; -1 when there is no hit or the hit is the ego
+ *                                     sample itself
+ *   clearance [batch][m] or NULL      min_a clear(k, a) for k < count, +inf where the scene has no present agent at that step, 0 at
+ *                                     k >= count
+ * With clearance = NULL the test skips agents whose centre is too far from the footprint's bounding centre to come within `margin`, and
+ * stops behind the 64 samples that hold the first hit; neither changes an output while the squares of the coordinates are finite (beyond
+ * about 1e154 the exact test's products overflow to NaN and the two forms may differ).  The results depend on the path's own rows, its scene
+ * and the parameters alone - not on the batch, the position in it or which form was called; no atomics, the same answer every run.
+ * The _device form is asynchronous on the handle's stream and allocates nothing; m, a_max and n_scenes are held to n_scenes * a_max * m
+ * <= 2^38 rows alone.  The host form stages
+ * frames itself, copies in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the outputs
+ * untouched, for a null pointer that is not optional, batch < 1, m < 1, stride < 3, n_scenes < 1, a_max < 0, n_scenes * a_max * m > 2^38, a margin that is not finite
+ * or is negative, or a car geometry that is not finite. */
+int pqp_agents_check_device(pqp_handle* h, double margin, const pqp_car_geometry* car, int batch, int m, int stride,
+                            const double* traj, const int32_t* m_of, int n_scenes, int a_max, const double* agents, const int32_t* a_of,
+                            const int32_t* scene_of, double* frames, int32_t* first_hit, int32_t* hit_agent, double* clearance);
+int pqp_agents_check(pqp_handle* h, double margin, const pqp_car_geometry* car, int batch, int m, int stride,
+                     const double* traj, const int32_t* m_of, int n_scenes, int a_max, const double* agents, const int32_t* a_of,
+                     const int32_t* scene_of, int32_t* first_hit, int32_t* hit_agent, double* clearance);
+
 #ifdef __cplusplus
 }
 #endif

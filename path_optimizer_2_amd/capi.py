@@ -163,6 +163,26 @@ def sample_default_params(lib=None, **over):
     return _defaults(lib, PqpSampleParams, "pqp_sample_default_params", over)
 
 
+class AgentsParams:
+    """what pqp_agents_check takes besides its arrays and the car: the margin alone, which the C ABI therefore passes as a double and not
+    in a struct.  Here it keeps the shape of the other parameter sets (agents_default_params(margin=...), prm=, agents_params=)."""
+    __slots__ = ("margin",)
+
+    def __init__(self, margin):
+        self.margin = float(margin)
+
+
+def agents_default_params(lib=None, **over):
+    """pqp_agents_default_params: margin 0 m (touching is no hit) - this library's choice - with `over` applied."""
+    lib = lib or load_library()
+    margin = C.c_double(-1.0)
+    lib.pqp_agents_default_params(C.byref(margin))
+    p = AgentsParams(margin.value)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
 def car_circles(car=None, lib=None):
     """pqp_car_circles (pure host): [7][3] x, y, r in the vehicle frame of rr, rl, fr, fl, fm, rm and the bounding circle."""
     lib = lib or load_library()
@@ -344,8 +364,8 @@ class Handle:
         return _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", over)
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
-                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, sample=None, samples=None,
-                      t0=None, speed=None, v_start=None, v_end=None):
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, agents=None, agents_of=None,
+                      scene_of=None, agents_params=None, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -365,23 +385,32 @@ class Handle:
         with check_footprint is refused.  The winners' profile crosses to the host with winners_only too.
         sample: PqpSampleParams (needs speed) - pqp_sample_trajectory_device behind the speed profile on the same stream, on the arrays it ran
         on: `samples` rows per path at t0 + k dt (t0 [B], or [groups] with select; None: all 0); adds traj [..][samples][8] = x, y, heading,
-        k, s, v, a, t, traj_n (the samples on the path) and traj_flags.  The winners' samples cross to the host with winners_only too."""
+        k, s, v, a, t, traj_n (the samples on the path) and traj_flags.  The winners' samples cross to the host with winners_only too.
+        agents: [n_scenes][a_max][samples][6] = x, y, heading, half_length, half_width, radius of predicted agents at the samples' time steps
+        (needs sample) - pqp_agents_check_device behind the sampler on the same stream, on its traj and traj_n, or on all `samples` rows
+        with sample.hold_last (the parked car is checked too); agents_of [n_scenes]: agents per scene (None: all), scene_of: the scene of
+        every row the sampler ran on ([B], or [groups] with select; None: scene 0), agents_params: AgentsParams (None: agents_default_params()),
+        car: the footprint.  Adds first_hit, hit_agent and agent_clearance [..][samples]."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
-                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed))
+                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
+                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
+                              winners_only=False, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
+                              t0=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
-        select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0: as for optimize_path)."""
+        select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
+        agents_params: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
-                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed))
+                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
+                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select))
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -406,6 +435,28 @@ class Handle:
             raise ValueError("sample needs samples >= 1")
         return (sample, int(samples), None if t0 is None else np.ascontiguousarray(t0, dtype=np.float64).ravel())
 
+    def _agents(self, agents, agents_of, scene_of, agents_params, sample, samples, car, batch, select):
+        if agents is None:
+            if agents_of is not None or scene_of is not None or agents_params is not None:
+                raise ValueError("agents_of / scene_of / agents_params need agents=")
+            return None
+        if sample is None:
+            raise ValueError("agents needs sample=PqpSampleParams: the agents are given at the samples' time steps")
+        agents = np.ascontiguousarray(agents, dtype=np.float64)
+        if agents.ndim != 4 or agents.shape[0] < 1 or agents.shape[2] != int(samples) or agents.shape[3] != AGENT_STRIDE:
+            raise ValueError(f"agents must be [n_scenes >= 1][a_max][{int(samples)}][{AGENT_STRIDE}], not {agents.shape}")
+        n_scenes = agents.shape[0]
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).ravel()
+        agents_of, scene_of = i32(agents_of), i32(scene_of)
+        if agents_of is not None and agents_of.size != n_scenes:
+            raise ValueError(f"agents_of must have one entry per scene ({n_scenes})")
+        if scene_of is not None and ((scene_of < 0) | (scene_of >= n_scenes)).any():
+            raise ValueError(f"scene_of outside [0, {n_scenes})")
+        rows = batch if select is None else np.size(select) - 1          # the rows the sampler runs on
+        if scene_of is not None and scene_of.size != rows:
+            raise ValueError(f"scene_of must have one entry per {'candidate' if select is None else 'group'} ({rows})")
+        return (agents, agents_of, scene_of, agents_params if agents_params is not None else agents_default_params(self.lib), car)
+
     def _selection(self, select, select_params, winners_only):
         if select is None:
             if winners_only or select_params is not None:
@@ -415,11 +466,12 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None):
+               selection=None, speed=None, sampling=None, moving=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
-        of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None"""
+        of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None; moving:
+        (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -456,6 +508,14 @@ class Handle:
             traj = torch.zeros((rows, m, TRAJ_STRIDE), dtype=torch.float64, device=dev)
             traj_n = torch.zeros(rows, dtype=torch.int32, device=dev)
             traj_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
+        if moving is not None:
+            ag, ag_of, scene_of, ag_prm, ag_car = moving
+            ag_car = ag_car if ag_car is not None else car_default_geometry(self.lib)
+            d_ag, d_ag_of, d_scene = t(ag, np.float64), t(ag_of, np.int32), t(scene_of, np.int32)
+            ag_frames = torch.zeros(ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
+            first_hit = torch.zeros(rows, dtype=torch.int32, device=dev)
+            hit_agent = torch.zeros(rows, dtype=torch.int32, device=dev)
+            agent_clearance = torch.zeros((rows, m), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -490,6 +550,11 @@ class Handle:
                 self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, out, ints[0],
                                                                   first if footprint is not None else None, profile, d_t0, m, traj,
                                                                   traj_n, traj_flags))
+        if moving is not None:              # behind the sampler, on its samples: all of them with hold_last (the parked car), else those on the path
+            self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, m, TRAJ_STRIDE, traj,
+                                                         None if sa_prm.hold_last else traj_n, ag.shape[0], ag.shape[1],
+                                                         d_ag if ag.size else None, d_ag_of, d_scene, ag_frames if ag.size else None,
+                                                         first_hit, hit_agent, agent_clearance))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -509,6 +574,8 @@ class Handle:
             res.update(profile=host(profile), speed_flags=host(speed_flags))
         if sampling is not None:
             res.update(traj=host(traj), traj_n=host(traj_n), traj_flags=host(traj_flags))
+        if moving is not None:
+            res.update(first_hit=host(first_hit), hit_agent=host(hit_agent), agent_clearance=host(agent_clearance))
         return res
 
     def distance_layer(self, grid, geom):
@@ -605,6 +672,35 @@ class Handle:
         self._check(self.lib.pqp_sample_trajectory(self._h, C.byref(prm), B, n, stride, paths, no, sb, profile, tt, m,
                                                    traj, m_of, flags))
         return traj, m_of, flags
+
+    def agents_check(self, traj, agents, m_of=None, a_of=None, scene_of=None, car=None, prm=None, clearance=False):
+        """pqp_agents_check (host arrays): traj [B][m][stride >= 3] (x, y, heading first; sample_trajectory's traj as it is), agents
+        [n_scenes][a_max][m][6] = x, y, heading, half_length, half_width, radius at the same m time steps (half_length or half_width < 0:
+        absent at that step), and optionally m_of [B] (the samples to check; None: all), a_of [n_scenes] (agents per scene), scene_of [B]
+        (None: scene 0); car = PqpCarGeometry (None: the reference's), prm = AgentsParams (None: agents_default_params()).  Returns
+        dict(first_hit [B], hit_agent [B][, clearance [B][m]])."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        B, m, stride = traj.shape
+        agents = np.ascontiguousarray(agents, dtype=np.float64)
+        if agents.ndim != 4 or agents.shape[2:] != (m, AGENT_STRIDE):
+            raise ValueError(f"agents_check: agents must be [n_scenes][a_max][{m}][{AGENT_STRIDE}], not {agents.shape}")
+        n_scenes, a_max = agents.shape[:2]
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        mo, ao, so = i32(m_of), i32(a_of), i32(scene_of)
+        for name, a, size in (("m_of", mo, B), ("a_of", ao, n_scenes), ("scene_of", so, B)):
+            if a is not None and a.size != size:
+                raise ValueError(f"agents_check: {name} must have {size} entries, not {a.size}")
+        car = car if car is not None else car_default_geometry(self.lib)
+        prm = prm if prm is not None else agents_default_params(self.lib)
+        first = np.zeros(B, dtype=np.int32)
+        who = np.zeros(B, dtype=np.int32)
+        cl = np.zeros((B, m)) if clearance else None
+        self._check(self.lib.pqp_agents_check(self._h, float(prm.margin), C.byref(car), B, m, stride, traj, mo, n_scenes, a_max,
+                                              agents if agents.size else None, ao, so, first, who, cl))
+        res = dict(first_hit=first, hit_agent=who)
+        if clearance:
+            res["clearance"] = cl
+        return res
 
     def corridor_params(self, **over):
         return _defaults(self.lib, PqpCorridorParams, "pqp_corridor_default_params", over)

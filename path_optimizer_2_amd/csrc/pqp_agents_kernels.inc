@@ -1,0 +1,140 @@
+// pqp_agents_kernels.inc — included by pqp_maps.hip after pqp_sample_kernels.inc.  Sampled trajectories against predicted moving agents
+// (pqp_agents_check): every sample of every trajectory against every agent of the path's scene at the same time step, the six-circle
+// footprint (pqp_car_circles, placed as pqp_footprint_kernels.inc places it) against a rounded oriented rectangle.  The reference has
+// no counterpart: it plans one path against a static map.  include/pqp.h states the definition operation by operation.
+//
+// agent_frames_kernel: one lane per (scene, agent, step).  The agent's sincos is taken here, once, so the batch x agents x steps tests
+//   never take it again; reach = the circumradius of the rounded rectangle, whose sign and NaN also say "absent" and "bad".
+// agents_check_kernel<CLEARANCE>: one wavefront per path, four per workgroup, one sample per lane in tiles of 64, no LDS, no atomics.
+//   The loop over agents is wave-uniform; lane k reads frame row [a][k], so a wavefront's 64 rows are one contiguous 4 KB, and a scene's
+//   table is read by every path of the scene: it stays in L2.  first_hit is a ballot and a count of trailing zeros, hit_agent is read from
+//   the hit lane.  Without a clearance to write (CLEARANCE = false) a lane leaves out the agents it cannot come within the margin of - by
+//   the centres' distance against Rb + reach + margin + a slack that is orders above the rounding of the exact test - and the agents behind
+//   its first hit, and the wavefront stops behind the tile of its first hit: none of that changes an output.
+
+namespace pqp {
+
+constexpr int kAgentsThreads = 256;
+
+struct AgentsArgs {
+    int batch, m, stride, n_scenes, a_max;
+    const double* traj;              // [batch][m][stride]  x, y, heading at offsets 0, 1, 2
+    const int32_t* m_of;             // [batch] or nullptr: all m
+    const double* agents;            // [n_scenes][a_max][m][PQP_AGENT_STRIDE]
+    const int32_t* a_of;             // [n_scenes] or nullptr: all a_max
+    const int32_t* scene_of;         // [batch] or nullptr: scene 0
+    double margin;
+    double cx[7], cy[7], cr[7];      // vehicle frame: rr, rl, fr, fl, fm, rm, then the bounding circle (pqp_car_circles)
+    double rb;                       // max_j (|c_j - c_6| + r_j): the six circles lie within rb of the bounding circle's centre
+    double* frames;                  // [n_scenes][a_max][m][PQP_AGENT_FRAME_STRIDE]
+    int32_t* first_hit;              // [batch]
+    int32_t* hit_agent;              // [batch]
+    double* clearance;               // [batch][m] or nullptr
+};
+
+// the slack of the broad phase: 2^-10 m and 2^-30 of the coordinates' size, against a rounding of the exact test near 2^-50 of it
+constexpr double kAgentsSlack = 0x1p-10, kAgentsSlackRel = 0x1p-30;
+
+__global__ void __launch_bounds__(kAgentsThreads) agent_frames_kernel(const AgentsArgs a) {
+#pragma clang fp contract(off)
+    const long long rows = (long long)a.n_scenes * a.a_max * a.m;
+    const long long i = (long long)blockIdx.x * kAgentsThreads + threadIdx.x;
+    if (i >= rows) return;
+    const double* __restrict__ r = a.agents + (size_t)i * PQP_AGENT_STRIDE;
+    double* __restrict__ o = a.frames + (size_t)i * PQP_AGENT_FRAME_STRIDE;
+    double f[PQP_AGENT_FRAME_STRIDE] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -1.0};
+    const double hl = r[3], hw = r[4];
+    if (!(hl < 0.0 || hw < 0.0)) {                                                        // present: the rest of the row is read
+        const double x = r[0], y = r[1], heading = r[2], radius = r[5];
+        if (isfinite(x) && isfinite(y) && isfinite(heading) && isfinite(hl) && isfinite(hw) && isfinite(radius) && radius >= 0.0) {
+            double sh, ch;
+            sincos(heading, &sh, &ch);
+            f[0] = x; f[1] = y; f[2] = ch; f[3] = sh; f[4] = hl; f[5] = hw; f[6] = radius;
+            f[7] = sqrt(hl * hl + hw * hw) + radius;
+        } else {
+            f[7] = NAN;                                                                   // bad
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < PQP_AGENT_FRAME_STRIDE; ++q) o[q] = f[q];
+}
+
+template <bool CLEARANCE>
+__global__ void __launch_bounds__(kAgentsThreads) agents_check_kernel(const AgentsArgs a) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long long b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kAgentsThreads / 64) + (threadIdx.x >> 6)));
+    if (b >= a.batch) return;
+    const int count = a.m_of ? min(max(a.m_of[b], 0), a.m) : a.m;
+    const int scene = a.scene_of ? min(max(a.scene_of[b], 0), a.n_scenes - 1) : 0;
+    const int A = a.a_of ? min(max(a.a_of[scene], 0), a.a_max) : a.a_max;
+    const double* __restrict__ traj = a.traj + (size_t)b * a.m * a.stride;
+    const double* __restrict__ frames = a.frames + (size_t)scene * a.a_max * a.m * PQP_AGENT_FRAME_STRIDE;
+    const double margin = a.margin;
+    int first = count, who = -1;                                                          // wave-uniform
+    const int k_end = CLEARANCE ? a.m : count;
+    for (int k0 = 0; k0 < k_end; k0 += 64) {
+        const int k = k0 + lane;
+        const bool checked = k < count;
+        double clear = INFINITY;
+        int hit_a = -1;
+        bool hit = false;
+        if (checked) {
+            const double* s = traj + (size_t)k * a.stride;
+            const double x = s[0], y = s[1], heading = s[2];
+            if (isfinite(x) && isfinite(y) && isfinite(heading)) {
+                double sh, ch;
+                sincos(heading, &sh, &ch);
+                // local2Global(state, circle): x cos - y sin + ref.x, x sin + y cos + ref.y  (tools.cpp:51-52), as footprint_check_kernel
+                double gx[6], gy[6];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) {
+                    gx[j] = a.cx[j] * ch - a.cy[j] * sh + x;
+                    gy[j] = a.cx[j] * sh + a.cy[j] * ch + y;
+                }
+                const double bx = a.cx[6] * ch - a.cy[6] * sh + x, by = a.cx[6] * sh + a.cy[6] * ch + y;
+                const double* f = frames + (size_t)k * PQP_AGENT_FRAME_STRIDE;
+                for (int ag = 0; ag < A; ++ag, f += (size_t)a.m * PQP_AGENT_FRAME_STRIDE) {
+                    if (!CLEARANCE && hit) break;                                         // the lowest hitting agent is found
+                    const double ax = f[0], ay = f[1], reach = f[7];
+                    if (reach < 0.0) continue;                                            // absent
+                    double c_ka = -INFINITY;                                              // bad: reach is NaN
+                    if (reach == reach) {
+                        if (!CLEARANCE) {
+                            const double ux = bx - ax, uy = by - ay;
+                            const double far = a.rb + reach + margin + kAgentsSlack + kAgentsSlackRel * (fabs(bx) + fabs(by) + fabs(ax) + fabs(ay));
+                            if (ux * ux + uy * uy > far * far) continue;                  // clear(k, a) >= margin + the slack: no hit
+                        }
+                        const double c = f[2], sn = f[3], hl = f[4], hw = f[5], radius = f[6];
+                        c_ka = INFINITY;
+#pragma unroll
+                        for (int j = 0; j < 6; ++j) {
+                            const double dx = gx[j] - ax, dy = gy[j] - ay;
+                            const double u = dx * c + dy * sn, w = dy * c - dx * sn;
+                            const double ex = fabs(u) - hl, ey = fabs(w) - hw;
+                            const double ox = fmax(ex, 0.0), oy = fmax(ey, 0.0);
+                            const double d = sqrt(ox * ox + oy * oy) + fmin(fmax(ex, ey), 0.0) - radius;
+                            c_ka = fmin(c_ka, d - a.cr[j]);
+                        }
+                    }
+                    clear = fmin(clear, c_ka);
+                    if (c_ka < margin && !hit) { hit = true; hit_a = ag; }
+                }
+            } else {
+                clear = -INFINITY;                                                        // the ego sample itself: hit_agent -1
+                hit = true;
+            }
+        }
+        if (CLEARANCE && k < a.m) a.clearance[(size_t)b * a.m + k] = checked ? clear : 0.0;
+        const uint64_t hits = __ballot(hit);
+        if (hits && first == count) {
+            const int at = __builtin_ctzll(hits);
+            first = k0 + at;
+            who = __builtin_amdgcn_readlane(hit_a, at);
+            if (!CLEARANCE) break;
+        }
+    }
+    if (lane == 0) { a.first_hit[b] = first; a.hit_agent[b] = who; }
+}
+
+}  // namespace pqp

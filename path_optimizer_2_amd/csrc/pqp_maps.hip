@@ -1,7 +1,8 @@
 // pqp_maps.hip — the entry points of include/pqp.h around the obstacle distance map and the planned paths: the distance layer from an
 // occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
 // group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc), samples of those trajectories on a time grid
-// (pqp_sample_kernels.inc).  Their kernels, launchers and entry points.
+// (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc).  Their kernels, launchers and entry
+// points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +30,7 @@ using namespace pqp_internal;
 #include "pqp_select_kernels.inc"
 #include "pqp_speed_kernels.inc"
 #include "pqp_sample_kernels.inc"
+#include "pqp_agents_kernels.inc"
 
 extern "C" {
 
@@ -334,6 +336,80 @@ int pqp_sample_trajectory(pqp_handle* h, const pqp_sample_params* prm, int batch
     int32_t* d_flags = st.out(flags, batch);
     return st.run([&]() -> int {
         return pqp_sample_trajectory_device(h, prm, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, d_t0, m, d_traj, d_m_of, d_flags);
+    });
+}
+
+// ---- sampled trajectories against predicted moving agents -------------------------------------------------------------------------------------
+void pqp_agents_default_params(double* margin) {
+    if (!margin) return;
+    *margin = 0.0;                  // touching is no hit; this library's choice, the reference has no moving obstacles
+}
+
+static const char* const kAgentsRefusal =
+    "pqp_agents_check: bad argument (batch >= 1; m >= 1; stride >= 3; n_scenes >= 1; a_max >= 0; n_scenes * a_max * m <= 2^38; margin finite and >= 0; "
+    "a finite car geometry)";
+
+static bool agents_ok(pqp_handle* h, double margin, const pqp_car_geometry* car, int batch, int m, int stride, const double* traj,
+                      int n_scenes, int a_max, const double* agents, const int32_t* first_hit, const int32_t* hit_agent) {
+    // (the frames' launch is one block per 256 rows in x: 2^38 rows are 2^30 blocks, and 16 TiB of frames)
+    return h && traj && first_hit && hit_agent && batch >= 1 && m >= 1 && stride >= 3 && n_scenes >= 1 && a_max >= 0 &&
+           (long long)n_scenes * a_max <= (1ll << 38) / m && (agents || a_max == 0) && std::isfinite(margin) && margin >= 0.0 && car_ok(car);
+}
+
+int pqp_agents_check_device(pqp_handle* h, double margin, const pqp_car_geometry* car, int batch, int m, int stride,
+                            const double* traj, const int32_t* m_of, int n_scenes, int a_max, const double* agents, const int32_t* a_of,
+                            const int32_t* scene_of, double* frames, int32_t* first_hit, int32_t* hit_agent, double* clearance) {
+    if (!agents_ok(h, margin, car, batch, m, stride, traj, n_scenes, a_max, agents, first_hit, hit_agent) || (!frames && a_max > 0))
+        return fail(PQP_ERR_INVALID, kAgentsRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    double circles[7][3];
+    int rc;
+    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
+    pqp::AgentsArgs a;
+    a.batch = batch; a.m = m; a.stride = stride; a.n_scenes = n_scenes; a.a_max = a_max; a.traj = traj; a.m_of = m_of; a.agents = agents;
+    a.a_of = a_of; a.scene_of = scene_of; a.margin = margin; a.frames = frames; a.first_hit = first_hit; a.hit_agent = hit_agent;
+    a.clearance = clearance;
+    a.rb = 0.0;
+    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
+    // the reference's own bounding circle (circles[6][2]) does not contain the corner circles: the broad phase takes the radius that does
+    for (int k = 0; k < 6; ++k) a.rb = std::max(a.rb, std::hypot(a.cx[k] - a.cx[6], a.cy[k] - a.cy[6]) + a.cr[k]);
+    const long long rows = (long long)n_scenes * a_max * m;
+    constexpr int per_block = pqp::kAgentsThreads / 64;
+    return h->launch_timed([&]() -> int {
+        if (rows > 0) {
+            hipLaunchKernelGGL(pqp::agent_frames_kernel, dim3((unsigned)((rows + pqp::kAgentsThreads - 1) / pqp::kAgentsThreads)),
+                               dim3(pqp::kAgentsThreads), 0, h->stream, a);
+            PQP_HIP(hipGetLastError());
+        }
+        const dim3 grid((unsigned)(((long long)batch + per_block - 1) / per_block));
+        if (clearance) hipLaunchKernelGGL(pqp::agents_check_kernel<true>, grid, dim3(pqp::kAgentsThreads), 0, h->stream, a);
+        else hipLaunchKernelGGL(pqp::agents_check_kernel<false>, grid, dim3(pqp::kAgentsThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_agents_check(pqp_handle* h, double margin, const pqp_car_geometry* car, int batch, int m, int stride,
+                     const double* traj, const int32_t* m_of, int n_scenes, int a_max, const double* agents, const int32_t* a_of,
+                     const int32_t* scene_of, int32_t* first_hit, int32_t* hit_agent, double* clearance) {
+    if (!agents_ok(h, margin, car, batch, m, stride, traj, n_scenes, a_max, agents, first_hit, hit_agent)) return fail(PQP_ERR_INVALID, kAgentsRefusal);
+    if (scene_of)
+        for (int b = 0; b < batch; ++b)
+            if (scene_of[b] < 0 || scene_of[b] >= n_scenes) return fail(PQP_ERR_INVALID, "pqp_agents_check: scene_of outside [0, n_scenes)");
+    const size_t bm = (size_t)batch * m, rows = (size_t)n_scenes * a_max * m;
+    Staging st(h);
+    const double* d_traj = st.in(traj, bm * stride);
+    const int32_t* d_m_of = st.in(m_of, batch);
+    const double* d_agents = rows ? st.in(agents, rows * PQP_AGENT_STRIDE) : nullptr;
+    const int32_t* d_a_of = st.in(a_of, n_scenes);
+    const int32_t* d_scene_of = st.in(scene_of, batch);
+    double* d_frames = rows ? st.out((double*)nullptr, rows * PQP_AGENT_FRAME_STRIDE) : nullptr;
+    int32_t* d_first = st.out(first_hit, batch);
+    int32_t* d_who = st.out(hit_agent, batch);
+    double* d_clear = clearance ? st.out(clearance, bm) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_agents_check_device(h, margin, car, batch, m, stride, d_traj, d_m_of, n_scenes, a_max, d_agents, d_a_of, d_scene_of, d_frames,
+                                       d_first, d_who, d_clear);
     });
 }
 
