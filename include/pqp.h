@@ -607,14 +607,26 @@ int pqp_dp_corridor(pqp_handle* h, int batch, int m, int max_layers, const doubl
  *   h  : the handle whose parameters the path QP uses (pqp_production_params or the reference's pqp_default_params);
  *   hs : the handle the two smoother QPs run on - the reference solves them at OSQP's default eps 1e-3 (tension_smoother_2.cpp:32-36),
  *        i.e. pqp_default_params with eps_abs = eps_rel = 1e-3 - or NULL: h's own parameters.  The two handles must live on the same device (PQP_ERR_INVALID otherwise); they are ordered by events of the chain's own (pqp_mark's slots stay the caller's).
- *   points [batch][p_max][2], n_points [batch]  PathOptimizer::solve's reference_points (fewer than 4: "Few reference points")
- *   start, target [batch][3]                    x, y, heading of the vehicle's start and target state (the PathOptimizer constructor)
+ *   points [batch][p_max][2], n_points [batch]  PathOptimizer::solve's reference_points (fewer than 4, zero and negative counts included:
+ *                                               "Few reference points", PQP_CHAIN_FEW_POINTS; so is every other count no raw line can be
+ *                                               built from, see pqp_chain_stage)
+ *   start, target [batch][3]                   x, y, heading of the vehicle's start and target state (the PathOptimizer constructor)
  *   start_k [batch] or NULL                     curvature of the start state (NULL: 0, State's default)
  *   dist / map_of / geom                        the obstacle distance layer(s), as for pqp_corridor_bounds
  *   out [batch][n_max][7], n_out [batch]        the path (the SlState fields getOptimizedPath fills) and its waypoint count
  *   status [batch]                              pqp_status of the path QP (PQP_STATUS_UNSOLVED when the scenario never got there)
  *   stage [batch] or NULL                       where a scenario stopped: the reference's `return false` sites
- *   iters [batch] or NULL                       ADMM iterations of the path QP */
+ *   iters [batch] or NULL                       ADMM iterations of the path QP
+ * A scenario stops at the first of the stages below that applies to it, in the order of the steps; the others of its batch are not touched
+ * by it.  A stopped scenario has n_out = 0 and status = PQP_STATUS_UNSOLVED (at PQP_CHAIN_PATH_QP_FAILED: the path QP's status).  Its
+ * rows out[b] and its iters[b] are unspecified: the launches behind the stop still run for it, on counts clamped into the capacities,
+ * and may write any of out[b]'s n_max rows (never anything outside out[b]); a caller reads out[b] up to n_out[b] only.
+ * Which inputs end at PQP_CHAIN_FEW_POINTS - every scenario no raw line can be built from, whatever an earlier call left in the handle:
+ *   n_points below 4 (the reference's test), n_points above p_max (points[b] holds no such polygon; it is not read), and n_points of
+ *   4 or 5 on a polygon whose mean spacing does not ask for a B-spline of a degree below n_points (at most 5 m: degree 5; at most 10 m:
+ *   degree 4, so 4 points need more than 10 m) - tinyspline refuses such a spline and the reference throws (pqp_bspline_resample: count 0).
+ * A line too short for the smoother QP - fewer than 3 of the 1 m samples (TENSION: 4), i.e. a raw line of less than a metre (two) - ends
+ * at PQP_CHAIN_CAPACITY, as a line with more samples than sample_max does: the count does not fit what the step can take. */
 typedef enum pqp_chain_stage {
     PQP_CHAIN_OK = 0,
     PQP_CHAIN_FEW_POINTS = 1,            /* reference_path_smoother.cpp:33-36 */

@@ -81,6 +81,7 @@ __global__ void chain_status_kernel(const ChainStatusArgs a) {
     if (b >= a.batch) return;
     int stage = PQP_CHAIN_OK;
     if (a.n_points[b] < 4) stage = PQP_CHAIN_FEW_POINTS;                                               // reference_path_smoother.cpp:33-36
+    else if (a.raw_count[b] < 1) stage = PQP_CHAIN_FEW_POINTS;                                         // no raw line: more points than p_max, or not more than the B-spline's degree (pqp.h)
     else if (a.raw_count[b] > a.raw_max || a.sample_count[b] > a.sample_max || a.sample_count[b] < a.sample_min) stage = PQP_CHAIN_CAPACITY;
     else if (a.sm_status[b] != PQP_STATUS_SOLVED) stage = PQP_CHAIN_SMOOTHER_FAILED;                   // "Tension smoother failed!"
     else if (a.layer_count[b] < 0) stage = PQP_CHAIN_CAPACITY;
@@ -137,12 +138,17 @@ __global__ void clearance_kernel(int batch, int n, const int32_t* __restrict__ n
 }
 
 // counts clamped into what the next step can take (a scenario that overflowed a capacity is flagged by chain_status_kernel and must
-// not make the next kernel read beyond its arrays)
-__global__ void chain_clamp_kernel(int batch, const int32_t* __restrict__ in, int lo, int hi, int32_t* __restrict__ out) {
+// not make the next kernel read beyond its arrays).  With x / y / s (the raw line's lists, [batch][stride]): a scenario without a line
+// (count 0: the step wrote none of its rows) gets the point (0, 0) at abscissa 0 as its first row - what the degenerate branch of the
+// spline fit and gather_last_kernel read for it - so that the steps behind it run on a line of length 0 and not on what an earlier
+// call left in the workspace
+__global__ void chain_clamp_kernel(int batch, const int32_t* __restrict__ in, int lo, int hi, int32_t* __restrict__ out, int stride,
+                                   double* __restrict__ x, double* __restrict__ y, double* __restrict__ s) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     const int v = in[b];
     out[b] = v < lo ? lo : (v > hi ? hi : v);
+    if (x && v < 1) { x[(size_t)b * stride] = 0.0; y[(size_t)b * stride] = 0.0; s[(size_t)b * stride] = 0.0; }
 }
 
 // dst[b] = src[b][count[b] - 1] + add: the length of a line from its abscissa list (the hand-over between the chain's steps)
@@ -209,8 +215,8 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
     if ((rc = h->chain.d.ensure(need.doubles * 8)) || (rc = h->chain.i.ensure(need.ints * 4))) return rc;
     carve(w, dims, (size_t)batch, h->chain.d.as<double>(), h->chain.i.as<int32_t>());
     const dim3 gb((batch + 255) / 256), tb(256);
-    auto clamp = [&](const int32_t* in, int lo, int hi, int32_t* o) {
-        hipLaunchKernelGGL(pqp::chain_clamp_kernel, gb, tb, 0, h->stream, batch, in, lo, hi, o);
+    auto clamp = [&](const int32_t* in, int lo, int hi, int32_t* o, double* x = nullptr, double* y = nullptr, double* s = nullptr) {
+        hipLaunchKernelGGL(pqp::chain_clamp_kernel, gb, tb, 0, h->stream, batch, in, lo, hi, o, hi, x, y, s);
     };
     auto last = [&](int stride, const int32_t* count, const double* src, double add, double* dst) {
         hipLaunchKernelGGL(pqp::gather_last_kernel, gb, tb, 0, h->stream, batch, stride, count, src, add, dst);
@@ -218,7 +224,7 @@ static int chain_body(pqp_handle* h, pqp_handle* hs, const pqp_chain_config& cfg
     const bool two = hs != h;
     // ---- reference line smoothing (ReferencePathSmoother::solve) -------------------------------------------------------------------
     if ((rc = pqp_bspline_resample_device(h, batch, p_max, R, points, n_points, w.rx, w.ry, w.rs, w.raw_count))) return rc;
-    clamp(w.raw_count, 0, R, w.raw_fit);
+    clamp(w.raw_count, 0, R, w.raw_fit, w.rx, w.ry, w.rs);
     if ((rc = pqp_spline_fit_var_device(h, batch, R, w.raw_fit, w.rs, w.rx, w.ry, w.raw_tab, w.raw_ext))) return rc;
     last(R, w.raw_fit, w.rs, 0.0, w.raw_len);
     if ((rc = pqp_segment_raw_reference_device(h, batch, S, R, w.raw_tab, w.raw_ext, w.raw_len, 1.0, w.gx, w.gy, w.gs, w.ga, w.gk, w.sample_count))) return rc;

@@ -1,0 +1,247 @@
+"""Scenarios that stop pqp_optimize_path_device at every stop site it has, and the stage each of them should get.
+
+* mixed_batch(): one ragged batch of healthy and stopped scenarios under one configuration (MIXED_CFG) whose capacities lie between the
+  counts of the healthy scenarios and those of the five scenarios that are to overflow them.  Every scenario says what it is meant to
+  be (`kind`); tests/test_chain_stops_cpu.py shows with oracle/corridor_oracle.py alone that each count lies on the intended side of its
+  threshold, tests/test_gpu_chain_stops.py runs the batch.
+* steps_one_by_one(): the chain for one scenario through the per-step host entry points, and where it stops - the precedence of the stop
+  sites restated here, step by step in the order the reference runs them (it does not come from the library's own table).
+"""
+import numpy as np
+
+import corridor_oracle as K
+from path_optimizer_2_amd import capi
+from path_optimizer_2_amd.synth import make_scene
+
+# stages (include/pqp.h, pqp_chain_stage)
+OK, FEW_POINTS, SMOOTHER_FAILED, SEARCH_FAILED, SHORT_REFERENCE, POST_SMOOTH_FAILED, HEADING, BLOCKED, PATH_QP_FAILED, CAPACITY = range(10)
+CAPACITY_SITES = ("raw_max", "sample_max", "sample_min", "layer_max", "n_max")
+
+# Capacities of the mixed batch: a healthy scenario (a polygon of 9 - 12 m, its target 1.5 m before the polygon's end) has at most
+# 14 raw points, 14 samples, 12 layers and about 40 waypoints; the overflowing scenarios are built to exceed one capacity each by 2 or more.
+MIXED_CFG = dict(raw_max=30, sample_max=24, layer_max=14, n_max=48)
+P_MAX = 13
+N_MAPS = 4
+
+
+def sample_min(method):
+    """the fewest samples the smoother QP takes: 3 (TensionSmoother2), 4 (TensionSmoother: the third-difference window)"""
+    return 4 if method == capi.SMOOTHING_TENSION else 3
+
+
+def smoother_params():
+    # the reference's smoother setting (OSQP default eps 1e-3) + the KKT-verified polish, as test_gpu_chain does
+    return capi.default_params(eps_abs=1e-3, eps_rel=1e-3, polish=1, polish_every=25, adaptive_rho_interval=25)
+
+
+def _along(c, at):
+    """points at arc lengths `at` of the scene's knot polygon (beyond its ends: the end segments continued)"""
+    kx, ky = np.asarray(c["knots_x"]), np.asarray(c["knots_y"])
+    seg = np.hypot(np.diff(kx), np.diff(ky))
+    cum = np.concatenate([[0.0], np.cumsum(seg)])
+    out = np.zeros((len(at), 2))
+    for i, a in enumerate(at):
+        j = int(np.clip(np.searchsorted(cum, a, side="right") - 1, 0, len(seg) - 1))
+        t = (a - cum[j]) / seg[j]
+        out[i] = (kx[j] + t * (kx[j + 1] - kx[j]), ky[j] + t * (ky[j + 1] - ky[j]))
+    return out
+
+
+# kind, points, spacing of the polygon [m]
+_PLAN = [
+    ("healthy", 6, 1.8),               # 0   9.0 m
+    ("few_points", 3, 3.05),           # 1   n_points = 3
+    ("few_points", 0, 3.05),           # 2   n_points = 0
+    ("few_points", -1, 3.05),          # 3   n_points = -1
+    ("no_line_p_max", P_MAX + 1, 3.05),  # 4 more points than the array holds
+    ("no_line_degree", 4, 3.0),        # 5   mean spacing <= 5 m: degree 5, not below 4 points
+    ("no_line_degree", 5, 3.0),        # 6   ... nor below 5
+    ("healthy", 7, 1.7),               # 7   10.2 m
+    ("cap_raw_max", 12, 3.05),         # 8   33.6 m of polygon: 35 raw points
+    ("cap_sample_max", 10, 2.822),     # 9   25.4 m: 27 raw points, 27 samples
+    ("cap_sample_min", 6, 0.12),       # 10  0.6 m: 2 raw points, 2 samples
+    ("cap_layer_max", 8, 2.786),       # 11  19.5 m: 21 samples, a smoothed line of 23 m, 17 layers
+    ("healthy", 7, 1.9),               # 12  11.4 m
+    ("cap_n_max", 7, 2.066),           # 13  12.4 m, the target far beyond the line: the whole 16 m of final line, 54 waypoints
+    ("short_reference", 6, 0.9),       # 14  4.5 m, the vehicle 0.75 m before the end of the 8 m the smoothed line is declared to have: 2 layers
+    ("search_failed", 7, 1.8),         # 15  the vehicle 14 m beside the line (lateral range 10 m)
+    ("heading", 7, 1.8),               # 16  92 degrees off the line's heading (limit 75)
+    ("healthy", 8, 1.5),               # 17  10.5 m
+    ("blocked", 7, 1.8),               # 18  a pit under the rear circle of the first waypoint
+    ("qp_nan", 7, 1.8),                # 19  start_k = NaN: the path QP ends NUMERICAL
+]
+GROUP_START = np.array([0, 1, 7, 12, 17, 20], dtype=np.int32)          # group 1 (rows 1 .. 6) holds stopped candidates only
+STOPPED_BEFORE_THE_QP = {"few_points": FEW_POINTS, "no_line_p_max": FEW_POINTS, "no_line_degree": FEW_POINTS, "cap_raw_max": CAPACITY,
+                         "cap_sample_max": CAPACITY, "cap_sample_min": CAPACITY, "cap_layer_max": CAPACITY, "cap_n_max": CAPACITY,
+                         "short_reference": SHORT_REFERENCE, "search_failed": SEARCH_FAILED, "heading": HEADING, "blocked": BLOCKED}
+INTENDED = dict(STOPPED_BEFORE_THE_QP, healthy=OK, qp_nan=PATH_QP_FAILED)
+
+
+def mixed_batch(seed=5):
+    """The mixed batch: dict(pts [B][P_MAX][2], n_pts, map_of, start, target, start_k, dist, geom, kind [B], healthy [B] bool)."""
+    cs = [make_scene(seed=s, n=40, n_obstacles=25, knots_every=3.05) for s in range(N_MAPS)]
+    rng = np.random.default_rng(seed)
+    B = len(_PLAN)
+    pts = np.zeros((B, P_MAX, 2)); n_pts = np.zeros(B, dtype=np.int32); map_of = (np.arange(B) % N_MAPS).astype(np.int32)
+    start = np.zeros((B, 3)); target = np.zeros((B, 3)); start_k = np.zeros(B)
+    dist = [c["dist"] for c in cs]
+    for b, (kind, P, spacing) in enumerate(_PLAN):
+        c = cs[b % N_MAPS]
+        n_pts[b] = P
+        m = min(max(P, 4), P_MAX)                           # (the rows are filled whatever the count says: a count is all a scenario's stop may depend on)
+        p = _along(c, spacing * np.arange(m))
+        if spacing > 1.0:
+            p[:, 1] += rng.normal(scale=0.1, size=m)
+        pts[b, :m] = p
+        h0 = np.arctan2(p[1, 1] - p[0, 1], p[1, 0] - p[0, 0])
+        start[b] = (p[0, 0] + 0.1 * (spacing > 1.0), p[0, 1] + 0.1 * (spacing > 1.0), h0 + 0.03)
+        h1 = np.arctan2(p[m - 1, 1] - p[m - 2, 1], p[m - 1, 0] - p[m - 2, 0])
+        # the target 1.5 m before the polygon's end: the reference line is cut at its projection (setReferencePathLength)
+        back = 1.5 if spacing > 1.0 else 0.0
+        target[b] = (p[m - 1, 0] - back * np.cos(h1), p[m - 1, 1] - back * np.sin(h1), h1)
+        if kind == "cap_n_max":
+            target[b, :2] = p[m - 1] + 10.0 * np.array([np.cos(h1), np.sin(h1)])
+        if kind == "short_reference":
+            # 7.25 m along the line the polygon's end segment continues: the smoothed line is declared to end at 5 + 3 = 8 m
+            sx, sy, s = raw_line(p)
+            x, y = K.spline_eval(sx, 7.25), K.spline_eval(sy, 7.25)
+            hh = np.arctan2(K.spline_deriv(sy, 1, 7.25), K.spline_deriv(sx, 1, 7.25))
+            start[b] = (x, y, hh + 0.03)
+        if kind == "search_failed":
+            start[b, :2] += np.array([-np.sin(start[b, 2]), np.cos(start[b, 2])]) * 14.0
+        if kind == "heading":
+            start[b, 2] += 1.6
+        if kind == "blocked":
+            # a pit of 0.6 m where the rear circle of the first waypoint lies, 1 m behind the vehicle (rear_length = -1): its clearance
+            # there is 0, the waypoint's rear interval is empty and the road is blocked at once (updateBounds).  The search does not look
+            # behind the vehicle and the cells around the pit keep their distance, so every earlier step runs as on the open road.
+            layer = dist[map_of[b]].copy()
+            px, py = start[b, 0] - np.cos(start[b, 2]), start[b, 1] - np.sin(start[b, 2])
+            g = grid_geom(c)
+            ii, jj = np.meshgrid(np.arange(g.rows), np.arange(g.cols), indexing="ij")
+            cx = g.pos_x + (g.length_x / 2 - g.resolution / 2) - g.resolution * ii          # K.grid_cell_position
+            cy = g.pos_y + (g.length_y / 2 - g.resolution / 2) - g.resolution * jj
+            layer[(cx - px) ** 2 + (cy - py) ** 2 < 0.6 ** 2] = 0.0
+            dist.append(layer)
+            map_of[b] = len(dist) - 1
+        if kind == "qp_nan":
+            start_k[b] = np.nan
+    c0 = cs[0]
+    geom = capi.PqpGridGeometry(c0["rows"], c0["cols"], c0["resolution"], c0["length"][0], c0["length"][1], c0["pos"][0], c0["pos"][1])
+    kind = [k for k, _, _ in _PLAN]
+    return dict(pts=pts, n_pts=n_pts, map_of=map_of, start=start, target=target, start_k=start_k, dist=np.stack(dist), geom=geom, kind=kind,
+                healthy=np.array([k == "healthy" for k in kind]), open_map=(np.arange(B) % N_MAPS).astype(np.int32))
+
+
+def all_healthy(sc):
+    """The batch with every scenario that is not healthy replaced by a copy of a healthy one (the healthy rows stay where they are)."""
+    out = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in sc.items()}
+    good = np.flatnonzero(sc["healthy"])
+    for i, b in enumerate(np.flatnonzero(~sc["healthy"])):
+        src = good[i % len(good)]
+        for k in ("pts", "n_pts", "map_of", "start", "target", "start_k"):
+            out[k][b] = sc[k][src]
+    out["kind"] = ["healthy"] * len(sc["kind"])
+    out["healthy"] = np.ones(len(sc["kind"]), dtype=bool)
+    return out
+
+
+def grid_geom(c):
+    """the oracle's GridGeom of a synth scene or of a PqpGridGeometry"""
+    if isinstance(c, dict):
+        return K.GridGeom(c["rows"], c["cols"], c["resolution"], c["length"][0], c["length"][1], c["pos"][0], c["pos"][1])
+    return K.GridGeom(c.rows, c.cols, c.resolution, c.length_x, c.length_y, c.pos_x, c.pos_y)
+
+
+def bspline_degree(p):
+    """the degree ReferencePathSmoother::bSpline picks for the polygon p (reference_path_smoother.cpp:495-505)"""
+    mean = np.hypot(np.diff(p[:, 0]), np.diff(p[:, 1])).sum() / (len(p) - 1)
+    return 3 if mean > 10.0 else (4 if mean > 5.0 else 5)
+
+
+def raw_line(p):
+    """the oracle's raw line of the polygon p: (spline x(s), spline y(s), s list)"""
+    x, y, s = K.bspline_resample(p)
+    return K.spline_fit(s, x), K.spline_fit(s, y), s
+
+
+# ---- the chain, one scenario and one step at a time -------------------------------------------------------------------------------------
+def steps_one_by_one(h, hs, sc, b, cfg, p_max=None):
+    """The chain for scenario b alone, exact sizes, through the per-step host-pointer entry points (each pinned to its oracle elsewhere),
+    and where it stops: dict(stage, status, site) - site names the capacity for stage 9 - plus nv and out where a path QP ran.
+    The stop sites in the order of the steps (the reference's `return false` sites and what stands in their way here):
+      n_points < 4                                   FEW_POINTS       reference_path_smoother.cpp:33-36
+      n_points > p_max, or not above the degree      FEW_POINTS       no raw line: bSpline gives no points (tinyspline refuses the spline)
+      raw points > raw_max                           CAPACITY
+      samples > sample_max, samples < 3 (TENSION: 4) CAPACITY         (two raw points: a polygon below 1 m, whose 1 m samples are two)
+      smoother QP not SOLVED                         SMOOTHER_FAILED
+      layers > layer_max                             CAPACITY
+      no layer                                       SEARCH_FAILED
+      fewer than 4 layers                            SHORT_REFERENCE
+      postSmooth QP not SOLVED                       POST_SMOOTH_FAILED
+      initial heading error > 75 degrees             HEADING
+      reference states > n_max                       CAPACITY
+      fewer than 2 waypoints before the road closes  BLOCKED
+      path QP not SOLVED                             PATH_QP_FAILED, with its status
+    p_max: the width of the batch's point array (None: sc["pts"].shape[1])."""
+    P = int(sc["n_pts"][b])
+    p_max = sc["pts"].shape[1] if p_max is None else p_max
+    mo = sc["map_of"][b:b + 1]
+    st, tg = sc["start"][b:b + 1], sc["target"][b:b + 1]
+    k0 = float(sc["start_k"][b]) if "start_k" in sc else 0.0
+    stop = lambda stage, site=None: dict(stage=stage, status=0, site=site)          # (0: PQP_STATUS_UNSOLVED, the status of a scenario no path QP ran for)
+    if P < 4 or P > p_max:
+        return stop(FEW_POINTS)
+    r = h.bspline_resample(sc["pts"][b:b + 1, :P], np.array([P], dtype=np.int32), cfg.raw_max)
+    n0 = int(r["count"][0])
+    if n0 == 0:
+        return stop(FEW_POINTS)
+    if n0 > cfg.raw_max:
+        return stop(CAPACITY, "raw_max")
+    if n0 < 3:
+        # two raw points (t = 0 and t = 1) are what a polygon shorter than 1 m gives: tk::spline takes no such line, and its samples at
+        # 0 and 1 m are fewer than any smoother QP takes
+        return stop(CAPACITY, "sample_min")
+    x0, y0, s0 = (r[k][:, :n0] for k in ("x", "y", "s"))
+    tab, ext = h.spline_fit(s0, x0, y0)
+    seg = h.segment_raw_reference(tab, ext, s0[:, -1].copy(), cfg.sample_max)
+    n1 = int(seg["count"][0])
+    if n1 > cfg.sample_max:
+        return stop(CAPACITY, "sample_max")
+    if n1 < sample_min(cfg.smoothing_method):
+        return stop(CAPACITY, "sample_min")
+    if cfg.smoothing_method == capi.SMOOTHING_TENSION:
+        gx, gy = seg["x"][:, :n1], seg["y"][:, :n1]
+        clr = np.array([[K.obstacle_distance(sc["dist"][mo[0]], sc["geom"], gx[0, i], gy[0, i]) for i in range(n1)]])
+        sm = hs.smooth_tension(gx, gy, seg["angle"][:, :n1], clr)
+    else:
+        sm = hs.smooth_tension2(*(seg[k][:, :n1] for k in ("x", "y", "angle", "k", "s")))
+    if sm["status"][0] != 1:
+        return stop(SMOOTHER_FAILED)
+    tab, ext = h.spline_fit(sm["s"], sm["x"], sm["y"])
+    ls, lb, ub, cnt, vl = h.dp_corridor(tab, ext, sm["s"][:, -1] + cfg.smoothed_length_margin, st, sc["dist"], sc["geom"], max_layers=cfg.layer_max, map_of=mo)
+    k = int(cnt[0])
+    if k < 0:
+        return stop(CAPACITY, "layer_max")
+    if k == 0:
+        return stop(SEARCH_FAILED)
+    if k < 4:
+        return stop(SHORT_REFERENCE)
+    ps = hs.post_smooth(ls[:, :k].copy(), lb[:, :k].copy(), ub[:, :k].copy(), vl)
+    if ps["status"][0] != 1:
+        return stop(POST_SMOOTH_FAILED)
+    x2, y2, s2 = h.offsets_to_points(tab, ext, ls[:, :k].copy(), ps["l"])
+    tab, ext = h.spline_fit(s2, x2, y2)
+    max_s = h.reference_length(tab, ext, s2[:, -1].copy(), tg)
+    ref, count, err = h.reference_states(tab, ext, max_s, cfg.n_max, start=st, ds_small=cfg.output_spacing / 2, ds_large=cfg.output_spacing, dynamic=True)
+    if abs(err[0, 1]) > 75.0 * np.pi / 180.0:
+        return stop(HEADING)
+    if count[0] > cfg.n_max:
+        return stop(CAPACITY, "n_max")
+    bounds, nv = h.corridor_bounds(ref, tab, ext, sc["dist"], sc["geom"], map_of=mo, n_of=count)
+    if nv[0] < 2:
+        return stop(BLOCKED)
+    scal = np.array([[err[0, 0], err[0, 1], k0, tg[0, 2], 1.0 if nv[0] < count[0] else 0.0, cfg.max_steering_angle]])
+    res = h.solve_var(nv, ref, bounds, scal, passes=1)
+    status = int(res["status"][0])
+    return dict(stage=OK if status == 1 else PATH_QP_FAILED, status=status, site=None, nv=int(nv[0]), out=res["out"][0])

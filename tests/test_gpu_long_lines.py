@@ -9,6 +9,7 @@ import pytest
 import corridor_oracle as K
 import corridor_util as U
 import long_line_util as LL
+from chain_stops_util import steps_one_by_one as _steps_one_by_one
 from path_optimizer_2_amd import capi
 from test_gpu_chain import _smoother_params
 from test_gpu_line_geometry import (REFUSED, SPLINE_SIZES, SEG_KEYS, _check_bspline, _check_segment, _check_states, check_spline_table,
@@ -330,52 +331,6 @@ def _long_scenarios(B, seed=11):
         start[b] = (p[0, 0] + 0.1, p[0, 1] + 0.1, np.arctan2(p[1, 1] - p[0, 1], p[1, 0] - p[0, 0]) + 0.02)
         target[b] = (p[-1, 0], p[-1, 1], np.arctan2(p[-1, 1] - p[-2, 1], p[-1, 0] - p[-2, 0]))
     return dict(pts=pts, n_pts=n_pts, map_of=np.zeros(B, dtype=np.int32), start=start, target=target, dist=road["dist"][None], geom=road["geom"])
-
-
-def _steps_one_by_one(h, hs, sc, b, cfg):
-    """test_gpu_chain._one_by_one for scenario b that also reports where the steps stop: the stage and QP status the chain should give
-    (stages FEW_POINTS .. BLOCKED as chain_status_kernel decides them; capacities are large enough never to be hit here)"""
-    P = int(sc["n_pts"][b])
-    mo = sc["map_of"][b:b + 1]
-    st, tg = sc["start"][b:b + 1], sc["target"][b:b + 1]
-    stop = lambda stage, status=0: dict(stage=stage, status=status)          # (0: PQP_STATUS_UNSOLVED, the status of a scenario no path QP ran for)
-    r = h.bspline_resample(sc["pts"][b:b + 1, :P], np.array([P], dtype=np.int32), cfg.raw_max)
-    n0 = int(r["count"][0])
-    x0, y0, s0 = (r[k][:, :n0] for k in ("x", "y", "s"))
-    tab, ext = h.spline_fit(s0, x0, y0)
-    seg = h.segment_raw_reference(tab, ext, s0[:, -1].copy(), cfg.sample_max)
-    n1 = int(seg["count"][0])
-    if cfg.smoothing_method == capi.SMOOTHING_TENSION:
-        gx, gy = seg["x"][:, :n1], seg["y"][:, :n1]
-        clr = np.array([[K.obstacle_distance(sc["dist"][mo[0]], sc["geom"], gx[0, i], gy[0, i]) for i in range(n1)]])
-        sm = hs.smooth_tension(gx, gy, seg["angle"][:, :n1], clr)
-    else:
-        sm = hs.smooth_tension2(*(seg[k][:, :n1] for k in ("x", "y", "angle", "k", "s")))
-    if sm["status"][0] != 1:
-        return stop(2)
-    tab, ext = h.spline_fit(sm["s"], sm["x"], sm["y"])
-    ls, lb, ub, cnt, vl = h.dp_corridor(tab, ext, sm["s"][:, -1] + cfg.smoothed_length_margin, st, sc["dist"], sc["geom"], max_layers=cfg.layer_max, map_of=mo)
-    k = int(cnt[0])
-    if k <= 0:
-        return stop(3 if k == 0 else 9)
-    if k < 4:
-        return stop(4)
-    ps = hs.post_smooth(ls[:, :k].copy(), lb[:, :k].copy(), ub[:, :k].copy(), vl)
-    if ps["status"][0] != 1:
-        return stop(5)
-    x2, y2, s2 = h.offsets_to_points(tab, ext, ls[:, :k].copy(), ps["l"])
-    tab, ext = h.spline_fit(s2, x2, y2)
-    max_s = h.reference_length(tab, ext, s2[:, -1].copy(), tg)
-    ref, count, err = h.reference_states(tab, ext, max_s, cfg.n_max, start=st, ds_small=cfg.output_spacing / 2, ds_large=cfg.output_spacing, dynamic=True)
-    if abs(err[0, 1]) > 75.0 * np.pi / 180.0:
-        return stop(6)
-    bounds, nv = h.corridor_bounds(ref, tab, ext, sc["dist"], sc["geom"], map_of=mo, n_of=count)
-    if nv[0] < 2:
-        return stop(7)
-    scal = np.array([[err[0, 0], err[0, 1], 0.0, tg[0, 2], 1.0 if nv[0] < count[0] else 0.0, cfg.max_steering_angle]])
-    res = h.solve_var(nv, ref, bounds, scal, passes=1)
-    status = int(res["status"][0])
-    return dict(stage=0 if status == 1 else 8, status=status, nv=int(nv[0]), out=res["out"][0])
 
 
 @pytest.mark.parametrize("method", [capi.SMOOTHING_TENSION2, capi.SMOOTHING_TENSION])
