@@ -494,6 +494,21 @@ class DpParams:
     car_width: float = 2.0               # :10  -> search_threshold = car_width / 2 + 0.2   reference_path_smoother.cpp:171
 
 
+@dataclass
+class DpCostKnobs:
+    """The constants of calculateCostAt (reference_path_smoother.cpp:107-140) by name, at the reference's values.  TEST INFRASTRUCTURE ONLY:
+    tests/test_dp_cases_cpu.py turns one at a time to show that the scenes of tests/dp_cases.py tell a search with that defect from the
+    reference's; nothing in the product reads them, and every default is the literal the reference writes (x * 1.0 is x: the arithmetic
+    of graph_search_dp under the defaults is bit for bit what it was without the knobs)."""
+    w_prev_dir: float = 16.0             # :128  turn against the predecessor's incoming direction
+    w_heading: float = 0.5               # :129  turn against the layer's heading
+    w_dist: float = 0.5                  # :112  (3 - d) / 3 of a node closer than 3 m to an obstacle
+    w_lateral: float = 1.0               # :114  |l| / lateral_range
+    tie_first: bool = True               # :131  `total < min_cost`: the first of equally cheap predecessors; False: `<=`, the last
+    window_factor: float = 1.0           # :124  a predecessor is admissible while |l_pre - l| <= window_factor * ds
+    use_prev_dir: bool = True            # :128  False: the predecessor's layer heading in place of its incoming direction
+
+
 def projection_newton(sx, sy, tx, ty, max_s, hint_s):                        # tools.cpp:98-126
     hint_s = min(hint_s, max_s)
     cur_s = hint_s
@@ -553,10 +568,26 @@ def reference_length(sx, sy, length, tx, ty):
     return projection(sx, sy, tx, ty, length, 0.0)
 
 
-def graph_search_dp(sx, sy, length, start, dist, g, prm=DpParams()):
+def graph_search_dp(sx, sy, length, start, dist, g, prm=DpParams(), knobs=None):
     """graphSearchDp (reference_path_smoother.cpp:142-295) with calculateCostAt (:107-140).
     start = (x, y, heading) of the vehicle.  Returns None when the reference returns false, else a dict with
-    layers_s, lb, ub (layers_bounds_), vehicle_l (vehicle_l_wrt_smoothed_ref_): the inputs of the postSmooth QP."""
+    layers_s, lb, ub (layers_bounds_), vehicle_l (vehicle_l_wrt_smoothed_ref_): the inputs of the postSmooth QP.
+
+    What the search decided, and how close each decision was (for tests: an implementation in other arithmetic - ocml's atan2 for libm's -
+    can only differ where one of these is within its round-off):
+      path           lateral index of the chosen node, per returned layer
+      max_layer      last layer reached
+      margin_cost    smallest non-zero (runner-up total - best total) over every node that got a parent, and (second cheapest - cheapest
+                     cost) over the final pick in the last layer reached; inf where no choice had a runner-up
+      n_ties         choices whose gap is exactly 0 (the tie rule decided), ties_on_path: those of them at the chosen nodes / the final pick
+      margin_d       smallest |d - threshold| over every threshold test that can shape the result: the feasibility test of every sample of
+                     layers 1 ... max_layer + 1 (layer 0 has the start node only; the layer after the last reached one is what stopped the
+                     search) and every probe of the 0.2 m walks from the chosen nodes
+      margin_lb/_ub  per returned layer: the smallest |d - threshold| among the tests that set that entry directly - the samples of the
+                     chosen node's feasible run and the one beyond its end on that side, and that side's probes (inf for layer 0).  A test
+                     of another sample acts on the bounds only through the path; margin_d covers it.
+    `knobs` (DpCostKnobs) is for tests; None is the reference's cost model."""
+    kn = knobs if knobs is not None else DpCostKnobs()
     thr = prm.car_width / 2.0 + 0.2
     tmp_s = projection(sx, sy, start[0], start[1], length)
     layers = []
@@ -603,30 +634,38 @@ def graph_search_dp(sx, sy, length, start, dist, g, prm=DpParams()):
         samples.append(pts)
     # costs (calculateCostAt)
     max_layer = 0
+    margin_cost, n_ties = math.inf, 0
     for i, layer in enumerate(samples):
         layer_feasible = False
         for pt in layer:
             if i > 0 and pt["feas"]:
                 self_cost = 0.0
                 if pt["dis"] < 3.0:
-                    self_cost += (3.0 - pt["dis"]) / 3.0 * 0.5
-                self_cost += abs(pt["l"]) / prm.lateral_range * 1.0
+                    self_cost += (3.0 - pt["dis"]) / 3.0 * kn.w_dist
+                self_cost += abs(pt["l"]) / prm.lateral_range * kn.w_lateral
                 min_cost = DBL_MAX
+                totals = []
                 for pre in samples[i - 1]:
                     if not pre["feas"]:
                         continue
-                    if abs(pre["l"] - pt["l"]) > (pt["s"] - pre["s"]):
+                    if abs(pre["l"] - pt["l"]) > (pt["s"] - pre["s"]) * kn.window_factor:
                         continue
                     direction = math.atan2(pt["y"] - pre["y"], pt["x"] - pre["x"])
-                    edge = abs(constrain_angle(direction - pre["dir"])) / (math.pi / 2) * 16.0 \
-                        + abs(constrain_angle(direction - pt["heading"])) / (math.pi / 2) * 0.5
+                    edge = abs(constrain_angle(direction - (pre["dir"] if kn.use_prev_dir else pre["heading"]))) / (math.pi / 2) * kn.w_prev_dir \
+                        + abs(constrain_angle(direction - pt["heading"])) / (math.pi / 2) * kn.w_heading
                     total = self_cost + edge + pre["cost"]
-                    if total < min_cost:
+                    totals.append(total)
+                    if total < min_cost or (not kn.tie_first and total == min_cost):
                         min_cost = total
                         pt["parent"] = pre
                         pt["dir"] = direction
                 if pt["parent"] is not None:
                     pt["cost"] = min_cost
+                    pt["gap"] = _runner_up_gap(totals)
+                    if pt["gap"] == 0.0:
+                        n_ties += 1
+                    else:
+                        margin_cost = min(margin_cost, pt["gap"])
             if pt["parent"] is not None:
                 layer_feasible = True
         if i != 0 and not layer_feasible:
@@ -637,11 +676,36 @@ def graph_search_dp(sx, sy, length, start, dist, g, prm=DpParams()):
     for pt in samples[max_layer]:
         if pt["cost"] < min_cost:
             ptr, min_cost = pt, pt["cost"]
-    bounds = []
+    ties_on_path = 0
+    final_gap = _runner_up_gap([pt["cost"] for pt in samples[max_layer] if pt["cost"] < DBL_MAX])
+    if final_gap == 0.0:
+        n_ties += 1
+        ties_on_path += 1
+    else:
+        margin_cost = min(margin_cost, final_gap)
+    # every feasibility test that the search saw: layers 1 ... max_layer + 1
+    margin_d = math.inf
+    for layer in samples[1:max_layer + 2]:
+        for pt in layer:
+            margin_d = min(margin_d, abs(pt["dis"] - thr))
+    bounds, path, m_lb, m_ub = [], [], [], []
     while ptr is not None:
+        path.append(ptr["j"])
         if ptr["i"] == 0:
             bounds.append((-10.0, 10.0))
+            m_lb.append(math.inf); m_ub.append(math.inf)
         else:
+            if ptr.get("gap") == 0.0:
+                ties_on_path += 1
+            layer = samples[ptr["i"]]
+            # the samples that set this node's rough bounds: its feasible run, and the infeasible sample that ends it on either side
+            jlo = jup = ptr["j"]
+            while jlo > 0 and layer[jlo]["feas"]:
+                jlo -= 1
+            while jup < len(layer) - 1 and layer[jup]["feas"]:
+                jup += 1
+            near_lb = min(abs(layer[j]["dis"] - thr) for j in range(jlo, ptr["j"] + 1))
+            near_ub = min(abs(layer[j]["dis"] - thr) for j in range(ptr["j"], jup + 1))
             check_s, limit = 0.2, 6.0
             ub = check_s + ptr["rup"]
             lb = -check_s + ptr["rlo"]
@@ -649,21 +713,40 @@ def graph_search_dp(sx, sy, length, start, dist, g, prm=DpParams()):
             ca, sa = math.cos(ptr["heading"] + math.pi / 2), math.sin(ptr["heading"] + math.pi / 2)
             while ub < limit:
                 x, y = rx + ub * ca, ry + ub * sa
-                if grid_is_inside(g, x, y) and obstacle_distance(dist, g, x, y) > thr:
+                inside = grid_is_inside(g, x, y)
+                d = obstacle_distance(dist, g, x, y) if inside else None
+                if inside:
+                    near_ub = min(near_ub, abs(d - thr))
+                if inside and d > thr:
                     ub += check_s
                 else:
                     ub -= check_s
                     break
             while lb > -limit:
                 x, y = rx + lb * ca, ry + lb * sa
-                if grid_is_inside(g, x, y) and obstacle_distance(dist, g, x, y) > thr:
+                inside = grid_is_inside(g, x, y)
+                d = obstacle_distance(dist, g, x, y) if inside else None
+                if inside:
+                    near_lb = min(near_lb, abs(d - thr))
+                if inside and d > thr:
                     lb -= check_s
                 else:
                     lb += check_s
                     break
             bounds.append((lb, ub))
+            m_lb.append(near_lb); m_ub.append(near_ub)
+            margin_d = min(margin_d, near_lb, near_ub)
         ptr = ptr["parent"]
-    bounds.reverse()
+    bounds.reverse(); path.reverse(); m_lb.reverse(); m_ub.reverse()
     n = len(bounds)
     return dict(layers_s=np.array(layers[:n]), lb=np.array([b[0] for b in bounds]), ub=np.array([b[1] for b in bounds]), vehicle_l=vehicle_l,
-                path=[None] * n, n_layers_sampled=len(layers))
+                path=path, n_layers_sampled=len(layers), max_layer=max_layer, margin_cost=margin_cost, n_ties=n_ties, ties_on_path=ties_on_path,
+                margin_d=margin_d, margin_lb=np.array(m_lb), margin_ub=np.array(m_ub))
+
+
+def _runner_up_gap(totals):
+    """second smallest - smallest of a list of costs (0 on an exact tie); inf when there is no runner-up"""
+    if len(totals) < 2:
+        return math.inf
+    a = sorted(totals)
+    return a[1] - a[0]

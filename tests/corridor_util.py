@@ -58,6 +58,38 @@ def tab_close(tab, ext, want_tab, want_ext=None):
         assert np.abs(np.asarray(ext) - np.asarray(want_ext)).max() <= SPLINE_TOL * max(1.0, float(np.abs(want_ext).max()))
 
 
+DP_D_FLAG = 1e-6        # a `d < 1.2` / `d > 1.2` test this close to the threshold may come out either way: > 4 ulp of the float32 threshold
+
+
+def dp_bounds_agree(lb, ub, want, what=None):
+    """lb / ub of one scenario of pqp_dp_corridor against the oracle's result `want` (graph_search_dp) on a scene that was not built to keep
+    its decisions away from round-off.  The bounds are sums of 0.6 m samples and 0.2 m steps, equal to round-off unless a distance sample sits
+    on the 1.2 m threshold, so
+      - at least 95 % of the layers agree in both bounds (as these comparisons always asked), and
+      - an entry that does not agree is one the oracle flags - a threshold test that sets that entry directly came within DP_D_FLAG of the
+        threshold (want["margin_lb" / "margin_ub"]) - and it is off by whole 0.2 m steps.
+    Entries flagged on the scenes this is used on (counted on the CPU, the oracle alone): none on any - the five seeds of
+    test_dp_corridor_search, the four grids of test_dp_corridor_search_on_other_grids, the 60 / 130 / 199 m lines of
+    test_dp_corridor_long_lines_several_maps, the 900 m and 2.7 km roads of test_dp_corridor_past_the_edge, scene_a and scene_b: 0 of up to
+    1805 layers x 2; the smallest margin of any test among them is 7.0e-5 (the 130 m line).  So on all of them every entry is held to 1e-9."""
+    k = len(want["lb"])
+    lb, ub = np.asarray(lb)[:k], np.asarray(ub)[:k]
+    d_lb, d_ub = np.abs(lb - want["lb"]), np.abs(ub - want["ub"])
+    same = (d_lb < 1e-9) & (d_ub < 1e-9)
+    assert same.mean() > 0.95, (what, same.mean(), lb, want["lb"], ub, want["ub"])
+    for side, d, margin in (("lb", d_lb, want["margin_lb"]), ("ub", d_ub, want["margin_ub"])):
+        for i in np.nonzero(d >= 1e-9)[0]:
+            assert margin[i] < DP_D_FLAG, (what, side, int(i), float(d[i]), float(margin[i]))
+            steps = d[i] / 0.2
+            assert round(steps) >= 1 and abs(steps - round(steps)) * 0.2 < 1e-9, (what, side, int(i), float(d[i]))
+    return int((~same).sum())
+
+
+def dp_flagged(want):
+    """the number of lb / ub entries of an oracle result that dp_bounds_agree would excuse"""
+    return int((want["margin_lb"] < DP_D_FLAG).sum() + (want["margin_ub"] < DP_D_FLAG).sum())
+
+
 # ---- LDS budgets of the line-geometry kernels (pqp_corridor_kernels.inc, launchers in pqp_lines.hip) -----------------------------
 LDS_PER_CU = 160 * 1024
 # static LDS of each kernel as the compiler reports it ("LDS Size"): its __shared__ variables padded to the 16-byte alignment of the

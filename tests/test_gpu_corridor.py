@@ -329,8 +329,7 @@ def test_dp_corridor_search(handle, seed, length):
     k = int(count[0])
     assert vl[0] == pytest.approx(want["vehicle_l"], abs=1e-12)
     np.testing.assert_allclose(ls[0, :k], want["layers_s"], rtol=0, atol=1e-11)
-    same = (np.abs(lb[0, :k] - want["lb"]) < 1e-9) & (np.abs(ub[0, :k] - want["ub"]) < 1e-9)
-    assert same.mean() > 0.95, (lb[0, :k], want["lb"], ub[0, :k], want["ub"])
+    U.dp_bounds_agree(lb[0], ub[0], want)
 
 
 @pytest.mark.parametrize("rng,spacing,lon,length", [(10.0, 0.6, 1.5, 40.0),      # the reference's grid: 34 samples, window of 7 predecessors
@@ -352,8 +351,7 @@ def test_dp_corridor_search_on_other_grids(handle, rng, spacing, lon, length):
     assert count[0] == len(want["layers_s"])
     k = int(count[0])
     np.testing.assert_allclose(ls[0, :k], want["layers_s"], rtol=0, atol=1e-11)
-    same = (np.abs(lb[0, :k] - want["lb"]) < 1e-9) & (np.abs(ub[0, :k] - want["ub"]) < 1e-9)
-    assert same.mean() > 0.95, (lb[0, :k], want["lb"], ub[0, :k], want["ub"])
+    U.dp_bounds_agree(lb[0], ub[0], want)
 
 
 def test_dp_corridor_edge_cases(handle):
@@ -415,7 +413,12 @@ def test_golden_scene_fixtures_through_the_hip_chain(handle, name):
     c = int(cnt[0])
     assert c == len(f["dp_layers_s"])
     np.testing.assert_allclose(ls[0, :c], f["dp_layers_s"], rtol=0, atol=1e-11)
-    assert ((np.abs(lb[0, :c] - f["dp_lb"]) < 1e-9) & (np.abs(ub[0, :c] - f["dp_ub"]) < 1e-9)).mean() > 0.95
+    # (the flags of the entries that may differ: the oracle on the fixture's own knots and layer, which reproduces the fixture's bounds)
+    sx, sy = K.spline_fit(f["knots_s"], f["knots_x"]), K.spline_fit(f["knots_s"], f["knots_y"])
+    want = K.graph_search_dp(sx, sy, float(f["length"]), tuple(f["start"]), np.asfortranarray(f["dist"]),
+                             K.GridGeom(int(gv[0]), int(gv[1]), *[float(v) for v in gv[2:]]))
+    assert np.array_equal(want["lb"], f["dp_lb"]) and np.array_equal(want["ub"], f["dp_ub"])
+    U.dp_bounds_agree(lb[0], ub[0], want, name)
     assert vl[0] == pytest.approx(float(f["dp_vehicle_l"]), abs=1e-12)
 
 

@@ -627,8 +627,7 @@ def _check_dp(out, q, c, length, start):
     k = int(count[q])
     assert k == len(want["layers_s"])
     np.testing.assert_allclose(ls[q, :k], want["layers_s"], rtol=0, atol=1e-11)
-    same = (np.abs(lb[q, :k] - want["lb"]) < 1e-9) & (np.abs(ub[q, :k] - want["ub"]) < 1e-9)
-    assert same.mean() > 0.95, (q, same.mean())
+    U.dp_bounds_agree(lb[q], ub[q], want, q)
 
 
 def test_dp_corridor_long_lines_several_maps(handle):

@@ -167,8 +167,7 @@ def test_dp_corridor_past_the_edge(handles, length):
     k = int(count[0])
     assert k == len(want["layers_s"])
     np.testing.assert_allclose(ls[0, :k], want["layers_s"], rtol=0, atol=1e-9)
-    same = (np.abs(lb[0, :k] - want["lb"]) < 1e-9) & (np.abs(ub[0, :k] - want["ub"]) < 1e-9)
-    assert same.mean() > 0.95, same.mean()
+    U.dp_bounds_agree(lb[0], ub[0], want, length)
     rc, outs = _road_dp(road, line, start, max_layers, handles[0])
     assert rc == REFUSED and all(o.untouched() for o in outs)
 
