@@ -508,7 +508,8 @@ int pqp_distance_layer(pqp_handle* h, int n_maps, const pqp_grid_geometry* geom,
  * PathOptimizer::processInitState                                              src/path_optimizer.cpp:73-85
  * spline, spline_ext as above; max_s [batch] = ReferencePath::getLength(); start [batch][3] = vehicle start state x, y, heading (or NULL)
  * ref [batch][n_max][5] = s, k, heading, x, y;  count [batch] = states the loop produces (when it exceeds n_max only n_max rows
- * were written);  init_err [batch][2] = initial_offset, initial_heading_error (NULL or needs start): scal[0..1] of pqp_path_solve */
+ * were written; 0 where |max_s| < 1e-6: "ref length is zero", :316-319, the reference returns false and builds none);
+ * init_err [batch][2] = initial_offset, initial_heading_error (NULL or needs start): scal[0..1] of pqp_path_solve */
 int pqp_reference_states_device(pqp_handle* h, int batch, int n_max, int m, const double* spline, const double* spline_ext,
                                 const double* max_s, const double* start, double ds_small, double ds_large, int dynamic, double* ref,
                                 int32_t* count, double* init_err);

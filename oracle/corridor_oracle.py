@@ -2,17 +2,25 @@
 
 TEST INFRASTRUCTURE ONLY: only tests/, __graft_entry__.smoke() and bench tools' cpu_baseline legs may import this module.
 
-PARITY UNPINNED.  The reference has no tests or vectors for this path, and two of its ingredients are third-party:
-  * grid_map_core (ANYbotics/grid_map, un-pinned `find_package(grid_map_core)`; not in /root/reference, not in this image).
-    `GridMap::isInside`, `getIndex`, `getPosition` and `atPosition(..., INTER_LINEAR)` are restated below from the published
-    1.6.x sources (GridMapMath.cpp, GridMap.cpp::atPositionLinearInterpolated), including their border behaviour.
+PARITY.  The reference has no tests or vectors for this path.  What is pinned to its own code, and what is not:
+  * tk::spline (src/tools/spline.cpp, std-only): oracle/Makefile builds it from where it lies into oracle/_ref/libref_spline.so and
+    tests/test_corridor_oracle.py checks the restatement below against it bit for bit.
+  * tools.cpp, ReferencePath(Impl) and Map - heading, curvature, distance, global2local_y, the projections, build_reference_from_spline,
+    clearance_strict, update_bounds_improved, and process_init_state / reference_length through their primitives: oracle/Makefile
+    builds them unchanged over the stand-in headers of oracle/stand_ins into oracle/_ref/libref_corridor.so, tests/ref_corridor.py records
+    what they compute and tests/test_ref_corridor.py holds the restatements below to it bit for bit.
+  * NOT pinned: grid_map_core (ANYbotics/grid_map, un-pinned `find_package(grid_map_core)`; third-party, not in the reference tree, not in
+    this image).  `GridMap::isInside`, `getIndex`, `getPosition` and `atPosition(..., INTER_LINEAR)` are restated below from the published
+    1.6.x sources (GridMapMath.cpp, GridMap.cpp::atPositionLinearInterpolated), including their border behaviour; the stand-in GridMap
+    under libref_corridor.so restates the same conventions and is held to these bit for bit, neither to grid_map itself.
+  * NOT pinned: graph_search_dp, bspline_resample, segment_raw_reference, offsets_to_points (their sources need Eigen's matrices,
+    OsqpEigen or tinyspline).
   * libm's sin/cos/atan2 (the GPU uses ocml's): bounds agree except where a clearance sample lies within round-off of
     the 0.5 m threshold.
-tk::spline IS in the reference tree (src/tools/spline.cpp, std-only): oracle/Makefile builds it from where it lies into
-oracle/_ref/libref_spline.so and tests/test_corridor_oracle.py checks the restatement below against it bit for bit.
 
 What is restated (reference file:line):
   spline_fit / spline_eval / spline_deriv      tk::spline::set_points / operator() / deriv       src/tools/spline.cpp:69-318
+  heading / curvature / distance               getHeading / getCurvature / distance              src/tools/tools.cpp:32-48
   directional_projection_newton                getDirectionalProjectionByNewton                  src/tools/tools.cpp:156-189
   global2local_y                               global2Local(...).y                               src/tools/tools.cpp:57-64
   obstacle_distance                            Map::getObstacleDistance                          src/tools/Map.cpp:16-22
@@ -165,6 +173,24 @@ def pack_spline(sx, sy):
 # ----------------------------------------------------------------------------------------------------------------------
 # tools.cpp
 # ----------------------------------------------------------------------------------------------------------------------
+# The reference writes squares as pow(v, 2).  gcc compiles that to v * v (at any optimisation level that inlines builtins), which is correctly
+# rounded; libm's pow(v, 2.0) - what math.pow(v, 2) calls - is accurate to under an ulp but is not always v * v in the last place.  The
+# restatements therefore square by multiplying (tests/test_ref_corridor.py holds them to the compiled reference bit for bit); pow(v, 1.5)
+# stays libm's pow in both.
+def heading(sx, sy, s):                                                       # getHeading   tools.cpp:32-36
+    return math.atan2(spline_deriv(sy, 1, s), spline_deriv(sx, 1, s))
+
+
+def curvature(sx, sy, s):                                                     # getCurvature tools.cpp:38-44
+    dx, dy = spline_deriv(sx, 1, s), spline_deriv(sy, 1, s)
+    ddx, ddy = spline_deriv(sx, 2, s), spline_deriv(sy, 2, s)
+    return (dx * ddy - dy * ddx) / math.pow(dx * dx + dy * dy, 1.5)
+
+
+def distance(x1, y1, x2, y2):                                                 # distance     tools.cpp:46-48
+    return math.sqrt((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2))
+
+
 def directional_projection_newton(sx, sy, tx, ty, angle, max_s, hint_s):      # tools.cpp:156-189
     hint_s = min(hint_s, max_s)
     cur_s = hint_s
@@ -201,14 +227,14 @@ def build_reference_from_spline(sx, sy, max_s, ds_small=0.15, ds_large=0.3, dyna
     output_spacing) = (0.15, 0.3) at path_optimizer.cpp:119.  Rows (s, k, heading, x, y): the ABI layout of the path QP."""
     large_k, small_k = 0.2, 0.08
     out = []
+    if abs(max_s - 0.0) < 1e-6:                   # isEqual(max_s_, 0.0), FLAGS_epsilon: "ref length is zero", returns false and builds nothing (:316-319)
+        return np.zeros((0, 5))
     tmp_s = 0.0
     while tmp_s <= max_s:
         x = spline_eval(sx, tmp_s)
         y = spline_eval(sy, tmp_s)
-        dx, dy = spline_deriv(sx, 1, tmp_s), spline_deriv(sy, 1, tmp_s)
-        ddx, ddy = spline_deriv(sx, 2, tmp_s), spline_deriv(sy, 2, tmp_s)
-        h = math.atan2(dy, dx)                                                            # getHeading   tools.cpp:32-36
-        k = (dx * ddy - dy * ddx) / math.pow(math.pow(dx, 2) + math.pow(dy, 2), 1.5)      # getCurvature tools.cpp:38-44
+        h = heading(sx, sy, tmp_s)
+        k = curvature(sx, sy, tmp_s)
         out.append((tmp_s, k, h, x, y))
         if dynamic:
             ak = abs(k)
@@ -308,7 +334,7 @@ def process_init_state(sx, sy, start_x, start_y, start_heading):
     ih = math.atan2(spline_deriv(sy, 1, 0.0), spline_deriv(sx, 1, 0.0))
     dx, dy = ix - start_x, iy - start_y
     local_y = -dx * math.sin(start_heading) + dy * math.cos(start_heading)                # global2Local(start, init_point).y
-    min_distance = math.sqrt(math.pow(start_x - ix, 2) + math.pow(start_y - iy, 2))       # distance()  tools.cpp:46-48
+    min_distance = distance(start_x, start_y, ix, iy)
     offset = min_distance if local_y < 0.0 else -min_distance
     return offset, constrain_angle(start_heading - ih)
 
@@ -531,11 +557,11 @@ def projection(sx, sy, tx, ty, max_s, start_s=0.0):                           # 
         return 0.0                                # State{xs(start_s), ys(start_s)}: s stays 0
     tmp_s, min_dis_s, min_dis = start_s, start_s, DBL_MAX
     while tmp_s <= max_s:
-        d = math.sqrt(math.pow(spline_eval(sx, tmp_s) - tx, 2) + math.pow(spline_eval(sy, tmp_s) - ty, 2))
+        d = distance(spline_eval(sx, tmp_s), spline_eval(sy, tmp_s), tx, ty)
         if d < min_dis:
             min_dis, min_dis_s = d, tmp_s
         tmp_s += 1.0
-    d_end = math.sqrt(math.pow(spline_eval(sx, max_s) - tx, 2) + math.pow(spline_eval(sy, max_s) - ty, 2))
+    d_end = distance(spline_eval(sx, max_s), spline_eval(sy, max_s), tx, ty)
     if d_end < min_dis:
         return max_s
     return projection_newton(sx, sy, tx, ty, max_s, min_dis_s)

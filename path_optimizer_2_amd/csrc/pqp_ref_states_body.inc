@@ -44,7 +44,10 @@
                 cnt += 1;
             }
         }
-        while (a.dynamic != 2 && tmp_s <= max_s && cnt < (1 << 20)) {
+        // isEqual(max_s_, 0.0) (FLAGS_epsilon = 1e-6, planning_flags.cpp:108): "ref length is zero", the reference returns false and builds
+        // no state (:316-319)
+        const bool zero_length = a.dynamic != 2 && fabs(max_s) < 1e-6;
+        while (a.dynamic != 2 && !zero_length && tmp_s <= max_s && cnt < (1 << 20)) {
             if (cnt < a.n_max) s_of[(size_t)cnt * s_step] = tmp_s;
             cnt += 1;
             if (a.dynamic) {

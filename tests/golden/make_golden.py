@@ -1,7 +1,8 @@
 """Generates the golden fixtures of tests/golden/*.npz from the oracle (oracle/pqp_oracle.py) and the synthetic
 generator.  The reference holds no vectors for this path, so these are produced here, by the
 build's own restatement, and pinned by the KKT certificate stored next to them.
-Run from the repo root:  python tests/golden/make_golden.py   (reference_pieces.npz: python tests/golden/make_golden.py reference)"""
+Run from the repo root:  python tests/golden/make_golden.py   (reference_pieces.npz: python tests/golden/make_golden.py reference;
+reference_corridor.npz: python tests/golden/make_golden.py reference_corridor)"""
 import os
 import sys
 
@@ -125,7 +126,25 @@ def make_reference_fixture(name):
     print(name, len(out), "arrays")
 
 
+def make_reference_corridor_fixture(name):
+    """What the reference's corridor layer computes on the fixed inputs of tests/ref_corridor.py (needs oracle/_ref: `make -C oracle ref`).
+    Written with a fixed member order and time stamp, so that the same values give the same file byte for byte."""
+    import io
+    import zipfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_corridor as RC
+    out = RC.record()
+    with zipfile.ZipFile(os.path.join(HERE, name + ".npz"), "w") as z:
+        for key in sorted(out):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(out[key]), allow_pickle=False)
+            z.writestr(zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0)), buf.getvalue(), compress_type=zipfile.ZIP_DEFLATED, compresslevel=9)
+    print(name, len(out), "arrays,", os.path.getsize(os.path.join(HERE, name + ".npz")), "bytes")
+
+
 if __name__ == "__main__":
+    if "reference_corridor" in sys.argv[1:]:
+        make_reference_corridor_fixture("reference_corridor"); sys.exit(0)
     if "smoothers" in sys.argv[1:]:
         make_smoother_fixture("smoothers"); sys.exit(0)
     if "reference" in sys.argv[1:]:

@@ -11,7 +11,7 @@ MAX_LENGTH = 1048576.0           # include/pqp.h: a longer (or infinite) line is
 
 
 def _dist(sx, sy, s, x, y):
-    return math.sqrt(math.pow(K.spline_eval(sx, s) - x, 2) + math.pow(K.spline_eval(sy, s) - y, 2))
+    return K.distance(K.spline_eval(sx, s), K.spline_eval(sy, s), x, y)
 
 
 def trace(sx, sy, length, x, y):
