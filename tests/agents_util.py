@@ -131,15 +131,6 @@ def near_margin(clears, margin, tol=1e-9):
     return [(np.abs(cl - margin) <= tol).any(axis=1) if cl.size else np.zeros(cl.shape[0], bool) for cl in clears]
 
 
-def same_bits(a, b):
-    """bit for bit, NaNs (whose sign and payload are no part of IEEE arithmetic) in the same places"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    if a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint64), b[~nb].view(np.uint64)))
-
-
 def seeded_case(rng, B, m, n_scenes, a_max, stride=3, span=1000.0, near=0.7):
     """traj [B][m][stride], agents [n_scenes][a_max][m][6]: cars that drive 0.2 to 1.5 m per step somewhere within +-span, and agents
     of which a share `near` is placed along one of the scene's paths (some into it, some beside it) and the rest anywhere; noise in the
@@ -272,3 +263,39 @@ def edge_cases(circles, margin=EDGE_MARGIN, eps=EDGE_EPS):
         want_first[b] = k_hit
     return dict(traj=traj, agents=agents, scene_of=np.arange(B, dtype=np.int32), margin=margin, want_first=want_first,
                 want_who=np.ones(B, np.int32))
+
+
+# the shapes of the seeded cases: trajectory lengths around the wavefront, batches, agents per scene
+MS = (1, 63, 64, 65, 130)
+BATCHES = (1, 4, 5)
+AGENTS = (0, 1, 3)
+
+
+def seeded(m, B, a_max):
+    """one case per shape, the seed from the shape: two scenes, ragged a_of and m_of (a 0 among them when the batch allows), stride 3 or 8"""
+    rng = np.random.default_rng(1000 * m + 10 * B + a_max)
+    stride = 3 if (m + B + a_max) % 2 else 8
+    traj, agents = seeded_case(rng, B, m, 2, a_max, stride=stride)
+    m_of = rng.integers(0, m + 1, B).astype(np.int32)
+    m_of[0] = m
+    if B > 1:
+        m_of[1] = 0
+    a_of = np.array([a_max, max(a_max - 1, 0)], np.int32)
+    scene_of = (np.arange(B) % 2).astype(np.int32)
+    return dict(id=f"m{m}-B{B}-A{a_max}", traj=traj, agents=agents, m_of=m_of, a_of=a_of, scene_of=scene_of, margin=0.3 if a_max == 3 else 0.0)
+
+
+def seeded_cases():
+    return [seeded(m, B, a) for m in MS for B in BATCHES for a in AGENTS]
+
+
+def write_case(path, traj, agents, margin, m_of, a_of, scene_of):
+    """the file tests/cpp/agents_demo.cpp reads; traj [B][m][stride >= 3], agents [n_scenes][a_max][m][6]"""
+    traj, agents = np.asarray(traj, dtype=np.float64), np.asarray(agents, dtype=np.float64)
+    with open(path, "wb") as f:
+        f.write(np.array(traj.shape[:2] + agents.shape[:2], np.int32).tobytes())
+        f.write(np.array([margin], np.float64).tobytes())
+        for a in (m_of, a_of, scene_of):
+            f.write(np.asarray(a, np.int32).tobytes())
+        f.write(np.ascontiguousarray(traj[:, :, :3]).tobytes())
+        f.write(np.ascontiguousarray(agents).tobytes())

@@ -4,14 +4,15 @@
   counts of the healthy scenarios and those of the five scenarios that are to overflow them.  Every scenario says what it is meant to
   be (`kind`); tests/test_chain_stops_cpu.py shows with oracle/corridor_oracle.py alone that each count lies on the intended side of its
   threshold, tests/test_gpu_chain_stops.py runs the batch.
-* steps_one_by_one(): the chain for one scenario through the per-step host entry points, and where it stops - the precedence of the stop
-  sites restated here, step by step in the order the reference runs them (it does not come from the library's own table).
+* tests/chain_util.py has the scenarios' way through the chain, steps_one_by_one(): one scenario through the per-step host entry points, and
+  where it stops.
 """
 import numpy as np
 
 import corridor_oracle as K
 from path_optimizer_2_amd import capi
 from path_optimizer_2_amd.synth import make_scene
+from shared_util import oracle_geom
 
 # stages (include/pqp.h, pqp_chain_stage)
 OK, FEW_POINTS, SMOOTHER_FAILED, SEARCH_FAILED, SHORT_REFERENCE, POST_SMOOTH_FAILED, HEADING, BLOCKED, PATH_QP_FAILED, CAPACITY = range(10)
@@ -27,11 +28,6 @@ N_MAPS = 4
 def sample_min(method):
     """the fewest samples the smoother QP takes: 3 (TensionSmoother2), 4 (TensionSmoother: the third-difference window)"""
     return 4 if method == capi.SMOOTHING_TENSION else 3
-
-
-def smoother_params():
-    # the reference's smoother setting (OSQP default eps 1e-3) + the KKT-verified polish, as test_gpu_chain does
-    return capi.default_params(eps_abs=1e-3, eps_rel=1e-3, polish=1, polish_every=25, adaptive_rho_interval=25)
 
 
 def _along(c, at):
@@ -117,7 +113,7 @@ def mixed_batch(seed=5):
             # behind the vehicle and the cells around the pit keep their distance, so every earlier step runs as on the open road.
             layer = dist[map_of[b]].copy()
             px, py = start[b, 0] - np.cos(start[b, 2]), start[b, 1] - np.sin(start[b, 2])
-            g = grid_geom(c)
+            g = oracle_geom(c)
             ii, jj = np.meshgrid(np.arange(g.rows), np.arange(g.cols), indexing="ij")
             cx = g.pos_x + (g.length_x / 2 - g.resolution / 2) - g.resolution * ii          # K.grid_cell_position
             cy = g.pos_y + (g.length_y / 2 - g.resolution / 2) - g.resolution * jj
@@ -146,13 +142,6 @@ def all_healthy(sc):
     return out
 
 
-def grid_geom(c):
-    """the oracle's GridGeom of a synth scene or of a PqpGridGeometry"""
-    if isinstance(c, dict):
-        return K.GridGeom(c["rows"], c["cols"], c["resolution"], c["length"][0], c["length"][1], c["pos"][0], c["pos"][1])
-    return K.GridGeom(c.rows, c.cols, c.resolution, c.length_x, c.length_y, c.pos_x, c.pos_y)
-
-
 def bspline_degree(p):
     """the degree ReferencePathSmoother::bSpline picks for the polygon p (reference_path_smoother.cpp:495-505)"""
     mean = np.hypot(np.diff(p[:, 0]), np.diff(p[:, 1])).sum() / (len(p) - 1)
@@ -163,85 +152,3 @@ def raw_line(p):
     """the oracle's raw line of the polygon p: (spline x(s), spline y(s), s list)"""
     x, y, s = K.bspline_resample(p)
     return K.spline_fit(s, x), K.spline_fit(s, y), s
-
-
-# ---- the chain, one scenario and one step at a time -------------------------------------------------------------------------------------
-def steps_one_by_one(h, hs, sc, b, cfg, p_max=None):
-    """The chain for scenario b alone, exact sizes, through the per-step host-pointer entry points (each pinned to its oracle elsewhere),
-    and where it stops: dict(stage, status, site) - site names the capacity for stage 9 - plus nv and out where a path QP ran.
-    The stop sites in the order of the steps (the reference's `return false` sites and what stands in their way here):
-      n_points < 4                                   FEW_POINTS       reference_path_smoother.cpp:33-36
-      n_points > p_max, or not above the degree      FEW_POINTS       no raw line: bSpline gives no points (tinyspline refuses the spline)
-      raw points > raw_max                           CAPACITY
-      samples > sample_max, samples < 3 (TENSION: 4) CAPACITY         (two raw points: a polygon below 1 m, whose 1 m samples are two)
-      smoother QP not SOLVED                         SMOOTHER_FAILED
-      layers > layer_max                             CAPACITY
-      no layer                                       SEARCH_FAILED
-      fewer than 4 layers                            SHORT_REFERENCE
-      postSmooth QP not SOLVED                       POST_SMOOTH_FAILED
-      initial heading error > 75 degrees             HEADING
-      reference states > n_max                       CAPACITY
-      fewer than 2 waypoints before the road closes  BLOCKED
-      path QP not SOLVED                             PATH_QP_FAILED, with its status
-    p_max: the width of the batch's point array (None: sc["pts"].shape[1])."""
-    P = int(sc["n_pts"][b])
-    p_max = sc["pts"].shape[1] if p_max is None else p_max
-    mo = sc["map_of"][b:b + 1]
-    st, tg = sc["start"][b:b + 1], sc["target"][b:b + 1]
-    k0 = float(sc["start_k"][b]) if "start_k" in sc else 0.0
-    stop = lambda stage, site=None: dict(stage=stage, status=0, site=site)          # (0: PQP_STATUS_UNSOLVED, the status of a scenario no path QP ran for)
-    if P < 4 or P > p_max:
-        return stop(FEW_POINTS)
-    r = h.bspline_resample(sc["pts"][b:b + 1, :P], np.array([P], dtype=np.int32), cfg.raw_max)
-    n0 = int(r["count"][0])
-    if n0 == 0:
-        return stop(FEW_POINTS)
-    if n0 > cfg.raw_max:
-        return stop(CAPACITY, "raw_max")
-    if n0 < 3:
-        # two raw points (t = 0 and t = 1) are what a polygon shorter than 1 m gives: tk::spline takes no such line, and its samples at
-        # 0 and 1 m are fewer than any smoother QP takes
-        return stop(CAPACITY, "sample_min")
-    x0, y0, s0 = (r[k][:, :n0] for k in ("x", "y", "s"))
-    tab, ext = h.spline_fit(s0, x0, y0)
-    seg = h.segment_raw_reference(tab, ext, s0[:, -1].copy(), cfg.sample_max)
-    n1 = int(seg["count"][0])
-    if n1 > cfg.sample_max:
-        return stop(CAPACITY, "sample_max")
-    if n1 < sample_min(cfg.smoothing_method):
-        return stop(CAPACITY, "sample_min")
-    if cfg.smoothing_method == capi.SMOOTHING_TENSION:
-        gx, gy = seg["x"][:, :n1], seg["y"][:, :n1]
-        clr = np.array([[K.obstacle_distance(sc["dist"][mo[0]], sc["geom"], gx[0, i], gy[0, i]) for i in range(n1)]])
-        sm = hs.smooth_tension(gx, gy, seg["angle"][:, :n1], clr)
-    else:
-        sm = hs.smooth_tension2(*(seg[k][:, :n1] for k in ("x", "y", "angle", "k", "s")))
-    if sm["status"][0] != 1:
-        return stop(SMOOTHER_FAILED)
-    tab, ext = h.spline_fit(sm["s"], sm["x"], sm["y"])
-    ls, lb, ub, cnt, vl = h.dp_corridor(tab, ext, sm["s"][:, -1] + cfg.smoothed_length_margin, st, sc["dist"], sc["geom"], max_layers=cfg.layer_max, map_of=mo)
-    k = int(cnt[0])
-    if k < 0:
-        return stop(CAPACITY, "layer_max")
-    if k == 0:
-        return stop(SEARCH_FAILED)
-    if k < 4:
-        return stop(SHORT_REFERENCE)
-    ps = hs.post_smooth(ls[:, :k].copy(), lb[:, :k].copy(), ub[:, :k].copy(), vl)
-    if ps["status"][0] != 1:
-        return stop(POST_SMOOTH_FAILED)
-    x2, y2, s2 = h.offsets_to_points(tab, ext, ls[:, :k].copy(), ps["l"])
-    tab, ext = h.spline_fit(s2, x2, y2)
-    max_s = h.reference_length(tab, ext, s2[:, -1].copy(), tg)
-    ref, count, err = h.reference_states(tab, ext, max_s, cfg.n_max, start=st, ds_small=cfg.output_spacing / 2, ds_large=cfg.output_spacing, dynamic=True)
-    if abs(err[0, 1]) > 75.0 * np.pi / 180.0:
-        return stop(HEADING)
-    if count[0] > cfg.n_max:
-        return stop(CAPACITY, "n_max")
-    bounds, nv = h.corridor_bounds(ref, tab, ext, sc["dist"], sc["geom"], map_of=mo, n_of=count)
-    if nv[0] < 2:
-        return stop(BLOCKED)
-    scal = np.array([[err[0, 0], err[0, 1], k0, tg[0, 2], 1.0 if nv[0] < count[0] else 0.0, cfg.max_steering_angle]])
-    res = h.solve_var(nv, ref, bounds, scal, passes=1)
-    status = int(res["status"][0])
-    return dict(stage=OK if status == 1 else PATH_QP_FAILED, status=status, site=None, nv=int(nv[0]), out=res["out"][0])

@@ -51,11 +51,12 @@ def rows_close(got, want, what):
 
 def tab_close(tab, ext, want_tab, want_ext=None):
     """a device spline table against a restatement / golden one: knots and values exact, coefficient rows to SPLINE_TOL of the row's largest"""
-    assert np.array_equal(np.asarray(tab)[[0, 1, 5]], np.asarray(want_tab)[[0, 1, 5]])
+    assert np.array_equal(np.asarray(tab)[[0, 1, 5]], np.asarray(want_tab)[[0, 1, 5]]), "knots or values of the spline table differ"
     for r in (2, 3, 4, 6, 7, 8):
         rows_close(tab[r], want_tab[r], ("row", r))
     if want_ext is not None:
-        assert np.abs(np.asarray(ext) - np.asarray(want_ext)).max() <= SPLINE_TOL * max(1.0, float(np.abs(want_ext).max()))
+        assert np.abs(np.asarray(ext) - np.asarray(want_ext)).max() <= SPLINE_TOL * max(1.0, float(np.abs(want_ext).max())), \
+            ("spline end coefficients", np.abs(np.asarray(ext) - np.asarray(want_ext)).max())
 
 
 DP_D_FLAG = 1e-6        # a `d < 1.2` / `d > 1.2` test this close to the threshold may come out either way: > 4 ulp of the float32 threshold

@@ -98,3 +98,17 @@ def to_reference_order(wx, wy, wye, n, precise=None):
             y[4 * n + 2 * precise + (i - precise)] = wy[i, 4]
     y[-2:] = wye
     return x, y
+
+
+def compare_counts(dev, emu, what):
+    """the device against the emulation, QP by QP: statuses, reduced-solve counts (info[5]) and factorisation counts (info[6]) all equal"""
+    st = dev["status"] != emu["status"]
+    kkt = dev["info"][:, 5] != emu["info"][:, 5]
+    fac = dev["info"][:, 6] != emu["info"][:, 6]
+    d = np.abs(dev["out"][:, :, 3:5] - emu["out"][:, :, 3:5]).max()
+    print(f"{what}: {len(st)} QPs, solved {int((dev['status'] == 1).sum())}; differing statuses {int(st.sum())}, reduced-solve counts {int(kkt.sum())}, "
+          f"factorisation counts {int(fac.sum())}; mean solves {dev['info'][:, 5].mean():.2f}, factorisations {dev['info'][:, 6].mean():.2f}; "
+          f"max |l, d_heading| device - emulation {d:.1e}")
+    assert not st.any(), np.nonzero(st)[0][:8]
+    assert not kkt.any(), (np.nonzero(kkt)[0][:8], dev["info"][kkt, 5][:8], emu["info"][kkt, 5][:8])
+    assert not fac.any(), (np.nonzero(fac)[0][:8], dev["info"][fac, 6][:8], emu["info"][fac, 6][:8])

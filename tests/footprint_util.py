@@ -9,6 +9,8 @@ import numpy as np
 
 import corridor_oracle as K
 
+FOOTPRINT_TOL = 1e-5             # the device's margins against this restatement's (tests/test_gpu_footprint.py), and near_threshold's default
+
 
 def car_circles(width=2.0, rear_length=-1.0, front_length=3.9):
     """[7][3]: x, y, r of rr, rl, fr, fl, fm, rm, then the bounding circle, in the vehicle frame.  The checker's car is

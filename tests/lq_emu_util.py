@@ -92,3 +92,8 @@ def timed_rate(make_sample, n, budget_s=6.0):
     return {"value": k / dt, "unit": "paths/s", "cores": cores, "per_core": k / dt / cores, "solved": int((r["status"] == 1).sum()),
             "sample": f"{k} paths of the bench distribution (N={n}) in {dt:.1f} s: csrc/pqp_path_lq.hpp (interior-point + active-set rounds, every path the "
                       f"exact optimum) compiled for the host with g++ -O3 -march=native -fopenmp, one QP per task over {cores} threads"}
+
+
+# QPs on which the plain active-set rounds cycle - from the interior point of every attempt - until the rounds run out (found by
+# tools/lq_robustness_sweep.py-style sweeps of 16 384 ... 131 072 QPs per size; none at 300 waypoints or fewer): (n, profile, seed, QP)
+CYCLING = [(512, "varied", None, 5742), (1000, "varied", 3001, 1450), (1000, "uniform", 3007, 3912)]

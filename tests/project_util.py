@@ -7,6 +7,7 @@ import numpy as np
 import corridor_oracle as K
 
 AT_END, BEFORE_START, NOT_CONVERGED, NOT_FINITE = 1, 2, 4, 8
+PROJECT_TOL = 1e-9                # tests/test_gpu_corridor.py's rule for pqp_reference_length: the same search, ocml against libm in sqrt / atan2 / sin / cos
 MAX_LENGTH = 1048576.0           # include/pqp.h: a longer (or infinite) line is refused like a point that is not finite
 
 
@@ -112,3 +113,11 @@ def scattered_points(c, length, count, seed):
         pts[i, :2] = point_at(c["sx"], c["sy"], s0, off)
         pts[i, 2] = rng.uniform(-math.pi, math.pi)
     return pts
+
+
+def write_case(path, s, x, y, points):
+    """the file tests/cpp/project_demo.cpp reads"""
+    with open(path, "wb") as f:
+        f.write(np.array([len(s), len(points)], np.int32).tobytes())
+        for a in (s, x, y, points):
+            f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())

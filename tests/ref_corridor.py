@@ -386,3 +386,12 @@ def reference():
             v.setflags(write=False)
         _REFERENCE = want
     return _REFERENCE
+
+
+NEAR_TOL = 1e-5              # footprint_util.near_threshold's: a clearance this close to the value it is tested against may fall either way on the device
+
+
+def footprint_near(ref, name):
+    """[n] bool: some circle of the state (the six or the bounding one) has |recorded clearance - radius| < NEAR_TOL"""
+    d = ref[f"footprint_{name}_distance"].astype(np.float64)
+    return (np.abs(d - ref[f"footprint_{name}_radius"][None]) < NEAR_TOL).any(axis=1)

@@ -94,15 +94,6 @@ def sample_batch(paths, profile, m, n_of=None, stop_before=None, t0=None, dt=0.1
     return np.stack([g[0] for g in got]), np.array([g[1] for g in got], np.int32), np.array([g[2] for g in got], np.int32)
 
 
-def same_bits(a, b):
-    """bit for bit, NaNs (whose sign and payload are no part of IEEE arithmetic) in the same places"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    if a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint64), b[~nb].view(np.uint64)))
-
-
 def seeded_path(rng, c, stride=7, step=(0.15, 1.0)):
     """[c][stride]: a slowly turning path of c waypoints, a chord of 0.15 to 1 m, heading across the +-pi seam, noise in the unused columns"""
     d = rng.uniform(step[0], step[1], c)
@@ -126,3 +117,15 @@ def seeded_profile(rng, path, v_lo=0.5, v_hi=8.0):
         prof[:-1, 2] = np.where(d > 0, (w[1:] - w[:-1]) / (2.0 * np.where(d > 0, d, 1.0)), 0.0)
         prof[1:, 3] = np.cumsum(np.where(d > 0, 2.0 * d / (v[:-1] + v[1:]), 0.0))
     return prof
+
+
+def write_case(path, paths, profile, m, n_of, stop_before, t0, dt, hold_last):
+    """the file tests/cpp/sample_demo.cpp reads; paths [B][n][stride >= 6], profile [B][n][4]"""
+    paths, profile = np.asarray(paths, dtype=np.float64), np.asarray(profile, dtype=np.float64)
+    with open(path, "wb") as f:
+        f.write(np.array(paths.shape[:2] + (m, hold_last), np.int32).tobytes())
+        f.write(np.array([dt], np.float64).tobytes())
+        f.write(np.asarray(n_of, np.int32).tobytes())
+        f.write(np.asarray(stop_before, np.int32).tobytes())
+        f.write(np.asarray(t0, np.float64).tobytes())
+        f.write(np.ascontiguousarray(np.concatenate([paths[:, :, [0, 1, 2, 5]], profile], axis=2)).tobytes())

@@ -106,3 +106,13 @@ def select(paths, group_start, n_of=None, status=None, stage=None, first_collisi
     best = winners(t, group_start)
     bp, bn = best_rows(paths, n_of, best)
     return dict(terms=t, best=best, best_paths=bp, best_n=bn)
+
+
+def write_candidates(path, candidates, group_start):
+    """the file tests/cpp/select_demo.cpp reads"""
+    with open(path, "wb") as f:
+        f.write(np.array([len(candidates), len(group_start) - 1], np.int32).tobytes())
+        f.write(np.asarray(group_start, np.int32).tobytes())
+        for c in candidates:
+            f.write(np.array([len(c)], np.int32).tobytes())
+            f.write(np.ascontiguousarray(c, dtype=np.float64).tobytes())

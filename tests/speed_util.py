@@ -201,3 +201,15 @@ def seeded_path(rng, n, stride=7):
     p[:, 5] = rng.normal(0.0, 0.15, n) * (rng.random(n) > 0.2)
     p[:, 2] = heading
     return p
+
+
+def write_case(path, paths, n_of, stop_before, v_start, v_end):
+    """the file tests/cpp/speed_demo.cpp reads; paths [B][n][stride >= 6]"""
+    paths = np.asarray(paths, dtype=np.float64)
+    with open(path, "wb") as f:
+        f.write(np.array(paths.shape[:2], np.int32).tobytes())
+        f.write(np.asarray(n_of, np.int32).tobytes())
+        f.write(np.asarray(stop_before, np.int32).tobytes())
+        f.write(np.asarray(v_start, np.float64).tobytes())
+        f.write(np.asarray(v_end, np.float64).tobytes())
+        f.write(np.ascontiguousarray(paths[:, :, [0, 1, 5]]).tobytes())

@@ -9,8 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from build_util import declared as _declared
 from path_optimizer_2_amd import capi, pqp_header
-from test_capi_symbols import _declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")

@@ -12,42 +12,22 @@ import numpy as np
 import pytest
 
 import agents_util as A
+import build_util
+import cpp_demo
 import footprint_util as F
 from path_optimizer_2_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "agents_demo")
 NAMES = ("pqp_agents_check", "pqp_agents_check_device")
 HAND_CIRCLES = F.car_circles(**A.HAND_CAR)
 INF = math.inf
 
 
-def build_demo():
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", EXE,
-                    os.path.join(ROOT, "tests", "cpp", "agents_demo.cpp"), "-L" + CSRC, "-lpqp_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return EXE
-
-
-def write_case(path, traj, agents, margin, m_of, a_of, scene_of):
-    """the file tests/cpp/agents_demo.cpp reads; traj [B][m][stride >= 3], agents [n_scenes][a_max][m][6]"""
-    traj, agents = np.asarray(traj, dtype=np.float64), np.asarray(agents, dtype=np.float64)
-    with open(path, "wb") as f:
-        f.write(np.array(traj.shape[:2] + agents.shape[:2], np.int32).tobytes())
-        f.write(np.array([margin], np.float64).tobytes())
-        for a in (m_of, a_of, scene_of):
-            f.write(np.asarray(a, np.int32).tobytes())
-        f.write(np.ascontiguousarray(traj[:, :, :3]).tobytes())
-        f.write(np.ascontiguousarray(agents).tobytes())
-
-
 # ---- the interface ---------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_bound(hip_lib):
-    import test_capi_symbols as T
     for nm in NAMES + ("pqp_agents_default_params",):
         assert nm in capi.EXPORTS and hasattr(hip_lib, nm), nm
-    assert set(T._declared()) == set(capi.EXPORTS)
+    assert set(build_util.declared()) == set(capi.EXPORTS)
     assert len(hip_lib.pqp_agents_check_device.argtypes) == 17 and len(hip_lib.pqp_agents_check.argtypes) == 16      # the host form: no frames
     assert list(inspect.signature(capi.Handle.agents_check).parameters) == ["self", "traj", "agents", "m_of", "a_of", "scene_of", "car", "prm",
                                                                             "clearance"]
@@ -119,27 +99,26 @@ def test_agents_arguments_of_the_chain_wrapper_are_checked_on_the_host(hip_lib):
 
 
 def test_checker_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
-    exe = build_demo()
+    exe = cpp_demo.build("agents_demo")
     import torch
     if torch.cuda.is_available():
         return
     path = tmp_path / "case.bin"
     c = A.hand_cases()["parked_box"]
-    write_case(path, c["traj"], c["agents"], c["margin"], [A.HAND_M], [1], [0])
+    A.write_case(path, c["traj"], c["agents"], c["margin"], [A.HAND_M], [1], [0])
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no checker" in r.stderr
 
 
 def test_checker_compiles_against_the_reference_headers():
     """with PQP_USE_REFERENCE_TYPES the checker reads the reference's own State (include/data_struct/data_struct.hpp:14-26)"""
-    import test_project_points as T
-    if not os.path.isdir(T.REF_INCLUDE):
+    if not os.path.isdir(cpp_demo.REF_INCLUDE):
         pytest.skip("the reference tree is not on this box")
     src = ("#include \"pqp_agent_checker.hpp\"\n"
            "using namespace PathOptimizationNS;\n"
            "bool f(AgentChecker& c, const std::vector<std::vector<State>>& a, const std::vector<std::vector<SlState>>& b,\n"
            "       const std::vector<std::vector<std::vector<PredictedAgent>>>& s, std::vector<int>* o) { return c.check(a, s, o, o) && c.check(b, s, o, o); }\n")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + T.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
            "-include", "data_struct/data_struct.hpp", "-"]
     r = subprocess.run(cmd, input=src, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -152,8 +131,7 @@ def test_the_kernels_use_no_scratch_and_no_lds(hip_lib, name, tag, vgprs, occupa
     """what the build gives today: 38 VGPRs for the frames, 94 with the clearance written and 106 without (the broad phase's operands),
     each held to the allocation granule of 8 it falls in (40, 96, 112) and to the occupancy that follows from it; an occupancy below 4
     would be a lane state that no longer fits 128 registers"""
-    import test_kernel_resources as R
-    r = R._find(R._report(), name, tag)
+    r = build_util.find_kernel(build_util.kernel_report(), name, tag)
     assert r["ScratchSize"] == 0, r
     assert r["LDS Size"] == 0, r
     assert r["VGPRs Spill"] == 0 and r["SGPRs Spill"] == 0, r
@@ -276,10 +254,9 @@ def test_hits_at_the_edge_of_the_broad_phase_would_be_lost_to_a_smaller_radius()
 def test_seeds_of_the_gpu_test_stay_clear_of_the_margin():
     """the samples whose hit a few ulp of sin / cos could flip, |clear - margin| <= 1e-9, are at most 0.1 % for every seeded case the GPU
     test runs (essentially none: the placements are continuous) - and the cases do hold hits, near misses and clear paths"""
-    import test_gpu_agents_check as G
     circles = F.car_circles()
     kinds = set()
-    for case in G.seeded_cases():
+    for case in A.seeded_cases():
         r = A.check(case["traj"], case["agents"], circles, case["m_of"], case["a_of"], case["scene_of"], case["margin"])
         near = A.near_margin(r["clear"], case["margin"])
         checked = sum(n.size for n in near)

@@ -1,19 +1,9 @@
 """CPU-side check of the drop-in boundary: the C-ABI library builds for gfx950, loads, and exports every
 symbol include/pqp.h declares.  No compute calls (there is no GPU here)."""
 import ctypes as C
-import os
-import re
 
+from build_util import declared as _declared
 from path_optimizer_2_amd import capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared():
-    txt = open(os.path.join(ROOT, "include", "pqp.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(pqp_[a-z_0-9]+)\s*\(", txt)))
-
 
 def test_header_symbols_are_exported(hip_lib):
     names = _declared()

@@ -13,6 +13,7 @@ import pytest
 
 import chain_stops_util as CS
 import corridor_oracle as K
+from shared_util import oracle_geom
 
 R, S, L, N = (CS.MIXED_CFG[k] for k in ("raw_max", "sample_max", "layer_max", "n_max"))
 MARGIN = 2
@@ -29,7 +30,7 @@ def _counts(sc, b, upto="all", map_of=None):
     search keeps), vehicle_l, heading_err, ref_count, n_valid"""
     P = int(sc["n_pts"][b])
     p = sc["pts"][b, :P]
-    g = CS.grid_geom(sc["geom"])
+    g = oracle_geom(sc["geom"])
     dist = sc["dist"][(sc["map_of"] if map_of is None else map_of)[b]]
     out = {}
     x, y, s = K.bspline_resample(p)

@@ -8,20 +8,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_demo
 from path_optimizer_2_amd import capi
 from path_optimizer_2_amd.synth import make_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "footprint_demo")
 
 
 @pytest.fixture(scope="module")
 def demo_exe(hip_lib):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", EXE,
-                    os.path.join(ROOT, "tests", "cpp", "footprint_demo.cpp"), "-L" + CSRC, "-lpqp_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return EXE
+    return cpp_demo.build("footprint_demo")
 
 
 def _scene(tmp_path):

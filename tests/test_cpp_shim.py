@@ -7,53 +7,36 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_demo
 import pqp_oracle as O
+from cpp_demo import shim_scenario_text as _scenario_text
 from path_optimizer_2_amd.synth import make_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "shim_demo")
 
 
 @pytest.fixture(scope="module")
 def shim_exe(hip_lib):
-    src = [os.path.join(ROOT, "tests", "cpp", "shim_demo.cpp"), os.path.join(CSRC, "base_solver_shim.cpp")]
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", EXE] + src + ["-L" + CSRC, "-lpqp_hip", "-Wl,-rpath," + CSRC], check=True)
-    return EXE
+    return cpp_demo.build("shim_demo", hip=False, extra=[cpp_demo.SHIM])
 
 
 @pytest.fixture(scope="module")
 def latency_exe(hip_lib):
-    exe = os.path.join(ROOT, "tests", "cpp", "shim_latency")
-    src = [os.path.join(ROOT, "tests", "cpp", "shim_latency.cpp"), os.path.join(CSRC, "base_solver_shim.cpp")]
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe] + src + ["-L" + CSRC, "-lpqp_hip", "-Wl,-rpath," + CSRC], check=True)
-    return exe
+    return cpp_demo.build("shim_latency", hip=False, extra=[cpp_demo.SHIM])
 
 
-REF_INCLUDE = "/root/reference/include"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_INCLUDE), reason="the reference tree is not on this box")
+@pytest.mark.skipif(not os.path.isdir(cpp_demo.REF_INCLUDE), reason="the reference tree is not on this box")
 @pytest.mark.parametrize("unit", ["path_optimizer_2_amd/csrc/base_solver_shim.cpp", "include/pqp_batched_solver.hpp"])
 def test_drop_in_mode_compiles_against_the_reference_headers(unit):
     """with PQP_USE_REFERENCE_TYPES the shim and the batched solver use the reference's OWN ReferencePath /
     VehicleState / SlState (include/data_struct/*.hpp, std-only) instead of include/pqp_types.hpp.  Pinned here as a compile check of
     exactly that configuration (syntax + types; the link step needs the reference's objects)."""
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
            "-include", "data_struct/data_struct.hpp", "-include", "data_struct/reference_path.hpp", "-include", "data_struct/vehicle_state_frenet.hpp",
            os.path.join(ROOT, unit)]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert "error" not in r.stderr
-
-
-def _scenario_text(b, q):
-    n = b["ref"].shape[1]
-    lines = [str(n)]
-    for i in range(n):
-        lines.append(" ".join(repr(float(v)) for v in list(b["ref"][q, i]) + list(b["bounds"][q, i])))
-    lines.append(" ".join(repr(float(v)) for v in b["scal"][q]))
-    return "\n".join(lines) + "\n"
 
 
 def test_shim_builds_and_fails_cleanly_without_gpu(shim_exe):

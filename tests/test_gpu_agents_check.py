@@ -18,13 +18,14 @@ import numpy as np
 import pytest
 
 import agents_util as A
+import chain_util
+import cpp_demo
 from path_optimizer_2_amd import capi
+from shared_util import same_bits
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
-MS = (1, 63, 64, 65, 130)
-BATCHES = (1, 4, 5)
-AGENTS = (0, 1, 3)
+MS, BATCHES, AGENTS = A.MS, A.BATCHES, A.AGENTS
 
 
 @pytest.fixture(scope="module")
@@ -39,28 +40,10 @@ def circles():
     return capi.car_circles()
 
 
-def _seeded(m, B, a_max):
-    """one case per shape, the seed from the shape: two scenes, ragged a_of and m_of (a 0 among them when the batch allows), stride 3 or 8"""
-    rng = np.random.default_rng(1000 * m + 10 * B + a_max)
-    stride = 3 if (m + B + a_max) % 2 else 8
-    traj, agents = A.seeded_case(rng, B, m, 2, a_max, stride=stride)
-    m_of = rng.integers(0, m + 1, B).astype(np.int32)
-    m_of[0] = m
-    if B > 1:
-        m_of[1] = 0
-    a_of = np.array([a_max, max(a_max - 1, 0)], np.int32)
-    scene_of = (np.arange(B) % 2).astype(np.int32)
-    return dict(id=f"m{m}-B{B}-A{a_max}", traj=traj, agents=agents, m_of=m_of, a_of=a_of, scene_of=scene_of, margin=0.3 if a_max == 3 else 0.0)
-
-
-def seeded_cases():
-    return [_seeded(m, B, a) for m in MS for B in BATCHES for a in AGENTS]
-
-
 @functools.lru_cache(maxsize=None)
 def _reference(m, B, a_max):
     """computed once per shape and shared; nobody writes to it"""
-    c = _seeded(m, B, a_max)
+    c = A.seeded(m, B, a_max)
     return c, A.check(c["traj"], c["agents"], circles(), c["m_of"], c["a_of"], c["scene_of"], c["margin"])
 
 
@@ -129,7 +112,7 @@ def test_frames_against_the_restatement(handle):
     got = _device(handle, c)[0]
     want = A.frames(agents)
     assert got.shape == want.shape == (3, 4, 70, 8)
-    assert A.same_bits(got[..., [0, 1, 4, 5, 6, 7]], want[..., [0, 1, 4, 5, 6, 7]])
+    assert same_bits(got[..., [0, 1, 4, 5, 6, 7]], want[..., [0, 1, 4, 5, 6, 7]])
     d = float(np.abs(got[..., 2:4] - want[..., 2:4]).max())
     print(f"frames: max |cos, sin - libm| = {d:.3e}")
     assert d <= 1e-15
@@ -166,14 +149,14 @@ def test_the_hand_cases_bit_for_bit(handle):
     import footprint_util as F
     car = capi.car_default_geometry(**A.HAND_CAR)
     hand = capi.car_circles(car)
-    assert A.same_bits(hand, F.car_circles(**A.HAND_CAR))
+    assert same_bits(hand, F.car_circles(**A.HAND_CAR))
     for name, c in A.hand_cases().items():
         want = A.check(c["traj"], c["agents"], hand, m_of=c.get("m_of"), margin=c["margin"])
         for clearance in (True, False):
             got = _host(handle, c, clearance=clearance, car=car)
             assert (got["first_hit"][0], got["hit_agent"][0]) == (want["first_hit"][0], want["hit_agent"][0]), (name, clearance)
             if clearance:
-                assert A.same_bits(got["clearance"], want["clearance"]), name
+                assert same_bits(got["clearance"], want["clearance"]), name
     # the grazing pair, spelled out: exactly the margin is no hit, one ulp of the box's coordinate nearer is
     cases = A.hand_cases()
     assert _host(handle, cases["grazing"], car=car)["first_hit"][0] == A.HAND_M
@@ -250,9 +233,9 @@ def test_same_bits_at_any_position_in_any_batch_from_either_form(handle):
         d = dict(traj=traj, agents=agents, m_of=m_of, a_of=np.array([2, c["a_of"][0], 3], np.int32), scene_of=scene_of, margin=c["margin"])
         got = _host(handle, d)
         assert got["first_hit"][at] == first["first_hit"][src] and got["hit_agent"][at] == first["hit_agent"][src], (B, at)
-        assert A.same_bits(got["clearance"][at], first["clearance"][src]), (B, at)
+        assert same_bits(got["clearance"][at], first["clearance"][src]), (B, at)
         fr, f, w, cl = _device(handle, d)                    # outputs and a workspace that held -7: fully overwritten
-        assert np.array_equal(f, got["first_hit"]) and np.array_equal(w, got["hit_agent"]) and A.same_bits(cl, got["clearance"]), (B, at)
+        assert np.array_equal(f, got["first_hit"]) and np.array_equal(w, got["hit_agent"]) and same_bits(cl, got["clearance"]), (B, at)
         assert not (fr == -7.0).any()
         f2, w2 = _device(handle, d, clearance=False)[1:3]
         assert np.array_equal(f2, f) and np.array_equal(w2, w)
@@ -273,10 +256,10 @@ def test_values_that_are_not_numbers_stay_in_their_path_and_scene(handle):
     _compare(got["first_hit"], got["hit_agent"], got["clearance"], bad, want, "hostile")
     for b in (0, 4):                                         # scene 0, their own rows clean: the same bits as before
         assert got["first_hit"][b] == clean["first_hit"][b] and got["hit_agent"][b] == clean["hit_agent"][b]
-        assert A.same_bits(got["clearance"][b], clean["clearance"][b])
+        assert same_bits(got["clearance"][b], clean["clearance"][b])
     assert got["clearance"][2, 40] == -math.inf and got["clearance"][2, 90] == -math.inf
     others = np.delete(np.arange(130), [40, 90])
-    assert A.same_bits(got["clearance"][2, others], clean["clearance"][2, others])
+    assert same_bits(got["clearance"][2, others], clean["clearance"][2, others])
     assert got["first_hit"][2] == min(40, clean["first_hit"][2])
     for b in (1, 3):
         assert got["clearance"][b, 5] == -math.inf and got["clearance"][b, 17] == -math.inf
@@ -292,7 +275,7 @@ def test_a_scene_outside_the_range_is_clamped_by_the_device_form(handle):
     wild = dict(c, scene_of=np.array([-5, 7, 2 ** 31 - 1, -2 ** 31, 1], np.int32))
     tame = dict(c, scene_of=np.array([0, 1, 1, 0, 1], np.int32))
     got, ref = _device(handle, wild), _device(handle, tame)
-    assert np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and A.same_bits(got[3], ref[3])
+    assert np.array_equal(got[1], ref[1]) and np.array_equal(got[2], ref[2]) and same_bits(got[3], ref[3])
     want = A.check(wild["traj"], wild["agents"], circles(), wild["m_of"], wild["a_of"], wild["scene_of"], wild["margin"])
     _compare(got[1], got[2], got[3], wild, want, "clamped")
     with pytest.raises(capi.PqpError, match="pqp_agents_check: scene_of outside"):
@@ -352,10 +335,8 @@ def test_the_check_behind_the_chain(hip_lib):
     """optimize_path(..., speed=, sample=, samples=, agents=) = the chain, the speed profile, the sampler and pqp_agents_check one after the
     other: what it adds equals the stand-alone host call on the traj it returns - on every candidate's samples, the parked car's included
     with hold_last, and with select on the winners' samples that lie on the path"""
-    import test_gpu_chain as T
-    import test_gpu_select_paths as TS
     B, m = 16, 40
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     gs = np.array([0, 8, 16], np.int32)
     sp = capi.speed_default_params(v_max=8.0)
     # scene s: agent 0 drives from candidate s's target back to its start, agent 1 stands beside that start, agent 2 is a pedestrian far away
@@ -376,7 +357,7 @@ def test_the_check_behind_the_chain(hip_lib):
                                   agents=agents, agents_of=a_of, scene_of=scene_all, agents_params=ap)),
                      ("select", dict(select=gs, speed=sp, v_start=np.array([2.0, 5.0]), sample=capi.sample_default_params(dt=0.2), samples=m,
                                      agents=agents, agents_of=a_of, scene_of=scene_grp, agents_params=ap))):
-        h, hs = TS._chain_handles(B)
+        h, hs = chain_util.handles(B)
         if name == "all":
             with pytest.raises(ValueError, match="scene_of must have one entry per candidate"):
                 h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs,
@@ -389,10 +370,10 @@ def test_the_check_behind_the_chain(hip_lib):
     h = capi.Handle(capi.default_params(), max_batch=8, max_n=16)
     want = h.agents_check(every["traj"], agents, m_of=None, a_of=a_of, scene_of=scene_all, prm=ap, clearance=True)
     assert np.array_equal(every["first_hit"], want["first_hit"]) and np.array_equal(every["hit_agent"], want["hit_agent"])
-    assert A.same_bits(every["agent_clearance"], want["clearance"])
+    assert same_bits(every["agent_clearance"], want["clearance"])
     want = h.agents_check(sel["traj"], agents, m_of=sel["traj_n"], a_of=a_of, scene_of=scene_grp, prm=ap, clearance=True)
     assert np.array_equal(sel["first_hit"], want["first_hit"]) and np.array_equal(sel["hit_agent"], want["hit_agent"])
-    assert A.same_bits(sel["agent_clearance"], want["clearance"])
+    assert same_bits(sel["agent_clearance"], want["clearance"])
     h.close()
     ref = A.check(every["traj"], agents, circles(), None, a_of, scene_all, 0.2)
     worst = _compare(every["first_hit"], every["hit_agent"], every["agent_clearance"], dict(traj=every["traj"], margin=0.2), ref, "chain")
@@ -402,11 +383,10 @@ def test_the_check_behind_the_chain(hip_lib):
 
 # ---- C++ -------------------------------------------------------------------------------------------------------------------------------
 def test_checker_agrees_with_the_python_call(handle, tmp_path):
-    import test_agents_check as T
-    exe = T.build_demo()
+    exe = cpp_demo.build("agents_demo")
     c, _ = _reference(65, 5, 3)
     path = tmp_path / "case.bin"
-    T.write_case(path, c["traj"], c["agents"], c["margin"], c["m_of"], c["a_of"], c["scene_of"])
+    A.write_case(path, c["traj"], c["agents"], c["margin"], c["m_of"], c["a_of"], c["scene_of"])
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     want = _host(handle, dict(c, traj=np.ascontiguousarray(c["traj"][:, :, :3])))
@@ -416,5 +396,5 @@ def test_checker_agrees_with_the_python_call(handle, tmp_path):
         rows = int(c["m_of"][b])
         assert head[0] == "path" and [int(v) for v in head[1:]] == [b, want["first_hit"][b], want["hit_agent"][b], rows], (b, head)
         got = np.array([float(next(lines)) for _ in range(rows)])
-        assert A.same_bits(got, want["clearance"][b, :rows]), b
+        assert same_bits(got, want["clearance"][b, :rows]), b
     assert next(lines, None) is None

@@ -6,76 +6,17 @@ import numpy as np
 import pytest
 
 import corridor_oracle as K
+from chain_util import scenarios, smoother_params, steps_one_by_one
 from path_optimizer_2_amd import capi
-from path_optimizer_2_amd.synth import make_scene
 
 pytestmark = pytest.mark.gpu
 
 
-def _smoother_params():
-    # the reference's smoother setting (OSQP default eps 1e-3) + the KKT-verified polish, so that both sides return the QP's optimum
-    return capi.default_params(eps_abs=1e-3, eps_rel=1e-3, polish=1, polish_every=25, adaptive_rho_interval=25)
-
-
-def _scenarios(B, n_maps=4, seed=5):
-    cs = [make_scene(seed=s, n=40, n_obstacles=25, knots_every=3.05) for s in range(n_maps)]
-    rng = np.random.default_rng(seed)
-    p_max = len(cs[0]["knots_x"])
-    pts = np.zeros((B, p_max, 2)); n_pts = np.zeros(B, dtype=np.int32); map_of = (np.arange(B) % n_maps).astype(np.int32)
-    start = np.zeros((B, 3)); target = np.zeros((B, 3))
-    for b in range(B):
-        c = cs[b % n_maps]
-        P = int(rng.integers(7, p_max + 1))                       # polygons of different length: every count downstream differs
-        n_pts[b] = P
-        pts[b, :P, 0] = c["knots_x"][:P]; pts[b, :P, 1] = c["knots_y"][:P] + rng.normal(scale=0.15, size=P)
-        h0 = np.arctan2(pts[b, 1, 1] - pts[b, 0, 1], pts[b, 1, 0] - pts[b, 0, 0])
-        start[b] = (pts[b, 0, 0] + 0.1, pts[b, 0, 1] + 0.1, h0 + 0.03)
-        h1 = np.arctan2(pts[b, P - 1, 1] - pts[b, P - 2, 1], pts[b, P - 1, 0] - pts[b, P - 2, 0])
-        target[b] = (pts[b, P - 1, 0], pts[b, P - 1, 1], h1)
-    c0 = cs[0]
-    geom = capi.PqpGridGeometry(c0["rows"], c0["cols"], c0["resolution"], c0["length"][0], c0["length"][1], c0["pos"][0], c0["pos"][1])
-    return dict(pts=pts, n_pts=n_pts, map_of=map_of, start=start, target=target, dist=np.stack([c["dist"] for c in cs]), geom=geom)
-
-
-def _one_by_one(h, hs, sc, b, cfg):
-    """The chain for scenario b alone, exact sizes, through the per-step host-pointer entry points."""
-    P = int(sc["n_pts"][b])
-    mo = sc["map_of"][b:b + 1]
-    st, tg = sc["start"][b:b + 1], sc["target"][b:b + 1]
-    r = h.bspline_resample(sc["pts"][b:b + 1, :P], np.array([P], dtype=np.int32), cfg.raw_max)
-    n0 = int(r["count"][0])
-    x0, y0, s0 = (r[k][:, :n0] for k in ("x", "y", "s"))
-    tab, ext = h.spline_fit(s0, x0, y0)
-    seg = h.segment_raw_reference(tab, ext, s0[:, -1].copy(), cfg.sample_max)
-    n1 = int(seg["count"][0])
-    if cfg.smoothing_method == capi.SMOOTHING_TENSION:
-        gx, gy = seg["x"][:, :n1], seg["y"][:, :n1]
-        clr = np.array([[K.obstacle_distance(sc["dist"][mo[0]], sc["geom"], gx[0, i], gy[0, i]) for i in range(n1)]])      # Map::getObstacleDistance, the oracle's
-        sm = hs.smooth_tension(gx, gy, seg["angle"][:, :n1], clr)
-    else:
-        sm = hs.smooth_tension2(*(seg[k][:, :n1] for k in ("x", "y", "angle", "k", "s")))
-    assert sm["status"][0] == 1
-    tab, ext = h.spline_fit(sm["s"], sm["x"], sm["y"])
-    ls, lb, ub, cnt, vl = h.dp_corridor(tab, ext, sm["s"][:, -1] + cfg.smoothed_length_margin, st, sc["dist"], sc["geom"], max_layers=cfg.layer_max, map_of=mo)
-    k = int(cnt[0])
-    assert k >= 4
-    ps = hs.post_smooth(ls[:, :k].copy(), lb[:, :k].copy(), ub[:, :k].copy(), vl)
-    assert ps["status"][0] == 1
-    x2, y2, s2 = h.offsets_to_points(tab, ext, ls[:, :k].copy(), ps["l"])
-    tab, ext = h.spline_fit(s2, x2, y2)
-    max_s = h.reference_length(tab, ext, s2[:, -1].copy(), tg)
-    ref, count, err = h.reference_states(tab, ext, max_s, cfg.n_max, start=st, ds_small=cfg.output_spacing / 2, ds_large=cfg.output_spacing, dynamic=True)
-    bounds, nv = h.corridor_bounds(ref, tab, ext, sc["dist"], sc["geom"], map_of=mo, n_of=count)
-    scal = np.array([[err[0, 0], err[0, 1], 0.0, tg[0, 2], 1.0 if nv[0] < count[0] else 0.0, cfg.max_steering_angle]])
-    res = h.solve_var(nv, ref, bounds, scal, passes=1)
-    return dict(n0=n0, n1=n1, layers=k, count=int(count[0]), nv=int(nv[0]), out=res["out"][0], status=int(res["status"][0]), ref=ref, bounds=bounds, scal=scal)
-
-
 def test_ragged_batch_equals_the_steps_run_one_scenario_at_a_time(hip_lib):
     B = 24
-    sc = _scenarios(B)
+    sc = scenarios(B)
     h = capi.Handle(capi.production_params(), max_batch=B, max_n=256)
-    hs = capi.Handle(_smoother_params(), max_batch=B, max_n=128)
+    hs = capi.Handle(smoother_params(), max_batch=B, max_n=128)
     cfg = h.chain_config()
     got = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs, cfg=cfg)
     assert (got["stage"] == 0).sum() >= B - 2, got["stage"]
@@ -83,7 +24,8 @@ def test_ragged_batch_equals_the_steps_run_one_scenario_at_a_time(hip_lib):
     for b in range(B):
         if got["stage"][b] != 0:
             continue
-        want = _one_by_one(h, hs, sc, b, cfg)
+        want = steps_one_by_one(h, hs, sc, b, cfg)
+        assert want["stage"] == 0, (b, want["stage"])
         seen.add((want["n0"], want["n1"], want["layers"], want["nv"]))
         assert got["n_out"][b] == want["nv"] and got["status"][b] == want["status"] == 1
         nv = want["nv"]
@@ -101,16 +43,17 @@ def test_configs0_the_demo_s_single_path(hip_lib):
     QP; the path against the C restatement of OSQP run to 1e-9 on the reference states and corridor the chain produced - the north_star
     bar: 1e-4 in lateral offset and heading."""
     import pqp_oracle_c as OC
-    sc = _scenarios(1, n_maps=1, seed=21)
+    sc = scenarios(1, n_maps=1, seed=21)
     sc["n_pts"][0] = 9                                             # ~24 m of input polygon -> ~18 m of line after the search: ~60 waypoints
     h = capi.Handle(capi.production_params(), max_batch=1, max_n=256)
-    hs = capi.Handle(_smoother_params(), max_batch=1, max_n=128)
+    hs = capi.Handle(smoother_params(), max_batch=1, max_n=128)
     cfg = h.chain_config()
     got = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs, cfg=cfg)
     assert got["stage"][0] == 0 and got["status"][0] == 1
     nv = int(got["n_out"][0])
     assert 40 <= nv <= 90, nv
-    want = _one_by_one(h, hs, sc, 0, cfg)
+    want = steps_one_by_one(h, hs, sc, 0, cfg)
+    assert want["stage"] == 0, (0, want["stage"])
     assert want["nv"] == nv
     ref = OC.solve_batch(OC.params(eps_abs=1e-9, eps_rel=1e-9, max_iter=200000), want["ref"][:, :nv].copy(), want["bounds"][:, :nv].copy(), want["scal"], passes=1)
     assert ref["solved"] == 1
@@ -124,9 +67,9 @@ def test_capacities_beyond_the_register_kernels(hip_lib):
     400 layers more than postSmooth's (251), 600 waypoints more than the lane-per-waypoint kernel's (512 - the handle is created for them;
     a line this short still runs there).  Same paths as with the default capacities; a smoother handle in the reference's ADMM setting gets
     the exact kernels where the generic core does not fit instead of PQP_ERR_CAPACITY."""
-    sc = _scenarios(3, n_maps=2, seed=33)
+    sc = scenarios(3, n_maps=2, seed=33)
     h = capi.Handle(capi.production_params(), max_batch=3, max_n=600)
-    hs = capi.Handle(_smoother_params(), max_batch=3, max_n=400)
+    hs = capi.Handle(smoother_params(), max_batch=3, max_n=400)
     big_cfg = h.chain_config(raw_max=400, sample_max=300, layer_max=400, n_max=600)
     for method in (capi.SMOOTHING_TENSION2, capi.SMOOTHING_TENSION):
         cfg0 = h.chain_config(smoothing_method=method)
@@ -149,9 +92,9 @@ def test_the_tension_smoothing_method(hip_lib):
     looks the clearance of the raw line's samples up on the device and runs TensionSmoother's QP (tension_smoother.cpp:49-177) in place of
     TensionSmoother2's; against the steps run one scenario at a time with the clearance from the oracle's grid_map restatement."""
     B = 10
-    sc = _scenarios(B, seed=11)
+    sc = scenarios(B, seed=11)
     h = capi.Handle(capi.production_params(), max_batch=B, max_n=256)
-    hs = capi.Handle(_smoother_params(), max_batch=B, max_n=128)
+    hs = capi.Handle(smoother_params(), max_batch=B, max_n=128)
     cfg = h.chain_config(smoothing_method=capi.SMOOTHING_TENSION)
     got = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs, cfg=cfg)
     assert (got["stage"] == 0).sum() >= B - 2, got["stage"]
@@ -160,7 +103,8 @@ def test_the_tension_smoothing_method(hip_lib):
     for b in range(B):
         if got["stage"][b] != 0:
             continue
-        want = _one_by_one(h, hs, sc, b, cfg)
+        want = steps_one_by_one(h, hs, sc, b, cfg)
+        assert want["stage"] == 0, (b, want["stage"])
         nv = want["nv"]
         assert got["n_out"][b] == nv and got["status"][b] == want["status"] == 1
         # (TensionSmoother's QP is ill-conditioned - test_tension: both sides sit on a ~1e-5 round-off floor of the smoothed line)
@@ -179,8 +123,8 @@ def test_chain_carries_the_previous_planning_cycle(hip_lib):
     smoother kernels start from their slot's previous active set.  Every cycle's paths equal those of handles that start cold (what the carried
     start saves is time: tools/bench_full_chain.py --carry, 892 k -> 989 k scenarios/s)."""
     B = 24
-    sc = _scenarios(B, seed=21)
-    pair = lambda: (capi.Handle(capi.production_params(), max_batch=B, max_n=256), capi.Handle(_smoother_params(), max_batch=B, max_n=128))
+    sc = scenarios(B, seed=21)
+    pair = lambda: (capi.Handle(capi.production_params(), max_batch=B, max_n=256), capi.Handle(smoother_params(), max_batch=B, max_n=128))
     h, hs = pair(); hc, hsc = pair()
     for x in (hc, hsc):
         x.set_option(capi.OPT_CARRY_CYCLES, 1)
@@ -208,12 +152,12 @@ def test_chain_carries_the_previous_planning_cycle(hip_lib):
 
 
 def test_stages_are_the_reference_s_return_false_sites(hip_lib):
-    sc = _scenarios(6, seed=9)
+    sc = scenarios(6, seed=9)
     sc["n_pts"][1] = 3                                               # "Few reference points" (reference_path_smoother.cpp:33-36)
     sc["start"][2, :2] += np.array([-np.sin(sc["start"][2, 2]), np.cos(sc["start"][2, 2])]) * 14.0      # 14 m beside the line: graphSearchDp quits
     sc["start"][3, 2] += 1.6                                         # 92 degrees off the line's heading: path_optimizer.cpp:113-116
     h = capi.Handle(capi.production_params(), max_batch=6, max_n=256)
-    hs = capi.Handle(_smoother_params(), max_batch=6, max_n=128)
+    hs = capi.Handle(smoother_params(), max_batch=6, max_n=128)
     got = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs)
     assert got["stage"][1] == 1 and got["stage"][2] == 3 and got["stage"][3] == 6, got["stage"]
     for b in (1, 2, 3):
@@ -230,7 +174,7 @@ def test_clearance_lookup_on_the_device(hip_lib):
     """pqp_clearance_device = Map::getObstacleDistance at the raw line's points (tension_smoother.cpp:168), against the restatement of
     grid_map's bilinear lookup in the corridor oracle; its output feeds pqp_smooth_tension."""
     import torch
-    sc = _scenarios(3, n_maps=3, seed=2)
+    sc = scenarios(3, n_maps=3, seed=2)
     h = capi.Handle(capi.default_params(eps_abs=1e-3, eps_rel=1e-3), max_batch=3, max_n=64)
     rng = np.random.default_rng(0)
     n = 40
@@ -262,7 +206,7 @@ def test_chain_replayed_as_a_hip_graph_is_bit_identical(hip_lib):
     back to plain launches."""
     import torch
     B = 40
-    sc = _scenarios(B, seed=11)
+    sc = scenarios(B, seed=11)
     dev = torch.device("cuda", 0)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     p = lambda x: capi.C.c_void_p(x.data_ptr())
@@ -277,7 +221,7 @@ def test_chain_replayed_as_a_hip_graph_is_bit_identical(hip_lib):
     results = {}
     for graph in (0, 1, 2):          # 2: replays without the fences against the smoother handle's stream (this test syncs both streams after every call)
         h = capi.Handle(capi.production_params(), device=0, max_batch=B, max_n=256)
-        hs = capi.Handle(_smoother_params(), device=0, max_batch=B, max_n=128)
+        hs = capi.Handle(smoother_params(), device=0, max_batch=B, max_n=128)
         h.set_option(capi.OPT_STORE_WARM, 0); h.set_option(capi.OPT_ORDER_BY_COST, 1); h.set_option(capi.OPT_CHAIN_GRAPH, graph)
         cfg = h.chain_config(raw_max=64, sample_max=48, layer_max=32, n_max=128)
         d_pts, d_st = t(cycles[0][0], np.float64), t(cycles[0][1], np.float64)
@@ -323,7 +267,7 @@ def test_chain_graph_on_the_lane_per_qp_kernel_leaves_the_ticket_counter_alone(h
     import torch
     from path_optimizer_2_amd.synth import make_batch
     B = 24
-    sc = _scenarios(B, seed=5)
+    sc = scenarios(B, seed=5)
     dev = torch.device("cuda", 0)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     p = lambda x: capi.C.c_void_p(x.data_ptr())
@@ -336,7 +280,7 @@ def test_chain_graph_on_the_lane_per_qp_kernel_leaves_the_ticket_counter_alone(h
     results = {}
     for graph in (0, 1):
         h = capi.Handle(capi.production_params(), device=0, max_batch=B, max_n=256)
-        hs = capi.Handle(_smoother_params(), device=0, max_batch=B, max_n=128)
+        hs = capi.Handle(smoother_params(), device=0, max_batch=B, max_n=128)
         h.set_option(capi.OPT_STORE_WARM, 0); h.set_option(capi.OPT_STREAM_BATCH, 1); h.set_option(capi.OPT_CHAIN_GRAPH, graph)
         cfg = h.chain_config(raw_max=64, sample_max=48, layer_max=32, n_max=128)
         d_pts, d_st = t(sc["pts"], np.float64), t(sc["start"], np.float64)
@@ -371,7 +315,7 @@ def test_chain_graph_is_not_replayed_after_the_smoother_handle_reallocates(hip_l
     (pqp_chain.hip) from replaying it.  Replay, grow the smoother handle's buffers, call the chain again: bit for bit a fresh pair's plain chain."""
     import torch
     B = 4
-    sc = _scenarios(B, seed=7)
+    sc = scenarios(B, seed=7)
     dev = torch.device("cuda", 0)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     p = lambda x: capi.C.c_void_p(x.data_ptr())
@@ -380,7 +324,7 @@ def test_chain_graph_is_not_replayed_after_the_smoother_handle_reallocates(hip_l
 
     def pair(graph):
         h = capi.Handle(capi.production_params(), device=0, max_batch=B, max_n=256)
-        hs = capi.Handle(_smoother_params(), device=0, max_batch=B, max_n=128)
+        hs = capi.Handle(smoother_params(), device=0, max_batch=B, max_n=128)
         h.set_option(capi.OPT_CHAIN_GRAPH, graph); hs.set_option(capi.OPT_CHAIN_GRAPH, graph)
         out = torch.zeros((B, 256, 7), dtype=torch.float64, device=dev)
         ints = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4)]          # n_out, status, stage, iters
@@ -430,7 +374,7 @@ def test_chain_graph_is_never_replayed_after_an_option_changed(hip_lib):
     (Not seen here: that PQP_OPT_STREAM_STAGED is in the key - both workspace layouts give the same bits and a capture is as silent as a replay.)"""
     import torch
     B = 4
-    sc = _scenarios(B, seed=7)
+    sc = scenarios(B, seed=7)
     dev = torch.device("cuda", 0)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     p = lambda x: capi.C.c_void_p(x.data_ptr())
@@ -444,7 +388,7 @@ def test_chain_graph_is_never_replayed_after_an_option_changed(hip_lib):
     def session(graph, warm_up):
         """warm_up None: call until the chain replays; else: that many calls.  Then one call per changed option: (results, launched plainly)."""
         h = capi.Handle(capi.production_params(), device=0, max_batch=B, max_n=128)
-        hs = capi.Handle(_smoother_params(), device=0, max_batch=B, max_n=128)
+        hs = capi.Handle(smoother_params(), device=0, max_batch=B, max_n=128)
         h.set_option(capi.OPT_CHAIN_GRAPH, graph); hs.set_option(capi.OPT_CHAIN_GRAPH, graph)
         cfg = h.chain_config(raw_max=64, sample_max=48, layer_max=32, n_max=128)
         out = torch.zeros((B, cfg.n_max, 7), dtype=torch.float64, device=dev)

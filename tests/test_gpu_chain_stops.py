@@ -7,8 +7,10 @@ import numpy as np
 import pytest
 
 import chain_stops_util as CS
+import chain_util
 import sample_util as S
 from path_optimizer_2_amd import capi
+from shared_util import same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +24,6 @@ def batch(hip_lib):
     return CS.mixed_batch()
 
 
-def _pair(path_params=None, smoother_params=None, max_n=(256, 128)):
-    return (capi.Handle(path_params or capi.production_params(), max_batch=B, max_n=max_n[0]),
-            capi.Handle(smoother_params or CS.smoother_params(), max_batch=B, max_n=max_n[1]))
-
-
 def _cfg(h, method=capi.SMOOTHING_TENSION2, **over):
     return h.chain_config(**{**CS.MIXED_CFG, "smoothing_method": method, **over})
 
@@ -38,12 +35,12 @@ def _run(h, hs, sc, cfg, **kw):
 
 def _same_rows(a, b, rows, keys=("out", "n_out", "status", "stage", "iters")):
     for k in keys:
-        assert S.same_bits(a[k][rows], b[k][rows]) if a[k].dtype == np.float64 else np.array_equal(a[k][rows], b[k][rows]), k
+        assert same_bits(a[k][rows], b[k][rows]) if a[k].dtype == np.float64 else np.array_equal(a[k][rows], b[k][rows]), k
 
 
 def _against_the_steps(got, h, hs, sc, cfg, tol):
     """stage, status and n_out of every scenario against the steps run one by one; the path where one comes out.  Returns the steps' answers."""
-    want = [CS.steps_one_by_one(h, hs, sc, b, cfg) for b in range(B)]
+    want = [chain_util.steps_one_by_one(h, hs, sc, b, cfg) for b in range(B)]
     for b, w in enumerate(want):
         print(b, sc["kind"][b], "chain:", got["stage"][b], got["status"][b], got["n_out"][b], " steps:", w["stage"], w["status"], w.get("site"), w.get("nv"))
     for b, w in enumerate(want):
@@ -77,7 +74,7 @@ def test_every_stop_site(batch, method):
     (TensionSmoother's QP is ill-conditioned: 2e-4 against the steps there, as test_gpu_chain.py has it; 2e-5 for TensionSmoother2.)"""
     sc = batch
     tol = 2e-4 if method == capi.SMOOTHING_TENSION else 2e-5
-    h, hs = _pair()
+    h, hs = chain_util.handles(B)
     cfg = _cfg(h, method)
     got = _run(h, hs, sc, cfg)
     want = _against_the_steps(got, h, hs, sc, cfg, tol)
@@ -127,7 +124,7 @@ def test_stopped_scenarios_leave_their_neighbours_alone(batch, method):
     and handles): the healthy scenarios' rows of out, n_out, status, stage and iters are the same bits - every kernel of the chain works per
     scenario, none of its results depends on the batch neighbours."""
     sc = batch
-    h, hs = _pair()
+    h, hs = chain_util.handles(B)
     cfg = _cfg(h, method)
     mixed = _run(h, hs, sc, cfg)
     clean = _run(h, hs, CS.all_healthy(sc), cfg)
@@ -184,7 +181,7 @@ class _Raw:
 @pytest.mark.parametrize("method", METHODS)
 def test_nothing_is_written_outside_the_outputs(batch, method):
     sc = batch
-    h, hs = _pair()
+    h, hs = chain_util.handles(B)
     cfg = _cfg(h, method)
     want = _run(h, hs, sc, cfg)
     raw = _Raw(sc, cfg)
@@ -202,11 +199,11 @@ def test_replayed_graph_gives_the_plain_chain_s_arrays(batch):
     buffer), capture, capture, replay - each give what the plainly launched chain gives: stage, status and n_out of every scenario, and the
     healthy scenarios' rows of out and iters bit for bit (a stopped scenario's rows of out are unspecified, pqp.h)."""
     sc = batch
-    h0, hs0 = _pair()
+    h0, hs0 = chain_util.handles(B)
     cfg = _cfg(h0)
     want = _run(h0, hs0, sc, cfg)
     h0.close(); hs0.close()
-    h, hs = _pair()
+    h, hs = chain_util.handles(B)
     h.set_option(capi.OPT_CHAIN_GRAPH, 1)
     raw = _Raw(sc, cfg)
     ms, untimed = C.c_float(), []
@@ -231,11 +228,11 @@ def test_stages_do_not_depend_on_what_the_handles_ran_before(batch, method):
     sc = batch
     big = dict(raw_max=400, sample_max=300, layer_max=400, n_max=600)
     sizes = (600, 400)
-    h, hs = _pair(max_n=sizes)
+    h, hs = chain_util.handles(B, max_n=sizes)
     cfg = _cfg(h, method)
     fresh = _run(h, hs, sc, cfg)
     h.close(); hs.close()
-    h, hs = _pair(max_n=sizes)
+    h, hs = chain_util.handles(B, max_n=sizes)
     other = _run(h, hs, CS.all_healthy(sc), _cfg(h, method, **big))
     assert (other["stage"] == 0).all()
     after_other = _run(h, hs, sc, cfg)
@@ -260,21 +257,21 @@ def test_the_steps_behind_the_chain_never_pick_a_stopped_candidate(batch):
     groups = len(gs) - 1
     sp, sa = capi.speed_default_params(v_max=8.0), capi.sample_default_params(dt=0.2, hold_last=1)
     vs = np.linspace(1.0, 4.0, groups)
-    h, hs = _pair()
+    h, hs = chain_util.handles(B)
     cfg = _cfg(h)
     got = _run(h, hs, sc, cfg, check_footprint=True, select=gs, speed=sp, v_start=vs, sample=sa, samples=m)
     hh = capi.Handle(capi.default_params(), max_batch=B, max_n=cfg.n_max)
     fp = hh.footprint_check(got["out"], got["n_out"], sc["dist"], sc["geom"], map_of=sc["map_of"], margin=True)
-    assert np.array_equal(got["free"], fp["free"]) and np.array_equal(got["first_collision"], fp["first_collision"]) and S.same_bits(got["margin"], fp["margin"])
+    assert np.array_equal(got["free"], fp["free"]) and np.array_equal(got["first_collision"], fp["first_collision"]) and same_bits(got["margin"], fp["margin"])
     sel = hh.select_paths(got["out"], gs, n_of=got["n_out"], status=got["status"], stage=got["stage"], first_collision=got["first_collision"],
                           margin=got["margin"])
     for k in ("terms", "best_paths"):
-        assert S.same_bits(got[k], sel[k]), k
+        assert same_bits(got[k], sel[k]), k
     assert np.array_equal(got["best"], sel["best"]) and np.array_equal(got["best_n"], sel["best_n"])
     prof, flags = hh.speed_profile(got["best_paths"], vs, n_of=got["best_n"], prm=sp)
-    assert S.same_bits(got["profile"], prof) and np.array_equal(got["speed_flags"], flags)
+    assert same_bits(got["profile"], prof) and np.array_equal(got["speed_flags"], flags)
     traj, traj_n, traj_flags = hh.sample_trajectory(got["best_paths"], got["profile"], m, n_of=got["best_n"], prm=sa)
-    assert S.same_bits(got["traj"], traj) and np.array_equal(got["traj_n"], traj_n) and np.array_equal(got["traj_flags"], traj_flags)
+    assert same_bits(got["traj"], traj) and np.array_equal(got["traj_n"], traj_n) and np.array_equal(got["traj_flags"], traj_flags)
     stopped = got["stage"] != 0
     assert np.array_equal(stopped, ~sc["healthy"])
     assert (got["terms"][stopped, 7] == 0.0).all() and (got["terms"][stopped] == 0.0).all()          # count 0: eight zeros, not eligible

@@ -11,6 +11,7 @@ import corridor_oracle as K
 import corridor_util as U
 from corridor_util import SPLINE_TOL, ref_spline_lib as _ref_spline_lib, rows_close as _rows_close, tab_close as _tab_close
 from path_optimizer_2_amd import capi
+from shared_util import capi_geom
 
 pytestmark = pytest.mark.gpu
 
@@ -20,10 +21,6 @@ def handle(hip_lib):
     h = capi.Handle(capi.default_params(), device=0, max_batch=64, max_n=128)
     yield h
     h.close()
-
-
-def _geom(g):
-    return capi.PqpGridGeometry(g.rows, g.cols, g.resolution, g.length_x, g.length_y, g.pos_x, g.pos_y)
 
 
 def _compare(got, n_valid_got, c, prm=K.CorridorParams()):
@@ -43,7 +40,7 @@ def _compare(got, n_valid_got, c, prm=K.CorridorParams()):
 @pytest.mark.parametrize("seed,n", [(0, 40), (1, 80), (2, 80), (5, 120)])
 def test_bounds_match_the_oracle(handle, seed, n):
     c = U.build(seed=seed, n=n)
-    got, nv = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], _geom(c["geom"]))
+    got, nv = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], capi_geom(c["geom"]))
     _compare(got[0], int(nv[0]), c)
 
 
@@ -58,7 +55,7 @@ def test_batch_with_one_map_per_scenario_and_a_blocked_road(handle):
         d2[i, :] = np.minimum(d2[i, :], np.float32(abs(x - x_wall)))
     cs[2]["dist"] = d2
     got, nv = handle.corridor_bounds(np.stack([c["ref"] for c in cs]), np.stack([c["tab"] for c in cs]), np.stack([c["ext"] for c in cs]),
-                                     np.stack([c["dist"] for c in cs]), _geom(g), map_of=[0, 1, 2])
+                                     np.stack([c["dist"] for c in cs]), capi_geom(g), map_of=[0, 1, 2])
     for q, c in enumerate(cs):
         _compare(got[q], int(nv[q]), c)
     assert nv[2] < 35 and nv[0] == 60
@@ -83,7 +80,7 @@ def test_paths_longer_than_the_lds_go_through_in_tiles(handle):
         x, _ = K.grid_cell_position(g, i, 0)
         d2[i, :] = np.minimum(d2[i, :], np.float32(abs(x - x_wall)))
     for dist in (c["dist"], d2):
-        got, nv = handle.corridor_bounds(c["ref"][None], tab[None], ext[None], dist, _geom(g))
+        got, nv = handle.corridor_bounds(c["ref"][None], tab[None], ext[None], dist, capi_geom(g))
         _compare(got[0], int(nv[0]), dict(ref=c["ref"], sx=dx, sy=dy, dist=dist, geom=g))
     assert 36 <= int(nv[0]) < 72
 
@@ -92,7 +89,7 @@ def test_non_default_vehicle_parameters(handle):
     c = U.build(seed=11, n=50)
     prm_o = K.CorridorParams(front_length=3.2, rear_length=-0.8, car_width=1.8, safety_margin=0.2)
     prm = handle.corridor_params(front_length=3.2, rear_length=-0.8, car_width=1.8, safety_margin=0.2)
-    got, nv = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], _geom(c["geom"]), prm=prm)
+    got, nv = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], capi_geom(c["geom"]), prm=prm)
     _compare(got[0], int(nv[0]), c, prm_o)
 
 
@@ -100,7 +97,7 @@ def test_feeds_the_path_qp(handle):
     """bounds computed on the device go straight into pqp_path_solve (same layout) and give the oracle's path"""
     import pqp_oracle as O
     c = U.build(seed=4, n=60)
-    got, nv = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], _geom(c["geom"]))
+    got, nv = handle.corridor_bounds(c["ref"][None], c["tab"][None], c["ext"][None], c["dist"], capi_geom(c["geom"]))
     n = int(nv[0])
     assert n >= 20
     ref = c["ref"][None, :n].copy()
@@ -244,7 +241,7 @@ def test_pipeline_spline_to_path_on_the_device(handle):
     m = tab.shape[2]
     ms, st_d, mo = t(max_s), t(start), torch.arange(B, dtype=torch.int32, device=dev)
     assert lib.pqp_reference_states_device(hh, B, n_max, m, p(tab), p(ext), p(ms), p(st_d), 0.15, 0.3, 1, p(ref), p(count), p(err)) == 0
-    geom = _geom(g); prm = hp.corridor_params()
+    geom = capi_geom(g); prm = hp.corridor_params()
     assert lib.pqp_corridor_bounds_device(hh, B, n_max, m, p(ref), p(count), p(tab), p(ext), p(dist), p(mo), capi.C.byref(geom), capi.C.byref(prm), p(bounds), p(nv)) == 0
     hp.sync()
     ref_h, nv_h, err_h = ref.cpu().numpy(), nv.cpu().numpy(), err.cpu().numpy()
@@ -323,7 +320,7 @@ def test_dp_corridor_search(handle, seed, length):
     (they are sums of 0.6 m and 0.2 m steps: equal to round-off unless a sample sits on the 1.2 m threshold)."""
     c = U.build(seed=seed, n=10)
     start = np.array([[c["ref"][0, 3] + 0.2, c["ref"][0, 4] + 0.5, c["ref"][0, 2] + 0.05]])
-    ls, lb, ub, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([length]), start, c["dist"], _geom(c["geom"]))
+    ls, lb, ub, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([length]), start, c["dist"], capi_geom(c["geom"]))
     want = K.graph_search_dp(c["sx"], c["sy"], length, tuple(start[0]), c["dist"], c["geom"])
     assert want is not None and count[0] == len(want["layers_s"])
     k = int(count[0])
@@ -342,7 +339,7 @@ def test_dp_corridor_search_on_other_grids(handle, rng, spacing, lon, length):
     c = U.build(seed=2, n=10)
     start = np.array([[c["ref"][0, 3] + 0.1, c["ref"][0, 4] + 0.3, c["ref"][0, 2] + 0.02]])
     prm = capi.PqpDpParams(rng, lon, spacing, 2.0)
-    ls, lb, ub, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([length]), start, c["dist"], _geom(c["geom"]), prm=prm, max_layers=96)
+    ls, lb, ub, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([length]), start, c["dist"], capi_geom(c["geom"]), prm=prm, max_layers=96)
     want = K.graph_search_dp(c["sx"], c["sy"], length, tuple(start[0]), c["dist"], c["geom"],
                              prm=K.DpParams(lateral_range=rng, longitudinal_spacing=lon, lateral_spacing=spacing))
     if want is None:
@@ -356,7 +353,7 @@ def test_dp_corridor_search_on_other_grids(handle, rng, spacing, lon, length):
 
 def test_dp_corridor_edge_cases(handle):
     c = U.build(seed=3, n=10)
-    g = _geom(c["geom"])
+    g = capi_geom(c["geom"])
     far = np.array([[c["ref"][0, 3], c["ref"][0, 4] + 15.0, c["ref"][0, 2]]])            # vehicle 15 m off the line: graphSearchDp returns false
     _, _, _, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([30.0]), far, c["dist"], g)
     assert count[0] == 0 and abs(vl[0]) > 10.0
@@ -370,7 +367,7 @@ def test_dp_corridor_feeds_post_smooth(handle):
     """layers_s / lb / ub / vehicle_l of the search are the inputs of the postSmooth QP (reference_path_smoother.cpp:44)"""
     c = U.build(seed=1, n=10)
     start = np.array([[c["ref"][0, 3] + 0.1, c["ref"][0, 4] + 0.3, c["ref"][0, 2]]])
-    ls, lb, ub, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([33.0]), start, c["dist"], _geom(c["geom"]))
+    ls, lb, ub, count, vl = handle.dp_corridor(c["tab"][None], c["ext"][None], np.array([33.0]), start, c["dist"], capi_geom(c["geom"]))
     k = int(count[0])
     assert k >= 4
     res = handle.post_smooth(ls[:, :k].copy(), lb[:, :k].copy(), ub[:, :k].copy(), vl.copy())
@@ -450,7 +447,7 @@ def test_golden_line_fixture_through_the_hip_chain(handle):
 def test_argument_errors(handle):
     """bad arguments come back as PQP_ERR_INVALID / PQP_ERR_CAPACITY (no exception crosses the ABI, nothing is launched)"""
     c = U.build(seed=0, n=8)
-    g = _geom(c["geom"])
+    g = capi_geom(c["geom"])
     with pytest.raises(capi.PqpError):
         handle.spline_fit(np.zeros((1, 2)), np.zeros((1, 2)), np.zeros((1, 2)))                      # fewer than 3 knots (spline.cpp:164)
     with pytest.raises(capi.PqpError):

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import chain_util
 import corridor_util as U
 import distance_util as D
 from path_optimizer_2_amd import capi
@@ -115,13 +116,12 @@ def test_device_layer_feeds_corridor_bounds_on_the_same_stream(handle):
 
 
 def test_optimize_path_on_grid_equals_optimize_path_on_the_layer(hip_lib):
-    from test_gpu_chain import _scenarios, _smoother_params
     B = 24
-    sc = _scenarios(B)
+    sc = chain_util.scenarios(B)
     occ = D.occupancy_of(sc["dist"])
     layer = D.distance_layer(occ, sc["geom"].resolution)
     h = capi.Handle(capi.production_params(), max_batch=B, max_n=256)
-    hs = capi.Handle(_smoother_params(), max_batch=B, max_n=128)
+    hs = capi.Handle(chain_util.smoother_params(), max_batch=B, max_n=128)
     try:
         want = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], layer, sc["geom"], map_of=sc["map_of"], smoother=hs)
         got = h.optimize_path_on_grid(sc["pts"], sc["n_pts"], sc["start"], sc["target"], occ, sc["geom"], map_of=sc["map_of"], smoother=hs)

@@ -8,8 +8,9 @@ import pytest
 
 import dp_cases as D
 import long_line_util as LL
+from device_form import SENT, d_dp, host_equals_device
 from path_optimizer_2_amd import capi
-from test_gpu_line_geometry import SENT, d_dp, host_equals_device, same_bits
+from shared_util import capi_geom, same_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -25,10 +26,6 @@ def handles(hip_lib):
         h.close()
 
 
-def _geom(g):
-    return capi.PqpGridGeometry(g.rows, g.cols, g.resolution, g.length_x, g.length_y, g.pos_x, g.pos_y)
-
-
 def _prm(p):
     return capi.PqpDpParams(p.lateral_range, p.longitudinal_spacing, p.lateral_spacing, p.car_width)
 
@@ -36,10 +33,10 @@ def _prm(p):
 def _launch(h, device, tab, ext, length, start, dist, geom, prm, max_layers, map_of=None):
     """(layers_s, lb, ub, count, vehicle_l) through the device or the host entry point"""
     if device:
-        rc, *out = d_dp(h, tab, ext, length, start, dist, _geom(geom), max_layers, map_of=map_of, prm=_prm(prm))
+        rc, *out = d_dp(h, tab, ext, length, start, dist, capi_geom(geom), max_layers, map_of=map_of, prm=_prm(prm))
         assert rc == 0
         return out
-    return h.dp_corridor(tab, ext, length, start, dist, _geom(geom), max_layers=max_layers, map_of=map_of, prm=_prm(prm))
+    return h.dp_corridor(tab, ext, length, start, dist, capi_geom(geom), max_layers=max_layers, map_of=map_of, prm=_prm(prm))
 
 
 def _scene_launch(h, device, sc, max_layers):
@@ -53,10 +50,10 @@ def _all_four(handles, sc, max_layers):
     base = got[(FORMS[0], False)]
     for v in FORMS:
         host, dev = got[(v, False)], got[(v, True)]
-        assert np.array_equal(host[3], dev[3]) and same_bits(host[4], dev[4]), (v, host[3], dev[3])
+        assert np.array_equal(host[3], dev[3]) and same_bytes(host[4], dev[4]), (v, host[3], dev[3])
         for j in range(3):
             host_equals_device(host[j], dev[j], dev[3], max_layers)
-        assert all(same_bits(a, b) for a, b in zip(host, base)), ("form", v)
+        assert all(same_bytes(a, b) for a, b in zip(host, base)), ("form", v)
     return base
 
 
@@ -112,15 +109,15 @@ def test_batch_on_several_maps_is_each_scenario_alone(handles):
         host = _launch(handles[v], False, b["tab"], b["ext"], b["length"], b["start"], b["dist"], D.GEOM, prm, max_layers, map_of=b["map_of"])
         dev = _launch(handles[v], True, b["tab"], b["ext"], b["length"], b["start"], b["dist"], D.GEOM, prm, max_layers, map_of=b["map_of"])
         assert np.array_equal(host[3], counts), (v, host[3], counts)
-        assert np.array_equal(dev[3], counts) and same_bits(host[4], dev[4])
+        assert np.array_equal(dev[3], counts) and same_bytes(host[4], dev[4])
         for j in range(3):
             host_equals_device(host[j], dev[j], dev[3], max_layers)
         base = base or host
-        assert all(same_bits(x, y) for x, y in zip(host, base)), ("form", v)
+        assert all(same_bytes(x, y) for x, y in zip(host, base)), ("form", v)
         for q in range(B):
             alone = _launch(handles[v], False, b["tab"][q:q + 1], b["ext"][q:q + 1], b["length"][q:q + 1], b["start"][q:q + 1],
                             b["dist"][b["map_of"][q]], D.GEOM, prm, max_layers)
-            assert all(same_bits(x[q:q + 1], y) for x, y in zip(host, alone)), (v, b["names"][q])
+            assert all(same_bytes(x[q:q + 1], y) for x, y in zip(host, alone)), (v, b["names"][q])
     for q in range(B):
         if counts[q] > 0:
             _against_the_oracle(base, q, want[q], "batch " + b["names"][q])

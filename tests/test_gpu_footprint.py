@@ -11,13 +11,15 @@ import math
 import numpy as np
 import pytest
 
+import chain_util
 import distance_util as D
 import footprint_util as F
 from path_optimizer_2_amd import capi
 from path_optimizer_2_amd.synth import make_scene
+from shared_util import oracle_geom
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5
+TOL = F.FOOTPRINT_TOL
 
 
 @pytest.fixture(scope="module")
@@ -29,11 +31,6 @@ def handle(hip_lib):
 
 def _geom(rows, cols, res, pos=(0.0, 0.0)):
     return capi.PqpGridGeometry(rows, cols, res, rows * res, cols * res, pos[0], pos[1])
-
-
-def _kgeom(g):
-    import corridor_oracle as K
-    return K.GridGeom(g.rows, g.cols, g.resolution, g.length_x, g.length_y, g.pos_x, g.pos_y)
 
 
 @pytest.fixture(scope="module")
@@ -60,7 +57,7 @@ def _random_states(rng, g, B, n, stride=7, spill=0.05):
 
 
 def _agree(got, states, n_of, dists, g, map_of, car, mode):
-    kg = _kgeom(g)
+    kg = oracle_geom(g)
     circles = capi.car_circles(car)
     free, first, mg = F.check(states, n_of, dists, kg, map_of, circles, mode)
     near = F.near_threshold(states, n_of, dists, kg, map_of, circles, TOL)
@@ -162,8 +159,8 @@ def test_a_path_longer_than_a_workgroup_and_a_large_batch(handle, synth_layers):
     assert got["first_collision"][0] == 2500 and got["free"].all()
     got = handle.footprint_check(states, None, dists[:1], g, margin=True)
     sample = np.sort(rng.choice(3000, 400, replace=False))
-    free, _, mg = F.check(states[:, sample], None, [dists[0]], _kgeom(g), None, capi.car_circles(), 0)
-    near = F.near_threshold(states[:, sample], None, [dists[0]], _kgeom(g), None, capi.car_circles(), TOL)
+    free, _, mg = F.check(states[:, sample], None, [dists[0]], oracle_geom(g), None, capi.car_circles(), 0)
+    near = F.near_threshold(states[:, sample], None, [dists[0]], oracle_geom(g), None, capi.car_circles(), TOL)
     assert ((got["free"][:, sample] == free) | near).all()
     np.testing.assert_allclose(got["margin"][:, sample], mg, atol=TOL, rtol=0)
     # 65 536 scenarios of 80 states on four maps
@@ -177,24 +174,18 @@ def test_a_path_longer_than_a_workgroup_and_a_large_batch(handle, synth_layers):
     first = np.where((got["free"] == 0) & (idx < n_of[:, None]), idx, n).min(axis=1)
     assert (got["first_collision"] == np.minimum(first, n_of)).all()
     pick = rng.choice(B, 24, replace=False)
-    free, _, _ = F.check(big[pick], n_of[pick], list(dists), _kgeom(g), map_of[pick], capi.car_circles(), 1)
-    near = F.near_threshold(big[pick], n_of[pick], list(dists), _kgeom(g), map_of[pick], capi.car_circles(), TOL)
+    free, _, _ = F.check(big[pick], n_of[pick], list(dists), oracle_geom(g), map_of[pick], capi.car_circles(), 1)
+    near = F.near_threshold(big[pick], n_of[pick], list(dists), oracle_geom(g), map_of[pick], capi.car_circles(), TOL)
     assert ((got["free"][pick] == free) | near).all()
 
 
 # ---- behind the device chain ---------------------------------------------------------------------------------------------------------
-def _chain_handles(B):
-    import test_gpu_chain as T
-    return capi.Handle(capi.production_params(), max_batch=B, max_n=256), capi.Handle(T._smoother_params(), max_batch=B, max_n=128)
-
-
 def test_check_footprint_behind_the_chain(hip_lib):
-    import test_gpu_chain as T
     B = 24
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     runs = {}
     for flag in (False, True):                         # fresh handles for each: nothing carried from one call to the other
-        h, hs = _chain_handles(B)
+        h, hs = chain_util.handles(B)
         runs[flag] = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs,
                                      check_footprint=flag)
         h.close(); hs.close()
@@ -211,11 +202,10 @@ def test_check_footprint_behind_the_chain(hip_lib):
 
 
 def test_check_footprint_on_grid_reads_the_layers_built_on_the_device(hip_lib):
-    import test_gpu_chain as T
     B = 8
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     occ = np.stack([D.occupancy_of(d) for d in sc["dist"]])
-    h, hs = _chain_handles(B)
+    h, hs = chain_util.handles(B)
     got = h.optimize_path_on_grid(sc["pts"], sc["n_pts"], sc["start"], sc["target"], occ, sc["geom"], map_of=sc["map_of"], smoother=hs,
                                   check_footprint=True, footprint_mode=capi.FOOTPRINT_BOUNDING_FIRST)
     layers = np.stack([D.distance_layer(o, sc["geom"].resolution) for o in occ])

@@ -3,10 +3,10 @@ The emulation exchanges neighbours through the shared array and runs one lane af
 side by side and the look's reduction across them.  An accept / reject decision that differed would show as another status or another count of reduced
 solves (info[5]) or factorisations (info[6]).  N = 17, 64, 65, 80: a row's last lane (15 | 16), a wavefront's (63 | 64), the last real lane on and
 beside them, N not a multiple of 16."""
-import numpy as np
 import pytest
 
 import emu_util as EU
+from emu_util import compare_counts as _compare
 from path_optimizer_2_amd.synth import make_batch
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +21,6 @@ def _both(hip_lib, batch, n, profile="uniform"):
     h.close()
     emu = EU.solve(EU.production(), b["ref"], b["bounds"], b["scal"], passes=1)
     return dev, emu
-
-
-def _compare(dev, emu, what):
-    st = dev["status"] != emu["status"]
-    kkt = dev["info"][:, 5] != emu["info"][:, 5]
-    fac = dev["info"][:, 6] != emu["info"][:, 6]
-    d = np.abs(dev["out"][:, :, 3:5] - emu["out"][:, :, 3:5]).max()
-    print(f"{what}: {len(st)} QPs, solved {int((dev['status'] == 1).sum())}; differing statuses {int(st.sum())}, reduced-solve counts {int(kkt.sum())}, "
-          f"factorisation counts {int(fac.sum())}; mean solves {dev['info'][:, 5].mean():.2f}, factorisations {dev['info'][:, 6].mean():.2f}; "
-          f"max |l, d_heading| device - emulation {d:.1e}")
-    assert not st.any(), np.nonzero(st)[0][:8]
-    assert not kkt.any(), (np.nonzero(kkt)[0][:8], dev["info"][kkt, 5][:8], emu["info"][kkt, 5][:8])
-    assert not fac.any(), (np.nonzero(fac)[0][:8], dev["info"][fac, 6][:8], emu["info"][fac, 6][:8])
 
 
 def test_bench_batch_counts_equal_the_emulation(hip_lib):

@@ -8,21 +8,20 @@ The device forms are called on torch tensors whose outputs lie in a larger alloc
 write (the guard band behind [batch][n_max], rows past a scenario's count) has to come back as the sentinel.  Properties that need no
 oracle - host form == device form, a permuted batch gives permuted outputs, a padded _var table gives what the exact-size table gives -
 are checked bit for bit on every scenario; the oracle on a seeded subset."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import corridor_oracle as K
 import corridor_util as U
 from corridor_util import tab_close
+from device_form import (d_bounds, d_bspline, d_dp, d_offsets, d_reference_length, d_reference_states, d_segment, d_spline_fit,
+                         host_equals_device)
+from line_cases import (REFUSED, SEG_KEYS, SPLINE_SIZES, _check_bspline, _check_segment, _check_states, _degree, check_spline_table, close,
+                        smooth_line, walk)
 from path_optimizer_2_amd import capi
+from shared_util import capi_geom, same_bytes
 
 pytestmark = pytest.mark.gpu
-
-SENT, SENT_I = -1.2345e300, -777          # what the device outputs are filled with before a call
-GUARD = 512                               # elements of sentinel behind every device output
-REFUSED = -4                              # PQP_ERR_CAPACITY
 
 
 @pytest.fixture(scope="module")
@@ -32,215 +31,9 @@ def handle(hip_lib):
     h.close()
 
 
-# ---- device-form plumbing ----------------------------------------------------------------------------------------------------------
-def _dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def _t(a, dt=np.float64):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(_dev())
-
-
-class Out:
-    """a device output of `shape` at the start of an allocation GUARD elements longer, all of it filled with the sentinel"""
-
-    def __init__(self, shape, dt=np.float64):
-        import torch
-        self.shape, self.n = tuple(shape), int(np.prod(shape))
-        self.sent = SENT if dt == np.float64 else SENT_I
-        self.t = torch.full((self.n + GUARD,), self.sent, dtype=torch.float64 if dt == np.float64 else torch.int32, device=_dev())
-
-    def get(self):
-        a = self.t.cpu().numpy()
-        assert np.all(a[self.n:] == self.sent), "the device form wrote behind its output"
-        return a[:self.n].reshape(self.shape)
-
-    def untouched(self):
-        return bool(np.all(self.t.cpu().numpy() == self.sent))
-
-
-def _call(h, name, *args):
-    import torch
-    conv = [C.c_void_p(a.t.data_ptr()) if isinstance(a, Out) else C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args]
-    torch.cuda.synchronize(_dev())
-    rc = getattr(h.lib, name)(h._h, *conv)
-    h.sync()
-    return rc
-
-
-def d_spline_fit(h, s, x, y, m_of=None):
-    B, m = np.shape(s)
-    tab, ext = Out((B, 9, m)), Out((B, 4))
-    if m_of is None:
-        rc = _call(h, "pqp_spline_fit_device", B, m, _t(s), _t(x), _t(y), tab, ext)
-    else:
-        rc = _call(h, "pqp_spline_fit_var_device", B, m, _t(m_of, np.int32), _t(s), _t(x), _t(y), tab, ext)
-    return (rc, tab, ext) if rc else (rc, tab.get(), ext.get())
-
-
-def d_reference_states(h, tab, ext, max_s, n_max, start=None, dynamic=True):
-    B, m = tab.shape[0], tab.shape[2]
-    ref, cnt = Out((B, n_max, 5)), Out((B,), np.int32)
-    err = Out((B, 2)) if start is not None else None
-    rc = _call(h, "pqp_reference_states_device", B, n_max, m, _t(tab), _t(ext), _t(max_s), None if start is None else _t(start), 0.15, 0.3,
-               1 if dynamic else 0, ref, cnt, err)
-    if rc:
-        return rc, (ref, cnt)
-    return rc, ref.get(), cnt.get(), None if err is None else err.get()
-
-
-SEG_KEYS = ("x", "y", "s", "angle", "k")
-
-
-def d_segment(h, tab, ext, max_s, n_max):
-    B, m = tab.shape[0], tab.shape[2]
-    o = {k: Out((B, n_max)) for k in SEG_KEYS}
-    cnt = Out((B,), np.int32)
-    rc = _call(h, "pqp_segment_raw_reference_device", B, n_max, m, _t(tab), _t(ext), _t(max_s), 1.0, *(o[k] for k in SEG_KEYS), cnt)
-    if rc:
-        return rc, list(o.values()) + [cnt]
-    r = {k: v.get() for k, v in o.items()}
-    r["count"] = cnt.get()
-    return rc, r
-
-
-def d_reference_length(h, tab, ext, length, target):
-    B, m = tab.shape[0], tab.shape[2]
-    out = Out((B,))
-    rc = _call(h, "pqp_reference_length_device", B, m, _t(tab), _t(ext), _t(length), _t(target), out)
-    return (rc, out) if rc else (rc, out.get())
-
-
-def d_offsets(h, tab, ext, at_s, l, m_of=None):
-    B, ms, m = tab.shape[0], tab.shape[2], at_s.shape[1]
-    x, y, s = Out((B, m)), Out((B, m)), Out((B, m))
-    rc = _call(h, "pqp_offsets_to_points_device", B, ms, m, _t(tab), _t(ext), _t(at_s), _t(l), None if m_of is None else _t(m_of, np.int32), x, y, s)
-    return (rc, [x, y, s]) if rc else (rc, x.get(), y.get(), s.get())
-
-
-def d_bspline(h, pts, n_pts, n_max):
-    B, p_max = pts.shape[0], pts.shape[1]
-    o = {k: Out((B, n_max)) for k in ("x", "y", "s")}
-    cnt = Out((B,), np.int32)
-    rc = _call(h, "pqp_bspline_resample_device", B, p_max, n_max, _t(pts), _t(n_pts, np.int32), o["x"], o["y"], o["s"], cnt)
-    if rc:
-        return rc, list(o.values()) + [cnt]
-    r = {k: v.get() for k, v in o.items()}
-    r["count"] = cnt.get()
-    return rc, r
-
-
-def d_dp(h, tab, ext, length, start, dist, geom, max_layers, map_of=None, prm=None):
-    B, m = tab.shape[0], tab.shape[2]
-    if prm is None:
-        prm = capi.PqpDpParams()
-        h.lib.pqp_dp_default_params(C.byref(prm))
-    ls, lb, ub, vl = Out((B, max_layers)), Out((B, max_layers)), Out((B, max_layers)), Out((B,))
-    cnt = Out((B,), np.int32)
-    rc = _call(h, "pqp_dp_corridor_device", B, m, max_layers, _t(tab), _t(ext), _t(length), _t(start), _t(capi._column_major(dist, np.float32), np.float32),
-               None if map_of is None else _t(map_of, np.int32), C.byref(geom), C.byref(prm), ls, lb, ub, cnt, vl)
-    if rc:
-        return rc, [ls, lb, ub, cnt, vl]
-    return rc, ls.get(), lb.get(), ub.get(), cnt.get(), vl.get()
-
-
-def d_bounds(h, ref, n_of, tab, ext, dist, geom, map_of=None):
-    B, n, m = ref.shape[0], ref.shape[1], tab.shape[2]
-    bounds, nv = Out((B, n, 6)), Out((B,), np.int32)
-    rc = _call(h, "pqp_corridor_bounds_device", B, n, m, _t(ref), _t(n_of, np.int32), _t(tab), _t(ext), _t(capi._column_major(dist, np.float32), np.float32),
-               None if map_of is None else _t(map_of, np.int32), C.byref(geom), C.byref(h.corridor_params()), bounds, nv)
-    assert rc == 0
-    return bounds.get(), nv.get()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def rows_after(count, n):
-    """mask [B][n]: True on the rows at and past each scenario's count"""
-    return np.arange(n)[None, :] >= np.minimum(np.maximum(np.asarray(count), 0), n)[:, None]
-
-
-def host_equals_device(host, dev, count, n):
-    """the host form's rows up to count equal the device form's bit for bit; past count the host form has zeros, the device form
-    wrote nothing (the sentinel)"""
-    past = rows_after(count, n)
-    past = past.reshape(past.shape + (1,) * (np.ndim(host) - 2))
-    past = np.broadcast_to(past, np.shape(host))
-    assert same_bits(np.where(past, 0.0, dev), np.where(past, 0.0, host))
-    assert np.all(np.asarray(host)[past] == 0.0)
-    assert np.all(np.asarray(dev)[past] == SENT)
-
-
-def _geom(g):
-    return capi.PqpGridGeometry(g.rows, g.cols, g.resolution, g.length_x, g.length_y, g.pos_x, g.pos_y)
-
-
-# ---- lines ------------------------------------------------------------------------------------------------------------------------
-def spacings(rng, m, lo=1e-3, hi=20.0):
-    return np.exp(rng.uniform(np.log(lo), np.log(hi), m - 1))
-
-
-def walk(rng, m, lo=1e-3, hi=20.0):
-    """random-walk knots (s, x, y) for the spline fit: spacings log-uniform in [lo, hi] m, values a random walk"""
-    s = np.concatenate([[0.0], np.cumsum(spacings(rng, m, lo, hi))])
-    return s, np.cumsum(rng.normal(size=m)), np.cumsum(rng.normal(size=m))
-
-
-def smooth_line(rng, m, length, heading=None, lo=1e-3, hi=20.0):
-    """m knots of a smooth curve of parameter length `length` (spacings log-uniform in [lo, hi], scaled to it), starting in direction
-    `heading` -> the restatement's splines and the packed table"""
-    d = spacings(rng, m, lo, hi)
-    s = np.concatenate([[0.0], np.cumsum(d * (length / d.sum()))])
-    s[-1] = length
-    th = rng.uniform(-np.pi, np.pi) if heading is None else heading
-    l1, l2, p1, p2 = rng.uniform(25.0, 60.0), rng.uniform(40.0, 90.0), rng.uniform(0, 6.3), rng.uniform(0, 6.3)
-    u = s + 0.3 * l1 * np.sin(s / l1 + p1) - 0.3 * l1 * np.sin(p1)
-    v = 0.25 * l2 * (np.sin(s / l2 + p2) - np.sin(p2))
-    x, y = 3.0 + u * np.cos(th) - v * np.sin(th), -2.0 + u * np.sin(th) + v * np.cos(th)
-    sx, sy = K.spline_fit(s, x), K.spline_fit(s, y)
-    tab, ext = K.pack_spline(sx, sy)
-    return dict(s=s, x=x, y=y, sx=sx, sy=sy, tab=tab, ext=ext, length=float(s[-1]))
-
-
-def close(got, want, rel, what=""):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = np.abs(got - want) / np.maximum(1.0, np.abs(want))
-    assert float(err.max(initial=0.0)) <= rel, (what, float(err.max()), int(err.argmax()))
-
-
-def check_spline_table(tab, ext, s, x, y, lib=None):
-    """one scenario's table against the restatement (and the reference's own tk::spline when it is built): SPLINE_TOL of a row's largest"""
-    want_tab, want_ext = K.pack_spline(K.spline_fit(s, x), K.spline_fit(s, y))
-    tab_close(tab, ext, want_tab, want_ext)
-    if lib is None:
-        return
-    m = len(s)
-    for vals, r0 in ((x, 1), (y, 5)):
-        sq, vq = np.ascontiguousarray(s, dtype=np.float64), np.ascontiguousarray(vals, dtype=np.float64)
-        hd = lib.ref_spline_new(m, sq.ctypes.data, vq.ctypes.data)
-        just_right = np.nextafter(sq[:-1], np.inf)
-        dl = just_right - sq[:-1]                # one ulp of the knot: on a line thousands of metres long the cubic term over it is not negligible
-        d1, d2, d3 = (np.array([lib.ref_spline_deriv(hd, o, t) for t in just_right]) for o in (1, 2, 3))
-        a = d3 / 6.0
-        b = (d2 - 6.0 * a * dl) / 2.0
-        c = d1 - (3.0 * a * dl + 2.0 * b) * dl
-        for r, want in ((1, a), (2, b), (3, c)):
-            U.rows_close(tab[r0 + r][:-1], want, ("reference build", r0, r))
-        lib.ref_spline_free(hd)
-
-
 # =====================================================================================================================================
 # pqp_spline_fit / pqp_spline_fit_var_device
 # =====================================================================================================================================
-SPLINE_SIZES = [3, 4, 63, 64, 65, 129, 400, 878, 2925]
-
-
 def test_spline_fit_sizes_cover_the_lds_edges():
     assert U.fits("spline_fit_kernel", m=2925) and not U.fits("spline_fit_kernel", m=2926)
     assert U.dynamic_lds("spline_fit_kernel", m=877) <= 48 * 1024 < U.dynamic_lds("spline_fit_kernel", m=878)
@@ -259,7 +52,7 @@ def test_spline_fit_against_the_oracle(handle, m):
     rc, tab, ext = d_spline_fit(handle, s, x, y)
     assert rc == 0
     htab, hext = handle.spline_fit(s, x, y)
-    assert same_bits(htab, tab) and same_bits(hext, ext)
+    assert same_bytes(htab, tab) and same_bytes(hext, ext)
     lib = U.ref_spline_lib()
     for q in range(B):
         check_spline_table(tab[q], ext[q], s[q], x[q], y[q], lib if q == B - 1 else None)
@@ -286,11 +79,11 @@ def _check_var_table(tab, ext, s, x, y, n, stride, fixed_tab=None, fixed_ext=Non
         assert np.all(tab[[2, 3, 4, 6, 7, 8]] == 0.0) and np.all(ext == 0.0)
         return
     n = min(n, stride)
-    assert same_bits(tab[:, :n], fixed_tab) and same_bits(ext, fixed_ext)
+    assert same_bytes(tab[:, :n], fixed_tab) and same_bytes(ext, fixed_ext)
     j = np.arange(1, stride - n + 1, dtype=np.float64)
-    assert same_bits(tab[0, n:], s[n - 1] + 1e6 * j)
+    assert same_bytes(tab[0, n:], s[n - 1] + 1e6 * j)
     assert np.all(tab[1, n:] == x[n - 1]) and np.all(tab[5, n:] == y[n - 1])
-    assert same_bits(tab[[2, 3, 4, 6, 7, 8], n:], np.zeros((6, stride - n)))
+    assert same_bytes(tab[[2, 3, 4, 6, 7, 8], n:], np.zeros((6, stride - n)))
 
 
 @pytest.mark.parametrize("m_max", [65, 400])
@@ -333,7 +126,7 @@ def test_spline_fit_var_large_batch(handle):
             _check_var_table(tab[q], ext[q], s[q], x[q], y[q], int(n), m_max, ft[j], fe[j])
     perm = rng.permutation(B)
     rc, ptab, pext = d_spline_fit(handle, s[perm], x[perm], y[perm], m_of=m_of[perm])
-    assert rc == 0 and same_bits(ptab, tab[perm]) and same_bits(pext, ext[perm])
+    assert rc == 0 and same_bytes(ptab, tab[perm]) and same_bytes(pext, ext[perm])
     for q in np.random.default_rng(5).choice(B, 16, replace=False):
         n = int(m_of[q])
         want_tab, want_ext = K.pack_spline(K.spline_fit(s[q, :n], x[q, :n]), K.spline_fit(s[q, :n], y[q, :n]))
@@ -343,22 +136,6 @@ def test_spline_fit_var_large_batch(handle):
 # =====================================================================================================================================
 # pqp_reference_states / pqp_segment_raw_reference
 # =====================================================================================================================================
-def _check_states(ref, count, line, max_s, n_max, dynamic=True):
-    want = K.build_reference_from_spline(line["sx"], line["sy"], float(max_s), dynamic=dynamic)
-    assert count == len(want), (count, len(want))
-    k = min(count, n_max)
-    close(ref[:k], want[:k], 1e-11, "reference states")
-
-
-def _check_segment(seg, q, line, max_s, n_max):
-    x, y, s, ang, k = K.segment_raw_reference(line["sx"], line["sy"], float(max_s))
-    assert seg["count"][q] == len(s)
-    n = min(len(s), n_max)
-    assert np.array_equal(seg["s"][q, :n], s[:n])
-    for key, want in (("x", x), ("y", y), ("angle", ang), ("k", k)):
-        close(seg[key][q, :n], want[:n], 1e-11, key)
-
-
 @pytest.mark.parametrize("m,length", [(65, 60.0), (129, 300.0), (400, 1200.0), (2000, 3000.0)])
 def test_reference_states_on_long_lines(handle, m, length):
     """lines of 60-3000 m on 65-2000 knots, n_max as large as LDS allows: max_s past the last knot, on a knot, below one step; fixed
@@ -436,7 +213,7 @@ def test_initial_error_with_headings_near_pi(handle):
     rc, ref, count, err = d_reference_states(handle, tab, ext, max_s, 1200, start=start)
     assert rc == 0
     href, hcount, herr = handle.reference_states(tab, ext, max_s, 1200, start=start)
-    assert same_bits(herr, err)
+    assert same_bytes(herr, err)
     for q, l in enumerate(lines):
         off, dpsi = K.process_init_state(l["sx"], l["sy"], *start[q])
         assert err[q, 0] == pytest.approx(off, abs=1e-12) and err[q, 1] == pytest.approx(dpsi, abs=1e-12)
@@ -492,7 +269,7 @@ def test_reference_length_scan_rounds_and_ties(handle, length):
     L = np.full(len(lines), length); target = np.array(targets)
     rc, got = d_reference_length(handle, tab, ext, L, target)
     assert rc == 0
-    assert same_bits(handle.reference_length(tab, ext, L, target), got)
+    assert same_bytes(handle.reference_length(tab, ext, L, target), got)
     for q, l in enumerate(lines):
         want = K.reference_length(l["sx"], l["sy"], length, target[q, 0], target[q, 1])
         assert got[q] == pytest.approx(want, abs=1e-9), (q, got[q], want)
@@ -551,27 +328,6 @@ def test_offsets_to_points_against_the_oracle(handle, m_spline, m):
 # =====================================================================================================================================
 # pqp_bspline_resample
 # =====================================================================================================================================
-def _degree(pts):
-    """ReferencePathSmoother::bSpline's degree by the average point spacing"""
-    d = np.diff(np.asarray(pts), axis=0)
-    length = 0.0
-    for ex, ey in d:
-        length += np.sqrt(ex * ex + ey * ey)
-    avg = length / (len(pts) - 1)
-    return 3 if avg > 10.0 else (4 if avg > 5.0 else 5)
-
-
-def _check_bspline(r, q, pts):
-    if len(pts) <= _degree(pts):                 # tinyspline refuses a degree >= the number of control points: no line
-        assert r["count"][q] == 0
-        return
-    x, y, s = K.bspline_resample(pts)
-    assert r["count"][q] == len(x)
-    n = min(len(x), r["x"].shape[1])
-    close(r["x"][q, :n], x[:n], 1e-12, "x"); close(r["y"][q, :n], y[:n], 1e-12, "y")
-    np.testing.assert_allclose(r["s"][q, :n], s[:n], rtol=0, atol=1e-11 * max(1.0, s[-1] / 50.0))
-
-
 @pytest.mark.parametrize("p", [4, 33, 64, 65, 200])
 def test_bspline_resample_degrees_and_sizes(handle, p):
     """all three degrees - average spacing exactly 10.0 (degree 4) and 5.0 (degree 5) from collinear points on integer x, above 10 (3) - and
@@ -644,17 +400,17 @@ def test_dp_corridor_long_lines_several_maps(handle):
     assert U.dynamic_lds("dp_corridor_kernel", m=m, max_layers=140, nlat=nlat) > 48 * 1024
     top = U.largest("dp_corridor_kernel", "max_layers", m=m, nlat=nlat)
     for max_layers in (140, top):
-        rc, *out = d_dp(handle, tab, ext, lengths, start, dist, _geom(g), max_layers, map_of=[0, 1, 2])
+        rc, *out = d_dp(handle, tab, ext, lengths, start, dist, capi_geom(g), max_layers, map_of=[0, 1, 2])
         assert rc == 0
         assert out[3].min() > 40
-        h = handle.dp_corridor(tab, ext, lengths, start, dist, _geom(g), max_layers=max_layers, map_of=[0, 1, 2])
-        assert np.array_equal(h[3], out[3]) and same_bits(h[4], out[4])
+        h = handle.dp_corridor(tab, ext, lengths, start, dist, capi_geom(g), max_layers=max_layers, map_of=[0, 1, 2])
+        assert np.array_equal(h[3], out[3]) and same_bytes(h[4], out[4])
         for j in range(3):
             host_equals_device(h[j], out[j], out[3], max_layers)
         if max_layers == top:
             for q, c in enumerate(cs):
                 _check_dp(out, q, c, lengths[q], start[q])
-    rc, outs = d_dp(handle, tab, ext, lengths, start, dist, _geom(g), top + 1, map_of=[0, 1, 2])
+    rc, outs = d_dp(handle, tab, ext, lengths, start, dist, capi_geom(g), top + 1, map_of=[0, 1, 2])
     assert rc == REFUSED and all(o.untouched() for o in outs)
 
 
@@ -762,15 +518,15 @@ def test_batch_reference_states_and_segment(handle, var_batch):
     rc, ref, count, err = d_reference_states(handle, tab, ext, max_s, n_max, start=start)
     assert rc == 0
     href, hcount, herr = handle.reference_states(tab, ext, max_s, n_max, start=start)
-    assert np.array_equal(hcount, count) and same_bits(herr, err)
+    assert np.array_equal(hcount, count) and same_bytes(herr, err)
     host_equals_device(href, ref, count, n_max)
     perm = np.random.default_rng(3).permutation(B)
     rc, pref, pcount, perr = d_reference_states(handle, tab[perm], ext[perm], max_s[perm], n_max, start=start[perm])
-    assert rc == 0 and same_bits(pref, ref[perm]) and np.array_equal(pcount, count[perm]) and same_bits(perr, err[perm])
+    assert rc == 0 and same_bytes(pref, ref[perm]) and np.array_equal(pcount, count[perm]) and same_bytes(perr, err[perm])
     # the padded tables against the exact-size ones
     for n, (idx, ft, fe) in vb["exact"].items():
         rc, eref, ecount, eerr = d_reference_states(handle, ft, fe, max_s[idx], n_max, start=start[idx])
-        assert rc == 0 and np.array_equal(ecount, count[idx]) and same_bits(eerr, err[idx]) and same_bits(eref, ref[idx])
+        assert rc == 0 and np.array_equal(ecount, count[idx]) and same_bytes(eerr, err[idx]) and same_bytes(eref, ref[idx])
     for q in SUBSET:
         line = _oracle_line(vb, q)
         _check_states(ref[q], int(count[q]), line, max_s[q], n_max)
@@ -784,10 +540,10 @@ def test_batch_reference_states_and_segment(handle, var_batch):
     for key in SEG_KEYS:
         host_equals_device(hseg[key], seg[key], seg["count"], n_seg)
     rc, pseg = d_segment(handle, tab[perm], ext[perm], max_s[perm], n_seg)
-    assert rc == 0 and all(same_bits(pseg[k], seg[k][perm]) for k in SEG_KEYS + ("count",))
+    assert rc == 0 and all(same_bytes(pseg[k], seg[k][perm]) for k in SEG_KEYS + ("count",))
     for n, (idx, ft, fe) in vb["exact"].items():
         rc, eseg = d_segment(handle, ft, fe, max_s[idx], n_seg)
-        assert rc == 0 and all(same_bits(eseg[k], seg[k][idx]) for k in SEG_KEYS + ("count",))
+        assert rc == 0 and all(same_bytes(eseg[k], seg[k][idx]) for k in SEG_KEYS + ("count",))
     for q in SUBSET:
         _check_segment(seg, q, _oracle_line(vb, q), max_s[q], n_seg)
 
@@ -807,13 +563,13 @@ def test_batch_reference_length_and_offsets(handle, var_batch):
         target[q, 1] = np.interp(sq, vb["s"][q, :n], vb["y"][q, :n]) + rng.uniform(-2, 2)
     rc, got = d_reference_length(handle, tab, ext, L, target)
     assert rc == 0
-    assert same_bits(handle.reference_length(tab, ext, L, target), got)
+    assert same_bytes(handle.reference_length(tab, ext, L, target), got)
     perm = rng.permutation(B)
     rc, pgot = d_reference_length(handle, tab[perm], ext[perm], L[perm], target[perm])
-    assert rc == 0 and same_bits(pgot, got[perm])
+    assert rc == 0 and same_bytes(pgot, got[perm])
     for n, (idx, ft, fe) in vb["exact"].items():
         rc, egot = d_reference_length(handle, ft, fe, L[idx], target[idx])
-        assert rc == 0 and same_bits(egot, got[idx])
+        assert rc == 0 and same_bytes(egot, got[idx])
     for q in SUBSET:
         line = _oracle_line(vb, q)
         assert got[q] == pytest.approx(K.reference_length(line["sx"], line["sy"], L[q], target[q, 0], target[q, 1]), abs=1e-9)
@@ -828,10 +584,10 @@ def test_batch_reference_length_and_offsets(handle, var_batch):
     for h_, d_ in ((hx, x), (hy, y), (hs, s)):
         host_equals_device(h_, d_, m_of, m)
     rc, px, py, ps = d_offsets(handle, tab[perm], ext[perm], at_s[perm], l[perm], m_of[perm])
-    assert rc == 0 and same_bits(px, x[perm]) and same_bits(py, y[perm]) and same_bits(ps, s[perm])
+    assert rc == 0 and same_bytes(px, x[perm]) and same_bytes(py, y[perm]) and same_bytes(ps, s[perm])
     for n, (idx, ft, fe) in vb["exact"].items():
         rc, ex, ey, es = d_offsets(handle, ft, fe, at_s[idx], l[idx], m_of[idx])
-        assert rc == 0 and same_bits(ex, x[idx]) and same_bits(ey, y[idx]) and same_bits(es, s[idx])
+        assert rc == 0 and same_bytes(ex, x[idx]) and same_bytes(ey, y[idx]) and same_bytes(es, s[idx])
     for q in SUBSET:
         k = int(m_of[q])
         line = _oracle_line(vb, q)
@@ -857,7 +613,7 @@ def test_batch_bspline_resample(handle):
         host_equals_device(h[key], r[key], r["count"], n_max)
     perm = rng.permutation(B)
     rc, pr = d_bspline(handle, pts[perm], n_pts[perm], n_max)
-    assert rc == 0 and all(same_bits(pr[k], r[k][perm]) for k in ("x", "y", "s", "count"))
+    assert rc == 0 and all(same_bytes(pr[k], r[k][perm]) for k in ("x", "y", "s", "count"))
     for q in SUBSET:
         if n_pts[q] >= 4 and r["count"][q] <= n_max:
             _check_bspline(r, q, pts[q, :n_pts[q]])
@@ -877,19 +633,19 @@ def test_batch_dp_corridor_and_corridor_bounds_on_padded_tables(handle):
     start = np.array([[cs[i]["ref"][0, 3] + rng.uniform(-0.5, 0.5), cs[i]["ref"][0, 4] + rng.uniform(-1.0, 1.0), cs[i]["ref"][0, 2] + rng.uniform(-0.1, 0.1)]
                       for i in map_of])
     max_layers = 96
-    rc, *out = d_dp(handle, tab, ext, lengths, start, dist, _geom(g), max_layers, map_of=map_of)
+    rc, *out = d_dp(handle, tab, ext, lengths, start, dist, capi_geom(g), max_layers, map_of=map_of)
     assert rc == 0 and np.all(out[3] > 0)
-    hout = handle.dp_corridor(tab, ext, lengths, start, dist, _geom(g), max_layers=max_layers, map_of=map_of)
-    assert np.array_equal(hout[3], out[3]) and same_bits(hout[4], out[4])
+    hout = handle.dp_corridor(tab, ext, lengths, start, dist, capi_geom(g), max_layers=max_layers, map_of=map_of)
+    assert np.array_equal(hout[3], out[3]) and same_bytes(hout[4], out[4])
     for j in range(3):
         host_equals_device(hout[j], out[j], out[3], max_layers)
     perm = rng.permutation(B)
-    rc, *pout = d_dp(handle, tab[perm], ext[perm], lengths[perm], start[perm], dist, _geom(g), max_layers, map_of=map_of[perm])
-    assert rc == 0 and all(same_bits(pout[j], out[j][perm]) for j in range(5))
+    rc, *pout = d_dp(handle, tab[perm], ext[perm], lengths[perm], start[perm], dist, capi_geom(g), max_layers, map_of=map_of[perm])
+    assert rc == 0 and all(same_bytes(pout[j], out[j][perm]) for j in range(5))
     for i, c in enumerate(cs):
         idx = np.nonzero(map_of == i)[0]
-        rc, *eout = d_dp(handle, np.repeat(c["tab"][None], len(idx), 0), ext[idx], lengths[idx], start[idx], dist, _geom(g), max_layers, map_of=map_of[idx])
-        assert rc == 0 and all(same_bits(eout[j], out[j][idx]) for j in range(5))
+        rc, *eout = d_dp(handle, np.repeat(c["tab"][None], len(idx), 0), ext[idx], lengths[idx], start[idx], dist, capi_geom(g), max_layers, map_of=map_of[idx])
+        assert rc == 0 and all(same_bytes(eout[j], out[j][idx]) for j in range(5))
     for q in SUBSET[:8]:
         _check_dp(out, q, cs[map_of[q]], lengths[q], start[q])
     # corridor_bounds on the same padded / exact tables (reference states of each line first)
@@ -897,8 +653,8 @@ def test_batch_dp_corridor_and_corridor_bounds_on_padded_tables(handle):
     rc, ref, count, _ = d_reference_states(handle, tab, ext, lengths, n)
     assert rc == 0
     n_of = np.minimum(count, n).astype(np.int32)
-    b, nv = d_bounds(handle, ref, n_of, tab, ext, dist, _geom(g), map_of)
+    b, nv = d_bounds(handle, ref, n_of, tab, ext, dist, capi_geom(g), map_of)
     for i, c in enumerate(cs):
         idx = np.nonzero(map_of == i)[0]
-        eb, env = d_bounds(handle, ref[idx], n_of[idx], np.repeat(c["tab"][None], len(idx), 0), ext[idx], dist, _geom(g), map_of[idx])
-        assert np.array_equal(env, nv[idx]) and same_bits(eb, b[idx])
+        eb, env = d_bounds(handle, ref[idx], n_of[idx], np.repeat(c["tab"][None], len(idx), 0), ext[idx], dist, capi_geom(g), map_of[idx])
+        assert np.array_equal(env, nv[idx]) and same_bytes(eb, b[idx])

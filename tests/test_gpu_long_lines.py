@@ -9,12 +9,13 @@ import pytest
 import corridor_oracle as K
 import corridor_util as U
 import long_line_util as LL
-from chain_stops_util import steps_one_by_one as _steps_one_by_one
+from chain_util import scenarios, smoother_params, steps_one_by_one
+from device_form import (d_bounds, d_bspline, d_dp, d_offsets, d_reference_length, d_reference_states, d_segment, d_spline_fit,
+                         host_equals_device)
+from line_cases import (REFUSED, SPLINE_SIZES, SEG_KEYS, _check_bspline, _check_segment, _check_states, check_spline_table, close, smooth_line,
+                        walk)
 from path_optimizer_2_amd import capi
-from test_gpu_chain import _smoother_params
-from test_gpu_line_geometry import (REFUSED, SPLINE_SIZES, SEG_KEYS, _check_bspline, _check_segment, _check_states, check_spline_table,
-                                    close, d_bounds, d_bspline, d_dp, d_offsets, d_reference_length, d_reference_states, d_segment,
-                                    d_spline_fit, host_equals_device, same_bits, smooth_line, walk)
+from shared_util import same_bytes
 
 pytestmark = pytest.mark.gpu
 
@@ -30,8 +31,8 @@ def handles(hip_lib):
 
 def _same_all(a, b):
     if isinstance(a, dict):
-        return all(same_bits(a[k], b[k]) for k in a)
-    return all(same_bits(x, y) for x, y in zip(a, b))
+        return all(same_bytes(a[k], b[k]) for k in a)
+    return all(same_bytes(x, y) for x, y in zip(a, b))
 
 
 # ---- 1 + 4: past the edge and well beyond under option 1; option 0 refuses the same inputs ---------------------------------------------------
@@ -43,16 +44,16 @@ def test_spline_fit_past_the_edge(handles, m):
     rc, tab, ext = d_spline_fit(handles[1], s, x, y)
     assert rc == 0
     htab, hext = handles[1].spline_fit(s, x, y)
-    assert same_bits(htab, tab) and same_bits(hext, ext)
+    assert same_bytes(htab, tab) and same_bytes(hext, ext)
     lib = U.ref_spline_lib()
     for q in range(2):
         check_spline_table(tab[q], ext[q], s[q], x[q], y[q], lib if q == 1 else None)
     # _var on the same knots, padded: the real rows are the fixed fit's
     m_of = np.array([m, m - 700], dtype=np.int32)
     rc, vtab, vext = d_spline_fit(handles[1], s, x, y, m_of=m_of)
-    assert rc == 0 and same_bits(vtab[0], tab[0]) and same_bits(vext[0], ext[0])
+    assert rc == 0 and same_bytes(vtab[0], tab[0]) and same_bytes(vext[0], ext[0])
     rc, t1, e1 = d_spline_fit(handles[1], s[1:, :m - 700], x[1:, :m - 700], y[1:, :m - 700])
-    assert rc == 0 and same_bits(vtab[1, :, :m - 700], t1[0]) and same_bits(vext[1], e1[0])
+    assert rc == 0 and same_bytes(vtab[1, :, :m - 700], t1[0]) and same_bytes(vext[1], e1[0])
     rc, t0, e0 = d_spline_fit(handles[0], s, x, y)
     assert rc == REFUSED and t0.untouched() and e0.untouched()
 
@@ -104,7 +105,7 @@ def test_reference_length_and_offsets_past_the_edge(handles, scale):
     L = np.array([line["length"]] * 2)
     rc, got = d_reference_length(handles[1], tab, ext, L, tgt)
     assert rc == 0
-    assert same_bits(handles[1].reference_length(tab, ext, L, tgt), got)
+    assert same_bytes(handles[1].reference_length(tab, ext, L, tgt), got)
     for q in range(2):
         assert got[q] == pytest.approx(K.reference_length(line["sx"], line["sy"], L[q], tgt[q, 0], tgt[q, 1]), abs=1e-9)
     rc, out = d_reference_length(handles[0], tab, ext, L, tgt)
@@ -118,7 +119,7 @@ def test_reference_length_and_offsets_past_the_edge(handles, scale):
     rc, x, y, s = d_offsets(handles[1], line["tab"][None], line["ext"][None], at_s, l)
     assert rc == 0
     hx, hy, hs = handles[1].offsets_to_points(line["tab"][None], line["ext"][None], at_s, l)
-    assert same_bits(hx, x) and same_bits(hy, y) and same_bits(hs, s)
+    assert same_bytes(hx, x) and same_bytes(hy, y) and same_bytes(hs, s)
     wx, wy, ws = K.offsets_to_points(line["sx"], line["sy"], at_s[0], l[0])
     close(x[0], wx, 1e-11, "x"); close(y[0], wy, 1e-11, "y")
     np.testing.assert_allclose(s[0], ws, rtol=0, atol=1e-10 * ws[-1] / 30.0)
@@ -159,7 +160,7 @@ def test_dp_corridor_past_the_edge(handles, length):
     assert rc == 0 and out[3][0] > 0.9 * length / 1.5
     h = handles[1].dp_corridor(line["tab"][None], line["ext"][None], np.array([line["length"]]), start[None], road["dist"][None], road["geom"],
                                max_layers=max_layers)
-    assert np.array_equal(h[3], out[3]) and same_bits(h[4], out[4])
+    assert np.array_equal(h[3], out[3]) and same_bytes(h[4], out[4])
     for j in range(3):
         host_equals_device(h[j], out[j], out[3], max_layers)
     want = K.graph_search_dp(line["sx"], line["sy"], line["length"], tuple(start), np.asfortranarray(road["dist"]), road["kgeom"])
@@ -192,7 +193,7 @@ def test_corridor_bounds_past_the_edge(handles, length):
     n_of = np.array([n], dtype=np.int32)
     bounds, nv = d_bounds(handles[1], ref, n_of, line["tab"][None], line["ext"][None], road["dist"][None], road["geom"])
     hb, hnv = handles[1].corridor_bounds(ref, line["tab"][None], line["ext"][None], road["dist"], road["geom"], n_of=n_of)
-    assert np.array_equal(hnv, nv) and same_bits(hb, bounds)
+    assert np.array_equal(hnv, nv) and same_bytes(hb, bounds)
     fdist = np.asfortranarray(road["dist"])              # (the oracle reads the layer through a column-major view)
     k = int(nv[0])
     assert k > 1000
@@ -213,7 +214,7 @@ def test_corridor_bounds_past_the_edge(handles, length):
     st[0, :, 4] = np.random.default_rng(3).uniform(-0.3, 0.3, n)
     b2, nv2 = handles[1].corridor_bounds_on_states(ref, st, line["tab"][None], line["ext"][None], road["dist"], road["geom"], n_of=n_of)
     b2l, nv2l = handles[2].corridor_bounds_on_states(ref, st, line["tab"][None], line["ext"][None], road["dist"], road["geom"], n_of=n_of)
-    assert same_bits(b2, b2l) and np.array_equal(nv2, nv2l)
+    assert same_bytes(b2, b2l) and np.array_equal(nv2, nv2l)
     with pytest.raises(capi.PqpError, match="pqp error -4:"):
         handles[0].corridor_bounds(ref, line["tab"][None], line["ext"][None], road["dist"], road["geom"], n_of=n_of)
     with pytest.raises(capi.PqpError, match="pqp error -4:"):
@@ -230,8 +231,8 @@ def test_spline_fit_long_form_bits(handles, m):
     for mo in (None, m_of):
         got = {v: d_spline_fit(handles[v], s, x, y, m_of=mo) for v in (0, 1, 2)}
         assert got[0][0] == got[1][0] == got[2][0] == 0
-        assert same_bits(got[0][1], got[2][1]) and same_bits(got[0][2], got[2][2])
-        assert same_bits(got[0][1], got[1][1]) and same_bits(got[0][2], got[1][2])
+        assert same_bytes(got[0][1], got[2][1]) and same_bytes(got[0][2], got[2][2])
+        assert same_bytes(got[0][1], got[1][1]) and same_bytes(got[0][2], got[1][2])
 
 
 @pytest.mark.parametrize("name", ["scene_a", "scene_b"])
@@ -342,7 +343,7 @@ def test_chain_on_long_lines(hip_lib, method):
     B = 10
     sc = _long_scenarios(B)
     h = LL.with_option(capi.Handle(capi.production_params(), max_batch=B, max_n=5200), 1)
-    hs = capi.Handle(_smoother_params(), max_batch=B, max_n=2700)
+    hs = capi.Handle(smoother_params(), max_batch=B, max_n=2700)
     cfg = h.chain_config(raw_max=2700, sample_max=2700, layer_max=1800, n_max=5200, output_spacing=1.0, smoothing_method=method)
     got = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs, cfg=cfg)
     assert not (got["stage"] == 9).any(), got["stage"]
@@ -352,7 +353,7 @@ def test_chain_on_long_lines(hip_lib, method):
             smoother_failed += 1
             if smoother_failed > 2:
                 continue
-        want = _steps_one_by_one(h, hs, sc, b, cfg)
+        want = steps_one_by_one(h, hs, sc, b, cfg)
         assert got["stage"][b] == want["stage"] and got["status"][b] == want["status"], (b, got["stage"][b], want)
         if want["stage"] == 0:
             nv = want["nv"]
@@ -369,21 +370,20 @@ def test_chain_on_long_lines(hip_lib, method):
 
 
 def test_chain_short_lines_option_1_is_option_0(hip_lib):
-    from test_gpu_chain import _scenarios
     B = 16
-    sc = _scenarios(B)
+    sc = scenarios(B)
     outs = []
     for opt in (0, 1):
         for graph in (0, 1):
             h = LL.with_option(capi.Handle(capi.production_params(), max_batch=B, max_n=256), opt)
             h.set_option(capi.OPT_CHAIN_GRAPH, graph)
-            hs = capi.Handle(_smoother_params(), max_batch=B, max_n=128)
+            hs = capi.Handle(smoother_params(), max_batch=B, max_n=128)
             for _ in range(4 if graph else 1):           # plain, plain, capture, replay
                 got = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs)
             outs.append(got)
             h.close(); hs.close()
     for o in outs[1:]:
-        assert all(same_bits(outs[0][k], o[k]) for k in outs[0])
+        assert all(same_bytes(outs[0][k], o[k]) for k in outs[0])
 
 
 # ---- 6: a NaN knot and an Inf abscissa in one scenario of a long-form batch ------------------------------------------------------------
@@ -405,7 +405,7 @@ def test_hostile_scenario_leaves_its_neighbours_alone(handles):
              d_reference_length(h, bad_tab, ext, L, np.zeros((B, 3)))]         # (an infinite length would be an endless coarse scan in either form)
     assert all(d[0] == 0 for d in dirty)
     keep = [0, 2, 3]
-    assert all(same_bits(a[keep], b[keep]) for a, b in zip(clean[0], dirty[0][1:]))
-    assert all(same_bits(a[keep], b[keep]) for a, b in zip(clean[1], dirty[1][1:3]))
-    assert all(same_bits(clean[2][k][keep], dirty[2][1][k][keep]) for k in clean[2])
-    assert same_bits(clean[3][keep], dirty[3][1][keep])
+    assert all(same_bytes(a[keep], b[keep]) for a, b in zip(clean[0], dirty[0][1:]))
+    assert all(same_bytes(a[keep], b[keep]) for a, b in zip(clean[1], dirty[1][1:3]))
+    assert all(same_bytes(clean[2][k][keep], dirty[2][1][k][keep]) for k in clean[2])
+    assert same_bytes(clean[3][keep], dirty[3][1][keep])

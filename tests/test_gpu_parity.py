@@ -547,7 +547,7 @@ def test_hip_solution_against_the_direct_active_set_solve(hip_lib):
     """A third, solver-free pin: the primal / dual the HIP kernel returns for a single solve (production setting) is fed
     to a direct sparse-LU solve of the KKT system on its active set; that point passes the KKT conditions by itself and the kernel's x
     equals it - no ADMM of any oracle is involved."""
-    from test_oracle import direct_active_set_solve
+    from kkt_util import direct_active_set_solve
     n = 80
     b = make_batch(6, n, "varied")
     h = capi.Handle(_polished(), max_batch=6, max_n=n)

@@ -223,14 +223,12 @@ def test_car_flags_through_the_drop_in(hip_lib):
     """BaseSolver::setParams with the `car` case (the reference reads these from gflags): solve() + updateProblemFormulationAndSolve() give what the same two
     calls of the C ABI give with the same pqp_params."""
     from path_optimizer_2_amd import capi
-    from test_cpp_shim import CSRC, ROOT, _scenario_text
-    exe = os.path.join(ROOT, "tests", "cpp", "shim_demo")
-    src = [os.path.join(ROOT, "tests", "cpp", "shim_demo.cpp"), os.path.join(CSRC, "base_solver_shim.cpp")]
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe] + src + ["-L" + CSRC, "-lpqp_hip", "-Wl,-rpath," + CSRC], check=True)
+    import cpp_demo
+    exe = cpp_demo.build("shim_demo", hip=False, extra=[cpp_demo.SHIM])
     n = 60
     b = PC.batch(4, n)
     car = PC.CASES["car"]
-    r = subprocess.run([exe] + ["%s=%r" % kv for kv in car.items()], input=_scenario_text(b, 0), capture_output=True, text=True)
+    r = subprocess.run([exe] + ["%s=%r" % kv for kv in car.items()], input=cpp_demo.shim_scenario_text(b, 0), capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     got = np.array([[float(v) for v in ln.split()] for ln in r.stdout.strip().splitlines()])
     one = {k: np.ascontiguousarray(v[:1]) for k, v in b.items()}

@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 
 import emu_util as EU
+from emu_util import compare_counts as _compare
 import pqp_oracle as O
 import width_cases as W
 from path_optimizer_2_amd import capi
-from test_gpu_fused_look import _compare
 
 pytestmark = pytest.mark.gpu
 

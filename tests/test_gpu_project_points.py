@@ -9,14 +9,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import chain_util
 import corridor_oracle as K
 import corridor_util as U
+import cpp_demo
 import project_util as P
 from path_optimizer_2_amd import capi
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1e-9          # tests/test_gpu_corridor.py's rule for pqp_reference_length: the same search, ocml against libm in sqrt / atan2 / sin / cos
+TOL = P.PROJECT_TOL
 LENGTHS = (30.0, 30.0, 25.5, 28.0)
 TILE = capi.PROJECT_TILE_SAMPLES
 
@@ -311,11 +313,10 @@ def test_a_planned_path_projects_onto_the_line_through_its_own_points(hip_lib):
     """pqp_optimize_path_device leaves `out` on the device; on the same stream: chord-length abscissae of its waypoints, pqp_spline_fit_var_device
     through them, pqp_project_points_device of the waypoints (stride 7, with heading) onto that line.  No host copy until all three ran."""
     import torch
-    import test_gpu_chain as T
     B = 4
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     h = capi.Handle(capi.production_params(), max_batch=B, max_n=256)
-    hs = capi.Handle(T._smoother_params(), max_batch=B, max_n=128)
+    hs = capi.Handle(chain_util.smoother_params(), max_batch=B, max_n=128)
     cfg = h.chain_config()
     dev = torch.device("cuda", 0)
     t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
@@ -357,12 +358,11 @@ def test_a_planned_path_projects_onto_the_line_through_its_own_points(hip_lib):
 
 
 def test_the_cpp_projector_agrees_with_the_python_call(handle, lines, tmp_path):
-    import test_project_points as T
-    exe = T.build_demo()
+    exe = cpp_demo.build("project_demo")
     sc = lines["cs"][2]["scene"]
     pts = lines["pts"][2, :40]
     path = tmp_path / "case.bin"
-    T.write_case(path, sc["knots_s"], sc["knots_x"], sc["knots_y"], pts)
+    P.write_case(path, sc["knots_s"], sc["knots_x"], sc["knots_y"], pts)
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     got = np.array([[float(v) for v in ln.split()] for ln in r.stdout.strip().splitlines()])

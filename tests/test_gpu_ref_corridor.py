@@ -7,7 +7,7 @@ the record that is a restatement (grid_map is third-party and not available): se
 Tolerances are the sibling tests', taken from them: test_gpu_corridor._compare / test_gpu_corridor_on_states._compare for the bounds (restated),
 test_gpu_corridor.test_reference_states_and_initial_error for the states, test_gpu_project_points.TOL and its `ambiguous` exemption,
 test_gpu_chain.test_clearance_lookup_on_the_device (equality), test_gpu_footprint._agree / TOL.  `free` is compared exactly except on states
-where a RECORDED clearance is within 1e-5 of its circle's radius (test_ref_corridor.footprint_near: at most 2 % of a scene's states,
+where a RECORDED clearance is within 1e-5 of its circle's radius (ref_corridor.footprint_near: at most 2 % of a scene's states,
 asserted there).  Run with -m gpu on an MI355X."""
 import numpy as np
 import pytest
@@ -15,10 +15,10 @@ import pytest
 import corridor_oracle as K
 import project_util as P
 import ref_corridor as RC
+from footprint_util import FOOTPRINT_TOL
 from path_optimizer_2_amd import capi
-from test_gpu_footprint import TOL as FOOTPRINT_TOL
-from test_gpu_project_points import TOL as PROJECT_TOL
-from test_ref_corridor import footprint_near
+from project_util import PROJECT_TOL
+from shared_util import capi_geom
 
 pytestmark = pytest.mark.gpu
 
@@ -40,10 +40,6 @@ def cs():
     c = RC.cases()
     c["tables"] = {k: K.pack_spline(sx, sy) for k, (sx, sy) in c["splines"].items()}      # (the restated fit is the reference's bit for bit)
     return c
-
-
-def _geom(g):
-    return capi.PqpGridGeometry(g.rows, g.cols, g.resolution, g.length_x, g.length_y, g.pos_x, g.pos_y)
 
 
 def _corridor_prm(handle, car):
@@ -104,7 +100,7 @@ def test_corridor_bounds(handle, ref, cs, name):
     tab, ext = cs["tables"][ln]
     dist, g = cs["layers"][layer]
     states = ref[f"corridor_{name}_states"]
-    got, nv = handle.corridor_bounds(states[None], tab[None], ext[None], dist, _geom(g), prm=_corridor_prm(handle, car))
+    got, nv = handle.corridor_bounds(states[None], tab[None], ext[None], dist, capi_geom(g), prm=_corridor_prm(handle, car))
     _compare(got[0], int(nv[0]), ref[f"corridor_{name}_bounds"], ref[f"corridor_{name}_blocked_row"])
 
 
@@ -115,7 +111,7 @@ def test_corridor_bounds_on_states(handle, ref, cs, name):
     dist, g = cs["layers"][layer]
     states, dpsi = ref[f"corridor_{name}_states"], ref[f"corridor_{name}_d_heading"]
     st = np.zeros((1, len(states), 5)); st[0, :len(dpsi), 4] = dpsi
-    got, nv = handle.corridor_bounds_on_states(states[None], st, tab[None], ext[None], dist, _geom(g), prm=_corridor_prm(handle, car), n_of=[len(dpsi)])
+    got, nv = handle.corridor_bounds_on_states(states[None], st, tab[None], ext[None], dist, capi_geom(g), prm=_corridor_prm(handle, car), n_of=[len(dpsi)])
     _compare(got[0], int(nv[0]), ref[f"corridor_{name}_on_states_bounds"], ref[f"corridor_{name}_on_states_blocked_row"])
 
 
@@ -149,7 +145,7 @@ def test_clearance_lookup(handle, ref, cs, layer):
     out = torch.full((1, len(pts)), -7.0, dtype=torch.float64, device=dev)
     torch.cuda.synchronize()
     p = lambda a: capi.C.c_void_p(a.data_ptr())
-    geom = _geom(g)
+    geom = capi_geom(g)
     assert handle.lib.pqp_clearance_device(handle._h, 1, len(pts), p(d_x), p(d_y), p(d_dist), p(d_map), capi.C.byref(geom), p(out)) == 0
     handle.sync()
     got = out.cpu().numpy()[0]
@@ -167,9 +163,9 @@ def test_footprint_check(handle, ref, cs, name, mode):
     circles = capi.car_circles(car)
     assert np.array_equal(circles[:, 2], ref[f"footprint_{name}_radius"])
     st = ref[f"footprint_{name}_state"]
-    got = handle.footprint_check(st[None], None, np.asarray(dist), _geom(g), car=car, mode=mode, margin=True)
+    got = handle.footprint_check(st[None], None, np.asarray(dist), capi_geom(g), car=car, mode=mode, margin=True)
     want = ref[f"footprint_{name}_free_circles" if mode == capi.FOOTPRINT_CIRCLES else f"footprint_{name}_free_bounding"]
-    near = footprint_near(ref, name)
+    near = RC.footprint_near(ref, name)
     mism = (got["free"][0] != want) & ~near
     assert not mism.any(), np.flatnonzero(mism)[:10]
     d = ref[f"footprint_{name}_distance"].astype(np.float64)[:, :6]

@@ -14,9 +14,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import chain_util
+import cpp_demo
 import sample_util as S
 import speed_util as V
 from path_optimizer_2_amd import capi
+from shared_util import same_bits
 
 pytestmark = pytest.mark.gpu
 COUNTS = (0, 1, 2, 3, 63, 64, 65, 128, 129, 200, 700)
@@ -72,7 +75,7 @@ def _check(got, a, m, dt, hold_last=0):
     assert traj.shape == (len(a["paths"]), m, 8)
     for b in range(len(a["paths"])):
         assert flags[b] == want[2][b] and m_of[b] == want[1][b], (b, flags[b], want[2][b], m_of[b], want[1][b])
-        if not S.same_bits(traj[b], want[0][b]):
+        if not same_bits(traj[b], want[0][b]):
             diff = np.argwhere(traj[b].view(np.uint64) != want[0][b].view(np.uint64))
             k, col = diff[0]
             raise AssertionError(f"path {b}: {len(diff)} cells differ, first at sample {k} column {col}: {traj[b, k, col]!r} != {want[0][b, k, col]!r}")
@@ -148,16 +151,16 @@ def test_sample_tiles_that_start_on_a_waypoint_tile_edge(handle):
     a = dict(paths=p[None], profile=o[None], n_of=None, stop_before=None, t0=None)
     traj, m_of, flags = _run(handle, a, 130, 0.25)           # sample k = waypoint k: sample 64 opens the second tile on waypoint 64
     _check((traj, m_of, flags), a, 130, 0.25)
-    assert m_of[0] == 130 and flags[0] == S.HORIZON_SHORT and S.same_bits(traj[0], rows[:130])
+    assert m_of[0] == 130 and flags[0] == S.HORIZON_SHORT and same_bits(traj[0], rows[:130])
     traj, m_of, flags = _run(handle, a, 130, 0.5)            # sample k = waypoint 2 k: sample 64 on waypoint 128, sample 99 on the last
     _check((traj, m_of, flags), a, 130, 0.5)
-    assert m_of[0] == 100 and flags[0] == S.ENDS_MOVING and S.same_bits(traj[0, :100], rows[::2]) and (traj[0, 100:] == 0).all()
+    assert m_of[0] == 100 and flags[0] == S.ENDS_MOVING and same_bits(traj[0, :100], rows[::2]) and (traj[0, 100:] == 0).all()
     for t0 in (16.0, 15.75, 32.0, 49.75):                    # sample 0 itself on waypoints 64, 63, 128 and the last
         a["t0"] = np.array([t0])
         traj, m_of, flags = _run(handle, a, 66, 0.25)
         _check((traj, m_of, flags), a, 66, 0.25)
         k = int(t0 * 4)
-        assert m_of[0] == min(66, n - k) and S.same_bits(traj[0, :m_of[0]], rows[k:k + 66])
+        assert m_of[0] == min(66, n - k) and same_bits(traj[0, :m_of[0]], rows[k:k + 66])
 
 
 # ---- t0, the arrival, the t column ----------------------------------------------------------------------------------------------------
@@ -170,7 +173,7 @@ def test_t0_absent_zero_positive_and_behind_the_arrival(handle):
     zero = _run(handle, a, 70, 0.1)
     _check(zero, a, 70, 0.1)
     absent = _run(handle, dict(a, t0=None), 70, 0.1)
-    assert all(S.same_bits(x, y) for x, y in zip(zero, absent))
+    assert all(same_bits(x, y) for x, y in zip(zero, absent))
     arrive = np.array([a["profile"][b, :c, 3].max() for b, c in enumerate((130, 64, 3, 131))])
     a["t0"] = np.array([0.4, 2.0, arrive[2] + 1.0, np.nextafter(arrive[3], math.inf)])
     got = _run(handle, a, 70, 0.1, 1)
@@ -283,14 +286,14 @@ def test_values_that_are_not_numbers_stay_in_their_path(handle):
         if b in hostile:
             assert got[2][b] == S.NOT_FINITE and got[1][b] == 0 and np.isnan(got[0][b]).all(), b
         else:
-            assert got[2][b] == want[2][b] and got[1][b] == want[1][b] and S.same_bits(got[0][b], want[0][b]), b
+            assert got[2][b] == want[2][b] and got[1][b] == want[1][b] and same_bits(got[0][b], want[0][b]), b
     # a launch without the hostile paths: the neighbours' bits are the same
     keep = [b for b in range(13) if b not in hostile]
     alone = _run(handle, {k: v[keep] for k, v in clean.items()}, m, dt)
-    assert S.same_bits(alone[0], got[0][keep]) and np.array_equal(alone[1], got[1][keep]) and np.array_equal(alone[2], got[2][keep])
+    assert same_bits(alone[0], got[0][keep]) and np.array_equal(alone[1], got[1][keep]) and np.array_equal(alone[2], got[2][keep])
     inf_t0 = dict(clean, t0=np.where(np.arange(13) == 4, math.inf, clean["t0"]))
     got = _run(handle, inf_t0, m, dt)
-    assert got[2][4] == S.NOT_FINITE and S.same_bits(got[0][keep[1:]], want[0][keep[1:]])
+    assert got[2][4] == S.NOT_FINITE and same_bits(got[0][keep[1:]], want[0][keep[1:]])
     # what is not read does no harm: behind the driven range
     bad = {k: v.copy() for k, v in clean.items()}
     bad["stop_before"][:] = 60
@@ -336,16 +339,16 @@ def test_same_bits_in_any_batch_for_any_n_and_m_and_from_either_form(handle):
             lst[at] = src[0]
         a = case.arrays()
         got = _run(handle, a, m, dt)
-        assert got[2][at] == first[2][0] and got[1][at] == first[1][0] and S.same_bits(got[0][at], first[0][0]), (B, at)
+        assert got[2][at] == first[2][0] and got[1][at] == first[1][0] and same_bits(got[0][at], first[0][0]), (B, at)
         dev = _device_form(handle, a, m, dt)                 # outputs that held -7: fully overwritten
-        assert S.same_bits(dev[0], got[0]) and np.array_equal(dev[1], got[1]) and np.array_equal(dev[2], got[2]), (B, at)
+        assert same_bits(dev[0], got[0]) and np.array_equal(dev[1], got[1]) and np.array_equal(dev[2], got[2]), (B, at)
     # n is no part of a sample: the same path in a shorter row; nor is m: a longer horizon shares the prefix
     short = dict(alone, paths=alone["paths"][:, :195], profile=alone["profile"][:, :195])
     got = _run(handle, short, m, dt)
-    assert S.same_bits(got[0], first[0]) and got[1][0] == first[1][0]
+    assert same_bits(got[0], first[0]) and got[1][0] == first[1][0]
     for m2 in (131, 300):
         got = _run(handle, alone, m2, dt)
-        assert S.same_bits(got[0][:, :m], first[0]) and got[1][0] >= first[1][0]
+        assert same_bits(got[0][:, :m], first[0]) and got[1][0] >= first[1][0]
 
 
 # ---- what is refused -------------------------------------------------------------------------------------------------------------------
@@ -428,7 +431,7 @@ def test_a_path_solve_s_out_sampled_in_place(hip_lib):
     got = traj.cpu().numpy(), m_of.cpu().numpy(), flags.cpu().numpy()
     copy = h.sample_trajectory(paths.copy(), profile.copy(), m)
     h.close()
-    assert S.same_bits(got[0], copy[0]) and np.array_equal(got[1], copy[1]) and np.array_equal(got[2], copy[2])
+    assert same_bits(got[0], copy[0]) and np.array_equal(got[1], copy[1]) and np.array_equal(got[2], copy[2])
     _check(got, dict(paths=paths, profile=profile, n_of=None, stop_before=None, t0=None), m, 0.1)
     assert (got[1] > 0).all() and (got[0][:, 1, 4] >= 0).all()
 
@@ -436,10 +439,8 @@ def test_a_path_solve_s_out_sampled_in_place(hip_lib):
 def test_samples_behind_the_chain(hip_lib):
     """optimize_path(check_footprint=True, speed=..., sample=...) = the chain, pqp_footprint_check, pqp_speed_profile and
     pqp_sample_trajectory one after the other; with select the winners' rows of best_paths are what is sampled"""
-    import test_gpu_chain as T
-    import test_gpu_select_paths as TS
     B, m = 16, 40
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     gs = np.array([0, 8, 16], np.int32)
     sp, sa = capi.speed_default_params(v_max=8.0), capi.sample_default_params(dt=0.2, hold_last=1)
     vs_all, vs_grp = np.linspace(0.0, 6.0, B), np.array([2.0, 5.0])
@@ -449,18 +450,18 @@ def test_samples_behind_the_chain(hip_lib):
                      ("all", dict(speed=sp, v_start=vs_all, sample=sa, samples=m, t0=t0_all)),
                      ("select", dict(select=gs, speed=sp, v_start=vs_grp, sample=sa, samples=m)),
                      ("winners", dict(select=gs, winners_only=True, speed=sp, v_start=vs_grp, sample=sa, samples=m, t0=t0_grp))):
-        h, hs = TS._chain_handles(B)
+        h, hs = chain_util.handles(B)
         runs[name] = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs,
                                      check_footprint=True, **kw)
         h.close(); hs.close()
     before, every, sel, win = runs["speed"], runs["all"], runs["select"], runs["winners"]
     assert list(every) == list(before) + ["traj", "traj_n", "traj_flags"]
     for k in before:                                         # sample=None: as before; with it: the same paths and profiles
-        assert S.same_bits(before[k], every[k]) if before[k].dtype == np.float64 else np.array_equal(before[k], every[k]), k
+        assert same_bits(before[k], every[k]) if before[k].dtype == np.float64 else np.array_equal(before[k], every[k]), k
     assert every["traj"].shape == (B, m, 8) and every["traj_n"].shape == (B,) and every["traj_flags"].shape == (B,)
     h = capi.Handle(capi.default_params(), max_batch=8, max_n=16)
     want = h.sample_trajectory(every["out"], every["profile"], m, n_of=every["n_out"], stop_before=every["first_collision"], t0=t0_all, prm=sa)
-    assert S.same_bits(every["traj"], want[0]) and np.array_equal(every["traj_n"], want[1]) and np.array_equal(every["traj_flags"], want[2])
+    assert same_bits(every["traj"], want[0]) and np.array_equal(every["traj_n"], want[1]) and np.array_equal(every["traj_flags"], want[2])
     a = dict(paths=every["out"], profile=every["profile"], n_of=every["n_out"], stop_before=every["first_collision"], t0=t0_all)
     _check((every["traj"], every["traj_n"], every["traj_flags"]), a, m, 0.2, 1)
     assert (every["traj_flags"] & S.NOT_FINITE == 0).all() and (every["traj_n"] > 0).any()
@@ -470,17 +471,16 @@ def test_samples_behind_the_chain(hip_lib):
     assert "out" in sel and sel["traj"].shape == (2, m, 8) == win["traj"].shape and (win["best"] >= 0).any()
     for res, t0 in ((sel, None), (win, t0_grp)):
         want = h.sample_trajectory(res["best_paths"], res["profile"], m, n_of=res["best_n"], t0=t0, prm=sa)
-        assert S.same_bits(res["traj"], want[0]) and np.array_equal(res["traj_n"], want[1]) and np.array_equal(res["traj_flags"], want[2])
+        assert same_bits(res["traj"], want[0]) and np.array_equal(res["traj_n"], want[1]) and np.array_equal(res["traj_flags"], want[2])
         for g in range(2):
             assert (res["traj_flags"][g] == S.EMPTY) == (res["best"][g] < 0)
     h.close()
-    assert S.same_bits(sel["best_paths"], win["best_paths"]) and S.same_bits(sel["profile"], win["profile"])
+    assert same_bits(sel["best_paths"], win["best_paths"]) and same_bits(sel["profile"], win["profile"])
 
 
 # ---- C++ -------------------------------------------------------------------------------------------------------------------------------
 def test_sampler_agrees_with_the_python_call(handle, tmp_path):
-    import test_sample_trajectory as T
-    exe = T.build_demo()
+    exe = cpp_demo.build("sample_demo")
     rng = np.random.default_rng(2001)
     counts = [30, 1, 64, 65, 0, 130]
     stops = [30, 1, 40, 65, 0, 129]
@@ -493,7 +493,7 @@ def test_sampler_agrees_with_the_python_call(handle, tmp_path):
             prof[b, :c] = S.seeded_profile(rng, paths[b, :c])
     for hold in (0, 1):
         path = tmp_path / f"paths{hold}.bin"
-        T.write_case(path, paths, prof, m, counts, stops, t0, dt, hold)
+        S.write_case(path, paths, prof, m, counts, stops, t0, dt, hold)
         r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stderr
         want = handle.sample_trajectory(paths, prof, m, n_of=counts, stop_before=stops, t0=t0, prm=_cprm(dt, hold))
@@ -503,5 +503,5 @@ def test_sampler_agrees_with_the_python_call(handle, tmp_path):
             rows_want = 0 if c == 0 else (m if hold else int(want[1][b]))
             assert head[0] == "path" and int(head[1]) == b and int(head[2]) == want[2][b] and int(head[3]) == rows_want, (b, head)
             rows = np.array([[float(v) for v in next(lines).split()] for _ in range(rows_want)]).reshape(rows_want, 8)
-            assert S.same_bits(rows, want[0][b, :rows_want]), b
+            assert same_bits(rows, want[0][b, :rows_want]), b
         assert next(lines, None) is None

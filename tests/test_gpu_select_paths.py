@@ -19,8 +19,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import chain_util
+import cpp_demo
 import select_util as S
 from path_optimizer_2_amd import capi
+from shared_util import same_bytes
 
 pytestmark = pytest.mark.gpu
 COUNTS = [0, 1, 2, 63, 64, 65, 80, 500, 2000]
@@ -64,10 +67,6 @@ def _random_groups(rng, B, groups):
     return np.concatenate([[0], cuts, [B]]).astype(np.int32)
 
 
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
-
-
 def _check(got, case, group_start, prm):
     """everything section by section: terms against the restatement, winners against the device's own scores and against the restatement's,
     the winners' rows"""
@@ -93,7 +92,7 @@ def _check(got, case, group_start, prm):
         w, m = best[g], ref[g]             # two scores, each within its own bound of the device's: the sum is the tight consequence
         assert want[w, 7] == 1.0 and want[w, 0] <= want[m, 0] + bound[w, 0] + bound[m, 0], (g, w, m)
     bp, bn = S.best_rows(case["paths"], case.get("n_of"), best)
-    assert np.array_equal(got["best_n"], bn) and _same_bits(got["best_paths"], bp)
+    assert np.array_equal(got["best_n"], bn) and same_bytes(got["best_paths"], bp)
     return want
 
 
@@ -156,10 +155,10 @@ def test_who_can_win(handle):
     got = handle.select_paths(paths, gs, n_of, status, stage, first)
     assert got["best"].tolist() == [1, 5, 12, -1, -1]
     assert got["terms"][:, 7].tolist() == [1, 1, 1, 1,  0, 1, 1,  0, 0, 0, 0, 0, 1,  0, 0]
-    assert _same_bits(got["terms"][1], got["terms"][2]) and (got["terms"][9] == 0).all()
+    assert same_bytes(got["terms"][1], got["terms"][2]) and (got["terms"][9] == 0).all()
     assert math.isnan(got["terms"][10, 0]) and not math.isfinite(got["terms"][11, 0])
     assert got["best_n"].tolist() == [n, n, n, 0, 0] and (got["best_paths"][3:] == 0).all()
-    assert _same_bits(got["best_paths"][2], mid)
+    assert same_bytes(got["best_paths"][2], mid)
     _check(got, dict(paths=paths, n_of=n_of, status=status, stage=stage, first_collision=first), gs, S.Params())
     # require_free = 0: the colliding candidates may win (14 collides and is solved; 13 is not solved)
     free_or_not = handle.select_paths(paths, gs, n_of, status, stage, first, prm=capi.select_default_params(require_free=0))
@@ -183,7 +182,7 @@ def test_one_group_of_65536_and_a_group_per_candidate(handle):
     assert np.array_equal(got["best"], np.where(got["terms"][:, 7] == 1.0, np.arange(B), -1))
     assert np.array_equal(got["best_n"], np.where(got["best"] >= 0, counts, 0))
     bp, _ = S.best_rows(case["paths"], counts, got["best"])
-    assert _same_bits(got["best_paths"], bp)
+    assert same_bytes(got["best_paths"], bp)
 
 
 # ---- reproducible, and a candidate's terms are its own ---------------------------------------------------------------------------------
@@ -198,16 +197,16 @@ def test_same_bits_every_run_and_in_any_batch(handle):
     args = (case["paths"], gs, case["n_of"], case["status"], case["stage"], case["first_collision"], case["margin"])
     a, b = handle.select_paths(*args, prm=prm), handle.select_paths(*args, prm=prm)
     for k in a:
-        assert _same_bits(a[k], b[k]), k
+        assert same_bytes(a[k], b[k]), k
     for at in (5, 4097, 8191, 77):
         one = handle.select_paths(case["paths"][at:at + 1], [0, 1], *(case[k][at:at + 1] for k in ("n_of", "status", "stage", "first_collision", "margin")),
                                   prm=prm)
-        assert _same_bits(one["terms"][0], a["terms"][at]), at
+        assert same_bytes(one["terms"][0], a["terms"][at]), at
         # and alone in a shorter row: n is no part of the sums
         c = int(counts[at])
         one = handle.select_paths(case["paths"][at:at + 1, :c], [0, 1], *(case[k][at:at + 1] for k in ("n_of", "status", "stage", "first_collision")),
                                   margin=case["margin"][at:at + 1, :c], prm=prm)
-        assert _same_bits(one["terms"][0], a["terms"][at]), at
+        assert same_bytes(one["terms"][0], a["terms"][at]), at
 
 
 # ---- the device form and a group_start nobody checked ----------------------------------------------------------------------------------
@@ -278,11 +277,6 @@ def test_host_form_refuses_and_leaves_the_outputs_alone(handle):
 
 
 # ---- behind the device chain -----------------------------------------------------------------------------------------------------------
-def _chain_handles(B):
-    import test_gpu_chain as T
-    return capi.Handle(capi.production_params(), max_batch=B, max_n=256), capi.Handle(T._smoother_params(), max_batch=B, max_n=128)
-
-
 def _restated(res, gs, prm=None):
     return S.select(res["out"], gs, res["n_out"], res["status"], res["stage"], res.get("first_collision"), res.get("margin"), prm)
 
@@ -290,15 +284,14 @@ def _restated(res, gs, prm=None):
 @pytest.mark.parametrize("on_grid", [False, True])
 def test_select_behind_the_chain(hip_lib, on_grid):
     import distance_util as D
-    import test_gpu_chain as T
     B = 24 if not on_grid else 16
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     gs = np.arange(0, B + 1, 8, dtype=np.int32)
     layers = np.stack([D.occupancy_of(d) for d in sc["dist"]]) if on_grid else sc["dist"]
     runs = {}
     for name, kw in (("plain", dict()), ("select", dict(select=gs)), ("winners", dict(select=gs, winners_only=True)),
                      ("no_check", dict(select=gs, check_footprint=False))):
-        h, hs = _chain_handles(B)                            # fresh handles for each: nothing carried from one call to the other
+        h, hs = chain_util.handles(B)                            # fresh handles for each: nothing carried from one call to the other
         run = h.optimize_path_on_grid if on_grid else h.optimize_path
         runs[name] = run(sc["pts"], sc["n_pts"], sc["start"], sc["target"], layers, sc["geom"], map_of=sc["map_of"], smoother=hs,
                          **{"check_footprint": True, **kw})
@@ -307,16 +300,16 @@ def test_select_behind_the_chain(hip_lib, on_grid):
     assert list(plain) == ["out", "n_out", "status", "stage", "iters", "free", "first_collision", "margin"]        # select=None: as before
     assert list(sel) == list(plain) + ["terms", "best", "best_paths", "best_n"]
     for k in plain:
-        assert _same_bits(plain[k], sel[k]), k
+        assert same_bytes(plain[k], sel[k]), k
     want = _restated(sel, gs)
     assert np.array_equal(sel["best"], want["best"]) and (sel["best"] >= 0).any()
-    assert np.array_equal(sel["best_n"], want["best_n"]) and _same_bits(sel["best_paths"], want["best_paths"])
+    assert np.array_equal(sel["best_n"], want["best_n"]) and same_bytes(sel["best_paths"], want["best_paths"])
     _check(sel, dict(paths=sel["out"], n_of=sel["n_out"], status=sel["status"], stage=sel["stage"], first_collision=sel["first_collision"],
                      margin=sel["margin"]), gs, S.Params())
     # winners only: the same answer, and neither the paths nor the per-waypoint arrays
     assert sorted(win) == sorted(["n_out", "status", "stage", "iters", "first_collision", "terms", "best", "best_paths", "best_n"])
     for k in ("best", "best_paths", "best_n", "terms", "n_out", "status", "stage", "first_collision"):
-        assert _same_bits(win[k], sel[k]), k
+        assert same_bytes(win[k], sel[k]), k
     # without the footprint check the selection reads neither first_collision nor margin
     assert "first_collision" not in no_check and np.array_equal(no_check["best"], _restated(no_check, gs)["best"])
     assert (no_check["terms"][:, 5:7] == 0).all()
@@ -333,8 +326,7 @@ def test_selection_arguments_without_select_are_refused(hip_lib):
 
 # ---- C++ -------------------------------------------------------------------------------------------------------------------------------
 def test_selector_agrees_with_the_python_call(handle, tmp_path):
-    import test_select_paths as T
-    exe = T.build_demo()
+    exe = cpp_demo.build("select_demo")
     rng = np.random.default_rng(71)
     counts = [30, 1, 12, 64, 65, 0, 5, 5, 90]
     n = max(counts)
@@ -342,7 +334,7 @@ def test_selector_agrees_with_the_python_call(handle, tmp_path):
     paths[7] = paths[6]                                      # a tie
     gs = [0, 3, 3, 6, 9]
     path = tmp_path / "candidates.bin"
-    T.write_candidates(path, [paths[b, :c] for b, c in enumerate(counts)], gs)
+    S.write_candidates(path, [paths[b, :c] for b, c in enumerate(counts)], gs)
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     lines = r.stdout.strip().splitlines()

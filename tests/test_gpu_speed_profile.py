@@ -16,8 +16,11 @@ import subprocess
 import numpy as np
 import pytest
 
+import chain_util
+import cpp_demo
 import speed_util as V
 from path_optimizer_2_amd import capi
+from shared_util import same_bytes
 
 pytestmark = pytest.mark.gpu
 COUNTS = (0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 200, 700)
@@ -34,10 +37,6 @@ def handle(hip_lib):
 
 def _cprm(prm=None):
     return capi.speed_default_params(**dict(V.DEFAULTS, **(prm or {})))
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 def _safe_v_start(path, want, **kw):
@@ -238,7 +237,7 @@ def test_values_that_are_not_numbers_stay_in_their_path(handle):
         if b in (1, 4, 7):
             assert got[1][b] == V.NOT_FINITE and np.isnan(got[0][b, :c]).all() and (got[0][b, c:] == 0).all(), b
         else:
-            assert got[1][b] == want[1][b] and _same_bits(got[0][b], want[0][b]), b
+            assert got[1][b] == want[1][b] and same_bytes(got[0][b], want[0][b]), b
     _check(got, bad, case.prm)
     # what is not read does no harm: behind the driven range, and a v_end of a path that stops early
     bad = {k: (None if v is None else v.copy()) for k, v in clean.items()}
@@ -286,16 +285,16 @@ def test_same_bits_in_any_batch_and_from_either_form(handle):
             lst[at] = src[0]
         a = case.arrays()
         got = _run(handle, a, case.prm)
-        assert got[1][at] == first[1][0] and _same_bits(got[0][at], first[0][0]), (B, at)
+        assert got[1][at] == first[1][0] and same_bytes(got[0][at], first[0][0]), (B, at)
         dev = _device_form(handle, a, case.prm)                      # outputs that held -7: fully overwritten
-        assert _same_bits(dev[0], got[0]) and np.array_equal(dev[1], got[1]), (B, at)
+        assert same_bytes(dev[0], got[0]) and np.array_equal(dev[1], got[1]), (B, at)
         again = _run(handle, a, case.prm)
-        assert _same_bits(again[0], got[0])
+        assert same_bytes(again[0], got[0])
     # n is no part of the sums: the same path in a shorter row
     short = {k: (None if v is None else v.copy()) for k, v in alone.items()}
     short["paths"], short["v_limit"] = alone["paths"][:, :200], alone["v_limit"][:, :200]
     got = _run(handle, short, one.prm)
-    assert _same_bits(got[0][0], first[0][0, :200]) and (first[0][0, 190:] == 0).all()
+    assert same_bytes(got[0][0], first[0][0, :200]) and (first[0][0, 190:] == 0).all()
 
 
 # ---- what is refused -------------------------------------------------------------------------------------------------------------------
@@ -371,7 +370,7 @@ def test_a_path_solve_s_out_profiled_in_place(hip_lib):
     got = prof.cpu().numpy(), flags.cpu().numpy()
     copy = h.speed_profile(paths.copy(), v_start)
     h.close()
-    assert _same_bits(got[0], copy[0]) and np.array_equal(got[1], copy[1])
+    assert same_bytes(got[0], copy[0]) and np.array_equal(got[1], copy[1])
     a = dict(paths=paths, n_of=None, stop_before=None, v_limit=None, v_start=v_start, v_end=None)
     _check(got, a, V.DEFAULTS)
     assert (got[0][:, -1, 0] > 0).all() and (got[0][:, -1, 3] > 0).all()         # paths of some length, and time passes
@@ -380,10 +379,8 @@ def test_a_path_solve_s_out_profiled_in_place(hip_lib):
 def test_speed_behind_the_chain(hip_lib):
     """optimize_path(check_footprint=True, speed=...) = the chain, pqp_footprint_check and pqp_speed_profile one after the other; with select
     the winners' rows of best_paths are what is profiled"""
-    import test_gpu_chain as T
-    import test_gpu_select_paths as TS
     B = 16
-    sc = T._scenarios(B)
+    sc = chain_util.scenarios(B)
     gs = np.array([0, 8, 16], np.int32)
     sp = capi.speed_default_params(v_max=8.0)
     vs_all, ve_all = np.linspace(0.0, 6.0, B), np.where(np.arange(B) % 2 == 0, 0.0, math.nan)
@@ -391,20 +388,20 @@ def test_speed_behind_the_chain(hip_lib):
     runs = {}
     for name, kw in (("plain", dict()), ("all", dict(speed=sp, v_start=vs_all, v_end=ve_all)),
                      ("winners", dict(select=gs, winners_only=True, speed=sp, v_start=vs_grp, v_end=ve_grp))):
-        h, hs = TS._chain_handles(B)
+        h, hs = chain_util.handles(B)
         runs[name] = h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], map_of=sc["map_of"], smoother=hs,
                                      check_footprint=True, **kw)
         h.close(); hs.close()
     plain, every, win = runs["plain"], runs["all"], runs["winners"]
     assert list(every) == list(plain) + ["profile", "speed_flags"]
     for k in plain:                                          # speed=None: as before; with it: the same paths
-        assert _same_bits(plain[k], every[k]), k
+        assert same_bytes(plain[k], every[k]), k
     assert every["profile"].shape == every["out"].shape[:2] + (4,) and every["speed_flags"].shape == (B,)
     h = capi.Handle(capi.default_params(), max_batch=8, max_n=16)
     fp = h.footprint_check(every["out"], every["n_out"], sc["dist"], sc["geom"], map_of=sc["map_of"])
     assert np.array_equal(fp["first_collision"], every["first_collision"])
     want = h.speed_profile(every["out"], vs_all, n_of=every["n_out"], stop_before=fp["first_collision"], v_end=ve_all, prm=sp)
-    assert _same_bits(every["profile"], want[0]) and np.array_equal(every["speed_flags"], want[1])
+    assert same_bytes(every["profile"], want[0]) and np.array_equal(every["speed_flags"], want[1])
     a = dict(paths=every["out"], n_of=every["n_out"], stop_before=every["first_collision"], v_limit=None, v_start=vs_all, v_end=ve_all)
     _check((every["profile"], every["speed_flags"]), a, dict(V.DEFAULTS, v_max=8.0))
     assert (every["speed_flags"] & V.NOT_FINITE == 0).all() and (every["profile"][:, :, 0].max(axis=1) > 0).any()
@@ -415,17 +412,16 @@ def test_speed_behind_the_chain(hip_lib):
     assert win["profile"].shape == (2,) + every["out"].shape[1:2] + (4,) and (win["best"] >= 0).any()
     want = h.speed_profile(win["best_paths"], vs_grp, n_of=win["best_n"], v_end=ve_grp, prm=sp)
     h.close()
-    assert _same_bits(win["profile"], want[0]) and np.array_equal(win["speed_flags"], want[1])
+    assert same_bytes(win["profile"], want[0]) and np.array_equal(win["speed_flags"], want[1])
     for g in range(2):
         assert (win["speed_flags"][g] == V.EMPTY) == (win["best"][g] < 0)
         if win["best"][g] >= 0:                              # an eligible winner is collision-free: its whole path is driven
-            assert _same_bits(win["best_paths"][g], every["out"][win["best"][g]]) and win["speed_flags"][g] & V.STOPS_EARLY == 0
+            assert same_bytes(win["best_paths"][g], every["out"][win["best"][g]]) and win["speed_flags"][g] & V.STOPS_EARLY == 0
 
 
 # ---- C++ -------------------------------------------------------------------------------------------------------------------------------
 def test_profiler_agrees_with_the_python_call(handle, tmp_path):
-    import test_speed_profile as T
-    exe = T.build_demo()
+    exe = cpp_demo.build("speed_demo")
     rng = np.random.default_rng(701)
     counts = [30, 1, 64, 65, 0, 130]
     stops = [30, 1, 40, 65, 0, 129]
@@ -436,7 +432,7 @@ def test_profiler_agrees_with_the_python_call(handle, tmp_path):
             paths[b, :c] = V.seeded_path(rng, c)
     v_start, v_end = rng.uniform(0.0, 5.0, len(counts)), np.array([math.nan, 0.5, math.nan, 0.0, 1.0, math.nan])
     path = tmp_path / "paths.bin"
-    T.write_case(path, paths, counts, stops, v_start, v_end)
+    V.write_case(path, paths, counts, stops, v_start, v_end)
     r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     want = handle.speed_profile(paths, v_start, n_of=counts, stop_before=stops, v_end=v_end)
@@ -446,6 +442,6 @@ def test_profiler_agrees_with_the_python_call(handle, tmp_path):
         assert head[0] == "path" and int(head[1]) == b and int(head[2]) == want[1][b]
         rows = np.array([[float(v) for v in next(lines).split()] for _ in range(c)]).reshape(c, 4)
         driven = min(c, stops[b])
-        assert _same_bits(rows[:driven], want[0][b, :driven]), b
+        assert same_bytes(rows[:driven], want[0][b, :driven]), b
         assert (rows[driven:] == 0.0).all()                  # states behind the stop keep the zeros they came with
     assert next(lines, None) is None

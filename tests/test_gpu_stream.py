@@ -347,7 +347,8 @@ def test_long_paths_whose_active_set_rounds_cycle(hip_lib):
     them) end at the optimum - SOLVED, and the returned path passes the KKT conditions of the assembled QP of the last pass."""
     from path_optimizer_2_amd import capi
     from path_optimizer_2_amd.synth import make_batch
-    from test_lq_emulation import CYCLING, kkt_certificate_of_the_last_pass
+    from kkt_util import kkt_certificate_of_the_last_pass
+    from lq_emu_util import CYCLING
     for n, profile, seed, qp in CYCLING:
         kw = {} if seed is None else {"seed": seed}
         # the QP among 63 neighbours: one wavefront, its other lanes on QPs of ordinary cost

@@ -2,39 +2,14 @@
 (__graft_entry__.build_hip -> csrc/libpqp_hip.resources.txt).  The solve kernels keep 86 doubles of lane state in registers;
 LLVM gives that up silently for innocent-looking source changes, and the kernel then runs several times
 slower while every parity test still passes.  This test is the tripwire."""
-import os
-import re
-
 import pytest
 
-import __graft_entry__ as g
-
-
-def _report():
-    g.build_hip()
-    if not os.path.exists(g.RESOURCES):
-        g.build_hip(force=True)
-    kernels, cur = {}, None
-    for line in open(g.RESOURCES):
-        m = re.search(r"remark: Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[\w/]+\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    return kernels
+from build_util import find_kernel as _find, kernel_report as _report
 
 
 @pytest.fixture(scope="module")
 def kernels():
     return _report()
-
-
-def _find(kernels, *parts):
-    hits = [(k, v) for k, v in kernels.items() if all(p in k for p in parts)]
-    assert len(hits) == 1, (parts, [k for k, _ in hits])
-    return hits[0][1]
 
 
 @pytest.mark.parametrize("nw", [1, 2, 4])

@@ -24,8 +24,8 @@ LONG_KERNELS = {"long_fit_kernel": 0, "long_ref_states_kernel": 4, "long_ref_len
 
 @pytest.fixture(scope="module")
 def kernels():
-    from test_kernel_resources import _report
-    return _report()
+    from build_util import kernel_report
+    return kernel_report()
 
 
 @pytest.mark.parametrize("name", sorted(LONG_KERNELS))

@@ -8,13 +8,13 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_demo
 from path_optimizer_2_amd import capi
 from path_optimizer_2_amd.shard import shard_range
 from path_optimizer_2_amd.synth import make_batch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "batched_demo")
 
 
 def test_shard_range_is_the_contiguous_split_of_the_python_side(hip_lib):
@@ -39,9 +39,7 @@ def test_multi_create_fails_loudly_without_a_device(hip_lib):
 
 @pytest.fixture(scope="module")
 def batched_exe(hip_lib):
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", EXE, os.path.join(ROOT, "tests", "cpp", "batched_demo.cpp"), "-L" + CSRC, "-lpqp_hip",
-                    "-Wl,-rpath," + CSRC], check=True)
-    return EXE
+    return cpp_demo.build("batched_demo", hip=False)
 
 
 def _scenarios_text(b, counts):

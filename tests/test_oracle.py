@@ -8,6 +8,7 @@ import pytest
 import scipy.sparse as sp
 
 import pqp_oracle as O
+from kkt_util import direct_active_set_solve
 from path_optimizer_2_amd.synth import make_batch
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -140,31 +141,6 @@ def test_golden_fixtures(name):
         np.testing.assert_allclose(up, g["upper"][q], rtol=1e-13, atol=1e-15)
         cert = O.kkt_certificate(sp.diags(Pd), np.zeros(sz["vars"]), A, lo, up, g["x_star"][q], g["y_star"][q])
         assert cert["pri"] < 1e-7 and cert["stat"] < 1e-7 and cert["comp"] < 1e-7
-
-
-def direct_active_set_solve(Pd, A, lo, up, x_hint, y_hint, tol=1e-7):
-    """A solver-free answer for a path QP: identify the active set from a (converged) primal-dual pair, then solve the
-    equality-constrained QP on that set DIRECTLY - one sparse LU of the KKT matrix [[P, A_act'], [A_act, 0]] (scipy splu), no ADMM,
-    no iteration - and check that the point it gives is the optimum: inactive rows strictly inside their boxes, multipliers of the
-    active rows correctly signed.  Returns (x, y, worst_kkt_violation)."""
-    import scipy.sparse.linalg as spla
-    ax = A @ x_hint
-    at_lo = (np.abs(ax - lo) <= tol * (1 + np.abs(lo))) & (lo > -1e19)
-    at_up = (np.abs(ax - up) <= tol * (1 + np.abs(up))) & (up < 1e19)
-    eq = (up - lo) <= 1e-12
-    act = eq | (at_lo & (y_hint < -1e-9)) | (at_up & (y_hint > 1e-9))
-    b = np.where(eq | (at_lo & ~at_up), lo, up)[act]
-    Aa = sp.csr_matrix(A[act])
-    nv, na = A.shape[1], int(act.sum())
-    K = sp.bmat([[sp.diags(Pd), Aa.T], [Aa, None]], format="csc")
-    sol = spla.splu(K).solve(np.r_[np.zeros(nv), b])
-    x, lam = sol[:nv], sol[nv:]
-    y = np.zeros(A.shape[0]); y[act] = lam
-    ax = A @ x
-    viol = max(float(np.max(np.maximum(lo - ax, ax - up))), 0.0)                       # primal feasibility of every row
-    sign = max(float(np.max(np.where(act & ~eq & at_lo & ~at_up, y, 0.0))), float(np.max(np.where(act & ~eq & at_up & ~at_lo, -y, 0.0))), 0.0)
-    stat = float(np.abs(Pd * x + A.T @ y).max())
-    return x, y, max(viol, sign, stat)
 
 
 @pytest.mark.parametrize("name", ["path_n8", "path_n80"])

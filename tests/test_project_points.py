@@ -8,30 +8,14 @@ import subprocess
 import numpy as np
 import pytest
 
+import build_util
 import corridor_oracle as K
+import cpp_demo
 import project_util as P
 from path_optimizer_2_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "project_demo")
 NAMES = ("pqp_project_points", "pqp_project_points_device")
-REF_INCLUDE = "/root/reference/include"
-
-
-def build_demo():
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", EXE,
-                    os.path.join(ROOT, "tests", "cpp", "project_demo.cpp"), "-L" + CSRC, "-lpqp_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return EXE
-
-
-def write_case(path, s, x, y, points):
-    """the file tests/cpp/project_demo.cpp reads"""
-    with open(path, "wb") as f:
-        f.write(np.array([len(s), len(points)], np.int32).tobytes())
-        for a in (s, x, y, points):
-            f.write(np.ascontiguousarray(a, dtype=np.float64).tobytes())
 
 
 def _header_constants():
@@ -43,10 +27,9 @@ def _header_constants():
 
 # ---- the interface ---------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_bound(hip_lib):
-    import test_capi_symbols as T
     for nm in NAMES:
         assert nm in capi.EXPORTS and hasattr(hip_lib, nm), nm
-    assert set(T._declared()) == set(capi.EXPORTS)
+    assert set(build_util.declared()) == set(capi.EXPORTS)
     for fn in (hip_lib.pqp_project_points, hip_lib.pqp_project_points_device):
         assert len(fn.argtypes) == 13
     assert callable(capi.Handle.project_points)
@@ -63,21 +46,21 @@ def test_constants_equal_the_headers():
 
 
 def test_projector_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
-    exe = build_demo()
+    exe = cpp_demo.build("project_demo")
     import torch
     if torch.cuda.is_available():
         return
     path = tmp_path / "case.bin"
     s = np.linspace(0.0, 10.0, 11)
-    write_case(path, s, s, np.zeros(11), np.array([[2.5, 1.0, 0.1]]))
+    P.write_case(path, s, s, np.zeros(11), np.array([[2.5, 1.0, 0.1]]))
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no projector" in r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INCLUDE), reason="the reference tree is not on this box")
+@pytest.mark.skipif(not os.path.isdir(cpp_demo.REF_INCLUDE), reason="the reference tree is not on this box")
 def test_projector_compiles_against_the_reference_headers():
     """with PQP_USE_REFERENCE_TYPES the projector takes the reference's own State / SlState (include/data_struct/data_struct.hpp)"""
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
            "-include", "data_struct/data_struct.hpp", os.path.join(ROOT, "include", "pqp_frenet_projector.hpp")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -85,8 +68,7 @@ def test_projector_compiles_against_the_reference_headers():
 
 
 def test_the_kernel_uses_no_scratch_and_one_tile_of_lds(hip_lib):
-    import test_kernel_resources as R
-    r = R._find(R._report(), "project_points_kernel")
+    r = build_util.find_kernel(build_util.kernel_report(), "project_points_kernel")
     assert r["ScratchSize"] == 0, r
     assert r["LDS Size"] == 16 * (capi.PROJECT_TILE_SAMPLES + 1), r           # x, y of a tile of coarse samples and of the end sample
     assert r["Occupancy"] >= 4, r

@@ -20,7 +20,7 @@ import corridor_states_util as S
 import footprint_util as F
 import ref_corridor as RC
 
-NEAR_TOL = 1e-5              # footprint_util.near_threshold's: a clearance this close to the value it is tested against may fall either way on the device
+NEAR_TOL = RC.NEAR_TOL
 NEAR_SHARE = 0.02
 
 
@@ -256,14 +256,8 @@ def test_few_states_sit_on_a_threshold(ref):
     value it is tested against - a circle's radius, or the 0.5 m search radius at the state itself: at most 2 % of any scene's states,
     counted here from the reference's recorded clearances alone"""
     for name in RC.FOOTPRINT_CASES:
-        near = footprint_near(ref, name)
+        near = RC.footprint_near(ref, name)
         assert near.mean() <= NEAR_SHARE, (name, near.mean())
     for key in [f"corridor_{n}_state_distance" for n in RC.CORRIDOR_CASES] + [f"clearance_{n}_distance" for n in RC.CLEARANCE_CASES]:
         near = np.abs(ref[key].astype(np.float64) - 0.5) < NEAR_TOL
         assert near.mean() <= NEAR_SHARE, (key, near.mean())
-
-
-def footprint_near(ref, name):
-    """[n] bool: some circle of the state (the six or the bounding one) has |recorded clearance - radius| < NEAR_TOL"""
-    d = ref[f"footprint_{name}_distance"].astype(np.float64)
-    return (np.abs(d - ref[f"footprint_{name}_radius"][None]) < NEAR_TOL).any(axis=1)

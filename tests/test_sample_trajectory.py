@@ -11,42 +11,23 @@ import subprocess
 import numpy as np
 import pytest
 
+import build_util
+import cpp_demo
 import sample_util as S
 import speed_util as V
 from path_optimizer_2_amd import capi
+from shared_util import same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "sample_demo")
 NAMES = ("pqp_sample_trajectory", "pqp_sample_trajectory_device")
 LDS_BYTES = 0                                                # the kernel's choice: the search runs across the lanes, not through LDS
 
 
-def build_demo():
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", EXE,
-                    os.path.join(ROOT, "tests", "cpp", "sample_demo.cpp"), "-L" + CSRC, "-lpqp_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return EXE
-
-
-def write_case(path, paths, profile, m, n_of, stop_before, t0, dt, hold_last):
-    """the file tests/cpp/sample_demo.cpp reads; paths [B][n][stride >= 6], profile [B][n][4]"""
-    paths, profile = np.asarray(paths, dtype=np.float64), np.asarray(profile, dtype=np.float64)
-    with open(path, "wb") as f:
-        f.write(np.array(paths.shape[:2] + (m, hold_last), np.int32).tobytes())
-        f.write(np.array([dt], np.float64).tobytes())
-        f.write(np.asarray(n_of, np.int32).tobytes())
-        f.write(np.asarray(stop_before, np.int32).tobytes())
-        f.write(np.asarray(t0, np.float64).tobytes())
-        f.write(np.ascontiguousarray(np.concatenate([paths[:, :, [0, 1, 2, 5]], profile], axis=2)).tobytes())
-
-
 # ---- the interface ---------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_bound(hip_lib):
-    import test_capi_symbols as T
     for nm in NAMES + ("pqp_sample_default_params",):
         assert nm in capi.EXPORTS and hasattr(hip_lib, nm), nm
-    assert set(T._declared()) == set(capi.EXPORTS)
+    assert set(build_util.declared()) == set(capi.EXPORTS)
     for fn in (hip_lib.pqp_sample_trajectory, hip_lib.pqp_sample_trajectory_device):
         assert len(fn.argtypes) == 14
     assert callable(capi.Handle.sample_trajectory)
@@ -101,28 +82,27 @@ def test_sample_arguments_of_the_chain_wrapper_are_checked_on_the_host(hip_lib):
 
 
 def test_sampler_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
-    exe = build_demo()
+    exe = cpp_demo.build("sample_demo")
     import torch
     if torch.cuda.is_available():
         return
     path = tmp_path / "case.bin"
     paths = np.zeros((1, 5, 7))
     paths[0, :, 0] = np.arange(5)
-    write_case(path, paths, np.zeros((1, 5, 4)), 3, [5], [5], [0.0], 0.1, 0)
+    S.write_case(path, paths, np.zeros((1, 5, 4)), 3, [5], [5], [0.0], 0.1, 0)
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no sampler" in r.stderr
 
 
 def test_sampler_compiles_against_the_reference_headers():
     """with PQP_USE_REFERENCE_TYPES the sampler reads and returns the reference's own State (include/data_struct/data_struct.hpp:14-26)"""
-    import test_project_points as T
-    if not os.path.isdir(T.REF_INCLUDE):
+    if not os.path.isdir(cpp_demo.REF_INCLUDE):
         pytest.skip("the reference tree is not on this box")
     src = ("#include \"pqp_trajectory_sampler.hpp\"\n"
            "using namespace PathOptimizationNS;\n"
            "bool f(TrajectorySampler& t, const std::vector<std::vector<State>>& a, const std::vector<std::vector<SlState>>& b,\n"
            "       const std::vector<std::vector<double>>& tt, std::vector<std::vector<State>>* o) { return t.sample(a, tt, 5, o) && t.sample(b, tt, 5, o); }\n")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + T.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
            "-include", "data_struct/data_struct.hpp", "-"]
     r = subprocess.run(cmd, input=src, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -130,8 +110,7 @@ def test_sampler_compiles_against_the_reference_headers():
 
 
 def test_the_kernel_uses_no_scratch_and_a_constant_lds(hip_lib):
-    import test_kernel_resources as R
-    r = R._find(R._report(), "sample_trajectory_kernel")
+    r = build_util.find_kernel(build_util.kernel_report(), "sample_trajectory_kernel")
     assert r["ScratchSize"] == 0, r
     assert r["Occupancy"] >= 4, r
     assert r["LDS Size"] <= LDS_BYTES, r
@@ -185,15 +164,15 @@ def test_a_sample_at_a_waypoints_time_is_that_waypoint():
     assert m_of == 9 and fl == S.ENDS_MOVING
     want = np.concatenate([p[:, [0, 1, 2, 5]], prof], axis=1)
     want[:, 6] = 0.0
-    assert S.same_bits(rows[:9], want) and (rows[9:] == 0).all()
+    assert same_bits(rows[:9], want) and (rows[9:] == 0).all()
     # t0 = 1: sample k is waypoint k + 2; a t0 behind the arrival leaves nothing on the path
     rows, m_of, fl = S.sample(p, prof, 12, t0=1.0, dt=0.5)
-    assert m_of == 7 and S.same_bits(rows[:7], want[2:])
+    assert m_of == 7 and same_bits(rows[:7], want[2:])
     rows, m_of, fl = S.sample(p, prof, 4, t0=4.5, dt=0.5)
     assert m_of == 0 and fl == S.ENDS_MOVING and (rows == 0).all()
     # the arrival time itself is on the path, one ulp later is not
     rows, m_of, fl = S.sample(p, prof, 1, t0=4.0, dt=0.5)
-    assert m_of == 1 and fl == 0 and S.same_bits(rows[0], want[8])
+    assert m_of == 1 and fl == 0 and same_bits(rows[0], want[8])
     rows, m_of, fl = S.sample(p, prof, 1, t0=np.nextafter(4.0, 5.0), dt=0.5)
     assert m_of == 0 and fl == S.ENDS_MOVING
     # halfway between two waypoints: halfway along the chord, the heading and curvature in between

@@ -8,38 +8,20 @@ import subprocess
 import numpy as np
 import pytest
 
+import build_util
+import cpp_demo
 import select_util as S
 from path_optimizer_2_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "select_demo")
 NAMES = ("pqp_select_default_params", "pqp_select_paths", "pqp_select_paths_device")
-
-
-def build_demo():
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", EXE,
-                    os.path.join(ROOT, "tests", "cpp", "select_demo.cpp"), "-L" + CSRC, "-lpqp_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return EXE
-
-
-def write_candidates(path, candidates, group_start):
-    """the file tests/cpp/select_demo.cpp reads"""
-    with open(path, "wb") as f:
-        f.write(np.array([len(candidates), len(group_start) - 1], np.int32).tobytes())
-        f.write(np.asarray(group_start, np.int32).tobytes())
-        for c in candidates:
-            f.write(np.array([len(c)], np.int32).tobytes())
-            f.write(np.ascontiguousarray(c, dtype=np.float64).tobytes())
 
 
 # ---- the interface ---------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_bound(hip_lib):
-    import test_capi_symbols as T
     for nm in NAMES:
         assert nm in capi.EXPORTS and hasattr(hip_lib, nm), nm
-    assert set(T._declared()) == set(capi.EXPORTS)
+    assert set(build_util.declared()) == set(capi.EXPORTS)
     assert capi.SCORE_STRIDE == 8 and C.sizeof(capi.PqpSelectParams) == 6 * 8 + 2 * 4
     for fn in (hip_lib.pqp_select_paths, hip_lib.pqp_select_paths_device):
         assert len(fn.argtypes) == 17
@@ -59,21 +41,20 @@ def test_default_params_are_the_path_qps_weights(hip_lib):
 
 
 def test_selector_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
-    exe = build_demo()
+    exe = cpp_demo.build("select_demo")
     import torch
     if torch.cuda.is_available():
         return
     path = tmp_path / "candidates.bin"
-    write_candidates(path, [np.zeros((3, 7)), np.ones((2, 7))], [0, 2])
+    S.write_candidates(path, [np.zeros((3, 7)), np.ones((2, 7))], [0, 2])
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no selector" in r.stderr
 
 
 def test_both_kernels_use_no_scratch_and_no_lds(hip_lib):
-    import test_kernel_resources as R
-    kernels = R._report()
+    kernels = build_util.kernel_report()
     for name in ("path_score_kernel", "group_select_kernel"):
-        r = R._find(kernels, name)
+        r = build_util.find_kernel(kernels, name)
         assert r["ScratchSize"] == 0 and r["LDS Size"] == 0 and r["Occupancy"] >= 8, (name, r)
 
 

@@ -9,12 +9,12 @@ import subprocess
 import numpy as np
 import pytest
 
+import build_util
+import cpp_demo
 import speed_util as V
 from path_optimizer_2_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "path_optimizer_2_amd", "csrc")
-EXE = os.path.join(ROOT, "tests", "cpp", "speed_demo")
 NAMES = ("pqp_speed_profile", "pqp_speed_profile_device")
 COUNTS = (0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 200, 700)
 # the restatement speaks the binding's flags: every test below reads them through V
@@ -22,31 +22,11 @@ assert (V.START_TOO_FAST, V.STOPS_EARLY, V.NEVER_ARRIVES, V.EMPTY, V.NOT_FINITE,
        (capi.SPEED_START_TOO_FAST, capi.SPEED_STOPS_EARLY, capi.SPEED_NEVER_ARRIVES, capi.SPEED_EMPTY, capi.SPEED_NOT_FINITE, capi.SPEED_STRIDE)
 
 
-def build_demo():
-    subprocess.run(["g++", "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"), "-o", EXE,
-                    os.path.join(ROOT, "tests", "cpp", "speed_demo.cpp"), "-L" + CSRC, "-lpqp_hip", "-L/opt/rocm/lib", "-lamdhip64",
-                    "-Wl,-rpath," + CSRC, "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return EXE
-
-
-def write_case(path, paths, n_of, stop_before, v_start, v_end):
-    """the file tests/cpp/speed_demo.cpp reads; paths [B][n][stride >= 6]"""
-    paths = np.asarray(paths, dtype=np.float64)
-    with open(path, "wb") as f:
-        f.write(np.array(paths.shape[:2], np.int32).tobytes())
-        f.write(np.asarray(n_of, np.int32).tobytes())
-        f.write(np.asarray(stop_before, np.int32).tobytes())
-        f.write(np.asarray(v_start, np.float64).tobytes())
-        f.write(np.asarray(v_end, np.float64).tobytes())
-        f.write(np.ascontiguousarray(paths[:, :, [0, 1, 5]]).tobytes())
-
-
 # ---- the interface ---------------------------------------------------------------------------------------------------------------------
 def test_symbols_are_exported_and_bound(hip_lib):
-    import test_capi_symbols as T
     for nm in NAMES + ("pqp_speed_default_params",):
         assert nm in capi.EXPORTS and hasattr(hip_lib, nm), nm
-    assert set(T._declared()) == set(capi.EXPORTS)
+    assert set(build_util.declared()) == set(capi.EXPORTS)
     for fn in (hip_lib.pqp_speed_profile, hip_lib.pqp_speed_profile_device):
         assert len(fn.argtypes) == 13
     assert callable(capi.Handle.speed_profile)
@@ -96,24 +76,23 @@ def test_speed_arguments_of_the_chain_wrapper_are_checked_on_the_host(hip_lib):
 
 
 def test_profiler_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
-    exe = build_demo()
+    exe = cpp_demo.build("speed_demo")
     import torch
     if torch.cuda.is_available():
         return
     path = tmp_path / "case.bin"
     paths = np.zeros((1, 5, 7))
     paths[0, :, 0] = np.arange(5)
-    write_case(path, paths, [5], [5], [1.0], [math.nan])
+    V.write_case(path, paths, [5], [5], [1.0], [math.nan])
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no profiler" in r.stderr
 
 
 def test_profiler_compiles_against_the_reference_headers():
     """with PQP_USE_REFERENCE_TYPES the profiler fills the reference's own State::s, v, a (include/data_struct/data_struct.hpp:14-26)"""
-    import test_project_points as T
-    if not os.path.isdir(T.REF_INCLUDE):
+    if not os.path.isdir(cpp_demo.REF_INCLUDE):
         pytest.skip("the reference tree is not on this box")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + T.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
+    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
            "-include", "data_struct/data_struct.hpp", os.path.join(ROOT, "include", "pqp_speed_profiler.hpp")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
@@ -121,8 +100,7 @@ def test_profiler_compiles_against_the_reference_headers():
 
 
 def test_the_kernel_uses_no_scratch_and_no_lds(hip_lib):
-    import test_kernel_resources as R
-    r = R._find(R._report(), "speed_profile_kernel")
+    r = build_util.find_kernel(build_util.kernel_report(), "speed_profile_kernel")
     assert r["ScratchSize"] == 0, r
     assert r["Occupancy"] >= 4, r
     assert r["LDS Size"] == 0, r                             # the tile carries are wave-uniform registers
