@@ -59,6 +59,7 @@
 #define PQP_H_
 
 #include <stdint.h>
+#include "pqp_search_params.h"      /* pqp_search_params, the parameters of pqp_speed_search (below) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -1027,6 +1028,98 @@ int pqp_agents_check_device(pqp_handle* h, double margin, const pqp_car_geometry
 int pqp_agents_check(pqp_handle* h, double margin, const pqp_car_geometry* car, int batch, int m, int stride,
                      const double* traj, const int32_t* m_of, int n_scenes, int a_max, const double* agents, const int32_t* a_of,
                      const int32_t* scene_of, int32_t* first_hit, int32_t* hit_agent, double* clearance);
+
+/* ---- speeds past predicted agents: a search in the path-time plane -------------------------------------------------------------------------
+ * pqp_agents_check says that a trajectory hits a predicted agent; most such hits are conflicts of timing on a good path.  This keeps the
+ * path and plans the speed: for every path it marks which cells of the path-time plane - station j at arc length j ds against layer k at
+ * time k dt - the car's footprint would share with an agent (the test of pqp_agents_check, unchanged), and finds by a layered dynamic
+ * program the cheapest sequence of stations over the layers that stays out of marked cells, within the acceleration and braking limits
+ * and under the envelope of pqp_speed_profile's v and a.  It is the coarse yield-or-pass decision of a path-speed decoupled planner,
+ * batched over the candidates, behind the speed profile on the same stream.  The reference has no counterpart (it plans one path
+ * against a static map and fills no State::v). */
+/* The parameters, pqp_search_params, are declared in pqp_search_params.h, which this header includes: dt (1.0 s) and ds (0.5 m), the grid;
+ * w_slow (1.0) and w_accel (1.0), the prices; margin (0.0 m), pqp_agents_check's; stations (128), S; q_max (20), Q <= 63; q_up (3) and
+ * q_down (6), by how much a step may grow and shrink per layer. */
+#define PQP_SEARCH_MAX_STATES 4096       /* stations * (q_max + 1) may not exceed it: two cost layers of that many doubles are 64 KiB of LDS */
+/* Both pure host.  pqp_search_params_from_speed starts from the defaults and sets q_max = floor(v_max dt / ds), q_up = max(1, floor(a_max
+ * dt^2 / ds)), q_down = max(1, floor(d_max dt^2 / ds)), the two held to 63 (beyond q_max they change nothing); PQP_ERR_INVALID for a null pointer, a dt or ds that is not finite and positive,
+ * or q_max > 63 (*p is then untouched).  The defaults are that call on pqp_speed_default_params with dt = 1, ds = 0.5. */
+void pqp_search_default_params(pqp_search_params* p);
+int pqp_search_params_from_speed(const pqp_speed_params* sp, double dt, double ds, pqp_search_params* p);
+enum { PQP_SEARCH_NO_PLAN = 1, PQP_SEARCH_START_BLOCKED = 2, PQP_SEARCH_GRID_SHORT = 4, PQP_SEARCH_ARRIVED = 8, PQP_SEARCH_EMPTY = 16, PQP_SEARCH_NOT_FINITE = 32 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   paths [batch][n][stride]          x, y, heading at offsets 0, 1, 2 and k at offset 5, stride >= 6: `out` or best_paths in place
+ *   n_of, stop_before [batch] or NULL the driven count c, by pqp_speed_profile's expression
+ *   profile [batch][n][PQP_SPEED_STRIDE]   s, v, a, t as pqp_speed_profile wrote them: s places the waypoints, v and a are the envelope (it
+ *                                     holds the curvature, the limits and the stop before a static collision); t is not read
+ *   v_start [batch]                   finite, >= 0
+ *   m >= 1                            layers
+ *   n_scenes, a_max, agents [n_scenes][a_max][m][PQP_AGENT_STRIDE], a_of, scene_of, car   exactly pqp_agents_check's; the agents' m steps
+ *                                     are the layers
+ *   frames [n_scenes][a_max][m][PQP_AGENT_FRAME_STRIDE], blocked [batch][m][W] (W = ceil(S / 32)), parents [batch][m][S][Q + 1]
+ *                                     (_device form only) workspaces of the caller's; nothing is allocated.  What they hold after the
+ *                                     call is not specified, except blocked
+ * The definition, in fp64, every product and sum rounded on its own (no contraction), min and max as fmin and fmax; every decision that can
+ * be an integer is one.  For a path with driven count c:
+ *   stations   sigma_j = (double)j * ds;  M_i = max_{i' <= i} s_i', the running maximum (as pqp_sample_trajectory takes T).  Station j is on
+ *              the path when sigma_j <= M_{c-1}; J = the number of such j < S (a prefix), j_last = J - 1
+ *   pose at sigma_j: the sampler's interpolation with e given.  i = max(#{ i' < c : M_i' <= sigma_j } - 1, 0).  At i = c - 1 the waypoint
+ *              itself.  Otherwise (dx, dy) = (x_{i+1} - x_i, y_{i+1} - y_i); d = sqrt(dx*dx + dy*dy); e = min(max(sigma_j - s_i, 0), d);
+ *              lambda = d > 0 ? e / d : 0; x, y, heading, k as pqp_sample_trajectory states them
+ *   envelope   w = v_i*v_i + (2*a_i)*e, or v_{c-1}*v_{c-1} at i = c - 1;  venv_j = sqrt(max(w, 0));
+ *              qenv_j = (int)min(floor(venv_j * dt / ds), (double)Q)
+ *   blocked(k, j), k < m, j < J: the footprint posed at station j has clear(., a) < margin against some agent a < A of the path's scene at
+ *              step k - the frames and the circle test of pqp_agents_check unchanged: an absent row is skipped, a bad row blocks every
+ *              station of its layer, and a pose that is not finite (an overflow) is blocked at every layer.  Bit j & 31 of word j >> 5 of
+ *              blocked[b][k] holds it; bits at j >= J are 0
+ *   states     (j, q) at layer k: at station j, arrived by a step of q cells.  Layer 0 holds the one state (0, q0), q0 = (int)min(max(
+ *              rint(v_start * dt / ds), 0), (double)Q), at cost 0; it lives unless blocked(0, 0) or J = 0.  From a living (j', q') at
+ *              layer k - 1 the step q to (j' + q, q) at layer k is allowed when
+ *                max(q' - q_down, 0) <= q <= min(q' + q_up, Q);   j' + q <= j_last;   q <= max(qenv_j', qenv_{j'+q})  (the envelope at
+ *                the departure covers a braking step, the one at the arrival an accelerating step);   no station of j' .. j' + q is
+ *                blocked at layer k - 1 or at layer k (the step must not jump over an agent that is crossing)
+ *              qref_j' = max over r in 1 .. min(Q, j_last - j') of min(r, max(qenv_j', qenv_{j'+r})), 0 when there is no such r: the largest
+ *                step the envelope admits from station j'.  An allowed q is never above it
+ *              edge = w_accel * (double)((q - q')*(q - q')) + w_slow * (double)(qref_j' - q)
+ *                (Priced against max(qenv_j', qenv_{j'+q}) itself, a car at rest - qenv_0 = 0 - would stand for nothing and pay for every
+ *                step it takes, and no plan would leave station 0: the step is priced against what the envelope allows from where it
+ *                starts, which is the same thing wherever the car runs along the envelope and is 0 at j_last.)
+ *              cost_k(j, q) = min_{q'} (cost_{k-1}(j - q, q') + edge), q' ascending and the lowest q' wins a tie.  A state lives when
+ *              its cost is below +inf
+ *   reached    the number of layers with a living state (m when the search gets through).  The plan ends in the cheapest state of layer
+ *              reached - 1, ties to the largest j, then the smallest q, and is followed back through the parents
+ * Outputs, fully overwritten:
+ *   steps [batch][m][2]               j_k, q_k for k < reached; -1, -1 behind
+ *   traj [batch][m][PQP_TRAJ_STRIDE]  k < reached: the pose at station j_k (x, y, heading, k), s = sigma_{j_k}, v = (double)q_k * ds / dt,
+ *                                     a = (double)(q_{k+1} - q_k) * ds / (dt*dt) and 0 at the last planned layer, t = (double)k * dt; zeros
+ *                                     behind.  It is pqp_agents_check's input shape: the plan can be handed back to the checker
+ *   cost [batch]                      the plan's cost; +inf when reached = 0
+ *   reached [batch], flags [batch]
+ *   blocked                           an output of the host form too, where NULL means not wanted
+ * flags:
+ *   PQP_SEARCH_NO_PLAN         reached < m
+ *   PQP_SEARCH_START_BLOCKED   reached = 0 (with PQP_SEARCH_NO_PLAN)
+ *   PQP_SEARCH_GRID_SHORT      M_{c-1} > sigma_{S-1}: the grid ends before the path
+ *   PQP_SEARCH_ARRIVED         the plan's last station is j_last and PQP_SEARCH_GRID_SHORT is clear
+ *   PQP_SEARCH_EMPTY           c = 0: set alone; traj zeros, steps -1, reached 0, cost +inf, the path's blocked words 0
+ *   PQP_SEARCH_NOT_FINITE      an x, y, heading, k, s, v or a below index c that is not finite, or a v_start that is not finite or is
+ *                              negative: set alone; traj NaN, steps -1, reached 0, cost NaN, the path's blocked words 0; neighbours untouched
+ * Rules this text settles where the plain reading leaves a gap: a path whose s column lies below 0 throughout has J = 0 and no state at
+ * layer 0 (PQP_SEARCH_START_BLOCKED); q0 is clamped as a double before it becomes an integer; a cost that overflows to +inf is a dead state.
+ * A path's result depends on its own rows, its scene and the parameters alone: the same bits at any batch position and from either form;
+ * no atomics, the same answer every run.  The _device form is three launches (the frames, the occupancy, the search), asynchronous on
+ * the handle's stream.  The host form stages the workspaces itself, copies in, runs, copies out and synchronises, and refuses a scene_of
+ * outside [0, n_scenes) where the device form clamps.  Both forms: PQP_ERR_INVALID, with nothing launched and the outputs untouched, for a
+ * null pointer that is not optional, batch < 1, n < 1, m < 1, stride < 6, a parameter outside the ranges pqp_search_params states,
+ * stations * (q_max + 1) > PQP_SEARCH_MAX_STATES, or what pqp_agents_check refuses. */
+int pqp_speed_search_device(pqp_handle* h, const pqp_search_params* prm, const pqp_car_geometry* car, int batch, int n, int stride,
+                            const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start,
+                            int m, int n_scenes, int a_max, const double* agents, const int32_t* a_of, const int32_t* scene_of, double* frames,
+                            int32_t* blocked, uint8_t* parents, int32_t* steps, double* traj, double* cost, int32_t* reached, int32_t* flags);
+int pqp_speed_search(pqp_handle* h, const pqp_search_params* prm, const pqp_car_geometry* car, int batch, int n, int stride,
+                     const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start, int m,
+                     int n_scenes, int a_max, const double* agents, const int32_t* a_of, const int32_t* scene_of, int32_t* blocked,
+                     int32_t* steps, double* traj, double* cost, int32_t* reached, int32_t* flags);
 
 #ifdef __cplusplus
 }

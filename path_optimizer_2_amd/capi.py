@@ -22,7 +22,7 @@ globals().update({k[len("PQP_"):]: v for k, v in HEADER.constants.items()})     
 
 _FIELD = {"double": C.c_double, "int32_t": C.c_int32}
 STRUCTS = {}                                                   # header name -> Structure class, in the header's order
-for _s in HEADER.structs.values():
+for _s in list(HEADER.structs.values()) + list(HEADER.included.values()):       # pqp.h's own, then those of the headers it includes
     STRUCTS[_s.name] = type(pqp_header.class_name(_s.name), (C.Structure,),
                             {"_fields_": [(f, _FIELD.get(t) or STRUCTS[t]) for f, t in _s.fields], "__module__": __name__})
 globals().update({c.__name__: c for c in STRUCTS.values()})    # PqpParams, PqpSizes, PqpGridGeometry, ...
@@ -180,6 +180,24 @@ def agents_default_params(lib=None, **over):
     p = AgentsParams(margin.value)
     for k, v in over.items():
         setattr(p, k, v)
+    return p
+
+
+SearchParams = PqpSearchParams                                 # pqp_search_params under the name the other parameter sets go by here
+
+
+def search_default_params(lib=None, **over):
+    """pqp_search_default_params: dt 1 s, ds 0.5 m, both weights 1, margin 0, 128 stations, steps up to 20 cells that grow by at most 3 and
+    shrink by at most 6 per layer - pqp_search_params_from_speed on the speed defaults - with `over` applied."""
+    return _defaults(lib, SearchParams, "pqp_search_default_params", over)
+
+
+def search_params_from_speed(lib, speed_prm, dt, ds):
+    """pqp_search_params_from_speed (pure host): the defaults with q_max, q_up and q_down from the speed limits of `speed_prm` at the grid
+    dt, ds.  PqpError when floor(v_max dt / ds) > 63."""
+    lib = lib or load_library()
+    p = SearchParams()
+    _raise_on(lib, lib.pqp_search_params_from_speed(C.byref(speed_prm), float(dt), float(ds), C.byref(p)))
     return p
 
 
@@ -364,8 +382,8 @@ class Handle:
         return _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", over)
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
-                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, agents=None, agents_of=None,
-                      scene_of=None, agents_params=None, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, agents=None,
+                      agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -390,27 +408,32 @@ class Handle:
         (needs sample) - pqp_agents_check_device behind the sampler on the same stream, on its traj and traj_n, or on all `samples` rows
         with sample.hold_last (the parked car is checked too); agents_of [n_scenes]: agents per scene (None: all), scene_of: the scene of
         every row the sampler ran on ([B], or [groups] with select; None: scene 0), agents_params: AgentsParams (None: agents_default_params()),
-        car: the footprint.  Adds first_hit, hit_agent and agent_clearance [..][samples]."""
+        car: the footprint.  Adds first_hit, hit_agent and agent_clearance [..][samples].
+        search: SearchParams (needs speed and agents; not sample) - pqp_speed_search_device behind the speed profile on the same stream, on
+        the rows it ran on, with its v_start: the agents' step count is the number of layers m (with sample too, that is `samples`, and
+        both run).  Adds search_steps [..][m][2], search_traj [..][m][8], search_cost, search_reached and search_flags."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
-                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select))
+                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
+                           self._search(search, speed, agents))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
-                              t0=None, speed=None, v_start=None, v_end=None):
+                              winners_only=False, search=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None,
+                              samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
-        agents_params: as for optimize_path)."""
+        agents_params / search: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
-                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select))
+                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
+                           self._search(search, speed, agents))
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -435,15 +458,29 @@ class Handle:
             raise ValueError("sample needs samples >= 1")
         return (sample, int(samples), None if t0 is None else np.ascontiguousarray(t0, dtype=np.float64).ravel())
 
-    def _agents(self, agents, agents_of, scene_of, agents_params, sample, samples, car, batch, select):
+    def _search(self, search, speed, agents):
+        if search is None:
+            return None
+        if not isinstance(search, SearchParams):
+            raise ValueError("search must be a SearchParams")
+        if speed is None:
+            raise ValueError("search needs speed=PqpSpeedParams: the search runs under its profile's envelope")
+        if agents is None:
+            raise ValueError("search needs agents=: the predicted agents at the layers' times")
+        return search
+
+    def _agents(self, agents, agents_of, scene_of, agents_params, sample, samples, car, batch, select, search=None):
         if agents is None:
             if agents_of is not None or scene_of is not None or agents_params is not None:
                 raise ValueError("agents_of / scene_of / agents_params need agents=")
             return None
-        if sample is None:
+        if sample is None and search is None:
             raise ValueError("agents needs sample=PqpSampleParams: the agents are given at the samples' time steps")
         agents = np.ascontiguousarray(agents, dtype=np.float64)
-        if agents.ndim != 4 or agents.shape[0] < 1 or agents.shape[2] != int(samples) or agents.shape[3] != AGENT_STRIDE:
+        if sample is None:                                             # the search alone: the agents' steps are its layers
+            if agents.ndim != 4 or agents.shape[0] < 1 or agents.shape[2] < 1 or agents.shape[3] != AGENT_STRIDE:
+                raise ValueError(f"agents must be [n_scenes >= 1][a_max][m >= 1][{AGENT_STRIDE}], not {agents.shape}")
+        elif agents.ndim != 4 or agents.shape[0] < 1 or agents.shape[2] != int(samples) or agents.shape[3] != AGENT_STRIDE:
             raise ValueError(f"agents must be [n_scenes >= 1][a_max][{int(samples)}][{AGENT_STRIDE}], not {agents.shape}")
         n_scenes = agents.shape[0]
         i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32).ravel()
@@ -466,12 +503,13 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None, moving=None):
+               selection=None, speed=None, sampling=None, moving=None, searching=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
         of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None; moving:
-        (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that, or None"""
+        (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that (when there is a sampling), or
+        None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -513,9 +551,19 @@ class Handle:
             ag_car = ag_car if ag_car is not None else car_default_geometry(self.lib)
             d_ag, d_ag_of, d_scene = t(ag, np.float64), t(ag_of, np.int32), t(scene_of, np.int32)
             ag_frames = torch.zeros(ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
+        if moving is not None and sampling is not None:
             first_hit = torch.zeros(rows, dtype=torch.int32, device=dev)
             hit_agent = torch.zeros(rows, dtype=torch.int32, device=dev)
             agent_clearance = torch.zeros((rows, m), dtype=torch.float64, device=dev)
+        if searching is not None:
+            layers, se_S, se_Q1 = ag.shape[2], int(searching.stations), int(searching.q_max) + 1
+            se_blocked = torch.zeros((rows, layers, (max(se_S, 0) + 31) // 32), dtype=torch.int32, device=dev)
+            se_parents = torch.zeros((rows, layers, max(se_S, 0), max(se_Q1, 1)), dtype=torch.uint8, device=dev)
+            se_steps = torch.zeros((rows, layers, 2), dtype=torch.int32, device=dev)
+            se_traj = torch.zeros((rows, layers, TRAJ_STRIDE), dtype=torch.float64, device=dev)
+            se_cost = torch.zeros(rows, dtype=torch.float64, device=dev)
+            se_reached = torch.zeros(rows, dtype=torch.int32, device=dev)
+            se_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -550,11 +598,19 @@ class Handle:
                 self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, out, ints[0],
                                                                   first if footprint is not None else None, profile, d_t0, m, traj,
                                                                   traj_n, traj_flags))
-        if moving is not None:              # behind the sampler, on its samples: all of them with hold_last (the parked car), else those on the path
+        if moving is not None and sampling is not None:      # behind the sampler, on its samples: all of them with hold_last (the parked car), else those on the path
             self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, m, TRAJ_STRIDE, traj,
                                                          None if sa_prm.hold_last else traj_n, ag.shape[0], ag.shape[1],
                                                          d_ag if ag.size else None, d_ag_of, d_scene, ag_frames if ag.size else None,
                                                          first_hit, hit_agent, agent_clearance))
+        if searching is not None:           # behind the speed profile, on the rows it ran on and under its envelope
+            on_winners = selection is not None
+            self._check(self.lib.pqp_speed_search_device(self._h, C.byref(searching), C.byref(ag_car), rows, cfg.n_max, 7,
+                                                         best_paths if on_winners else out, best_n if on_winners else ints[0],
+                                                         first if (footprint is not None and not on_winners) else None, profile, d_vs, layers,
+                                                         ag.shape[0], ag.shape[1], d_ag if ag.size else None, d_ag_of, d_scene,
+                                                         ag_frames if ag.size else None, se_blocked, se_parents, se_steps, se_traj, se_cost,
+                                                         se_reached, se_flags))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -574,8 +630,11 @@ class Handle:
             res.update(profile=host(profile), speed_flags=host(speed_flags))
         if sampling is not None:
             res.update(traj=host(traj), traj_n=host(traj_n), traj_flags=host(traj_flags))
-        if moving is not None:
+        if moving is not None and sampling is not None:
             res.update(first_hit=host(first_hit), hit_agent=host(hit_agent), agent_clearance=host(agent_clearance))
+        if searching is not None:
+            res.update(search_steps=host(se_steps), search_traj=host(se_traj), search_cost=host(se_cost), search_reached=host(se_reached),
+                       search_flags=host(se_flags))
         return res
 
     def distance_layer(self, grid, geom):
@@ -700,6 +759,45 @@ class Handle:
         res = dict(first_hit=first, hit_agent=who)
         if clearance:
             res["clearance"] = cl
+        return res
+
+    def speed_search(self, paths, profile, v_start, agents, m=None, n_of=None, stop_before=None, a_of=None, scene_of=None, car=None, prm=None,
+                     blocked=False):
+        """pqp_speed_search (host arrays): paths [B][n][stride >= 6] (the chain's `out` or best_paths as they are), profile [B][n][4] = s, v,
+        a, t (speed_profile's), v_start [B], agents [n_scenes][a_max][m][6] at the m layers' times k dt (m=None: the agents' step count;
+        without agents, a_max = 0, m must be given), and optionally n_of [B], stop_before [B] (the two speed_profile got), a_of [n_scenes],
+        scene_of [B] (None: scene 0); car = PqpCarGeometry (None: the reference's), prm = SearchParams (None: search_default_params()).
+        Returns dict(steps [B][m][2] = j, q, traj [B][m][8], cost [B], reached [B], flags [B] of SEARCH_*[, blocked [B][m][W] int32])."""
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        B, n, stride = paths.shape
+        profile = np.ascontiguousarray(profile, dtype=np.float64)
+        if profile.shape != (B, n, SPEED_STRIDE):
+            raise ValueError(f"speed_search: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        agents = np.ascontiguousarray(agents, dtype=np.float64)
+        if agents.ndim != 4 or agents.shape[3] != AGENT_STRIDE or (m is not None and agents.shape[2] != int(m)):
+            raise ValueError(f"speed_search: agents must be [n_scenes][a_max][{'m' if m is None else int(m)}][{AGENT_STRIDE}], not {agents.shape}")
+        m = agents.shape[2] if m is None else int(m)
+        n_scenes, a_max = agents.shape[:2]
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        no, sb, ao, so = i32(n_of), i32(stop_before), i32(a_of), i32(scene_of)
+        vs = np.ascontiguousarray(v_start, dtype=np.float64)
+        for name, a, size in (("n_of", no, B), ("stop_before", sb, B), ("v_start", vs, B), ("a_of", ao, n_scenes), ("scene_of", so, B)):
+            if a is not None and a.size != size:
+                raise ValueError(f"speed_search: {name} must have {size} entries, not {a.size}")
+        car = car if car is not None else car_default_geometry(self.lib)
+        prm = prm if prm is not None else search_default_params(self.lib)
+        rows = max(m, 0)
+        steps = np.zeros((B, rows, 2), dtype=np.int32)
+        traj = np.zeros((B, rows, TRAJ_STRIDE))
+        cost = np.zeros(B)
+        reached = np.zeros(B, dtype=np.int32)
+        flags = np.zeros(B, dtype=np.int32)
+        blk = np.zeros((B, rows, (max(int(prm.stations), 0) + 31) // 32), dtype=np.int32) if blocked else None
+        self._check(self.lib.pqp_speed_search(self._h, C.byref(prm), C.byref(car), B, n, stride, paths, no, sb, profile, vs, m, n_scenes, a_max,
+                                              agents if agents.size else None, ao, so, blk, steps, traj, cost, reached, flags))
+        res = dict(steps=steps, traj=traj, cost=cost, reached=reached, flags=flags)
+        if blocked:
+            res["blocked"] = blk
         return res
 
     def corridor_params(self, **over):

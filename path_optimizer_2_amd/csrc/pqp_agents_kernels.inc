@@ -59,6 +59,24 @@ __global__ void __launch_bounds__(kAgentsThreads) agent_frames_kernel(const Agen
     for (int q = 0; q < PQP_AGENT_FRAME_STRIDE; ++q) o[q] = f[q];
 }
 
+// clear(k, a) of include/pqp.h: the six circles at (gx, gy) with radii cr against the rounded rectangle of one frame row; the test of
+// agents_check_kernel and of st_occupancy_kernel (pqp_search_kernels.inc)
+__device__ __forceinline__ double agent_clear(const double (&gx)[6], const double (&gy)[6], const double* cr, double ax, double ay, double c,
+                                              double sn, double hl, double hw, double radius) {
+#pragma clang fp contract(off)
+    double c_ka = INFINITY;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const double dx = gx[j] - ax, dy = gy[j] - ay;
+        const double u = dx * c + dy * sn, w = dy * c - dx * sn;
+        const double ex = fabs(u) - hl, ey = fabs(w) - hw;
+        const double ox = fmax(ex, 0.0), oy = fmax(ey, 0.0);
+        const double d = sqrt(ox * ox + oy * oy) + fmin(fmax(ex, ey), 0.0) - radius;
+        c_ka = fmin(c_ka, d - cr[j]);
+    }
+    return c_ka;
+}
+
 template <bool CLEARANCE>
 __global__ void __launch_bounds__(kAgentsThreads) agents_check_kernel(const AgentsArgs a) {
 #pragma clang fp contract(off)
@@ -105,17 +123,7 @@ __global__ void __launch_bounds__(kAgentsThreads) agents_check_kernel(const Agen
                             const double far = a.rb + reach + margin + kAgentsSlack + kAgentsSlackRel * (fabs(bx) + fabs(by) + fabs(ax) + fabs(ay));
                             if (ux * ux + uy * uy > far * far) continue;                  // clear(k, a) >= margin + the slack: no hit
                         }
-                        const double c = f[2], sn = f[3], hl = f[4], hw = f[5], radius = f[6];
-                        c_ka = INFINITY;
-#pragma unroll
-                        for (int j = 0; j < 6; ++j) {
-                            const double dx = gx[j] - ax, dy = gy[j] - ay;
-                            const double u = dx * c + dy * sn, w = dy * c - dx * sn;
-                            const double ex = fabs(u) - hl, ey = fabs(w) - hw;
-                            const double ox = fmax(ex, 0.0), oy = fmax(ey, 0.0);
-                            const double d = sqrt(ox * ox + oy * oy) + fmin(fmax(ex, ey), 0.0) - radius;
-                            c_ka = fmin(c_ka, d - a.cr[j]);
-                        }
+                        c_ka = agent_clear(gx, gy, a.cr, ax, ay, f[2], f[3], f[4], f[5], f[6]);
                     }
                     clear = fmin(clear, c_ka);
                     if (c_ka < margin && !hit) { hit = true; hit_a = ag; }

@@ -241,7 +241,7 @@ struct pqp_handle {
         bool capturing = false;
     } chain;
 
-    static constexpr int kStage = 12;
+    static constexpr int kStage = 16;           // pqp_speed_search stages the most: eight inputs, three workspaces, five outputs
     DevBuf stage[kStage];                       // device copies of the arrays of a host-pointer entry point (Staging), in argument order
                                                 // (no key: the chain is a device-pointer entry point and stages nothing)
 

@@ -1,8 +1,8 @@
 // pqp_maps.hip — the entry points of include/pqp.h around the obstacle distance map and the planned paths: the distance layer from an
 // occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
 // group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc), samples of those trajectories on a time grid
-// (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc).  Their kernels, launchers and entry
-// points.
+// (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc), speeds that pass those agents in
+// the path-time plane (pqp_search_kernels.inc).  Their kernels, launchers and entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +31,7 @@ using namespace pqp_internal;
 #include "pqp_speed_kernels.inc"
 #include "pqp_sample_kernels.inc"
 #include "pqp_agents_kernels.inc"
+#include "pqp_search_kernels.inc"
 
 extern "C" {
 
@@ -410,6 +411,121 @@ int pqp_agents_check(pqp_handle* h, double margin, const pqp_car_geometry* car, 
     return st.run([&]() -> int {
         return pqp_agents_check_device(h, margin, car, batch, m, stride, d_traj, d_m_of, n_scenes, a_max, d_agents, d_a_of, d_scene_of, d_frames,
                                        d_first, d_who, d_clear);
+    });
+}
+
+// ---- speeds past predicted agents: a search in the path-time plane ---------------------------------------------------------------------------
+int pqp_search_params_from_speed(const pqp_speed_params* sp, double dt, double ds, pqp_search_params* p) {
+    if (!sp || !p || !(std::isfinite(dt) && dt > 0.0) || !(std::isfinite(ds) && ds > 0.0))
+        return fail(PQP_ERR_INVALID, "pqp_search_params_from_speed: bad argument (dt and ds finite and > 0)");
+    // this library's choice, as pqp_speed_default_params: the reference has no time axis
+    const double q_max = std::floor(sp->v_max * dt / ds), q_up = std::floor(sp->a_max * (dt * dt) / ds), q_down = std::floor(sp->d_max * (dt * dt) / ds);
+    if (!(q_max >= 0.0 && q_max <= 63.0)) return fail(PQP_ERR_INVALID, "pqp_search_params_from_speed: floor(v_max dt / ds) outside 0 .. 63");
+    p->dt = dt;
+    p->ds = ds;
+    p->w_slow = 1.0;
+    p->w_accel = 1.0;
+    p->margin = 0.0;
+    p->stations = 128;
+    p->q_max = (int32_t)q_max;
+    p->q_up = (int32_t)std::fmin(std::fmax(q_up, 1.0), 63.0);
+    p->q_down = (int32_t)std::fmin(std::fmax(q_down, 1.0), 63.0);
+    return PQP_OK;
+}
+
+void pqp_search_default_params(pqp_search_params* p) {
+    if (!p) return;
+    pqp_speed_params sp;
+    pqp_speed_default_params(&sp);
+    (void)pqp_search_params_from_speed(&sp, 1.0, 0.5, p);
+}
+
+static const char* const kSearchRefusal =
+    "pqp_speed_search: bad argument (batch >= 1; n >= 1; m >= 1; stride >= 6; dt and ds finite and > 0; w_slow, w_accel and margin finite and >= 0; "
+    "stations >= 1; 0 <= q_max <= 63; q_up, q_down >= 0; stations * (q_max + 1) <= 4096; n_scenes >= 1; a_max >= 0; n_scenes * a_max * m <= 2^38; "
+    "a finite car geometry)";
+
+static bool search_ok(pqp_handle* h, const pqp_search_params* prm, const pqp_car_geometry* car, int batch, int n, int stride, const double* paths,
+                      const double* profile, const double* v_start, int m, int n_scenes, int a_max, const double* agents, const int32_t* steps,
+                      const double* traj, const double* cost, const int32_t* reached, const int32_t* flags) {
+    if (!(h && prm && paths && profile && v_start && steps && traj && cost && reached && flags && batch >= 1 && n >= 1 && m >= 1 && stride >= 6))
+        return false;
+    const auto price = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    if (!(std::isfinite(prm->dt) && prm->dt > 0.0 && std::isfinite(prm->ds) && prm->ds > 0.0 && price(prm->w_slow) && price(prm->w_accel))) return false;
+    if (!(prm->stations >= 1 && prm->q_max >= 0 && prm->q_max <= 63 && prm->q_up >= 0 && prm->q_down >= 0 &&
+          (long long)prm->stations * (prm->q_max + 1) <= PQP_SEARCH_MAX_STATES))
+        return false;
+    return n_scenes >= 1 && a_max >= 0 && (long long)n_scenes * a_max <= (1ll << 38) / m && (agents || a_max == 0) && price(prm->margin) && car_ok(car);
+}
+
+int pqp_speed_search_device(pqp_handle* h, const pqp_search_params* prm, const pqp_car_geometry* car, int batch, int n, int stride,
+                            const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start,
+                            int m, int n_scenes, int a_max, const double* agents, const int32_t* a_of, const int32_t* scene_of, double* frames,
+                            int32_t* blocked, uint8_t* parents, int32_t* steps, double* traj, double* cost, int32_t* reached, int32_t* flags) {
+    if (!search_ok(h, prm, car, batch, n, stride, paths, profile, v_start, m, n_scenes, a_max, agents, steps, traj, cost, reached, flags) ||
+        !blocked || !parents || (!frames && a_max > 0))
+        return fail(PQP_ERR_INVALID, kSearchRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    double circles[7][3];
+    int rc;
+    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
+    pqp::AgentsArgs fa = {};
+    fa.m = m; fa.n_scenes = n_scenes; fa.a_max = a_max; fa.agents = agents; fa.frames = frames;
+    pqp::SearchArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.m = m; a.n_scenes = n_scenes; a.a_max = a_max; a.paths = paths; a.n_of = n_of;
+    a.stop_before = stop_before; a.profile = profile; a.v_start = v_start; a.a_of = a_of; a.scene_of = scene_of; a.prm = *prm; a.frames = frames;
+    a.blocked = blocked; a.parents = parents; a.steps = steps; a.traj = traj; a.cost = cost; a.reached = reached; a.flags = flags;
+    a.rb = 0.0;
+    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
+    for (int k = 0; k < 6; ++k) a.rb = std::max(a.rb, std::hypot(a.cx[k] - a.cx[6], a.cy[k] - a.cy[6]) + a.cr[k]);      // as pqp_agents_check_device
+    const long long rows = (long long)n_scenes * a_max * m;
+    const long long waves = (long long)batch * ((prm->stations + 63) / 64);
+    constexpr int per_block = pqp::kAgentsThreads / 64;
+    return h->launch_timed([&]() -> int {
+        if (rows > 0) {
+            hipLaunchKernelGGL(pqp::agent_frames_kernel, dim3((unsigned)((rows + pqp::kAgentsThreads - 1) / pqp::kAgentsThreads)),
+                               dim3(pqp::kAgentsThreads), 0, h->stream, fa);
+            PQP_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(pqp::st_occupancy_kernel, dim3((unsigned)((waves + per_block - 1) / per_block)), dim3(pqp::kAgentsThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        hipLaunchKernelGGL(pqp::st_search_kernel, dim3((unsigned)batch), dim3(pqp::kSearchThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_speed_search(pqp_handle* h, const pqp_search_params* prm, const pqp_car_geometry* car, int batch, int n, int stride,
+                     const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start, int m,
+                     int n_scenes, int a_max, const double* agents, const int32_t* a_of, const int32_t* scene_of, int32_t* blocked,
+                     int32_t* steps, double* traj, double* cost, int32_t* reached, int32_t* flags) {
+    if (!search_ok(h, prm, car, batch, n, stride, paths, profile, v_start, m, n_scenes, a_max, agents, steps, traj, cost, reached, flags))
+        return fail(PQP_ERR_INVALID, kSearchRefusal);
+    if (scene_of)
+        for (int b = 0; b < batch; ++b)
+            if (scene_of[b] < 0 || scene_of[b] >= n_scenes) return fail(PQP_ERR_INVALID, "pqp_speed_search: scene_of outside [0, n_scenes)");
+    const size_t bn = (size_t)batch * n, bm = (size_t)batch * m, rows = (size_t)n_scenes * a_max * m;
+    const size_t words = (size_t)(prm->stations + 31) / 32, states = (size_t)prm->stations * (prm->q_max + 1);
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_stop = st.in(stop_before, batch);
+    const double* d_profile = st.in(profile, bn * PQP_SPEED_STRIDE);
+    const double* d_start = st.in(v_start, batch);
+    const double* d_agents = rows ? st.in(agents, rows * PQP_AGENT_STRIDE) : nullptr;
+    const int32_t* d_a_of = st.in(a_of, n_scenes);
+    const int32_t* d_scene_of = st.in(scene_of, batch);
+    double* d_frames = rows ? st.out((double*)nullptr, rows * PQP_AGENT_FRAME_STRIDE) : nullptr;
+    int32_t* d_blocked = st.out(blocked, bm * words);
+    uint8_t* d_parents = st.out((uint8_t*)nullptr, bm * states);
+    int32_t* d_steps = st.out(steps, bm * 2);
+    double* d_traj = st.out(traj, bm * PQP_TRAJ_STRIDE);
+    double* d_cost = st.out(cost, batch);
+    int32_t* d_reached = st.out(reached, batch);
+    int32_t* d_flags = st.out(flags, batch);
+    return st.run([&]() -> int {
+        return pqp_speed_search_device(h, prm, car, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, d_start, m, n_scenes, a_max, d_agents,
+                                       d_a_of, d_scene_of, d_frames, d_blocked, d_parents, d_steps, d_traj, d_cost, d_reached, d_flags);
     });
 }
 

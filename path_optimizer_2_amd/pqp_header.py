@@ -2,7 +2,8 @@
 
 capi.py builds its ctypes classes, constants and argtypes from what read() returns, so the header is the one place the ABI is written
 down.  The header's vocabulary is small (see _statement); whatever falls outside it is refused with a HeaderError, never skipped: a
-declaration this reader does not understand must not become a binding that is silently short of it.
+declaration this reader does not understand must not become a binding that is silently short of it.  A header that pqp.h includes by
+`#include "pqp_x.h"` (pqp_search_params.h) is read too: it may hold struct typedefs and nothing else, and they arrive in Header.included.
 """
 import functools
 import os
@@ -16,7 +17,8 @@ HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__fil
 Struct = namedtuple("Struct", "name fields")
 Param = namedtuple("Param", "name type")
 Function = namedtuple("Function", "name ret params")
-Header = namedtuple("Header", "constants structs opaque functions")     # constants: {name: int}, #defines and enumerators alike
+# constants: {name: int}, #defines and enumerators alike; included: the structs of the headers pqp.h includes (pqp_search_params.h), as structs
+Header = namedtuple("Header", "constants structs opaque functions included")
 
 SCALARS = ("int", "double")
 DATA = ("double", "float", "int32_t", "int", "uint8_t")                 # pointees of the data pointers
@@ -50,8 +52,9 @@ def pointee(ctype):
     return m.group(1), {"": 0, "*": 1}.get(m.group(2), 2)
 
 
-def _preprocessor(text, constants):
-    """takes the # lines out; every one must be the include guard, <stdint.h>, the extern "C" bracket or #define PQP_X <int>"""
+def _preprocessor(text, constants, includes):
+    """takes the # lines out; every one must be the include guard, <stdint.h>, #include "pqp_x.h" (its name goes to `includes`), the
+    extern "C" bracket or #define PQP_X <int>"""
     text, n = re.subn(r'#ifdef __cplusplus\s*(?:extern "C" \{|\})\s*#endif', "", text)
     if n != 2:
         raise HeaderError('expected one opening and one closing extern "C" bracket')
@@ -62,8 +65,11 @@ def _preprocessor(text, constants):
             out.append(line)
             continue
         m = re.fullmatch(rf"#define (PQP_[A-Z_0-9]+)\s+({_INT})", s)
+        inc = re.fullmatch(r'#include "(pqp_[a-z_0-9]+\.h)"', s)
         if m and m.group(1) not in constants:
             constants[m.group(1)] = int(m.group(2))
+        elif inc and inc.group(1) not in includes:
+            includes.append(inc.group(1))
         elif s not in (f"#ifndef {_GUARD}", f"#define {_GUARD}", "#include <stdint.h>", "#endif"):
             raise HeaderError(f"preprocessor line not understood: {s!r}")
     return "\n".join(out)
@@ -107,6 +113,29 @@ def _struct(name, body, structs):
     structs[name] = Struct(name, tuple(fields))
 
 
+def _included(name, include_dir, h):
+    """a header pqp.h includes: its own guard, <stdint.h> and struct typedefs, nothing else; the structs go to h.included"""
+    if include_dir is None:
+        raise HeaderError(f'#include "{name}": no directory to read it from')
+    with open(os.path.join(include_dir, name)) as f:
+        text = strip_comments(f.read())
+    guard = name[:-2].upper() + "_H_"
+    body = []
+    for line in text.split("\n"):
+        s = line.strip()
+        if not s.startswith("#"):
+            body.append(line)
+        elif s not in (f"#ifndef {guard}", f"#define {guard}", "#include <stdint.h>", "#endif"):
+            raise HeaderError(f"{name}: preprocessor line not understood: {s!r}")
+    known = dict(h.structs)
+    for s in _statements("\n".join(body)):
+        m = re.fullmatch(rf"typedef struct ({_NAME}) \{{(.*)\}} \1", s)
+        if not m or m.group(1) in h.included or m.group(1) in h.opaque:
+            raise HeaderError(f"{name}: declaration not understood (struct typedefs only): {s[:120]!r}")
+        _struct(m.group(1), m.group(2), known)
+        h.included[m.group(1)] = known[m.group(1)]
+
+
 def _param(fn, text, h):
     m = re.fullmatch(rf"(.*\W)({_NAME})", text.strip())
     if not m:
@@ -114,7 +143,7 @@ def _param(fn, text, h):
     ctype, name = _norm_type(m.group(1)), m.group(2)
     base, stars = pointee(ctype)
     ok = (stars == 0 and ctype in SCALARS
-          or stars == 1 and (base in DATA or base in h.structs or base in h.opaque or ctype == "void*")
+          or stars == 1 and (base in DATA or base in h.structs or base in h.included or base in h.opaque or ctype == "void*")
           or ctype in ("void**", "double* const*") or (stars == 2 and ctype == base + "**" and base in h.opaque))
     if not ok:
         raise HeaderError(f"{fn}: type of parameter {name} not understood: {ctype!r}")
@@ -143,11 +172,14 @@ def _statement(s, h):
     raise HeaderError(f"declaration not understood: {s[:120]!r}")
 
 
-def parse(text):
-    """Header of a header text.  Raises HeaderError on anything outside the vocabulary."""
-    h = Header({}, {}, [], {})
+def parse(text, include_dir=None):
+    """Header of a header text; include_dir: where the headers it includes lie.  Raises HeaderError on anything outside the vocabulary."""
+    h = Header({}, {}, [], {}, {})
     text = strip_comments(text)
-    body = _preprocessor(text, h.constants)
+    includes = []
+    body = _preprocessor(text, h.constants, includes)
+    for name in includes:
+        _included(name, include_dir, h)
     for s in _statements(body):
         _statement(s, h)
     # the tripwire: every name the text calls like a function was read as one (the count tests/test_capi_symbols.py uses)
@@ -159,7 +191,7 @@ def parse(text):
 
 def read(path=HEADER_PATH):
     with open(path) as f:
-        return parse(f.read())
+        return parse(f.read(), os.path.dirname(path))
 
 
 def class_name(struct):

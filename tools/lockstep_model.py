@@ -36,7 +36,8 @@ T256 = 1.13
 def build_tracing_emulation(tmp):
     for sub in ("path_optimizer_2_amd/csrc", "tests/emu", "include"):
         os.makedirs(os.path.join(tmp, sub))
-    shutil.copy(os.path.join(ROOT, "include", "pqp.h"), os.path.join(tmp, "include"))
+    for f in ("pqp.h", "pqp_search_params.h"):
+        shutil.copy(os.path.join(ROOT, "include", f), os.path.join(tmp, "include"))
     for f in os.listdir(os.path.join(ROOT, "path_optimizer_2_amd", "csrc")):
         if f.endswith(".hpp"):
             shutil.copy(os.path.join(ROOT, "path_optimizer_2_amd", "csrc", f), os.path.join(tmp, "path_optimizer_2_amd", "csrc"))
