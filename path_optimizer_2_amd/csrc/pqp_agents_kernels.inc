@@ -1,6 +1,6 @@
 // pqp_agents_kernels.inc — included by pqp_maps.hip after pqp_sample_kernels.inc.  Sampled trajectories against predicted moving agents
 // (pqp_agents_check): every sample of every trajectory against every agent of the path's scene at the same time step, the six-circle
-// footprint (pqp_car_circles, placed as pqp_footprint_kernels.inc places it) against a rounded oriented rectangle.  The reference has
+// footprint (pqp_car_circles, placed by pqp_footprint_kernels.inc's local_to_global) against a rounded oriented rectangle.  The reference has
 // no counterpart: it plans one path against a static map.  include/pqp.h states the definition operation by operation.
 //
 // agent_frames_kernel: one lane per (scene, agent, step).  The agent's sincos is taken here, once, so the batch x agents x steps tests
@@ -8,9 +8,11 @@
 // agents_check_kernel<CLEARANCE>: one wavefront per path, four per workgroup, one sample per lane in tiles of 64, no LDS, no atomics.
 //   The loop over agents is wave-uniform; lane k reads frame row [a][k], so a wavefront's 64 rows are one contiguous 4 KB, and a scene's
 //   table is read by every path of the scene: it stays in L2.  first_hit is a ballot and a count of trailing zeros, hit_agent is read from
-//   the hit lane.  Without a clearance to write (CLEARANCE = false) a lane leaves out the agents it cannot come within the margin of - by
-//   the centres' distance against Rb + reach + margin + a slack that is orders above the rounding of the exact test - and the agents behind
-//   its first hit, and the wavefront stops behind the tile of its first hit: none of that changes an output.
+//   the hit lane.  Without a clearance to write (CLEARANCE = false) a lane leaves out the agents it cannot come within the margin of
+//   (agent_out_of_reach, whose slack is orders above the rounding of the exact test) and the agents behind its first hit, and the
+//   wavefront stops behind the tile of its first hit: none of that changes an output.
+// agent_clear, the reading of a frame row's reach, the broad phase and the scene's lookup are also st_occupancy_kernel's
+// (pqp_search_kernels.inc).
 
 namespace pqp {
 
@@ -20,26 +22,26 @@ struct AgentsArgs {
     int batch, m, stride, n_scenes, a_max;
     const double* traj;              // [batch][m][stride]  x, y, heading at offsets 0, 1, 2
     const int32_t* m_of;             // [batch] or nullptr: all m
-    const double* agents;            // [n_scenes][a_max][m][PQP_AGENT_STRIDE]
     const int32_t* a_of;             // [n_scenes] or nullptr: all a_max
     const int32_t* scene_of;         // [batch] or nullptr: scene 0
     double margin;
-    double cx[7], cy[7], cr[7];      // vehicle frame: rr, rl, fr, fl, fm, rm, then the bounding circle (pqp_car_circles)
-    double rb;                       // max_j (|c_j - c_6| + r_j): the six circles lie within rb of the bounding circle's centre
+    CarCircles car;
     double* frames;                  // [n_scenes][a_max][m][PQP_AGENT_FRAME_STRIDE]
     int32_t* first_hit;              // [batch]
     int32_t* hit_agent;              // [batch]
     double* clearance;               // [batch][m] or nullptr
 };
 
-// the slack of the broad phase: 2^-10 m and 2^-30 of the coordinates' size, against a rounding of the exact test near 2^-50 of it
-constexpr double kAgentsSlack = 0x1p-10, kAgentsSlackRel = 0x1p-30;
+struct AgentFramesArgs {
+    long long rows;                  // n_scenes * a_max * m
+    const double* agents;            // [rows][PQP_AGENT_STRIDE]
+    double* frames;                  // [rows][PQP_AGENT_FRAME_STRIDE]
+};
 
-__global__ void __launch_bounds__(kAgentsThreads) agent_frames_kernel(const AgentsArgs a) {
+__global__ void __launch_bounds__(kAgentsThreads) agent_frames_kernel(const AgentFramesArgs a) {
 #pragma clang fp contract(off)
-    const long long rows = (long long)a.n_scenes * a.a_max * a.m;
     const long long i = (long long)blockIdx.x * kAgentsThreads + threadIdx.x;
-    if (i >= rows) return;
+    if (i >= a.rows) return;
     const double* __restrict__ r = a.agents + (size_t)i * PQP_AGENT_STRIDE;
     double* __restrict__ o = a.frames + (size_t)i * PQP_AGENT_FRAME_STRIDE;
     double f[PQP_AGENT_FRAME_STRIDE] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, -1.0};
@@ -77,17 +79,42 @@ __device__ __forceinline__ double agent_clear(const double (&gx)[6], const doubl
     return c_ka;
 }
 
+// a frame row's reach, as agent_frames_kernel wrote it: negative - the agent is absent; NaN - its row is bad; else the circumradius
+__device__ __forceinline__ bool agent_absent(double reach) { return reach < 0.0; }
+__device__ __forceinline__ bool agent_bad(double reach) { return !(reach == reach); }
+
+// the slack of the broad phase: 2^-10 m and 2^-30 of the coordinates' size, against a rounding of the exact test near 2^-50 of it
+constexpr double kAgentsSlack = 0x1p-10, kAgentsSlackRel = 0x1p-30;
+
+// the broad phase: the bounding circle's centre (bx, by) is so far from the agent's (ax, ay) that clear(k, a) >= margin + the slack.
+// Leaving such an agent out changes no hit.
+__device__ __forceinline__ bool agent_out_of_reach(double rb, double reach, double margin, double bx, double by, double ax, double ay) {
+#pragma clang fp contract(off)
+    const double ux = bx - ax, uy = by - ay;
+    const double far = rb + reach + margin + kAgentsSlack + kAgentsSlackRel * (fabs(bx) + fabs(by) + fabs(ax) + fabs(ay));
+    return ux * ux + uy * uy > far * far;
+}
+
+// the frames of path b's scene, and in *A how many of its a_max agents count; of an argument struct with scene_of, a_of and frames
+template <class Args>
+__device__ __forceinline__ const double* scene_frames(const Args& a, long long b, int* A) {
+    const int scene = a.scene_of ? min(max(a.scene_of[b], 0), a.n_scenes - 1) : 0;
+    *A = clamped_count(a.a_of, scene, a.a_max);
+    return a.frames + (size_t)scene * a.a_max * a.m * PQP_AGENT_FRAME_STRIDE;
+}
+
 template <bool CLEARANCE>
 __global__ void __launch_bounds__(kAgentsThreads) agents_check_kernel(const AgentsArgs a) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const long long b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kAgentsThreads / 64) + (threadIdx.x >> 6)));
     if (b >= a.batch) return;
-    const int count = a.m_of ? min(max(a.m_of[b], 0), a.m) : a.m;
-    const int scene = a.scene_of ? min(max(a.scene_of[b], 0), a.n_scenes - 1) : 0;
-    const int A = a.a_of ? min(max(a.a_of[scene], 0), a.a_max) : a.a_max;
+    const int count = clamped_count(a.m_of, b, a.m);
+    // (in front of the scene lookup: the traj pointer is then fetched with the frames pointer, one round of argument loads fewer before
+    // the first tile - 0.2 us of a 17 us call, profiles/r19a_path_kernels_speed.txt)
     const double* __restrict__ traj = a.traj + (size_t)b * a.m * a.stride;
-    const double* __restrict__ frames = a.frames + (size_t)scene * a.a_max * a.m * PQP_AGENT_FRAME_STRIDE;
+    int A;
+    const double* __restrict__ frames = scene_frames(a, b, &A);
     const double margin = a.margin;
     int first = count, who = -1;                                                          // wave-uniform
     const int k_end = CLEARANCE ? a.m : count;
@@ -103,27 +130,22 @@ __global__ void __launch_bounds__(kAgentsThreads) agents_check_kernel(const Agen
             if (isfinite(x) && isfinite(y) && isfinite(heading)) {
                 double sh, ch;
                 sincos(heading, &sh, &ch);
-                // local2Global(state, circle): x cos - y sin + ref.x, x sin + y cos + ref.y  (tools.cpp:51-52), as footprint_check_kernel
                 double gx[6], gy[6];
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
-                    gx[j] = a.cx[j] * ch - a.cy[j] * sh + x;
-                    gy[j] = a.cx[j] * sh + a.cy[j] * ch + y;
+                    const Point2 g = local_to_global(a.car.cx[j], a.car.cy[j], sh, ch, x, y);
+                    gx[j] = g.x; gy[j] = g.y;
                 }
-                const double bx = a.cx[6] * ch - a.cy[6] * sh + x, by = a.cx[6] * sh + a.cy[6] * ch + y;
+                const Point2 bp = local_to_global(a.car.cx[6], a.car.cy[6], sh, ch, x, y);
                 const double* f = frames + (size_t)k * PQP_AGENT_FRAME_STRIDE;
                 for (int ag = 0; ag < A; ++ag, f += (size_t)a.m * PQP_AGENT_FRAME_STRIDE) {
                     if (!CLEARANCE && hit) break;                                         // the lowest hitting agent is found
                     const double ax = f[0], ay = f[1], reach = f[7];
-                    if (reach < 0.0) continue;                                            // absent
-                    double c_ka = -INFINITY;                                              // bad: reach is NaN
-                    if (reach == reach) {
-                        if (!CLEARANCE) {
-                            const double ux = bx - ax, uy = by - ay;
-                            const double far = a.rb + reach + margin + kAgentsSlack + kAgentsSlackRel * (fabs(bx) + fabs(by) + fabs(ax) + fabs(ay));
-                            if (ux * ux + uy * uy > far * far) continue;                  // clear(k, a) >= margin + the slack: no hit
-                        }
-                        c_ka = agent_clear(gx, gy, a.cr, ax, ay, f[2], f[3], f[4], f[5], f[6]);
+                    if (agent_absent(reach)) continue;
+                    double c_ka = -INFINITY;                                              // what a bad agent gives
+                    if (!agent_bad(reach)) {
+                        if (!CLEARANCE && agent_out_of_reach(a.car.rb, reach, margin, bp.x, bp.y, ax, ay)) continue;        // no hit
+                        c_ka = agent_clear(gx, gy, a.car.cr, ax, ay, f[2], f[3], f[4], f[5], f[6]);
                     }
                     clear = fmin(clear, c_ka);
                     if (c_ka < margin && !hit) { hit = true; hit_a = ag; }

@@ -14,6 +14,22 @@ namespace pqp {
 
 constexpr int kFootprintThreads = 256;
 
+// The car's circles as the kernels take them, filled by car_circles_of (pqp_maps.hip) from a pqp_car_geometry.  rb is the broad phase's
+// radius (pqp_agents_kernels.inc): the reference's own bounding circle (cr[6]) does not contain the corner circles, rb does.
+struct CarCircles {
+    double cx[7], cy[7], cr[7];      // vehicle frame: rr, rl, fr, fl, fm, rm, then the bounding circle (pqp_car_circles)
+    double rb;                       // max_j (|c_j - c_6| + r_j): the six circles lie within rb of the bounding circle's centre
+};
+
+struct Point2 { double x, y; };
+
+// local2Global(state, circle): x cos - y sin + ref.x, x sin + y cos + ref.y  (tools.cpp:51-52): one circle's centre (cx, cy) of the
+// vehicle frame at the pose (x, y) with its heading's sine and cosine
+__device__ __forceinline__ Point2 local_to_global(double cx, double cy, double sh, double ch, double x, double y) {
+#pragma clang fp contract(off)
+    return {cx * ch - cy * sh + x, cx * sh + cy * ch + y};
+}
+
 struct FootprintArgs {
     int batch, n, stride;
     const double* states;            // [batch][n][stride]  x, y, heading at offsets 0, 1, 2
@@ -21,7 +37,7 @@ struct FootprintArgs {
     const float* dist;               // [n_maps][cols][rows]  as for CorridorArgs
     const int32_t* map_of;           // [batch] or nullptr: map 0
     pqp_grid_geometry g;
-    double cx[7], cy[7], cr[7];      // vehicle frame: rr, rl, fr, fl, fm, rm, then the bounding circle (pqp_car_circles)
+    CarCircles car;
     uint8_t* free_out;               // [batch][n]
     int32_t* first_collision;        // [batch]
     double* margin;                  // [batch][n] or nullptr
@@ -41,7 +57,7 @@ __global__ void __launch_bounds__(kFootprintThreads) footprint_check_kernel(cons
 #pragma clang fp contract(off)
     __shared__ int wave_first[kFootprintThreads / 64];
     const int b = blockIdx.x, wave = threadIdx.x >> 6;
-    const int nb = a.n_of ? min(max(a.n_of[b], 0), a.n) : a.n;
+    const int nb = clamped_count(a.n_of, b, a.n);
     const float* __restrict__ dist = a.dist + (size_t)(a.map_of ? a.map_of[b] : 0) * a.g.rows * a.g.cols;
     const double* st = a.states + (size_t)b * a.n * a.stride;
     int first = INT_MAX;                                                     // wave-uniform: the wavefront's first colliding index
@@ -53,14 +69,12 @@ __global__ void __launch_bounds__(kFootprintThreads) footprint_check_kernel(cons
             const double x = st[(size_t)i * a.stride], y = st[(size_t)i * a.stride + 1], heading = st[(size_t)i * a.stride + 2];
             double sh, ch;
             sincos(heading, &sh, &ch);
-            // local2Global(current, circle): x cos - y sin + ref.x, x sin + y cos + ref.y  (tools.cpp:51-52)
-            auto gx = [&](int k) { return a.cx[k] * ch - a.cy[k] * sh + x; };
-            auto gy = [&](int k) { return a.cx[k] * sh + a.cy[k] * ch + y; };
+            const auto place = [&](int k) { return local_to_global(a.car.cx[k], a.car.cy[k], sh, ch, x, y); };      // a circle where it is asked for
             bool bound_in = true, exact = true;
             if (MODE == PQP_FOOTPRINT_BOUNDING_FIRST) {
-                const double bx = gx(6), by = gy(6);
-                bound_in = map_is_inside(a.g, bx, by);
-                exact = bound_in && obstacle_distance(dist, a.g, bx, by) < a.cr[6];          // :49-53: the big circle is not clear
+                const Point2 bp = place(6);
+                bound_in = map_is_inside(a.g, bp.x, bp.y);
+                exact = bound_in && obstacle_distance(dist, a.g, bp.x, bp.y) < a.car.cr[6];  // :49-53: the big circle is not clear
             }
             bool six = false;
             if (exact || a.margin) {
@@ -68,15 +82,15 @@ __global__ void __launch_bounds__(kFootprintThreads) footprint_check_kernel(cons
                 bool in[6];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
-                    const double px = gx(k), py = gy(k);
-                    in[k] = map_is_inside(a.g, px, py);
-                    d[k] = obstacle_distance(dist, a.g, px, py);                             // Map::getObstacleDistance: 0 outside
+                    const Point2 pk = place(k);
+                    in[k] = map_is_inside(a.g, pk.x, pk.y);
+                    d[k] = obstacle_distance(dist, a.g, pk.x, pk.y);                         // Map::getObstacleDistance: 0 outside
                 }
-                mg = d[0] - a.cr[0];
+                mg = d[0] - a.car.cr[0];
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
-                    six = six || !in[k] || d[k] < a.cr[k];                                    // :28-35
-                    const double v = d[k] - a.cr[k];
+                    six = six || !in[k] || d[k] < a.car.cr[k];                                // :28-35
+                    const double v = d[k] - a.car.cr[k];
                     mg = v < mg ? v : mg;
                 }
             }

@@ -20,6 +20,7 @@
 #include "pqp_defaults.hpp"
 #include "pqp_path_lane.hpp"
 #include "pqp_wave.hpp"
+#include "pqp_driven_path.hpp"
 #include "pqp_line_device.hpp"
 #include "pqp_internal.hpp"
 
@@ -32,6 +33,42 @@ using namespace pqp_internal;
 #include "pqp_sample_kernels.inc"
 #include "pqp_agents_kernels.inc"
 #include "pqp_search_kernels.inc"
+
+// ---- what the entry points below share ------------------------------------------------------------------------------------------------
+// the grid of a kernel that gives every item a wavefront, threads / 64 of them to a workgroup
+static dim3 wave_grid(long long items, int threads) {
+    const int per_block = threads / 64;
+    return dim3((unsigned)((items + per_block - 1) / per_block));
+}
+
+// an optional index array of a host form: every entry inside [0, count), or the refusal `what`
+static int index_range(const int32_t* of, int batch, int count, const char* what) {
+    if (of)
+        for (int b = 0; b < batch; ++b)
+            if (of[b] < 0 || of[b] >= count) return fail(PQP_ERR_INVALID, what);
+    return PQP_OK;
+}
+
+// the car's circles as the kernels take them
+static int car_circles_of(const pqp_car_geometry* car, pqp::CarCircles* c) {
+    double circles[7][3];
+    if (const int rc = pqp_car_circles(car, &circles[0][0])) return rc;
+    for (int k = 0; k < 7; ++k) { c->cx[k] = circles[k][0]; c->cy[k] = circles[k][1]; c->cr[k] = circles[k][2]; }
+    // the reference's own bounding circle (circles[6][2]) does not contain the corner circles: the broad phase takes the radius that does
+    c->rb = 0.0;
+    for (int k = 0; k < 6; ++k) c->rb = std::max(c->rb, std::hypot(c->cx[k] - c->cx[6], c->cy[k] - c->cy[6]) + c->cr[k]);
+    return PQP_OK;
+}
+
+// agent_frames_kernel over every (scene, agent, step) row, inside a launch_timed
+static int launch_agent_frames(pqp_handle* h, int n_scenes, int a_max, int m, const double* agents, double* frames) {
+    const pqp::AgentFramesArgs fa = {(long long)n_scenes * a_max * m, agents, frames};
+    if (fa.rows == 0) return PQP_OK;
+    hipLaunchKernelGGL(pqp::agent_frames_kernel, dim3((unsigned)((fa.rows + pqp::kAgentsThreads - 1) / pqp::kAgentsThreads)),
+                       dim3(pqp::kAgentsThreads), 0, h->stream, fa);
+    PQP_HIP(hipGetLastError());
+    return PQP_OK;
+}
 
 extern "C" {
 
@@ -119,12 +156,9 @@ int pqp_footprint_check_device(pqp_handle* h, int batch, int n, int stride, cons
         return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument (stride >= 3; a finite car geometry; mode CIRCLES or BOUNDING_FIRST; "
                                      "a map layer of 2 x 2 to 2^30 cells)");
     PQP_HIP(hipSetDevice(h->device));
-    double circles[7][3];
-    int rc;
-    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
     pqp::FootprintArgs a;
+    if (const int rc = car_circles_of(car, &a.car)) return rc;
     a.batch = batch; a.n = n; a.stride = stride; a.states = states; a.n_of = n_of; a.dist = dist; a.map_of = map_of; a.g = *geom;
-    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
     a.free_out = free_out; a.first_collision = first_collision; a.margin = margin;
     return h->launch_timed([&]() -> int {
         if (mode == PQP_FOOTPRINT_CIRCLES)
@@ -141,9 +175,7 @@ int pqp_footprint_check(pqp_handle* h, int batch, int n, int stride, const doubl
                         int32_t* first_collision, double* margin) {
     if (!footprint_ok(h, batch, n, stride, states, dist, geom, car, mode, free_out, first_collision) || n_maps < 1)
         return fail(PQP_ERR_INVALID, "pqp_footprint_check: bad argument");
-    if (map_of)
-        for (int b = 0; b < batch; ++b)
-            if (map_of[b] < 0 || map_of[b] >= n_maps) return fail(PQP_ERR_INVALID, "pqp_footprint_check: map_of outside [0, n_maps)");
+    if (const int rc = index_range(map_of, batch, n_maps, "pqp_footprint_check: map_of outside [0, n_maps)")) return rc;
     const size_t bn = (size_t)batch * n;
     Staging st(h);
     const double* d_states = st.in(states, bn * stride);
@@ -189,12 +221,11 @@ int pqp_select_paths_device(pqp_handle* h, const pqp_select_params* prm, int bat
     a.batch = batch; a.n = n; a.stride = stride; a.groups = groups; a.paths = paths; a.n_of = n_of; a.status = status; a.stage = stage;
     a.first_collision = first_collision; a.margin = margin; a.group_start = group_start; a.prm = *prm; a.terms = terms; a.best = best;
     a.best_paths = best_paths; a.best_n = best_n;
-    constexpr int per_block = pqp::kSelectThreads / 64;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::path_score_kernel, dim3((unsigned)((batch + per_block - 1) / per_block)), dim3(pqp::kSelectThreads), 0, h->stream, a);
+        hipLaunchKernelGGL(pqp::path_score_kernel, wave_grid(batch, pqp::kSelectThreads), dim3(pqp::kSelectThreads), 0, h->stream, a);
         PQP_HIP(hipGetLastError());
         if (groups > 0) {
-            hipLaunchKernelGGL(pqp::group_select_kernel, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(pqp::kSelectThreads), 0, h->stream, a);
+            hipLaunchKernelGGL(pqp::group_select_kernel, wave_grid(groups, pqp::kSelectThreads), dim3(pqp::kSelectThreads), 0, h->stream, a);
             PQP_HIP(hipGetLastError());
         }
         return PQP_OK;
@@ -259,10 +290,8 @@ int pqp_speed_profile_device(pqp_handle* h, const pqp_speed_params* prm, int bat
     pqp::SpeedArgs a;
     a.batch = batch; a.n = n; a.stride = stride; a.paths = paths; a.n_of = n_of; a.stop_before = stop_before; a.v_limit = v_limit;
     a.v_start = v_start; a.v_end = v_end; a.prm = *prm; a.profile = profile; a.flags = flags;
-    constexpr int per_block = pqp::kSpeedThreads / 64;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::speed_profile_kernel, dim3((unsigned)(((long long)batch + per_block - 1) / per_block)), dim3(pqp::kSpeedThreads), 0,
-                           h->stream, a);
+        hipLaunchKernelGGL(pqp::speed_profile_kernel, wave_grid(batch, pqp::kSpeedThreads), dim3(pqp::kSpeedThreads), 0, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -312,10 +341,8 @@ int pqp_sample_trajectory_device(pqp_handle* h, const pqp_sample_params* prm, in
     pqp::SampleArgs a;
     a.batch = batch; a.n = n; a.stride = stride; a.m = m; a.paths = paths; a.n_of = n_of; a.stop_before = stop_before; a.profile = profile;
     a.t0 = t0; a.prm = *prm; a.traj = traj; a.m_of = m_of; a.flags = flags;
-    constexpr int per_block = pqp::kSampleThreads / 64;
     return h->launch_timed([&]() -> int {
-        hipLaunchKernelGGL(pqp::sample_trajectory_kernel, dim3((unsigned)(((long long)batch + per_block - 1) / per_block)), dim3(pqp::kSampleThreads),
-                           0, h->stream, a);
+        hipLaunchKernelGGL(pqp::sample_trajectory_kernel, wave_grid(batch, pqp::kSampleThreads), dim3(pqp::kSampleThreads), 0, h->stream, a);
         PQP_HIP(hipGetLastError());
         return PQP_OK;
     });
@@ -363,26 +390,14 @@ int pqp_agents_check_device(pqp_handle* h, double margin, const pqp_car_geometry
     if (!agents_ok(h, margin, car, batch, m, stride, traj, n_scenes, a_max, agents, first_hit, hit_agent) || (!frames && a_max > 0))
         return fail(PQP_ERR_INVALID, kAgentsRefusal);
     PQP_HIP(hipSetDevice(h->device));
-    double circles[7][3];
-    int rc;
-    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
     pqp::AgentsArgs a;
-    a.batch = batch; a.m = m; a.stride = stride; a.n_scenes = n_scenes; a.a_max = a_max; a.traj = traj; a.m_of = m_of; a.agents = agents;
+    if (const int rc = car_circles_of(car, &a.car)) return rc;
+    a.batch = batch; a.m = m; a.stride = stride; a.n_scenes = n_scenes; a.a_max = a_max; a.traj = traj; a.m_of = m_of;
     a.a_of = a_of; a.scene_of = scene_of; a.margin = margin; a.frames = frames; a.first_hit = first_hit; a.hit_agent = hit_agent;
     a.clearance = clearance;
-    a.rb = 0.0;
-    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
-    // the reference's own bounding circle (circles[6][2]) does not contain the corner circles: the broad phase takes the radius that does
-    for (int k = 0; k < 6; ++k) a.rb = std::max(a.rb, std::hypot(a.cx[k] - a.cx[6], a.cy[k] - a.cy[6]) + a.cr[k]);
-    const long long rows = (long long)n_scenes * a_max * m;
-    constexpr int per_block = pqp::kAgentsThreads / 64;
     return h->launch_timed([&]() -> int {
-        if (rows > 0) {
-            hipLaunchKernelGGL(pqp::agent_frames_kernel, dim3((unsigned)((rows + pqp::kAgentsThreads - 1) / pqp::kAgentsThreads)),
-                               dim3(pqp::kAgentsThreads), 0, h->stream, a);
-            PQP_HIP(hipGetLastError());
-        }
-        const dim3 grid((unsigned)(((long long)batch + per_block - 1) / per_block));
+        if (const int rc = launch_agent_frames(h, n_scenes, a_max, m, agents, frames)) return rc;
+        const dim3 grid = wave_grid(batch, pqp::kAgentsThreads);
         if (clearance) hipLaunchKernelGGL(pqp::agents_check_kernel<true>, grid, dim3(pqp::kAgentsThreads), 0, h->stream, a);
         else hipLaunchKernelGGL(pqp::agents_check_kernel<false>, grid, dim3(pqp::kAgentsThreads), 0, h->stream, a);
         PQP_HIP(hipGetLastError());
@@ -394,9 +409,7 @@ int pqp_agents_check(pqp_handle* h, double margin, const pqp_car_geometry* car, 
                      const double* traj, const int32_t* m_of, int n_scenes, int a_max, const double* agents, const int32_t* a_of,
                      const int32_t* scene_of, int32_t* first_hit, int32_t* hit_agent, double* clearance) {
     if (!agents_ok(h, margin, car, batch, m, stride, traj, n_scenes, a_max, agents, first_hit, hit_agent)) return fail(PQP_ERR_INVALID, kAgentsRefusal);
-    if (scene_of)
-        for (int b = 0; b < batch; ++b)
-            if (scene_of[b] < 0 || scene_of[b] >= n_scenes) return fail(PQP_ERR_INVALID, "pqp_agents_check: scene_of outside [0, n_scenes)");
+    if (const int rc = index_range(scene_of, batch, n_scenes, "pqp_agents_check: scene_of outside [0, n_scenes)")) return rc;
     const size_t bm = (size_t)batch * m, rows = (size_t)n_scenes * a_max * m;
     Staging st(h);
     const double* d_traj = st.in(traj, bm * stride);
@@ -466,28 +479,15 @@ int pqp_speed_search_device(pqp_handle* h, const pqp_search_params* prm, const p
         !blocked || !parents || (!frames && a_max > 0))
         return fail(PQP_ERR_INVALID, kSearchRefusal);
     PQP_HIP(hipSetDevice(h->device));
-    double circles[7][3];
-    int rc;
-    if ((rc = pqp_car_circles(car, &circles[0][0]))) return rc;
-    pqp::AgentsArgs fa = {};
-    fa.m = m; fa.n_scenes = n_scenes; fa.a_max = a_max; fa.agents = agents; fa.frames = frames;
     pqp::SearchArgs a;
+    if (const int rc = car_circles_of(car, &a.car)) return rc;
     a.batch = batch; a.n = n; a.stride = stride; a.m = m; a.n_scenes = n_scenes; a.a_max = a_max; a.paths = paths; a.n_of = n_of;
     a.stop_before = stop_before; a.profile = profile; a.v_start = v_start; a.a_of = a_of; a.scene_of = scene_of; a.prm = *prm; a.frames = frames;
     a.blocked = blocked; a.parents = parents; a.steps = steps; a.traj = traj; a.cost = cost; a.reached = reached; a.flags = flags;
-    a.rb = 0.0;
-    for (int k = 0; k < 7; ++k) { a.cx[k] = circles[k][0]; a.cy[k] = circles[k][1]; a.cr[k] = circles[k][2]; }
-    for (int k = 0; k < 6; ++k) a.rb = std::max(a.rb, std::hypot(a.cx[k] - a.cx[6], a.cy[k] - a.cy[6]) + a.cr[k]);      // as pqp_agents_check_device
-    const long long rows = (long long)n_scenes * a_max * m;
     const long long waves = (long long)batch * ((prm->stations + 63) / 64);
-    constexpr int per_block = pqp::kAgentsThreads / 64;
     return h->launch_timed([&]() -> int {
-        if (rows > 0) {
-            hipLaunchKernelGGL(pqp::agent_frames_kernel, dim3((unsigned)((rows + pqp::kAgentsThreads - 1) / pqp::kAgentsThreads)),
-                               dim3(pqp::kAgentsThreads), 0, h->stream, fa);
-            PQP_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(pqp::st_occupancy_kernel, dim3((unsigned)((waves + per_block - 1) / per_block)), dim3(pqp::kAgentsThreads), 0, h->stream, a);
+        if (const int rc = launch_agent_frames(h, n_scenes, a_max, m, agents, frames)) return rc;
+        hipLaunchKernelGGL(pqp::st_occupancy_kernel, wave_grid(waves, pqp::kAgentsThreads), dim3(pqp::kAgentsThreads), 0, h->stream, a);
         PQP_HIP(hipGetLastError());
         hipLaunchKernelGGL(pqp::st_search_kernel, dim3((unsigned)batch), dim3(pqp::kSearchThreads), 0, h->stream, a);
         PQP_HIP(hipGetLastError());
@@ -501,9 +501,7 @@ int pqp_speed_search(pqp_handle* h, const pqp_search_params* prm, const pqp_car_
                      int32_t* steps, double* traj, double* cost, int32_t* reached, int32_t* flags) {
     if (!search_ok(h, prm, car, batch, n, stride, paths, profile, v_start, m, n_scenes, a_max, agents, steps, traj, cost, reached, flags))
         return fail(PQP_ERR_INVALID, kSearchRefusal);
-    if (scene_of)
-        for (int b = 0; b < batch; ++b)
-            if (scene_of[b] < 0 || scene_of[b] >= n_scenes) return fail(PQP_ERR_INVALID, "pqp_speed_search: scene_of outside [0, n_scenes)");
+    if (const int rc = index_range(scene_of, batch, n_scenes, "pqp_speed_search: scene_of outside [0, n_scenes)")) return rc;
     const size_t bn = (size_t)batch * n, bm = (size_t)batch * m, rows = (size_t)n_scenes * a_max * m;
     const size_t words = (size_t)(prm->stations + 31) / 32, states = (size_t)prm->stations * (prm->q_max + 1);
     Staging st(h);

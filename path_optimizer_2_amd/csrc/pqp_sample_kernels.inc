@@ -4,13 +4,12 @@
 // reference has no counterpart (nothing fills State::v there).  include/pqp.h states the definition operation by operation.
 //
 // sample_trajectory_kernel: one wavefront per path, four per workgroup, no LDS, no atomics.
-//   1  tiles of 64 waypoints ascending: every value below the driven count is judged (a ballot decides for the path), and the running
-//      maximum of the t column - a DPP prefix minimum of -t, which is exact - gives the arrival time T_{c-1}
-//   2  tiles of 64 samples ascending, one sample per lane.  tau and T both ascend, so the t column is walked forward by a wave-uniform
-//      cursor: a tile of it is taken while its last T is <= the sample tile's last tau, and the next sample tile starts at the tile the
-//      previous one ended in.  In a waypoint tile a lane counts the T_j <= tau by a binary search across the lanes (seven steps of
-//      __shfl), which with a monotone T is the count the definition asks for.  Then it gathers its segment's two rows - read a moment
-//      ago by step 1, so they come from this CU's cache or L2 - and writes its row of eight doubles.
+//   1  tiles of 64 waypoints ascending: every value below the driven count is judged (row_not_finite of pqp_driven_path.hpp and this
+//      kernel's own terms on t and t0; a ballot decides for the path), and the maximum of the t column gives the arrival time T_{c-1}
+//   2  tiles of 64 samples ascending, one sample per lane.  tau and T both ascend, so the t column is walked forward (walk_tile of
+//      pqp_driven_path.hpp) by a wave-uniform cursor: a tile of it is taken while its last T is <= the sample tile's last tau, and the
+//      next sample tile starts at the tile the previous one ended in.  Then a lane gathers its segment's two rows - read a moment ago
+//      by step 1, so they come from this CU's cache or L2 - places itself on the chord (chord_pose) and writes its row of eight doubles.
 // A sample's operations depend on its path's driven rows, t0, dt and k alone.
 
 namespace pqp {
@@ -35,8 +34,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_trajectory_kernel(const
     const int lane = threadIdx.x & 63;
     const long long b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kSampleThreads / 64) + (threadIdx.x >> 6)));
     if (b >= a.batch) return;
-    const int count = a.n_of ? min(max(a.n_of[b], 0), a.n) : a.n;
-    const int c = a.stop_before ? min(count, max(a.stop_before[b], 0)) : count;
+    const int c = driven_count(clamped_count(a.n_of, b, a.n), a.stop_before, b);
     const long long cells = (long long)a.m * PQP_TRAJ_STRIDE;
     double* traj = a.traj + (size_t)b * a.m * PQP_TRAJ_STRIDE;
     if (c == 0) {                                                                         // nothing is read, t0 neither
@@ -59,8 +57,7 @@ __global__ void __launch_bounds__(kSampleThreads) sample_trajectory_kernel(const
             const double* r = p + (size_t)j * a.stride;
             const double* o = prof + (size_t)j * PQP_SPEED_STRIDE;
             t = o[3];
-            bad = bad || !isfinite(r[0]) || !isfinite(r[1]) || !isfinite(r[2]) || !isfinite(r[5]) || !isfinite(o[0]) || !isfinite(o[1]) ||
-                  !isfinite(o[2]) || !(t >= 0.0);
+            bad = bad || row_not_finite(r, o) || !(t >= 0.0);
         }
         t_arrive = fmax(t_arrive, wave_max(t));
     }
@@ -87,19 +84,8 @@ __global__ void __launch_bounds__(kSampleThreads) sample_trajectory_kernel(const
         int w = wt;
         double cw = carry;
         while (w * 64 < c) {
-            const int j = w * 64 + lane;
-            const int nv = min(64, c - w * 64);
-            const double neg = j < c ? -prof[(size_t)j * PQP_SPEED_STRIDE + 3] : INFINITY;
-            const double T = fmax(cw, -wave_prefix_min(neg));                             // lanes behind the count repeat the last T
-            int pos = 0;                                                                  // #{ j in this tile : T_j <= tau }
-#pragma unroll
-            for (int step = 64; step >= 1; step >>= 1) {
-                const int at = pos + step - 1;
-                const double Tv = __shfl(T, at & 63);
-                if (at < nv && Tv <= tau) pos += step;
-            }
-            cnt += pos;
-            const double T_end = wave_read<63>(T);
+            double T_end;
+            cnt += walk_tile(prof, 3, c, w, cw, tau, lane, &T_end);                       // #{ j in this tile : T_j <= tau }
             if (!(T_end <= tau_hi)) break;
             ++w; cw = T_end;
             wt = w; carry = cw;
@@ -109,27 +95,20 @@ __global__ void __launch_bounds__(kSampleThreads) sample_trajectory_kernel(const
         const int i = max(cnt - 1, 0);           // (cnt = 0 only where the t column does not start at 0 and tau lies in front of it)
         double row[PQP_TRAJ_STRIDE] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (on && i < c - 1) {
-            const double* r0 = p + (size_t)i * a.stride;
-            const double* r1 = r0 + a.stride;
             const double* o0 = prof + (size_t)i * PQP_SPEED_STRIDE;
-            const double x0 = r0[0], y0 = r0[1], h0 = r0[2], c0 = r0[5], x1 = r1[0], y1 = r1[1], h1 = r1[2], c1 = r1[5];
             const double s0 = o0[0], v0 = o0[1], a0 = o0[2], ti = o0[3], t_next = o0[PQP_SPEED_STRIDE + 3];
             stands = stands || fmax(ti, t_next) == INFINITY;                          // T_{i+1}: T_i <= tau is finite here
-            const double dx = x1 - x0, dy = y1 - y0;
-            const double d = sqrt(dx * dx + dy * dy);
             const double u = tau - ti;
-            const double e = fmin(fmax((v0 + (0.5 * a0) * u) * u, 0.0), d);
-            const double lam = d > 0.0 ? e / d : 0.0;
-            row[0] = x0 + lam * dx;
-            row[1] = y0 + lam * dy;
-            row[2] = constrain_angle(h0 + lam * constrain_angle(h1 - h0));
-            row[3] = c0 + lam * (c1 - c0);
+            double e;
+            const PathPose at = chord_pose(p + (size_t)i * a.stride, a.stride, (v0 + (0.5 * a0) * u) * u, &e);
+            row[0] = at.x; row[1] = at.y; row[2] = at.heading; row[3] = at.k;
             row[4] = s0 + e;
             row[5] = fmax(v0 + a0 * u, 0.0);
             row[6] = a0;
             row[7] = tau;
         } else if (on || (valid && a.prm.hold_last)) {                                    // the last driven waypoint itself; behind it: at rest
-            row[0] = last[0]; row[1] = last[1]; row[2] = last[2]; row[3] = last[5]; row[4] = last_o[0];
+            const PathPose at = waypoint_pose(last);
+            row[0] = at.x; row[1] = at.y; row[2] = at.heading; row[3] = at.k; row[4] = last_o[0];
             row[5] = on ? v_last : 0.0;
             row[7] = tau;
         }

@@ -4,13 +4,14 @@
 //
 // agent_frames_kernel (pqp_agents_kernels.inc) runs first, as it is.
 // st_occupancy_kernel: one wavefront per (path, tile of 64 stations), four per workgroup, one station per lane, no LDS, no atomics.
-//   1  tiles of 64 waypoints: every value below the driven count is judged, and the maximum of the s column is M_{c-1}
-//   2  the lanes' segments, by pqp_sample_trajectory's walk: the running maximum of the s column per waypoint tile (a DPP prefix minimum
-//      of -s, exact) and a binary search across the lanes; then the pose, its sincos once, the six centres in registers, and qenv_j, which
-//      goes as a byte into layer 0 of `parents` - the search has no parents at layer 0 - because the search kernel's LDS is full
+//   1  tiles of 64 waypoints: every value below the driven count is judged (row_not_finite of pqp_driven_path.hpp, and v_start), and the
+//      maximum of the s column is M_{c-1}
+//   2  the lanes' segments, by the walk pqp_sample_trajectory takes (walk_tile), here on the s column and from tile 0; then the pose on
+//      the chord (chord_pose), its sincos once, the six centres in registers (local_to_global), and qenv_j, which goes as a byte into
+//      layer 0 of `parents` - the search has no parents at layer 0 - because the search kernel's LDS is full
 //   3  the loops over layers and agents are wave-uniform: a frame row's address is the same for the whole wavefront.  A layer's 64 answers
-//      are one ballot, stored as two words by lane 0.  An agent is left out by the centres' distance under pqp_agents_check's bound
-//      (Rb, the slack), which changes no output.
+//      are one ballot, stored as two words by lane 0.  An agent is left out by pqp_agents_check's broad phase (agent_out_of_reach),
+//      which changes no output.
 // st_search_kernel: one workgroup of 256 per path, the two cost layers [S][Q + 1] ping-pong in 64 KiB of LDS, one barrier per layer.
 //   qref_j, a byte per station, goes behind qenv into layer 0 of `parents`.  A lane runs over the states (j, q) of a layer and pulls from
 //   (j - q, q'); the swept range test is a mask over at most three words of `blocked`.  Every lane keeps the best state, by the terminal rule, of the last layer in which one of its own states lived: the
@@ -33,7 +34,7 @@ struct SearchArgs {
     const int32_t* a_of;             // [n_scenes] or nullptr
     const int32_t* scene_of;         // [batch] or nullptr
     pqp_search_params prm;
-    double cx[7], cy[7], cr[7], rb;  // as AgentsArgs
+    CarCircles car;
     const double* frames;            // [n_scenes][a_max][m][PQP_AGENT_FRAME_STRIDE]
     int32_t* blocked;                // [batch][m][W]
     uint8_t* parents;                // [batch][m][S][Q + 1]
@@ -43,11 +44,6 @@ struct SearchArgs {
     int32_t* reached;                // [batch]
     int32_t* flags;                  // [batch]
 };
-
-__device__ __forceinline__ int st_driven(const SearchArgs& a, long long b) {
-    const int count = a.n_of ? min(max(a.n_of[b], 0), a.n) : a.n;
-    return a.stop_before ? min(count, max(a.stop_before[b], 0)) : count;
-}
 
 // step 1, by a whole wavefront: whether a value read below the driven count is not what it must be, and M_{c-1}
 __device__ __forceinline__ bool st_judge(const SearchArgs& a, long long b, int c, int lane, double* m_last) {
@@ -63,7 +59,7 @@ __device__ __forceinline__ bool st_judge(const SearchArgs& a, long long b, int c
             const double* r = p + (size_t)i * a.stride;
             const double* o = prof + (size_t)i * PQP_SPEED_STRIDE;
             s = o[0];
-            bad = bad || !isfinite(r[0]) || !isfinite(r[1]) || !isfinite(r[2]) || !isfinite(r[5]) || !isfinite(s) || !isfinite(o[1]) || !isfinite(o[2]);
+            bad = bad || row_not_finite(r, o);
         }
         top = fmax(top, wave_max(s));
     }
@@ -71,58 +67,35 @@ __device__ __forceinline__ bool st_judge(const SearchArgs& a, long long b, int c
     return __ballot(bad) != 0;
 }
 
-// #{ i' < c : M_i' <= sigma } for the sigma of every lane, by a whole wavefront (lanes with nothing to place pass -inf)
+// #{ i' < c : M_i' <= sigma } for the sigma of every lane, by a whole wavefront (lanes with nothing to place pass -inf): the s column
+// walked from tile 0 until a tile ends above every lane's sigma
 __device__ __forceinline__ int st_count(const double* __restrict__ prof, int c, double sigma, int lane) {
     const double sigma_hi = wave_max(sigma);
     int cnt = 0;
     double carry = -INFINITY;
     for (int w = 0; w * 64 < c; ++w) {
-        const int i = w * 64 + lane;
-        const int nv = min(64, c - w * 64);
-        const double neg = i < c ? -prof[(size_t)i * PQP_SPEED_STRIDE] : INFINITY;
-        const double M = fmax(carry, -wave_prefix_min(neg));                              // lanes behind the count repeat the last M
-        int pos = 0;                                                                      // #{ i' in this tile : M_i' <= sigma }
-#pragma unroll
-        for (int step = 64; step >= 1; step >>= 1) {
-            const int at = pos + step - 1;
-            const double Mv = __shfl(M, at & 63);
-            if (at < nv && Mv <= sigma) pos += step;
-        }
-        cnt += pos;
-        carry = wave_read<63>(M);
+        cnt += walk_tile(prof, 0, c, w, carry, sigma, lane, &carry);
         if (!(carry <= sigma_hi)) break;
     }
     return cnt;
 }
 
-struct StPose { double x, y, heading, k, w; };              // w: the envelope's v^2
-
-__device__ __forceinline__ StPose st_pose(const double* __restrict__ p, const double* __restrict__ prof, int stride, int c, int cnt, double sigma) {
+// the pose at sigma, cnt waypoints at or in front of it, and *w, the envelope's v^2 there
+__device__ __forceinline__ PathPose st_pose(const double* __restrict__ p, const double* __restrict__ prof, int stride, int c, int cnt, double sigma,
+                                            double* w) {
 #pragma clang fp contract(off)
     const int i = max(cnt - 1, 0);
-    StPose o;
     if (i < c - 1) {
-        const double* r0 = p + (size_t)i * stride;
-        const double* r1 = r0 + stride;
         const double* o0 = prof + (size_t)i * PQP_SPEED_STRIDE;
-        const double x0 = r0[0], y0 = r0[1], h0 = r0[2], c0 = r0[5], x1 = r1[0], y1 = r1[1], h1 = r1[2], c1 = r1[5];
         const double s0 = o0[0], v0 = o0[1], a0 = o0[2];
-        const double dx = x1 - x0, dy = y1 - y0;
-        const double d = sqrt(dx * dx + dy * dy);
-        const double e = fmin(fmax(sigma - s0, 0.0), d);
-        const double lam = d > 0.0 ? e / d : 0.0;
-        o.x = x0 + lam * dx;
-        o.y = y0 + lam * dy;
-        o.heading = constrain_angle(h0 + lam * constrain_angle(h1 - h0));
-        o.k = c0 + lam * (c1 - c0);
-        o.w = v0 * v0 + (2.0 * a0) * e;
-    } else {
-        const double* r = p + (size_t)(c - 1) * stride;
-        const double v = prof[(size_t)(c - 1) * PQP_SPEED_STRIDE + 1];
-        o.x = r[0]; o.y = r[1]; o.heading = r[2]; o.k = r[5];
-        o.w = v * v;
+        double e;
+        const PathPose o = chord_pose(p + (size_t)i * stride, stride, sigma - s0, &e);
+        *w = v0 * v0 + (2.0 * a0) * e;
+        return o;
     }
-    return o;
+    const double v = prof[(size_t)(c - 1) * PQP_SPEED_STRIDE + 1];
+    *w = v * v;
+    return waypoint_pose(p + (size_t)(c - 1) * stride);
 }
 
 __global__ void __launch_bounds__(kAgentsThreads) st_occupancy_kernel(const SearchArgs a) {
@@ -133,7 +106,7 @@ __global__ void __launch_bounds__(kAgentsThreads) st_occupancy_kernel(const Sear
     const long long b = __builtin_amdgcn_readfirstlane((int)(wave / tiles));
     const int tile = __builtin_amdgcn_readfirstlane((int)(wave % tiles));
     if (b >= a.batch) return;
-    const int c = st_driven(a, b);
+    const int c = driven_count(clamped_count(a.n_of, b, a.n), a.stop_before, b);
     int32_t* __restrict__ blk = a.blocked + (size_t)b * a.m * W + 2 * tile;               // this tile's word pair of layer 0
     const bool second = 2 * tile + 1 < W;
     double m_last = -INFINITY;
@@ -151,41 +124,39 @@ __global__ void __launch_bounds__(kAgentsThreads) st_occupancy_kernel(const Sear
     const bool on = j < S && sigma <= m_last;
     const int cnt = st_count(prof, c, on ? sigma : -INFINITY, lane);
     bool always = false;                                     // a pose that is not finite: blocked at every layer
-    double gx[6], gy[6], bx = 0.0, by = 0.0;
+    double gx[6], gy[6];
+    Point2 bc = {0.0, 0.0};                                  // the bounding circle's centre
     if (on) {
-        const StPose o = st_pose(p, prof, a.stride, c, cnt, sigma);
-        const double venv = sqrt(fmax(o.w, 0.0));
+        double w;
+        const PathPose o = st_pose(p, prof, a.stride, c, cnt, sigma, &w);
+        const double venv = sqrt(fmax(w, 0.0));
         a.parents[(size_t)b * a.m * S * Q1 + j] = (uint8_t)(int)fmin(floor(venv * a.prm.dt / a.prm.ds), (double)a.prm.q_max);
         always = !(isfinite(o.x) && isfinite(o.y) && isfinite(o.heading));
         double sh, ch;
         sincos(always ? 0.0 : o.heading, &sh, &ch);
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
-            gx[q] = a.cx[q] * ch - a.cy[q] * sh + o.x;
-            gy[q] = a.cx[q] * sh + a.cy[q] * ch + o.y;
+            const Point2 g = local_to_global(a.car.cx[q], a.car.cy[q], sh, ch, o.x, o.y);
+            gx[q] = g.x; gy[q] = g.y;
         }
-        bx = a.cx[6] * ch - a.cy[6] * sh + o.x;
-        by = a.cx[6] * sh + a.cy[6] * ch + o.y;
+        bc = local_to_global(a.car.cx[6], a.car.cy[6], sh, ch, o.x, o.y);
     } else {
 #pragma unroll
         for (int q = 0; q < 6; ++q) gx[q] = gy[q] = 0.0;
     }
-    const int scene = a.scene_of ? min(max(a.scene_of[b], 0), a.n_scenes - 1) : 0;
-    const int A = a.a_of ? min(max(a.a_of[scene], 0), a.a_max) : a.a_max;
-    const double* __restrict__ frames = a.frames + (size_t)scene * a.a_max * a.m * PQP_AGENT_FRAME_STRIDE;
+    int A;
+    const double* __restrict__ frames = scene_frames(a, b, &A);
     const double margin = a.prm.margin;
     for (int k = 0; k < a.m; ++k) {
         bool hit = always;
         const double* f = frames + (size_t)k * PQP_AGENT_FRAME_STRIDE;
         for (int ag = 0; ag < A; ++ag, f += (size_t)a.m * PQP_AGENT_FRAME_STRIDE) {
             const double ax = f[0], ay = f[1], reach = f[7];                              // wave-uniform
-            if (reach < 0.0) continue;                                                    // absent
-            if (!(reach == reach)) { hit = true; continue; }                              // bad: every station of the layer
+            if (agent_absent(reach)) continue;
+            if (agent_bad(reach)) { hit = true; continue; }                               // every station of the layer
             if (!on || hit) continue;
-            const double ux = bx - ax, uy = by - ay;
-            const double far = a.rb + reach + margin + kAgentsSlack + kAgentsSlackRel * (fabs(bx) + fabs(by) + fabs(ax) + fabs(ay));
-            if (ux * ux + uy * uy > far * far) continue;                                  // clear(k, a) >= margin + the slack
-            if (agent_clear(gx, gy, a.cr, ax, ay, f[2], f[3], f[4], f[5], f[6]) < margin) hit = true;
+            if (agent_out_of_reach(a.car.rb, reach, margin, bc.x, bc.y, ax, ay)) continue;
+            if (agent_clear(gx, gy, a.car.cr, ax, ay, f[2], f[3], f[4], f[5], f[6]) < margin) hit = true;
         }
         const uint64_t bits = __ballot(hit && on);
         if (lane == 0) {
@@ -219,7 +190,7 @@ __global__ void __launch_bounds__(kSearchThreads) st_search_kernel(const SearchA
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const long long b = blockIdx.x;
     const int S = a.prm.stations, Q = a.prm.q_max, Q1 = Q + 1, W = (S + 31) / 32, states = S * Q1, m = a.m;
-    const int c = st_driven(a, b);
+    const int c = driven_count(clamped_count(a.n_of, b, a.n), a.stop_before, b);
     double m_last = -INFINITY;
     const bool bad = c > 0 && st_judge(a, b, c, lane, &m_last);                            // every wavefront for itself: nothing to share
     if (c == 0 || bad) {
@@ -352,7 +323,8 @@ __global__ void __launch_bounds__(kSearchThreads) st_search_kernel(const SearchA
         const int cnt = st_count(prof, c, planned ? sigma : -INFINITY, lane);
         double row[PQP_TRAJ_STRIDE] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
         if (planned) {
-            const StPose o = st_pose(p, prof, a.stride, c, cnt, sigma);
+            double w;                                        // (the envelope is not asked for here)
+            const PathPose o = st_pose(p, prof, a.stride, c, cnt, sigma, &w);
             row[0] = o.x; row[1] = o.y; row[2] = o.heading; row[3] = o.k; row[4] = sigma;
             row[5] = (double)q * ds / dt;
             row[6] = (double)(q_next - q) * ds / (dt * dt);

@@ -29,14 +29,12 @@ struct SelectArgs {
     int32_t* best_n;                 // [groups] or nullptr
 };
 
-__device__ __forceinline__ int select_count(const SelectArgs& a, int b) { return a.n_of ? min(max(a.n_of[b], 0), a.n) : a.n; }
-
 __global__ void __launch_bounds__(kSelectThreads) path_score_kernel(const SelectArgs a) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x & 63;
     const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kSelectThreads / 64) + (threadIdx.x >> 6)));
     if (b >= a.batch) return;
-    const int count = select_count(a, b);
+    const int count = clamped_count(a.n_of, b, a.n);
     double* rec = a.terms + (size_t)b * PQP_SCORE_STRIDE;
     if (count < 2) {
         if (lane < PQP_SCORE_STRIDE) rec[lane] = 0.0;
@@ -100,7 +98,7 @@ __global__ void __launch_bounds__(kSelectThreads) group_select_kernel(const Sele
     const int winner = winner_or_max == INT_MAX ? -1 : winner_or_max;
     if (lane == 0) a.best[g] = winner;
     if (!a.best_paths) return;
-    const int count = winner >= 0 ? select_count(a, winner) : 0;
+    const int count = winner >= 0 ? clamped_count(a.n_of, winner, a.n) : 0;
     if (lane == 0) a.best_n[g] = count;
     const double* __restrict__ src = winner >= 0 ? a.paths + (size_t)winner * a.n * a.stride : nullptr;
     double* dst = a.best_paths + (size_t)g * a.n * 7;

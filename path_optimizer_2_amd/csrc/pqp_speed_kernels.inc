@@ -40,8 +40,8 @@ __global__ void __launch_bounds__(kSpeedThreads) speed_profile_kernel(const Spee
     const int lane = threadIdx.x & 63;
     const int b = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kSpeedThreads / 64) + (threadIdx.x >> 6)));
     if (b >= a.batch) return;
-    const int count = a.n_of ? min(max(a.n_of[b], 0), a.n) : a.n;
-    const int c = a.stop_before ? min(count, max(a.stop_before[b], 0)) : count;
+    const int count = clamped_count(a.n_of, b, a.n);
+    const int c = driven_count(count, a.stop_before, b);
     const bool early = c < count;
     double* prof = a.profile + (size_t)b * a.n * PQP_SPEED_STRIDE;
     // rows that are not driven: zeros (four doubles a row: one contiguous span)

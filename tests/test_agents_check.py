@@ -128,7 +128,7 @@ def test_checker_compiles_against_the_reference_headers():
 @pytest.mark.parametrize("name,tag,vgprs,occupancy", [("agent_frames_kernel", "", 40, 8), ("agents_check_kernel", "ILb1E", 96, 5),
                                                        ("agents_check_kernel", "ILb0E", 112, 4)])
 def test_the_kernels_use_no_scratch_and_no_lds(hip_lib, name, tag, vgprs, occupancy):
-    """what the build gives today: 38 VGPRs for the frames, 94 with the clearance written and 106 without (the broad phase's operands),
+    """what the build gives today: 38 VGPRs for the frames, 92 with the clearance written and 97 without (the broad phase's operands),
     each held to the allocation granule of 8 it falls in (40, 96, 112) and to the occupancy that follows from it; an occupancy below 4
     would be a lane state that no longer fits 128 registers"""
     r = build_util.find_kernel(build_util.kernel_report(), name, tag)
