@@ -1121,6 +1121,77 @@ int pqp_speed_search(pqp_handle* h, const pqp_search_params* prm, const pqp_car_
                      int n_scenes, int a_max, const double* agents, const int32_t* a_of, const int32_t* scene_of, int32_t* blocked,
                      int32_t* steps, double* traj, double* cost, int32_t* reached, int32_t* flags);
 
+/* ---- searched speed plans made drivable: a jerk-limited speed QP ---------------------------------------------------------------------------
+ * pqp_speed_search ends in a staircase: stations are whole cells of ds, speeds whole cells per layer, accelerations jump by ds / dt^2 from
+ * layer to layer.  It decides who yields.  This turns the decision into a plan a car can drive, behind the search on the same stream: a
+ * corridor in the path-time plane around the searched stations, taken from the search's own occupancy bits, and in it the QP over
+ * (s_k, v_k, a_k) per layer under the sampler's constant-acceleration kinematics, solved exactly on the banded core of the smoothers.  The
+ * reference has no counterpart. */
+/* The grid comes as the search's pqp_search_params, of which dt, ds and stations are read.  The refine's own numbers are PQP_REFINE_PARAMS
+ * doubles, prm[PQP_REFINE_W_REF] ... prm[PQP_REFINE_D_MAX], and an int `window` beside them.  pqp_refine_default_params (pure host; a NULL
+ * pointer is ignored) writes the weights 1, 1, 1, pqp_speed_default_params' a_max and d_max, and window = 4. */
+#define PQP_REFINE_PARAMS 5
+enum { PQP_REFINE_W_REF = 0, PQP_REFINE_W_ACCEL = 1, PQP_REFINE_W_JERK = 2, PQP_REFINE_A_MAX = 3, PQP_REFINE_D_MAX = 4 };
+void pqp_refine_default_params(double* prm, int* window);
+enum { PQP_REFINE_REFINED = 1, PQP_REFINE_KEPT = 2, PQP_REFINE_INFEASIBLE = 4 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   paths, n_of, stop_before, profile, v_start, m     exactly what pqp_speed_search got
+ *   blocked [batch][m][W], steps [batch][m][2], reached [batch], search_traj [batch][m][PQP_TRAJ_STRIDE]   what it wrote (search_traj: its traj)
+ * Outputs, fully overwritten:
+ *   traj [batch][m][PQP_TRAJ_STRIDE]  the refined rows, or search_traj's for a path that is kept
+ *   bounds [batch][m][3] or NULL      lo_k, hi_k, vcap_k; zeros for a path that is kept
+ *   cost [batch]                      the QP's objective at the solver's (s, v, a), terms added in wavefront-scan order; NaN when kept
+ *   excess [batch] or NULL            see below; NaN when kept
+ *   status, iters [batch]             the banded core's; PQP_STATUS_UNSOLVED and 0 for a path that never went to it
+ *   flags [batch]
+ * The definition, in fp64; the corridor, the QP's numbers and the placement with every product and sum rounded on its own (no
+ * contraction), min and max as fmin and fmax.
+ *   refined or kept   A path is refined when m >= 2 and reached = m.  Every other path is kept: its traj rows are search_traj's bit for
+ *              bit, flags = PQP_REFINE_KEPT, bounds zeros, status PQP_STATUS_UNSOLVED - this covers PQP_SEARCH_NO_PLAN, PQP_SEARCH_EMPTY
+ *              and PQP_SEARCH_NOT_FINITE.  Kept too, because the arrays are the device's and are judged there: a path with c = 0 or with a
+ *              value the search would flag PQP_SEARCH_NOT_FINITE, J = 0, a j_k outside 0 .. j_last, or a j_k that is not free in occ_k
+ *              (no search wrote such steps)
+ *   corridor   all integer.  J and j_last as the search defines them, recomputed from the running maximum of the s column; j_k = steps[k][0].
+ *              occ_k = blocked[k] | blocked[max(k-1, 0)] | blocked[min(k+1, m-1)], word by word: what the car must stay out of at layer k
+ *              and while it moves to and from it.  The search's swept-range rule makes j_k free in all three, so the corridor is never
+ *              empty.  jlo_k = the smallest j >= max(j_k - min(window, S), 0) with j .. j_k free in occ_k; jhi_k = the largest
+ *              j <= min(j_k + min(window, S), j_last) with j_k .. j free.  lo_k = (double)jlo_k * ds; hi_k = (double)jhi_k * ds;
+ *              vcap_k = max over jlo_k .. jhi_k of venv_j, the search's envelope at a station (max in ascending j).  At layer 0 lo = hi = 0
+ *   QP         variables (s_k, v_k, a_k) per layer; a_k is the constant acceleration over [k dt, (k+1) dt] - pqp_sample_trajectory's
+ *              kinematics.  minimise  sum_k w_ref (s_k - sigma_{j_k})^2 + w_accel a_k^2  +  sum_{k < m-1} w_jerk ((a_{k+1} - a_k) / dt)^2
+ *              over  s_0 = 0, lo_k <= s_k <= hi_k (k >= 1);  v_0 = v_start, 0 <= v_k <= vcap_k (k >= 1);  -d_max <= a_k <= a_max (k < m-1),
+ *              a_{m-1} = 0 (the search's convention for the last layer);  s_{k+1} - s_k - dt v_k - (dt^2 / 2) a_k = 0;
+ *              v_{k+1} - v_k - dt a_k = 0.  3m variables, 5m - 2 rows; with w_ref > 0 or w_accel > 0 the optimum is unique
+ *   solve      always the exact optimum: the banded core with polish = 1 and the tolerances of pqp_production_params, whatever the handle's
+ *              path-QP setting (plain ADMM at eps 1e-3 ends a decimetre from the optimum of this QP).  A solve that ends anything but
+ *              PQP_STATUS_SOLVED keeps the path as above, with status the core's, and PQP_REFINE_INFEASIBLE beside PQP_REFINE_KEPT for
+ *              PQP_STATUS_PRIMAL_INFEASIBLE.  Feasibility is not guaranteed: the staircase does not satisfy the constant-acceleration
+ *              dynamics, and v_start is not a whole cell
+ *   refined rows, flags = PQP_REFINE_REFINED:  s = min(max(s_k, lo_k), hi_k), so the corridor holds exactly (only the solver's tolerance
+ *              is clamped away); v = max(v_k, 0); a = a_k, and 0 at k = m - 1, where the row pins it; t = (double)k * dt; x, y, heading, k
+ *              by the search's "pose at sigma_j" with s in place of sigma_j
+ *   excess     max_k (v - sqrt(max(w, 0))), w the search's envelope expression v_i*v_i + (2*a_i)*e at the placed pose: how far the plan
+ *              runs above the envelope where it actually is.  vcap_k is the largest envelope speed of the window, it does not tie v_k to
+ *              s_k inside it, so excess may be positive: a limit of this QP, reported and not hidden
+ * What the refine does not promise: that the refined plan is clear of every agent (stations between two free cells are not tested, as in
+ * the search), and that a feasible refinement exists.
+ * A path's result depends on its own rows and the parameters alone: the same bits at any batch position and from either form; no atomics.
+ * The _device form is four launches (the corridor, the assembly, the solve, the placement), asynchronous on the handle's stream; its QP
+ * arrays and the corridor are the handle's own, apart from the smoothers', sized on first use and reused, and the rows' sparsity is uploaded
+ * once per m.  The host form copies in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the
+ * outputs untouched, for a null pointer that is not optional, batch < 1, n < 1, m < 1, stride < 6, a dt or ds that is not finite and
+ * positive, stations outside 1 .. PQP_SEARCH_MAX_STATES, a weight that is not finite or is negative, w_ref + w_accel = 0, an a_max or d_max
+ * that is not finite and positive, or window < 0; PQP_ERR_CAPACITY, likewise, when the QP of m layers is beyond what the core holds in one
+ * compute unit's LDS (m > 193). */
+int pqp_speed_refine_device(pqp_handle* h, const pqp_search_params* grid, const double* prm, int window, int batch, int n, int stride,
+                            const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start,
+                            int m, const int32_t* blocked, const int32_t* steps, const int32_t* reached, const double* search_traj,
+                            double* traj, double* bounds, double* cost, double* excess, int32_t* status, int32_t* iters, int32_t* flags);
+int pqp_speed_refine(pqp_handle* h, const pqp_search_params* grid, const double* prm, int window, int batch, int n, int stride,
+                     const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start, int m,
+                     const int32_t* blocked, const int32_t* steps, const int32_t* reached, const double* search_traj, double* traj,
+                     double* bounds, double* cost, double* excess, int32_t* status, int32_t* iters, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

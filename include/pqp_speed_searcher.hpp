@@ -8,6 +8,7 @@
 //   params()                              pqp_search_params to edit (pqp_search_default_params; pqp_search_params_from_speed)
 //   car()                                 pqp_car_geometry to edit (pqp_car_default_geometry: the reference's flags)
 //   search(paths, v_start, scenes, ...)   per path the planned (station, step) of every layer, the layers reached and PQP_SEARCH_* flags
+//   search_raw(...)                       the same call with the C ABI's arrays left to the caller (SpeedRefiner's input)
 //
 // Not copyable, not thread-safe, no exceptions; search() returns false on a GPU error or a bad argument (pqp_last_error()).
 #pragma once
@@ -38,6 +39,14 @@ class SpeedSearcher {
         double cost = 0.0;
     };
 
+    // what one call hands to pqp_speed_search and gets back, as the C ABI's arrays: search() reads plans out of it, and SpeedRefiner
+    // (pqp_speed_refiner.hpp) hands it on to pqp_speed_refine
+    struct Raw {
+        size_t B = 0, n = 0, m = 0;
+        std::vector<double> rows, profile, traj, cost;       // [B][n][6], [B][n][4], [B][m][8], [B]
+        std::vector<int32_t> n_of, steps, reached, flags, blocked;      // blocked [B][m][W], filled when asked for
+    };
+
     // paths: State or SlState with x, y, heading, k and the s, v, a SpeedProfiler::profile wrote
     // v_start [paths]: the speed at waypoint 0
     // scenes [scene][agent][layer]: the predicted agents at the layers' times k dt; the longest agent gives the number of layers m (at
@@ -48,7 +57,35 @@ class SpeedSearcher {
     bool search(const std::vector<std::vector<StateT>>& paths, const std::vector<double>& v_start,
                 const std::vector<std::vector<std::vector<PredictedAgent>>>& scenes, std::vector<Plan>* plans,
                 std::vector<std::vector<StateT>>* states = nullptr, const std::vector<int>* scene_of = nullptr, int layers = 1) {
-        if (!plans || paths.empty() || scenes.empty() || v_start.size() != paths.size()) return false;
+        Raw raw;
+        if (!plans || !search_raw(paths, v_start, scenes, scene_of, layers, false, &raw)) return false;
+        const size_t B = raw.B, m = raw.m;
+        plans->assign(B, Plan());
+        if (states) states->assign(B, std::vector<StateT>());
+        for (size_t b = 0; b < B; ++b) {
+            Plan& p = (*plans)[b];
+            p.flags = raw.flags[b];
+            p.cost = raw.cost[b];
+            for (int k = 0; k < raw.reached[b]; ++k) {
+                p.station.push_back(raw.steps[(b * m + k) * 2]);
+                p.step.push_back(raw.steps[(b * m + k) * 2 + 1]);
+                if (states) {
+                    const double* r = &raw.traj[(b * m + k) * PQP_TRAJ_STRIDE];
+                    StateT st{};
+                    st.x = r[0]; st.y = r[1]; st.heading = r[2]; st.k = r[3]; st.s = r[4]; st.v = r[5]; st.a = r[6];
+                    (*states)[b].push_back(st);
+                }
+            }
+        }
+        return true;
+    }
+
+    // the same call with its arrays left in *raw (with_blocked: the occupancy bits too)
+    template <class StateT>
+    bool search_raw(const std::vector<std::vector<StateT>>& paths, const std::vector<double>& v_start,
+                    const std::vector<std::vector<std::vector<PredictedAgent>>>& scenes, const std::vector<int>* scene_of, int layers,
+                    bool with_blocked, Raw* raw) {
+        if (!raw || paths.empty() || scenes.empty() || v_start.size() != paths.size()) return false;
         const size_t B = paths.size(), S = scenes.size();
         if (scene_of && scene_of->size() != B) return false;
         size_t n = 1, m = (size_t)std::max(layers, 1), a_max = 0;
@@ -57,15 +94,21 @@ class SpeedSearcher {
             a_max = std::max(a_max, s.size());
             for (const auto& a : s) m = std::max(m, a.size());
         }
-        std::vector<double> rows(B * n * 6, 0.0), profile(B * n * PQP_SPEED_STRIDE, 0.0), agents(S * a_max * m * PQP_AGENT_STRIDE, 0.0);
-        std::vector<double> traj(B * m * PQP_TRAJ_STRIDE), cost(B);
-        std::vector<int32_t> n_of(B), a_of(S), scene, steps(B * m * 2), reached(B), flags(B);
+        raw->B = B; raw->n = n; raw->m = m;
+        raw->rows.assign(B * n * 6, 0.0);
+        raw->profile.assign(B * n * PQP_SPEED_STRIDE, 0.0);
+        raw->traj.assign(B * m * PQP_TRAJ_STRIDE, 0.0);
+        raw->cost.assign(B, 0.0);
+        raw->n_of.assign(B, 0); raw->steps.assign(B * m * 2, 0); raw->reached.assign(B, 0); raw->flags.assign(B, 0);
+        raw->blocked.assign(with_blocked ? B * m * (size_t)((std::max(prm_.stations, 0) + 31) / 32) : 0, 0);
+        std::vector<double> agents(S * a_max * m * PQP_AGENT_STRIDE, 0.0);
+        std::vector<int32_t> a_of(S), scene;
         for (size_t b = 0; b < B; ++b) {
-            n_of[b] = (int32_t)paths[b].size();
+            raw->n_of[b] = (int32_t)paths[b].size();
             for (size_t i = 0; i < paths[b].size(); ++i) {
                 const StateT& st = paths[b][i];
-                double* r = &rows[(b * n + i) * 6];
-                double* o = &profile[(b * n + i) * PQP_SPEED_STRIDE];
+                double* r = &raw->rows[(b * n + i) * 6];
+                double* o = &raw->profile[(b * n + i) * PQP_SPEED_STRIDE];
                 r[0] = st.x; r[1] = st.y; r[2] = st.heading; r[5] = st.k;
                 o[0] = st.s; o[1] = st.v; o[2] = st.a;
             }
@@ -84,29 +127,13 @@ class SpeedSearcher {
                 }
         }
         if (scene_of) scene.assign(scene_of->begin(), scene_of->end());
-        if (pqp_speed_search(&h_, &prm_, &car_, (int)B, (int)n, 6, rows.data(), n_of.data(), nullptr, profile.data(), v_start.data(), (int)m, (int)S,
-                             (int)a_max, a_max ? agents.data() : nullptr, a_of.data(), scene_of ? scene.data() : nullptr, nullptr, steps.data(),
-                             traj.data(), cost.data(), reached.data(), flags.data()) != PQP_OK)
-            return false;
-        plans->assign(B, Plan());
-        if (states) states->assign(B, std::vector<StateT>());
-        for (size_t b = 0; b < B; ++b) {
-            Plan& p = (*plans)[b];
-            p.flags = flags[b];
-            p.cost = cost[b];
-            for (int k = 0; k < reached[b]; ++k) {
-                p.station.push_back(steps[(b * m + k) * 2]);
-                p.step.push_back(steps[(b * m + k) * 2 + 1]);
-                if (states) {
-                    const double* r = &traj[(b * m + k) * PQP_TRAJ_STRIDE];
-                    StateT st{};
-                    st.x = r[0]; st.y = r[1]; st.heading = r[2]; st.k = r[3]; st.s = r[4]; st.v = r[5]; st.a = r[6];
-                    (*states)[b].push_back(st);
-                }
-            }
-        }
-        return true;
+        return pqp_speed_search(&h_, &prm_, &car_, (int)B, (int)n, 6, raw->rows.data(), raw->n_of.data(), nullptr, raw->profile.data(), v_start.data(),
+                                (int)m, (int)S, (int)a_max, a_max ? agents.data() : nullptr, a_of.data(), scene_of ? scene.data() : nullptr,
+                                with_blocked ? raw->blocked.data() : nullptr, raw->steps.data(), raw->traj.data(), raw->cost.data(),
+                                raw->reached.data(), raw->flags.data()) == PQP_OK;
     }
+
+    pqp_handle& handle() { return h_; }
 
  private:
     pqp_handle& h_;

@@ -201,6 +201,36 @@ def search_params_from_speed(lib, speed_prm, dt, ds):
     return p
 
 
+class RefineParams:
+    """what pqp_speed_refine takes besides its arrays and the search's grid: the REFINE_PARAMS doubles the C ABI passes as a plain array
+    (w_ref, w_accel, w_jerk, a_max, d_max, at REFINE_W_REF .. REFINE_D_MAX) and the window beside them, under the names of the header's
+    enumerators.  refine_default_params(w_jerk=...) as for the other parameter sets."""
+    __slots__ = ("w_ref", "w_accel", "w_jerk", "a_max", "d_max", "window")
+    _INDEX = (("w_ref", REFINE_W_REF), ("w_accel", REFINE_W_ACCEL), ("w_jerk", REFINE_W_JERK), ("a_max", REFINE_A_MAX), ("d_max", REFINE_D_MAX))
+
+    def __init__(self, values, window):
+        for name, i in self._INDEX:
+            setattr(self, name, float(values[i]))
+        self.window = int(window)
+
+    def array(self):
+        out = np.zeros(REFINE_PARAMS)
+        for name, i in self._INDEX:
+            out[i] = getattr(self, name)
+        return out
+
+
+def refine_default_params(lib=None, **over):
+    """pqp_refine_default_params: the weights 1, 1, 1, the speed defaults' a_max 1.5 and d_max 3 m/s^2, window 4 - with `over` applied."""
+    lib = lib or load_library()
+    values, window = np.full(REFINE_PARAMS, -1.0), C.c_int(-1)
+    lib.pqp_refine_default_params(values, C.byref(window))
+    p = RefineParams(values, window.value)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
 def car_circles(car=None, lib=None):
     """pqp_car_circles (pure host): [7][3] x, y, r in the vehicle frame of rr, rl, fr, fl, fm, rm and the bounding circle."""
     lib = lib or load_library()
@@ -382,8 +412,8 @@ class Handle:
         return _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", over)
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
-                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, agents=None,
-                      agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
+                      car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
+                      agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -411,29 +441,31 @@ class Handle:
         car: the footprint.  Adds first_hit, hit_agent and agent_clearance [..][samples].
         search: SearchParams (needs speed and agents; not sample) - pqp_speed_search_device behind the speed profile on the same stream, on
         the rows it ran on, with its v_start: the agents' step count is the number of layers m (with sample too, that is `samples`, and
-        both run).  Adds search_steps [..][m][2], search_traj [..][m][8], search_cost, search_reached and search_flags."""
+        both run).  Adds search_steps [..][m][2], search_traj [..][m][8], search_cost, search_reached and search_flags.
+        refine: RefineParams (needs search) - pqp_speed_refine_device behind the search on the same stream, on the rows the search ran on and
+        on what it wrote.  Adds search_blocked [..][m][W] (what the refine read), refine_traj [..][m][8], refine_bounds [..][m][3], refine_cost, refine_excess, refine_status and refine_flags."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents))
+                           self._search(search, speed, agents), self._refine(refine, search))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False, search=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None,
+                              winners_only=False, search=None, refine=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None,
                               samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
-        agents_params / search: as for optimize_path)."""
+        agents_params / search / refine: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents))
+                           self._search(search, speed, agents), self._refine(refine, search))
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -469,6 +501,15 @@ class Handle:
             raise ValueError("search needs agents=: the predicted agents at the layers' times")
         return search
 
+    def _refine(self, refine, search):
+        if refine is None:
+            return None
+        if not isinstance(refine, RefineParams):
+            raise ValueError("refine must be a RefineParams")
+        if search is None:
+            raise ValueError("refine needs search=SearchParams: it refines the plan the search wrote")
+        return refine
+
     def _agents(self, agents, agents_of, scene_of, agents_params, sample, samples, car, batch, select, search=None):
         if agents is None:
             if agents_of is not None or scene_of is not None or agents_params is not None:
@@ -503,13 +544,14 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None, moving=None, searching=None):
+               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
         of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None; moving:
         (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that (when there is a sampling), or
-        None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None"""
+        None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None; refining: RefineParams
+        of the speed QP behind that search, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -564,6 +606,11 @@ class Handle:
             se_cost = torch.zeros(rows, dtype=torch.float64, device=dev)
             se_reached = torch.zeros(rows, dtype=torch.int32, device=dev)
             se_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
+        if refining is not None:
+            rf_traj = torch.zeros((rows, layers, TRAJ_STRIDE), dtype=torch.float64, device=dev)
+            rf_bounds = torch.zeros((rows, layers, 3), dtype=torch.float64, device=dev)
+            rf_cost, rf_excess = (torch.zeros(rows, dtype=torch.float64, device=dev) for _ in range(2))
+            rf_status, rf_iters, rf_flags = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(3))
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -611,6 +658,12 @@ class Handle:
                                                          ag.shape[0], ag.shape[1], d_ag if ag.size else None, d_ag_of, d_scene,
                                                          ag_frames if ag.size else None, se_blocked, se_parents, se_steps, se_traj, se_cost,
                                                          se_reached, se_flags))
+        if refining is not None:            # behind the search, on the rows it ran on and on what it wrote
+            self._check(self.lib.pqp_speed_refine_device(self._h, C.byref(searching), refining.array(), int(refining.window), rows, cfg.n_max, 7,
+                                                         best_paths if on_winners else out, best_n if on_winners else ints[0],
+                                                         first if (footprint is not None and not on_winners) else None, profile, d_vs, layers,
+                                                         se_blocked, se_steps, se_reached, se_traj, rf_traj, rf_bounds, rf_cost, rf_excess,
+                                                         rf_status, rf_iters, rf_flags))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -635,6 +688,9 @@ class Handle:
         if searching is not None:
             res.update(search_steps=host(se_steps), search_traj=host(se_traj), search_cost=host(se_cost), search_reached=host(se_reached),
                        search_flags=host(se_flags))
+        if refining is not None:
+            res.update(search_blocked=host(se_blocked), refine_traj=host(rf_traj), refine_bounds=host(rf_bounds), refine_cost=host(rf_cost), refine_excess=host(rf_excess),
+                       refine_status=host(rf_status), refine_flags=host(rf_flags))
         return res
 
     def distance_layer(self, grid, geom):
@@ -799,6 +855,39 @@ class Handle:
         if blocked:
             res["blocked"] = blk
         return res
+
+    def speed_refine(self, paths, profile, v_start, blocked, steps, reached, search_traj, n_of=None, stop_before=None, grid=None, prm=None):
+        """pqp_speed_refine (host arrays): paths [B][n][stride >= 6], profile [B][n][4], v_start [B] and optionally n_of [B], stop_before [B]
+        as speed_search got them; blocked [B][m][W], steps [B][m][2], reached [B] and search_traj [B][m][8] as it returned them (its
+        blocked=True); grid = the search's SearchParams (None: search_default_params()), prm = RefineParams (None:
+        refine_default_params()).  Returns dict(traj [B][m][8], bounds [B][m][3] = lo, hi, vcap, cost [B], excess [B], status [B], iters
+        [B], flags [B] of REFINE_*)."""
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        B, n, stride = paths.shape
+        profile = np.ascontiguousarray(profile, dtype=np.float64)
+        if profile.shape != (B, n, SPEED_STRIDE):
+            raise ValueError(f"speed_refine: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        grid = grid if grid is not None else search_default_params(self.lib)
+        prm = prm if prm is not None else refine_default_params(self.lib)
+        search_traj = np.ascontiguousarray(search_traj, dtype=np.float64)
+        if search_traj.ndim != 3 or search_traj.shape[0] != B or search_traj.shape[2] != TRAJ_STRIDE:
+            raise ValueError(f"speed_refine: search_traj must be [{B}][m][{TRAJ_STRIDE}], not {search_traj.shape}")
+        m = search_traj.shape[1]
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        no, sb, blk, stp, rch = i32(n_of), i32(stop_before), i32(blocked), i32(steps), i32(reached)
+        vs = np.ascontiguousarray(v_start, dtype=np.float64)
+        words = (max(int(grid.stations), 0) + 31) // 32
+        for name, a, size in (("n_of", no, B), ("stop_before", sb, B), ("v_start", vs, B), ("blocked", blk, B * m * words), ("steps", stp, B * m * 2),
+                              ("reached", rch, B)):
+            if a is not None and a.size != size:
+                raise ValueError(f"speed_refine: {name} must have {size} entries, not {a.size}")
+        traj = np.zeros((B, m, TRAJ_STRIDE))
+        bounds = np.zeros((B, m, 3))
+        cost, excess = np.zeros(B), np.zeros(B)
+        status, iters, flags = (np.zeros(B, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.pqp_speed_refine(self._h, C.byref(grid), prm.array(), int(prm.window), B, n, stride, paths, no, sb, profile, vs, m, blk,
+                                              stp, rch, search_traj, traj, bounds, cost, excess, status, iters, flags))
+        return dict(traj=traj, bounds=bounds, cost=cost, excess=excess, status=status, iters=iters, flags=flags)
 
     def corridor_params(self, **over):
         return _defaults(self.lib, PqpCorridorParams, "pqp_corridor_default_params", over)

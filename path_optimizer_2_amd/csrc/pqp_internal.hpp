@@ -54,6 +54,14 @@ struct DevBuf {
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
 
+// The arrays of a batch of QPs for the generic banded core (pqp_banded_qp.hpp): the problem data, the solution and the sparsity its batch
+// shares, cached per structure type and size.  Each user of the core on the handle owns one (the smoothers, the speed refine), so one's
+// structure never displaces another's.
+struct BandedGroup {
+    DevBuf pband, q, aval, lo, up, x, y, acol, trow, tslot;
+    int struct_type = -1, struct_n = -1;
+};
+
 // one CU's LDS on gfx950: the most dynamic LDS a workgroup can have
 constexpr size_t kLdsPerCu = 160 * 1024;
 
@@ -215,10 +223,8 @@ struct pqp_handle {
     } strm;
 
     // pqp_smoothers.hip
-    struct PQP_HIDDEN Smoothers {
-        // smoother QPs: banded problem data + shared sparsity (cached per type and size)
-        DevBuf pband, q, aval, lo, up, x, y, acol, trow, tslot;
-        int struct_type = -1, struct_n = -1;
+    struct PQP_HIDDEN Smoothers : pqp_internal::BandedGroup {
+        // smoother QPs: banded problem data + shared sparsity (cached per type and size) are the base's
         DevBuf act[2];                              // final active sets of the exact TensionSmoother / postSmooth kernels (PQP_OPT_CARRY_CYCLES)
         int act_batch[2] = {0, 0}, act_n[2] = {0, 0};
         // a captured launch holds the carry flags of the exact kernels; a structure upload cannot be captured at all (sm_upload_structure)
@@ -226,6 +232,10 @@ struct pqp_handle {
             k.put_int(act_batch[0]); k.put_int(act_n[0]); k.put_int(act_batch[1]); k.put_int(act_n[1]); k.put_int(struct_type); k.put_int(struct_n);
         }
     } sm;
+
+    // pqp_speed_refine_device (pqp_maps.hip): the speed QPs' own group for the banded core, and the corridor [batch][m][3] its three
+    // kernels share.  (no key: the chain runs none of it, and its structure is not the smoothers')
+    struct PQP_HIDDEN Refine : pqp_internal::BandedGroup { DevBuf bounds; } rf;
 
     // line_launch: workspace of the long forms of the line kernels (one launch at a time on the stream).
     // (no key: which form runs follows from opt.long_lines and the call's sizes; a reallocation moves the allocation generation)
@@ -295,6 +305,18 @@ class Staging {
     bool pending_ = false;
     Back back_[pqp_handle::kStage];
 };
+
+// The generic banded core on a buffer group of the handle's (pqp_smoothers.hip, where its kernels are instantiated).  kBanded*: the QP
+// families whose sparsity sm_alloc knows; n: points (layers) of the pattern.
+enum { kBandedTension2 = 0, kBandedTension = 1, kBandedPost = 2, kBandedRefine = 3 };
+// does the core hold a QP of this family and size (its vectors, factor rows and row data in one CU's LDS, one lane per padded variable)?
+bool sm_generic_fits(int type, int n);
+// the group's arrays for `batch` QPs, and the family's sparsity uploaded unless the group holds it
+int sm_alloc(pqp_handle* h, BandedGroup& g, int type, int batch, int n);
+// one launch of banded_solve_kernel on what an assemble kernel wrote into the group, under `prm`; `timed`: between a pair of the
+// handle's timing events of its own (a caller that times a longer sequence passes false)
+int sm_solve(pqp_handle* h, BandedGroup& g, const pqp_params& prm, int type, int batch, int n, const int32_t* n_of, int32_t* status, int32_t* iters,
+             double* info, bool timed);
 
 // PQP_OPT_CARRY_CYCLES for an exact smoother kernel (slot 0: TensionSmoother, 1: postSmooth): the active set every scenario ended with is kept
 // on the handle; a solve of the shape of the previous one (and the buffer still where it was) starts from it (carry = 1)

@@ -2,7 +2,8 @@
 // occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
 // group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc), samples of those trajectories on a time grid
 // (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc), speeds that pass those agents in
-// the path-time plane (pqp_search_kernels.inc).  Their kernels, launchers and entry points.
+// the path-time plane (pqp_search_kernels.inc), the speed QP that makes such a plan drivable (pqp_refine_kernels.inc; its solve is the
+// banded core's, launched from pqp_smoothers.hip).  Their kernels, launchers and entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 
 #include "pqp_defaults.hpp"
 #include "pqp_path_lane.hpp"
+#include "pqp_banded_qp.hpp"
 #include "pqp_wave.hpp"
 #include "pqp_driven_path.hpp"
 #include "pqp_line_device.hpp"
@@ -33,6 +35,7 @@ using namespace pqp_internal;
 #include "pqp_sample_kernels.inc"
 #include "pqp_agents_kernels.inc"
 #include "pqp_search_kernels.inc"
+#include "pqp_refine_kernels.inc"
 
 // ---- what the entry points below share ------------------------------------------------------------------------------------------------
 // the grid of a kernel that gives every item a wavefront, threads / 64 of them to a workgroup
@@ -524,6 +527,110 @@ int pqp_speed_search(pqp_handle* h, const pqp_search_params* prm, const pqp_car_
     return st.run([&]() -> int {
         return pqp_speed_search_device(h, prm, car, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, d_start, m, n_scenes, a_max, d_agents,
                                        d_a_of, d_scene_of, d_frames, d_blocked, d_parents, d_steps, d_traj, d_cost, d_reached, d_flags);
+    });
+}
+
+// ---- searched speed plans made drivable: a jerk-limited speed QP ---------------------------------------------------------------------------
+void pqp_refine_default_params(double* prm, int* window) {
+    if (prm) {
+        pqp_speed_params sp;
+        pqp_speed_default_params(&sp);
+        prm[PQP_REFINE_W_REF] = prm[PQP_REFINE_W_ACCEL] = prm[PQP_REFINE_W_JERK] = 1.0;
+        prm[PQP_REFINE_A_MAX] = sp.a_max;
+        prm[PQP_REFINE_D_MAX] = sp.d_max;
+    }
+    if (window) *window = 4;
+}
+
+static const char* const kRefineRefusal =
+    "pqp_speed_refine: bad argument (batch >= 1; n >= 1; m >= 1; stride >= 6; dt and ds finite and > 0; 1 <= stations <= 4096; the three weights "
+    "finite and >= 0, w_ref + w_accel > 0; a_max and d_max finite and > 0; window >= 0)";
+
+static bool refine_ok(pqp_handle* h, const pqp_search_params* grid, const double* prm, int window, int batch, int n, int stride, const double* paths,
+                      const double* profile, const double* v_start, int m, const int32_t* blocked, const int32_t* steps, const int32_t* reached,
+                      const double* search_traj, const double* traj, const double* cost, const int32_t* status, const int32_t* iters,
+                      const int32_t* flags) {
+    if (!(h && grid && prm && paths && profile && v_start && blocked && steps && reached && search_traj && traj && cost && status && iters && flags &&
+          batch >= 1 && n >= 1 && m >= 1 && stride >= 6 && window >= 0))
+        return false;
+    const auto weight = [](double v) { return std::isfinite(v) && v >= 0.0; };
+    const auto limit = [](double v) { return std::isfinite(v) && v > 0.0; };
+    return limit(grid->dt) && limit(grid->ds) && grid->stations >= 1 && grid->stations <= PQP_SEARCH_MAX_STATES && weight(prm[PQP_REFINE_W_REF]) &&
+           weight(prm[PQP_REFINE_W_ACCEL]) && weight(prm[PQP_REFINE_W_JERK]) && prm[PQP_REFINE_W_REF] + prm[PQP_REFINE_W_ACCEL] > 0.0 &&
+           limit(prm[PQP_REFINE_A_MAX]) && limit(prm[PQP_REFINE_D_MAX]);
+}
+
+// the layers the banded core holds in one CU's LDS: sm_generic_fits is monotone in m
+static bool refine_fits(int m) { return m < 2 || sm_generic_fits(kBandedRefine, m); }
+
+int pqp_speed_refine_device(pqp_handle* h, const pqp_search_params* grid, const double* prm, int window, int batch, int n, int stride,
+                            const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start,
+                            int m, const int32_t* blocked, const int32_t* steps, const int32_t* reached, const double* search_traj,
+                            double* traj, double* bounds, double* cost, double* excess, int32_t* status, int32_t* iters, int32_t* flags) {
+    if (!refine_ok(h, grid, prm, window, batch, n, stride, paths, profile, v_start, m, blocked, steps, reached, search_traj, traj, cost, status, iters, flags))
+        return fail(PQP_ERR_INVALID, kRefineRefusal);
+    if (!refine_fits(m)) return fail(PQP_ERR_CAPACITY, "pqp_speed_refine: the QP of m layers is beyond what the banded core holds in one CU's LDS");
+    PQP_HIP(hipSetDevice(h->device));
+    const bool solve = m >= 2;               // m = 1: every path is kept, there is no QP to assemble or solve
+    int rc;
+    if ((rc = h->rf.bounds.ensure((size_t)batch * m * 3 * 8))) return rc;
+    if (solve && (rc = sm_alloc(h, h->rf, kBandedRefine, batch, m))) return rc;
+    pqp::RefineArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.m = m; a.stations = grid->stations; a.window = window;
+    a.dt = grid->dt; a.ds = grid->ds; a.w_ref = prm[PQP_REFINE_W_REF]; a.w_accel = prm[PQP_REFINE_W_ACCEL]; a.w_jerk = prm[PQP_REFINE_W_JERK];
+    a.a_max = prm[PQP_REFINE_A_MAX]; a.d_max = prm[PQP_REFINE_D_MAX];
+    a.paths = paths; a.n_of = n_of; a.stop_before = stop_before; a.profile = profile; a.v_start = v_start; a.blocked = blocked; a.steps = steps;
+    a.reached = reached; a.search_traj = search_traj; a.corridor = h->rf.bounds.as<double>();
+    a.pband = h->rf.pband.as<double>(); a.q = h->rf.q.as<double>(); a.aval = h->rf.aval.as<double>(); a.lo = h->rf.lo.as<double>();
+    a.up = h->rf.up.as<double>(); a.x = h->rf.x.as<double>();
+    a.traj = traj; a.bounds = bounds; a.cost = cost; a.excess = excess; a.status = status; a.iters = iters; a.flags = flags;
+    // always the exact optimum: the production tolerances with the KKT-verified polish, whatever the handle's path-QP setting
+    pqp_params exact;
+    pqp::production_params(&exact);
+    exact.polish = 1;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::st_corridor_kernel, dim3((unsigned)batch), dim3(pqp::kRefineThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        if (solve) {
+            const long long total = (long long)batch * m;
+            hipLaunchKernelGGL(pqp::refine_assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, a);
+            PQP_HIP(hipGetLastError());
+            if (const int rc2 = sm_solve(h, h->rf, exact, kBandedRefine, batch, m, nullptr, status, iters, nullptr, false)) return rc2;
+        }
+        hipLaunchKernelGGL(pqp::refine_finish_kernel, dim3((unsigned)batch), dim3(pqp::kRefineThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_speed_refine(pqp_handle* h, const pqp_search_params* grid, const double* prm, int window, int batch, int n, int stride,
+                     const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start, int m,
+                     const int32_t* blocked, const int32_t* steps, const int32_t* reached, const double* search_traj, double* traj,
+                     double* bounds, double* cost, double* excess, int32_t* status, int32_t* iters, int32_t* flags) {
+    if (!refine_ok(h, grid, prm, window, batch, n, stride, paths, profile, v_start, m, blocked, steps, reached, search_traj, traj, cost, status, iters, flags))
+        return fail(PQP_ERR_INVALID, kRefineRefusal);
+    if (!refine_fits(m)) return fail(PQP_ERR_CAPACITY, "pqp_speed_refine: the QP of m layers is beyond what the banded core holds in one CU's LDS");
+    const size_t bn = (size_t)batch * n, bm = (size_t)batch * m, words = (size_t)(grid->stations + 31) / 32;
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_stop = st.in(stop_before, batch);
+    const double* d_profile = st.in(profile, bn * PQP_SPEED_STRIDE);
+    const double* d_start = st.in(v_start, batch);
+    const int32_t* d_blocked = st.in(blocked, bm * words);
+    const int32_t* d_steps = st.in(steps, bm * 2);
+    const int32_t* d_reached = st.in(reached, batch);
+    const double* d_from = st.in(search_traj, bm * PQP_TRAJ_STRIDE);
+    double* d_traj = st.out(traj, bm * PQP_TRAJ_STRIDE);
+    double* d_bounds = bounds ? st.out(bounds, bm * 3) : nullptr;
+    double* d_cost = st.out(cost, batch);
+    double* d_excess = excess ? st.out(excess, batch) : nullptr;
+    int32_t* d_status = st.out(status, batch);
+    int32_t* d_iters = st.out(iters, batch);
+    int32_t* d_flags = st.out(flags, batch);
+    return st.run([&]() -> int {
+        return pqp_speed_refine_device(h, grid, prm, window, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, d_start, m, d_blocked, d_steps,
+                                       d_reached, d_from, d_traj, d_bounds, d_cost, d_excess, d_status, d_iters, d_flags);
     });
 }
 

@@ -24,31 +24,30 @@ using namespace pqp_internal;
 
 #include "pqp_smoother_kernels.inc"
 
-extern "C" {
-
 // ---------------------------------------------------------------------------------------------------------
-// smoother QPs
+// smoother QPs, and the speed refine's QP on the same core (pqp_maps.hip)
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-enum { SM_TENSION2 = 0, SM_TENSION = 1, SM_POST = 2 };
+enum { SM_TENSION2 = kBandedTension2, SM_TENSION = kBandedTension, SM_POST = kBandedPost, SM_REFINE = kBandedRefine };
 
 struct SmShape { int nv, nc, bw, pbw, stride; };
 SmShape sm_shape(int type, int n) {
     if (type == SM_TENSION2) return {4 * n - 1, 3 * (n - 1) + 2, 4, 4, 4};
     if (type == SM_TENSION) return {3 * n, 3 * n, 9, 9, 3};
+    if (type == SM_REFINE) return {3 * n, 5 * n - 2, 3, 3, 3};
     return {3 * n, 3 * n - 2, 3, 0, 3};
 }
 
-// shared sparsity of a smoother QP in the interleaved variable order: integer host logic (like pqp_path_sizes)
-int sm_upload_structure(pqp_handle* h, int type, int n) {
-    if (h->sm.struct_type == type && h->sm.struct_n == n) return PQP_OK;
+// shared sparsity of a QP family in the interleaved variable order: integer host logic (like pqp_path_sizes)
+int sm_upload_structure(pqp_handle* h, BandedGroup& g, int type, int n) {
+    if (g.struct_type == type && g.struct_n == n) return PQP_OK;
     // a host -> device copy from vectors that go out of scope + a synchronise: not something a capturing stream may do.  The capture of
     // pqp_optimize_path_device is abandoned cleanly (the body fails, the call falls back to plain launches and never captures these arguments again:
     // a chain whose smoothers alternate between two structure types on the generic core uploads on every call)
     if (h->chain.capturing) return fail(PQP_ERR_INVALID, "smoother structure upload inside a graph capture");
     const SmShape sh = sm_shape(type, n);
     std::vector<int> acol((size_t)sh.nc * pqp::kRMax, -1), trow((size_t)sh.nv * pqp::kCMax, -1), tslot((size_t)sh.nv * pqp::kCMax, 0);
-    auto row = [&](int r, int c0, int c1, int c2) { int* a = &acol[(size_t)r * pqp::kRMax]; a[0] = c0; a[1] = c1; a[2] = c2; };
+    auto row = [&](int r, int c0, int c1, int c2, int c3 = -1) { int* a = &acol[(size_t)r * pqp::kRMax]; a[0] = c0; a[1] = c1; a[2] = c2; a[3] = c3; };
     if (type == SM_TENSION2) {
         for (int i = 0; i < n - 1; ++i) {
             row(i, 4 * (i + 1), 4 * i, 4 * i + 2);
@@ -59,6 +58,11 @@ int sm_upload_structure(pqp_handle* h, int type, int n) {
         row(3 * (n - 1) + 1, 1, -1, -1);
     } else if (type == SM_TENSION) {
         for (int i = 0; i < n; ++i) { row(i, 3 * i, 3 * i + 2, -1); row(n + i, 3 * i + 1, 3 * i + 2, -1); row(2 * n + i, 3 * i + 2, -1, -1); }
+    } else if (type == SM_REFINE) {
+        // (s, v, a)_k -> 3k + {0, 1, 2}.  rows k, m + k, 2m + k: the boxes of s_k, v_k, a_k;  3m + k: s_{k+1} - s_k - dt v_k - dt^2/2 a_k;
+        // 4m - 1 + k: v_{k+1} - v_k - dt a_k  (refine_assemble_kernel writes the values in this slot order)
+        for (int k = 0; k < n; ++k) { row(k, 3 * k, -1, -1); row(n + k, 3 * k + 1, -1, -1); row(2 * n + k, 3 * k + 2, -1, -1); }
+        for (int k = 0; k < n - 1; ++k) { row(3 * n + k, 3 * k, 3 * k + 1, 3 * k + 2, 3 * k + 3); row(4 * n - 1 + k, 3 * k + 1, 3 * k + 2, 3 * k + 4); }
     } else {
         for (int i = 0; i < n; ++i) row(i, 3 * i, -1, -1);
         for (int i = 0; i < n - 1; ++i) { row(n + i, 3 * (i + 1), 3 * i, 3 * i + 1); row(2 * n - 1 + i, 3 * (i + 1) + 1, 3 * i + 1, 3 * i + 2); }
@@ -72,25 +76,29 @@ int sm_upload_structure(pqp_handle* h, int type, int n) {
             trow[(size_t)c * pqp::kCMax + fill[c]] = r; tslot[(size_t)c * pqp::kCMax + fill[c]] = s; ++fill[c];
         }
     int rc;
-    if ((rc = h->sm.acol.ensure(acol.size() * 4)) || (rc = h->sm.trow.ensure(trow.size() * 4)) || (rc = h->sm.tslot.ensure(tslot.size() * 4))) return rc;
-    PQP_HIP(hipMemcpyAsync(h->sm.acol.p, acol.data(), acol.size() * 4, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->sm.trow.p, trow.data(), trow.size() * 4, hipMemcpyHostToDevice, h->stream));
-    PQP_HIP(hipMemcpyAsync(h->sm.tslot.p, tslot.data(), tslot.size() * 4, hipMemcpyHostToDevice, h->stream));
+    if ((rc = g.acol.ensure(acol.size() * 4)) || (rc = g.trow.ensure(trow.size() * 4)) || (rc = g.tslot.ensure(tslot.size() * 4))) return rc;
+    PQP_HIP(hipMemcpyAsync(g.acol.p, acol.data(), acol.size() * 4, hipMemcpyHostToDevice, h->stream));
+    PQP_HIP(hipMemcpyAsync(g.trow.p, trow.data(), trow.size() * 4, hipMemcpyHostToDevice, h->stream));
+    PQP_HIP(hipMemcpyAsync(g.tslot.p, tslot.data(), tslot.size() * 4, hipMemcpyHostToDevice, h->stream));
     PQP_HIP(hipStreamSynchronize(h->stream));      // the vectors go out of scope
-    h->sm.struct_type = type; h->sm.struct_n = n;
+    g.struct_type = type; g.struct_n = n;
     return PQP_OK;
 }
+}  // namespace
 
-// assemble (already enqueued by the caller into b_pband ...) -> banded ADMM solve -> finish.  All device pointers.  n_of: the counts the assemble
+namespace pqp_internal {
+
+// assemble (already enqueued by the caller into g.pband ...) -> banded ADMM solve.  All device pointers.  n_of: the counts the assemble
 // kernel padded by (or nullptr)
-int sm_solve(pqp_handle* h, int type, int batch, int n, const int32_t* n_of, int32_t* status, int32_t* iters, double* info) {
+int sm_solve(pqp_handle* h, BandedGroup& g, const pqp_params& prm, int type, int batch, int n, const int32_t* n_of, int32_t* status, int32_t* iters,
+             double* info, bool timed) {
     const SmShape sh = sm_shape(type, n);
     pqp::BandedQpArgs a;
     std::memset(&a, 0, sizeof(a));
     a.batch = batch; a.nv = sh.nv; a.nc = sh.nc; a.bw = sh.bw; a.pbw = sh.pbw;
-    a.pband = h->sm.pband.as<double>(); a.q = h->sm.q.as<double>(); a.acol = h->sm.acol.as<int>(); a.aval = h->sm.aval.as<double>();
-    a.trow = h->sm.trow.as<int>(); a.tslot = h->sm.tslot.as<int>(); a.lo = h->sm.lo.as<double>(); a.up = h->sm.up.as<double>();
-    a.x = h->sm.x.as<double>(); a.y = h->sm.y.as<double>(); a.status = status; a.iters = iters; a.info = info; a.prm = h->prm;
+    a.pband = g.pband.as<double>(); a.q = g.q.as<double>(); a.acol = g.acol.as<int>(); a.aval = g.aval.as<double>();
+    a.trow = g.trow.as<int>(); a.tslot = g.tslot.as<int>(); a.lo = g.lo.as<double>(); a.up = g.up.as<double>();
+    a.x = g.x.as<double>(); a.y = g.y.as<double>(); a.status = status; a.iters = iters; a.info = info; a.prm = prm;
     a.n_of = n_of; a.n_pts = n; a.n_min = type == SM_TENSION2 ? 2 : (type == SM_TENSION ? 4 : 1); a.per_pt = sh.stride;      // (n_min: the assemble kernels' clamps)
     pqp::resolve_banded_params(&a.prm);
     // the row data of A, the index lists and q staged in LDS once per QP (256-lane kernels: always - two of them still share a CU's LDS up
@@ -112,31 +120,42 @@ int sm_solve(pqp_handle* h, int type, int batch, int n, const int32_t* n_of, int
 #undef PQP_BQ_PICK
     const int rc = lds_opt_in(fn, lds, "smoother QP too large for one CU's LDS");
     if (rc) return rc;
-    return h->launch_timed([&]() -> int {
+    const auto launch = [&]() -> int {
         void* kargs[] = {(void*)&a};
         PQP_HIP(hipLaunchKernel(fn, dim3(batch), dim3(threads), kargs, lds, h->stream));
         PQP_HIP(hipGetLastError());
         return PQP_OK;
-    });
+    };
+    return timed ? h->launch_timed(launch) : launch();
 }
 
-// does the generic banded core hold a smoother QP of this size (its vectors, factor rows and row data in one CU's LDS, one lane per padded variable)?
 bool sm_generic_fits(int type, int n) {
     const SmShape sh = sm_shape(type, n);
     const pqp::BqLayout lay{sh.nv, sh.nc, sh.bw};
     return (size_t)lay.total(false) * 8 <= kLdsPerCu && 64 * ((lay.nbb() + 63) / 64) <= 1024;
 }
 
-int sm_alloc(pqp_handle* h, int type, int batch, int n) {
+int sm_alloc(pqp_handle* h, BandedGroup& g, int type, int batch, int n) {
     const SmShape sh = sm_shape(type, n);
     int rc;
-    if ((rc = h->sm.pband.ensure((size_t)batch * (sh.pbw + 1) * sh.nv * 8)) || (rc = h->sm.q.ensure((size_t)batch * sh.nv * 8)) ||
-        (rc = h->sm.aval.ensure((size_t)batch * sh.nc * pqp::kRMax * 8)) || (rc = h->sm.lo.ensure((size_t)batch * sh.nc * 8)) ||
-        (rc = h->sm.up.ensure((size_t)batch * sh.nc * 8)) || (rc = h->sm.x.ensure((size_t)batch * sh.nv * 8)) || (rc = h->sm.y.ensure((size_t)batch * sh.nc * 8)))
+    if ((rc = g.pband.ensure((size_t)batch * (sh.pbw + 1) * sh.nv * 8)) || (rc = g.q.ensure((size_t)batch * sh.nv * 8)) ||
+        (rc = g.aval.ensure((size_t)batch * sh.nc * pqp::kRMax * 8)) || (rc = g.lo.ensure((size_t)batch * sh.nc * 8)) ||
+        (rc = g.up.ensure((size_t)batch * sh.nc * 8)) || (rc = g.x.ensure((size_t)batch * sh.nv * 8)) || (rc = g.y.ensure((size_t)batch * sh.nc * 8)))
         return rc;
-    return sm_upload_structure(h, type, n);
+    return sm_upload_structure(h, g, type, n);
 }
+
+}  // namespace pqp_internal
+
+namespace {
+// the smoothers' own group, under the handle's parameters
+int sm_solve(pqp_handle* h, int type, int batch, int n, const int32_t* n_of, int32_t* status, int32_t* iters, double* info) {
+    return sm_solve(h, h->sm, h->prm, type, batch, n, n_of, status, iters, info, true);
+}
+int sm_alloc(pqp_handle* h, int type, int batch, int n) { return sm_alloc(h, h->sm, type, batch, n); }
 }  // namespace
+
+extern "C" {
 
 static bool tension2_ok(pqp_handle* h, int batch, int n, const double* x_list, const double* y_list, const double* angle_list, const double* k_list,
                         const double* s_list, const double* out_x, const double* out_y, const double* out_s) {
