@@ -192,6 +192,16 @@ def finish(path, profile, su, found, x, status, dt):
     return dict(traj=rows, bounds=b, excess=excess, status=SOLVED, flags=REFINED)
 
 
+def finished_x(su, x):
+    """the (s, v, a) the call writes for a solved path from the solver's x, both in the order [s v a]: finish()'s clamps - s into its
+    corridor, v to 0 from below, a[m - 1] = 0"""
+    m = len(su["sigma"])
+    b = su["bounds"]
+    a = np.array(x[2 * m:], dtype=np.float64)
+    a[m - 1] = 0.0
+    return np.concatenate([np.fmin(np.fmax(x[:m], b[:, 0]), b[:, 1]), np.fmax(x[m:2 * m], 0.0), a])
+
+
 def from_interleaved(x3, m):
     """the device's (s, v, a)_k order -> [s(m) v(m) a(m)]"""
     return np.concatenate([x3[0::3][:m], x3[1::3][:m], x3[2::3][:m]])
@@ -223,7 +233,66 @@ def hand_wait():
     return dict(c, m=S.HAND_M, prm=dict(c["prm"], margin=1.0))
 
 
-CHECK_MARGIN = 0.5                                           # pqp_agents_check's margin for the refined waiting plan
+MAX_ITER = 2                                                 # PQP_STATUS_MAX_ITER
+HIGHS_TOL = 1e-9                                             # HiGHS's primal and dual feasibility tolerance in every verdict here
+HIGHS_SECONDS = 5.0
+
+# ---- the case families of tests/test_speed_refine_fallback.py and tests/test_gpu_speed_refine_fallback.py ------------------------------------
+# What the banded core does with polish = 1 after its direct active-set attempt is rejected (equilibration, ADMM, periodic polish
+# attempts, the infeasibility certificate) runs for these QPs; the lists were chosen on the host emulation from the grid a_max in
+# {0.8, 1.5, 1.6, 2.5} x d_max in {0.5, 3} x window in {1, 4, 12} x w_jerk in {0, 1, 50} and a few weights beside it.
+JERKY = ((1.0, 1.0, 50.0, 1.5, 3.0), 1)                     # a heavy jerk weight in a narrow corridor: the fallback solves every path from m = 85 on
+_STUCK = ((1.0, 1.0, 50.0, 1.5, 0.5), 1)                     # and with d_max = 0.5: no feasible point; the emulation ends two paths at MAX_ITER
+_SLOW = ((1.0, 4.0, 0.0, 0.8, 3.0), 1)                       # w_accel = 4, no jerk term, a_max = 0.8: one path by the fallback, two directly
+_EAGER = ((2.0, 1.0, 0.0, 1.5, 3.0), 4)                      # w_ref = 2, no jerk term: every path directly
+_HEAVY = ((1.0, 4.0, 1.0, 1.5, 3.0), 4)                      # w_accel = 4: 24 iterations from m = 130 on
+_LOOSE = ((0.5, 1.0, 50.0, 1.5, 3.0), 4)                     # w_ref = 0.5
+# "params": (search case, refine parameters [w_ref w_accel w_jerk a_max d_max], window)
+PARAMS = tuple((name,) + combo for name, combos in (
+    ("m8", (_STUCK, _SLOW)), ("m40", (JERKY, _STUCK)), ("m85", (JERKY, _STUCK, _SLOW, _EAGER, _LOOSE)),
+    ("m130", (JERKY, _STUCK, _SLOW)), ("m131", (JERKY, _STUCK, _SLOW, _EAGER)), ("m170", (_SLOW, _HEAVY)),
+    ("m171", (JERKY, _SLOW)), ("m193", (JERKY, _STUCK, _HEAVY))) for combo in combos)
+EDGE_M = (85, 86, 130, 131, 170, 171)                        # both sides of every form edge: under the defaults and under JERKY
+
+# "staircases": name -> (m, seed, draws, the draws kept in their order, refine parameters, window): one batch per (window, w_jerk) of
+# {1, 2, 4} x {0, 1, 50} under a_max = d_max = 0.6; kept are the draws the fallback solves, those without a feasible point and the first
+# few that are solved directly
+_STAIR_PRM = lambda w_jerk: (1.0, 1.0, w_jerk, 0.6, 0.6)
+STAIRCASES = {
+    "stairs_w1_j0": (8, 100, 200, (0, 1, 2, 3, 4, 5, 6, 7, 8, 36, 44, 83, 113, 128, 154, 160), _STAIR_PRM(0.0), 1),
+    "stairs_w1_j1": (12, 101, 200, (0, 1, 2, 3, 4, 5, 6, 16, 24, 36, 48, 61, 81, 125, 141, 165), _STAIR_PRM(1.0), 1),
+    "stairs_w1_j50": (8, 102, 200, (0, 1, 2, 3, 4, 5, 30, 104, 105, 110, 111, 126, 135, 193), _STAIR_PRM(50.0), 1),
+    "stairs_w2_j0": (12, 103, 200, (0, 1, 2, 3, 4, 5, 22, 40, 59, 61, 68, 75, 122, 127, 138, 163), _STAIR_PRM(0.0), 2),
+    "stairs_w2_j1": (8, 104, 200, (0, 1, 2, 3, 4, 5, 36, 97), _STAIR_PRM(1.0), 2),
+    "stairs_w2_j50": (12, 105, 200, (0, 1, 2, 3, 4, 5, 8, 18, 58, 185, 193), _STAIR_PRM(50.0), 2),
+    "stairs_w4_j0": (8, 106, 200, (0, 1, 2, 3, 4, 5, 6, 7), _STAIR_PRM(0.0), 4),
+    "stairs_w4_j1": (12, 107, 200, (0, 1, 2, 3, 4, 5, 88, 90, 104, 112, 148), _STAIR_PRM(1.0), 4),
+    "stairs_w4_j50": (8, 108, 200, (0, 1, 2, 3, 4, 5, 6, 37, 108, 138), _STAIR_PRM(50.0), 4),
+}
+STAIR_CALLS = tuple((name, v[4], v[5]) for name, v in STAIRCASES.items())
+
+# "threshold": the hand case "quick" is infeasible below a_max = THRESHOLD_A_MAX and feasible from it on - bisected on HiGHS's verdict
+# (2026-10-20, HIGHS_TOL = 1e-9, the interval left was 8e-13 wide); 1.0047 x 7 / 4.5
+THRESHOLD_A_MAX = 1.5629168251338
+THRESHOLD_NEAR = (1e-2, 1e-3)                                # these members follow HiGHS's verdict
+THRESHOLD_CLOSE = (1e-5, 1e-7)                               # these are within rounding of the edge: only the safety properties
+_around = lambda eps, sign: ("quick", (1.0, 1.0, 1.0, THRESHOLD_A_MAX * (1.0 + sign * eps), 3.0), DEFAULT_WINDOW)
+THRESHOLD_FOLLOWS = tuple(_around(eps, sign) for eps in THRESHOLD_NEAR for sign in (-1.0, 1.0))
+THRESHOLD_LEFT_OUT = tuple(_around(eps, sign) for eps in THRESHOLD_CLOSE for sign in (-1.0, 1.0))
+THRESHOLD = THRESHOLD_FOLLOWS + THRESHOLD_LEFT_OUT
+
+
+def verdict_class(one):
+    """the emulation's verdict on one refined path: "direct" (SOLVED at iteration 0), "fallback" (SOLVED later), "infeasible" or "max_iter\""""
+    e = one["emu"]
+    if e["status"] == SOLVED:
+        return "direct" if e["iters"] == 0 else "fallback"
+    return {PRIMAL_INFEASIBLE: "infeasible", MAX_ITER: "max_iter"}[e["status"]]
+
+
+def form_of_case(name):
+    return form_of_layers(searched(name)[2])
+CHECK_MARGIN = 0.5                                     # pqp_agents_check's margin for the refined waiting plan
 
 
 def seeded(name):
@@ -262,50 +331,162 @@ def layout_doubles(m):
     return nb * 4 * bw + (nb // 2 + 1) * 2 * bw * bw + nv + 4 * nbb + 3 * nv + 12 * nc + 128
 
 
+def refine_shape(m):
+    """sm_shape (pqp_smoothers.hip) for kBandedRefine: variables, rows, block size, half-bandwidth of P"""
+    return dict(nv=3 * m, nc=5 * m - 2, bw=3, pbw=3)
+
+
+def form_of_layers(m):
+    """(B, MAXT, STAGE) of the kernel sm_solve launches for the refine's QP of m layers, None where the core does not hold it: banded_cases'
+    selection on the refine's shape"""
+    import banded_cases as BC
+    sh = refine_shape(m)
+    lay = BC.layout(sh["nv"], sh["nc"], sh["bw"])
+    threads = 64 * ((lay["nbb"] + 63) // 64)
+    if lay["plain"] * 8 > BC.LDS_PER_CU or threads > 1024:
+        return None
+    stage = threads <= 512 and lay["staged"] * 8 <= BC.LDS_PER_CU
+    if threads <= 256 and stage:
+        return (sh["bw"], 256, 1)
+    if threads <= 512:
+        return (sh["bw"], 512, 1 if stage else 0)
+    return (sh["bw"], 1024, 0)
+
+
+# first m, last m, form: every form the refine's shape selects; one layer more than the last does not fit
+FORM_RANGES = ((2, 85, (3, 256, 1)), (86, 130, (3, 512, 1)), (131, 170, (3, 512, 0)), (171, 193, (3, 1024, 0)))
+FIRST_PLAIN_M = 131                                          # from here on the device runs a non-staged form: the emulation runs both
+
+
+# ---- "staircases": many different QPs in one call ---------------------------------------------------------------------------------------------
+def staircase_draws(m, seed, count, q_top=6):
+    """`count` seeded staircases of m layers on the hand road (hand_rest's path, profile and grid): the step q_k a random walk in 0 .. q_top
+    with |q_k+1 - q_k| <= 2, j_k their running sum from j_0 = 0; a draw that leaves the path (j > j_last) is drawn again.  v_start lies
+    within 0.2 m/s of q_0 ds / dt.  -> (case, res): what searched() returns for a search case, `blocked` zeros, reached = m, and traj the
+    rows search_util.search writes for those steps"""
+    base = hand_rest()
+    grid = S.params(**base["prm"])
+    path, profile = base["paths"][0], base["profile"][0]
+    J, _, pose, _, _ = S.stations(path, profile, path.shape[0], grid)
+    ds, dt = np.float64(grid["ds"]), np.float64(grid["dt"])
+    rng = np.random.default_rng(seed)
+    steps, v_start = np.zeros((count, m, 2), np.int32), np.zeros(count)
+    got = 0
+    while got < count:
+        q = np.zeros(m, np.int64)
+        q[0] = rng.integers(0, q_top + 1)
+        for k in range(1, m):
+            q[k] = min(max(q[k - 1] + rng.integers(-2, 3), 0), q_top)
+        j = np.concatenate([[0], np.cumsum(q[:-1])])         # layer k + 1 stands q_k cells behind layer k
+        v0 = max(0.0, float(q[0]) * float(ds / dt) + rng.uniform(-0.2, 0.2))
+        if j[-1] > J - 1:
+            continue
+        steps[got, :, 0], steps[got, :, 1], v_start[got] = j, q, v0
+        got += 1
+    traj = np.zeros((count, m, 8))
+    for b in range(count):
+        for k in range(m):
+            j, q = (int(v) for v in steps[b, k])
+            dq = int(steps[b, k + 1, 1]) - q if k + 1 < m else 0
+            traj[b, k] = [pose[j, 0], pose[j, 1], pose[j, 2], pose[j, 3], np.float64(j) * ds, np.float64(q) * ds / dt, np.float64(dq) * ds / (dt * dt),
+                          np.float64(k) * dt]
+    case = dict(paths=np.repeat(base["paths"], count, axis=0), profile=np.repeat(base["profile"], count, axis=0), v_start=v_start, prm=grid, m=m,
+                n_of=None, stop_before=None)
+    res = dict(blocked=np.zeros((count, m, S.words(grid["stations"])), np.int32), steps=steps, reached=np.full(count, m, np.int32), traj=traj)
+    return case, res
+
+
+def staircases(name):
+    """the batch `name` of STAIRCASES: the draws listed there, in that order"""
+    m, seed, count, keep = STAIRCASES[name][:4]
+    c, res = staircase_draws(m, seed, count)
+    keep = np.asarray(keep)
+    c = {k: (v[keep] if k in ("paths", "profile", "v_start") else v) for k, v in c.items()}
+    return c, {k: v[keep] for k, v in res.items()}
+
+
 def circles_of(name):
     import footprint_util as F
-    return F.car_circles(**S.HAND_CAR) if name in HAND else F.car_circles()
+    return F.car_circles(**S.HAND_CAR) if name in HAND or name in STAIRCASES else F.car_circles()
 
 
-_REFERENCE = {}
+_REFERENCE, _SEARCHED = {}, {}
 
 
-def reference(name, highs=True):
-    """one case through the search's restatement, the setup, the core's host emulation and (highs) HiGHS, computed once and shared;
-    nobody writes to it.  dict(case, res, m, each = [dict(su, found, emu, xe, xh, highs)]): xe / xh in the order [s v a], None where the
-    path is kept or the solver found the QP infeasible; highs: HiGHS's model status"""
-    key = (name, highs)
-    if key in _REFERENCE:
-        return _REFERENCE[key]
+def searched(name):
+    """(case, what the search's restatement writes for it, m) of a case by name, computed once; nobody writes to it"""
+    if name not in _SEARCHED:
+        if name in STAIRCASES:
+            c, res = staircases(name)
+        else:
+            c = seeded(name)
+            res = S.run_case(c, circles_of(name))
+        _SEARCHED[name] = (c, res, c.get("m") or c["agents"].shape[2])
+    return _SEARCHED[name]
+
+
+def highs_verdict(P, q, A, lo, up):
+    """(x or None, HiGHS's model status).  Its active-set solver cycles on an ordering now and then: each run has HIGHS_SECONDS, after
+    which highs_qp.solve_qp hands the QP over in another ordering"""
     import scipy.sparse as sp
 
+    import highs_qp as H
+    try:
+        return H.solve_qp(P, q, A, lo, up, tol=HIGHS_TOL, time_limit=HIGHS_SECONDS)[0], "Optimal"
+    except RuntimeError:
+        x, _, status = H._solve_once(sp.csc_matrix(P), q, sp.csc_matrix(A), lo, up, HIGHS_TOL, HIGHS_SECONDS)
+        return (None, status) if x is None else (x, "Optimal (rows missed)")
+
+
+def reference(name, highs=True, prm=None, window=None):
+    """one case through the search's restatement, the setup under the refine's parameters (prm [5], window; the defaults when None), the
+    core's host emulation and (highs) HiGHS, computed once and shared; nobody writes to it.  dict(case, res, m, prm, window, each =
+    [dict(su, found, emu, plain, xe, xh, highs)]): emu: the emulation's staged form, plain: its non-staged form where the device runs one
+    (m >= FIRST_PLAIN_M); xe / xh in the order [s v a], None where the path is kept or the solver found the QP infeasible; highs:
+    HiGHS's model status"""
+    prm = DEFAULT_PRM if prm is None else np.asarray(prm, dtype=np.float64)
+    window = DEFAULT_WINDOW if window is None else int(window)
+    key = (name, highs, tuple(prm.tolist()), window)
+    if key in _REFERENCE:
+        return _REFERENCE[key]
     import banded_util as B
     import emu_util as E
-    import highs_qp as H
-    c = seeded(name)
-    res = S.run_case(c, circles_of(name))
-    m = c.get("m") or c["agents"].shape[2]
+    c, res, m = searched(name)
     each = []
     for b in range(len(c["paths"])):
         pick = lambda a: None if a is None else a[b]
         found = found_of(res, b)
-        su = setup(c["paths"][b], c["profile"][b], c["v_start"][b], found, m, pick(c.get("n_of")), pick(c.get("stop_before")), c["prm"])
-        one = dict(su=su, found=found, emu=None, xe=None, xh=None, highs=None)
+        su = setup(c["paths"][b], c["profile"][b], c["v_start"][b], found, m, pick(c.get("n_of")), pick(c.get("stop_before")), c["prm"], prm, window)
+        one = dict(su=su, found=found, emu=None, plain=None, xe=None, xh=None, highs=None)
         if not su["kept"]:
             P, q, A, lo, up = su["qp"]
-            one["emu"] = B.emu_solve(E.production(polish=1), B.to_banded(P, q, A, lo, up, B.interleave3(m)))
+            bd = B.to_banded(P, q, A, lo, up, B.interleave3(m))
+            one["emu"] = B.emu_solve(E.production(polish=1), bd)
+            if m >= FIRST_PLAIN_M:
+                one["plain"] = B.emu_solve(E.production(polish=1), bd, stage=False)
             if one["emu"]["status"] == SOLVED:
                 one["xe"] = from_interleaved(one["emu"]["x"], m)
             if highs:
-                try:
-                    one["xh"], one["highs"] = H.solve_qp(P, q, A, lo, up)[0], "Optimal"
-                except RuntimeError:
-                    one["highs"] = H._solve_once(sp.csc_matrix(P), q, sp.csc_matrix(A), lo, up, 1e-9)[2]
+                one["xh"], one["highs"] = highs_verdict(P, q, A, lo, up)
         each.append(one)
-    _REFERENCE[key] = dict(case=c, res=res, m=m, each=each)
+    _REFERENCE[key] = dict(case=c, res=res, m=m, prm=prm, window=window, each=each)
     return _REFERENCE[key]
+
 
 # what tests/test_speed_refine.py measures over GPU_CASES on the emulation (its docstring has the figures to three digits); the GPU test's
 # bounds are 4 x KKT_WORST and 2 x HIGHS_DIST
 KKT_WORST = dict(stationarity=3.6e-8, primal=3.0e-8, complementarity=2.6e-7)
 HIGHS_DIST = 2.9e-6
+# the same over the families above, where the core's fallback runs (tests/test_speed_refine_fallback.py measures them over FIGURES_QPS
+# solved QPs): the emulation's own multipliers, the multipliers recovered from x alone, the distance to HiGHS.  The complementarity is
+# the same figure either way - a multiplier times the distance a row that counts as active is left off its bound - and a hundred times
+# KKT_WORST's.  KKT_RETURNED_FALLBACK: the recovered-multiplier figures of what the call returns for the emulation's x, finished_x() - the
+# clamps move a variable by what the polish leaves an active row off its bound (up to 6e-8 here: a[m - 1] = 0, s into its corridor),
+# and under w_jerk = 50 the jerk term's Hessian entries of 2 w_jerk / dt^2 = 100 turn that into a stationarity residual of 3.5e-6.
+# tests/test_gpu_speed_refine_fallback.py certifies the rows the device returns the same way and holds them to 4 x KKT_RETURNED_FALLBACK
+# and 2 x the distance
+KKT_WORST_FALLBACK = dict(stationarity=1.0e-7, primal=8.7e-8, complementarity=3.1e-5)
+KKT_RECOVERED_FALLBACK = dict(stationarity=6.2e-8, primal=8.7e-8, complementarity=3.1e-5)
+KKT_RETURNED_FALLBACK = dict(stationarity=3.5e-6, primal=1.6e-7, complementarity=5.5e-5)
+HIGHS_DIST_FALLBACK = 4.7e-6
+FIGURES_QPS = 173
