@@ -1174,7 +1174,8 @@ enum { PQP_REFINE_REFINED = 1, PQP_REFINE_KEPT = 2, PQP_REFINE_INFEASIBLE = 4 };
  *              runs above the envelope where it actually is.  vcap_k is the largest envelope speed of the window, it does not tie v_k to
  *              s_k inside it, so excess may be positive: a limit of this QP, reported and not hidden
  * What the refine does not promise: that the refined plan is clear of every agent (stations between two free cells are not tested, as in
- * the search), and that a feasible refinement exists.
+ * the search; pqp_sample_plan puts the plan on a fine time step for pqp_agents_check to take that verdict), and that a feasible refinement
+ * exists.
  * A path's result depends on its own rows and the parameters alone: the same bits at any batch position and from either form; no atomics.
  * The _device form is four launches (the corridor, the assembly, the solve, the placement), asynchronous on the handle's stream; its QP
  * arrays and the corridor are the handle's own, apart from the smoothers', sized on first use and reused, and the rows' sparsity is uploaded
@@ -1191,6 +1192,62 @@ int pqp_speed_refine(pqp_handle* h, const pqp_search_params* grid, const double*
                      const double* paths, const int32_t* n_of, const int32_t* stop_before, const double* profile, const double* v_start, int m,
                      const int32_t* blocked, const int32_t* steps, const int32_t* reached, const double* search_traj, double* traj,
                      double* bounds, double* cost, double* excess, int32_t* status, int32_t* iters, int32_t* flags);
+
+/* ---- speed plans on a fine time step --------------------------------------------------------------------------------------------------------
+ * pqp_speed_search and pqp_speed_refine write a plan as m rows, one per layer, dt (a second, by default) apart.  A controller tracks a
+ * trajectory at a tenth of that, and an agent that crosses the lane between two layers is seen by neither the occupancy nor a check of the
+ * m rows.  This puts every plan on r sub-steps per layer with the plan's own kinematics and places those stations on the path by the walk
+ * the search and the refine share; the rows are pqp_agents_check's input, so the last verdict is taken at the resolution the agents are
+ * predicted at.  The reference has no counterpart: it has no time axis. */
+enum { PQP_PLAN_EMPTY = 1, PQP_PLAN_NOT_FINITE = 2, PQP_PLAN_BACKWARD = 4 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional.  dt, r and linear
+ * travel by value, as pqp_agents_check's margin does:
+ *   paths, n_of, stop_before, profile    exactly what pqp_speed_search and pqp_speed_refine got; c, the driven count, by the same expression
+ *   plan [batch][m][PQP_TRAJ_STRIDE]     pqp_speed_refine's traj, pqp_speed_search's traj or any array of that shape: s, v, a at 4, 5, 6 are
+ *                                        read.  Layer k is at time (double)k * dt
+ *   count_of [batch] or NULL             the planned layers, L = min(max(count_of, 0), m): the search's `reached`.  NULL: m
+ *   refine_flags [batch] or NULL         NULL: every path has the kinematics `linear` says (0: constant acceleration, 1: linear).  Given: a
+ *                                        path with PQP_REFINE_REFINED set has constant acceleration, every other path is linear, and
+ *                                        `linear` is not read - pqp_speed_refine's output goes in as it is.  A refined path satisfies the
+ *                                        constant-acceleration rows; a kept one is the search's staircase, which does not, and a step of q
+ *                                        cells is a straight line in the path-time plane: the swept range the search tested
+ *   r >= 1                               sub-steps per layer: M = (m - 1) * r + 1 fine samples per path
+ * Outputs, fully overwritten:
+ *   fine [batch][M][PQP_TRAJ_STRIDE]     x, y, heading, k, s, v, a, t
+ *   m_of [batch]                         the samples on the plan; the rows behind them are zeros
+ *   defect, excess [batch] or NULL       see below
+ *   flags [batch]
+ * The definition, in fp64, every product and sum rounded on its own (no contraction), min and max as fmin and fmax, for a path with c >= 1
+ * and L >= 1 (s_k, v_k, a_k: columns 4, 5, 6 of plan row k):
+ *   m_of       (L - 1) * r + 1
+ *   sample f < m_of - 1   belongs to layer k = f / r at sub-step i = f % r;  u = ((double)i * dt) / (double)r
+ *              constant acceleration:  sk = s_k + (v_k + (0.5 * a_k) * u) * u (pqp_sample_trajectory's expression);  v = max(v_k + a_k * u, 0);
+ *                                      a = a_k
+ *              linear:                 sk = s_k + ((s_{k+1} - s_k) * (double)i) / (double)r;  v = (s_{k+1} - s_k) / dt;  a = 0
+ *              both:                   s = min(max(sk, s_k), max(s_{k+1}, s_k)) - of a refined plan only the solver's tolerance is clamped
+ *                                      away; a layer with s_{k+1} < s_k stands at s_k and sets PQP_PLAN_BACKWARD;  t = (double)k * dt + u
+ *   sample f = m_of - 1   is row L - 1 itself: its s, max(v, 0), a, and t = (double)(L - 1) * dt
+ *   x, y, heading, k      pqp_speed_search's "pose at sigma_j" with s in place of sigma_j.  So at i = 0 a row has the plan row's x, y,
+ *              heading, k, s and t bit for bit, and r = 1 under constant acceleration returns a refined plan in all eight columns
+ *   defect     how far the plan is from its own kinematics: under constant acceleration max over k < L - 1 of
+ *              |(s_k + (v_k + (0.5 * a_k) * dt) * dt) - s_{k+1}|; 0 for a linear path or L = 1.  Reported, as excess is, not hidden
+ *   excess     max over the samples on the plan of v - sqrt(max(w, 0)), w the search's envelope expression at the placed pose:
+ *              pqp_speed_refine's excess, taken between the layers as well
+ *   flags      PQP_PLAN_EMPTY, alone: c = 0 or L = 0; the rows are zeros, m_of = 0, defect and excess NaN.  PQP_PLAN_NOT_FINITE, alone: a
+ *              path row below c that is not finite in x, y, heading, k, s, v or a, or a plan row below L whose s, v or a is not; all M
+ *              rows are NaN, m_of = 0, defect and excess NaN, and the neighbours are untouched.  PQP_PLAN_BACKWARD: as above
+ * A path's result depends on its own rows and the parameters alone: the same bits at any batch position and from either form; no atomics.
+ * The _device form is one launch, asynchronous on the handle's stream, and allocates nothing; n, m and r are bounded only by M fitting an
+ * int.  The host form copies in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the outputs
+ * untouched, for a null pointer that is not optional, batch < 1, n < 1, m < 1, r < 1, stride < 6, a dt that is not finite and positive, a
+ * linear other than 0 or 1, or (m - 1) * r + 1 > INT_MAX. */
+int pqp_sample_plan_device(pqp_handle* h, double dt, int r, int linear, int batch, int n, int stride, const double* paths,
+                           const int32_t* n_of, const int32_t* stop_before, const double* profile, int m, const double* plan,
+                           const int32_t* count_of, const int32_t* refine_flags, double* fine, int32_t* m_of, double* defect,
+                           double* excess, int32_t* flags);
+int pqp_sample_plan(pqp_handle* h, double dt, int r, int linear, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                    const int32_t* stop_before, const double* profile, int m, const double* plan, const int32_t* count_of,
+                    const int32_t* refine_flags, double* fine, int32_t* m_of, double* defect, double* excess, int32_t* flags);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
 //   params()                              the PQP_REFINE_PARAMS doubles to edit, by PQP_REFINE_W_REF .. PQP_REFINE_D_MAX
 //   window()                              the corridor's half-width in cells, to edit
 //   refine(paths, v_start, scenes, ...)   per path the states of every layer, PQP_REFINE_* flags, the QP's status, cost and excess
+//   refine_raw(...)                       the same calls with the C ABI's arrays left to the caller (PlanSampler's input)
 //
 // Not copyable, not thread-safe, no exceptions; refine() returns false on a GPU error or a bad argument (pqp_last_error()).
 #pragma once
@@ -36,32 +37,33 @@ class SpeedRefiner {
         std::vector<double> lo, hi, vcap; // the corridor of every layer; zeros for a path that is kept
     };
 
+    // what the two calls wrote, as the C ABI has it (PlanSampler's input): the search's arrays, then pqp_speed_refine's
+    struct Raw {
+        SpeedSearcher::Raw search;
+        std::vector<double> traj, bounds, cost, excess;     // [B][m][8], [B][m][3], [B], [B]
+        std::vector<int32_t> status, iters, flags;          // [B]
+    };
+
     // paths, v_start, scenes, scene_of, layers: SpeedSearcher::search's
     // results: per path the outcome; states: per path the state of every layer the search reached - x, y, heading, k, s, v, a
     template <class StateT>
     bool refine(const std::vector<std::vector<StateT>>& paths, const std::vector<double>& v_start,
                 const std::vector<std::vector<std::vector<PredictedAgent>>>& scenes, std::vector<Result>* results,
                 std::vector<std::vector<StateT>>* states, const std::vector<int>* scene_of = nullptr, int layers = 1) {
-        SpeedSearcher::Raw raw;
-        if (!results || !states || !searcher_.search_raw(paths, v_start, scenes, scene_of, layers, true, &raw)) return false;
-        const size_t B = raw.B, m = raw.m;
-        std::vector<double> traj(B * m * PQP_TRAJ_STRIDE), bounds(B * m * 3), cost(B), excess(B);
-        std::vector<int32_t> status(B), iters(B), flags(B);
-        if (pqp_speed_refine(&searcher_.handle(), &searcher_.params(), prm_, window_, (int)B, (int)raw.n, 6, raw.rows.data(), raw.n_of.data(), nullptr,
-                             raw.profile.data(), v_start.data(), (int)m, raw.blocked.data(), raw.steps.data(), raw.reached.data(), raw.traj.data(),
-                             traj.data(), bounds.data(), cost.data(), excess.data(), status.data(), iters.data(), flags.data()) != PQP_OK)
-            return false;
+        Raw raw;
+        if (!results || !states || !refine_raw(paths, v_start, scenes, scene_of, layers, &raw)) return false;
+        const size_t B = raw.search.B, m = raw.search.m;
         results->assign(B, Result());
         states->assign(B, std::vector<StateT>());
         for (size_t b = 0; b < B; ++b) {
             Result& r = (*results)[b];
-            r.flags = flags[b]; r.status = status[b]; r.search_flags = raw.flags[b]; r.cost = cost[b]; r.excess = excess[b];
+            r.flags = raw.flags[b]; r.status = raw.status[b]; r.search_flags = raw.search.flags[b]; r.cost = raw.cost[b]; r.excess = raw.excess[b];
             for (size_t k = 0; k < m; ++k) {
-                const double* c = &bounds[(b * m + k) * 3];
+                const double* c = &raw.bounds[(b * m + k) * 3];
                 r.lo.push_back(c[0]); r.hi.push_back(c[1]); r.vcap.push_back(c[2]);
             }
-            for (int k = 0; k < raw.reached[b]; ++k) {
-                const double* row = &traj[(b * m + k) * PQP_TRAJ_STRIDE];
+            for (int k = 0; k < raw.search.reached[b]; ++k) {
+                const double* row = &raw.traj[(b * m + k) * PQP_TRAJ_STRIDE];
                 StateT st{};
                 st.x = row[0]; st.y = row[1]; st.heading = row[2]; st.k = row[3]; st.s = row[4]; st.v = row[5]; st.a = row[6];
                 (*states)[b].push_back(st);
@@ -69,6 +71,23 @@ class SpeedRefiner {
         }
         return true;
     }
+
+    // the same two calls with the C ABI's arrays left to the caller
+    template <class StateT>
+    bool refine_raw(const std::vector<std::vector<StateT>>& paths, const std::vector<double>& v_start,
+                    const std::vector<std::vector<std::vector<PredictedAgent>>>& scenes, const std::vector<int>* scene_of, int layers, Raw* out) {
+        if (!out || !searcher_.search_raw(paths, v_start, scenes, scene_of, layers, true, &out->search)) return false;
+        const SpeedSearcher::Raw& raw = out->search;
+        const size_t B = raw.B, m = raw.m;
+        out->traj.assign(B * m * PQP_TRAJ_STRIDE, 0.0); out->bounds.assign(B * m * 3, 0.0); out->cost.assign(B, 0.0); out->excess.assign(B, 0.0);
+        out->status.assign(B, 0); out->iters.assign(B, 0); out->flags.assign(B, 0);
+        return pqp_speed_refine(&searcher_.handle(), &searcher_.params(), prm_, window_, (int)B, (int)raw.n, 6, raw.rows.data(), raw.n_of.data(), nullptr,
+                                raw.profile.data(), v_start.data(), (int)m, raw.blocked.data(), raw.steps.data(), raw.reached.data(), raw.traj.data(),
+                                out->traj.data(), out->bounds.data(), out->cost.data(), out->excess.data(), out->status.data(), out->iters.data(),
+                                out->flags.data()) == PQP_OK;
+    }
+
+    SpeedSearcher& searcher() { return searcher_; }
 
  private:
     SpeedSearcher& searcher_;

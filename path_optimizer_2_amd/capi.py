@@ -413,7 +413,8 @@ class Handle:
 
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
-                      agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None, t0=None, speed=None, v_start=None, v_end=None):
+                      plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
+                      t0=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -443,29 +444,36 @@ class Handle:
         the rows it ran on, with its v_start: the agents' step count is the number of layers m (with sample too, that is `samples`, and
         both run).  Adds search_steps [..][m][2], search_traj [..][m][8], search_cost, search_reached and search_flags.
         refine: RefineParams (needs search) - pqp_speed_refine_device behind the search on the same stream, on the rows the search ran on and
-        on what it wrote.  Adds search_blocked [..][m][W] (what the refine read), refine_traj [..][m][8], refine_bounds [..][m][3], refine_cost, refine_excess, refine_status and refine_flags."""
+        on what it wrote.  Adds search_blocked [..][m][W] (what the refine read), refine_traj [..][m][8], refine_bounds [..][m][3], refine_cost, refine_excess, refine_status and refine_flags.
+        plan_samples: r >= 1 (needs search) - pqp_sample_plan_device behind the refine on the same stream, r sub-steps per layer of the grid's
+        dt: with refine on its traj and flags (a refined path under constant acceleration, a kept one linearly) and the search's reached,
+        without refine on the search's traj, linearly.  Adds plan_traj [..][(m - 1) r + 1][8], plan_m_of, plan_defect, plan_excess and
+        plan_flags.  plan_agents: [n_scenes][a_max][(m - 1) r + 1][6], the agents of `agents` on the fine steps - pqp_agents_check_device behind
+        that on plan_traj and plan_m_of, under agents_params' margin and the same agents_of / scene_of; adds plan_first_hit and
+        plan_hit_agent."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents), self._refine(refine, search))
+                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False, search=None, refine=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None,
+                              winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None,
+                              agents_params=None, sample=None,
                               samples=None, t0=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
-        agents_params / search / refine: as for optimize_path)."""
+        agents_params / search / refine / plan_samples / plan_agents: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents), self._refine(refine, search))
+                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents))
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -510,6 +518,28 @@ class Handle:
             raise ValueError("refine needs search=SearchParams: it refines the plan the search wrote")
         return refine
 
+    def _plan(self, plan_samples, plan_agents, search, agents):
+        if plan_samples is None:
+            if plan_agents is not None:
+                raise ValueError("plan_agents needs plan_samples=r: the agents are given at the fine steps")
+            return None
+        if search is None:
+            raise ValueError("plan_samples needs search=SearchParams: the plan it samples is the search's or the refine's")
+        if isinstance(plan_samples, bool) or int(plan_samples) != plan_samples or int(plan_samples) < 1:
+            raise ValueError("plan_samples must be a whole number of sub-steps per layer, >= 1")
+        r = int(plan_samples)
+        layers = np.shape(agents)[2]                                   # (search needs agents: _search has checked that they are there)
+        fine = (layers - 1) * r + 1
+        if fine > 2 ** 31 - 1:
+            raise ValueError(f"plan_samples: (m - 1) r + 1 = {fine} samples per path do not fit an int")
+        if plan_agents is not None:
+            plan_agents = np.ascontiguousarray(plan_agents, dtype=np.float64)
+            want = tuple(np.shape(agents)[:2]) + (fine, AGENT_STRIDE)
+            if plan_agents.shape != want:
+                raise ValueError(f"plan_agents must be [n_scenes][a_max][(m - 1) r + 1][{AGENT_STRIDE}] = {want}, the scenes and agents of agents=, "
+                                 f"not {plan_agents.shape}")
+        return (r, plan_agents)
+
     def _agents(self, agents, agents_of, scene_of, agents_params, sample, samples, car, batch, select, search=None):
         if agents is None:
             if agents_of is not None or scene_of is not None or agents_params is not None:
@@ -544,14 +574,14 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None):
+               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None, planning=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
         of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None; moving:
         (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that (when there is a sampling), or
         None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None; refining: RefineParams
-        of the speed QP behind that search, or None"""
+        of the speed QP behind that search, or None; planning: (r, plan_agents or None) of the plan's fine time step behind both, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -611,6 +641,16 @@ class Handle:
             rf_bounds = torch.zeros((rows, layers, 3), dtype=torch.float64, device=dev)
             rf_cost, rf_excess = (torch.zeros(rows, dtype=torch.float64, device=dev) for _ in range(2))
             rf_status, rf_iters, rf_flags = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(3))
+        if planning is not None:
+            pl_r, pl_ag = planning
+            pl_m = (layers - 1) * pl_r + 1
+            pl_traj = torch.zeros((rows, pl_m, TRAJ_STRIDE), dtype=torch.float64, device=dev)
+            pl_m_of, pl_flags = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
+            pl_defect, pl_excess = (torch.zeros(rows, dtype=torch.float64, device=dev) for _ in range(2))
+            if pl_ag is not None:
+                d_pl_ag = t(pl_ag, np.float64)
+                pl_frames = torch.zeros(pl_ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
+                pl_first, pl_who = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -664,6 +704,18 @@ class Handle:
                                                          first if (footprint is not None and not on_winners) else None, profile, d_vs, layers,
                                                          se_blocked, se_steps, se_reached, se_traj, rf_traj, rf_bounds, rf_cost, rf_excess,
                                                          rf_status, rf_iters, rf_flags))
+        if planning is not None:            # behind the refine (or the search alone), on the rows they ran on and on the plan they wrote
+            on_winners = selection is not None
+            self._check(self.lib.pqp_sample_plan_device(self._h, float(searching.dt), pl_r, 0 if refining is not None else 1, rows, cfg.n_max, 7,
+                                                        best_paths if on_winners else out, best_n if on_winners else ints[0],
+                                                        first if (footprint is not None and not on_winners) else None, profile, layers,
+                                                        rf_traj if refining is not None else se_traj, se_reached,
+                                                        rf_flags if refining is not None else None, pl_traj, pl_m_of, pl_defect, pl_excess,
+                                                        pl_flags))
+            if pl_ag is not None:           # behind that, on the fine rows that are on the plan
+                self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, pl_m, TRAJ_STRIDE, pl_traj,
+                                                             pl_m_of, pl_ag.shape[0], pl_ag.shape[1], d_pl_ag if pl_ag.size else None, d_ag_of,
+                                                             d_scene, pl_frames if pl_ag.size else None, pl_first, pl_who, None))
         self.sync()
         if smoother is not None:
             smoother.sync()
@@ -691,6 +743,11 @@ class Handle:
         if refining is not None:
             res.update(search_blocked=host(se_blocked), refine_traj=host(rf_traj), refine_bounds=host(rf_bounds), refine_cost=host(rf_cost), refine_excess=host(rf_excess),
                        refine_status=host(rf_status), refine_flags=host(rf_flags))
+        if planning is not None:
+            res.update(plan_traj=host(pl_traj), plan_m_of=host(pl_m_of), plan_defect=host(pl_defect), plan_excess=host(pl_excess),
+                       plan_flags=host(pl_flags))
+            if pl_ag is not None:
+                res.update(plan_first_hit=host(pl_first), plan_hit_agent=host(pl_who))
         return res
 
     def distance_layer(self, grid, geom):
@@ -888,6 +945,36 @@ class Handle:
         self._check(self.lib.pqp_speed_refine(self._h, C.byref(grid), prm.array(), int(prm.window), B, n, stride, paths, no, sb, profile, vs, m, blk,
                                               stp, rch, search_traj, traj, bounds, cost, excess, status, iters, flags))
         return dict(traj=traj, bounds=bounds, cost=cost, excess=excess, status=status, iters=iters, flags=flags)
+
+    def sample_plan(self, paths, profile, plan, r, dt=1.0, n_of=None, stop_before=None, count_of=None, refine_flags=None, linear=False):
+        """pqp_sample_plan (host arrays): paths [B][n][stride >= 6], profile [B][n][4] and optionally n_of [B], stop_before [B] as
+        speed_search and speed_refine got them; plan [B][m][8]: the traj either of them returned, dt the grid's; r sub-steps per layer;
+        count_of [B]: the planned layers (the search's reached; None: m); refine_flags [B]: speed_refine's flags - a REFINED path is sampled
+        under constant acceleration, every other path linearly (None: every path by `linear`).  Returns dict(traj [B][(m - 1) r + 1][8],
+        m_of [B]: the samples on the plan, defect [B], excess [B], flags [B] of PLAN_*)."""
+        paths = np.ascontiguousarray(paths, dtype=np.float64)
+        B, n, stride = paths.shape
+        profile = np.ascontiguousarray(profile, dtype=np.float64)
+        if profile.shape != (B, n, SPEED_STRIDE):
+            raise ValueError(f"sample_plan: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        plan = np.ascontiguousarray(plan, dtype=np.float64)
+        if plan.ndim != 3 or plan.shape[0] != B or plan.shape[2] != TRAJ_STRIDE:
+            raise ValueError(f"sample_plan: plan must be [{B}][m][{TRAJ_STRIDE}], not {plan.shape}")
+        m, r = plan.shape[1], int(r)
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        no, sb, co, rfl = i32(n_of), i32(stop_before), i32(count_of), i32(refine_flags)
+        for name, a in (("n_of", no), ("stop_before", sb), ("count_of", co), ("refine_flags", rfl)):
+            if a is not None and a.size != B:
+                raise ValueError(f"sample_plan: {name} must have {B} entries, not {a.size}")
+        M = max(m - 1, 0) * max(r, 0) + 1
+        if M > 2 ** 31 - 1:
+            raise ValueError(f"sample_plan: (m - 1) r + 1 = {M} samples per path do not fit an int")
+        traj = np.zeros((B, M, TRAJ_STRIDE))
+        m_of, flags = np.zeros(B, dtype=np.int32), np.zeros(B, dtype=np.int32)
+        defect, excess = np.zeros(B), np.zeros(B)
+        self._check(self.lib.pqp_sample_plan(self._h, float(dt), r, int(linear), B, n, stride, paths, no, sb, profile, m, plan, co, rfl, traj, m_of,
+                                             defect, excess, flags))
+        return dict(traj=traj, m_of=m_of, defect=defect, excess=excess, flags=flags)
 
     def corridor_params(self, **over):
         return _defaults(self.lib, PqpCorridorParams, "pqp_corridor_default_params", over)

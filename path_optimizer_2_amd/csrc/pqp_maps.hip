@@ -3,7 +3,8 @@
 // group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc), samples of those trajectories on a time grid
 // (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc), speeds that pass those agents in
 // the path-time plane (pqp_search_kernels.inc), the speed QP that makes such a plan drivable (pqp_refine_kernels.inc; its solve is the
-// banded core's, launched from pqp_smoothers.hip).  Their kernels, launchers and entry points.
+// banded core's, launched from pqp_smoothers.hip), those plans on a fine time step (pqp_plan_kernels.inc).  Their kernels, launchers and
+// entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +37,7 @@ using namespace pqp_internal;
 #include "pqp_agents_kernels.inc"
 #include "pqp_search_kernels.inc"
 #include "pqp_refine_kernels.inc"
+#include "pqp_plan_kernels.inc"
 
 // ---- what the entry points below share ------------------------------------------------------------------------------------------------
 // the grid of a kernel that gives every item a wavefront, threads / 64 of them to a workgroup
@@ -631,6 +633,57 @@ int pqp_speed_refine(pqp_handle* h, const pqp_search_params* grid, const double*
     return st.run([&]() -> int {
         return pqp_speed_refine_device(h, grid, prm, window, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, d_start, m, d_blocked, d_steps,
                                        d_reached, d_from, d_traj, d_bounds, d_cost, d_excess, d_status, d_iters, d_flags);
+    });
+}
+
+// ---- speed plans on a fine time step --------------------------------------------------------------------------------------------------------
+static const char* const kPlanRefusal =
+    "pqp_sample_plan: bad argument (batch >= 1; n >= 1; m >= 1; r >= 1; stride >= 6; dt finite and > 0; linear 0 or 1; (m - 1) * r + 1 <= INT_MAX)";
+
+static bool plan_ok(pqp_handle* h, double dt, int r, int linear, int batch, int n, int stride, const double* paths, const double* profile, int m,
+                    const double* plan, const double* fine, const int32_t* m_of, const int32_t* flags) {
+    return h && paths && profile && plan && fine && m_of && flags && batch >= 1 && n >= 1 && m >= 1 && r >= 1 && stride >= 6 && std::isfinite(dt) &&
+           dt > 0.0 && (linear == 0 || linear == 1) && (long long)(m - 1) * r + 1 <= INT_MAX;
+}
+
+int pqp_sample_plan_device(pqp_handle* h, double dt, int r, int linear, int batch, int n, int stride, const double* paths,
+                           const int32_t* n_of, const int32_t* stop_before, const double* profile, int m, const double* plan,
+                           const int32_t* count_of, const int32_t* refine_flags, double* fine, int32_t* m_of, double* defect,
+                           double* excess, int32_t* flags) {
+    if (!plan_ok(h, dt, r, linear, batch, n, stride, paths, profile, m, plan, fine, m_of, flags)) return fail(PQP_ERR_INVALID, kPlanRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::PlanArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.m = m; a.r = r; a.linear = linear; a.dt = dt; a.paths = paths; a.n_of = n_of;
+    a.stop_before = stop_before; a.profile = profile; a.plan = plan; a.count_of = count_of; a.refine_flags = refine_flags; a.fine = fine;
+    a.m_of = m_of; a.defect = defect; a.excess = excess; a.flags = flags;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::plan_sample_kernel, wave_grid(batch, pqp::kPlanThreads), dim3(pqp::kPlanThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_sample_plan(pqp_handle* h, double dt, int r, int linear, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                    const int32_t* stop_before, const double* profile, int m, const double* plan, const int32_t* count_of,
+                    const int32_t* refine_flags, double* fine, int32_t* m_of, double* defect, double* excess, int32_t* flags) {
+    if (!plan_ok(h, dt, r, linear, batch, n, stride, paths, profile, m, plan, fine, m_of, flags)) return fail(PQP_ERR_INVALID, kPlanRefusal);
+    const size_t bn = (size_t)batch * n, fine_rows = (size_t)batch * ((size_t)(m - 1) * r + 1);
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_stop = st.in(stop_before, batch);
+    const double* d_profile = st.in(profile, bn * PQP_SPEED_STRIDE);
+    const double* d_plan = st.in(plan, (size_t)batch * m * PQP_TRAJ_STRIDE);
+    const int32_t* d_count = st.in(count_of, batch);
+    const int32_t* d_rflags = st.in(refine_flags, batch);
+    double* d_fine = st.out(fine, fine_rows * PQP_TRAJ_STRIDE);
+    int32_t* d_m_of = st.out(m_of, batch);
+    double* d_defect = defect ? st.out(defect, batch) : nullptr;
+    double* d_excess = excess ? st.out(excess, batch) : nullptr;
+    int32_t* d_flags = st.out(flags, batch);
+    return st.run([&]() -> int {
+        return pqp_sample_plan_device(h, dt, r, linear, batch, n, stride, d_paths, d_n_of, d_stop, d_profile, m, d_plan, d_count, d_rflags, d_fine,
+                                      d_m_of, d_defect, d_excess, d_flags);
     });
 }
 
