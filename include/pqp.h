@@ -1249,6 +1249,84 @@ int pqp_sample_plan(pqp_handle* h, double dt, int r, int linear, int batch, int 
                     const int32_t* stop_before, const double* profile, int m, const double* plan, const int32_t* count_of,
                     const int32_t* refine_flags, double* fine, int32_t* m_of, double* defect, double* excess, int32_t* flags);
 
+/* ---- scores of finished trajectories and each group's best --------------------------------------------------------------------------------
+ * pqp_select_paths chooses between the candidates of a vehicle before any speed is planned: by the path QP's own objective.  Since
+ * pqp_speed_search that is too early - the straightest candidate wins and then waits behind a pedestrian its curvier neighbour would have
+ * passed.  This is the last stage of the path-speed decoupled planner: behind pqp_speed_refine, pqp_sample_plan and the fine
+ * pqp_agents_check, on the same stream, it scores every finished trajectory - the path and the speed plan on it together - and leaves the
+ * winner of every group on the device: its index, its waypoints and its plan rows.  The reference has no counterpart: it plans one path
+ * per call and has no time axis. */
+/* The parameters are PQP_RANK_PARAMS doubles, prm[PQP_RANK_W_PATH] ... prm[PQP_RANK_CLEARANCE_WANT], and an int `require_free` beside them,
+ * by value, as pqp_speed_refine's are: no struct.  pqp_rank_default_params (pure host; a NULL pointer is ignored) writes the weights
+ * 1, 1, 1, 1, 1, 0, pqp_select_default_params' clearance_want 0.6, and require_free = 1. */
+#define PQP_PLAN_SCORE_STRIDE 10
+#define PQP_RANK_PARAMS 7
+enum { PQP_RANK_W_PATH = 0, PQP_RANK_W_PROGRESS = 1, PQP_RANK_W_ACCEL = 2, PQP_RANK_W_JUMP = 3, PQP_RANK_W_LATERAL = 4, PQP_RANK_W_CLEARANCE = 5,
+       PQP_RANK_CLEARANCE_WANT = 6 };
+void pqp_rank_default_params(double* prm, int* require_free);
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   traj [batch][m][stride]             stride >= 8, columns as PQP_TRAJ_STRIDE documents; k (3), s (4), v (5), a (6) and t (7) are read.
+ *                                       pqp_sample_plan's fine, pqp_speed_refine's traj and pqp_speed_search's traj are read where they are
+ *   m_of [batch] or NULL                the rows of each candidate, c = min(max(m_of, 0), m): pqp_sample_plan's m_of, or the search's
+ *                                       reached.  NULL: m.  Rows at f >= c are not read
+ *   path_terms [batch][PQP_SCORE_STRIDE] or NULL   what pqp_select_paths wrote (with groups = 0 it only scores): entry 0 is the path's
+ *                                       score, entry 7 its eligibility
+ *   search_flags [batch] or NULL        pqp_speed_search's flags
+ *   first_hit [batch] or NULL, clearance [batch][m] or NULL   what pqp_agents_check wrote on these same rows
+ *   paths [batch][n][path_stride] or NULL, n_of [batch] or NULL   path_stride >= 7: the waypoints to gather for the winner (the chain's
+ *                                       `out` and n_out); n_of is clamped to [0, n], NULL: all have n.  Without paths, n, path_stride
+ *                                       and n_of are not read
+ *   group_start [groups + 1]            exactly as pqp_select_paths takes it
+ * The definition, in fp64, every product and sum rounded on its own (no contraction), min and max as fmin and fmax, for a candidate with
+ * c >= 1; h_f = t_{f+1} - t_f for f < c - 1; want = prm[PQP_RANK_CLEARANCE_WANT]:
+ *   terms [batch][PQP_PLAN_SCORE_STRIDE]
+ *     1  progress                s_{c-1} - s_0
+ *     2  acceleration effort     sum_{f < c-1} (a_f * a_f) * h_f
+ *     3  acceleration jumps      sum_{f < c-1} (a_{f+1} - a_f) * (a_{f+1} - a_f); not divided by time, so under piecewise-constant
+ *                                acceleration it is the same for the m plan rows and for pqp_sample_plan's fine rows at any r
+ *     4  lateral acceleration    sum_{f < c-1} ((k_f * (v_f * v_f)) * (k_f * (v_f * v_f))) * h_f: where the path and the speed meet
+ *     5  least clearance         min over f < c of clearance_f: +inf when every one is, NaN when one is; 0 when clearance is NULL
+ *     6  clearance shortfall     sum_{f < c-1} (max(0, want - clearance_f) * max(0, want - clearance_f)) * h_f; 0 when clearance is NULL;
+ *                                a clearance of -inf makes it +inf
+ *     7  the path's score        path_terms[b][0]; 0 when path_terms is NULL
+ *     8  duration                t_{c-1} - t_0
+ *     0  score                   w_path * e7 - w_progress * e1 + w_accel * e2 + w_jump * e3 + w_lateral * e4 + w_clearance * e6, added
+ *                                from left to right
+ *     9  eligible                1.0 or 0.0
+ * A candidate is eligible when all of these hold: c >= 1; search_flags is absent or has none of PQP_SEARCH_NO_PLAN, PQP_SEARCH_EMPTY and
+ * PQP_SEARCH_NOT_FINITE; first_hit is absent, or require_free is 0, or first_hit[b] equals c; path_terms is absent or path_terms[b][7] is
+ * not 0; its score is finite.  A candidate that is not eligible still gets its terms; one with c = 0 gets ten zeros.  A lane adds its own
+ * samples in ascending order and the 64 partial sums meet in a fixed order, so the order of a candidate's additions depends on c alone:
+ * the same candidate gives the same bits at any batch position, in any group and from either form.  No atomics.
+ * Outputs, fully overwritten:
+ *   terms                               as above
+ *   best [groups]                       the row of the group's eligible candidate with the least score, the lowest row among equal
+ *                                       scores; -1 when the group has none
+ *   best_traj [groups][m][PQP_TRAJ_STRIDE], best_m [groups]   both or neither (NULL): the winner's eight columns below its count c and
+ *                                       zeros behind, and c; a group without a winner is all zeros with best_m 0
+ *   best_paths [groups][n][7], best_n [groups]   both or neither (NULL), and only with paths: the winner's seven columns and its count,
+ *                                       zeros beyond the count; a group without a winner is all zeros with best_n 0
+ * The _device form is asynchronous on the handle's stream and allocates nothing: two launches, the scores, then the groups; with
+ * groups = 0 it only scores.  It cannot see group_start, so, as in pqp_select_paths, the kernel clamps every group boundary to [0, batch]
+ * and takes a descending pair for an empty group: no array makes it read outside its inputs.  What a damaged array yields follows from
+ * that rule alone: a group that starts at a value above batch, and the group of a descending pair, are empty (best -1, zeros); a group
+ * that ends at a value above batch runs to the last row; a negative boundary counts as 0; every other group is what its own two
+ * boundaries say.
+ * The host form copies in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the outputs
+ * untouched, for a null pointer that is not optional (h, prm, traj, group_start, terms, best), batch < 1, m < 1, stride < 8, paths given
+ * with n < 1 or path_stride < 7, best_traj without best_m or the reverse, best_paths without best_n or the reverse, best_paths without
+ * paths, groups < 0, a parameter that is not finite, or a require_free other than 0 or 1.  The host form also refuses a group_start that
+ * is not ascending from 0 to batch (so, batch being at least 1, it needs one group or more). */
+int pqp_select_plans_device(pqp_handle* h, const double* prm, int require_free, int batch, int m, int stride, const double* traj,
+                            const int32_t* m_of, const double* path_terms, const int32_t* search_flags, const int32_t* first_hit,
+                            const double* clearance, int n, int path_stride, const double* paths, const int32_t* n_of, int groups,
+                            const int32_t* group_start, double* terms, int32_t* best, double* best_traj, int32_t* best_m, double* best_paths,
+                            int32_t* best_n);
+int pqp_select_plans(pqp_handle* h, const double* prm, int require_free, int batch, int m, int stride, const double* traj, const int32_t* m_of,
+                     const double* path_terms, const int32_t* search_flags, const int32_t* first_hit, const double* clearance, int n,
+                     int path_stride, const double* paths, const int32_t* n_of, int groups, const int32_t* group_start, double* terms,
+                     int32_t* best, double* best_traj, int32_t* best_m, double* best_paths, int32_t* best_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -231,6 +231,37 @@ def refine_default_params(lib=None, **over):
     return p
 
 
+class RankParams:
+    """what pqp_select_plans takes besides its arrays: the RANK_PARAMS doubles the C ABI passes as a plain array (w_path, w_progress,
+    w_accel, w_jump, w_lateral, w_clearance, clearance_want, at RANK_W_PATH .. RANK_CLEARANCE_WANT) and require_free beside them, under
+    the names of the header's enumerators.  rank_default_params(w_progress=...) as for the other parameter sets."""
+    __slots__ = ("w_path", "w_progress", "w_accel", "w_jump", "w_lateral", "w_clearance", "clearance_want", "require_free")
+    _INDEX = (("w_path", RANK_W_PATH), ("w_progress", RANK_W_PROGRESS), ("w_accel", RANK_W_ACCEL), ("w_jump", RANK_W_JUMP),
+              ("w_lateral", RANK_W_LATERAL), ("w_clearance", RANK_W_CLEARANCE), ("clearance_want", RANK_CLEARANCE_WANT))
+
+    def __init__(self, values, require_free):
+        for name, i in self._INDEX:
+            setattr(self, name, float(values[i]))
+        self.require_free = int(require_free)
+
+    def array(self):
+        out = np.zeros(RANK_PARAMS)
+        for name, i in self._INDEX:
+            out[i] = getattr(self, name)
+        return out
+
+
+def rank_default_params(lib=None, **over):
+    """pqp_rank_default_params: the weights 1, 1, 1, 1, 1, 0, the selection's clearance_want 0.6, require_free 1 - with `over` applied."""
+    lib = lib or load_library()
+    values, require_free = np.full(RANK_PARAMS, -1.0), C.c_int(-1)
+    lib.pqp_rank_default_params(values, C.byref(require_free))
+    p = RankParams(values, require_free.value)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
 def car_circles(car=None, lib=None):
     """pqp_car_circles (pure host): [7][3] x, y, r in the vehicle frame of rr, rl, fr, fl, fm, rm and the bounding circle."""
     lib = lib or load_library()
@@ -414,7 +445,7 @@ class Handle:
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
                       plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
-                      t0=None, speed=None, v_start=None, v_end=None):
+                      t0=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -450,30 +481,40 @@ class Handle:
         without refine on the search's traj, linearly.  Adds plan_traj [..][(m - 1) r + 1][8], plan_m_of, plan_defect, plan_excess and
         plan_flags.  plan_agents: [n_scenes][a_max][(m - 1) r + 1][6], the agents of `agents` on the fine steps - pqp_agents_check_device behind
         that on plan_traj and plan_m_of, under agents_params' margin and the same agents_of / scene_of; adds plan_first_hit and
-        plan_hit_agent."""
+        plan_hit_agent.
+        rank: group_start [groups + 1] (needs search; not select: the speed stages run on every candidate) - behind everything else on the
+        same stream, pqp_select_paths_device with groups = 0 for the paths' terms (select_default_params(); first_collision and margin
+        when the footprint was checked), then pqp_select_plans_device on the fine rows (plan_traj, plan_m_of) when plan_samples is given,
+        else on the refine's traj, else the search's, with search_reached; with plan_agents the fine check also writes its clearance,
+        and plan_first_hit and that clearance go in.  rank_params: RankParams (None: rank_default_params()).  Adds terms [B][8],
+        rank_terms [B][10], rank_best [groups], best_paths [groups][n_max][7], best_n, best_traj [groups][rows][8], best_m (and
+        plan_clearance with plan_agents).  winners_only (with rank): out, free, margin, profile, search_traj, refine_traj, plan_traj and
+        plan_clearance stay on the device and are not in the dict."""
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
+                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only and rank is None),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents))
+                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents),
+                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]))
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
                               winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None,
                               agents_params=None, sample=None,
-                              samples=None, t0=None, speed=None, v_start=None, v_end=None):
+                              samples=None, t0=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
-        agents_params / search / refine / plan_samples / plan_agents: as for optimize_path)."""
+        agents_params / search / refine / plan_samples / plan_agents / rank / rank_params: as for optimize_path)."""
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only),
+                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only and rank is None),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents))
+                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents),
+                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]))
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -540,6 +581,21 @@ class Handle:
                                  f"not {plan_agents.shape}")
         return (r, plan_agents)
 
+    def _ranking(self, rank, rank_params, winners_only, search, select, batch):
+        if rank is None:
+            if rank_params is not None:
+                raise ValueError("rank_params needs rank=group_start")
+            return None
+        if search is None:
+            raise ValueError("rank needs search=SearchParams: it ranks the trajectories the speed stages finished")
+        if select is not None:
+            raise ValueError("rank is refused together with select: the speed stages must run on every candidate")
+        if rank_params is not None and not isinstance(rank_params, RankParams):
+            raise ValueError("rank_params must be a RankParams")
+        group_start = np.ascontiguousarray(rank, dtype=np.int32).ravel()
+        _check_group_start(group_start, batch)
+        return (group_start, rank_params if rank_params is not None else rank_default_params(self.lib), bool(winners_only))
+
     def _agents(self, agents, agents_of, scene_of, agents_params, sample, samples, car, batch, select, search=None):
         if agents is None:
             if agents_of is not None or scene_of is not None or agents_params is not None:
@@ -574,14 +630,15 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None, planning=None):
+               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None, planning=None, ranking=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
         of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None; moving:
         (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that (when there is a sampling), or
         None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None; refining: RefineParams
-        of the speed QP behind that search, or None; planning: (r, plan_agents or None) of the plan's fine time step behind both, or None"""
+        of the speed QP behind that search, or None; planning: (r, plan_agents or None) of the plan's fine time step behind both, or None;
+        ranking: (group_start, RankParams, winners_only) of the choice between the finished trajectories behind everything, or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -651,6 +708,18 @@ class Handle:
                 d_pl_ag = t(pl_ag, np.float64)
                 pl_frames = torch.zeros(pl_ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
                 pl_first, pl_who = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
+        if ranking is not None:             # (no selection: the rows are the B candidates)
+            rk_start, rk_prm, rk_winners = ranking
+            rk_groups = rk_start.size - 1
+            d_rk_start = t(rk_start, np.int32)
+            rk_sel = select_default_params(self.lib)
+            rk_path_terms = torch.zeros((B, SCORE_STRIDE), dtype=torch.float64, device=dev)
+            rk_rows = pl_m if planning is not None else layers
+            rk_terms = torch.zeros((B, PLAN_SCORE_STRIDE), dtype=torch.float64, device=dev)
+            rk_best, rk_best_m, rk_best_n = (torch.zeros(rk_groups, dtype=torch.int32, device=dev) for _ in range(3))
+            rk_best_traj = torch.zeros((rk_groups, rk_rows, TRAJ_STRIDE), dtype=torch.float64, device=dev)
+            rk_best_paths = torch.zeros((rk_groups, cfg.n_max, 7), dtype=torch.float64, device=dev)
+            rk_clear = torch.zeros((B, pl_m), dtype=torch.float64, device=dev) if planning is not None and pl_ag is not None else None
         torch.cuda.synchronize(dev)
         if build is not None:
             build(d_layer, d_dist)
@@ -715,12 +784,25 @@ class Handle:
             if pl_ag is not None:           # behind that, on the fine rows that are on the plan
                 self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, pl_m, TRAJ_STRIDE, pl_traj,
                                                              pl_m_of, pl_ag.shape[0], pl_ag.shape[1], d_pl_ag if pl_ag.size else None, d_ag_of,
-                                                             d_scene, pl_frames if pl_ag.size else None, pl_first, pl_who, None))
+                                                             d_scene, pl_frames if pl_ag.size else None, pl_first, pl_who,
+                                                             rk_clear if ranking is not None else None))
+        if ranking is not None:             # behind everything: the paths' terms, then the finished trajectories and each group's best
+            self._check(self.lib.pqp_select_paths_device(self._h, C.byref(rk_sel), B, cfg.n_max, 7, out, ints[0], ints[1], ints[2],
+                                                         first if footprint is not None else None, margin if footprint is not None else None,
+                                                         0, d_rk_start, rk_path_terms, rk_best, None, None))
+            if planning is not None:
+                rk_traj, rk_m_of = pl_traj, pl_m_of
+            else:
+                rk_traj, rk_m_of = rf_traj if refining is not None else se_traj, se_reached
+            self._check(self.lib.pqp_select_plans_device(self._h, rk_prm.array(), int(rk_prm.require_free), B, rk_rows, TRAJ_STRIDE, rk_traj, rk_m_of,
+                                                         rk_path_terms, se_flags, pl_first if rk_clear is not None else None, rk_clear, cfg.n_max, 7,
+                                                         out, ints[0], rk_groups, d_rk_start, rk_terms, rk_best, rk_best_traj, rk_best_m,
+                                                         rk_best_paths, rk_best_n))
         self.sync()
         if smoother is not None:
             smoother.sync()
         host = lambda x: x.cpu().numpy()
-        everything = selection is None or not selection[2]          # winners_only: out, free and margin stay on the device
+        everything = (selection is None or not selection[2]) and (ranking is None or not ranking[2])     # winners_only: out, free and margin stay on the device
         res = dict(out=host(out)) if everything else {}
         res.update(n_out=host(ints[0]), status=host(ints[1]), stage=host(ints[2]), iters=host(ints[3]))
         if footprint is not None:
@@ -731,23 +813,37 @@ class Handle:
                 res.update(margin=host(margin))
         if selection is not None:
             res.update(terms=host(terms), best=host(best), best_paths=host(best_paths), best_n=host(best_n))
+        every_row = ranking is None or not ranking[2]               # winners_only with rank: nor do the rows of every candidate's speed stages
         if speed is not None:
-            res.update(profile=host(profile), speed_flags=host(speed_flags))
+            if every_row:
+                res.update(profile=host(profile))
+            res.update(speed_flags=host(speed_flags))
         if sampling is not None:
             res.update(traj=host(traj), traj_n=host(traj_n), traj_flags=host(traj_flags))
         if moving is not None and sampling is not None:
             res.update(first_hit=host(first_hit), hit_agent=host(hit_agent), agent_clearance=host(agent_clearance))
         if searching is not None:
-            res.update(search_steps=host(se_steps), search_traj=host(se_traj), search_cost=host(se_cost), search_reached=host(se_reached),
-                       search_flags=host(se_flags))
+            res.update(search_steps=host(se_steps))
+            if every_row:
+                res.update(search_traj=host(se_traj))
+            res.update(search_cost=host(se_cost), search_reached=host(se_reached), search_flags=host(se_flags))
         if refining is not None:
-            res.update(search_blocked=host(se_blocked), refine_traj=host(rf_traj), refine_bounds=host(rf_bounds), refine_cost=host(rf_cost), refine_excess=host(rf_excess),
-                       refine_status=host(rf_status), refine_flags=host(rf_flags))
+            res.update(search_blocked=host(se_blocked))
+            if every_row:
+                res.update(refine_traj=host(rf_traj))
+            res.update(refine_bounds=host(rf_bounds), refine_cost=host(rf_cost), refine_excess=host(rf_excess), refine_status=host(rf_status),
+                       refine_flags=host(rf_flags))
         if planning is not None:
-            res.update(plan_traj=host(pl_traj), plan_m_of=host(pl_m_of), plan_defect=host(pl_defect), plan_excess=host(pl_excess),
-                       plan_flags=host(pl_flags))
+            if every_row:
+                res.update(plan_traj=host(pl_traj))
+            res.update(plan_m_of=host(pl_m_of), plan_defect=host(pl_defect), plan_excess=host(pl_excess), plan_flags=host(pl_flags))
             if pl_ag is not None:
                 res.update(plan_first_hit=host(pl_first), plan_hit_agent=host(pl_who))
+        if ranking is not None:
+            if rk_clear is not None and every_row:
+                res.update(plan_clearance=host(rk_clear))
+            res.update(terms=host(rk_path_terms), rank_terms=host(rk_terms), rank_best=host(rk_best), best_paths=host(rk_best_paths),
+                       best_n=host(rk_best_n), best_traj=host(rk_best_traj), best_m=host(rk_best_m))
         return res
 
     def distance_layer(self, grid, geom):
@@ -975,6 +1071,45 @@ class Handle:
         self._check(self.lib.pqp_sample_plan(self._h, float(dt), r, int(linear), B, n, stride, paths, no, sb, profile, m, plan, co, rfl, traj, m_of,
                                              defect, excess, flags))
         return dict(traj=traj, m_of=m_of, defect=defect, excess=excess, flags=flags)
+
+    def select_plans(self, traj, group_start, m_of=None, path_terms=None, search_flags=None, first_hit=None, clearance=None, paths=None, n_of=None,
+                     prm=None):
+        """pqp_select_plans (host arrays): traj [B][m][stride >= 8] (sample_plan's, speed_refine's or speed_search's traj as it is),
+        group_start [groups + 1] (ascending, 0 .. B), and optionally m_of [B] (the rows of each: sample_plan's m_of or the search's reached),
+        path_terms [B][8] (select_paths' terms), search_flags [B], first_hit [B] and clearance [B][m] (agents_check's on these rows), paths
+        [B][n][path_stride >= 7] with n_of [B] (the waypoints to gather for the winners); prm = RankParams (None: rank_default_params()).
+        Returns dict(terms [B][10], best [groups], best_traj [groups][m][8], best_m [groups][, best_paths [groups][n][7], best_n [groups]])."""
+        traj = np.ascontiguousarray(traj, dtype=np.float64)
+        if traj.ndim != 3:
+            raise ValueError(f"select_plans: traj must be [B][m][stride], not {traj.shape}")
+        B, m, stride = traj.shape
+        gs = np.ascontiguousarray(group_start, dtype=np.int32).ravel()
+        _check_group_start(gs, B)
+        groups = gs.size - 1
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+        mo, sf, fh, no, pt, cl, pa = i32(m_of), i32(search_flags), i32(first_hit), i32(n_of), f64(path_terms), f64(clearance), f64(paths)
+        if pa is not None and pa.ndim != 3:
+            raise ValueError(f"select_plans: paths must be [B][n][path_stride], not {pa.shape}")
+        n, path_stride = (0, 0) if pa is None else pa.shape[1:]
+        if no is not None and pa is None:
+            raise ValueError("select_plans: n_of needs paths")
+        for name, a, size in (("m_of", mo, B), ("search_flags", sf, B), ("first_hit", fh, B), ("n_of", no, B), ("path_terms", pt, B * SCORE_STRIDE),
+                              ("clearance", cl, B * m), ("paths", pa, B * n * path_stride)):
+            if a is not None and a.size != size:
+                raise ValueError(f"select_plans: {name} must have {size} entries, not {a.size}")
+        prm = prm if prm is not None else rank_default_params(self.lib)
+        terms = np.zeros((B, PLAN_SCORE_STRIDE))
+        best, best_m = np.zeros(groups, dtype=np.int32), np.zeros(groups, dtype=np.int32)
+        best_traj = np.zeros((groups, m, TRAJ_STRIDE))
+        best_paths = None if pa is None else np.zeros((groups, n, 7))
+        best_n = None if pa is None else np.zeros(groups, dtype=np.int32)
+        self._check(self.lib.pqp_select_plans(self._h, prm.array(), int(prm.require_free), B, m, stride, traj, mo, pt, sf, fh, cl, n, path_stride,
+                                              pa, no, groups, gs, terms, best, best_traj, best_m, best_paths, best_n))
+        res = dict(terms=terms, best=best, best_traj=best_traj, best_m=best_m)
+        if pa is not None:
+            res.update(best_paths=best_paths, best_n=best_n)
+        return res
 
     def corridor_params(self, **over):
         return _defaults(self.lib, PqpCorridorParams, "pqp_corridor_default_params", over)

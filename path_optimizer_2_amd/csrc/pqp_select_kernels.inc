@@ -7,7 +7,7 @@
 // contiguous span of `paths`, lane i also reads row i + 1's x, y for the chord.  Every lane adds its own waypoints in ascending order and
 // the 64 partial sums meet in wave_sum, so the order of the additions depends on the candidate's count alone: the same candidate gives the
 // same bits wherever it stands in whatever batch.  group_select_kernel: one wavefront per group over the 64-byte records the first kernel
-// wrote.  No atomics, no LDS.
+// wrote; its reading of group_start and its choice of the winner are device functions that pqp_rank_kernels.inc uses too.  No atomics, no LDS.
 
 namespace pqp {
 
@@ -79,23 +79,37 @@ __global__ void __launch_bounds__(kSelectThreads) path_score_kernel(const Select
     if (lane < PQP_SCORE_STRIDE) rec[lane] = v;
 }
 
-__global__ void __launch_bounds__(kSelectThreads) group_select_kernel(const SelectArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kSelectThreads / 64) + (threadIdx.x >> 6)));
-    if (g >= a.groups) return;
-    // group_start is the caller's: whatever it holds, the rows read stay inside [0, batch)
-    const int lo = min(max(a.group_start[g], 0), a.batch), hi = min(max(a.group_start[g + 1], 0), a.batch);
+// What group_select_kernel and plan_group_kernel (pqp_rank_kernels.inc) share: the rows of group g, and the group's winner.
+// group_start is the caller's: whatever it holds, the rows read stay inside [0, batch); a descending pair is an empty group
+__device__ __forceinline__ void group_rows(const int32_t* group_start, int g, int batch, int* lo, int* hi) {
+    *lo = min(max(group_start[g], 0), batch);
+    *hi = min(max(group_start[g + 1], 0), batch);
+}
+
+// the row in [lo, hi) of the least score (entry 0 of a record of STRIDE doubles) among those whose entry ELIGIBLE is not 0, the lowest row
+// among equal scores, -1 when there is none; the same value in every lane.  Called by the whole wavefront
+template <int STRIDE, int ELIGIBLE>
+__device__ __forceinline__ int group_least(const double* terms, int lo, int hi, int lane) {
     double least = INFINITY;
     int at = INT_MAX;
     for (int b = lo + lane; b < hi; b += 64) {
-        const double* rec = a.terms + (size_t)b * PQP_SCORE_STRIDE;
+        const double* rec = terms + (size_t)b * STRIDE;
         const double score = rec[0];
-        if (rec[7] != 0.0 && score < least) { least = score; at = b; }          // ascending b: the lane keeps the lowest index of its least
+        if (rec[ELIGIBLE] != 0.0 && score < least) { least = score; at = b; }   // ascending b: the lane keeps the lowest index of its least
     }
     const double wave_least = -wave_max(-least);
     const int cand = (at != INT_MAX && least == wave_least) ? at : INT_MAX;
     const int winner_or_max = (int)-wave_max(-(double)cand);                     // an index is exact in a double
-    const int winner = winner_or_max == INT_MAX ? -1 : winner_or_max;
+    return winner_or_max == INT_MAX ? -1 : winner_or_max;
+}
+
+__global__ void __launch_bounds__(kSelectThreads) group_select_kernel(const SelectArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int g = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (kSelectThreads / 64) + (threadIdx.x >> 6)));
+    if (g >= a.groups) return;
+    int lo, hi;
+    group_rows(a.group_start, g, a.batch, &lo, &hi);
+    const int winner = group_least<PQP_SCORE_STRIDE, 7>(a.terms, lo, hi, lane);
     if (lane == 0) a.best[g] = winner;
     if (!a.best_paths) return;
     const int count = winner >= 0 ? clamped_count(a.n_of, winner, a.n) : 0;
