@@ -115,7 +115,9 @@ def _gap(values):
 
 
 def dp(cells, qenv, J, q0, prm, swept=True):
-    """the layered search on cells bool [m][>= J]: (reached, steps [reached][2], cost, margins dict(cost_gap, end_gap))"""
+    """the layered search on cells bool [m][>= J]: (reached, steps [reached][2], cost, margins dict(cost_gap, end_gap), parents, qref).
+    parents: per living layer k the map state (j, q) -> the step q' of its parent (layer 0: empty; a layer's keys are its living states);
+    qref [J]: reference_steps"""
     m = cells.shape[0]
     Q, q_up, q_down = prm["q_max"], prm["q_up"], prm["q_down"]
     w_slow, w_accel = np.float64(prm["w_slow"]), np.float64(prm["w_accel"])
@@ -131,7 +133,7 @@ def dp(cells, qenv, J, q0, prm, swept=True):
         prev, cur, par = layers[-1], {}, {}
         if not prev:
             break
-        for j in range(J):
+        for j in range(min(J, max(jq[0] for jq in prev) + Q + 1)):           # beyond: j - q lies behind every living state of the layer before
             for q in range(min(Q, j) + 1):
                 jp = j - q
                 qe = max(int(qenv[jp]), int(qenv[j]))
@@ -161,7 +163,7 @@ def dp(cells, qenv, J, q0, prm, swept=True):
         layers.append(cur)
         parents.append(par)
     if not layers[0]:
-        return 0, np.zeros((0, 2), np.int32), INF, dict(cost_gap=cost_gap, end_gap=INF)
+        return 0, np.zeros((0, 2), np.int32), INF, dict(cost_gap=cost_gap, end_gap=INF), [{}], qref
     last = layers[-1]
     end = min(last, key=lambda jq: (last[jq], -jq[0], jq[1]))
     steps = [end]
@@ -169,12 +171,13 @@ def dp(cells, qenv, J, q0, prm, swept=True):
         j, q = steps[-1]
         steps.append((j - q, parents[k][(j, q)]))
     steps.reverse()
-    return len(layers), np.array(steps, np.int32), float(last[end]), dict(cost_gap=cost_gap, end_gap=_gap(list(last.values())))
+    return len(layers), np.array(steps, np.int32), float(last[end]), dict(cost_gap=cost_gap, end_gap=_gap(list(last.values()))), parents, qref
 
 
 def search(path, profile, v_start, fr, circles, m, n_of=None, stop_before=None, prm=None, swept=True, cells=None):
     """one path [n][stride >= 6] with its profile [n][4] against its scene's frames fr [A][m][8] ->
-    dict(steps [m][2], traj [m][8], cost, reached, flags, blocked [m][W], margins dict(clear, cost_gap, end_gap), qenv, J).
+    dict(steps [m][2], traj [m][8], cost, reached, flags, blocked [m][W], margins dict(clear, cost_gap, end_gap), qenv, J, q0, parents, qref):
+    parents and qref as dp() gives them - the whole table, not the winning plan alone; q0 is the start's step.
     swept=False takes the swept-range rule out; cells: a bool [m][S] to search in place of the occupancy (the brute-force cases)"""
     prm = params(**(prm or {}))
     path, profile = np.asarray(path, dtype=np.float64), np.asarray(profile, dtype=np.float64)
@@ -182,7 +185,7 @@ def search(path, profile, v_start, fr, circles, m, n_of=None, stop_before=None, 
     ds, dt = np.float64(prm["ds"]), np.float64(prm["dt"])
     c = T.driven(path.shape[0], n_of, stop_before)
     out = dict(steps=np.full((m, 2), -1, np.int32), traj=np.zeros((m, 8)), cost=INF, reached=0, flags=0, blocked=np.zeros((m, words(S)), np.int32),
-               margins=dict(clear=INF, cost_gap=INF, end_gap=INF), qenv=np.zeros(0, np.int64), J=0)
+               margins=dict(clear=INF, cost_gap=INF, end_gap=INF), qenv=np.zeros(0, np.int64), J=0, q0=0, parents=[{}], qref=[])
     if c == 0:
         out["flags"] = EMPTY
         return out
@@ -203,8 +206,9 @@ def search(path, profile, v_start, fr, circles, m, n_of=None, stop_before=None, 
     out["blocked"], out["qenv"], out["J"] = pack(full), qenv, J
     with np.errstate(all="ignore"):
         q0 = int(np.fmin(np.fmax(np.rint(v0 * dt / ds), 0.0), np.float64(Q)))
-    reached, steps, cost, margins = dp(full, qenv, J, q0, prm, swept)
+    reached, steps, cost, margins, out["parents"], out["qref"] = dp(full, qenv, J, q0, prm, swept)
     out["margins"].update(margins)
+    out["q0"] = q0
     out["reached"], out["cost"] = reached, cost
     out["steps"][:reached] = steps
     for k in range(reached):
@@ -388,7 +392,8 @@ def _at_station(case, b, j, layers, shape, side=0.0, ahead=0.0):
 
 def seeded(name):
     """dict(paths, profile, v_start, agents, a_of, scene_of, n_of, stop_before, prm, m) of one case of the GPU test.  The weights are
-    dyadic, so every cost is exact and a gap between two candidates is a multiple of 2^-4 or a tie"""
+    dyadic, so every cost is exact and a gap between two candidates is a multiple of 2^-4 or a tie.  Every plan of these three gets
+    through; family() below has the cases whose plans die, with more layers, other steps and weights, and q_max = 0"""
     if name == "tiles":                                      # a second station tile; words 0 / 1 / 2 with runs across 31 / 32 and 63 / 64
         B, n, m = 5, 160, 6
         prm = params(stations=70, q_max=5, q_up=2, q_down=3, w_accel=0.25, margin=0.25)
@@ -430,6 +435,128 @@ def seeded(name):
 
 
 SEEDED = ("tiles", "cap", "long")
+
+
+# ---- the families of tests/test_gpu_speed_search_table.py -------------------------------------------------------------------------------
+SLOW = dict(v_max=2.0, a_max=0.5, d_max=1.0)                 # a speed profile whose envelope stays below five cells of 0.5 m a second
+
+
+def _bad_row(m, layer, heading):
+    """agent rows [m][6]: absent but at `layer`, where its heading is no number - which blocks every station of that layer"""
+    rows = absent(m)
+    rows[layer] = [500.0, 0.0, heading, 1.0, 1.0, 0.0]
+    return rows
+
+
+def _scenes(m, rows):
+    """agents [n_scenes][a_max][m][6] and a_of from a list, per scene, of agent rows; absent agents fill up to a_max"""
+    a_max = max(len(r) for r in rows)
+    agents = np.stack([np.stack(list(r) + [absent(m)] * (a_max - len(r))) if a_max else np.zeros((0, m, 6)) for r in rows])
+    return agents, np.array([len(r) for r in rows], np.int32)
+
+
+def family(name):
+    """one batch, as seeded() gives one, of a family of cases that the three seeded shapes leave out.  tests/test_speed_search.py asserts
+    on the restatement what each is there for (who dies where, which wavefronts hold living states, which flags occur) and the margins.
+      "dead"        S = 200, Q = 19, m = 12, n = 300: plans that die late, at full-table size.  Path 0: an agent row with heading = inf at
+                    layer 8 (from rest); 1: heading = nan at layer 5 (from 3 m/s); 2: a wall of discs across every station in reach at
+                    layer 5; 3: a start far above a slow envelope (q0 clamped to Q, q_down = 6: layer 1 is empty); 4: gets through
+      "ties"        the same batch with w_slow = w_accel = 0: every cost is 0, the terminal rule and the parent rule decide everything
+      "horizon70",  S = 24, Q = 3, m = 70 and 260: few states and many layers, an agent that stands on the path for most of them, and an
+      "horizon260"  empty and a non-finite path between the ordinary ones.  Path 0 ends on the grid (ARRIVED), 2 and 4 run past it
+                    (GRID_SHORT)
+      "steps"       dt = 0.8, ds = 0.3, w_slow = 0.75, w_accel = 0.5, q_up = 5 > q_down = 2, margin = 0.1, S = 150, Q = 12, m = 10, paths of
+                    stride 9 whose columns 7 and 8 hold 1e9; path 2 starts above the grid's fastest step
+      "standing"    q_max = 0, S = 130 (three station tiles, five words): a car that can only stand; one is driven into, one starts blocked
+      "wide"        q_max = 0, S = 4096, ds = 0.02, m = 3: 64 station tiles, 128 words a layer; path 1 has n_of = 150, so its stations end
+                    inside a tile and whole tiles behind hold nothing; agents beyond tile 15 and beyond tile 31
+      "thin"        S = 1365, Q = 2 (4095 states), ds = 0.05, m = 40: many station tiles under a plan that moves for 39 layers; path 0 waits
+                    and gets through, 1 and 2 die at layers 10 and 20"""
+    if name in ("dead", "ties"):
+        B, n, m = 5, 300, 12
+        prm = params(stations=200, q_max=19, q_up=3, q_down=6, w_accel=0.5)
+        if name == "ties":
+            prm = dict(prm, w_slow=0.0, w_accel=0.0)
+        c = dict(paths=synth_paths(B, n, first=11), v_start=np.array([0.0, 3.0, 0.0, 30.0, 1.0]), prm=prm, m=m, n_of=None, stop_before=None)
+        c["profile"] = _profiles(c["paths"], c["v_start"])
+        c["profile"][3] = profile_of(c["paths"][3], 1.0, prm=SLOW)                  # the profile of a slower car than the one that starts at 30 m/s
+        c["scene_of"] = np.arange(B, dtype=np.int32)
+        wall = [_at_station(c, 2, j, (5,), (0.0, 0.0, 0.5)) for j in range(0, 80, 8)]
+        c["agents"], c["a_of"] = _scenes(m, [[_bad_row(m, 8, math.inf)], [_bad_row(m, 5, math.nan)], wall, [],
+                                             [_at_station(c, 4, 14, (1, 2, 3, 4), (0.0, 0.0, 0.45), side=0.2)]])
+        return c
+    if name in ("horizon70", "horizon260"):
+        B, n, m = 5, 80, 70 if name == "horizon70" else 260
+        prm = params(stations=24, q_max=3, q_up=1, q_down=2, w_accel=0.25)
+        paths = synth_paths(B, n, first=5)
+        paths[3, 17, 1] = math.nan                           # path 3 is not finite, path 1 is empty
+        n_of = np.array([30, 0, n, n, n], np.int32)
+        c = dict(paths=paths, v_start=np.array([0.0, 0.0, 0.5, 0.0, 1.5]), prm=prm, m=m, n_of=n_of, stop_before=None)
+        fin = paths.copy()
+        fin[3, 17, 1] = 0.0
+        c["profile"] = _profiles(fin, c["v_start"], n_of)
+        c["scene_of"] = np.array([0, 0, 1, 1, 2], np.int32)
+        wait = range(0, m - 20)
+        c["agents"], c["a_of"] = _scenes(m, [[_at_station(c, 0, 12, wait, (0.0, 0.0, 0.3), ahead=3.5)],
+                                             [_at_station(c, 2, 14, wait, (1.0, 0.5, 0.1), ahead=3.5, side=0.3)],
+                                             [_at_station(c, 4, 9, range(3, m - 30), (0.0, 0.0, 0.4), ahead=3.5, side=-0.2)]])
+        return c
+    if name == "steps":
+        B, n, m = 3, 220, 10
+        prm = params(dt=0.8, ds=0.3, w_slow=0.75, w_accel=0.5, margin=0.1, stations=150, q_max=12, q_up=5, q_down=2)
+        paths = np.full((B, n, 9), 1e9)
+        paths[:, :, :7] = synth_paths(B, n, first=13)
+        c = dict(paths=paths, v_start=np.array([0.0, 2.0, 6.0]), prm=prm, m=m, n_of=np.array([n, 171, n], np.int32), stop_before=None)
+        c["profile"] = _profiles(paths, c["v_start"], c["n_of"])
+        c["scene_of"], c["a_of"] = np.array([0, 1, 1], np.int32), np.array([1, 2], np.int32)
+        c["agents"] = _scenes(m, [[_at_station(c, 0, 20, (3, 4, 5), (0.0, 0.0, 0.4), side=0.3)],
+                                  [_at_station(c, 1, 45, (4, 5, 6), (1.5, 0.7, 0.1), side=-0.6), _at_station(c, 2, 70, (5, 6), (0.0, 0.0, 0.5), side=0.1)]])[0]
+        return c
+    if name == "standing":
+        B, n, m = 3, 300, 6
+        prm = params(stations=130, q_max=0, margin=0.25)
+        c = dict(paths=synth_paths(B, n, first=17), v_start=np.array([0.0, 2.0, 0.0]), prm=prm, m=m, n_of=None, stop_before=None)
+        c["profile"] = _profiles(c["paths"], c["v_start"])
+        c["scene_of"] = np.arange(B, dtype=np.int32)
+        c["agents"], c["a_of"] = _scenes(m, [[_at_station(c, 0, 31, (1, 2, 3), (0.0, 0.0, 0.4), side=0.3), _at_station(c, 0, 100, (0, 4, 5), (2.0, 1.0, 0.0), side=1.0)],
+                                             [_at_station(c, 1, 2, (3, 4, 5), (0.0, 0.0, 0.5)), _at_station(c, 1, 64, (0, 1, 2), (1.5, 0.7, 0.1), side=-0.8)],
+                                             [_at_station(c, 2, 0, (0, 1), (0.0, 0.0, 0.3), ahead=1.0), _at_station(c, 2, 127, (2,), (0.0, 0.0, 0.5))]])
+        return c
+    if name == "wide":
+        B, n, m = 2, 400, 3
+        prm = params(ds=0.02, stations=4096, q_max=0, margin=0.2)
+        c = dict(paths=synth_paths(B, n, first=19), v_start=np.array([1.0, 0.0]), prm=prm, m=m, n_of=np.array([n, 150], np.int32), stop_before=None)
+        c["profile"] = _profiles(c["paths"], c["v_start"], c["n_of"])
+        c["scene_of"], c["a_of"] = np.array([0, 1], np.int32), None
+        c["agents"], _ = _scenes(m, [[_at_station(c, 0, 1100, (0, 2), (0.0, 0.0, 0.4), side=0.3), _at_station(c, 0, 2500, (1,), (1.5, 0.7, 0.1), side=-0.6)],
+                                     [_at_station(c, 1, 1300, (1, 2), (0.0, 0.0, 0.5), side=0.2), _at_station(c, 1, 2100, (0,), (2.0, 1.0, 0.0), side=0.9)]])
+        return c
+    if name == "thin":
+        B, n, m = 3, 300, 40
+        prm = params(ds=0.05, stations=1365, q_max=2, q_up=1, q_down=1, w_accel=0.25, margin=0.1)
+        c = dict(paths=synth_paths(B, n, first=23), v_start=np.array([0.0, 0.05, 0.1]), prm=prm, m=m, n_of=None, stop_before=None)
+        c["profile"] = _profiles(c["paths"], np.array([0.5, 0.5, 0.5]))
+        c["scene_of"], c["a_of"] = np.arange(B, dtype=np.int32), None
+        c["agents"], _ = _scenes(m, [[_at_station(c, 0, 20, range(4, 16), (0.0, 0.0, 0.3), ahead=4.5)],
+                                     [_at_station(c, 1, 10, range(10, m), (0.0, 0.0, 0.5), ahead=1.5)],
+                                     [_at_station(c, 2, 20, range(20, m), (0.0, 0.0, 0.5), ahead=1.5)]])
+        return c
+    raise KeyError(name)
+
+
+DEAD_ENDS = ("dead", "ties")
+HORIZONS = ("horizon70", "horizon260")
+FAMILIES = DEAD_ENDS + HORIZONS + ("steps", "standing", "wide", "thin")
+
+
+def last_lanes(one, prm):
+    """of one path's result: (the lanes e mod 256 of the states that live in its last living layer, e = j (Q + 1) + q; the winner's lane)"""
+    if one["reached"] == 0:
+        return [], None
+    Q1 = prm["q_max"] + 1
+    last = list(one["parents"][one["reached"] - 1]) if one["reached"] > 1 else [(0, one["q0"])]
+    j, q = (int(v) for v in one["steps"][one["reached"] - 1])
+    return [(j_ * Q1 + q_) % 256 for j_, q_ in last], (j * Q1 + q) % 256
 
 
 def run_case(c, circles, **kw):

@@ -9,7 +9,9 @@ bounds.  The shapes are the smallest that reach each piece of the kernels:
            and six layers no plan gets to station 32, so the steps that cross those word edges are the next case's);
   "cap"    S = 64, Q = 63, q_up = q_down = 63, m = 3: the widest step and window at 4096 states exactly - and one state more refused;
   "long"   S = 200, Q = 19, m = 12, n = 300, ragged n_of and stop_before: 4000 states on 256 lanes, five waypoint tiles, steps across the
-           words' edges up to station 120."""
+           words' edges up to station 120.
+Every plan of these gets through.  tests/test_gpu_speed_search_table.py has the plans that die late, more layers than lanes, other steps
+and weights, q_max = 0 - and holds the device form's whole `parents` table, of these cases too, to the restatement's."""
 import ctypes as C
 import functools
 import math
@@ -57,8 +59,12 @@ def _host(handle, c, car=None, blocked=True):
                                a_of=c.get("a_of"), scene_of=c.get("scene_of"), car=car, prm=_prm(c["prm"]), blocked=blocked)
 
 
-def _device(handle, c, car=None):
-    """the device form through device_form: the outputs lie in sentinel-filled allocations with a guard band behind them"""
+TABLE_SENTINEL = 77                                          # what `parents` is filled with before a call: no step is that large
+
+
+def _device(handle, c, car=None, table=None):
+    """the device form through device_form: the outputs lie in sentinel-filled allocations with a guard band behind them.
+    table: a list that gets `parents` [B][m][S][Q + 1] as the call left it (tests/test_gpu_speed_search_table.py reads it)"""
     import torch
     paths, profile, agents = (np.ascontiguousarray(c[k], dtype=np.float64) for k in ("paths", "profile", "agents"))
     B, n, stride = paths.shape
@@ -70,14 +76,17 @@ def _device(handle, c, car=None):
     out = dict(blocked=D.Out((B, m, S.words(Sn)), np.int32), steps=D.Out((B, m, 2), np.int32), traj=D.Out((B, m, 8)), cost=D.Out((B,)),
                reached=D.Out((B,), np.int32), flags=D.Out((B,), np.int32))
     frames = D.Out((n_scenes, a_max, m, 8)) if a_max else None
-    parents = torch.full((B * m * Sn * Q1 + D.GUARD,), 77, dtype=torch.uint8, device=D.dev())
+    parents = torch.full((B * m * Sn * Q1 + D.GUARD,), TABLE_SENTINEL, dtype=torch.uint8, device=D.dev())
     car = car if car is not None else capi.car_default_geometry()
     rc = D.call(handle, "pqp_speed_search_device", C.byref(_prm(p)), C.byref(car), B, n, stride, D.to_device(paths), opt("n_of"), opt("stop_before"),
                 D.to_device(profile), D.to_device(c["v_start"]), m, n_scenes, a_max, D.to_device(agents) if a_max else None, opt("a_of"), opt("scene_of"),
                 frames, out["blocked"], C.c_void_p(parents.data_ptr()), out["steps"], out["traj"], out["cost"], out["reached"], out["flags"])
     if rc:
         return rc, out, frames
-    assert (parents.cpu().numpy()[B * m * Sn * Q1:] == 77).all(), "the device form wrote behind the parents"
+    bytes_ = parents.cpu().numpy()
+    assert (bytes_[B * m * Sn * Q1:] == TABLE_SENTINEL).all(), "the device form wrote behind the parents"
+    if table is not None:
+        table.append(bytes_[:B * m * Sn * Q1].reshape(B, m, Sn, Q1))
     return rc, {k: v.get() for k, v in out.items()}, None if frames is None else frames.get()
 
 

@@ -1,8 +1,12 @@
 """pqp_speed_search without a GPU: the symbols and the binding, the constants and defaults, the refusals, the chain wrapper's argument
 checks, the C++ wrapper's build, the kernels' resources - and the numpy restatement the GPU tests compare the kernels against
-(tests/search_util.py): against every admissible plan by brute force, on hand cases with answers worked out on dyadic numbers, and the
-decision margins of the seeds the GPU test runs."""
+(tests/search_util.py): against every admissible plan by brute force (the plan, and the way back through the parents from every state of
+the last living layer), on hand cases with answers worked out on dyadic numbers, and the decision margins of the seeds the GPU tests run:
+the three seeded shapes and the hand cases of tests/test_gpu_speed_search.py, and the families of tests/test_gpu_speed_search_table.py
+("dead", "ties", "horizon70", "horizon260", "steps", "standing", "wide", "thin") with what each is there for - who dies where, which
+wavefronts hold the living states of a last layer, which flags occur."""
 import ctypes as C
+import functools
 import inspect
 import math
 import os
@@ -191,12 +195,21 @@ def test_the_kernels_use_no_scratch_and_spill_nothing(hip_lib, name, vgprs, occu
 
 # ---- the restatement against every admissible plan ---------------------------------------------------------------------------------------
 BRUTE = [(seed, 6 + seed % 7, 2 + seed % 2, 3 + seed % 3) for seed in range(8)]          # S 6 .. 12, Q 2 .. 3, m 3 .. 5
+# the parameter classes of search_util.family(): q_up > q_down, a car that can only stand, a price on slowness alone, other steps of time and arc
+BRUTE_MORE = {9: dict(q_up=3, q_down=1), 12: dict(q_up=2, q_down=1), 10: dict(q_max=0), 11: dict(w_slow=0.75, w_accel=0.0), 15: dict(w_slow=2.5, w_accel=0.0),
+              13: dict(dt=0.8, ds=0.3), 16: dict(dt=0.8, ds=0.3, q_up=3, q_down=1, w_slow=0.75, w_accel=0.5)}
+BRUTE += [(seed, 7 + seed % 5, 0 if seed == 10 else 3, 4 + seed % 2) for seed in BRUTE_MORE]
+
+
+def _q0(v0, prm):
+    return int(min(max(np.rint(np.float64(v0) * np.float64(prm["dt"]) / np.float64(prm["ds"])), 0.0), prm["q_max"]))
 
 
 def _brute_case(seed, Sn, Q, m, density):
     rng = np.random.default_rng(100 + seed)
     weights = {1: (0.0, 0.0), 2: (0.0, 0.0), 5: (0.0, 1.0)}.get(seed,(0.5, 2.0) if seed % 2 == 0 else (0.3, 1.7))      # dyadic and not; two that tie all over
     prm = S.params(stations=Sn, q_max=Q, q_up=1 + seed % 2, q_down=1 + (seed // 2) % 3, w_accel=weights[0], w_slow=weights[1])
+    prm.update(BRUTE_MORE.get(seed, {}))
     n = 2 * Sn + 1 - (seed % 3)                              # waypoints every 0.25 m: the path ends at, before or behind the grid
     path = S.straight(n, step=0.25)
     profile = S.profile_of(path, 1.0 * (seed % 3), v_end=None if seed % 4 else 0.0, prm=dict(v_max=1.75, a_max=0.75))
@@ -212,9 +225,10 @@ def test_the_search_finds_what_the_enumeration_finds(seed, Sn, Q, m, density):
     got = S.search(path, profile, v0, np.zeros((0, m, 8)), HAND_CIRCLES, m, prm=prm, cells=cells)
     full = S.unpack(got["blocked"], Sn)
     assert np.array_equal(full[:, :got["J"]], cells[:, :got["J"]]) and not full[:, got["J"]:].any()
-    q0 = min(max(int(round(v0 / 0.5)), 0), Q)
+    q0 = _q0(v0, prm)
+    assert q0 == min(max(int(round(v0 * prm["dt"] / prm["ds"])), 0), Q) == got["q0"]
     reached, plans = S.enumerate_plans(full, got["qenv"], got["J"], q0, prm)
-    assert got["reached"] == reached
+    assert got["reached"] == reached and len(got["parents"]) == max(reached, 1) and list(got["qref"]) == S.reference_steps(got["qenv"], got["J"], Q)
     if reached == 0:
         assert not plans and got["cost"] == INF and got["flags"] & S.START_BLOCKED
         return
@@ -223,6 +237,18 @@ def test_the_search_finds_what_the_enumeration_finds(seed, Sn, Q, m, density):
     assert got["cost"] == min(c for c, _ in plans) == cost                   # bit for bit: the same edges added in the same order
     assert got["steps"][:reached].tolist() == [list(jq) for jq in seq]
     assert (got["steps"][reached:] == -1).all() and bool(got["flags"] & S.NO_PLAN) == (reached < m)
+    # the table behind the plan: the states of the last living layer are the ends of the enumeration's sequences, and the way back from
+    # each of them through the parents is the first, by the parent rule, of the cheapest sequences that end there
+    ends = {}
+    for cs in plans:
+        ends.setdefault(cs[1][-1], []).append(cs)
+    assert set(ends) == (set(got["parents"][reached - 1]) if reached > 1 else {(0, q0)})
+    for (j, q), group in ends.items():
+        cost, seq = S.first_plan(group)
+        back = [(j, q)]
+        for k in range(reached - 1, 0, -1):
+            back.append((back[-1][0] - back[-1][1], got["parents"][k][back[-1]]))
+        assert back[::-1] == seq, (j, q)
 
 
 def test_the_brute_force_cases_hold_plans_dead_ends_and_ties():
@@ -232,7 +258,7 @@ def test_the_brute_force_cases_hold_plans_dead_ends_and_ties():
             prm, path, profile, v0, cells = _brute_case(seed, Sn, Q, m, density)
             got = S.search(path, profile, v0, np.zeros((0, m, 8)), HAND_CIRCLES, m, prm=prm, cells=cells)
             kinds.add("through" if got["reached"] == m else "blocked at the start" if got["reached"] == 0 else "dead end")
-            reached, plans = S.enumerate_plans(S.unpack(got["blocked"], Sn), got["qenv"], got["J"], min(int(round(v0 / 0.5)), Q), prm)
+            reached, plans = S.enumerate_plans(S.unpack(got["blocked"], Sn), got["qenv"], got["J"], _q0(v0, prm), prm)
             ties += sum(1 for c, _ in plans if c == got["cost"]) > 1
     assert kinds == {"through", "blocked at the start", "dead end"} and ties >= 2
 
@@ -384,3 +410,97 @@ def test_seeds_of_the_gpu_test_stay_clear_of_every_decision():
     for name, c in S.hand_cases().items():
         r = S.run_case(c, HAND_CIRCLES)
         assert r["margins"]["clear"] >= S.CLEAR_MARGIN and min(r["margins"]["cost_gap"], r["margins"]["end_gap"]) >= S.COST_MARGIN, (name, r["margins"])
+
+
+# ---- the families of tests/test_gpu_speed_search_table.py ------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _family(name):
+    c = S.family(name)
+    return c, S.run_case(c, F.car_circles())
+
+
+@pytest.mark.parametrize("name", S.FAMILIES)
+def test_families_of_the_table_test_stay_clear_of_every_decision(name):
+    """the same two margins as the seeds', no family and no path left out (an exact tie has an infinite gap: "ties" has nothing else)"""
+    c, r = _family(name)
+    assert r["margins"]["clear"] >= S.CLEAR_MARGIN, (name, r["margins"])
+    assert min(r["margins"]["cost_gap"], r["margins"]["end_gap"]) >= S.COST_MARGIN, (name, r["margins"])
+    assert (r["blocked"] != 0).any() and c["prm"]["stations"] * (c["prm"]["q_max"] + 1) <= S.MAX_STATES
+    for w in ("w_slow", "w_accel"):                          # dyadic: a cost gap is a tie or large
+        assert (c["prm"][w] * 16.0).is_integer()
+
+
+def _waves(one, prm):
+    lanes, win = S.last_lanes(one, prm)
+    return {l // 64 for l in lanes}, win, len(lanes) - len(set(lanes))
+
+
+@pytest.mark.parametrize("name", S.DEAD_ENDS)
+def test_the_dead_ends_die_late_and_in_every_wavefront(name):
+    """who dies where: the bad rows at layers 8 and 5, the wall at layer 5, the start above the envelope at layer 1, and path 4 gets through.
+    The last living layers of the four that move hold living states in all four wavefronts (e mod 256 in each range of 64) and lanes with
+    several living states; at least one winner lies in a wavefront that is neither the first nor the last, so no rule that takes the
+    first or the last wavefront's state finds it"""
+    c, r = _family(name)
+    m, prm = c["m"], c["prm"]
+    assert r["reached"].tolist() == [8, 5, 5, 1, m] and r["flags"].tolist() == [S.NO_PLAN] * 4 + [0]
+    assert [e["q0"] for e in r["each"]] == [0, 6, 0, prm["q_max"], 2] and r["each"][3]["qenv"].max() < prm["q_max"] - prm["q_down"]
+    cells = S.unpack(r["blocked"], prm["stations"])
+    for b, k in ((0, 8), (1, 5)):                            # the bad row: every station of the path at that layer, none elsewhere
+        J = r["each"][b]["J"]
+        assert cells[b, k, :J].all() and not np.delete(cells[b], k, axis=0).any()
+    in_reach = max(j for j, _ in r["each"][2]["parents"][4]) + prm["q_max"]
+    assert cells[2, 5, :in_reach + 1].all() and not cells[2, 5, r["each"][2]["J"] - 1] and not cells[2, :5].any()            # a wall, not a bad row
+    assert not cells[3].any()
+    seen = [_waves(r["each"][b], prm) for b in (0, 1, 2, 4)]
+    assert all(waves == {0, 1, 2, 3} for waves, _, _ in seen)
+    assert sum(win >= 64 for _, win, _ in seen) >= 1 and any(64 <= win < 192 for _, win, _ in seen)
+    assert sum(dup >= 1 for _, _, dup in seen) >= 2
+    for b in range(5):                                       # behind a dead end
+        k = r["reached"][b]
+        assert (r["steps"][b, k:] == -1).all() and (r["traj"][b, k:] == 0).all() and r["traj"][b, k - 1, 6] == 0
+    if name == "ties":
+        assert (r["cost"] == 0).all() and r["margins"]["cost_gap"] == INF == r["margins"]["end_gap"]
+        for b in (0, 1, 2, 4):                               # the terminal rule alone: the largest j of the last layer, then the smallest q
+            last = list(r["each"][b]["parents"][r["reached"][b] - 1])
+            assert tuple(r["steps"][b, r["reached"][b] - 1]) == min(last, key=lambda jq: (-jq[0], jq[1]))
+    else:
+        assert (r["cost"][[0, 1, 2, 4]] > 0).all()
+
+
+@pytest.mark.parametrize("name", S.HORIZONS)
+def test_the_horizons_wait_and_go_beside_an_empty_and_a_bad_path(name):
+    c, r = _family(name)
+    m = c["m"]
+    assert m in (70, 260) and r["reached"].tolist() == [m, 0, m, 0, m]
+    assert r["flags"].tolist() == [S.ARRIVED, S.EMPTY, S.GRID_SHORT, S.NOT_FINITE, S.GRID_SHORT] and r["each"][0]["J"] < c["prm"]["stations"]
+    for b in (0, 2, 4):                                      # stands for most of the horizon, then goes to the last station
+        j = r["steps"][b, :, 0]
+        stand = np.flatnonzero(np.diff(j) == 0)
+        assert (np.diff(j) >= 0).all() and j[-1] == r["each"][b]["J"] - 1 and j[m - 25] < j[-1] and len(stand) >= m - 25
+
+
+def test_the_other_families_hold_what_they_are_there_for():
+    c, r = _family("steps")
+    assert c["paths"].shape[2] == 9 and (c["paths"][:, :, 7:] == 1e9).all() and c["prm"]["q_up"] > c["prm"]["q_down"]
+    assert (r["reached"] == c["m"]).all() and [e["q0"] for e in r["each"]] == [0, 5, 12] and c["v_start"][2] * 0.8 / 0.3 > 12.5
+    assert all(_waves(e, c["prm"])[0] == {0, 1, 2, 3} for e in r["each"])
+    c, r = _family("standing")
+    assert S.words(c["prm"]["stations"]) == 5 and r["reached"].tolist() == [6, 3, 0]
+    assert r["flags"].tolist() == [S.GRID_SHORT, S.GRID_SHORT | S.NO_PLAN, S.GRID_SHORT | S.NO_PLAN | S.START_BLOCKED]
+    assert (r["steps"][0] == 0).all() and (r["traj"][0, :, 4:7] == 0).all() and r["traj"][0, :, 7].tolist() == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0]
+    assert (r["blocked"] != 0).any(axis=(0, 1)).all()          # every one of the five words, the third tile's single one too
+    c, r = _family("wide")
+    J = [e["J"] for e in r["each"]]
+    assert J[0] == 4096 and J[1] % 64 != 0 and 2048 < J[1] < 4096 - 64 and r["flags"].tolist() == [S.GRID_SHORT, 0] and (r["reached"] == 3).all()
+    cells = S.unpack(r["blocked"], 4096)
+    for b in range(2):                                       # agents beyond tile 15 and beyond tile 31; nothing behind the path's last station
+        assert cells[b, :, 1024:2048].any() and cells[b, :, 2048:J[b]].any() and not cells[b, :, J[b]:].any()
+    c, r = _family("thin")
+    assert c["prm"]["stations"] * 3 == S.MAX_STATES - 1 and r["reached"].tolist() == [40, 10, 20]
+    j = r["steps"][0, :, 0]
+    assert (np.diff(j) == 1)[:11].all() and j[-1] > 64                       # held back by the waiting agent, then at the full step into a second station tile
+    # somewhere on a curved path: ARRIVED, GRID_SHORT, and neither with the path ending on the grid
+    assert _family("horizon70")[1]["flags"][0] == S.ARRIVED and _family("steps")[1]["flags"][0] == S.GRID_SHORT
+    dead = _family("dead")
+    assert dead[1]["flags"][4] == 0 and dead[1]["each"][4]["J"] < dead[0]["prm"]["stations"]
