@@ -1327,6 +1327,99 @@ int pqp_select_plans(pqp_handle* h, const double* prm, int require_free, int bat
                      int path_stride, const double* paths, const int32_t* n_of, int groups, const int32_t* group_start, double* terms,
                      int32_t* best, double* best_traj, int32_t* best_m, double* best_paths, int32_t* best_n);
 
+/* ---- tracked agents to predicted rows, on the layers' steps and on fine steps ---------------------------------------------------------
+ * pqp_agents_check, pqp_speed_search and the fine check behind pqp_sample_plan read agents [n_scenes][a_max][steps][PQP_AGENT_STRIDE], a
+ * pose and a size per agent per time step.  A perception stack delivers tracks: a pose, a speed, an acceleration, a yaw rate, a size and
+ * usually the lane the agent is in.  This turns tracks into those rows on the device: one call with r = 1 fills the rows the search reads
+ * at its m layers, a second with r > 1 fills the rows of the fine check on M = (m - 1) * r + 1 steps, and by the time expression below
+ * the two agree at the layers bit for bit.  Only the tracks cross to the device.  The reference has no counterpart: it plans against a
+ * static map. */
+/* The parameters are PQP_PREDICT_PARAMS doubles, prm[PQP_PREDICT_V_CAP] ... prm[PQP_PREDICT_L_MAX], by value as pqp_speed_refine's are: no
+ * struct.  pqp_predict_default_params (pure host; a NULL pointer is ignored) writes v_cap 40 m/s (no track accelerates beyond it), grow
+ * 0 m/s (what a row's radius gains per second of prediction) and l_max 3 m (how far from its lane's line a track may lie and still follow
+ * it). */
+#define PQP_TRACK_STRIDE 9         /* x, y, heading, v, a, yaw_rate, half_length, half_width, radius */
+#define PQP_ANCHOR_STRIDE 4        /* s0, l0, dir, heading error to the lane */
+#define PQP_PREDICT_PARAMS 3
+enum { PQP_PREDICT_V_CAP = 0, PQP_PREDICT_GROW = 1, PQP_PREDICT_L_MAX = 2 };
+void pqp_predict_default_params(double* prm);
+enum { PQP_PREDICT_ABSENT = 1, PQP_PREDICT_BAD = 2, PQP_PREDICT_ON_LANE = 4, PQP_PREDICT_LANE_FAR = 8, PQP_PREDICT_OFF_LANE = 16,
+       PQP_PREDICT_STOPS = 32, PQP_PREDICT_CAPPED = 64 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional.  t0, dt, m and r
+ * travel by value:
+ *   tracks [n_scenes][a_max][PQP_TRACK_STRIDE]   x, y, heading, v >= 0 along the heading, a, yaw rate w, half_length, half_width, radius >= 0
+ *   a_of [n_scenes] or NULL              agents per scene, min(max(a_of, 0), a_max); NULL: a_max.  A slot at or beyond it is not read
+ *   lane_of [n_scenes][a_max] int32 or NULL   the lane a track follows.  Below 0, or NULL: the free model.  At or above n_lanes: the free model
+ *                                        with PQP_PREDICT_LANE_FAR; the host form refuses it
+ *   lane_spline [n_lanes][9][lane_m], lane_ext [n_lanes][4], lane_length [n_lanes]   spline tables as pqp_spline_fit writes and
+ *                                        pqp_project_points reads them.  With n_lanes = 0 they may be NULL
+ *   m >= 1 layers dt apart from t0 on, r >= 1 sub-steps per layer: M = (m - 1) * r + 1 steps
+ * Outputs, fully overwritten:
+ *   agents [n_scenes][a_max][M][PQP_AGENT_STRIDE]   x, y, heading, half_length, half_width, radius: pqp_agents_check's input
+ *   anchor [n_scenes][a_max][PQP_ANCHOR_STRIDE] or NULL
+ *   flags [n_scenes][a_max]
+ * The definition, in fp64, every product, quotient and sum rounded on its own (no contraction), min as fmin, for one track (x0, y0, h0,
+ * v, a, w, ...):
+ *   time of step f       k = f / r, i = f % r;  tau = t0 + ((double)k * dt + ((double)i * dt) / (double)r): pqp_sample_plan's t.  The rows
+ *                        of an r = 1 call are rows k * r of an r > 1 call bit for bit
+ *   the speed            a acts for te seconds, then the speed is ve for tc = tau - te seconds:
+ *                          a < 0:          ts = v / (-a); te = min(tau, ts); ve = 0 when tau >= ts (the stop is reached), else v + a * te
+ *                          a > 0, v < v_cap:   tl = (v_cap - v) / a; te = min(tau, tl); ve = v_cap when tau >= tl (the cap is reached), else
+ *                                          v + a * te
+ *                          a > 0, v >= v_cap:  te = 0, ve = v, the cap is reached: it ends an acceleration and slows nobody down
+ *                          a = 0, v > 0:   te = tau, ve = v
+ *                          a = 0, v = 0:   te = 0, ve = 0, the stop is reached: the track stands from the start (*)
+ *                        D = (v + (0.5 * a) * te) * te + ve * tc, the distance driven.  A stopped agent neither moves nor turns.
+ *                        PQP_PREDICT_STOPS: some step has reached the stop; PQP_PREDICT_CAPPED: some step has reached the cap
+ *   free model           constant turn rate and acceleration in closed form.  th = w * te;  vt = v * te;  at = a * (te * te);
+ *                          p = vt * sinc(th) + at * f1(th);  q = vt * cosc(th) + at * f2(th)     in the frame of h0
+ *                          h1 = h0 + th;  th2 = w * tc when ve > 0, else 0;  vt2 = ve * tc
+ *                          p2 = vt2 * sinc(th2);  q2 = vt2 * cosc(th2)                          in the frame of h1
+ *                          x = (x0 + (p * cos h0 - q * sin h0)) + (p2 * cos h1 - q2 * sin h1)
+ *                          y = (y0 + (p * sin h0 + q * cos h0)) + (p2 * sin h1 + q2 * cos h1)    one sincos per frame
+ *                          heading = constrainAngle(h1 + th2)
+ *                        with, for |th| >= 2^-6 and sh = sin(0.5 * th), hv = 2 * (sh * sh):
+ *                          sinc = sin th / th;  cosc = hv / th;  f1 = (th * sin th - hv) / (th * th);  f2 = (sin th - th * cos th) / (th * th)
+ *                        and below it their Taylor polynomials through th^5, t2 = th * th:
+ *                          sinc = 1 - t2 * (1/6 - t2 * (1/120));        cosc = th * (0.5 - t2 * (1/24 - t2 * (1/720)))
+ *                          f1 = 0.5 - t2 * (1/8 - t2 * (1/144));        f2 = th * (1/3 - t2 * (1/30 - t2 * (1/840)))
+ *                        (the quotients 1/6 ... as fp64 constants), so w = 0 needs no case of its own and nothing divides by a small
+ *                        number.  At the switch the two forms of each function differ by less than 4e-15
+ *   lane model           for 0 <= lane_of < n_lanes, once per track: s0 = the abscissa of (x0, y0) on its lane as pqp_project_points
+ *                        finds it (the same search, bit for bit), the lane's point and heading hp = atan2(y', x') at s0, l0 by
+ *                        global2Local exactly as pqp_project_points takes its l, dh = constrainAngle(h0 - hp), dir = +1 when
+ *                        cos(h0 - hp) >= 0, else -1: oncoming traffic drives towards decreasing s.
+ *                        The track is not on that lane when l0 is not finite, |l0| > l_max, or the lane's length is <= 0 or >= 2^20 m
+ *                        (no search is made then: s0 = l0 = dh = 0).  It gets the free model, PQP_PREDICT_LANE_FAR, and anchor
+ *                        (s0, l0, 0, dh).  Otherwise PQP_PREDICT_ON_LANE is set, the yaw rate is not read, and at every step
+ *                          s_f = s0 + dir * D
+ *                          x, y = pqp_offsets_to_points' expression at (s_f, l0): beyond the lane's ends the spline's own extrapolation
+ *                          heading = the lane's at s_f, atan2(y', x'); for dir < 0 constrainAngle of that + pi
+ *                        PQP_PREDICT_OFF_LANE: some s_f lies outside [0, length]
+ *   rows                 half_length and half_width are copied bit for bit; radius_f = radius + grow * tau
+ *   anchor               (s0, l0, dir, dh) of a track that was searched for on a lane; four zeros for every other
+ *   absent               a slot at or beyond a_of, or a track with half_length < 0 or half_width < 0: (0, 0, 0, -1, -1, 0) at every step
+ *                        and PQP_PREDICT_ABSENT alone
+ *   bad                  a present track with a value that is not finite, v < 0 or radius < 0: x, y and heading are NaN at every step,
+ *                        half_length, half_width and radius are the track's own (no growth), and PQP_PREDICT_BAD is set alone.
+ *                        pqp_agents_check reads such a row as a bad frame that hits everything: the conservative reading.  The
+ *                        neighbours are untouched
+ * (*) the one rule the cases above leave open: with a = 0 a standing track would otherwise turn on the spot under its yaw rate.
+ * A result depends on the track, its lane and the parameters alone: the same bits at any (scene, agent) position and from either form.
+ * No atomics.  The _device form is one launch, asynchronous on the handle's stream, and allocates nothing; with a_max = 0 it launches
+ * nothing.  The host form copies in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the
+ * outputs untouched, for a null pointer that is not optional (h, prm; tracks, agents and flags unless a_max = 0; the three lane arrays
+ * unless n_lanes = 0), n_scenes < 1, a_max < 0, m < 1, r < 1, M > INT_MAX, n_scenes * a_max * M > 2^38, a t0 that is not finite or
+ * negative, a dt that is not finite and positive, a parameter that is not finite or negative, n_lanes < 0, or lane_m < 2 with
+ * n_lanes > 0. */
+int pqp_predict_agents_device(pqp_handle* h, const double* prm, double t0, double dt, int m, int r, int n_scenes, int a_max,
+                              const double* tracks, const int32_t* a_of, const int32_t* lane_of, int n_lanes, int lane_m,
+                              const double* lane_spline, const double* lane_ext, const double* lane_length, double* agents, double* anchor,
+                              int32_t* flags);
+int pqp_predict_agents(pqp_handle* h, const double* prm, double t0, double dt, int m, int r, int n_scenes, int a_max, const double* tracks,
+                       const int32_t* a_of, const int32_t* lane_of, int n_lanes, int lane_m, const double* lane_spline,
+                       const double* lane_ext, const double* lane_length, double* agents, double* anchor, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,65 @@ def rank_default_params(lib=None, **over):
     return p
 
 
+class PredictParams:
+    """what pqp_predict_agents takes besides its arrays and the time grid: the PREDICT_PARAMS doubles the C ABI passes as a plain array
+    (v_cap, grow, l_max, at PREDICT_V_CAP .. PREDICT_L_MAX), under the names of the header's enumerators.
+    predict_default_params(grow=...) as for the other parameter sets."""
+    __slots__ = ("v_cap", "grow", "l_max")
+    _INDEX = (("v_cap", PREDICT_V_CAP), ("grow", PREDICT_GROW), ("l_max", PREDICT_L_MAX))
+
+    def __init__(self, values):
+        for name, i in self._INDEX:
+            setattr(self, name, float(values[i]))
+
+    def array(self):
+        out = np.zeros(PREDICT_PARAMS)
+        for name, i in self._INDEX:
+            out[i] = getattr(self, name)
+        return out
+
+
+def predict_default_params(lib=None, **over):
+    """pqp_predict_default_params: v_cap 40 m/s, grow 0 m/s, l_max 3 m - this library's choice - with `over` applied."""
+    lib = lib or load_library()
+    values = np.full(PREDICT_PARAMS, -1.0)
+    lib.pqp_predict_default_params(values)
+    p = PredictParams(values)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+class _PredictedAgents:
+    """the shape of an agents array that a prediction fills on the device (optimize_path's tracks=): what the checks of agents= and
+    plan_agents= read of a host array, without the array"""
+    __slots__ = ("shape",)
+
+    def __init__(self, shape):
+        self.shape = tuple(int(v) for v in shape)
+
+    @property
+    def size(self):
+        return int(np.prod(self.shape))
+
+    @property
+    def ndim(self):
+        return len(self.shape)
+
+
+def _lanes(lanes, who):
+    """lanes = (spline [n_lanes][9][lane_m], spline_ext [n_lanes][4], length [n_lanes]) or None -> (n_lanes, lane_m, the three arrays)"""
+    if lanes is None:
+        return 0, 0, None, None, None
+    spl, ext, length = (np.ascontiguousarray(a, dtype=np.float64) for a in lanes)
+    if spl.ndim != 3 or spl.shape[1] != 9 or ext.shape != (spl.shape[0], 4) or length.shape != (spl.shape[0],):
+        raise ValueError(f"{who}: lanes must be (spline [n_lanes][9][lane_m], spline_ext [n_lanes][4], length [n_lanes]), not "
+                         f"{spl.shape}, {ext.shape}, {length.shape}")
+    if spl.shape[0] == 0:
+        return 0, 0, None, None, None
+    return spl.shape[0], spl.shape[2], spl, ext, length
+
+
 def car_circles(car=None, lib=None):
     """pqp_car_circles (pure host): [7][3] x, y, r in the vehicle frame of rr, rl, fr, fl, fm, rm and the bounding circle."""
     lib = lib or load_library()
@@ -445,7 +504,7 @@ class Handle:
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
                       plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
-                      t0=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                      t0=None, tracks=None, layers=None, predict_anchor=False, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -489,24 +548,34 @@ class Handle:
         and plan_first_hit and that clearance go in.  rank_params: RankParams (None: rank_default_params()).  Adds terms [B][8],
         rank_terms [B][10], rank_best [groups], best_paths [groups][n_max][7], best_n, best_traj [groups][rows][8], best_m (and
         plan_clearance with plan_agents).  winners_only (with rank): out, free, margin, profile, search_traj, refine_traj, plan_traj and
-        plan_clearance stay on the device and are not in the dict."""
+        plan_clearance stay on the device and are not in the dict.
+        tracks: (tracks [n_scenes][a_max][9], lane_of [n_scenes][a_max] or None, lanes = (spline, spline_ext, length) or None, PredictParams or
+        None) with layers=m (needs search; refused together with agents= or plan_agents=) - pqp_predict_agents_device on the same stream
+        in place of both uploads: with r = 1 at the search's dt into the rows the search reads, and with plan_samples=r into the rows the
+        fine check reads, so only the tracks cross to the device and the two agree at the layers.  agents_of / scene_of / agents_params
+        apply as with agents=.  Adds predict_flags [n_scenes][a_max] of PREDICT_* (and predict_anchor [n_scenes][a_max][4] with
+        predict_anchor=True).  (tracks, layers and predict_anchor stand in front of rank: tests pin the last five names of the signature.)"""
+        predicting, agents, plan_agents = self._tracks(tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples)
         return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
                            (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only and rank is None),
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
                            self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents),
-                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]))
+                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]), predicting)
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
                               winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None,
                               agents_params=None, sample=None,
-                              samples=None, t0=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                              samples=None, t0=None, tracks=None, layers=None, predict_anchor=False, rank=None, rank_params=None, speed=None,
+                              v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
-        agents_params / search / refine / plan_samples / plan_agents / rank / rank_params: as for optimize_path)."""
+        agents_params / search / refine / plan_samples / plan_agents / rank / rank_params / tracks / layers / predict_anchor: as for
+        optimize_path)."""
+        predicting, agents, plan_agents = self._tracks(tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples)
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
         return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
@@ -514,7 +583,42 @@ class Handle:
                            self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
                            self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
                            self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents),
-                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]))
+                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]), predicting)
+
+    def _tracks(self, tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples):
+        """tracks= of optimize_path: (what _chain predicts from, or None; agents; plan_agents) - with tracks the two arrays are the shapes
+        of what the prediction fills on the device"""
+        if tracks is None:
+            if layers is not None or predict_anchor:
+                raise ValueError("layers / predict_anchor need tracks=")
+            return None, agents, plan_agents
+        if agents is not None or plan_agents is not None:
+            raise ValueError("tracks is refused together with agents= or plan_agents=: the prediction fills both on the device")
+        if not isinstance(search, SearchParams):
+            raise ValueError("tracks needs search=SearchParams: the agents are predicted at its layers' times")
+        if len(tracks) != 4:
+            raise ValueError("tracks must be (tracks, lane_of or None, lanes or None, PredictParams or None)")
+        tr, lane_of, lanes, prm = tracks
+        tr = np.ascontiguousarray(tr, dtype=np.float64)
+        if tr.ndim != 3 or tr.shape[0] < 1 or tr.shape[2] != TRACK_STRIDE:
+            raise ValueError(f"tracks must be [n_scenes >= 1][a_max][{TRACK_STRIDE}], not {tr.shape}")
+        if layers is None or isinstance(layers, bool) or int(layers) != layers or int(layers) < 1:
+            raise ValueError("tracks needs layers=m >= 1, the layers of the search")
+        layers = int(layers)
+        if lane_of is not None:
+            lane_of = np.ascontiguousarray(lane_of, dtype=np.int32)
+            if lane_of.shape != tr.shape[:2]:
+                raise ValueError(f"tracks: lane_of must be {tr.shape[:2]}, not {lane_of.shape}")
+        lanes = _lanes(lanes, "tracks")
+        if lane_of is not None and (lane_of >= lanes[0]).any():
+            raise ValueError(f"tracks: lane_of at or above the {lanes[0]} lanes given")
+        if prm is not None and not isinstance(prm, PredictParams):
+            raise ValueError("tracks: the parameters must be a PredictParams")
+        prm = prm if prm is not None else predict_default_params(self.lib)
+        fine = None
+        if plan_samples is not None and not isinstance(plan_samples, bool) and int(plan_samples) == plan_samples and int(plan_samples) >= 1:
+            fine = _PredictedAgents(tr.shape[:2] + ((layers - 1) * int(plan_samples) + 1, AGENT_STRIDE))
+        return (tr, lane_of, lanes, prm, bool(predict_anchor)), _PredictedAgents(tr.shape[:2] + (layers, AGENT_STRIDE)), fine
 
     def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
         if speed is None:
@@ -574,7 +678,8 @@ class Handle:
         if fine > 2 ** 31 - 1:
             raise ValueError(f"plan_samples: (m - 1) r + 1 = {fine} samples per path do not fit an int")
         if plan_agents is not None:
-            plan_agents = np.ascontiguousarray(plan_agents, dtype=np.float64)
+            if not isinstance(plan_agents, _PredictedAgents):
+                plan_agents = np.ascontiguousarray(plan_agents, dtype=np.float64)
             want = tuple(np.shape(agents)[:2]) + (fine, AGENT_STRIDE)
             if plan_agents.shape != want:
                 raise ValueError(f"plan_agents must be [n_scenes][a_max][(m - 1) r + 1][{AGENT_STRIDE}] = {want}, the scenes and agents of agents=, "
@@ -603,7 +708,8 @@ class Handle:
             return None
         if sample is None and search is None:
             raise ValueError("agents needs sample=PqpSampleParams: the agents are given at the samples' time steps")
-        agents = np.ascontiguousarray(agents, dtype=np.float64)
+        if not isinstance(agents, _PredictedAgents):
+            agents = np.ascontiguousarray(agents, dtype=np.float64)
         if sample is None:                                             # the search alone: the agents' steps are its layers
             if agents.ndim != 4 or agents.shape[0] < 1 or agents.shape[2] < 1 or agents.shape[3] != AGENT_STRIDE:
                 raise ValueError(f"agents must be [n_scenes >= 1][a_max][m >= 1][{AGENT_STRIDE}], not {agents.shape}")
@@ -630,7 +736,8 @@ class Handle:
                 bool(winners_only))
 
     def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None, planning=None, ranking=None):
+               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None, planning=None, ranking=None,
+               predicting=None):
         """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
         them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
         selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
@@ -638,7 +745,9 @@ class Handle:
         (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that (when there is a sampling), or
         None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None; refining: RefineParams
         of the speed QP behind that search, or None; planning: (r, plan_agents or None) of the plan's fine time step behind both, or None;
-        ranking: (group_start, RankParams, winners_only) of the choice between the finished trajectories behind everything, or None"""
+        ranking: (group_start, RankParams, winners_only) of the choice between the finished trajectories behind everything, or None;
+        predicting: (tracks, lane_of or None, _lanes' tuple, PredictParams, anchor) of a prediction that fills the agents' rows on the device -
+        moving's agents and planning's plan_agents are then shapes (_PredictedAgents) - or None"""
         import torch
         dev = torch.device("cuda", self.device)
         cfg = cfg or self.chain_config()
@@ -678,7 +787,16 @@ class Handle:
         if moving is not None:
             ag, ag_of, scene_of, ag_prm, ag_car = moving
             ag_car = ag_car if ag_car is not None else car_default_geometry(self.lib)
-            d_ag, d_ag_of, d_scene = t(ag, np.float64), t(ag_of, np.int32), t(scene_of, np.int32)
+            d_ag_of, d_scene = t(ag_of, np.int32), t(scene_of, np.int32)
+            if predicting is None:
+                d_ag = t(ag, np.float64)
+            else:                           # the rows are predicted where the search reads them: only the tracks cross to the device
+                pr_tracks, pr_lane_of, (pr_n_lanes, pr_lane_m, pr_spl, pr_ext, pr_len), pr_prm, pr_want_anchor = predicting
+                d_ag = torch.empty(ag.shape, dtype=torch.float64, device=dev)
+                d_pr_tracks, d_pr_lane_of = t(pr_tracks, np.float64), t(pr_lane_of, np.int32)
+                d_pr_spl, d_pr_ext, d_pr_len = t(pr_spl, np.float64), t(pr_ext, np.float64), t(pr_len, np.float64)
+                pr_flags, pr_fine_flags = (torch.zeros(ag.shape[:2], dtype=torch.int32, device=dev) for _ in range(2))
+                pr_anchor = torch.zeros(ag.shape[:2] + (ANCHOR_STRIDE,), dtype=torch.float64, device=dev) if pr_want_anchor else None
             ag_frames = torch.zeros(ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
         if moving is not None and sampling is not None:
             first_hit = torch.zeros(rows, dtype=torch.int32, device=dev)
@@ -705,7 +823,7 @@ class Handle:
             pl_m_of, pl_flags = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
             pl_defect, pl_excess = (torch.zeros(rows, dtype=torch.float64, device=dev) for _ in range(2))
             if pl_ag is not None:
-                d_pl_ag = t(pl_ag, np.float64)
+                d_pl_ag = t(pl_ag, np.float64) if predicting is None else torch.empty(pl_ag.shape, dtype=torch.float64, device=dev)
                 pl_frames = torch.zeros(pl_ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
                 pl_first, pl_who = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
         if ranking is not None:             # (no selection: the rows are the B candidates)
@@ -754,6 +872,13 @@ class Handle:
                 self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, out, ints[0],
                                                                   first if footprint is not None else None, profile, d_t0, m, traj,
                                                                   traj_n, traj_flags))
+        if predicting is not None:          # the agents' rows at the layers' times, and on the fine steps the plan is checked at
+            predict = lambda r, d_rows, anchor, flags: self._check(self.lib.pqp_predict_agents_device(
+                self._h, pr_prm.array(), 0.0, float(searching.dt), ag.shape[2], r, ag.shape[0], ag.shape[1], d_pr_tracks, d_ag_of, d_pr_lane_of,
+                pr_n_lanes, pr_lane_m, d_pr_spl, d_pr_ext, d_pr_len, d_rows, anchor, flags))
+            predict(1, d_ag, pr_anchor, pr_flags)
+            if planning is not None and pl_ag is not None:
+                predict(pl_r, d_pl_ag, None, pr_fine_flags)
         if moving is not None and sampling is not None:      # behind the sampler, on its samples: all of them with hold_last (the parked car), else those on the path
             self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, m, TRAJ_STRIDE, traj,
                                                          None if sa_prm.hold_last else traj_n, ag.shape[0], ag.shape[1],
@@ -839,6 +964,10 @@ class Handle:
             res.update(plan_m_of=host(pl_m_of), plan_defect=host(pl_defect), plan_excess=host(pl_excess), plan_flags=host(pl_flags))
             if pl_ag is not None:
                 res.update(plan_first_hit=host(pl_first), plan_hit_agent=host(pl_who))
+        if predicting is not None:
+            res.update(predict_flags=host(pr_flags))
+            if pr_anchor is not None:
+                res.update(predict_anchor=host(pr_anchor))
         if ranking is not None:
             if rk_clear is not None and every_row:
                 res.update(plan_clearance=host(rk_clear))
@@ -968,6 +1097,38 @@ class Handle:
         res = dict(first_hit=first, hit_agent=who)
         if clearance:
             res["clearance"] = cl
+        return res
+
+    def predict_agents(self, tracks, t0=0.0, dt=1.0, m=1, r=1, a_of=None, lane_of=None, lanes=None, prm=None, anchor=False):
+        """pqp_predict_agents (host arrays): tracks [n_scenes][a_max][9] = x, y, heading, v, a, yaw_rate, half_length, half_width, radius
+        -> the agents' rows at m layers dt apart from t0 on, r sub-steps per layer; optionally a_of [n_scenes] (agents per scene), lane_of
+        [n_scenes][a_max] (the lane a track follows; < 0 or None: the free model) with lanes = (spline [n_lanes][9][lane_m], spline_ext
+        [n_lanes][4], length [n_lanes]) as spline_fit returns and project_points takes them; prm = PredictParams (None:
+        predict_default_params()).  Returns dict(agents [n_scenes][a_max][(m - 1) r + 1][6], flags [n_scenes][a_max] of PREDICT_*[, anchor
+        [n_scenes][a_max][4] = s0, l0, dir, heading error])."""
+        tracks = np.ascontiguousarray(tracks, dtype=np.float64)
+        if tracks.ndim != 3 or tracks.shape[2] != TRACK_STRIDE:
+            raise ValueError(f"predict_agents: tracks must be [n_scenes][a_max][{TRACK_STRIDE}], not {tracks.shape}")
+        n_scenes, a_max = tracks.shape[:2]
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        ao, lo = i32(a_of), i32(lane_of)
+        for name, a, size in (("a_of", ao, n_scenes), ("lane_of", lo, n_scenes * a_max)):
+            if a is not None and a.size != size:
+                raise ValueError(f"predict_agents: {name} must have {size} entries, not {a.size}")
+        n_lanes, lane_m, spl, ext, length = _lanes(lanes, "predict_agents")
+        prm = prm if prm is not None else predict_default_params(self.lib)
+        m, r = int(m), int(r)
+        M = max(m - 1, 0) * max(r, 0) + 1
+        if M > 2 ** 31 - 1:
+            raise ValueError(f"predict_agents: (m - 1) r + 1 = {M} steps do not fit an int")
+        agents = np.zeros((n_scenes, a_max, M, AGENT_STRIDE))
+        flags = np.zeros((n_scenes, a_max), dtype=np.int32)
+        anc = np.zeros((n_scenes, a_max, ANCHOR_STRIDE)) if anchor else None
+        self._check(self.lib.pqp_predict_agents(self._h, prm.array(), float(t0), float(dt), m, r, n_scenes, a_max, tracks, ao, lo, n_lanes, lane_m,
+                                                spl, ext, length, agents, anc, flags))
+        res = dict(agents=agents, flags=flags)
+        if anchor:
+            res["anchor"] = anc
         return res
 
     def speed_search(self, paths, profile, v_start, agents, m=None, n_of=None, stop_before=None, a_of=None, scene_of=None, car=None, prm=None,
