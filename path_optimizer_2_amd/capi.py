@@ -6,8 +6,11 @@ fallback: if the library or a HIP device is missing, loading / pqp_create fails 
 Nothing of the ABI is restated here: the Structure classes (pqp_grid_geometry -> PqpGridGeometry), the constants (PQP_OPT_STORE_WARM ->
 OPT_STORE_WARM), EXPORTS and every function's argtypes / restype are built from what pqp_header reads in include/pqp.h.
 """
+import collections
 import ctypes as C
+import inspect
 import os
+import types
 
 import numpy as np
 
@@ -435,6 +438,206 @@ def _column_major(maps, dtype):
     return np.ascontiguousarray(np.transpose(maps, (0, 2, 1)))
 
 
+_i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+_f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _check_sizes(who, *named):
+    """(name, array or None, entries) of a host-array method's optional arrays"""
+    for name, a, size in named:
+        if a is not None and a.size != size:
+            raise ValueError(f"{who}: {name} must have {size} entries, not {a.size}")
+
+
+def _paths_with_profile(who, paths, profile):
+    """paths [B][n][stride] and their profile [B][n][4] as float64 arrays, and (B, n, stride)"""
+    paths = _f64(paths)
+    B, n, stride = paths.shape
+    profile = _f64(profile)
+    if profile.shape != (B, n, SPEED_STRIDE):
+        raise ValueError(f"{who}: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+    return paths, profile, (B, n, stride)
+
+
+# ---- the steps of Handle.optimize_path, one record each ----------------------------------------------------------------------------------
+# A stage function takes the call's context c (Handle._chain_plan) and returns its record; _STAGES below says which calls have the step:
+#   outputs  (result key, shape, dtype, per_candidate): a zero-filled device buffer of that name, downloaded under that key - unless
+#            per_candidate (a row per candidate, not per winner) and winners_only, which keep it on the device
+#   scratch  (name, shape, dtype[, "empty"]): device buffers nothing downloads, zero-filled unless "empty"
+#   uploads  (name, host array or None, dtype)
+#   launch   launch(h, c, d): the step's library calls on handle h, d = the call's device buffers by name (a name may hold None, and
+#            d.get(name) is None too where no stage of this call made the buffer)
+# Every buffer exists before the call's one torch.cuda.synchronize, which orders torch's uploads and fills before the launches on the
+# handle's non-blocking stream: a launch allocates nothing.
+_Stage = collections.namedtuple("_Stage", "outputs scratch uploads launch")
+_F, _I, _U8 = "float64", "int32", "uint8"
+_per_row = lambda rows, dtype, *keys: tuple((k, (rows,), dtype, False) for k in keys)
+_paths = lambda c, d: (d[c.paths[0]], d[c.paths[1]], d.get(c.paths[2]))         # paths, n_of, stop_before of the speed stages
+
+
+def _agent_rows(c, d, rows="agents", frames="agent_frames"):
+    """n_scenes, a_max, the agents' rows, agents_of, scene_of, the frames: what every reader of the agents takes (a_max = 0: no rows)"""
+    shape, some = c.moving[0].shape, c.moving[0].size > 0
+    return shape[0], shape[1], d[rows] if some else None, d["agents_of"], d["scene_of"], d[frames] if some else None
+
+
+def _stage_chain(c):
+    """pqp_optimize_path_device itself, in the same form"""
+    a = c.args
+    launch = lambda h, c, d: h._check(h.lib.pqp_optimize_path_device(
+        h._h, a.smoother._h if a.smoother is not None else None, C.byref(c.cfg), c.B, np.shape(a.points)[1], d["points"], d["n_points"], d["start"],
+        d["target"], d["dist"], d["map_of"], C.byref(a.geom), d["start_k"], d["out"], d["n_out"], d["status"], d["stage"], d["iters"]))
+    return _Stage((("out", (c.B, c.n_max, 7), _F, True),) + _per_row(c.B, _I, "n_out", "status", "stage", "iters"), (),
+                  (("points", a.points, _F), ("n_points", a.n_points, _I), ("start", a.start, _F), ("target", a.target, _F), ("map_of", a.map_of, _I),
+                   ("start_k", a.start_k, _F)), launch)
+
+
+def _stage_footprint(c):
+    """behind the chain: reads out / n_out where they are"""
+    launch = lambda h, c, d: h._check(h.lib.pqp_footprint_check_device(
+        h._h, c.B, c.n_max, 7, d["out"], d["n_out"], d["dist"], d["map_of"], C.byref(c.args.geom), C.byref(c.car), c.footprint, d["free"],
+        d["first_collision"], d["margin"]))
+    return _Stage((("free", (c.B, c.n_max), _U8, True), ("first_collision", (c.B,), _I, False), ("margin", (c.B, c.n_max), _F, True)), (), (), launch)
+
+
+def _stage_selection(c):
+    """behind both: reads out, n_out, status, stage (and first_collision, margin) where they are"""
+    launch = lambda h, c, d: h._check(h.lib.pqp_select_paths_device(
+        h._h, C.byref(c.selection[1]), c.B, c.n_max, 7, d["out"], d["n_out"], d["status"], d["stage"], d.get("first_collision"), d.get("margin"),
+        c.groups, d["group_start"], d["terms"], d["best"], d["best_paths"], d["best_n"]))
+    return _Stage((("terms", (c.B, SCORE_STRIDE), _F, False), ("best", (c.groups,), _I, False), ("best_paths", (c.groups, c.n_max, 7), _F, False),
+                   ("best_n", (c.groups,), _I, False)), (), (("group_start", c.selection[0], _I),), launch)
+
+
+def _stage_speed(c):
+    """behind all of them, on c.paths: the winners where the selection left them (an eligible winner is collision-free: require_free), or
+    every candidate in `out` up to its first collision"""
+    launch = lambda h, c, d: h._check(h.lib.pqp_speed_profile_device(
+        h._h, C.byref(c.speed[0]), c.rows, c.n_max, 7, *_paths(c, d), None, d["v_start"], d["v_end"], d["profile"], d["speed_flags"]))
+    return _Stage((("profile", (c.rows, c.n_max, SPEED_STRIDE), _F, c.per_candidate), ("speed_flags", (c.rows,), _I, False)), (),
+                  (("v_start", c.speed[1], _F), ("v_end", c.speed[2], _F)), launch)
+
+
+def _stage_sampling(c):
+    """behind the speed profile, on the arrays it ran on"""
+    prm, m, t0 = c.sampling
+    launch = lambda h, c, d: h._check(h.lib.pqp_sample_trajectory_device(
+        h._h, C.byref(prm), c.rows, c.n_max, 7, *_paths(c, d), d["profile"], d["t0"], m, d["traj"], d["traj_n"], d["traj_flags"]))
+    return _Stage((("traj", (c.rows, m, TRAJ_STRIDE), _F, False),) + _per_row(c.rows, _I, "traj_n", "traj_flags"), (), (("t0", t0, _F),), launch)
+
+
+def _stage_predicting(c):
+    """the agents' rows on the device, for every step that reads them: uploaded, or with tracks= predicted where the search reads them - at
+    the layers' times, and on the fine steps the plan is checked at - so that only the tracks cross to the device"""
+    ag, agents_of, scene_of = c.moving[:3]
+    uploads = (("agents_of", agents_of, _I), ("scene_of", scene_of, _I))
+    frames = (("agent_frames", ag.shape[:3] + (AGENT_FRAME_STRIDE,), _F),)
+    if c.predicting is None:
+        return _Stage((), frames, uploads + (("agents", ag, _F),), lambda h, c, d: None)
+    tracks, lane_of, (n_lanes, lane_m, spl, ext, length), prm, want_anchor = c.predicting
+
+    def launch(h, c, d):
+        predict = lambda r, rows, anchor, flags: h._check(h.lib.pqp_predict_agents_device(
+            h._h, prm.array(), 0.0, float(c.searching.dt), ag.shape[2], r, ag.shape[0], ag.shape[1], d["tracks"], d["agents_of"], d["lane_of"], n_lanes,
+            lane_m, d["lane_spline"], d["lane_ext"], d["lane_length"], rows, anchor, flags))
+        predict(1, d["agents"], d.get("predict_anchor"), d["predict_flags"])
+        if d.get("plan_agents") is not None:
+            predict(c.planning, d["plan_agents"], None, d["predict_fine_flags"])          # (written, never returned)
+    return _Stage((("predict_flags", ag.shape[:2], _I, False),) + ((("predict_anchor", ag.shape[:2] + (ANCHOR_STRIDE,), _F, False),) if want_anchor else ()),
+                  frames + (("agents", ag.shape, _F, "empty"), ("predict_fine_flags", ag.shape[:2], _I)),
+                  uploads + (("tracks", tracks, _F), ("lane_of", lane_of, _I), ("lane_spline", spl, _F), ("lane_ext", ext, _F), ("lane_length", length, _F)),
+                  launch)
+
+
+def _stage_agents(c):
+    """behind the sampler, on its samples: all of them with hold_last (the parked car), else those on the path"""
+    launch = lambda h, c, d: h._check(h.lib.pqp_agents_check_device(
+        h._h, float(c.moving[3].margin), C.byref(c.car), c.rows, c.samples, TRAJ_STRIDE, d["traj"], None if c.sampling[0].hold_last else d["traj_n"],
+        *_agent_rows(c, d), d["first_hit"], d["hit_agent"], d["agent_clearance"]))
+    return _Stage(_per_row(c.rows, _I, "first_hit", "hit_agent") + (("agent_clearance", (c.rows, c.samples), _F, False),), (), (), launch)
+
+
+def _stage_searching(c):
+    """behind the speed profile, on the rows it ran on and under its envelope; its blocked bits are the refine's to read and to report"""
+    se, n, m = c.searching, c.rows, c.layers
+    launch = lambda h, c, d: h._check(h.lib.pqp_speed_search_device(
+        h._h, C.byref(se), C.byref(c.car), n, c.n_max, 7, *_paths(c, d), d["profile"], d["v_start"], m, *_agent_rows(c, d), d["search_blocked"],
+        d["search_parents"], d["search_steps"], d["search_traj"], d["search_cost"], d["search_reached"], d["search_flags"]))
+    stations = max(int(se.stations), 0)
+    blocked = ("search_blocked", (n, m, (stations + 31) // 32), _I, False)
+    return _Stage((("search_steps", (n, m, 2), _I, False), ("search_traj", (n, m, TRAJ_STRIDE), _F, c.per_candidate), ("search_cost", (n,), _F, False))
+                  + _per_row(n, _I, "search_reached", "search_flags") + ((blocked,) if c.refining is not None else ()),
+                  (("search_parents", (n, m, stations, max(int(se.q_max) + 1, 1)), _U8),) + ((blocked[:3],) if c.refining is None else ()), (), launch)
+
+
+def _stage_refining(c):
+    """behind the search, on the rows it ran on and on what it wrote"""
+    rf, n, m = c.refining, c.rows, c.layers
+    launch = lambda h, c, d: h._check(h.lib.pqp_speed_refine_device(
+        h._h, C.byref(c.searching), rf.array(), int(rf.window), n, c.n_max, 7, *_paths(c, d), d["profile"], d["v_start"], m, d["search_blocked"],
+        d["search_steps"], d["search_reached"], d["search_traj"], d["refine_traj"], d["refine_bounds"], d["refine_cost"], d["refine_excess"],
+        d["refine_status"], d["refine_iters"], d["refine_flags"]))
+    return _Stage((("refine_traj", (n, m, TRAJ_STRIDE), _F, c.per_candidate), ("refine_bounds", (n, m, 3), _F, False))
+                  + _per_row(n, _F, "refine_cost", "refine_excess") + _per_row(n, _I, "refine_status", "refine_flags"),
+                  (("refine_iters", (n,), _I),), (), launch)
+
+
+def _stage_planning(c):
+    """behind the refine (or the search alone), on the rows they ran on and on the plan they wrote: a refined path under constant
+    acceleration, the search's or a kept one linearly"""
+    n, refined = c.rows, c.refining is not None
+    launch = lambda h, c, d: h._check(h.lib.pqp_sample_plan_device(
+        h._h, float(c.searching.dt), c.planning, 0 if refined else 1, n, c.n_max, 7, *_paths(c, d), d["profile"], c.layers,
+        d["refine_traj" if refined else "search_traj"], d["search_reached"], d.get("refine_flags"), d["plan_traj"], d["plan_m_of"], d["plan_defect"],
+        d["plan_excess"], d["plan_flags"]))
+    return _Stage((("plan_traj", (n, c.fine, TRAJ_STRIDE), _F, c.per_candidate), ("plan_m_of", (n,), _I, False))
+                  + _per_row(n, _F, "plan_defect", "plan_excess") + _per_row(n, _I, "plan_flags"), (), (), launch)
+
+
+def _stage_plan_agents(c):
+    """behind that, on the fine rows that are on the plan - uploaded, or with tracks= filled by the prediction; with rank= the check also
+    writes the clearance the ranking reads"""
+    fine = c.plan_agents
+    launch = lambda h, c, d: h._check(h.lib.pqp_agents_check_device(
+        h._h, float(c.moving[3].margin), C.byref(c.car), c.rows, c.fine, TRAJ_STRIDE, d["plan_traj"], d["plan_m_of"],
+        *_agent_rows(c, d, "plan_agents", "plan_frames"), d["plan_first_hit"], d["plan_hit_agent"], d.get("plan_clearance")))
+    frames = (("plan_frames", fine.shape[:3] + (AGENT_FRAME_STRIDE,), _F),)
+    rows = (("plan_agents", fine.shape, _F, "empty"),) if c.predicting is not None else ()          # predicted: no upload
+    return _Stage(_per_row(c.rows, _I, "plan_first_hit", "plan_hit_agent"), frames + rows, () if rows else (("plan_agents", fine, _F),), launch)
+
+
+def _stage_ranking(c):
+    """behind everything (no selection: the rows are the B candidates): the paths' terms, then the finished trajectories - the fine rows,
+    else the refine's, else the search's - and each group's best"""
+    group_start, prm = c.ranking[:2]
+    groups, steps = group_start.size - 1, c.fine if c.planning is not None else c.layers
+    traj, m_of = ("plan_traj", "plan_m_of") if c.planning is not None else ("refine_traj" if c.refining is not None else "search_traj", "search_reached")
+    clearance = c.plan_agents is not None          # the fine check ran: its first hits and clearance go in
+
+    def launch(h, c, d):
+        h._check(h.lib.pqp_select_paths_device(h._h, C.byref(select_default_params(h.lib)), c.B, c.n_max, 7, d["out"], d["n_out"], d["status"], d["stage"],
+                                               d.get("first_collision"), d.get("margin"), 0, d["rank_start"], d["terms"], d["rank_best"], None, None))
+        h._check(h.lib.pqp_select_plans_device(h._h, prm.array(), int(prm.require_free), c.B, steps, TRAJ_STRIDE, d[traj], d[m_of], d["terms"],
+                                               d["search_flags"], d["plan_first_hit"] if clearance else None, d.get("plan_clearance"), c.n_max, 7,
+                                               d["out"], d["n_out"], groups, d["rank_start"], d["rank_terms"], d["rank_best"], d["best_traj"],
+                                               d["best_m"], d["best_paths"], d["best_n"]))
+    return _Stage(((("plan_clearance", (c.B, c.fine), _F, True),) if clearance else ())
+                  + (("terms", (c.B, SCORE_STRIDE), _F, False), ("rank_terms", (c.B, PLAN_SCORE_STRIDE), _F, False), ("rank_best", (groups,), _I, False),
+                     ("best_paths", (groups, c.n_max, 7), _F, False), ("best_n", (groups,), _I, False),
+                     ("best_traj", (groups, steps, TRAJ_STRIDE), _F, False), ("best_m", (groups,), _I, False)),
+                  (), (("rank_start", group_start, _I),), launch)
+
+
+# (stage, the fields of the context it needs: the call has the step when none of them is None), in launch order; the result's keys come
+# in the same order, except that the prediction's stand behind the fine plan's
+_STAGES = ((_stage_chain, ()), (_stage_footprint, ("footprint",)), (_stage_selection, ("selection",)), (_stage_speed, ("speed",)),
+           (_stage_sampling, ("sampling",)), (_stage_predicting, ("moving",)), (_stage_agents, ("moving", "sampling")),
+           (_stage_searching, ("searching",)), (_stage_refining, ("refining",)), (_stage_planning, ("planning",)),
+           (_stage_plan_agents, ("plan_agents",)), (_stage_ranking, ("ranking",)))
+_RESULT_ORDER = [f for f, _ in _STAGES if f is not _stage_predicting]
+_RESULT_ORDER.insert(_RESULT_ORDER.index(_stage_ranking), _stage_predicting)
+
+
 class Handle:
     """Thin RAII wrapper over pqp_handle (one per GPU)."""
 
@@ -554,36 +757,30 @@ class Handle:
         in place of both uploads: with r = 1 at the search's dt into the rows the search reads, and with plan_samples=r into the rows the
         fine check reads, so only the tracks cross to the device and the two agree at the layers.  agents_of / scene_of / agents_params
         apply as with agents=.  Adds predict_flags [n_scenes][a_max] of PREDICT_* (and predict_anchor [n_scenes][a_max][4] with
-        predict_anchor=True).  (tracks, layers and predict_anchor stand in front of rank: tests pin the last five names of the signature.)"""
-        predicting, agents, plan_agents = self._tracks(tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples)
-        return self._chain(points, n_points, start, target, _column_major(dist, np.float32), np.float32, None, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only and rank is None),
-                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
-                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents),
-                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]), predicting)
+        predict_anchor=True).  (tracks, layers and predict_anchor stand in front of rank: tests pin the last five names of the signature.)
+        Every step behind the chain is one record of _STAGES above (its outputs, its uploads, its calls); _chain_plan checks the arguments and
+        lays the call out from them without a device, _chain runs it."""
+        a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
+        del a["self"], a["dist"]
+        return self._chain(self._chain_plan(**a), dist, np.float32, None)
 
     def optimize_path_on_grid(self, points, n_points, start, target, grid, geom, map_of=None, smoother=None, cfg=None, start_k=None,
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
-                              winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None,
-                              agents_params=None, sample=None,
-                              samples=None, t0=None, tracks=None, layers=None, predict_anchor=False, rank=None, rank_params=None, speed=None,
-                              v_start=None, v_end=None):
+                              winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None,
+                              scene_of=None, agents_params=None, sample=None, samples=None, t0=None, tracks=None, layers=None, predict_anchor=False,
+                              rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
         agents_params / search / refine / plan_samples / plan_agents / rank / rank_params / tracks / layers / predict_anchor: as for
         optimize_path)."""
-        predicting, agents, plan_agents = self._tracks(tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples)
+        a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
+        del a["self"], a["grid"]
+        plan = self._chain_plan(**a)
         grid = _occupancy(grid, "optimize_path_on_grid")
         build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
-        return self._chain(points, n_points, start, target, _column_major(grid, np.uint8), np.uint8, build, geom, map_of, smoother, cfg, start_k,
-                           (car, footprint_mode) if check_footprint else None, self._selection(select, select_params, winners_only and rank is None),
-                           self._speed(speed, v_start, v_end, check_footprint, select, select_params), self._sample(sample, samples, t0, speed),
-                           self._agents(agents, agents_of, scene_of, agents_params, sample, samples, car, np.shape(points)[0], select, search),
-                           self._search(search, speed, agents), self._refine(refine, search), self._plan(plan_samples, plan_agents, search, agents),
-                           self._ranking(rank, rank_params, winners_only, search, select, np.shape(points)[0]), predicting)
+        return self._chain(plan, grid, np.uint8, build)
 
     def _tracks(self, tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples):
         """tracks= of optimize_path: (what _chain predicts from, or None; agents; plan_agents) - with tracks the two arrays are the shapes
@@ -735,245 +932,83 @@ class Handle:
         return (np.ascontiguousarray(select, dtype=np.int32), select_params if select_params is not None else select_default_params(self.lib),
                 bool(winners_only))
 
-    def _chain(self, points, n_points, start, target, layer_cm, layer_dtype, build, geom, map_of, smoother, cfg, start_k, footprint=None,
-               selection=None, speed=None, sampling=None, moving=None, searching=None, refining=None, planning=None, ranking=None,
-               predicting=None):
-        """layer_cm: the maps in the ABI's column-major order, uploaded as layer_dtype; build(d_grid, d_dist): enqueues the float layer from
-        them on the handle's stream (None: they are the layer); footprint: (car, mode) of a footprint check behind the chain, or None;
-        selection: (group_start, PqpSelectParams, winners_only) of a selection behind both, or None; speed: (PqpSpeedParams, v_start, v_end)
-        of a speed profile behind all three, or None; sampling: (PqpSampleParams, samples, t0) of a time grid behind that, or None; moving:
-        (agents, agents_of, scene_of, AgentsParams, car) of a check against predicted agents behind that (when there is a sampling), or
-        None; searching: SearchParams of a path-time search against those agents behind the speed profile, or None; refining: RefineParams
-        of the speed QP behind that search, or None; planning: (r, plan_agents or None) of the plan's fine time step behind both, or None;
-        ranking: (group_start, RankParams, winners_only) of the choice between the finished trajectories behind everything, or None;
-        predicting: (tracks, lane_of or None, _lanes' tuple, PredictParams, anchor) of a prediction that fills the agents' rows on the device -
-        moving's agents and planning's plan_agents are then shapes (_PredictedAgents) - or None"""
+    def _chain_plan(self, **a):
+        """optimize_path's arguments by name (what is not given has the signature's default) -> the call laid out, without a device: every
+        argument check - the one place the validators above are called from - and then the context c that the stage records read:
+          c.args, c.cfg, c.B, c.n_max    the arguments, the chain's configuration, the batch and the waypoints per path
+          c.footprint .. c.predicting    each step's checked parameters (planning: r, plan_agents beside it), or None where the call has no such step
+          c.car                          the footprint of the footprint check and of every check against agents
+          c.groups, c.rows, c.paths      the rows of the speed stages - `groups` with select=, else B - and the buffers they run on as (paths,
+                                         n_of, stop_before): the winners' best_paths / best_n and no stop, or out / n_out and first_collision
+          c.per_candidate                whether those rows are the candidates', which winners_only keeps on the device
+          c.samples, c.layers, c.fine    the step counts: the sampler's, the search's m and the fine plan's (m - 1) r + 1
+          c.stages                       the records of the call's steps, in launch order
+          c.result, c.on_device          (key, shape, dtype) of the returned dict in its order, and the keys winners_only keeps on the device"""
+        if not a.keys() <= _CHAIN_ARGS.keys():
+            raise TypeError(f"optimize_path has no argument {', '.join(sorted(a.keys() - _CHAIN_ARGS.keys()))}")
+        a = types.SimpleNamespace(**{**_CHAIN_ARGS, **a})
+        B = np.shape(a.points)[0]
+        predicting, agents, plan_agents = self._tracks(a.tracks, a.layers, a.predict_anchor, a.search, a.agents, a.plan_agents, a.plan_samples)
+        c = types.SimpleNamespace(
+            args=a, B=B, predicting=predicting, footprint=int(a.footprint_mode) if a.check_footprint else None,
+            selection=self._selection(a.select, a.select_params, a.winners_only and a.rank is None),
+            speed=self._speed(a.speed, a.v_start, a.v_end, a.check_footprint, a.select, a.select_params),
+            sampling=self._sample(a.sample, a.samples, a.t0, a.speed),
+            moving=self._agents(agents, a.agents_of, a.scene_of, a.agents_params, a.sample, a.samples, a.car, B, a.select, a.search),
+            searching=self._search(a.search, a.speed, agents), refining=self._refine(a.refine, a.search),
+            planning=self._plan(a.plan_samples, plan_agents, a.search, agents),
+            ranking=self._ranking(a.rank, a.rank_params, a.winners_only, a.search, a.select, B))
+        c.planning, c.plan_agents = c.planning or (None, None)         # r, and the agents' fine rows or their shape
+        c.cfg = a.cfg or _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", {})
+        c.n_max = c.cfg.n_max
+        if c.selection is not None:
+            _check_group_start(c.selection[0], B)
+        c.groups = None if c.selection is None else c.selection[0].size - 1          # (one or more: group_start runs from 0 to B)
+        c.per_candidate = c.selection is None
+        c.rows, per = (B, "candidate") if c.per_candidate else (c.groups, "group")
+        c.paths = ("out", "n_out", None if c.footprint is None else "first_collision") if c.per_candidate else ("best_paths", "best_n", None)
+        if c.speed is not None and (c.speed[1].size != c.rows or (c.speed[2] is not None and c.speed[2].size != c.rows)):
+            raise ValueError(f"v_start / v_end must have one entry per {per} ({c.rows})")
+        if c.sampling is not None and c.sampling[2] is not None and c.sampling[2].size != c.rows:
+            raise ValueError(f"t0 must have one entry per {per} ({c.rows})")
+        needs_car = c.footprint is not None or c.moving is not None
+        c.car = car_default_geometry(self.lib) if needs_car and a.car is None else a.car
+        c.samples = None if c.sampling is None else c.sampling[1]
+        c.layers = None if c.searching is None else c.moving[0].shape[2]
+        c.fine = None if c.planning is None else (c.layers - 1) * c.planning + 1
+        have = vars(c)
+        records = {f: f(c) for f, needs in _STAGES if all(have[n] is not None for n in needs)}
+        c.stages = list(records.values())
+        outputs = [o for f in _RESULT_ORDER if f in records for o in records[f].outputs]
+        winners = bool(a.winners_only)
+        c.result = [o[:3] for o in outputs if not (winners and o[3])]
+        c.on_device = [o[0] for o in outputs if winners and o[3]]
+        return c
+
+    def _chain(self, c, maps, layer_dtype, build):
+        """runs the call _chain_plan laid out.  maps: [n_maps][rows][cols] (or 2-D), uploaded in the ABI's column-major order as layer_dtype;
+        build(d_grid, d_dist): enqueues the float layer from them on the handle's stream (None: they are the layer)"""
         import torch
         dev = torch.device("cuda", self.device)
-        cfg = cfg or self.chain_config()
-        t = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        d_layer = t(layer_cm, layer_dtype)
-        d_dist = d_layer if build is None else torch.empty(d_layer.shape, dtype=torch.float32, device=dev)
-        B, p_max = points.shape[0], points.shape[1]
-        d_pts, d_np, d_st, d_tg = t(points, np.float64), t(n_points, np.int32), t(start, np.float64), t(target, np.float64)
-        d_map, d_k = t(map_of, np.int32), t(start_k, np.float64)
-        out = torch.zeros((B, cfg.n_max, 7), dtype=torch.float64, device=dev)
-        ints = [torch.zeros(B, dtype=torch.int32, device=dev) for _ in range(4)]
-        if selection is not None:
-            group_start, sel_prm, winners_only = selection
-            _check_group_start(group_start, B)
-            groups = group_start.size - 1           # (one or more: group_start runs from 0 to B)
-            d_start = t(group_start, np.int32)
-            terms = torch.zeros((B, SCORE_STRIDE), dtype=torch.float64, device=dev)
-            best = torch.zeros(groups, dtype=torch.int32, device=dev)
-            best_paths = torch.zeros((groups, cfg.n_max, 7), dtype=torch.float64, device=dev)
-            best_n = torch.zeros(groups, dtype=torch.int32, device=dev)
-        if speed is not None:
-            sp_prm, v_start, v_end = speed
-            rows = groups if selection is not None else B
-            if v_start.size != rows or (v_end is not None and v_end.size != rows):
-                raise ValueError(f"v_start / v_end must have one entry per {'group' if selection is not None else 'candidate'} ({rows})")
-            d_vs, d_ve = t(v_start, np.float64), t(v_end, np.float64)
-            profile = torch.zeros((rows, cfg.n_max, SPEED_STRIDE), dtype=torch.float64, device=dev)
-            speed_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
-        if sampling is not None:
-            sa_prm, m, t0 = sampling
-            if t0 is not None and t0.size != rows:
-                raise ValueError(f"t0 must have one entry per {'group' if selection is not None else 'candidate'} ({rows})")
-            d_t0 = t(t0, np.float64)
-            traj = torch.zeros((rows, m, TRAJ_STRIDE), dtype=torch.float64, device=dev)
-            traj_n = torch.zeros(rows, dtype=torch.int32, device=dev)
-            traj_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
-        if moving is not None:
-            ag, ag_of, scene_of, ag_prm, ag_car = moving
-            ag_car = ag_car if ag_car is not None else car_default_geometry(self.lib)
-            d_ag_of, d_scene = t(ag_of, np.int32), t(scene_of, np.int32)
-            if predicting is None:
-                d_ag = t(ag, np.float64)
-            else:                           # the rows are predicted where the search reads them: only the tracks cross to the device
-                pr_tracks, pr_lane_of, (pr_n_lanes, pr_lane_m, pr_spl, pr_ext, pr_len), pr_prm, pr_want_anchor = predicting
-                d_ag = torch.empty(ag.shape, dtype=torch.float64, device=dev)
-                d_pr_tracks, d_pr_lane_of = t(pr_tracks, np.float64), t(pr_lane_of, np.int32)
-                d_pr_spl, d_pr_ext, d_pr_len = t(pr_spl, np.float64), t(pr_ext, np.float64), t(pr_len, np.float64)
-                pr_flags, pr_fine_flags = (torch.zeros(ag.shape[:2], dtype=torch.int32, device=dev) for _ in range(2))
-                pr_anchor = torch.zeros(ag.shape[:2] + (ANCHOR_STRIDE,), dtype=torch.float64, device=dev) if pr_want_anchor else None
-            ag_frames = torch.zeros(ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
-        if moving is not None and sampling is not None:
-            first_hit = torch.zeros(rows, dtype=torch.int32, device=dev)
-            hit_agent = torch.zeros(rows, dtype=torch.int32, device=dev)
-            agent_clearance = torch.zeros((rows, m), dtype=torch.float64, device=dev)
-        if searching is not None:
-            layers, se_S, se_Q1 = ag.shape[2], int(searching.stations), int(searching.q_max) + 1
-            se_blocked = torch.zeros((rows, layers, (max(se_S, 0) + 31) // 32), dtype=torch.int32, device=dev)
-            se_parents = torch.zeros((rows, layers, max(se_S, 0), max(se_Q1, 1)), dtype=torch.uint8, device=dev)
-            se_steps = torch.zeros((rows, layers, 2), dtype=torch.int32, device=dev)
-            se_traj = torch.zeros((rows, layers, TRAJ_STRIDE), dtype=torch.float64, device=dev)
-            se_cost = torch.zeros(rows, dtype=torch.float64, device=dev)
-            se_reached = torch.zeros(rows, dtype=torch.int32, device=dev)
-            se_flags = torch.zeros(rows, dtype=torch.int32, device=dev)
-        if refining is not None:
-            rf_traj = torch.zeros((rows, layers, TRAJ_STRIDE), dtype=torch.float64, device=dev)
-            rf_bounds = torch.zeros((rows, layers, 3), dtype=torch.float64, device=dev)
-            rf_cost, rf_excess = (torch.zeros(rows, dtype=torch.float64, device=dev) for _ in range(2))
-            rf_status, rf_iters, rf_flags = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(3))
-        if planning is not None:
-            pl_r, pl_ag = planning
-            pl_m = (layers - 1) * pl_r + 1
-            pl_traj = torch.zeros((rows, pl_m, TRAJ_STRIDE), dtype=torch.float64, device=dev)
-            pl_m_of, pl_flags = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
-            pl_defect, pl_excess = (torch.zeros(rows, dtype=torch.float64, device=dev) for _ in range(2))
-            if pl_ag is not None:
-                d_pl_ag = t(pl_ag, np.float64) if predicting is None else torch.empty(pl_ag.shape, dtype=torch.float64, device=dev)
-                pl_frames = torch.zeros(pl_ag.shape[:3] + (AGENT_FRAME_STRIDE,), dtype=torch.float64, device=dev)
-                pl_first, pl_who = (torch.zeros(rows, dtype=torch.int32, device=dev) for _ in range(2))
-        if ranking is not None:             # (no selection: the rows are the B candidates)
-            rk_start, rk_prm, rk_winners = ranking
-            rk_groups = rk_start.size - 1
-            d_rk_start = t(rk_start, np.int32)
-            rk_sel = select_default_params(self.lib)
-            rk_path_terms = torch.zeros((B, SCORE_STRIDE), dtype=torch.float64, device=dev)
-            rk_rows = pl_m if planning is not None else layers
-            rk_terms = torch.zeros((B, PLAN_SCORE_STRIDE), dtype=torch.float64, device=dev)
-            rk_best, rk_best_m, rk_best_n = (torch.zeros(rk_groups, dtype=torch.int32, device=dev) for _ in range(3))
-            rk_best_traj = torch.zeros((rk_groups, rk_rows, TRAJ_STRIDE), dtype=torch.float64, device=dev)
-            rk_best_paths = torch.zeros((rk_groups, cfg.n_max, 7), dtype=torch.float64, device=dev)
-            rk_clear = torch.zeros((B, pl_m), dtype=torch.float64, device=dev) if planning is not None and pl_ag is not None else None
-        torch.cuda.synchronize(dev)
+        t = lambda x, dt: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)
+        d = dict(layer=t(_column_major(maps, layer_dtype), layer_dtype))
+        d["dist"] = d["layer"] if build is None else torch.empty(d["layer"].shape, dtype=torch.float32, device=dev)
+        for s in c.stages:
+            for name, x, dt in s.uploads:
+                d[name] = t(x, dt)
+            for name, shape, dtype, _ in s.outputs:
+                d[name] = torch.zeros(shape, dtype=getattr(torch, dtype), device=dev)
+            for name, shape, dtype, *how in s.scratch:
+                d[name] = (torch.empty if how else torch.zeros)(shape, dtype=getattr(torch, dtype), device=dev)
+        torch.cuda.synchronize(dev)         # the one fence between torch's stream and the handle's: nothing is created after it
         if build is not None:
-            build(d_layer, d_dist)
-        self._check(self.lib.pqp_optimize_path_device(self._h, smoother._h if smoother is not None else None, C.byref(cfg), B, p_max, d_pts, d_np,
-                                                      d_st, d_tg, d_dist, d_map, C.byref(geom), d_k, out, ints[0], ints[1],
-                                                      ints[2], ints[3]))
-        if footprint is not None:           # behind the chain on the handle's stream: reads out / n_out where they are
-            car, mode = footprint
-            car = car if car is not None else car_default_geometry(self.lib)
-            free = torch.zeros((B, cfg.n_max), dtype=torch.uint8, device=dev)
-            first = torch.zeros(B, dtype=torch.int32, device=dev)
-            margin = torch.zeros((B, cfg.n_max), dtype=torch.float64, device=dev)
-            self._check(self.lib.pqp_footprint_check_device(self._h, B, cfg.n_max, 7, out, ints[0], d_dist, d_map, C.byref(geom),
-                                                            C.byref(car), int(mode), free, first, margin))
-        if selection is not None:           # behind both: reads out, n_out, status, stage (and first_collision, margin) where they are
-            self._check(self.lib.pqp_select_paths_device(self._h, C.byref(sel_prm), B, cfg.n_max, 7, out, ints[0], ints[1], ints[2],
-                                                         first if footprint is not None else None, margin if footprint is not None else None,
-                                                         groups, d_start, terms, best, best_paths, best_n))
-        if speed is not None:               # behind all of them: the winners where the selection left them, or every candidate in `out`
-            if selection is not None:       # (an eligible winner is collision-free: require_free)
-                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), groups, cfg.n_max, 7, best_paths, best_n, None, None,
-                                                              d_vs, d_ve, profile, speed_flags))
-            else:
-                self._check(self.lib.pqp_speed_profile_device(self._h, C.byref(sp_prm), B, cfg.n_max, 7, out, ints[0],
-                                                              first if footprint is not None else None, None, d_vs, d_ve, profile,
-                                                              speed_flags))
-        if sampling is not None:            # behind the speed profile, on the arrays it ran on
-            if selection is not None:
-                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), groups, cfg.n_max, 7, best_paths, best_n, None,
-                                                                  profile, d_t0, m, traj, traj_n, traj_flags))
-            else:
-                self._check(self.lib.pqp_sample_trajectory_device(self._h, C.byref(sa_prm), B, cfg.n_max, 7, out, ints[0],
-                                                                  first if footprint is not None else None, profile, d_t0, m, traj,
-                                                                  traj_n, traj_flags))
-        if predicting is not None:          # the agents' rows at the layers' times, and on the fine steps the plan is checked at
-            predict = lambda r, d_rows, anchor, flags: self._check(self.lib.pqp_predict_agents_device(
-                self._h, pr_prm.array(), 0.0, float(searching.dt), ag.shape[2], r, ag.shape[0], ag.shape[1], d_pr_tracks, d_ag_of, d_pr_lane_of,
-                pr_n_lanes, pr_lane_m, d_pr_spl, d_pr_ext, d_pr_len, d_rows, anchor, flags))
-            predict(1, d_ag, pr_anchor, pr_flags)
-            if planning is not None and pl_ag is not None:
-                predict(pl_r, d_pl_ag, None, pr_fine_flags)
-        if moving is not None and sampling is not None:      # behind the sampler, on its samples: all of them with hold_last (the parked car), else those on the path
-            self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, m, TRAJ_STRIDE, traj,
-                                                         None if sa_prm.hold_last else traj_n, ag.shape[0], ag.shape[1],
-                                                         d_ag if ag.size else None, d_ag_of, d_scene, ag_frames if ag.size else None,
-                                                         first_hit, hit_agent, agent_clearance))
-        if searching is not None:           # behind the speed profile, on the rows it ran on and under its envelope
-            on_winners = selection is not None
-            self._check(self.lib.pqp_speed_search_device(self._h, C.byref(searching), C.byref(ag_car), rows, cfg.n_max, 7,
-                                                         best_paths if on_winners else out, best_n if on_winners else ints[0],
-                                                         first if (footprint is not None and not on_winners) else None, profile, d_vs, layers,
-                                                         ag.shape[0], ag.shape[1], d_ag if ag.size else None, d_ag_of, d_scene,
-                                                         ag_frames if ag.size else None, se_blocked, se_parents, se_steps, se_traj, se_cost,
-                                                         se_reached, se_flags))
-        if refining is not None:            # behind the search, on the rows it ran on and on what it wrote
-            self._check(self.lib.pqp_speed_refine_device(self._h, C.byref(searching), refining.array(), int(refining.window), rows, cfg.n_max, 7,
-                                                         best_paths if on_winners else out, best_n if on_winners else ints[0],
-                                                         first if (footprint is not None and not on_winners) else None, profile, d_vs, layers,
-                                                         se_blocked, se_steps, se_reached, se_traj, rf_traj, rf_bounds, rf_cost, rf_excess,
-                                                         rf_status, rf_iters, rf_flags))
-        if planning is not None:            # behind the refine (or the search alone), on the rows they ran on and on the plan they wrote
-            on_winners = selection is not None
-            self._check(self.lib.pqp_sample_plan_device(self._h, float(searching.dt), pl_r, 0 if refining is not None else 1, rows, cfg.n_max, 7,
-                                                        best_paths if on_winners else out, best_n if on_winners else ints[0],
-                                                        first if (footprint is not None and not on_winners) else None, profile, layers,
-                                                        rf_traj if refining is not None else se_traj, se_reached,
-                                                        rf_flags if refining is not None else None, pl_traj, pl_m_of, pl_defect, pl_excess,
-                                                        pl_flags))
-            if pl_ag is not None:           # behind that, on the fine rows that are on the plan
-                self._check(self.lib.pqp_agents_check_device(self._h, float(ag_prm.margin), C.byref(ag_car), rows, pl_m, TRAJ_STRIDE, pl_traj,
-                                                             pl_m_of, pl_ag.shape[0], pl_ag.shape[1], d_pl_ag if pl_ag.size else None, d_ag_of,
-                                                             d_scene, pl_frames if pl_ag.size else None, pl_first, pl_who,
-                                                             rk_clear if ranking is not None else None))
-        if ranking is not None:             # behind everything: the paths' terms, then the finished trajectories and each group's best
-            self._check(self.lib.pqp_select_paths_device(self._h, C.byref(rk_sel), B, cfg.n_max, 7, out, ints[0], ints[1], ints[2],
-                                                         first if footprint is not None else None, margin if footprint is not None else None,
-                                                         0, d_rk_start, rk_path_terms, rk_best, None, None))
-            if planning is not None:
-                rk_traj, rk_m_of = pl_traj, pl_m_of
-            else:
-                rk_traj, rk_m_of = rf_traj if refining is not None else se_traj, se_reached
-            self._check(self.lib.pqp_select_plans_device(self._h, rk_prm.array(), int(rk_prm.require_free), B, rk_rows, TRAJ_STRIDE, rk_traj, rk_m_of,
-                                                         rk_path_terms, se_flags, pl_first if rk_clear is not None else None, rk_clear, cfg.n_max, 7,
-                                                         out, ints[0], rk_groups, d_rk_start, rk_terms, rk_best, rk_best_traj, rk_best_m,
-                                                         rk_best_paths, rk_best_n))
+            build(d["layer"], d["dist"])
+        for s in c.stages:
+            s.launch(self, c, d)
         self.sync()
-        if smoother is not None:
-            smoother.sync()
-        host = lambda x: x.cpu().numpy()
-        everything = (selection is None or not selection[2]) and (ranking is None or not ranking[2])     # winners_only: out, free and margin stay on the device
-        res = dict(out=host(out)) if everything else {}
-        res.update(n_out=host(ints[0]), status=host(ints[1]), stage=host(ints[2]), iters=host(ints[3]))
-        if footprint is not None:
-            if everything:
-                res.update(free=host(free))
-            res.update(first_collision=host(first))
-            if everything:
-                res.update(margin=host(margin))
-        if selection is not None:
-            res.update(terms=host(terms), best=host(best), best_paths=host(best_paths), best_n=host(best_n))
-        every_row = ranking is None or not ranking[2]               # winners_only with rank: nor do the rows of every candidate's speed stages
-        if speed is not None:
-            if every_row:
-                res.update(profile=host(profile))
-            res.update(speed_flags=host(speed_flags))
-        if sampling is not None:
-            res.update(traj=host(traj), traj_n=host(traj_n), traj_flags=host(traj_flags))
-        if moving is not None and sampling is not None:
-            res.update(first_hit=host(first_hit), hit_agent=host(hit_agent), agent_clearance=host(agent_clearance))
-        if searching is not None:
-            res.update(search_steps=host(se_steps))
-            if every_row:
-                res.update(search_traj=host(se_traj))
-            res.update(search_cost=host(se_cost), search_reached=host(se_reached), search_flags=host(se_flags))
-        if refining is not None:
-            res.update(search_blocked=host(se_blocked))
-            if every_row:
-                res.update(refine_traj=host(rf_traj))
-            res.update(refine_bounds=host(rf_bounds), refine_cost=host(rf_cost), refine_excess=host(rf_excess), refine_status=host(rf_status),
-                       refine_flags=host(rf_flags))
-        if planning is not None:
-            if every_row:
-                res.update(plan_traj=host(pl_traj))
-            res.update(plan_m_of=host(pl_m_of), plan_defect=host(pl_defect), plan_excess=host(pl_excess), plan_flags=host(pl_flags))
-            if pl_ag is not None:
-                res.update(plan_first_hit=host(pl_first), plan_hit_agent=host(pl_who))
-        if predicting is not None:
-            res.update(predict_flags=host(pr_flags))
-            if pr_anchor is not None:
-                res.update(predict_anchor=host(pr_anchor))
-        if ranking is not None:
-            if rk_clear is not None and every_row:
-                res.update(plan_clearance=host(rk_clear))
-            res.update(terms=host(rk_path_terms), rank_terms=host(rk_terms), rank_best=host(rk_best), best_paths=host(rk_best_paths),
-                       best_n=host(rk_best_n), best_traj=host(rk_best_traj), best_m=host(rk_best_m))
-        return res
+        if c.args.smoother is not None:
+            c.args.smoother.sync()
+        return {key: d[key].cpu().numpy() for key, _, _ in c.result}
 
     def distance_layer(self, grid, geom):
         """pqp_distance_layer (host arrays): grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, in the orientation corridor_bounds takes
@@ -993,8 +1028,7 @@ class Handle:
         states = np.ascontiguousarray(states, dtype=np.float64)
         dist_cm = _column_major(dist, np.float32)
         B, n, stride = states.shape
-        no = None if n_of is None else np.ascontiguousarray(n_of, dtype=np.int32)
-        mo = None if map_of is None else np.ascontiguousarray(map_of, dtype=np.int32)
+        no, mo = _i32(n_of), _i32(map_of)
         car = car if car is not None else car_default_geometry(self.lib)
         free = np.zeros((B, n), dtype=np.uint8)
         first = np.zeros(B, dtype=np.int32)
@@ -1015,9 +1049,8 @@ class Handle:
         gs = np.ascontiguousarray(group_start, dtype=np.int32).ravel()
         _check_group_start(gs, B)
         groups = gs.size - 1
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        no, stt, stg, fc = i32(n_of), i32(status), i32(stage), i32(first_collision)
-        mg = None if margin is None else np.ascontiguousarray(margin, dtype=np.float64)
+        no, stt, stg, fc = _i32(n_of), _i32(status), _i32(stage), _i32(first_collision)
+        mg = _f64(margin)
         prm = prm if prm is not None else select_default_params(self.lib)
         terms = np.zeros((B, SCORE_STRIDE))
         best = np.zeros(groups, dtype=np.int32)
@@ -1033,12 +1066,8 @@ class Handle:
         PqpSpeedParams (None: the defaults).  Returns (profile [B][n][4] = s, v, a, t, flags [B] of SPEED_*)."""
         paths = np.ascontiguousarray(paths, dtype=np.float64)
         B, n, stride = paths.shape
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        no, sb, vl, vs, ve = i32(n_of), i32(stop_before), f64(v_limit), f64(v_start), f64(v_end)
-        for name, a, size in (("n_of", no, B), ("stop_before", sb, B), ("v_limit", vl, B * n), ("v_start", vs, B), ("v_end", ve, B)):
-            if a is not None and a.size != size:
-                raise ValueError(f"speed_profile: {name} must have {size} entries, not {a.size}")
+        no, sb, vl, vs, ve = _i32(n_of), _i32(stop_before), _f64(v_limit), _f64(v_start), _f64(v_end)
+        _check_sizes("speed_profile", ("n_of", no, B), ("stop_before", sb, B), ("v_limit", vl, B * n), ("v_start", vs, B), ("v_end", ve, B))
         prm = prm if prm is not None else speed_default_params(self.lib)
         profile = np.zeros((B, n, SPEED_STRIDE))
         flags = np.zeros(B, dtype=np.int32)
@@ -1051,17 +1080,10 @@ class Handle:
         as they are), profile [B][n][4] = s, v, a, t (speed_profile's), m samples per path at t0 + k dt, and optionally n_of [B], stop_before
         [B] (the two speed_profile got), t0 [B] (None: all 0); prm = PqpSampleParams (None: the defaults).  Returns (traj [B][m][8] = x, y,
         heading, k, s, v, a, t, m_of [B]: the samples on the path, flags [B] of TRAJ_*)."""
-        paths = np.ascontiguousarray(paths, dtype=np.float64)
-        B, n, stride = paths.shape
-        profile = np.ascontiguousarray(profile, dtype=np.float64)
-        if profile.shape != (B, n, SPEED_STRIDE):
-            raise ValueError(f"sample_trajectory: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        paths, profile, (B, n, stride) = _paths_with_profile("sample_trajectory", paths, profile)
         m = int(m)
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        no, sb, tt = i32(n_of), i32(stop_before), None if t0 is None else np.ascontiguousarray(t0, dtype=np.float64)
-        for name, a in (("n_of", no), ("stop_before", sb), ("t0", tt)):
-            if a is not None and a.size != B:
-                raise ValueError(f"sample_trajectory: {name} must have {B} entries, not {a.size}")
+        no, sb, tt = _i32(n_of), _i32(stop_before), _f64(t0)
+        _check_sizes("sample_trajectory", ("n_of", no, B), ("stop_before", sb, B), ("t0", tt, B))
         prm = prm if prm is not None else sample_default_params(self.lib)
         traj = np.zeros((B, max(m, 0), TRAJ_STRIDE))
         m_of = np.zeros(B, dtype=np.int32)
@@ -1082,11 +1104,8 @@ class Handle:
         if agents.ndim != 4 or agents.shape[2:] != (m, AGENT_STRIDE):
             raise ValueError(f"agents_check: agents must be [n_scenes][a_max][{m}][{AGENT_STRIDE}], not {agents.shape}")
         n_scenes, a_max = agents.shape[:2]
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        mo, ao, so = i32(m_of), i32(a_of), i32(scene_of)
-        for name, a, size in (("m_of", mo, B), ("a_of", ao, n_scenes), ("scene_of", so, B)):
-            if a is not None and a.size != size:
-                raise ValueError(f"agents_check: {name} must have {size} entries, not {a.size}")
+        mo, ao, so = _i32(m_of), _i32(a_of), _i32(scene_of)
+        _check_sizes("agents_check", ("m_of", mo, B), ("a_of", ao, n_scenes), ("scene_of", so, B))
         car = car if car is not None else car_default_geometry(self.lib)
         prm = prm if prm is not None else agents_default_params(self.lib)
         first = np.zeros(B, dtype=np.int32)
@@ -1110,11 +1129,8 @@ class Handle:
         if tracks.ndim != 3 or tracks.shape[2] != TRACK_STRIDE:
             raise ValueError(f"predict_agents: tracks must be [n_scenes][a_max][{TRACK_STRIDE}], not {tracks.shape}")
         n_scenes, a_max = tracks.shape[:2]
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        ao, lo = i32(a_of), i32(lane_of)
-        for name, a, size in (("a_of", ao, n_scenes), ("lane_of", lo, n_scenes * a_max)):
-            if a is not None and a.size != size:
-                raise ValueError(f"predict_agents: {name} must have {size} entries, not {a.size}")
+        ao, lo = _i32(a_of), _i32(lane_of)
+        _check_sizes("predict_agents", ("a_of", ao, n_scenes), ("lane_of", lo, n_scenes * a_max))
         n_lanes, lane_m, spl, ext, length = _lanes(lanes, "predict_agents")
         prm = prm if prm is not None else predict_default_params(self.lib)
         m, r = int(m), int(r)
@@ -1138,22 +1154,15 @@ class Handle:
         without agents, a_max = 0, m must be given), and optionally n_of [B], stop_before [B] (the two speed_profile got), a_of [n_scenes],
         scene_of [B] (None: scene 0); car = PqpCarGeometry (None: the reference's), prm = SearchParams (None: search_default_params()).
         Returns dict(steps [B][m][2] = j, q, traj [B][m][8], cost [B], reached [B], flags [B] of SEARCH_*[, blocked [B][m][W] int32])."""
-        paths = np.ascontiguousarray(paths, dtype=np.float64)
-        B, n, stride = paths.shape
-        profile = np.ascontiguousarray(profile, dtype=np.float64)
-        if profile.shape != (B, n, SPEED_STRIDE):
-            raise ValueError(f"speed_search: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        paths, profile, (B, n, stride) = _paths_with_profile("speed_search", paths, profile)
         agents = np.ascontiguousarray(agents, dtype=np.float64)
         if agents.ndim != 4 or agents.shape[3] != AGENT_STRIDE or (m is not None and agents.shape[2] != int(m)):
             raise ValueError(f"speed_search: agents must be [n_scenes][a_max][{'m' if m is None else int(m)}][{AGENT_STRIDE}], not {agents.shape}")
         m = agents.shape[2] if m is None else int(m)
         n_scenes, a_max = agents.shape[:2]
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        no, sb, ao, so = i32(n_of), i32(stop_before), i32(a_of), i32(scene_of)
+        no, sb, ao, so = _i32(n_of), _i32(stop_before), _i32(a_of), _i32(scene_of)
         vs = np.ascontiguousarray(v_start, dtype=np.float64)
-        for name, a, size in (("n_of", no, B), ("stop_before", sb, B), ("v_start", vs, B), ("a_of", ao, n_scenes), ("scene_of", so, B)):
-            if a is not None and a.size != size:
-                raise ValueError(f"speed_search: {name} must have {size} entries, not {a.size}")
+        _check_sizes("speed_search", ("n_of", no, B), ("stop_before", sb, B), ("v_start", vs, B), ("a_of", ao, n_scenes), ("scene_of", so, B))
         car = car if car is not None else car_default_geometry(self.lib)
         prm = prm if prm is not None else search_default_params(self.lib)
         rows = max(m, 0)
@@ -1176,25 +1185,18 @@ class Handle:
         blocked=True); grid = the search's SearchParams (None: search_default_params()), prm = RefineParams (None:
         refine_default_params()).  Returns dict(traj [B][m][8], bounds [B][m][3] = lo, hi, vcap, cost [B], excess [B], status [B], iters
         [B], flags [B] of REFINE_*)."""
-        paths = np.ascontiguousarray(paths, dtype=np.float64)
-        B, n, stride = paths.shape
-        profile = np.ascontiguousarray(profile, dtype=np.float64)
-        if profile.shape != (B, n, SPEED_STRIDE):
-            raise ValueError(f"speed_refine: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        paths, profile, (B, n, stride) = _paths_with_profile("speed_refine", paths, profile)
         grid = grid if grid is not None else search_default_params(self.lib)
         prm = prm if prm is not None else refine_default_params(self.lib)
         search_traj = np.ascontiguousarray(search_traj, dtype=np.float64)
         if search_traj.ndim != 3 or search_traj.shape[0] != B or search_traj.shape[2] != TRAJ_STRIDE:
             raise ValueError(f"speed_refine: search_traj must be [{B}][m][{TRAJ_STRIDE}], not {search_traj.shape}")
         m = search_traj.shape[1]
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        no, sb, blk, stp, rch = i32(n_of), i32(stop_before), i32(blocked), i32(steps), i32(reached)
+        no, sb, blk, stp, rch = _i32(n_of), _i32(stop_before), _i32(blocked), _i32(steps), _i32(reached)
         vs = np.ascontiguousarray(v_start, dtype=np.float64)
         words = (max(int(grid.stations), 0) + 31) // 32
-        for name, a, size in (("n_of", no, B), ("stop_before", sb, B), ("v_start", vs, B), ("blocked", blk, B * m * words), ("steps", stp, B * m * 2),
-                              ("reached", rch, B)):
-            if a is not None and a.size != size:
-                raise ValueError(f"speed_refine: {name} must have {size} entries, not {a.size}")
+        _check_sizes("speed_refine", ("n_of", no, B), ("stop_before", sb, B), ("v_start", vs, B), ("blocked", blk, B * m * words), ("steps", stp, B * m * 2),
+                     ("reached", rch, B))
         traj = np.zeros((B, m, TRAJ_STRIDE))
         bounds = np.zeros((B, m, 3))
         cost, excess = np.zeros(B), np.zeros(B)
@@ -1209,20 +1211,13 @@ class Handle:
         count_of [B]: the planned layers (the search's reached; None: m); refine_flags [B]: speed_refine's flags - a REFINED path is sampled
         under constant acceleration, every other path linearly (None: every path by `linear`).  Returns dict(traj [B][(m - 1) r + 1][8],
         m_of [B]: the samples on the plan, defect [B], excess [B], flags [B] of PLAN_*)."""
-        paths = np.ascontiguousarray(paths, dtype=np.float64)
-        B, n, stride = paths.shape
-        profile = np.ascontiguousarray(profile, dtype=np.float64)
-        if profile.shape != (B, n, SPEED_STRIDE):
-            raise ValueError(f"sample_plan: profile must be {(B, n, SPEED_STRIDE)}, not {profile.shape}")
+        paths, profile, (B, n, stride) = _paths_with_profile("sample_plan", paths, profile)
         plan = np.ascontiguousarray(plan, dtype=np.float64)
         if plan.ndim != 3 or plan.shape[0] != B or plan.shape[2] != TRAJ_STRIDE:
             raise ValueError(f"sample_plan: plan must be [{B}][m][{TRAJ_STRIDE}], not {plan.shape}")
         m, r = plan.shape[1], int(r)
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        no, sb, co, rfl = i32(n_of), i32(stop_before), i32(count_of), i32(refine_flags)
-        for name, a in (("n_of", no), ("stop_before", sb), ("count_of", co), ("refine_flags", rfl)):
-            if a is not None and a.size != B:
-                raise ValueError(f"sample_plan: {name} must have {B} entries, not {a.size}")
+        no, sb, co, rfl = _i32(n_of), _i32(stop_before), _i32(count_of), _i32(refine_flags)
+        _check_sizes("sample_plan", ("n_of", no, B), ("stop_before", sb, B), ("count_of", co, B), ("refine_flags", rfl, B))
         M = max(m - 1, 0) * max(r, 0) + 1
         if M > 2 ** 31 - 1:
             raise ValueError(f"sample_plan: (m - 1) r + 1 = {M} samples per path do not fit an int")
@@ -1247,18 +1242,14 @@ class Handle:
         gs = np.ascontiguousarray(group_start, dtype=np.int32).ravel()
         _check_group_start(gs, B)
         groups = gs.size - 1
-        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
-        mo, sf, fh, no, pt, cl, pa = i32(m_of), i32(search_flags), i32(first_hit), i32(n_of), f64(path_terms), f64(clearance), f64(paths)
+        mo, sf, fh, no, pt, cl, pa = _i32(m_of), _i32(search_flags), _i32(first_hit), _i32(n_of), _f64(path_terms), _f64(clearance), _f64(paths)
         if pa is not None and pa.ndim != 3:
             raise ValueError(f"select_plans: paths must be [B][n][path_stride], not {pa.shape}")
         n, path_stride = (0, 0) if pa is None else pa.shape[1:]
         if no is not None and pa is None:
             raise ValueError("select_plans: n_of needs paths")
-        for name, a, size in (("m_of", mo, B), ("search_flags", sf, B), ("first_hit", fh, B), ("n_of", no, B), ("path_terms", pt, B * SCORE_STRIDE),
-                              ("clearance", cl, B * m), ("paths", pa, B * n * path_stride)):
-            if a is not None and a.size != size:
-                raise ValueError(f"select_plans: {name} must have {size} entries, not {a.size}")
+        _check_sizes("select_plans", ("m_of", mo, B), ("search_flags", sf, B), ("first_hit", fh, B), ("n_of", no, B), ("path_terms", pt, B * SCORE_STRIDE),
+                     ("clearance", cl, B * m), ("paths", pa, B * n * path_stride))
         prm = prm if prm is not None else rank_default_params(self.lib)
         terms = np.zeros((B, PLAN_SCORE_STRIDE))
         best, best_m = np.zeros(groups, dtype=np.int32), np.zeros(groups, dtype=np.int32)
@@ -1556,3 +1547,8 @@ class Handle:
     def last_path_kernel(self):
         """pqp_last_path_kernel: 1 = lane-per-waypoint kernel, 2 = lane-per-QP kernel served the last solve (0: none yet)."""
         return int(self.lib.pqp_last_path_kernel(self._h))
+
+
+# optimize_path's arguments by name with the signature's defaults (None where it has none): what Handle._chain_plan takes
+_CHAIN_ARGS = {k: None if p.default is p.empty else p.default for k, p in inspect.signature(Handle.optimize_path).parameters.items()
+               if k not in ("self", "dist")}

@@ -170,6 +170,42 @@ def test_stages_are_the_reference_s_return_false_sites(hip_lib):
     h.close(); hs.close()
 
 
+def _wrapper_call(hip_lib, name, sc, handles=None):
+    """configuration `name` of chain_plan_cases through Handle.optimize_path at the cases' shapes: (the plan, the returned dict, the handles)"""
+    import chain_plan_cases as cases
+    import chain_util
+    on_grid, kw = cases.configs(hip_lib, sc["start"], sc["target"])[name]
+    assert not on_grid
+    h, hs = handles or chain_util.handles(cases.B, max_n=(cases.N_MAX, cases.N_MAX))
+    kw = dict(kw, map_of=sc["map_of"], smoother=hs, cfg=h.chain_config(**cases.CHAIN_CONFIG))
+    plan = h._chain_plan(points=sc["pts"], n_points=sc["n_pts"], start=sc["start"], target=sc["target"], geom=sc["geom"], **kw)
+    return plan, h.optimize_path(sc["pts"], sc["n_pts"], sc["start"], sc["target"], sc["dist"], sc["geom"], **kw), (h, hs)
+
+
+@pytest.mark.parametrize("name", ["d", "d_winners", "h", "j", "j_winners", "k"])
+def test_the_wrapper_returns_what_its_plan_says(hip_lib, name):
+    """the dict Handle.optimize_path returns has exactly the plan's keys, in its order, with its shapes and dtypes (the plan's own table
+    is pinned without a device in test_chain_plan.py)"""
+    plan, res, (h, hs) = _wrapper_call(hip_lib, name, scenarios(4))
+    h.close(); hs.close()
+    assert [(k, v.shape, str(v.dtype)) for k, v in res.items()] == plan.result
+    assert not set(plan.on_device) & set(res)
+
+
+def test_the_footprint_check_behind_the_chain_repeats_bit_for_bit(hip_lib):
+    """free, first_collision and margin of two calls on one pair of handles are the same bits, and those are Handle.footprint_check's on
+    the out / n_out the call returned.  (That their zero-fill stands before the call's one synchronize is Handle._chain's structure: the
+    fill is far shorter than the chain in front of the check, so no run can show where it stands.)"""
+    sc = scenarios(4)
+    _, first, handles = _wrapper_call(hip_lib, "b", sc)
+    _, again, (h, hs) = _wrapper_call(hip_lib, "b", sc, handles)
+    want = h.footprint_check(again["out"], again["n_out"], sc["dist"], sc["geom"], map_of=sc["map_of"], margin=True)
+    h.close(); hs.close()
+    for k in ("free", "first_collision", "margin"):
+        assert first[k].tobytes() == again[k].tobytes() == want[k].tobytes(), k
+        assert first[k].shape == want[k].shape and first[k].dtype == want[k].dtype, k
+
+
 def test_clearance_lookup_on_the_device(hip_lib):
     """pqp_clearance_device = Map::getObstacleDistance at the raw line's points (tension_smoother.cpp:168), against the restatement of
     grid_map's bilinear lookup in the corridor oracle; its output feeds pqp_smooth_tension."""
