@@ -1420,6 +1420,68 @@ int pqp_predict_agents(pqp_handle* h, const double* prm, double t0, double dt, i
                        const int32_t* a_of, const int32_t* lane_of, int n_lanes, int lane_m, const double* lane_spline,
                        const double* lane_ext, const double* lane_length, double* agents, double* anchor, int32_t* flags);
 
+/* ---- standing agents laid over the distance layers, one layer per scene ------------------------------------------------------------------
+ * The corridor bounds, the DP search, the path QP and pqp_footprint_check read one thing about obstacles: the float distance layer.  The
+ * stages around moving agents only ever change the speed along a path that was planned as if the agents were not there, so a parked car
+ * that intrudes into the lane stops every candidate behind it.  This lays a scene's standing agents over a base layer: the distance to a
+ * union of obstacle sets is the minimum of the distances to each, and a rounded oriented rectangle - the agent shape of pqp_agents_check -
+ * has a closed-form distance, so layer(scene) = min(base layer, distance to the scene's standing agents) in one streaming pass, and no
+ * distance transform is run again.  The scenes' layers then go where layers go (dist and map_of of pqp_optimize_path_device,
+ * pqp_corridor_bounds, pqp_footprint_check): the scenes become the maps.  Moving agents are not overlaid: they are the speed stages'.  The
+ * reference has no counterpart: it plans against one static map. */
+/* The one parameter travels by value, as pqp_agents_check's margin does: inflate, in m, finite and >= 0 - extra room around every agent.
+ * The corridor and the footprint check already add the car's circles and the safety margin.  pqp_overlay_default_params writes this
+ * library's choice of it, 0.0, to *inflate (pure host; NULL ignored). */
+void pqp_overlay_default_params(double* inflate);
+enum { PQP_OVERLAY_BAD = 1, PQP_OVERLAY_NONE = 2 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   dist [n_maps][cols][rows] float   the base layers, in the layout every reader of a layer takes
+ *   geom                              as for pqp_corridor_bounds; every field is read here, the cells' centres being needed
+ *   agents [n_scenes][a_max][PQP_AGENT_STRIDE]   a row per agent, x, y, heading, half_length, half_width, radius: pqp_agents_check's agents
+ *                                     with m = 1 and its readings - half_length < 0 or half_width < 0: absent, the rest of the row is not
+ *                                     read; a present row with a value that is not finite or with a negative radius is bad.  a_max = 0 is
+ *                                     allowed (agents and frames may then be NULL)
+ *   a_of [n_scenes] or NULL           agents per scene: A = clamp(a_of, 0, a_max); NULL: all a_max
+ *   base_of [n_scenes] or NULL        the base layer a scene starts from; the host form refuses values outside [0, n_maps), the device
+ *                                     form clamps them.  NULL: layer 0 when n_maps = 1, else scene s starts from layer s, which needs
+ *                                     n_scenes = n_maps
+ *   frames [n_scenes][a_max][PQP_AGENT_FRAME_STRIDE]   (_device form only) a workspace of the caller's, fully written by the first launch
+ * Outputs, fully overwritten:
+ *   dist_out [n_scenes][cols][rows] float   the scenes' layers.  dist_out = dist is allowed exactly when base_of is NULL and n_scenes =
+ *                                     n_maps: every cell is read and then written by the same lane, and nothing else of the layer is read
+ *   flags [n_scenes]                  PQP_OVERLAY_BAD, PQP_OVERLAY_NONE or 0
+ * Two launches on the handle's stream.  The first is pqp_agents_check's with one step per agent: every agent row becomes a frame row
+ * (ax, ay, c, s, hl, hw, radius, reach), bit for bit what pqp_agents_check makes of it.  The second is the overlay.  The definition, in
+ * fp64, every product and sum rounded on its own (no contraction), min and max as fmin and fmax, for cell (i, j) of scene s - index
+ * j * rows + i of its layer - and agent a < A:
+ *   cx = (pos_x + (0.5*length_x - 0.5*resolution)) + resolution * (double)(-i);  cy likewise with pos_y, length_y and j
+ *                                     (GridMap::getPosition, the expression the readers of a layer place their cells by)
+ *   dx = cx - ax;  dy = cy - ay;  u = dx*c + dy*s;  w = dy*c - dx*s
+ *   ex = fabs(u) - hl;  ey = fabs(w) - hw;  ox = fmax(ex, 0);  oy = fmax(ey, 0)
+ *   d = sqrt(ox*ox + oy*oy) + fmin(fmax(ex, ey), 0) - radius          (pqp_agents_check's d for one point, r_j = 0)
+ *   da = fmax(d - inflate, 0)
+ *   dmin = min over the scene's present agents of da, +inf when there is none
+ *   out = (dmin < (double)b) ? (float)dmin : b          b: the base value of the cell; (float) rounds to nearest
+ * A NaN base value therefore stays, and a cell the agents do not undercut is copied bit for bit.  A scene with a bad agent below its
+ * count gets 0.0f in every cell and PQP_OVERLAY_BAD: the conservative reading - pqp_agents_check lets a bad agent hit everything, and
+ * here the corridor is empty, so the chain reports the scenario blocked; the neighbouring scenes are untouched.  A scene with no present
+ * agent is a copy of its base layer and gets PQP_OVERLAY_NONE.  Every other scene gets 0.
+ * The overlay leaves out an agent that is too far from a tile of cells to undercut the largest base value in it (not where a base value
+ * of the tile is NaN); that changes no output while the squares of the coordinates are finite.  A result depends on the cell, the
+ * scene's rows, its base layer and inflate alone - not on the tiling, the position in the batch or which form was called; no atomics, the
+ * same answer every run.
+ * The _device form is asynchronous on the handle's stream and allocates nothing, so it can stand between pqp_distance_layer_device and
+ * pqp_optimize_path_device; rows, cols, a_max and n_scenes have no cap beyond those below.  The host form stages frames itself, copies
+ * in, runs, copies out and synchronises.  Both forms: PQP_ERR_INVALID, with nothing launched and the outputs untouched, for a null
+ * pointer that is not optional, n_maps < 1, n_scenes < 1, a_max < 0, a geometry pqp_distance_layer refuses or one whose lengths or
+ * position are not finite, an inflate that is not finite or is negative, n_scenes * rows * cols > 2^38, base_of = NULL with n_maps > 1
+ * and n_scenes != n_maps, or dist_out = dist in any other case than the one allowed above. */
+int pqp_overlay_agents_device(pqp_handle* h, double inflate, int n_maps, const pqp_grid_geometry* geom, const float* dist, int n_scenes,
+                              int a_max, const double* agents, const int32_t* a_of, const int32_t* base_of, double* frames, float* dist_out,
+                              int32_t* flags);
+int pqp_overlay_agents(pqp_handle* h, double inflate, int n_maps, const pqp_grid_geometry* geom, const float* dist, int n_scenes, int a_max,
+                       const double* agents, const int32_t* a_of, const int32_t* base_of, float* dist_out, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

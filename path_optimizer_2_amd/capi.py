@@ -294,6 +294,48 @@ def predict_default_params(lib=None, **over):
     return p
 
 
+class OverlayParams:
+    """what pqp_overlay_agents takes besides its arrays: inflate alone, which the C ABI therefore passes as a double and not in a struct
+    (AgentsParams' case)."""
+    __slots__ = ("inflate",)
+
+    def __init__(self, inflate):
+        self.inflate = float(inflate)
+
+
+def overlay_default_params(lib=None, **over):
+    """pqp_overlay_default_params: inflate 0 m (the corridor and the footprint check add the car's circles and the safety margin
+    themselves) - this library's choice - with `over` applied."""
+    lib = lib or load_library()
+    inflate = C.c_double(-1.0)
+    lib.pqp_overlay_default_params(C.byref(inflate))
+    p = OverlayParams(inflate.value)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
+def standing_rows(tracks, v_still=0.0):
+    """tracks [n_scenes][a_max][9] = x, y, heading, v, a, yaw_rate, half_length, half_width, radius (predict_agents' input) -> the rows
+    [n_scenes][a_max][6] = x, y, heading, half_length, half_width, radius that overlay_agents and parked= take: of a track that stands
+    (v <= v_still and a <= 0) the pose and the size, copied; of a present track with a value that is not finite a bad row (its pose NaN:
+    it must not vanish, the overlay then closes the scene); of every other track - absent, or moving: the speed stages' - the absent
+    row (0, 0, 0, -1, -1, 0).  Host numpy."""
+    tracks = np.asarray(tracks, dtype=np.float64)
+    if tracks.ndim != 3 or tracks.shape[2] != TRACK_STRIDE:
+        raise ValueError(f"standing_rows: tracks must be [n_scenes][a_max][{TRACK_STRIDE}], not {tracks.shape}")
+    absent = (tracks[..., 6] < 0.0) | (tracks[..., 7] < 0.0)
+    bad = ~absent & ~np.isfinite(tracks).all(axis=2)
+    with np.errstate(invalid="ignore"):
+        stands = ~absent & ~bad & (tracks[..., 3] <= float(v_still)) & (tracks[..., 4] <= 0.0)
+    rows = np.empty(tracks.shape[:2] + (AGENT_STRIDE,))
+    rows[...] = [0.0, 0.0, 0.0, -1.0, -1.0, 0.0]
+    rows[stands] = tracks[stands][:, [0, 1, 2, 6, 7, 8]]
+    rows[bad] = tracks[bad][:, [0, 1, 2, 6, 7, 8]]
+    rows[bad, :3] = np.nan
+    return rows
+
+
 class _PredictedAgents:
     """the shape of an agents array that a prediction fills on the device (optimize_path's tracks=): what the checks of agents= and
     plan_agents= read of a host array, without the array"""
@@ -481,6 +523,19 @@ def _agent_rows(c, d, rows="agents", frames="agent_frames"):
     return shape[0], shape[1], d[rows] if some else None, d["agents_of"], d["scene_of"], d[frames] if some else None
 
 
+def _stage_overlay(c):
+    """in front of the chain: the scenes' layers from the base layers (d["base"]: uploaded, or built from the grid) and the standing
+    agents.  Its scratch is named dist, so every later reader of d["dist"] - the chain, the footprint check - reads the scenes' layers"""
+    ag, base_of, inflate = c.parked
+    g, some = c.args.geom, ag.size > 0
+    launch = lambda h, c, d: h._check(h.lib.pqp_overlay_agents_device(
+        h._h, inflate, d["base"].shape[0], C.byref(g), d["base"], ag.shape[0], ag.shape[1], d["parked_agents"] if some else None, None,
+        d["parked_base_of"], d["parked_frames"] if some else None, d["dist"], d["parked_flags"]))
+    return _Stage((("parked_flags", (ag.shape[0],), _I, False),),
+                  (("dist", (ag.shape[0], g.cols, g.rows), "float32", "empty"), ("parked_frames", ag.shape[:2] + (AGENT_FRAME_STRIDE,), _F, "empty")),
+                  (("parked_agents", ag, _F), ("parked_base_of", base_of, _I)), launch)
+
+
 def _stage_chain(c):
     """pqp_optimize_path_device itself, in the same form"""
     a = c.args
@@ -629,13 +684,14 @@ def _stage_ranking(c):
 
 
 # (stage, the fields of the context it needs: the call has the step when none of them is None), in launch order; the result's keys come
-# in the same order, except that the prediction's stand behind the fine plan's
-_STAGES = ((_stage_chain, ()), (_stage_footprint, ("footprint",)), (_stage_selection, ("selection",)), (_stage_speed, ("speed",)),
+# in the same order, except that the prediction's stand behind the fine plan's and the overlay's behind everything else
+_STAGES = ((_stage_overlay, ("parked",)), (_stage_chain, ()), (_stage_footprint, ("footprint",)), (_stage_selection, ("selection",)), (_stage_speed, ("speed",)),
            (_stage_sampling, ("sampling",)), (_stage_predicting, ("moving",)), (_stage_agents, ("moving", "sampling")),
            (_stage_searching, ("searching",)), (_stage_refining, ("refining",)), (_stage_planning, ("planning",)),
            (_stage_plan_agents, ("plan_agents",)), (_stage_ranking, ("ranking",)))
-_RESULT_ORDER = [f for f, _ in _STAGES if f is not _stage_predicting]
+_RESULT_ORDER = [f for f, _ in _STAGES if f not in (_stage_predicting, _stage_overlay)]
 _RESULT_ORDER.insert(_RESULT_ORDER.index(_stage_ranking), _stage_predicting)
+_RESULT_ORDER.append(_stage_overlay)
 
 
 class Handle:
@@ -707,7 +763,7 @@ class Handle:
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
                       plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
-                      t0=None, tracks=None, layers=None, predict_anchor=False, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                      t0=None, tracks=None, layers=None, predict_anchor=False, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -757,7 +813,16 @@ class Handle:
         in place of both uploads: with r = 1 at the search's dt into the rows the search reads, and with plan_samples=r into the rows the
         fine check reads, so only the tracks cross to the device and the two agree at the layers.  agents_of / scene_of / agents_params
         apply as with agents=.  Adds predict_flags [n_scenes][a_max] of PREDICT_* (and predict_anchor [n_scenes][a_max][4] with
-        predict_anchor=True).  (tracks, layers and predict_anchor stand in front of rank: tests pin the last five names of the signature.)
+        predict_anchor=True).  (tracks, layers, predict_anchor and parked stand in front of rank: tests pin the last five names of the
+        signature.)
+        parked: (agents [n_scenes][a_max][6] = x, y, heading, half_length, half_width, radius of the scenes' standing agents (standing_rows
+        makes them from tracks), base_of [n_scenes] or None: the layer of `dist` a scene starts from (None: layer 0 of one, else layer s of
+        n_scenes), inflate in m or None: overlay_default_params()) - pqp_overlay_agents_device behind the layers' upload (or build) and in
+        front of the chain on the same stream: layer(scene) = min(base layer, distance to the scene's standing agents), and every later
+        reader of the layers - the chain, the footprint check, the second pass - reads those.  map_of then indexes scenes: it is refused
+        outside [0, n_scenes), and None means scene 0.  Adds parked_flags [n_scenes] of OVERLAY_*, behind every other key.  Moving agents are
+        not overlaid: they are the speed stages'.  A standing agent may be given both here and to the speed stages (agents= / tracks=): the
+        path then goes round it and the checks still see it.
         Every step behind the chain is one record of _STAGES above (its outputs, its uploads, its calls); _chain_plan checks the arguments and
         lays the call out from them without a device, _chain runs it."""
         a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
@@ -768,18 +833,19 @@ class Handle:
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
                               winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None,
                               scene_of=None, agents_params=None, sample=None, samples=None, t0=None, tracks=None, layers=None, predict_anchor=False,
-                              rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                              parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
         agents_params / search / refine / plan_samples / plan_agents / rank / rank_params / tracks / layers / predict_anchor: as for
-        optimize_path)."""
+        optimize_path; parked: as for optimize_path, over the layers built on the device, base_of indexing the grids.  Moving agents are not
+        overlaid; a standing agent may be given both to parked= and to the speed stages)."""
         a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
         del a["self"], a["grid"]
         plan = self._chain_plan(**a)
         grid = _occupancy(grid, "optimize_path_on_grid")
-        build = lambda d_grid, d_dist: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_dist))
+        build = lambda d_grid, d_base: self._check(self.lib.pqp_distance_layer_device(self._h, grid.shape[0], C.byref(geom), d_grid, d_base))
         return self._chain(plan, grid, np.uint8, build)
 
     def _tracks(self, tracks, layers, predict_anchor, search, agents, plan_agents, plan_samples):
@@ -924,6 +990,31 @@ class Handle:
             raise ValueError(f"scene_of must have one entry per {'candidate' if select is None else 'group'} ({rows})")
         return (agents, agents_of, scene_of, agents_params if agents_params is not None else agents_default_params(self.lib), car)
 
+    def _parked(self, parked, map_of, geom):
+        """parked= of optimize_path: (agents [n_scenes][a_max][6], base_of or None, inflate) checked, or None"""
+        if parked is None:
+            return None
+        if not isinstance(parked, (tuple, list)) or len(parked) != 3:
+            raise ValueError("parked must be (agents, base_of or None, inflate or None)")
+        agents, base_of, inflate = parked
+        agents = np.ascontiguousarray(agents, dtype=np.float64)
+        if agents.ndim != 3 or agents.shape[0] < 1 or agents.shape[2] != AGENT_STRIDE:
+            raise ValueError(f"parked: agents must be [n_scenes >= 1][a_max][{AGENT_STRIDE}], not {agents.shape}")
+        n_scenes = agents.shape[0]
+        if geom is None:
+            raise ValueError("parked needs geom: the scenes' layers have its cells")
+        base_of = None if base_of is None else np.ascontiguousarray(base_of, dtype=np.int32).ravel()
+        if base_of is not None and (base_of.size != n_scenes or (base_of < 0).any()):
+            raise ValueError(f"parked: base_of must have one entry >= 0 per scene ({n_scenes})")
+        inflate = overlay_default_params(self.lib).inflate if inflate is None else float(inflate)
+        if not (np.isfinite(inflate) and inflate >= 0.0):
+            raise ValueError(f"parked: inflate must be finite and >= 0, not {inflate}")
+        if map_of is not None:
+            map_of = np.asarray(map_of)
+            if ((map_of < 0) | (map_of >= n_scenes)).any():
+                raise ValueError(f"map_of outside [0, {n_scenes}): with parked it indexes the scenes")
+        return (agents, base_of, inflate)
+
     def _selection(self, select, select_params, winners_only):
         if select is None:
             if winners_only or select_params is not None:
@@ -937,6 +1028,7 @@ class Handle:
         argument check - the one place the validators above are called from - and then the context c that the stage records read:
           c.args, c.cfg, c.B, c.n_max    the arguments, the chain's configuration, the batch and the waypoints per path
           c.footprint .. c.predicting    each step's checked parameters (planning: r, plan_agents beside it), or None where the call has no such step
+          c.parked                       (standing agents' rows, base_of, inflate) of the overlay in front of the chain, or None
           c.car                          the footprint of the footprint check and of every check against agents
           c.groups, c.rows, c.paths      the rows of the speed stages - `groups` with select=, else B - and the buffers they run on as (paths,
                                          n_of, stop_before): the winners' best_paths / best_n and no stop, or out / n_out and first_collision
@@ -957,7 +1049,8 @@ class Handle:
             moving=self._agents(agents, a.agents_of, a.scene_of, a.agents_params, a.sample, a.samples, a.car, B, a.select, a.search),
             searching=self._search(a.search, a.speed, agents), refining=self._refine(a.refine, a.search),
             planning=self._plan(a.plan_samples, plan_agents, a.search, agents),
-            ranking=self._ranking(a.rank, a.rank_params, a.winners_only, a.search, a.select, B))
+            ranking=self._ranking(a.rank, a.rank_params, a.winners_only, a.search, a.select, B),
+            parked=self._parked(a.parked, a.map_of, a.geom))
         c.planning, c.plan_agents = c.planning or (None, None)         # r, and the agents' fine rows or their shape
         c.cfg = a.cfg or _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", {})
         c.n_max = c.cfg.n_max
@@ -992,7 +1085,15 @@ class Handle:
         dev = torch.device("cuda", self.device)
         t = lambda x, dt: None if x is None else torch.from_numpy(np.ascontiguousarray(x, dtype=dt)).to(dev)
         d = dict(layer=t(_column_major(maps, layer_dtype), layer_dtype))
-        d["dist"] = d["layer"] if build is None else torch.empty(d["layer"].shape, dtype=torch.float32, device=dev)
+        if c.parked is not None:            # what pqp_overlay_agents refuses and the plan, which has no maps, cannot see
+            n_maps, (ag, base_of, _) = d["layer"].shape[0], c.parked
+            if base_of is None and n_maps != 1 and n_maps != ag.shape[0]:
+                raise ValueError(f"parked: base_of=None needs one map or one per scene ({ag.shape[0]}), not {n_maps}")
+            if base_of is not None and (base_of >= n_maps).any():
+                raise ValueError(f"parked: base_of outside [0, {n_maps})")
+        # base: the layers as uploaded or built; dist: what the chain and the footprint check read - the same, or with parked= the
+        # scenes' layers, which the overlay's record lays out under that name
+        d["dist"] = d["base"] = d["layer"] if build is None else torch.empty(d["layer"].shape, dtype=torch.float32, device=dev)
         for s in c.stages:
             for name, x, dt in s.uploads:
                 d[name] = t(x, dt)
@@ -1002,7 +1103,7 @@ class Handle:
                 d[name] = (torch.empty if how else torch.zeros)(shape, dtype=getattr(torch, dtype), device=dev)
         torch.cuda.synchronize(dev)         # the one fence between torch's stream and the handle's: nothing is created after it
         if build is not None:
-            build(d["layer"], d["dist"])
+            build(d["layer"], d["base"])
         for s in c.stages:
             s.launch(self, c, d)
         self.sync()
@@ -1019,6 +1120,26 @@ class Handle:
         self._check(self.lib.pqp_distance_layer(self._h, cm.shape[0], C.byref(geom), cm, out))
         out = np.transpose(out, (0, 2, 1))
         return out[0] if two_d else out
+
+    def overlay_agents(self, dist, geom, agents, a_of=None, base_of=None, inflate=None):
+        """pqp_overlay_agents (host arrays): dist [n_maps][rows][cols] (or 2-D) float32, the base layers in distance_layer's orientation,
+        geom = PqpGridGeometry, agents [n_scenes][a_max][6] = x, y, heading, half_length, half_width, radius of the scenes' standing agents
+        (half_length or half_width < 0: absent), and optionally a_of [n_scenes] (agents per scene), base_of [n_scenes] (the layer a scene
+        starts from; None: layer 0 of one, else layer s of n_scenes), inflate in m (None: overlay_default_params()).  Returns (layers
+        [n_scenes][rows][cols] float32 = min(base layer, distance to the scene's agents), flags [n_scenes] of OVERLAY_*)."""
+        cm = _column_major(dist, np.float32)
+        agents = np.ascontiguousarray(agents, dtype=np.float64)
+        if agents.ndim != 3 or agents.shape[2] != AGENT_STRIDE:
+            raise ValueError(f"overlay_agents: agents must be [n_scenes][a_max][{AGENT_STRIDE}], not {agents.shape}")
+        n_scenes, a_max = agents.shape[:2]
+        ao, bo = _i32(a_of), _i32(base_of)
+        _check_sizes("overlay_agents", ("a_of", ao, n_scenes), ("base_of", bo, n_scenes))
+        inflate = overlay_default_params(self.lib).inflate if inflate is None else float(inflate)
+        out = np.empty((n_scenes,) + cm.shape[1:], dtype=np.float32)
+        flags = np.zeros(n_scenes, dtype=np.int32)
+        self._check(self.lib.pqp_overlay_agents(self._h, inflate, cm.shape[0], C.byref(geom), cm, n_scenes, a_max, agents if agents.size else None,
+                                                ao, bo, out, flags))
+        return np.transpose(out, (0, 2, 1)), flags
 
     def footprint_check(self, states, n_of, dist, geom, map_of=None, car=None, mode=FOOTPRINT_CIRCLES, margin=False):
         """pqp_footprint_check (host arrays): states [B][n][stride >= 3] (x, y, heading first; the chain's `out` as it is), n_of [B] or None,

@@ -12,7 +12,7 @@
 //   (agent_out_of_reach, whose slack is orders above the rounding of the exact test) and the agents behind its first hit, and the
 //   wavefront stops behind the tile of its first hit: none of that changes an output.
 // agent_clear, the reading of a frame row's reach, the broad phase and the scene's lookup are also st_occupancy_kernel's
-// (pqp_search_kernels.inc).
+// (pqp_search_kernels.inc); agent_frames_kernel, agent_point_distance and the slack are also overlay_kernel's (pqp_overlay_kernels.inc).
 
 namespace pqp {
 
@@ -61,6 +61,18 @@ __global__ void __launch_bounds__(kAgentsThreads) agent_frames_kernel(const Agen
     for (int q = 0; q < PQP_AGENT_FRAME_STRIDE; ++q) o[q] = f[q];
 }
 
+// d of include/pqp.h: the distance of the point (px, py) to the rounded rectangle of one frame row, negative inside it.  The one text of
+// it: agent_clear below takes it for the car's circles, overlay_kernel (pqp_overlay_kernels.inc) for a cell's centre
+__device__ __forceinline__ double agent_point_distance(double px, double py, double ax, double ay, double c, double sn, double hl, double hw,
+                                                       double radius) {
+#pragma clang fp contract(off)
+    const double dx = px - ax, dy = py - ay;
+    const double u = dx * c + dy * sn, w = dy * c - dx * sn;
+    const double ex = fabs(u) - hl, ey = fabs(w) - hw;
+    const double ox = fmax(ex, 0.0), oy = fmax(ey, 0.0);
+    return sqrt(ox * ox + oy * oy) + fmin(fmax(ex, ey), 0.0) - radius;
+}
+
 // clear(k, a) of include/pqp.h: the six circles at (gx, gy) with radii cr against the rounded rectangle of one frame row; the test of
 // agents_check_kernel and of st_occupancy_kernel (pqp_search_kernels.inc)
 __device__ __forceinline__ double agent_clear(const double (&gx)[6], const double (&gy)[6], const double* cr, double ax, double ay, double c,
@@ -68,14 +80,7 @@ __device__ __forceinline__ double agent_clear(const double (&gx)[6], const doubl
 #pragma clang fp contract(off)
     double c_ka = INFINITY;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const double dx = gx[j] - ax, dy = gy[j] - ay;
-        const double u = dx * c + dy * sn, w = dy * c - dx * sn;
-        const double ex = fabs(u) - hl, ey = fabs(w) - hw;
-        const double ox = fmax(ex, 0.0), oy = fmax(ey, 0.0);
-        const double d = sqrt(ox * ox + oy * oy) + fmin(fmax(ex, ey), 0.0) - radius;
-        c_ka = fmin(c_ka, d - cr[j]);
-    }
+    for (int j = 0; j < 6; ++j) c_ka = fmin(c_ka, agent_point_distance(gx[j], gy[j], ax, ay, c, sn, hl, hw, radius) - cr[j]);
     return c_ka;
 }
 

@@ -54,6 +54,13 @@ __device__ __forceinline__ double exact_div(double a, double b, double y) {
     return fma(fma(-b, q, a), y, q);
 }
 
+// GridMap::getPosition along one axis: the centre of the cell with index `index`, of a map centred at `pos` with extent `length`.  The one
+// text of it: obstacle_distance below and overlay_kernel (pqp_overlay_kernels.inc) place their cells by it.
+__device__ __forceinline__ double cell_centre(double pos, double length, double resolution, int index) {
+#pragma clang fp contract(off)
+    return (pos + (0.5 * length - 0.5 * resolution)) + resolution * (double)(-index);
+}
+
 // grid_map_core 1.6.x: isInside, getIndex, getPosition, atPositionLinearInterpolated, nearest fallback (restated from the
 // published sources; oracle/corridor_oracle.py carries the same restatement and the notes on its border behaviour)
 __device__ __forceinline__ double obstacle_distance(const float* __restrict__ dist, const pqp_grid_geometry& g, double px, double py) {
@@ -63,8 +70,7 @@ __device__ __forceinline__ double obstacle_distance(const float* __restrict__ di
     const double inv_res = 1.0 / g.resolution;           // (the same for every sample of the kernel: hoisted by the compiler)
     const int i0x = -(int)exact_div(px - 0.5 * g.length_x - g.pos_x, g.resolution, inv_res);
     const int i0y = -(int)exact_div(py - 0.5 * g.length_y - g.pos_y, g.resolution, inv_res);
-    const double ox = 0.5 * g.length_x - 0.5 * g.resolution, oy = 0.5 * g.length_y - 0.5 * g.resolution;
-    const double cx = (g.pos_x + ox) + g.resolution * (double)(-i0x), cy = (g.pos_y + oy) + g.resolution * (double)(-i0y);
+    const double cx = cell_centre(g.pos_x, g.length_x, g.resolution, i0x), cy = cell_centre(g.pos_y, g.length_y, g.resolution, i0y);
     const bool dirx = px >= cx, diry = py >= cy;
     const int i1x = dirx ? i0x - 1 : i0x + 1;          // indices[1] = (i1x, i0y), indices[2] = (i0x, i2y), indices[3] = (i1x, i2y)
     const int i2y = diry ? i0y - 1 : i0y + 1;
@@ -90,7 +96,7 @@ __device__ __forceinline__ double obstacle_distance(const float* __restrict__ di
 #pragma unroll
     for (int k = 0; k < 4; ++k) f[k] = dist[lin[k]];
     if (!ok) return (double)dist[i0y * g.rows + i0x];                // INTER_NEAREST fallback of GridMap::atPosition
-    const double qx = (g.pos_x + ox) + g.resolution * (double)(-ax), qy = (g.pos_y + oy) + g.resolution * (double)(-ay);
+    const double qx = cell_centre(g.pos_x, g.length_x, g.resolution, ax), qy = cell_centre(g.pos_y, g.length_y, g.resolution, ay);
     const double rx = exact_div(px - qx, g.resolution, inv_res), ry = exact_div(py - qy, g.resolution, inv_res);
     const double ux = 1.0 - rx, uy = 1.0 - ry;
     const double v = (double)f[0] * ux * uy + (double)f[1] * rx * uy + (double)f[2] * ux * ry + (double)f[3] * rx * ry;

@@ -1,7 +1,8 @@
 // pqp_maps.hip — the entry points of include/pqp.h around the obstacle distance map and the planned paths: the distance layer from an
 // occupancy grid (pqp_distance_kernels.inc), vehicle footprints against it (pqp_footprint_kernels.inc), scores of candidate paths and each
 // group's best (pqp_select_kernels.inc), speed profiles along them (pqp_speed_kernels.inc), samples of those trajectories on a time grid
-// (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc), those agents' rows from their tracks
+// (pqp_sample_kernels.inc), those samples against predicted moving agents (pqp_agents_kernels.inc), standing agents laid over the distance
+// layers (pqp_overlay_kernels.inc), those agents' rows from their tracks
 // (pqp_predict_kernels.inc), speeds that pass those agents in
 // the path-time plane (pqp_search_kernels.inc), the speed QP that makes such a plan drivable (pqp_refine_kernels.inc; its solve is the
 // banded core's, launched from pqp_smoothers.hip), those plans on a fine time step (pqp_plan_kernels.inc), scores of the finished
@@ -36,6 +37,7 @@ using namespace pqp_internal;
 #include "pqp_speed_kernels.inc"
 #include "pqp_sample_kernels.inc"
 #include "pqp_agents_kernels.inc"
+#include "pqp_overlay_kernels.inc"
 #include "pqp_predict_kernels.inc"
 #include "pqp_search_kernels.inc"
 #include "pqp_refine_kernels.inc"
@@ -507,6 +509,71 @@ int pqp_predict_agents(pqp_handle* h, const double* prm, double t0, double dt, i
     return st.run([&]() -> int {
         return pqp_predict_agents_device(h, prm, t0, dt, m, r, n_scenes, a_max, d_tracks, d_a_of, d_lane_of, n_lanes, lane_m, d_spl, d_ext, d_len,
                                          d_agents, d_anchor, d_flags);
+    });
+}
+
+// ---- standing agents laid over the distance layers, one layer per scene ---------------------------------------------------------------------
+void pqp_overlay_default_params(double* inflate) {
+    if (!inflate) return;
+    *inflate = 0.0;                 // the corridor and the footprint check add the car's circles and the safety margin themselves
+}
+
+static const char* const kOverlayRefusal =
+    "pqp_overlay_agents: bad argument (n_maps >= 1; n_scenes >= 1; a_max >= 0; a finite map geometry of 2 x 2 to 2^30 cells, resolution > 0; "
+    "n_scenes * rows * cols <= 2^38; inflate finite and >= 0; base_of = NULL needs n_maps = 1 or n_scenes = n_maps; dist_out = dist needs "
+    "base_of = NULL and n_scenes = n_maps)";
+
+static bool overlay_ok(pqp_handle* h, double inflate, int n_maps, const pqp_grid_geometry* geom, const float* dist, int n_scenes, int a_max,
+                       const double* agents, const int32_t* base_of, const float* dist_out, const int32_t* flags) {
+    if (!(h && dist && dist_out && flags && n_maps >= 1 && n_scenes >= 1 && a_max >= 0 && (agents || a_max == 0) && geometry_ok(geom))) return false;
+    if (!(std::isfinite(geom->resolution) && std::isfinite(geom->length_x) && std::isfinite(geom->length_y) && std::isfinite(geom->pos_x) &&
+          std::isfinite(geom->pos_y) && std::isfinite(inflate) && inflate >= 0.0))
+        return false;
+    if ((long long)n_scenes > (1ll << 38) / ((long long)geom->rows * geom->cols)) return false;
+    const bool own_layer = !base_of && n_scenes == n_maps;               // every scene reads the layer of its own index alone
+    if (!base_of && n_maps != 1 && !own_layer) return false;
+    return dist_out != dist || own_layer;
+}
+
+int pqp_overlay_agents_device(pqp_handle* h, double inflate, int n_maps, const pqp_grid_geometry* geom, const float* dist, int n_scenes,
+                              int a_max, const double* agents, const int32_t* a_of, const int32_t* base_of, double* frames, float* dist_out,
+                              int32_t* flags) {
+    if (!overlay_ok(h, inflate, n_maps, geom, dist, n_scenes, a_max, agents, base_of, dist_out, flags) || (!frames && a_max > 0))
+        return fail(PQP_ERR_INVALID, kOverlayRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::OverlayArgs a;
+    a.n_maps = n_maps; a.n_scenes = n_scenes; a.a_max = a_max; a.g = *geom; a.inflate = inflate; a.dist = dist; a.a_of = a_of;
+    a.base_of = base_of; a.frames = frames; a.out = dist_out; a.flags = flags;
+    a.tiles_i = ((unsigned)geom->rows + 63) / 64;
+    a.tiles_j = ((unsigned)geom->cols + pqp::kOverlayCols - 1) / pqp::kOverlayCols;
+    // (rows * cols < 2^30: at most 2^26 tiles of a scene; the scenes go over y and z, 65535 to a row)
+    a.scenes_y = (unsigned)std::min(n_scenes, 65535);
+    const unsigned per_block = pqp::kOverlayThreads / 64;
+    const dim3 grid((a.tiles_i * a.tiles_j + per_block - 1) / per_block, a.scenes_y, ((unsigned)n_scenes + a.scenes_y - 1) / a.scenes_y);
+    return h->launch_timed([&]() -> int {
+        if (const int rc = launch_agent_frames(h, n_scenes, a_max, 1, agents, frames)) return rc;
+        hipLaunchKernelGGL(pqp::overlay_kernel, grid, dim3(pqp::kOverlayThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_overlay_agents(pqp_handle* h, double inflate, int n_maps, const pqp_grid_geometry* geom, const float* dist, int n_scenes, int a_max,
+                       const double* agents, const int32_t* a_of, const int32_t* base_of, float* dist_out, int32_t* flags) {
+    if (!overlay_ok(h, inflate, n_maps, geom, dist, n_scenes, a_max, agents, base_of, dist_out, flags)) return fail(PQP_ERR_INVALID, kOverlayRefusal);
+    if (const int rc = index_range(base_of, n_scenes, n_maps, "pqp_overlay_agents: base_of outside [0, n_maps)")) return rc;
+    const size_t cells = (size_t)geom->rows * geom->cols, rows = (size_t)n_scenes * a_max;
+    Staging st(h);
+    // (dist_out = dist: the device form then runs on two arrays, and by the definition gives what it gives in place)
+    const float* d_dist = st.in(dist, (size_t)n_maps * cells);
+    const double* d_agents = rows ? st.in(agents, rows * PQP_AGENT_STRIDE) : nullptr;
+    const int32_t* d_a_of = st.in(a_of, n_scenes);
+    const int32_t* d_base_of = st.in(base_of, n_scenes);
+    double* d_frames = rows ? st.out((double*)nullptr, rows * PQP_AGENT_FRAME_STRIDE) : nullptr;
+    float* d_out = st.out(dist_out, (size_t)n_scenes * cells);
+    int32_t* d_flags = st.out(flags, n_scenes);
+    return st.run([&]() -> int {
+        return pqp_overlay_agents_device(h, inflate, n_maps, geom, d_dist, n_scenes, a_max, d_agents, d_a_of, d_base_of, d_frames, d_out, d_flags);
     });
 }
 
