@@ -1,6 +1,6 @@
-// pqp_agents_kernels.inc — included by pqp_maps.hip after pqp_sample_kernels.inc.  Sampled trajectories against predicted moving agents
+// pqp_agents_kernels.inc — instantiated by pqp_agents.hip; includes pqp_car_circles.hpp and pqp_agent_frames.hpp.  Sampled trajectories against predicted moving agents
 // (pqp_agents_check): every sample of every trajectory against every agent of the path's scene at the same time step, the six-circle
-// footprint (pqp_car_circles, placed by pqp_footprint_kernels.inc's local_to_global) against a rounded oriented rectangle.  The reference has
+// footprint (pqp_car_circles, placed by local_to_global) against a rounded oriented rectangle.  The reference has
 // no counterpart: it plans one path against a static map.  include/pqp.h states the definition operation by operation.
 //
 // agent_frames_kernel: one lane per (scene, agent, step).  The agent's sincos is taken here, once, so the batch x agents x steps tests
@@ -11,12 +11,14 @@
 //   the hit lane.  Without a clearance to write (CLEARANCE = false) a lane leaves out the agents it cannot come within the margin of
 //   (agent_out_of_reach, whose slack is orders above the rounding of the exact test) and the agents behind its first hit, and the
 //   wavefront stops behind the tile of its first hit: none of that changes an output.
-// agent_clear, the reading of a frame row's reach, the broad phase and the scene's lookup are also st_occupancy_kernel's
-// (pqp_search_kernels.inc); agent_frames_kernel, agent_point_distance and the slack are also overlay_kernel's (pqp_overlay_kernels.inc).
+// agent_frames_kernel also writes the frames of st_occupancy_kernel (pqp_search_kernels.inc) and of overlay_kernel (pqp_overlay_kernels.inc):
+// their units call launch_agent_frames (pqp_internal.hpp, defined in pqp_agents.hip), so the kernel exists in this unit alone.  What the
+// three share about a frame row - agent_clear, the reading of its reach, the broad phase, the scene's lookup - is pqp_agent_frames.hpp.
+
+#include "pqp_car_circles.hpp"
+#include "pqp_agent_frames.hpp"
 
 namespace pqp {
-
-constexpr int kAgentsThreads = 256;
 
 struct AgentsArgs {
     int batch, m, stride, n_scenes, a_max;
@@ -59,53 +61,6 @@ __global__ void __launch_bounds__(kAgentsThreads) agent_frames_kernel(const Agen
     }
 #pragma unroll
     for (int q = 0; q < PQP_AGENT_FRAME_STRIDE; ++q) o[q] = f[q];
-}
-
-// d of include/pqp.h: the distance of the point (px, py) to the rounded rectangle of one frame row, negative inside it.  The one text of
-// it: agent_clear below takes it for the car's circles, overlay_kernel (pqp_overlay_kernels.inc) for a cell's centre
-__device__ __forceinline__ double agent_point_distance(double px, double py, double ax, double ay, double c, double sn, double hl, double hw,
-                                                       double radius) {
-#pragma clang fp contract(off)
-    const double dx = px - ax, dy = py - ay;
-    const double u = dx * c + dy * sn, w = dy * c - dx * sn;
-    const double ex = fabs(u) - hl, ey = fabs(w) - hw;
-    const double ox = fmax(ex, 0.0), oy = fmax(ey, 0.0);
-    return sqrt(ox * ox + oy * oy) + fmin(fmax(ex, ey), 0.0) - radius;
-}
-
-// clear(k, a) of include/pqp.h: the six circles at (gx, gy) with radii cr against the rounded rectangle of one frame row; the test of
-// agents_check_kernel and of st_occupancy_kernel (pqp_search_kernels.inc)
-__device__ __forceinline__ double agent_clear(const double (&gx)[6], const double (&gy)[6], const double* cr, double ax, double ay, double c,
-                                              double sn, double hl, double hw, double radius) {
-#pragma clang fp contract(off)
-    double c_ka = INFINITY;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) c_ka = fmin(c_ka, agent_point_distance(gx[j], gy[j], ax, ay, c, sn, hl, hw, radius) - cr[j]);
-    return c_ka;
-}
-
-// a frame row's reach, as agent_frames_kernel wrote it: negative - the agent is absent; NaN - its row is bad; else the circumradius
-__device__ __forceinline__ bool agent_absent(double reach) { return reach < 0.0; }
-__device__ __forceinline__ bool agent_bad(double reach) { return !(reach == reach); }
-
-// the slack of the broad phase: 2^-10 m and 2^-30 of the coordinates' size, against a rounding of the exact test near 2^-50 of it
-constexpr double kAgentsSlack = 0x1p-10, kAgentsSlackRel = 0x1p-30;
-
-// the broad phase: the bounding circle's centre (bx, by) is so far from the agent's (ax, ay) that clear(k, a) >= margin + the slack.
-// Leaving such an agent out changes no hit.
-__device__ __forceinline__ bool agent_out_of_reach(double rb, double reach, double margin, double bx, double by, double ax, double ay) {
-#pragma clang fp contract(off)
-    const double ux = bx - ax, uy = by - ay;
-    const double far = rb + reach + margin + kAgentsSlack + kAgentsSlackRel * (fabs(bx) + fabs(by) + fabs(ax) + fabs(ay));
-    return ux * ux + uy * uy > far * far;
-}
-
-// the frames of path b's scene, and in *A how many of its a_max agents count; of an argument struct with scene_of, a_of and frames
-template <class Args>
-__device__ __forceinline__ const double* scene_frames(const Args& a, long long b, int* A) {
-    const int scene = a.scene_of ? min(max(a.scene_of[b], 0), a.n_scenes - 1) : 0;
-    *A = clamped_count(a.a_of, scene, a.a_max);
-    return a.frames + (size_t)scene * a.a_max * a.m * PQP_AGENT_FRAME_STRIDE;
 }
 
 template <bool CLEARANCE>

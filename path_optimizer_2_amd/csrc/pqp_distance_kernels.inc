@@ -1,4 +1,4 @@
-// pqp_distance_kernels.inc — included by pqp_maps.hip.  The obstacle distance layer from an occupancy grid (pqp_distance_layer):
+// pqp_distance_kernels.inc — instantiated by pqp_maps.hip; includes pqp_distance_layer.hpp.  The obstacle distance layer from an occupancy grid (pqp_distance_layer):
 //   cv::distanceTransform(obstacle, dist, CV_DIST_L2, CV_DIST_MASK_PRECISE); dist *= resolution     src/test/demo.cpp:104-113
 // Two launches on the handle's stream, the per-line routines of pqp_distance_layer.hpp:
 //   distance_lines_kernel      phase A: one wavefront per column line (rows contiguous bytes): one byte per lane and a ballot per block of

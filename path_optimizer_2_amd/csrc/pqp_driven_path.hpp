@@ -1,4 +1,5 @@
-// pqp_driven_path.hpp - what the kernels of pqp_maps.hip share about a solved path and its speed profile: how many of its waypoints are
+// pqp_driven_path.hpp - what the kernels of pqp_maps.hip, pqp_agents.hip, pqp_speed.hip and pqp_select.hip share about a solved path and
+// its speed profile, each .inc including it for itself: the count an optional array gives an item, how many of a path's waypoints are
 // driven, whether a driven row holds numbers, the walk along a monotone column of the profile and the pose on a chord between two
 // waypoints.  include/pqp.h states each of them once, operation by operation; this is the one place the kernels state them.  Device code
 // only.  Every function is forced inline, and those that compute keep fp contraction off: a fused multiply-add here breaks bit equality

@@ -1,34 +1,23 @@
-// pqp_footprint_kernels.inc — included by pqp_maps.hip.  Vehicle footprints of planned states against
-// the obstacle distance layer (pqp_footprint_check):
+// pqp_footprint_kernels.inc — instantiated by pqp_maps.hip; includes pqp_car_circles.hpp (the circles and their placement),
+// pqp_driven_path.hpp (clamped_count) and pqp_line_device.hpp (obstacle_distance).  Vehicle footprints of planned states against the
+// obstacle distance layer (pqp_footprint_check):
 //   CollisionChecker::isSingleStateCollisionFree          src/tools/collision_checker.cpp:17-39
 //   CollisionChecker::isSingleStateCollisionFreeImproved  src/tools/collision_checker.cpp:41-58
 //   CarGeometry::getCircles / getBoundingCircle           src/tools/car_geometry.cpp:59-72 (the circles themselves: pqp_car_circles, host)
-//   local2Global                                          src/tools/tools.cpp:50-55
+//   local2Global                                          src/tools/tools.cpp:50-55 (local_to_global of pqp_car_circles.hpp)
 //   Map::getObstacleDistance / isInside                   src/tools/Map.cpp:16-26   (obstacle_distance of pqp_corridor_kernels.inc)
 // One workgroup of 256 lanes per scenario, one state per lane, striding over the scenario's states.  A state takes one sincos and six
 // map samples; the six samples' 24 cell loads are independent of each other, so they are in flight together (the layer, <= a few MB,
 // sits in L2).  first_collision: one ballot per wavefront and stride step, then the least of the four wavefronts' indices through LDS -
 // no atomics, the same answer every run, any n.
 
+#include "pqp_car_circles.hpp"
+#include "pqp_driven_path.hpp"
+#include "pqp_line_device.hpp"
+
 namespace pqp {
 
 constexpr int kFootprintThreads = 256;
-
-// The car's circles as the kernels take them, filled by car_circles_of (pqp_maps.hip) from a pqp_car_geometry.  rb is the broad phase's
-// radius (pqp_agents_kernels.inc): the reference's own bounding circle (cr[6]) does not contain the corner circles, rb does.
-struct CarCircles {
-    double cx[7], cy[7], cr[7];      // vehicle frame: rr, rl, fr, fl, fm, rm, then the bounding circle (pqp_car_circles)
-    double rb;                       // max_j (|c_j - c_6| + r_j): the six circles lie within rb of the bounding circle's centre
-};
-
-struct Point2 { double x, y; };
-
-// local2Global(state, circle): x cos - y sin + ref.x, x sin + y cos + ref.y  (tools.cpp:51-52): one circle's centre (cx, cy) of the
-// vehicle frame at the pose (x, y) with its heading's sine and cosine
-__device__ __forceinline__ Point2 local_to_global(double cx, double cy, double sh, double ch, double x, double y) {
-#pragma clang fp contract(off)
-    return {cx * ch - cy * sh + x, cx * sh + cy * ch + y};
-}
 
 struct FootprintArgs {
     int batch, n, stride;

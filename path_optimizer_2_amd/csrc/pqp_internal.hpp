@@ -1,16 +1,19 @@
 // pqp_internal.hpp — host side only: what the translation units of libpqp_hip.so share behind the C ABI of include/pqp.h.  The handle, its
-// device buffers, launch timing and host staging, the error message of pqp_last_error, and the launch helpers that several kernel families use.
+// device buffers, launch timing and host staging, the error message of pqp_last_error, and the launch and checking helpers that several kernel families use.
 // Everything here lives in a namespace of hidden visibility: the library exports the entry points of pqp.h (and its kernels' host stubs), nothing of this.
 // The state behind it - the thread-local error message, the allocation generation, the cache of static_lds - is defined once, in pqp_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cmath>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/pqp.h"
+
+namespace pqp { struct CarCircles; }     // pqp_car_circles.hpp (device side)
 
 #ifndef PQP_HIDDEN
 #define PQP_HIDDEN __attribute__((visibility("hidden")))      // (also pqp_chain_ws.hpp, which stands alone)
@@ -233,7 +236,7 @@ struct pqp_handle {
         }
     } sm;
 
-    // pqp_speed_refine_device (pqp_maps.hip): the speed QPs' own group for the banded core, and the corridor [batch][m][3] its three
+    // pqp_speed_refine_device (pqp_speed.hip): the speed QPs' own group for the banded core, and the corridor [batch][m][3] its three
     // kernels share.  (no key: the chain runs none of it, and its structure is not the smoothers')
     struct PQP_HIDDEN Refine : pqp_internal::BandedGroup { DevBuf bounds; } rf;
 
@@ -380,6 +383,56 @@ int line_launch(pqp_handle* h, const void* fn, size_t lds, const char* who, size
 // a distance-map layer the kernels can index with 32 bits (obstacle_distance, pqp_line_device.hpp)
 inline bool geometry_ok(const pqp_grid_geometry* g) {
     return g && g->rows >= 2 && g->cols >= 2 && g->resolution > 0.0 && (long long)g->rows * g->cols < (1ll << 30);
+}
+
+// ---- what the entry points of the planning stages share (pqp_maps.hip, pqp_agents.hip, pqp_speed.hip, pqp_select.hip) -----------------
+// the grid of a kernel that gives every item a wavefront, threads / 64 of them to a workgroup
+inline dim3 wave_grid(long long items, int threads) {
+    const int per_block = threads / 64;
+    return dim3((unsigned)((items + per_block - 1) / per_block));
+}
+
+// an optional index array of a host form: every entry inside [0, count), or the refusal `what`
+inline int index_range(const int32_t* of, int batch, int count, const char* what) {
+    if (of)
+        for (int b = 0; b < batch; ++b)
+            if (of[b] < 0 || of[b] >= count) return fail(PQP_ERR_INVALID, what);
+    return PQP_OK;
+}
+
+inline bool car_ok(const pqp_car_geometry* c) {
+    return c && std::isfinite(c->width) && std::isfinite(c->rear_length) && std::isfinite(c->front_length);
+}
+// the car's circles as the kernels take them (pqp_car_circles.hpp); beside pqp_car_circles in pqp_maps.hip
+int car_circles_of(const pqp_car_geometry* car, pqp::CarCircles* c);
+
+// The predicted rows [n_scenes][a_max][steps >= 1] of a stage that tests against agents (the agent check, the overlay, the speed search)
+// or writes them (the prediction).  (the frames' launch is one block per 256 rows in x: 2^38 rows are 2^30 blocks, and 16 TiB of frames)
+inline bool agent_rows_ok(int n_scenes, int a_max, int steps, const double* agents) {
+    return n_scenes >= 1 && a_max >= 0 && (long long)n_scenes * a_max <= (1ll << 38) / steps && (agents || a_max == 0);
+}
+// agent_frames_kernel over every (scene, agent, step) row into `frames`, inside a launch_timed; the kernel and this are pqp_agents.hip's
+int launch_agent_frames(pqp_handle* h, int n_scenes, int a_max, int m, const double* agents, double* frames);
+// the device copies of those rows in a host form: the rows, the scenes' counts, the stage's own index array `of` [n_of] (scene_of, base_of)
+// and the frames scratch, in the pool order of all three stages; no rows: neither they nor the frames take a slot
+struct AgentArrays { const double* agents; const int32_t* a_of; const int32_t* of; double* frames; };
+inline AgentArrays stage_agents(Staging& st, int n_scenes, int a_max, int steps, const double* agents, const int32_t* a_of, const int32_t* of,
+                                size_t n_of) {
+    const size_t rows = (size_t)n_scenes * a_max * steps;
+    AgentArrays d;
+    d.agents = rows ? st.in(agents, rows * PQP_AGENT_STRIDE) : nullptr;
+    d.a_of = st.in(a_of, n_scenes);
+    d.of = st.in(of, n_of);
+    d.frames = rows ? st.out((double*)nullptr, rows * PQP_AGENT_FRAME_STRIDE) : nullptr;
+    return d;
+}
+
+// a selector's group_start [groups + 1] in its host form: from 0 to batch, ascending, or the refusal under the entry point's name `who`
+inline int group_start_ok(const char* who, const int32_t* group_start, int groups, int batch) {
+    if (group_start[0] != 0 || group_start[groups] != batch) return fail(PQP_ERR_INVALID, std::string(who) + ": group_start must run from 0 to batch");
+    for (int g = 0; g < groups; ++g)
+        if (group_start[g + 1] < group_start[g]) return fail(PQP_ERR_INVALID, std::string(who) + ": group_start must be ascending");
+    return PQP_OK;
 }
 
 }  // namespace pqp_internal

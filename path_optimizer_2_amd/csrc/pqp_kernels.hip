@@ -13,7 +13,9 @@
 //
 // The other kernel families, each with its kernels, launchers and entry points: pqp_smoothers.hip (the reference-line smoothing QPs),
 // pqp_lines.hip (line geometry: corridor bounds, reference states, spline fit, DP, projection), pqp_maps.hip (distance layer, footprints,
-// path selection), pqp_chain.hip (pqp_optimize_path_device).
+// standing agents over the layers), pqp_agents.hip (trajectories against predicted agents, the agents' prediction), pqp_speed.hip (speed
+// profile, trajectory samples, path-time search, speed refine, fine plan samples), pqp_select.hip (path selection, plan ranking),
+// pqp_chain.hip (pqp_optimize_path_device).
 //
 // No CPU fallback: every entry point needs a HIP device.
 #include <hip/hip_runtime.h>

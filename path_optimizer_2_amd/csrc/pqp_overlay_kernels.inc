@@ -1,9 +1,10 @@
-// pqp_overlay_kernels.inc — included by pqp_maps.hip after pqp_agents_kernels.inc.  Standing agents laid over the obstacle distance layers
+// pqp_overlay_kernels.inc — instantiated by pqp_maps.hip; includes pqp_agent_frames.hpp.  Standing agents laid over the obstacle distance layers
 // (pqp_overlay_agents): layer(scene) = min(base layer, distance to the scene's standing agents), so that every reader of a layer - the
 // corridor bounds, the DP search, the footprint check - goes round a parked agent as it goes round an obstacle.  The reference has no
 // counterpart: it plans against one static map.  include/pqp.h states the definition operation by operation.
 //
-// The frames are agent_frames_kernel's (pqp_agents_kernels.inc) with one step per agent: the sincos is taken once per agent.
+// The frames are agent_frames_kernel's (pqp_agents_kernels.inc, through launch_agent_frames) with one step per agent: the sincos is taken
+// once per agent.
 // overlay_kernel: one wavefront per tile of a scene's layer, four per workgroup: 64 consecutive i (the contiguous axis, a cell per lane per
 //   column) times kOverlayCols columns j.  Every global access of a wavefront is one contiguous 256 B line, the base layer in and the
 //   scene's layer out; the base layers are shared by many scenes and stay in L2.  The scene's frame rows are wave-uniform: the address is
@@ -12,6 +13,8 @@
 //   The broad phase: an agent whose rounded rectangle stays further from every cell centre of the tile than the tile's largest base value
 //   (overlay_out_of_reach, whose slack is orders above the rounding of the exact distance) cannot undercut a cell and is left out; a tile
 //   with a NaN base value takes no such shortcut.  None of that changes an output.
+
+#include "pqp_agent_frames.hpp"
 
 namespace pqp {
 

@@ -1,5 +1,6 @@
-// pqp_plan_kernels.inc — included by pqp_maps.hip after pqp_refine_kernels.inc.  Speed plans on a fine time step (pqp_sample_plan): the
-// m rows a second apart that pqp_speed_search or pqp_speed_refine wrote, put on r sub-steps per layer under the plan's own kinematics -
+// pqp_plan_kernels.inc — instantiated by pqp_speed.hip behind pqp_search_kernels.inc, whose st_count and st_pose it uses;
+// includes nothing of its own.  Speed plans on a fine time step (pqp_sample_plan): the m rows a second apart that pqp_speed_search
+// or pqp_speed_refine wrote, put on r sub-steps per layer under the plan's own kinematics -
 // constant acceleration for a refined path, a straight line in the path-time plane for a searched staircase - and placed on the path by
 // the walk the search and the refine share.  The rows are pqp_agents_check's input.  The reference has no counterpart.  include/pqp.h
 // states the definition operation by operation.

@@ -1,4 +1,4 @@
-// pqp_predict_kernels.inc — included by pqp_maps.hip after pqp_agents_kernels.inc.  Tracked agents to predicted rows (pqp_predict_agents):
+// pqp_predict_kernels.inc — instantiated by pqp_agents.hip; includes pqp_driven_path.hpp and pqp_line_device.hpp.  Tracked agents to predicted rows (pqp_predict_agents):
 // a pose, a speed, an acceleration, a yaw rate and a size per track become the [step][PQP_AGENT_STRIDE] rows pqp_agents_check,
 // pqp_speed_search and the fine check behind pqp_sample_plan read, on the layers' times (r = 1) or on r sub-steps per layer, under
 // pqp_sample_plan's time expression.  The reference has no counterpart: it plans against a static map.  include/pqp.h states the
@@ -13,6 +13,9 @@
 //      its pose - the closed CTRA form, or pqp_offsets_to_points' expression at (s0 + dir D, l0) - and writes its row of six doubles;
 //      a wavefront's 64 rows are one contiguous 3 KB.  The flags are ballots carried over the tiles; lane 0 writes them and the anchor.
 // A (scene, agent)'s result depends on its track, its lane and the parameters alone.
+
+#include "pqp_driven_path.hpp"
+#include "pqp_line_device.hpp"
 
 namespace pqp {
 

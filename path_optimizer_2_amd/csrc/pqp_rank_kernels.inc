@@ -1,5 +1,6 @@
-// pqp_rank_kernels.inc — included by pqp_maps.hip after pqp_plan_kernels.inc.  Scores of finished trajectories - a path and the speed plan
-// on it - and each group's best (pqp_select_plans): the last stage of the path-speed decoupled planner, behind pqp_speed_refine,
+// pqp_rank_kernels.inc — instantiated by pqp_select.hip behind pqp_select_kernels.inc, whose group_rows and group_least it uses;
+// includes nothing of its own.  Scores of finished trajectories - a path and the speed plan on it - and each group's best
+// (pqp_select_plans): the last stage of the path-speed decoupled planner, behind pqp_speed_refine,
 // pqp_sample_plan and the fine pqp_agents_check on the same stream.  The reference plans one path per call and has no time axis; it has
 // nothing to rank.  include/pqp.h states the definition operation by operation.
 // plan_score_kernel: one wavefront per candidate, four per workgroup, lanes striding over its samples; a wavefront's 64 rows are one

@@ -1,4 +1,5 @@
-// pqp_refine_kernels.inc — included by pqp_maps.hip after pqp_search_kernels.inc.  The jerk-limited speed QP behind the path-time search
+// pqp_refine_kernels.inc — instantiated by pqp_speed.hip behind pqp_search_kernels.inc, whose st_count, st_pose and st_judge it
+// uses; includes pqp_banded_qp.hpp (kRMax, the core's row length).  The jerk-limited speed QP behind the path-time search
 // (pqp_speed_refine): the corridor around the searched plan from the search's own occupancy bits, the assembly of the QP for the generic
 // banded core (pqp_banded_qp.hpp, launched from pqp_smoothers.hip between the second and the third kernel here), and the placement of the
 // refined stations back on the path.  The reference has no counterpart.  include/pqp.h states the definition operation by operation.
@@ -11,6 +12,8 @@
 //   rows, bounds +-1e30), which the core solves at x = 0 beside the real ones.
 // refine_finish_kernel: a lane per layer clamps s_k into its corridor, places it with the same walk, writes the row and the excess over the
 //   envelope at the placed pose; a kept path gets search_traj's rows.
+
+#include "pqp_banded_qp.hpp"
 
 namespace pqp {
 

@@ -1,4 +1,4 @@
-// pqp_sample_kernels.inc — included by pqp_maps.hip after pqp_speed_kernels.inc.  Time-stamped trajectories on a fixed time step
+// pqp_sample_kernels.inc — instantiated by pqp_speed.hip; includes pqp_driven_path.hpp.  Time-stamped trajectories on a fixed time step
 // (pqp_sample_trajectory): where the car is at t0 + k dt, from the waypoints in `paths` and their s, v, a, t in `profile`.  The kinematics
 // inside a segment are the speed profile's own - constant acceleration along the chord - so a sample is the closed form of them; the
 // reference has no counterpart (nothing fills State::v there).  include/pqp.h states the definition operation by operation.
@@ -11,6 +11,8 @@
 //      next sample tile starts at the tile the previous one ended in.  Then a lane gathers its segment's two rows - read a moment ago
 //      by step 1, so they come from this CU's cache or L2 - places itself on the chord (chord_pose) and writes its row of eight doubles.
 // A sample's operations depend on its path's driven rows, t0, dt and k alone.
+
+#include "pqp_driven_path.hpp"
 
 namespace pqp {
 

@@ -1,8 +1,8 @@
-// pqp_search_kernels.inc — included by pqp_maps.hip after pqp_agents_kernels.inc.  Speeds past predicted agents (pqp_speed_search): the
+// pqp_search_kernels.inc — instantiated by pqp_speed.hip; includes pqp_car_circles.hpp and pqp_agent_frames.hpp.  Speeds past predicted agents (pqp_speed_search): the
 // occupancy of every path's path-time plane, station against layer, by the footprint test of pqp_agents_check, and a layered dynamic
 // program through its free cells.  The reference has no counterpart.  include/pqp.h states the definition operation by operation.
 //
-// agent_frames_kernel (pqp_agents_kernels.inc) runs first, as it is.
+// agent_frames_kernel (pqp_agents_kernels.inc, through launch_agent_frames) runs first, as it is.
 // st_occupancy_kernel: one wavefront per (path, tile of 64 stations), four per workgroup, one station per lane, no LDS, no atomics.
 //   1  tiles of 64 waypoints: every value below the driven count is judged (row_not_finite of pqp_driven_path.hpp, and v_start), and the
 //      maximum of the s column is M_{c-1}
@@ -18,6 +18,9 @@
 //   last living layer and its cheapest state are then one reduction behind the loop (wave_max, and one LDS step across the wavefronts in
 //   a cost layer that is free by then), whatever the ping-pong has overwritten.  One lane walks back through the parents, then the
 //   wavefronts place the planned stations on the path as step 2 does and a lane per layer writes its traj row.
+
+#include "pqp_car_circles.hpp"
+#include "pqp_agent_frames.hpp"
 
 namespace pqp {
 

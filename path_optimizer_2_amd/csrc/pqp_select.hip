@@ -1,0 +1,172 @@
+// pqp_select.hip — the entry points of include/pqp.h that choose: scores of candidate paths and each group's best
+// (pqp_select_kernels.inc), scores of the finished trajectories and each group's best (pqp_rank_kernels.inc).  Their kernels, launchers
+// and entry points.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+#include "pqp_defaults.hpp"
+#include "pqp_internal.hpp"
+
+using namespace pqp_internal;
+
+#include "pqp_select_kernels.inc"
+#include "pqp_rank_kernels.inc"
+
+extern "C" {
+
+// ---- scores of candidate paths and each group's best ----------------------------------------------------------------------------------
+void pqp_select_default_params(pqp_select_params* p) {
+    if (!p) return;
+    pqp_params d;
+    pqp::default_params(&d);
+    p->weight_kappa = d.weight_kappa;          // base_solver.cpp:124
+    p->weight_dkappa = d.weight_dkappa;        // :125
+    p->weight_offset = 0.0;                    // :123: weight_l is 0
+    p->weight_length = 0.0;
+    p->weight_clearance = 0.0;
+    p->clearance_want = d.expected_safety_margin;      // FLAGS_expected_safety_margin, planning_flags.cpp:95
+    p->per_waypoint = 0;
+    p->require_free = 1;
+}
+
+static bool select_ok(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, int groups,
+                      const int32_t* group_start, const double* terms, const int32_t* best, const double* best_paths, const int32_t* best_n) {
+    return h && prm && paths && group_start && terms && best && batch >= 1 && n >= 1 && n <= (1 << 30) && stride >= 7 && groups >= 0 &&
+           (best_paths != nullptr) == (best_n != nullptr);
+}
+
+int pqp_select_paths_device(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                            const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                            const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n) {
+    if (!select_ok(h, prm, batch, n, stride, paths, groups, group_start, terms, best, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, "pqp_select_paths: bad argument (stride >= 7; groups >= 0; best_paths and best_n both or neither)");
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::SelectArgs a;
+    a.batch = batch; a.n = n; a.stride = stride; a.groups = groups; a.paths = paths; a.n_of = n_of; a.status = status; a.stage = stage;
+    a.first_collision = first_collision; a.margin = margin; a.group_start = group_start; a.prm = *prm; a.terms = terms; a.best = best;
+    a.best_paths = best_paths; a.best_n = best_n;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::path_score_kernel, wave_grid(batch, pqp::kSelectThreads), dim3(pqp::kSelectThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        if (groups > 0) {
+            hipLaunchKernelGGL(pqp::group_select_kernel, wave_grid(groups, pqp::kSelectThreads), dim3(pqp::kSelectThreads), 0, h->stream, a);
+            PQP_HIP(hipGetLastError());
+        }
+        return PQP_OK;
+    });
+}
+
+int pqp_select_paths(pqp_handle* h, const pqp_select_params* prm, int batch, int n, int stride, const double* paths, const int32_t* n_of,
+                     const int32_t* status, const int32_t* stage, const int32_t* first_collision, const double* margin, int groups,
+                     const int32_t* group_start, double* terms, int32_t* best, double* best_paths, int32_t* best_n) {
+    if (!select_ok(h, prm, batch, n, stride, paths, groups, group_start, terms, best, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, "pqp_select_paths: bad argument (stride >= 7; groups >= 0; best_paths and best_n both or neither)");
+    for (const double v : {prm->weight_kappa, prm->weight_dkappa, prm->weight_offset, prm->weight_length, prm->weight_clearance, prm->clearance_want})
+        if (!std::isfinite(v)) return fail(PQP_ERR_INVALID, "pqp_select_paths: a parameter that is not finite");
+    if (const int rc = group_start_ok("pqp_select_paths", group_start, groups, batch)) return rc;
+    // (from here on groups >= 1: group_start runs from 0 to batch >= 1)
+    const size_t bn = (size_t)batch * n;
+    Staging st(h);
+    const double* d_paths = st.in(paths, bn * stride);
+    const int32_t* d_n_of = st.in(n_of, batch);
+    const int32_t* d_status = st.in(status, batch);
+    const int32_t* d_stage = st.in(stage, batch);
+    const int32_t* d_first = st.in(first_collision, batch);
+    const double* d_margin = st.in(margin, bn);
+    const int32_t* d_start = st.in(group_start, (size_t)groups + 1);
+    double* d_terms = st.out(terms, (size_t)batch * PQP_SCORE_STRIDE);
+    int32_t* d_best = st.out(best, groups);
+    double* d_best_paths = best_paths ? st.out(best_paths, (size_t)groups * n * 7) : nullptr;
+    int32_t* d_best_n = best_n ? st.out(best_n, groups) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_select_paths_device(h, prm, batch, n, stride, d_paths, d_n_of, d_status, d_stage, d_first, d_margin, groups, d_start, d_terms,
+                                       d_best, d_best_paths, d_best_n);
+    });
+}
+
+// ---- scores of finished trajectories and each group's best ---------------------------------------------------------------------------------
+void pqp_rank_default_params(double* prm, int* require_free) {
+    if (prm) {
+        pqp_select_params sel;
+        pqp_select_default_params(&sel);
+        // this library's choice: the reference has no speed plan to weigh against its path
+        prm[PQP_RANK_W_PATH] = prm[PQP_RANK_W_PROGRESS] = prm[PQP_RANK_W_ACCEL] = prm[PQP_RANK_W_JUMP] = prm[PQP_RANK_W_LATERAL] = 1.0;
+        prm[PQP_RANK_W_CLEARANCE] = 0.0;
+        prm[PQP_RANK_CLEARANCE_WANT] = sel.clearance_want;
+    }
+    if (require_free) *require_free = 1;
+}
+
+static const char* const kRankRefusal =
+    "pqp_select_plans: bad argument (batch >= 1; m >= 1; stride >= 8; with paths n >= 1 and path_stride >= 7; groups >= 0; best_traj and best_m "
+    "both or neither; best_paths and best_n both or neither, and only with paths; every parameter finite; require_free 0 or 1)";
+
+static bool rank_ok(pqp_handle* h, const double* prm, int require_free, int batch, int m, int stride, const double* traj, int n, int path_stride,
+                    const double* paths, int groups, const int32_t* group_start, const double* terms, const int32_t* best, const double* best_traj,
+                    const int32_t* best_m, const double* best_paths, const int32_t* best_n) {
+    if (!(h && prm && traj && group_start && terms && best && batch >= 1 && m >= 1 && stride >= PQP_TRAJ_STRIDE && groups >= 0)) return false;
+    if (paths && !(n >= 1 && n <= (1 << 30) && path_stride >= 7)) return false;
+    if ((best_traj != nullptr) != (best_m != nullptr) || (best_paths != nullptr) != (best_n != nullptr) || (best_paths && !paths)) return false;
+    for (int k = 0; k < PQP_RANK_PARAMS; ++k)
+        if (!std::isfinite(prm[k])) return false;
+    return require_free == 0 || require_free == 1;
+}
+
+int pqp_select_plans_device(pqp_handle* h, const double* prm, int require_free, int batch, int m, int stride, const double* traj,
+                            const int32_t* m_of, const double* path_terms, const int32_t* search_flags, const int32_t* first_hit,
+                            const double* clearance, int n, int path_stride, const double* paths, const int32_t* n_of, int groups,
+                            const int32_t* group_start, double* terms, int32_t* best, double* best_traj, int32_t* best_m, double* best_paths,
+                            int32_t* best_n) {
+    if (!rank_ok(h, prm, require_free, batch, m, stride, traj, n, path_stride, paths, groups, group_start, terms, best, best_traj, best_m, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, kRankRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::RankArgs a;
+    a.batch = batch; a.m = m; a.stride = stride; a.n = n; a.path_stride = path_stride; a.groups = groups; a.require_free = require_free;
+    a.traj = traj; a.m_of = m_of; a.path_terms = path_terms; a.search_flags = search_flags; a.first_hit = first_hit; a.clearance = clearance;
+    a.paths = paths; a.n_of = n_of; a.group_start = group_start;
+    for (int k = 0; k < PQP_RANK_PARAMS; ++k) a.prm[k] = prm[k];
+    a.terms = terms; a.best = best; a.best_traj = best_traj; a.best_m = best_m; a.best_paths = best_paths; a.best_n = best_n;
+    return h->launch_timed([&]() -> int {
+        hipLaunchKernelGGL(pqp::plan_score_kernel, wave_grid(batch, pqp::kRankThreads), dim3(pqp::kRankThreads), 0, h->stream, a);
+        PQP_HIP(hipGetLastError());
+        if (groups > 0) {
+            hipLaunchKernelGGL(pqp::plan_group_kernel, wave_grid(groups, pqp::kRankThreads), dim3(pqp::kRankThreads), 0, h->stream, a);
+            PQP_HIP(hipGetLastError());
+        }
+        return PQP_OK;
+    });
+}
+
+int pqp_select_plans(pqp_handle* h, const double* prm, int require_free, int batch, int m, int stride, const double* traj, const int32_t* m_of,
+                     const double* path_terms, const int32_t* search_flags, const int32_t* first_hit, const double* clearance, int n,
+                     int path_stride, const double* paths, const int32_t* n_of, int groups, const int32_t* group_start, double* terms,
+                     int32_t* best, double* best_traj, int32_t* best_m, double* best_paths, int32_t* best_n) {
+    if (!rank_ok(h, prm, require_free, batch, m, stride, traj, n, path_stride, paths, groups, group_start, terms, best, best_traj, best_m, best_paths, best_n))
+        return fail(PQP_ERR_INVALID, kRankRefusal);
+    if (const int rc = group_start_ok("pqp_select_plans", group_start, groups, batch)) return rc;
+    // (from here on groups >= 1: group_start runs from 0 to batch >= 1)
+    const size_t bm = (size_t)batch * m;
+    Staging st(h);
+    const double* d_traj = st.in(traj, bm * stride);
+    const int32_t* d_m_of = st.in(m_of, batch);
+    const double* d_path_terms = st.in(path_terms, (size_t)batch * PQP_SCORE_STRIDE);
+    const int32_t* d_sflags = st.in(search_flags, batch);
+    const int32_t* d_first = st.in(first_hit, batch);
+    const double* d_clear = st.in(clearance, bm);
+    const double* d_paths = paths ? st.in(paths, (size_t)batch * n * path_stride) : nullptr;
+    const int32_t* d_n_of = paths ? st.in(n_of, batch) : nullptr;
+    const int32_t* d_start = st.in(group_start, (size_t)groups + 1);
+    double* d_terms = st.out(terms, (size_t)batch * PQP_PLAN_SCORE_STRIDE);
+    int32_t* d_best = st.out(best, groups);
+    double* d_best_traj = best_traj ? st.out(best_traj, (size_t)groups * m * PQP_TRAJ_STRIDE) : nullptr;
+    int32_t* d_best_m = best_m ? st.out(best_m, groups) : nullptr;
+    double* d_best_paths = best_paths ? st.out(best_paths, (size_t)groups * n * 7) : nullptr;
+    int32_t* d_best_n = best_n ? st.out(best_n, groups) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_select_plans_device(h, prm, require_free, batch, m, stride, d_traj, d_m_of, d_path_terms, d_sflags, d_first, d_clear, n, path_stride,
+                                       d_paths, d_n_of, groups, d_start, d_terms, d_best, d_best_traj, d_best_m, d_best_paths, d_best_n);
+    });
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// pqp_select_kernels.inc — included by pqp_maps.hip after pqp_footprint_kernels.inc.  Scores of candidate paths and each group's best
+// pqp_select_kernels.inc — instantiated by pqp_select.hip; includes pqp_driven_path.hpp.  Scores of candidate paths and each group's best
 // (pqp_select_paths).  The reference plans one path per call and has nothing to rank; the default weights are the path QP's own
 //   weight_kappa 20, weight_dkappa 100, weight_l 0          src/solver/base_solver.cpp:123-147 (the diagonal of P)
 //   clearance_want 0.6                                       src/config/planning_flags.cpp:95 (FLAGS_expected_safety_margin)
@@ -8,6 +8,8 @@
 // the 64 partial sums meet in wave_sum, so the order of the additions depends on the candidate's count alone: the same candidate gives the
 // same bits wherever it stands in whatever batch.  group_select_kernel: one wavefront per group over the 64-byte records the first kernel
 // wrote; its reading of group_start and its choice of the winner are device functions that pqp_rank_kernels.inc uses too.  No atomics, no LDS.
+
+#include "pqp_driven_path.hpp"
 
 namespace pqp {
 

@@ -25,7 +25,7 @@ using namespace pqp_internal;
 #include "pqp_smoother_kernels.inc"
 
 // ---------------------------------------------------------------------------------------------------------
-// smoother QPs, and the speed refine's QP on the same core (pqp_maps.hip)
+// smoother QPs, and the speed refine's QP on the same core (pqp_speed.hip)
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 enum { SM_TENSION2 = kBandedTension2, SM_TENSION = kBandedTension, SM_POST = kBandedPost, SM_REFINE = kBandedRefine };

@@ -1,4 +1,4 @@
-// pqp_speed_kernels.inc — included by pqp_maps.hip after pqp_select_kernels.inc.  Planned paths to trajectories (pqp_speed_profile): arc
+// pqp_speed_kernels.inc — instantiated by pqp_speed.hip; includes pqp_driven_path.hpp.  Planned paths to trajectories (pqp_speed_profile): arc
 // length, speed, acceleration and time of every waypoint.  The reference's State carries s, v and a (include/data_struct/data_struct.hpp:14-26)
 // and nothing fills them; getOptimizedPath adds the chords up in tmp_s and drops the sum (src/solver/base_solver.cpp:268,282-284).
 //
@@ -17,6 +17,8 @@
 //   C  tiles ascending    the prefix sum of those times
 // A row is written by one lane in a sweep and read by another in the next, hence the workgroup fence between the sweeps.
 // The order of a path's additions depends on its driven count alone.
+
+#include "pqp_driven_path.hpp"
 
 namespace pqp {
 

@@ -8,7 +8,7 @@ import numpy as np
 
 AGENT_STRIDE, FRAME_STRIDE = 6, 8
 DEFAULTS = dict(margin=0.0)
-SLACK, SLACK_REL = 2.0 ** -10, 2.0 ** -30                    # the broad phase's (csrc/pqp_agents_kernels.inc)
+SLACK, SLACK_REL = 2.0 ** -10, 2.0 ** -30                    # the broad phase's (csrc/pqp_agent_frames.hpp)
 
 
 def frames(agents):

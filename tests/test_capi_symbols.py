@@ -66,6 +66,10 @@ def _refused_calls(lib):
         ("pqp_corridor_bounds", lambda: lib.pqp_corridor_bounds_device(None, 1, 1, 3, None, None, None, None, None, None, None, None, None, None)),       # pqp_lines.hip
         ("pqp_post_smooth", lambda: lib.pqp_post_smooth_device(None, 1, 4, None, None, None, None, None, None, None, None)),                              # pqp_smoothers.hip
         ("pqp_footprint_check", lambda: lib.pqp_footprint_check_device(None, 1, 1, 3, None, None, None, None, None, None, 0, None, None, None)),           # pqp_maps.hip
+        ("pqp_agents_check", lambda: lib.pqp_agents_check_device(None, 0.0, None, 1, 1, 3, None, None, 1, 0, None, None, None, None, None, None, None)),  # pqp_agents.hip
+        ("pqp_speed_profile", lambda: lib.pqp_speed_profile_device(None, None, 1, 1, 6, None, None, None, None, None, None, None, None)),                 # pqp_speed.hip
+        ("pqp_select_paths", lambda: lib.pqp_select_paths_device(None, None, 1, 1, 7, None, None, None, None, None, None, 0, None, None, None, None,
+                                                                  None)),                                                                                 # pqp_select.hip
         ("pqp_optimize_path", lambda: lib.pqp_optimize_path_device(None, None, None, 1, 4, None, None, None, None, None, None, None, None, None, None,
                                                                     None, None, None)),                                                                   # pqp_chain.hip
         ("pqp_path_sizes", lambda: lib.pqp_path_sizes(None, 1, None, C.byref(sizes))),                                                                   # pqp_kernels.hip

@@ -209,8 +209,8 @@ def main():
                 for n, s, e, c in rows[:a.regions]:
                     print(f"   +{s - base:#07x}..+{e - base:#07x} {fmt(c)}")
                 if a.lines:
-                    srcs = [os.path.join(ROOT, "path_optimizer_2_amd", "csrc", f) for f in ("pqp_path_lane.hpp", "pqp_path_solve.hip", "pqp_kernels.hip", "pqp_smoothers.hip", "pqp_lines.hip", "pqp_maps.hip", "pqp_chain.hip",
-                                                                                                    "pqp_line_device.hpp")]
+                    srcs = [os.path.join(ROOT, "path_optimizer_2_amd", "csrc", f) for f in ("pqp_path_lane.hpp", "pqp_path_solve.hip", "pqp_kernels.hip", "pqp_smoothers.hip", "pqp_lines.hip", "pqp_maps.hip", "pqp_agents.hip",
+                                                                                                    "pqp_speed.hip", "pqp_select.hip", "pqp_chain.hip", "pqp_line_device.hpp")]
                     tab = source_functions([s for s in srcs if os.path.exists(s)])
                     per = {}
                     for _, cls, _, _, loc in insns:
