@@ -1482,6 +1482,97 @@ int pqp_overlay_agents_device(pqp_handle* h, double inflate, int n_maps, const p
 int pqp_overlay_agents(pqp_handle* h, double inflate, int n_maps, const pqp_grid_geometry* geom, const float* dist, int n_scenes, int a_max,
                        const double* agents, const int32_t* a_of, const int32_t* base_of, float* dist_out, int32_t* flags);
 
+/* ---- the start of a cycle from the previous cycle's plan: trajectory stitching ------------------------------------------------------------
+ * Every stage from the tracks to pqp_select_plans plans one cycle, from a start, a start curvature and a start speed the caller gives.  A
+ * planner that starts every cycle from the measured pose feeds its own tracking error back into the plan: the path and the speed jump
+ * at every cycle.  The new plan therefore starts on the old one, a little ahead of the car; it starts from the measurement only when the
+ * car has left the plan, and the controller gets the piece of the old plan that bridges the gap.  This is that stage, in front of
+ * pqp_optimize_path_device as pqp_overlay_agents is: per group it reads the previous cycle's winner where pqp_select_plans left it
+ * (best_traj and best_m; pqp_sample_plan's and pqp_sample_trajectory's rows are the same rows), a measured state and the time since that
+ * plan began, and writes the state the new cycle plans from, the verdict and its reasons, the deviations, the re-based piece of the old
+ * plan that leads to the start, and that start spread over the group's candidates in the arrays the chain (start, start_k) and
+ * pqp_speed_profile (v_start) read.  Only the measurements cross to the device.  The reference has no counterpart: it plans one path per
+ * call from the state it is given. */
+/* The parameters are PQP_STITCH_PARAMS doubles, prm[PQP_STITCH_T_AHEAD] ... prm[PQP_STITCH_V_CAP], and two ints beside them, keep and
+ * prefix_max, by value as pqp_select_plans' are: no struct.  pqp_stitch_default_params (pure host; a NULL pointer is ignored) writes
+ * t_ahead 0.1 s (how far ahead of the measurement's time the new plan starts), lat_max 0.5 m, lon_max 2.5 m and dh_max 0.5 rad (the
+ * deviations beyond which the car has left the plan), v_still 0.1 m/s (at or below it a replanned start has curvature 0), v_cap +inf
+ * (the cap of the free model of pqp_predict_agents), and keep = 20 (the rows of the old plan kept behind the car). */
+#define PQP_STITCH_PARAMS 6
+enum { PQP_STITCH_T_AHEAD = 0, PQP_STITCH_LAT_MAX = 1, PQP_STITCH_LON_MAX = 2, PQP_STITCH_DH_MAX = 3, PQP_STITCH_V_STILL = 4, PQP_STITCH_V_CAP = 5 };
+void pqp_stitch_default_params(double* prm, int* keep);
+enum { PQP_STITCH_BAD = 1, PQP_STITCH_NO_PREVIOUS = 2, PQP_STITCH_TIME = 4, PQP_STITCH_BAD_PLAN = 8, PQP_STITCH_LATERAL = 16,
+       PQP_STITCH_LONGITUDINAL = 32, PQP_STITCH_HEADING = 64, PQP_STITCH_REPLAN = 128, PQP_STITCH_STITCHED = 256, PQP_STITCH_PREFIX_CUT = 512,
+       PQP_STITCH_STANDING = 1024 };
+/* Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   prev [groups][m][stride]            stride >= 8, the columns of PQP_TRAJ_STRIDE: x, y, heading, k, s, v, a, t.  Columns beyond 7 are not read
+ *   m_of [groups] or NULL               the rows of each plan, M = min(max(m_of, 0), m): pqp_select_plans' best_m.  NULL: m.  Rows at
+ *                                       f >= M are not read
+ *   meas [groups][6]                    x, y, heading, v >= 0, a, yaw rate w: the first six columns of a row of PQP_TRACK_STRIDE
+ *   t_now [groups]                      the time of the measurement in the previous plan's time base (its column t)
+ *   batch, group_start [groups + 1] or NULL   the candidates of group g are group_start[g] .. group_start[g + 1] - 1, read exactly as
+ *                                       pqp_select_paths reads them (every boundary clamped to [0, batch], a descending pair an empty
+ *                                       group); NULL: candidate g is group g's, and batch = groups
+ * The definition, in fp64, every product, quotient and sum rounded on its own (no contraction), for one group; x_f ... t_f are the
+ * columns of row f < M, (x, y, hd, v, a, w) the measurement, tq = t_now + t_ahead:
+ *   1  bad measurement   one of the six values or t_now is not finite, or v < 0: PQP_STITCH_BAD alone; the state row, dev and the prefix
+ *                        are zeros, idx is (-1, -1, -1), prefix_n = 0, and the group's candidates get the zero start.  Nothing else is
+ *                        evaluated: the flag tells the caller to ignore what the cycle makes of these candidates, and no NaN goes on
+ *   2  no previous plan  M < 2: PQP_STITCH_NO_PREVIOUS.  3 to 5 are not evaluated: idx is (-1, -1, -1), dev zeros
+ *   3  time match        i_now = the first f with t_f >= t_now;  i_start = the first f with t_f >= tq.  "First" is a plain scan from 0:
+ *                        ascending rows are not assumed, and a comparison with a NaN is false.  -1 where there is none.
+ *                        PQP_STITCH_TIME: t_now < t_0, or there is no i_start.  (t_ahead >= 0, so i_now <= i_start where both are)
+ *   4  position match    d2_f = (x - x_f) * (x - x_f) + (y - y_f) * (y - y_f), +inf where that is not finite;  p = the lowest f with the
+ *                        least d2_f, -1 when every d2_f is +inf.  PQP_STITCH_BAD_PLAN: p = -1, or one of the rows p, i_now, i_now - 1
+ *                        and i_start - those that exist - holds a value that is not finite among its eight columns
+ *   5  deviations        evaluated when PQP_STITCH_BAD_PLAN is not set and i_now exists, else dev is zeros and none of their three
+ *                        flags is set.  In the frame of row p:  sh, ch = sincos(heading_p);  dx = x - x_p;  dy = y - y_p;
+ *                          lat = -dx * sh + dy * ch                                            (global2Local's expression order)
+ *                          s_ref = s_0 when i_now = 0, else with i = i_now
+ *                                  s_{i-1} + (s_i - s_{i-1}) * ((t_now - t_{i-1}) / (t_i - t_{i-1}))  (t_{i-1} < t_now <= t_i: no division by 0)
+ *                          lon = s_ref - (s_p + (dx * ch + dy * sh))
+ *                          dh = constrainAngle(hd - heading_p)
+ *                        PQP_STITCH_LATERAL: not |lat| <= lat_max;  PQP_STITCH_LONGITUDINAL: not |lon| <= lon_max;  PQP_STITCH_HEADING:
+ *                        not |dh| <= dh_max - for numbers that is |.| > max, and a deviation that overflowed to NaN is flagged too
+ *   6  verdict           one of NO_PREVIOUS, TIME, BAD_PLAN, LATERAL, LONGITUDINAL, HEADING: PQP_STITCH_REPLAN, else
+ *                        PQP_STITCH_STITCHED.  Every reason that applies is set
+ *   7  stitched          the state row is row i_start, its eight columns bit for bit.  i0 = max(0, i_now - keep); when prefix is given
+ *                        and i_start - i0 + 1 > prefix_max: i0 = i_start - prefix_max + 1 and PQP_STITCH_PREFIX_CUT.
+ *                        prefix_n = i_start - i0 + 1;  prefix row j < prefix_n is row i0 + j with s - s_{i_start} in column 4 and
+ *                        t - t_{i_start} in column 7, every other column copied bit for bit: it ends at s = 0, t = 0
+ *   8  replanned         the measurement advanced by tau = t_ahead under pqp_predict_agents' free model, v_cap its cap: (te, ve) and
+ *                        whether the stop or the cap is reached by "the speed" there, tc = tau - te, (px, py, ph) by "free model".
+ *                        The state row is (px, py, ph, k, 0, ve, ae, tq) with k = w / ve when ve > v_still, else 0, and ae = a, or
+ *                        0 when the stop or the cap is reached (the acceleration no longer acts at tau).  PQP_STITCH_STANDING: ve = 0.
+ *                        prefix_n = 1, and the one prefix row is the state row with t = 0
+ *   9  candidates        for every candidate b of the group: start[b] = columns 0, 1, 2 of the state row, start_k[b] = column 3,
+ *                        v_start[b] = column 5
+ * Outputs, fully overwritten (start, start_k and v_start: at the candidates that are in a group):
+ *   state [groups][PQP_TRAJ_STRIDE]     the state the new cycle plans from.  Column 7 is the instant, in the old time base, at which the
+ *                                       new plan's t = 0 lies: the caller keeps its clock by it.  Column 6 is reported, no stage consumes it
+ *   flags [groups]                      PQP_STITCH_*
+ *   dev [groups][3]                     lon, lat, dh
+ *   idx [groups][3] int32               i_now, p, i_start
+ *   prefix [groups][prefix_max][PQP_TRAJ_STRIDE] or NULL   rows at and beyond prefix_n are zeros.  NULL: prefix_max is not read and nothing
+ *                                       is cut; prefix_n is still the count
+ *   prefix_n [groups]
+ *   start [batch][3], start_k [batch], v_start [batch]   each or NULL
+ * A group's result depends on its own inputs alone: the same bits at any position in any batch and from either form.  No atomics.  The
+ * _device form is one launch, asynchronous on the handle's stream, and allocates nothing, so it can stand in front of
+ * pqp_optimize_path_device with the previous call's best_traj as prev.  The host form copies in, runs, copies out and synchronises.
+ * Both forms: PQP_ERR_INVALID, with nothing launched and the outputs untouched, for a null pointer that is not optional (h, prm, prev,
+ * meas, t_now, state, flags, dev, idx, prefix_n), groups < 1, m < 1, stride < 8, batch < 0, keep < 0, prefix given with prefix_max < 1,
+ * a parameter that is negative or NaN, a t_ahead or v_still that is not finite, or group_start = NULL with one of start, start_k and
+ * v_start given and batch != groups.  The host form also refuses a group_start that is not ascending from 0 to batch. */
+int pqp_stitch_trajectory_device(pqp_handle* h, const double* prm, int keep, int prefix_max, int groups, int m, int stride, const double* prev,
+                                 const int32_t* m_of, const double* meas, const double* t_now, int batch, const int32_t* group_start,
+                                 double* state, int32_t* flags, double* dev, int32_t* idx, double* prefix, int32_t* prefix_n, double* start,
+                                 double* start_k, double* v_start);
+int pqp_stitch_trajectory(pqp_handle* h, const double* prm, int keep, int prefix_max, int groups, int m, int stride, const double* prev,
+                          const int32_t* m_of, const double* meas, const double* t_now, int batch, const int32_t* group_start, double* state,
+                          int32_t* flags, double* dev, int32_t* idx, double* prefix, int32_t* prefix_n, double* start, double* start_k,
+                          double* v_start);
+
 #ifdef __cplusplus
 }
 #endif

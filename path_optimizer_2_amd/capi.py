@@ -315,6 +315,38 @@ def overlay_default_params(lib=None, **over):
     return p
 
 
+class StitchParams:
+    """what pqp_stitch_trajectory takes besides its arrays: the STITCH_PARAMS doubles the C ABI passes as a plain array (t_ahead, lat_max,
+    lon_max, dh_max, v_still, v_cap, at STITCH_T_AHEAD .. STITCH_V_CAP) and keep beside them, under the names of the header's
+    enumerators.  stitch_default_params(lat_max=...) as for the other parameter sets."""
+    __slots__ = ("t_ahead", "lat_max", "lon_max", "dh_max", "v_still", "v_cap", "keep")
+    _INDEX = (("t_ahead", STITCH_T_AHEAD), ("lat_max", STITCH_LAT_MAX), ("lon_max", STITCH_LON_MAX), ("dh_max", STITCH_DH_MAX),
+              ("v_still", STITCH_V_STILL), ("v_cap", STITCH_V_CAP))
+
+    def __init__(self, values, keep):
+        for name, i in self._INDEX:
+            setattr(self, name, float(values[i]))
+        self.keep = int(keep)
+
+    def array(self):
+        out = np.zeros(STITCH_PARAMS)
+        for name, i in self._INDEX:
+            out[i] = getattr(self, name)
+        return out
+
+
+def stitch_default_params(lib=None, **over):
+    """pqp_stitch_default_params: t_ahead 0.1 s, lat_max 0.5 m, lon_max 2.5 m, dh_max 0.5 rad, v_still 0.1 m/s, v_cap +inf, keep 20 - this
+    library's choice - with `over` applied."""
+    lib = lib or load_library()
+    values, keep = np.full(STITCH_PARAMS, -1.0), C.c_int(-1)
+    lib.pqp_stitch_default_params(values, C.byref(keep))
+    p = StitchParams(values, keep.value)
+    for k, v in over.items():
+        setattr(p, k, v)
+    return p
+
+
 def standing_rows(tracks, v_still=0.0):
     """tracks [n_scenes][a_max][9] = x, y, heading, v, a, yaw_rate, half_length, half_width, radius (predict_agents' input) -> the rows
     [n_scenes][a_max][6] = x, y, heading, half_length, half_width, radius that overlay_agents and parked= take: of a track that stands
@@ -536,6 +568,29 @@ def _stage_overlay(c):
                   (("parked_agents", ag, _F), ("parked_base_of", base_of, _I)), launch)
 
 
+def _stage_stitch(c):
+    """in front of the chain, beside the overlay: the start of this cycle from the previous cycle's plan.  Its scratch is named start,
+    start_k and v_start, so the chain and the speed profile read what it wrote: start and start_k a row per candidate, v_start a row per
+    row of the speed stages - per candidate, or with select= per group, which a second launch over the groups alone writes (the
+    per-group column of the state row, contiguous as pqp_speed_profile takes it)"""
+    prev, prev_m, meas, t_now, prm, group_start = c.previous
+    G, m, stride = prev.shape
+    per_group = c.speed is not None and not c.per_candidate
+
+    def launch(h, c, d):
+        call = lambda batch, starts, start, start_k, v_start: h._check(h.lib.pqp_stitch_trajectory_device(
+            h._h, prm.array(), int(prm.keep), m, G, m, stride, d["stitch_prev"], d["stitch_prev_m"], d["stitch_meas"], d["stitch_t_now"], batch, starts,
+            d["stitch_state"], d["stitch_flags"], d["stitch_dev"], d["stitch_idx"], d["stitch_prefix"], d["stitch_prefix_n"], start, start_k, v_start))
+        call(c.B, d["stitch_group_start"], d["start"], d["start_k"], None if per_group else d.get("v_start"))
+        if per_group:
+            call(G, None, None, None, d["v_start"])
+    return _Stage((("stitch_state", (G, TRAJ_STRIDE), _F, False), ("stitch_flags", (G,), _I, False), ("stitch_dev", (G, 3), _F, False),
+                   ("stitch_prefix", (G, m, TRAJ_STRIDE), _F, False), ("stitch_prefix_n", (G,), _I, False)),
+                  (("stitch_idx", (G, 3), _I), ("start", (c.B, 3), _F), ("start_k", (c.B,), _F)) + ((("v_start", (c.rows,), _F),) if c.speed is not None else ()),
+                  (("stitch_prev", prev, _F), ("stitch_prev_m", prev_m, _I), ("stitch_meas", meas, _F), ("stitch_t_now", t_now, _F),
+                   ("stitch_group_start", group_start, _I)), launch)
+
+
 def _stage_chain(c):
     """pqp_optimize_path_device itself, in the same form"""
     a = c.args
@@ -684,14 +739,14 @@ def _stage_ranking(c):
 
 
 # (stage, the fields of the context it needs: the call has the step when none of them is None), in launch order; the result's keys come
-# in the same order, except that the prediction's stand behind the fine plan's and the overlay's behind everything else
-_STAGES = ((_stage_overlay, ("parked",)), (_stage_chain, ()), (_stage_footprint, ("footprint",)), (_stage_selection, ("selection",)), (_stage_speed, ("speed",)),
+# in the same order, except that the prediction's stand behind the fine plan's and the overlay's and the stitch's behind everything else
+_STAGES = ((_stage_overlay, ("parked",)), (_stage_stitch, ("previous",)), (_stage_chain, ()), (_stage_footprint, ("footprint",)), (_stage_selection, ("selection",)), (_stage_speed, ("speed",)),
            (_stage_sampling, ("sampling",)), (_stage_predicting, ("moving",)), (_stage_agents, ("moving", "sampling")),
            (_stage_searching, ("searching",)), (_stage_refining, ("refining",)), (_stage_planning, ("planning",)),
            (_stage_plan_agents, ("plan_agents",)), (_stage_ranking, ("ranking",)))
-_RESULT_ORDER = [f for f, _ in _STAGES if f not in (_stage_predicting, _stage_overlay)]
+_RESULT_ORDER = [f for f, _ in _STAGES if f not in (_stage_predicting, _stage_overlay, _stage_stitch)]
 _RESULT_ORDER.insert(_RESULT_ORDER.index(_stage_ranking), _stage_predicting)
-_RESULT_ORDER.append(_stage_overlay)
+_RESULT_ORDER += [_stage_overlay, _stage_stitch]
 
 
 class Handle:
@@ -763,7 +818,7 @@ class Handle:
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
                       plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
-                      t0=None, tracks=None, layers=None, predict_anchor=False, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                      t0=None, tracks=None, layers=None, predict_anchor=False, previous=None, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -813,8 +868,8 @@ class Handle:
         in place of both uploads: with r = 1 at the search's dt into the rows the search reads, and with plan_samples=r into the rows the
         fine check reads, so only the tracks cross to the device and the two agree at the layers.  agents_of / scene_of / agents_params
         apply as with agents=.  Adds predict_flags [n_scenes][a_max] of PREDICT_* (and predict_anchor [n_scenes][a_max][4] with
-        predict_anchor=True).  (tracks, layers, predict_anchor and parked stand in front of rank: tests pin the last five names of the
-        signature.)
+        predict_anchor=True).  (tracks, layers, predict_anchor, previous and parked stand in front of rank: tests pin the last five names
+        of the signature, and parked in front of them.)
         parked: (agents [n_scenes][a_max][6] = x, y, heading, half_length, half_width, radius of the scenes' standing agents (standing_rows
         makes them from tracks), base_of [n_scenes] or None: the layer of `dist` a scene starts from (None: layer 0 of one, else layer s of
         n_scenes), inflate in m or None: overlay_default_params()) - pqp_overlay_agents_device behind the layers' upload (or build) and in
@@ -823,6 +878,15 @@ class Handle:
         outside [0, n_scenes), and None means scene 0.  Adds parked_flags [n_scenes] of OVERLAY_*, behind every other key.  Moving agents are
         not overlaid: they are the speed stages'.  A standing agent may be given both here and to the speed stages (agents= / tracks=): the
         path then goes round it and the checks still see it.
+        previous: (prev [groups][m][stride >= 8], prev_m [groups] or None, meas [groups][6], t_now [groups], StitchParams or None:
+        stitch_default_params()) - pqp_stitch_trajectory_device in front of the chain on the same stream: the previous cycle's best_traj /
+        best_m (or any rows x, y, heading, k, s, v, a, t), the measured x, y, heading, v, a, yaw rate and its time in that plan's time base
+        give the start, start_k and v_start of this cycle's candidates, on the device.  The groups are rank='s or select='s, without either one
+        group per candidate; with select= and speed= the profile runs on the winners and v_start is written per group.  start (positional:
+        pass None), start_k and v_start must be None.  Adds stitch_state [groups][8] (column 7: where this cycle's t = 0 lies in the old
+        time base), stitch_flags [groups] of STITCH_*, stitch_dev [groups][3] = lon, lat, heading deviation, stitch_prefix [groups][m][8] (the
+        re-based piece of the old plan up to the start) and stitch_prefix_n, behind every other key.  A group flagged STITCH_BAD plans from
+        the zero start: its results are to be ignored.
         Every step behind the chain is one record of _STAGES above (its outputs, its uploads, its calls); _chain_plan checks the arguments and
         lays the call out from them without a device, _chain runs it."""
         a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
@@ -833,14 +897,14 @@ class Handle:
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
                               winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None,
                               scene_of=None, agents_params=None, sample=None, samples=None, t0=None, tracks=None, layers=None, predict_anchor=False,
-                              parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                              previous=None, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
         agents_params / search / refine / plan_samples / plan_agents / rank / rank_params / tracks / layers / predict_anchor: as for
         optimize_path; parked: as for optimize_path, over the layers built on the device, base_of indexing the grids.  Moving agents are not
-        overlaid; a standing agent may be given both to parked= and to the speed stages)."""
+        overlaid; a standing agent may be given both to parked= and to the speed stages; previous: as for optimize_path)."""
         a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
         del a["self"], a["grid"]
         plan = self._chain_plan(**a)
@@ -883,12 +947,12 @@ class Handle:
             fine = _PredictedAgents(tr.shape[:2] + ((layers - 1) * int(plan_samples) + 1, AGENT_STRIDE))
         return (tr, lane_of, lanes, prm, bool(predict_anchor)), _PredictedAgents(tr.shape[:2] + (layers, AGENT_STRIDE)), fine
 
-    def _speed(self, speed, v_start, v_end, check_footprint, select, select_params):
+    def _speed(self, speed, v_start, v_end, check_footprint, select, select_params, previous=None):
         if speed is None:
             if v_start is not None or v_end is not None:
                 raise ValueError("v_start / v_end need speed=PqpSpeedParams")
             return None
-        if v_start is None:
+        if v_start is None and previous is None:
             raise ValueError("speed needs v_start")
         if select is not None and check_footprint and select_params is not None and not select_params.require_free:
             raise ValueError("speed with select and check_footprint needs select_params.require_free: a winner's collision index is not at hand")
@@ -1015,6 +1079,32 @@ class Handle:
                 raise ValueError(f"map_of outside [0, {n_scenes}): with parked it indexes the scenes")
         return (agents, base_of, inflate)
 
+    def _previous(self, previous, start, start_k, v_start, batch, select, rank):
+        """previous= of optimize_path: (prev, prev_m or None, meas, t_now, StitchParams, group_start or None) checked, or None"""
+        if previous is None:
+            return None
+        if start is not None or start_k is not None or v_start is not None:
+            raise ValueError("previous is refused together with start, start_k or v_start: the stitch writes all three on the device")
+        if not isinstance(previous, (tuple, list)) or len(previous) != 5:
+            raise ValueError("previous must be (prev, prev_m or None, meas, t_now, StitchParams or None)")
+        prev, prev_m, meas, t_now, prm = previous
+        starts = rank if rank is not None else select
+        starts = None if starts is None else np.ascontiguousarray(starts, dtype=np.int32).ravel()
+        if starts is not None:
+            _check_group_start(starts, batch)
+        G, per = (batch, "candidate") if starts is None else (starts.size - 1, "group")
+        prev = np.ascontiguousarray(prev, dtype=np.float64)
+        if prev.ndim != 3 or prev.shape[0] != G or prev.shape[1] < 1 or prev.shape[2] < TRAJ_STRIDE:
+            raise ValueError(f"previous: prev must be [{G}][m >= 1][stride >= {TRAJ_STRIDE}], a plan per {per}, not {prev.shape}")
+        prev_m = None if prev_m is None else np.ascontiguousarray(prev_m, dtype=np.int32).ravel()
+        meas = np.ascontiguousarray(meas, dtype=np.float64)
+        t_now = np.ascontiguousarray(t_now, dtype=np.float64).ravel()
+        if (prev_m is not None and prev_m.size != G) or meas.shape != (G, 6) or t_now.size != G:
+            raise ValueError(f"previous: prev_m, meas and t_now must be [{G}], [{G}][6] and [{G}], one per {per}")
+        if prm is not None and not isinstance(prm, StitchParams):
+            raise ValueError("previous: the parameters must be a StitchParams")
+        return (prev, prev_m, meas, t_now, prm if prm is not None else stitch_default_params(self.lib), starts)
+
     def _selection(self, select, select_params, winners_only):
         if select is None:
             if winners_only or select_params is not None:
@@ -1029,6 +1119,7 @@ class Handle:
           c.args, c.cfg, c.B, c.n_max    the arguments, the chain's configuration, the batch and the waypoints per path
           c.footprint .. c.predicting    each step's checked parameters (planning: r, plan_agents beside it), or None where the call has no such step
           c.parked                       (standing agents' rows, base_of, inflate) of the overlay in front of the chain, or None
+          c.previous                     (prev, prev_m, meas, t_now, StitchParams, group_start or None) of the stitch in front of the chain, or None
           c.car                          the footprint of the footprint check and of every check against agents
           c.groups, c.rows, c.paths      the rows of the speed stages - `groups` with select=, else B - and the buffers they run on as (paths,
                                          n_of, stop_before): the winners' best_paths / best_n and no stop, or out / n_out and first_collision
@@ -1044,7 +1135,8 @@ class Handle:
         c = types.SimpleNamespace(
             args=a, B=B, predicting=predicting, footprint=int(a.footprint_mode) if a.check_footprint else None,
             selection=self._selection(a.select, a.select_params, a.winners_only and a.rank is None),
-            speed=self._speed(a.speed, a.v_start, a.v_end, a.check_footprint, a.select, a.select_params),
+            speed=self._speed(a.speed, a.v_start, a.v_end, a.check_footprint, a.select, a.select_params, a.previous),
+            previous=self._previous(a.previous, a.start, a.start_k, a.v_start, B, a.select, a.rank),
             sampling=self._sample(a.sample, a.samples, a.t0, a.speed),
             moving=self._agents(agents, a.agents_of, a.scene_of, a.agents_params, a.sample, a.samples, a.car, B, a.select, a.search),
             searching=self._search(a.search, a.speed, agents), refining=self._refine(a.refine, a.search),
@@ -1060,7 +1152,7 @@ class Handle:
         c.per_candidate = c.selection is None
         c.rows, per = (B, "candidate") if c.per_candidate else (c.groups, "group")
         c.paths = ("out", "n_out", None if c.footprint is None else "first_collision") if c.per_candidate else ("best_paths", "best_n", None)
-        if c.speed is not None and (c.speed[1].size != c.rows or (c.speed[2] is not None and c.speed[2].size != c.rows)):
+        if c.speed is not None and ((c.speed[1] is not None and c.speed[1].size != c.rows) or (c.speed[2] is not None and c.speed[2].size != c.rows)):
             raise ValueError(f"v_start / v_end must have one entry per {per} ({c.rows})")
         if c.sampling is not None and c.sampling[2] is not None and c.sampling[2].size != c.rows:
             raise ValueError(f"t0 must have one entry per {per} ({c.rows})")
@@ -1096,7 +1188,8 @@ class Handle:
         d["dist"] = d["base"] = d["layer"] if build is None else torch.empty(d["layer"].shape, dtype=torch.float32, device=dev)
         for s in c.stages:
             for name, x, dt in s.uploads:
-                d[name] = t(x, dt)
+                if x is not None or name not in d:          # nothing to upload: what an earlier stage laid out under that name stays
+                    d[name] = t(x, dt)
             for name, shape, dtype, _ in s.outputs:
                 d[name] = torch.zeros(shape, dtype=getattr(torch, dtype), device=dev)
             for name, shape, dtype, *how in s.scratch:
@@ -1382,6 +1475,38 @@ class Handle:
         res = dict(terms=terms, best=best, best_traj=best_traj, best_m=best_m)
         if pa is not None:
             res.update(best_paths=best_paths, best_n=best_n)
+        return res
+
+    def stitch_trajectory(self, prev, meas, t_now, m_of=None, group_start=None, batch=None, prm=None, prefix_max=None):
+        """pqp_stitch_trajectory (host arrays): prev [G][m][stride >= 8] = x, y, heading, k, s, v, a, t (select_plans' best_traj, sample_plan's
+        or sample_trajectory's rows as they are), meas [G][6] = x, y, heading, v, a, yaw rate, t_now [G] in the plan's time base, and
+        optionally m_of [G] (the rows of each plan: best_m), group_start [groups + 1] with batch (the candidates of each group; None: one
+        candidate per group), prm = StitchParams (None: stitch_default_params()), prefix_max (the rows of prefix; None: m).  Returns
+        dict(state [G][8], flags [G] of STITCH_*, dev [G][3] = lon, lat, dh, idx [G][3] = i_now, p, i_start, prefix [G][prefix_max][8],
+        prefix_n [G], start [batch][3], start_k [batch], v_start [batch])."""
+        prev = np.ascontiguousarray(prev, dtype=np.float64)
+        if prev.ndim != 3:
+            raise ValueError(f"stitch_trajectory: prev must be [G][m][stride], not {prev.shape}")
+        G, m, stride = prev.shape
+        meas, tn, mo = _f64(meas), _f64(t_now), _i32(m_of)
+        if meas.shape != (G, 6):
+            raise ValueError(f"stitch_trajectory: meas must be {(G, 6)}, not {meas.shape}")
+        _check_sizes("stitch_trajectory", ("t_now", tn, G), ("m_of", mo, G))
+        gs = None
+        if group_start is not None:
+            gs = np.ascontiguousarray(group_start, dtype=np.int32).ravel()
+            if batch is None or gs.size != G + 1:
+                raise ValueError(f"stitch_trajectory: group_start needs batch and {G + 1} entries")
+            _check_group_start(gs, int(batch))
+        batch = G if batch is None else int(batch)
+        prm = prm if prm is not None else stitch_default_params(self.lib)
+        prefix_max = m if prefix_max is None else int(prefix_max)
+        res = dict(state=np.zeros((G, TRAJ_STRIDE)), flags=np.zeros(G, dtype=np.int32), dev=np.zeros((G, 3)), idx=np.zeros((G, 3), dtype=np.int32),
+                   prefix=np.zeros((G, max(prefix_max, 0), TRAJ_STRIDE)), prefix_n=np.zeros(G, dtype=np.int32), start=np.zeros((batch, 3)),
+                   start_k=np.zeros(batch), v_start=np.zeros(batch))
+        self._check(self.lib.pqp_stitch_trajectory(self._h, prm.array(), int(prm.keep), prefix_max, G, m, stride, prev, mo, meas, tn, batch, gs,
+                                                   res["state"], res["flags"], res["dev"], res["idx"], res["prefix"], res["prefix_n"], res["start"],
+                                                   res["start_k"], res["v_start"]))
         return res
 
     def corridor_params(self, **over):

@@ -1,4 +1,4 @@
-// pqp_predict_kernels.inc — instantiated by pqp_agents.hip; includes pqp_driven_path.hpp and pqp_line_device.hpp.  Tracked agents to predicted rows (pqp_predict_agents):
+// pqp_predict_kernels.inc — instantiated by pqp_agents.hip; includes pqp_driven_path.hpp, pqp_free_motion.hpp (the four CTRA functions) and pqp_line_device.hpp.  Tracked agents to predicted rows (pqp_predict_agents):
 // a pose, a speed, an acceleration, a yaw rate and a size per track become the [step][PQP_AGENT_STRIDE] rows pqp_agents_check,
 // pqp_speed_search and the fine check behind pqp_sample_plan read, on the layers' times (r = 1) or on r sub-steps per layer, under
 // pqp_sample_plan's time expression.  The reference has no counterpart: it plans against a static map.  include/pqp.h states the
@@ -15,6 +15,7 @@
 // A (scene, agent)'s result depends on its track, its lane and the parameters alone.
 
 #include "pqp_driven_path.hpp"
+#include "pqp_free_motion.hpp"
 #include "pqp_line_device.hpp"
 
 namespace pqp {
@@ -23,7 +24,6 @@ constexpr int kPredictThreads = 256;
 constexpr long long kPredictMaxBlocks = 1ll << 22;      // beyond that many workgroups a wavefront takes several (scene, agent) slots in turn
 // a lane of 2^20 m and more is not projected on, as pqp_project_points refuses it: the coarse scan has floor(length) + 1 steps
 constexpr double kPredictMaxLength = 1048576.0;
-constexpr double kPredictSmallAngle = 0x1p-6;           // below it the four CTRA functions are their Taylor polynomials
 
 struct PredictArgs {
     int n_scenes, a_max, m, r, n_lanes, lane_m;
@@ -38,28 +38,6 @@ struct PredictArgs {
     double* anchor;                  // [n_scenes][a_max][PQP_ANCHOR_STRIDE] or nullptr
     int32_t* flags;                  // [n_scenes][a_max]
 };
-
-// sinc, cosc, f1, f2 of include/pqp.h at one angle: sin th / th, 2 sin^2(th / 2) / th, (th sin th - 2 sin^2(th / 2)) / th^2 and
-// (sin th - th cos th) / th^2, or their Taylor polynomials through th^5 below kPredictSmallAngle
-__device__ __forceinline__ void ctra_functions(double th, double& sinc, double& cosc, double& f1, double& f2) {
-#pragma clang fp contract(off)
-    const double t2 = th * th;
-    if (fabs(th) < kPredictSmallAngle) {
-        sinc = 1.0 - t2 * (1.0 / 6.0 - t2 * (1.0 / 120.0));
-        cosc = th * (0.5 - t2 * (1.0 / 24.0 - t2 * (1.0 / 720.0)));
-        f1 = 0.5 - t2 * (1.0 / 8.0 - t2 * (1.0 / 144.0));
-        f2 = th * (1.0 / 3.0 - t2 * (1.0 / 30.0 - t2 * (1.0 / 840.0)));
-    } else {
-        double sn, cs;
-        sincos(th, &sn, &cs);
-        const double sh = sin(0.5 * th);
-        const double hv = 2.0 * (sh * sh);
-        sinc = sn / th;
-        cosc = hv / th;
-        f1 = (th * sn - hv) / t2;
-        f2 = (sn - th * cs) / t2;
-    }
-}
 
 // one (scene, agent) slot, by a whole wavefront
 __device__ __forceinline__ void predict_slot(const PredictArgs& a, long long item, int lane) {

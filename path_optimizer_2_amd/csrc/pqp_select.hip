@@ -1,6 +1,6 @@
 // pqp_select.hip — the entry points of include/pqp.h that choose: scores of candidate paths and each group's best
-// (pqp_select_kernels.inc), scores of the finished trajectories and each group's best (pqp_rank_kernels.inc).  Their kernels, launchers
-// and entry points.
+// (pqp_select_kernels.inc), scores of the finished trajectories and each group's best (pqp_rank_kernels.inc), and the start of the next
+// cycle on the winner a cycle left (pqp_stitch_kernels.inc).  Their kernels, launchers and entry points.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -12,6 +12,7 @@ using namespace pqp_internal;
 
 #include "pqp_select_kernels.inc"
 #include "pqp_rank_kernels.inc"
+#include "pqp_stitch_kernels.inc"
 
 extern "C" {
 
@@ -166,6 +167,92 @@ int pqp_select_plans(pqp_handle* h, const double* prm, int require_free, int bat
     return st.run([&]() -> int {
         return pqp_select_plans_device(h, prm, require_free, batch, m, stride, d_traj, d_m_of, d_path_terms, d_sflags, d_first, d_clear, n, path_stride,
                                        d_paths, d_n_of, groups, d_start, d_terms, d_best, d_best_traj, d_best_m, d_best_paths, d_best_n);
+    });
+}
+
+// ---- the start of a cycle from the previous cycle's plan -------------------------------------------------------------------------------------
+void pqp_stitch_default_params(double* prm, int* keep) {
+    if (prm) {
+        // this library's choice: the reference plans from the state it is given
+        prm[PQP_STITCH_T_AHEAD] = 0.1;
+        prm[PQP_STITCH_LAT_MAX] = 0.5;
+        prm[PQP_STITCH_LON_MAX] = 2.5;
+        prm[PQP_STITCH_DH_MAX] = 0.5;
+        prm[PQP_STITCH_V_STILL] = 0.1;
+        prm[PQP_STITCH_V_CAP] = INFINITY;
+    }
+    if (keep) *keep = 20;
+}
+
+static const char* const kStitchRefusal =
+    "pqp_stitch_trajectory: bad argument (groups >= 1; m >= 1; stride >= 8; batch >= 0; keep >= 0; with prefix prefix_max >= 1; t_ahead and "
+    "v_still finite and >= 0; lat_max, lon_max, dh_max and v_cap >= 0; without group_start and with start, start_k or v_start batch = groups)";
+
+static bool stitch_ok(pqp_handle* h, const double* prm, int keep, int prefix_max, int groups, int m, int stride, const double* prev,
+                      const double* meas, const double* t_now, int batch, const int32_t* group_start, const double* state, const int32_t* flags,
+                      const double* dev, const int32_t* idx, const double* prefix, const int32_t* prefix_n, const double* start, const double* start_k,
+                      const double* v_start) {
+    if (!(h && prm && prev && meas && t_now && state && flags && dev && idx && prefix_n)) return false;
+    if (!(groups >= 1 && m >= 1 && stride >= PQP_TRAJ_STRIDE && batch >= 0 && keep >= 0 && (!prefix || prefix_max >= 1))) return false;
+    for (int k = 0; k < PQP_STITCH_PARAMS; ++k)
+        if (!(prm[k] >= 0.0)) return false;                                // (a NaN fails it too)
+    if (!(std::isfinite(prm[PQP_STITCH_T_AHEAD]) && std::isfinite(prm[PQP_STITCH_V_STILL]))) return false;
+    return group_start || !(start || start_k || v_start) || batch == groups;
+}
+
+int pqp_stitch_trajectory_device(pqp_handle* h, const double* prm, int keep, int prefix_max, int groups, int m, int stride, const double* prev,
+                                 const int32_t* m_of, const double* meas, const double* t_now, int batch, const int32_t* group_start,
+                                 double* state, int32_t* flags, double* dev, int32_t* idx, double* prefix, int32_t* prefix_n, double* start,
+                                 double* start_k, double* v_start) {
+    if (!stitch_ok(h, prm, keep, prefix_max, groups, m, stride, prev, meas, t_now, batch, group_start, state, flags, dev, idx, prefix, prefix_n, start,
+                   start_k, v_start))
+        return fail(PQP_ERR_INVALID, kStitchRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::StitchArgs a;
+    a.groups = groups; a.m = m; a.stride = stride; a.batch = batch; a.keep = keep; a.prefix_max = prefix ? prefix_max : 0;
+    a.t_ahead = prm[PQP_STITCH_T_AHEAD]; a.lat_max = prm[PQP_STITCH_LAT_MAX]; a.lon_max = prm[PQP_STITCH_LON_MAX]; a.dh_max = prm[PQP_STITCH_DH_MAX];
+    a.v_still = prm[PQP_STITCH_V_STILL]; a.v_cap = prm[PQP_STITCH_V_CAP];
+    a.prev = prev; a.m_of = m_of; a.meas = meas; a.t_now = t_now; a.group_start = group_start;
+    a.state = state; a.flags = flags; a.dev = dev; a.idx = idx; a.prefix = prefix; a.prefix_n = prefix_n; a.start = start; a.start_k = start_k;
+    a.v_start = v_start;
+    return h->launch_timed([&]() -> int {
+        const long long blocks = ((long long)groups + pqp::kStitchThreads / 64 - 1) / (pqp::kStitchThreads / 64);
+        hipLaunchKernelGGL(pqp::stitch_trajectory_kernel, dim3((unsigned)std::min(blocks, pqp::kStitchMaxBlocks)), dim3(pqp::kStitchThreads), 0,
+                           h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_stitch_trajectory(pqp_handle* h, const double* prm, int keep, int prefix_max, int groups, int m, int stride, const double* prev,
+                          const int32_t* m_of, const double* meas, const double* t_now, int batch, const int32_t* group_start, double* state,
+                          int32_t* flags, double* dev, int32_t* idx, double* prefix, int32_t* prefix_n, double* start, double* start_k,
+                          double* v_start) {
+    if (!stitch_ok(h, prm, keep, prefix_max, groups, m, stride, prev, meas, t_now, batch, group_start, state, flags, dev, idx, prefix, prefix_n, start,
+                   start_k, v_start))
+        return fail(PQP_ERR_INVALID, kStitchRefusal);
+    if (group_start)
+        if (const int rc = group_start_ok("pqp_stitch_trajectory", group_start, groups, batch)) return rc;
+    const size_t G = groups;
+    Staging st(h);
+    const double* d_prev = st.in(prev, G * m * stride);
+    const int32_t* d_m_of = st.in(m_of, G);
+    const double* d_meas = st.in(meas, G * 6);
+    const double* d_t_now = st.in(t_now, G);
+    const int32_t* d_start_of = st.in(group_start, G + 1);
+    double* d_state = st.out(state, G * PQP_TRAJ_STRIDE);
+    int32_t* d_flags = st.out(flags, G);
+    double* d_dev = st.out(dev, G * 3);
+    int32_t* d_idx = st.out(idx, G * 3);
+    double* d_prefix = prefix ? st.out(prefix, G * prefix_max * PQP_TRAJ_STRIDE) : nullptr;
+    int32_t* d_prefix_n = st.out(prefix_n, G);
+    // (every candidate is in one group here: group_start runs from 0 to batch, or there is none and batch = groups)
+    double* d_start = start && batch ? st.out(start, (size_t)batch * 3) : nullptr;
+    double* d_start_k = start_k && batch ? st.out(start_k, batch) : nullptr;
+    double* d_v_start = v_start && batch ? st.out(v_start, batch) : nullptr;
+    return st.run([&]() -> int {
+        return pqp_stitch_trajectory_device(h, prm, keep, prefix_max, groups, m, stride, d_prev, d_m_of, d_meas, d_t_now, batch, d_start_of, d_state,
+                                            d_flags, d_dev, d_idx, d_prefix, d_prefix_n, d_start, d_start_k, d_v_start);
     });
 }
 
