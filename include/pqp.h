@@ -1573,6 +1573,128 @@ int pqp_stitch_trajectory(pqp_handle* h, const double* prm, int keep, int prefix
                           int32_t* flags, double* dev, int32_t* idx, double* prefix, int32_t* prefix_n, double* start, double* start_k,
                           double* v_start);
 
+/* ---- a plan for every group: braking fallbacks where no candidate wins ---------------------------------------------------------------
+ * pqp_select_plans leaves a group none of whose candidates is eligible with best = -1, best_m = 0 and zero rows: a pedestrian stands in
+ * every candidate's lane for the whole horizon, every search ends PQP_SEARCH_NO_PLAN, or every path QP fails.  The controller then has
+ * nothing to track, and the next cycle's stitch reads best_m = 0 and replans from the raw measurement: the plan is lost in the cycle in
+ * which continuity matters most.  These two stages, behind pqp_select_plans on the same stream, close that hole: the car brakes along the
+ * plan it is already on - prev of pqp_stitch_trajectory, from the state that stitch chose - as gently as the agents and the distance
+ * layers allow.  pqp_fallback_rows writes one braking plan per group and braking level; pqp_agents_check_device (m_of = NULL: the car is
+ * checked while it stands too) and pqp_footprint_check_device (stride 8: x, y, heading lie where it reads them) test the groups *
+ * n_levels plans as the batch of trajectories they are, unchanged; pqp_fallback_pick keeps a group's winner where it has one and else
+ * takes the gentlest level that passed both.  Column 6 of the stitch's state row, the acceleration at the seam, is consumed here: the
+ * braking starts from it and leaves it at a bounded jerk.  The reference has no counterpart: its solve returns false and the caller has
+ * no path.
+ * What this does not do: it does not steer away (the place is on the old plan or on the arc, never beside them), it does not re-plan the
+ * path, it has no plan for a state flagged bad, and it has one jerk phase only: the release of the brake at the stop is a step, as in the
+ * free model's "standing once stopped". */
+/* The parameters: PQP_FALLBACK_PARAMS doubles (prm[PQP_FALLBACK_A_CAP], the cap on the acceleration the braking starts from) and the
+ * levels [n_levels][2], each row (d, j): a braking d > 0 in m/s^2 and a jerk j > 0 in m/s^3, d ascending (equal neighbours are allowed),
+ * 1 <= n_levels <= PQP_FALLBACK_MAX_LEVELS.  Both are host pointers in both forms, as prm is elsewhere; no struct.
+ * pqp_fallback_default_params (pure host; a NULL pointer is ignored; levels must hold PQP_FALLBACK_DEFAULT_LEVELS rows) writes this
+ * library's choice, around pqp_speed_default_params' d_max = 3.0 and a_max = 1.5:
+ *   level 0  d = 1.5 (d_max / 2), j = 2.5   comfortable: inside the 2 m/s^2 and 2.5 m/s^3 ISO 15622 lets an adaptive cruise control use at speed
+ *   level 1  d = 3.0 (d_max),     j = 5.0   what the speed stages plan with; 5 m/s^3 is ISO 15622's jerk bound at low speed
+ *   level 2  d = 6.0 (2 d_max),   j = 15.0  emergency: above the 5 m/s^2 UN Regulation 152 demands of an emergency braking system, below what dry
+ *                                           asphalt gives (8 to 10 m/s^2); the brake pressure of such a system builds up in a few tenths of a second
+ *   a_cap = a_max = 1.5: a seam acceleration above what the speed stages plan with is a bad number, not a state to continue */
+#define PQP_FALLBACK_PARAMS 1
+#define PQP_FALLBACK_MAX_LEVELS 8
+#define PQP_FALLBACK_DEFAULT_LEVELS 3
+enum { PQP_FALLBACK_A_CAP = 0 };
+void pqp_fallback_default_params(double* prm, double* levels, int* n_levels);
+enum { PQP_FALLBACK_BAD = 1, PQP_FALLBACK_ARC = 2, PQP_FALLBACK_BAD_PLAN = 4, PQP_FALLBACK_PATH_SHORT = 8, PQP_FALLBACK_HORIZON = 16,
+       PQP_FALLBACK_TAKEN = 32, PQP_FALLBACK_NOT_CLEAR = 64 };
+/* pqp_fallback_rows.  Inputs (device pointers for the _device form, host pointers for the other); every one marked "or NULL" is optional:
+ *   prev [groups][mp][stride] or NULL   the arrays pqp_stitch_trajectory reads: stride >= 8, columns 0 to 4 (x, y, heading, k, s) are read.
+ *                                       NULL: every group brakes on its arc; mp and stride are then not read, and prev_m must be NULL
+ *   prev_m [groups] or NULL             the rows of each plan, Mp = min(max(prev_m, 0), mp).  NULL: mp
+ *   state [groups][PQP_TRAJ_STRIDE]     the stitch's state row: x0, y0, h0, k0, the station s on prev, v0, the acceleration a.  Column 7 is
+ *                                       not read
+ *   stitch_flags [groups] or NULL       pqp_stitch_trajectory's flags.  NULL: every group counts as PQP_STITCH_STITCHED and none as bad
+ *   dt, r, m                            M = (m - 1) r + 1 rows per plan; row f lies at t_f = (double)(f / r) * dt + ((double)(f % r) * dt) / (double)r,
+ *                                       pqp_sample_plan's expression: the agents' rows on the plan's fine steps and these rows share their
+ *                                       instants bit for bit.  r = 1 gives the layers' steps
+ * The definition, in fp64, every product, quotient, sum and square root rounded on its own (no contraction), for one group and one level
+ * (d, j):
+ *   1  bad state         one of the state's columns 0 to 6 is not finite, v0 < 0, or stitch_flags has PQP_STITCH_BAD: PQP_FALLBACK_BAD alone;
+ *                        the rows and stop are zeros, stop_row = 0.  Nothing else is evaluated, and no NaN goes on
+ *   2  the law           a0 = min(max(a, -d), a_cap).  The acceleration falls from a0 at -j until it is -d, holds -d until the car stands,
+ *                        and is 0 from then on:
+ *                          t1 = (a0 + d) / j                                     (the end of the ramp; 0 when a0 = -d)
+ *                          ts = (a0 + sqrt(a0 * a0 + (2 * j) * v0)) / j          (where v0 + a0 t - j t^2 / 2 reaches 0)
+ *                          E(t) = (v0 + (0.5 * a0 - (j * t) / 6) * t) * t;   V(t) = v0 + (a0 - (0.5 * j) * t) * t
+ *                          v1 = max(V(t1), 0);   s1 = E(t1);   u1 = v1 / d
+ *                          ts <= t1 (the car comes to rest inside the ramp):  T = ts, eT = max(E(ts), 0)
+ *                          else:                                              T = t1 + u1, eT = max(s1 + (v1 - (0.5 * d) * u1) * u1, 0)
+ *                        Row f, at t = t_f:
+ *                          t >= T   at rest:   e = eT, v = 0, acc = 0
+ *                          t < t1   the ramp:  e = E(t), v = V(t), acc = a0 - j * t
+ *                          else     the hold:  u = t - t1;  e = s1 + (v1 - (0.5 * d) * u) * u;  v = v1 - d * u;  acc = -d
+ *                        then e = min(max(e, 0), eT) and v = max(v, 0).  Columns 4, 5, 6, 7 of the row are e, v, acc, t: the plan starts at
+ *                        s = 0, t = 0, where the stitch's prefix ends.  A car with v0 = 0 and a0 <= 0 has ts = 0 and stands from row 0
+ *   3  the place         on the arc - PQP_FALLBACK_ARC - when stitch_flags is given without PQP_STITCH_STITCHED or Mp < 2; else the rows
+ *                        below Mp are examined, and one whose columns 0 to 4 hold a value that is not finite sets PQP_FALLBACK_BAD_PLAN
+ *                        and PQP_FALLBACK_ARC.  (A group that is on the arc for one of the first two reasons has no row read.)
+ *      on the plan       sigma = s + e.  S_i = max(s_0 .. s_i), the exact running maximum of prev's s column (pqp_sample_trajectory's walk,
+ *                        there over t); cnt = #{ i < Mp : S_i <= sigma }; i = max(cnt - 1, 0).
+ *                          i < Mp - 1:  ds = s_{i+1} - s_i;  lambda = min(max((sigma - s_i) / ds, 0), 1) when ds > 0, else 0;
+ *                                       x = x_i + lambda * (x_{i+1} - x_i), y likewise, k = k_i + lambda * (k_{i+1} - k_i),
+ *                                       heading = constrainAngle(h_i + lambda * constrainAngle(h_{i+1} - h_i))   (pqp_sample_trajectory's chord)
+ *                          else:        columns 0 to 3 of row Mp - 1, and PQP_FALLBACK_PATH_SHORT when sigma > S_{Mp-1}: the plan ends
+ *                                       before the car stands
+ *                        A sigma in front of row 0 has cnt = 0 and lambda = 0: it stands on row 0
+ *      on the arc        th = k0 * e;  sinc, cosc = pqp_predict_agents' "free model" functions at th, with its Taylor switch at 2^-6;
+ *                        sh0, ch0 = sincos(h0);  p = e * sinc;  q = e * cosc;
+ *                          x = x0 + (p * ch0 - q * sh0);  y = y0 + (p * sh0 + q * ch0);  heading = constrainAngle(h0 + th);  k = k0
+ *                        With k0 = 0 the heading, k and the columns 4 to 7 hold no sincos and are the same bits on any machine; x and y
+ *                        are x0 + e * ch0 and y0 + e * sh0 and are so only where sincos(h0) is exact (h0 = 0): elsewhere the device's sincos
+ *                        and a host's may differ in the last bits, as for every pose of the free model
+ *   4  the records       stop = (T, eT).  stop_row = #{ f < M : t_f < T }, which is the first row at rest, or M - and
+ *                        PQP_FALLBACK_HORIZON - when the stop lies beyond the horizon.  The rows at and behind stop_row are equal but for t
+ * Outputs, fully overwritten:
+ *   rows [groups][n_levels][M][PQP_TRAJ_STRIDE]   x, y, heading, k, s, v, a, t
+ *   stop [groups][n_levels][2], stop_row [groups][n_levels], flags [groups][n_levels] of PQP_FALLBACK_BAD .. PQP_FALLBACK_HORIZON
+ * A plan depends on its own group, its level and the parameters alone: the same bits at any position in any batch and from either form.
+ * No atomics.  The _device form is one launch, asynchronous on the handle's stream, and allocates nothing.  Both forms: PQP_ERR_INVALID,
+ * with nothing launched and the outputs untouched, for a null pointer that is not optional (h, prm, levels, state, rows, stop, stop_row,
+ * flags), groups < 1, n_levels outside 1 .. 8, groups * n_levels beyond an int, a level whose d or j is not finite and positive, a d
+ * below its predecessor's, an a_cap that is negative or NaN, a dt that is not finite and positive, r < 1, m < 1, (m - 1) r + 1 beyond
+ * INT_MAX - 64 (a tile of 64 samples is indexed by an int), prev given with mp < 1 or stride < 8, or prev_m given without prev. */
+int pqp_fallback_rows_device(pqp_handle* h, const double* prm, int n_levels, const double* levels, double dt, int r, int m, int groups, int mp,
+                             int stride, const double* prev, const int32_t* prev_m, const double* state, const int32_t* stitch_flags, double* rows,
+                             double* stop, int32_t* stop_row, int32_t* flags);
+int pqp_fallback_rows(pqp_handle* h, const double* prm, int n_levels, const double* levels, double dt, int r, int m, int groups, int mp, int stride,
+                      const double* prev, const int32_t* prev_m, const double* state, const int32_t* stitch_flags, double* rows, double* stop,
+                      int32_t* stop_row, int32_t* flags);
+/* pqp_fallback_pick: one trajectory per group, always.  Inputs, with m_rows = M:
+ *   best [groups] or NULL               pqp_select_plans' winners.  NULL: every group falls back
+ *   best_traj [groups][m_rows][PQP_TRAJ_STRIDE], best_m [groups]   both or neither: the winners' rows
+ *   rows, row_flags                     pqp_fallback_rows' rows and flags
+ *   first_hit [groups * n_levels] or NULL, first_collision [groups * n_levels] or NULL   pqp_agents_check's and pqp_footprint_check's
+ *                                       verdicts on the plans, plan g * n_levels + l being level l of group g.  NULL: that check was not run
+ * A group with best[g] >= 0 keeps its winner: final_traj is best_traj's rows bit for bit and final_m = best_m[g] (without best_traj: zeros
+ * and 0 - the caller has the winner), level = -1, flags = 0.  Any other group falls back.  A level is usable when its flags have neither
+ * PQP_FALLBACK_BAD nor PQP_FALLBACK_PATH_SHORT, first_hit is absent or equals m_rows, and first_collision is absent or equals m_rows.
+ *   a bad group       a level flagged PQP_FALLBACK_BAD: level = -1, final_traj zeros, final_m = 0, flags = PQP_FALLBACK_BAD alone
+ *   a usable level    the lowest one; flags = its flags | PQP_FALLBACK_TAKEN
+ *   none usable       the level whose first contact min(first_hit, first_collision) - an absent one counting as m_rows - is latest, among
+ *                     equal ones the highest; flags = its flags | PQP_FALLBACK_TAKEN | PQP_FALLBACK_NOT_CLEAR.  The verdicts are read as
+ *                     they are, not clamped: a negative one is an earlier contact than any row, and the rule still names a level
+ *   final_traj is that level's rows bit for bit and final_m = m_rows: the car is planned for the whole horizon, standing rows included
+ * Outputs, fully overwritten: final_traj [groups][m_rows][PQP_TRAJ_STRIDE], final_m [groups], level [groups], flags [groups] - by shape and
+ * by meaning what the next cycle passes to pqp_stitch_trajectory as prev and m_of.  A group's result depends on its own inputs alone; no
+ * atomics; the _device form is one launch on the handle's stream and allocates nothing.  Both forms: PQP_ERR_INVALID, with nothing
+ * launched and the outputs untouched, for a null pointer that is not optional (h, rows, row_flags, final_traj, final_m, level, flags),
+ * groups < 1, n_levels outside 1 .. 8, groups * n_levels beyond an int, m_rows < 1 or beyond INT_MAX - 64, or one of best_traj and best_m
+ * without the other. */
+int pqp_fallback_pick_device(pqp_handle* h, int groups, int n_levels, int m_rows, const int32_t* best, const double* best_traj, const int32_t* best_m,
+                             const double* rows, const int32_t* row_flags, const int32_t* first_hit, const int32_t* first_collision,
+                             double* final_traj, int32_t* final_m, int32_t* level, int32_t* flags);
+int pqp_fallback_pick(pqp_handle* h, int groups, int n_levels, int m_rows, const int32_t* best, const double* best_traj, const int32_t* best_m,
+                      const double* rows, const int32_t* row_flags, const int32_t* first_hit, const int32_t* first_collision, double* final_traj,
+                      int32_t* final_m, int32_t* level, int32_t* flags);
+
 #ifdef __cplusplus
 }
 #endif

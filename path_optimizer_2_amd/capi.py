@@ -347,6 +347,50 @@ def stitch_default_params(lib=None, **over):
     return p
 
 
+class FallbackParams:
+    """what pqp_fallback_rows takes besides its arrays: levels [L][2] = (braking d, jerk j) per level, d ascending, 1 <= L <=
+    FALLBACK_MAX_LEVELS, and a_cap, the cap on the acceleration the braking starts from (prm[FALLBACK_A_CAP] of the C ABI).
+    fallback_default_params(a_cap=...) as for the other parameter sets."""
+    __slots__ = ("levels", "a_cap")
+
+    def __init__(self, levels, a_cap):
+        self.levels = np.array(levels, dtype=np.float64).reshape(-1, 2)
+        self.a_cap = float(a_cap)
+
+    def array(self):
+        out = np.zeros(FALLBACK_PARAMS)
+        out[FALLBACK_A_CAP] = self.a_cap
+        return out
+
+    def level_rows(self):
+        """(L, levels as the contiguous [L][2] float64 array the C ABI reads)"""
+        levels = np.ascontiguousarray(self.levels, dtype=np.float64).reshape(-1, 2)
+        return levels.shape[0], levels
+
+
+def _check_fallback_params(who, prm):
+    """what pqp_fallback_rows refuses of its parameters, for a caller that wants it refused before anything is launched"""
+    levels = np.asarray(prm.levels, dtype=np.float64)
+    if levels.ndim != 2 or levels.shape[1] != 2 or not 1 <= levels.shape[0] <= FALLBACK_MAX_LEVELS:
+        raise ValueError(f"{who}: levels must be [L][2] = (d, j) with 1 <= L <= {FALLBACK_MAX_LEVELS}, not {levels.shape}")
+    if not (np.isfinite(levels).all() and (levels > 0.0).all() and (np.diff(levels[:, 0]) >= 0.0).all()):
+        raise ValueError(f"{who}: every level's d and j must be finite and > 0, and d must ascend")
+    if not prm.a_cap >= 0.0:
+        raise ValueError(f"{who}: a_cap must be >= 0, not {prm.a_cap}")
+
+
+def fallback_default_params(lib=None, **over):
+    """pqp_fallback_default_params: levels (1.5, 2.5), (3.0, 5.0), (6.0, 15.0) in m/s^2 and m/s^3 around the speed profile's d_max, a_cap
+    1.5 m/s^2 = its a_max - this library's choice - with `over` applied."""
+    lib = lib or load_library()
+    prm, levels, count = np.full(FALLBACK_PARAMS, -1.0), np.full((FALLBACK_DEFAULT_LEVELS, 2), -1.0), C.c_int(-1)
+    lib.pqp_fallback_default_params(prm, levels, C.byref(count))
+    p = FallbackParams(levels[:count.value], prm[FALLBACK_A_CAP])
+    for k, v in over.items():
+        setattr(p, k, np.array(v, dtype=np.float64).reshape(-1, 2) if k == "levels" else v)
+    return p
+
+
 def standing_rows(tracks, v_still=0.0):
     """tracks [n_scenes][a_max][9] = x, y, heading, v, a, yaw_rate, half_length, half_width, radius (predict_agents' input) -> the rows
     [n_scenes][a_max][6] = x, y, heading, half_length, half_width, radius that overlay_agents and parked= take: of a track that stands
@@ -738,15 +782,51 @@ def _stage_ranking(c):
                   (), (("rank_start", group_start, _I),), launch)
 
 
+def _stage_fallback(c):
+    """behind the ranking: a braking plan per group and level along the plan the stitch read, from the state it wrote; the agent check
+    (every row: the car is checked while it stands) and the footprint check on those G * L plans as the batch of trajectories they are,
+    against the agents' rows of the finest check the call has - whose frames lie in their workspace already - and the scenes' layers; then
+    one trajectory per group: the winner's, or the gentlest level that passed both"""
+    prm, scene_of, map_of = c.fallback
+    G, mp, stride = c.previous[0].shape
+    L, levels = prm.level_rows()
+    fine = c.planning is not None
+    M, r = (c.fine, c.planning) if fine else (c.layers, 1)
+    rows, frames = ("plan_agents", "plan_frames") if fine else ("agents", "agent_frames")
+    mode = c.footprint if c.footprint is not None else FOOTPRINT_CIRCLES
+
+    def launch(h, c, d):
+        h._check(h.lib.pqp_fallback_rows_device(
+            h._h, prm.array(), L, levels, float(c.searching.dt), r, c.layers, G, mp, stride, d["stitch_prev"], d["stitch_prev_m"], d["stitch_state"],
+            d["stitch_flags"], d["fallback_rows"], d["fallback_stop"], d["fallback_stop_row"], d["fallback_row_flags"]))
+        n_scenes, a_max, agents, agents_of, _, fr = _agent_rows(c, d, rows, frames)
+        h._check(h.lib.pqp_agents_check_device(
+            h._h, float(c.moving[3].margin), C.byref(c.car), G * L, M, TRAJ_STRIDE, d["fallback_rows"], None, n_scenes, a_max, agents, agents_of,
+            d["fallback_scene_of"], fr, d["fallback_first_hit"], d["fallback_hit_agent"], None))
+        h._check(h.lib.pqp_footprint_check_device(
+            h._h, G * L, M, TRAJ_STRIDE, d["fallback_rows"], None, d["dist"], d["fallback_map_of"], C.byref(c.args.geom), C.byref(c.car), mode,
+            d["fallback_free"], d["fallback_first_collision"], None))
+        h._check(h.lib.pqp_fallback_pick_device(
+            h._h, G, L, M, d["rank_best"], d["best_traj"], d["best_m"], d["fallback_rows"], d["fallback_row_flags"], d["fallback_first_hit"],
+            d["fallback_first_collision"], d["final_traj"], d["final_m"], d["fallback_level"], d["fallback_flags"]))
+    return _Stage((("final_traj", (G, M, TRAJ_STRIDE), _F, False), ("final_m", (G,), _I, False), ("fallback_level", (G,), _I, False),
+                   ("fallback_flags", (G,), _I, False), ("fallback_rows", (G, L, M, TRAJ_STRIDE), _F, False), ("fallback_first_hit", (G * L,), _I, False),
+                   ("fallback_first_collision", (G * L,), _I, False)),
+                  (("fallback_stop", (G, L, 2), _F), ("fallback_stop_row", (G, L), _I), ("fallback_row_flags", (G, L), _I),
+                   ("fallback_hit_agent", (G * L,), _I), ("fallback_free", (G * L, M), _U8)),
+                  (("fallback_scene_of", scene_of, _I), ("fallback_map_of", map_of, _I)), launch)
+
+
 # (stage, the fields of the context it needs: the call has the step when none of them is None), in launch order; the result's keys come
-# in the same order, except that the prediction's stand behind the fine plan's and the overlay's and the stitch's behind everything else
+# in the same order, except that the prediction's stand behind the fine plan's, the overlay's and the stitch's behind everything else,
+# and the fallback's behind those
 _STAGES = ((_stage_overlay, ("parked",)), (_stage_stitch, ("previous",)), (_stage_chain, ()), (_stage_footprint, ("footprint",)), (_stage_selection, ("selection",)), (_stage_speed, ("speed",)),
            (_stage_sampling, ("sampling",)), (_stage_predicting, ("moving",)), (_stage_agents, ("moving", "sampling")),
            (_stage_searching, ("searching",)), (_stage_refining, ("refining",)), (_stage_planning, ("planning",)),
-           (_stage_plan_agents, ("plan_agents",)), (_stage_ranking, ("ranking",)))
-_RESULT_ORDER = [f for f, _ in _STAGES if f not in (_stage_predicting, _stage_overlay, _stage_stitch)]
+           (_stage_plan_agents, ("plan_agents",)), (_stage_ranking, ("ranking",)), (_stage_fallback, ("fallback",)))
+_RESULT_ORDER = [f for f, _ in _STAGES if f not in (_stage_predicting, _stage_overlay, _stage_stitch, _stage_fallback)]
 _RESULT_ORDER.insert(_RESULT_ORDER.index(_stage_ranking), _stage_predicting)
-_RESULT_ORDER += [_stage_overlay, _stage_stitch]
+_RESULT_ORDER += [_stage_overlay, _stage_stitch, _stage_fallback]
 
 
 class Handle:
@@ -818,7 +898,7 @@ class Handle:
     def optimize_path(self, points, n_points, start, target, dist, geom, map_of=None, smoother=None, cfg=None, start_k=None, check_footprint=False,
                       car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None, winners_only=False, search=None, refine=None,
                       plan_samples=None, plan_agents=None, agents=None, agents_of=None, scene_of=None, agents_params=None, sample=None, samples=None,
-                      t0=None, tracks=None, layers=None, predict_anchor=False, previous=None, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                      t0=None, tracks=None, layers=None, predict_anchor=False, fallback=None, previous=None, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """pqp_optimize_path_device with torch as the memory plumbing: host arrays in, device-resident chain, host arrays out.
         points [B][p_max][2], n_points [B], start / target [B][3], dist [n_maps][rows][cols] float32.  smoother: the handle the two
         smoother QPs run on (None: this one).  cfg: PqpChainConfig (None: chain_config()); chain_config(second_pass=SECOND_PASS_BOUNDS_ON_STATES)
@@ -887,6 +967,15 @@ class Handle:
         time base), stitch_flags [groups] of STITCH_*, stitch_dev [groups][3] = lon, lat, heading deviation, stitch_prefix [groups][m][8] (the
         re-based piece of the old plan up to the start) and stitch_prefix_n, behind every other key.  A group flagged STITCH_BAD plans from
         the zero start: its results are to be ignored.
+        fallback: True (fallback_default_params()) or a FallbackParams (needs previous= and rank=) - behind the ranking on the same stream,
+        pqp_fallback_rows_device along the plan the stitch read, from the state it wrote: L braking plans per group, M rows each, M and the
+        agents' rows being the fine check's (plan_samples= with plan_agents= or tracks=) where the call has one, else the layers'; then
+        pqp_agents_check_device (every row: the car is checked while it stands) and pqp_footprint_check_device on those groups * L plans -
+        each under its group's first candidate's scene_of and map_of, so a group without candidates is refused - and
+        pqp_fallback_pick_device.  Adds final_traj [groups][M][8] and final_m (a group's winner where it has one, else the gentlest braking
+        plan that passed both checks: what the next cycle passes as prev and prev_m), fallback_level [groups] (-1: the winner, or a bad
+        state), fallback_flags [groups] of FALLBACK_*, fallback_rows [groups][L][M][8], fallback_first_hit and fallback_first_collision
+        [groups * L], behind every other key.  (fallback stands in front of previous for the reason previous stands in front of parked.)
         Every step behind the chain is one record of _STAGES above (its outputs, its uploads, its calls); _chain_plan checks the arguments and
         lays the call out from them without a device, _chain runs it."""
         a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
@@ -897,14 +986,14 @@ class Handle:
                               check_footprint=False, car=None, footprint_mode=FOOTPRINT_CIRCLES, select=None, select_params=None,
                               winners_only=False, search=None, refine=None, plan_samples=None, plan_agents=None, agents=None, agents_of=None,
                               scene_of=None, agents_params=None, sample=None, samples=None, t0=None, tracks=None, layers=None, predict_anchor=False,
-                              previous=None, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
+                              fallback=None, previous=None, parked=None, rank=None, rank_params=None, speed=None, v_start=None, v_end=None):
         """optimize_path with occupancy grids in place of distance layers: grid [n_maps][rows][cols] (or 2-D) uint8, 0 = obstacle, goes to the
         device as bytes, pqp_distance_layer_device builds the layers there and pqp_optimize_path_device reads them, on the same stream with
         no host round trip between the two.  Returns what optimize_path returns (check_footprint: against the layers built on the device;
         select / select_params / winners_only / speed / v_start / v_end / sample / samples / t0 / agents / agents_of / scene_of /
         agents_params / search / refine / plan_samples / plan_agents / rank / rank_params / tracks / layers / predict_anchor: as for
         optimize_path; parked: as for optimize_path, over the layers built on the device, base_of indexing the grids.  Moving agents are not
-        overlaid; a standing agent may be given both to parked= and to the speed stages; previous: as for optimize_path)."""
+        overlaid; a standing agent may be given both to parked= and to the speed stages; previous, fallback: as for optimize_path)."""
         a = dict(locals())                  # the arguments by name, as _chain_plan takes them: no statement may stand above this one
         del a["self"], a["grid"]
         plan = self._chain_plan(**a)
@@ -1105,6 +1194,29 @@ class Handle:
             raise ValueError("previous: the parameters must be a StitchParams")
         return (prev, prev_m, meas, t_now, prm if prm is not None else stitch_default_params(self.lib), starts)
 
+    def _fallback(self, fallback, previous, ranking, planning, scene_of, map_of):
+        """fallback= of optimize_path: (FallbackParams, the plans' scene_of, the plans' map_of or None) checked, or None.  previous,
+        ranking and planning are those arguments as checked"""
+        if fallback is None or fallback is False:
+            return None
+        if fallback is not True and not isinstance(fallback, FallbackParams):
+            raise ValueError("fallback must be True or a FallbackParams")
+        if previous is None or ranking is None:
+            raise ValueError("fallback needs previous= and rank=: it brakes along the previous plan, in the groups that end without a winner")
+        if planning is not None and planning[1] is None:
+            raise ValueError("fallback with plan_samples= needs plan_agents= (or tracks=): its plans are checked on the fine steps")
+        prm = fallback_default_params(self.lib) if fallback is True else fallback
+        L = prm.level_rows()[0]
+        _check_fallback_params("fallback", prm)
+        group_start = ranking[0]
+        empty = np.flatnonzero(np.diff(group_start) == 0)
+        if empty.size:
+            raise ValueError(f"fallback: group {int(empty[0])} is empty, so it has no scene to check a braking plan in")
+        first = group_start[:-1]
+        per_plan = lambda of: None if of is None else np.repeat(np.ascontiguousarray(of, dtype=np.int32).ravel()[first], L)
+        plans_scene = per_plan(scene_of)
+        return (prm, plans_scene if plans_scene is not None else np.zeros(first.size * L, np.int32), per_plan(map_of))
+
     def _selection(self, select, select_params, winners_only):
         if select is None:
             if winners_only or select_params is not None:
@@ -1120,6 +1232,7 @@ class Handle:
           c.footprint .. c.predicting    each step's checked parameters (planning: r, plan_agents beside it), or None where the call has no such step
           c.parked                       (standing agents' rows, base_of, inflate) of the overlay in front of the chain, or None
           c.previous                     (prev, prev_m, meas, t_now, StitchParams, group_start or None) of the stitch in front of the chain, or None
+          c.fallback                     (FallbackParams, scene_of [groups * L], map_of [groups * L] or None) of the braking plans behind the ranking, or None
           c.car                          the footprint of the footprint check and of every check against agents
           c.groups, c.rows, c.paths      the rows of the speed stages - `groups` with select=, else B - and the buffers they run on as (paths,
                                          n_of, stop_before): the winners' best_paths / best_n and no stop, or out / n_out and first_collision
@@ -1143,6 +1256,7 @@ class Handle:
             planning=self._plan(a.plan_samples, plan_agents, a.search, agents),
             ranking=self._ranking(a.rank, a.rank_params, a.winners_only, a.search, a.select, B),
             parked=self._parked(a.parked, a.map_of, a.geom))
+        c.fallback = self._fallback(a.fallback, c.previous, c.ranking, c.planning, a.scene_of, a.map_of)
         c.planning, c.plan_agents = c.planning or (None, None)         # r, and the agents' fine rows or their shape
         c.cfg = a.cfg or _defaults(self.lib, PqpChainConfig, "pqp_chain_default_config", {})
         c.n_max = c.cfg.n_max
@@ -1507,6 +1621,54 @@ class Handle:
         self._check(self.lib.pqp_stitch_trajectory(self._h, prm.array(), int(prm.keep), prefix_max, G, m, stride, prev, mo, meas, tn, batch, gs,
                                                    res["state"], res["flags"], res["dev"], res["idx"], res["prefix"], res["prefix_n"], res["start"],
                                                    res["start_k"], res["v_start"]))
+        return res
+
+    def fallback_rows(self, state, m, dt=1.0, r=1, prev=None, prev_m=None, stitch_flags=None, prm=None):
+        """pqp_fallback_rows (host arrays): state [G][8] (stitch_trajectory's state), m layers of dt with r sub-steps each (M = (m - 1) r + 1
+        rows per plan), and optionally prev [G][mp][stride >= 8] with prev_m [G] (the plan the stitch read; None: every group brakes on its
+        arc), stitch_flags [G] (the stitch's; None: all stitched), prm = FallbackParams (None: fallback_default_params()).  Returns
+        dict(rows [G][L][M][8], stop [G][L][2] = T, e(T), stop_row [G][L], flags [G][L] of FALLBACK_*)."""
+        state = _f64(state)
+        if state.ndim != 2 or state.shape[1] != TRAJ_STRIDE:
+            raise ValueError(f"fallback_rows: state must be [G][{TRAJ_STRIDE}], not {state.shape}")
+        G = state.shape[0]
+        prev, pm, sf = _f64(prev), _i32(prev_m), _i32(stitch_flags)
+        if prev is not None and (prev.ndim != 3 or prev.shape[0] != G):
+            raise ValueError(f"fallback_rows: prev must be [{G}][mp][stride], not {prev.shape}")
+        if prev is None and pm is not None:
+            raise ValueError("fallback_rows: prev_m needs prev")
+        _check_sizes("fallback_rows", ("prev_m", pm, G), ("stitch_flags", sf, G))
+        mp, stride = (0, 0) if prev is None else prev.shape[1:]
+        prm = prm if prm is not None else fallback_default_params(self.lib)
+        L, levels = prm.level_rows()
+        m, r = int(m), int(r)
+        M = max(m - 1, 0) * max(r, 0) + 1
+        if M > 2 ** 31 - 1 - 64:
+            raise ValueError(f"fallback_rows: (m - 1) r + 1 = {M} rows per plan do not fit an int (less a tile of 64)")
+        res = dict(rows=np.zeros((G, L, M, TRAJ_STRIDE)), stop=np.zeros((G, L, 2)), stop_row=np.zeros((G, L), dtype=np.int32),
+                   flags=np.zeros((G, L), dtype=np.int32))
+        self._check(self.lib.pqp_fallback_rows(self._h, prm.array(), L, levels, float(dt), r, m, G, mp, stride, prev, pm, state, sf, res["rows"],
+                                               res["stop"], res["stop_row"], res["flags"]))
+        return res
+
+    def fallback_pick(self, rows, row_flags, best=None, best_traj=None, best_m=None, first_hit=None, first_collision=None):
+        """pqp_fallback_pick (host arrays): rows [G][L][M][8] and row_flags [G][L] as fallback_rows returned them, and optionally best [G]
+        (select_plans' winners; None: every group falls back), best_traj [G][M][8] with best_m [G] (both or neither), first_hit [G * L]
+        and first_collision [G * L] (agents_check's and footprint_check's verdicts on the G * L plans; None: not checked).  Returns
+        dict(final_traj [G][M][8], final_m [G], level [G], flags [G] of FALLBACK_*): what the next cycle passes as prev and prev_m."""
+        rows = _f64(rows)
+        if rows.ndim != 4 or rows.shape[3] != TRAJ_STRIDE:
+            raise ValueError(f"fallback_pick: rows must be [G][L][M][{TRAJ_STRIDE}], not {rows.shape}")
+        G, L, M = rows.shape[:3]
+        rf, b, bt, bm, fh, fc = _i32(row_flags), _i32(best), _f64(best_traj), _i32(best_m), _i32(first_hit), _i32(first_collision)
+        if (bt is None) != (bm is None):
+            raise ValueError("fallback_pick: best_traj and best_m go together")
+        _check_sizes("fallback_pick", ("row_flags", rf, G * L), ("best", b, G), ("best_traj", bt, G * M * TRAJ_STRIDE), ("best_m", bm, G),
+                     ("first_hit", fh, G * L), ("first_collision", fc, G * L))
+        res = dict(final_traj=np.zeros((G, M, TRAJ_STRIDE)), final_m=np.zeros(G, dtype=np.int32), level=np.zeros(G, dtype=np.int32),
+                   flags=np.zeros(G, dtype=np.int32))
+        self._check(self.lib.pqp_fallback_pick(self._h, G, L, M, b, bt, bm, rows, rf, fh, fc, res["final_traj"], res["final_m"], res["level"],
+                                               res["flags"]))
         return res
 
     def corridor_params(self, **over):

@@ -44,6 +44,26 @@ __device__ __forceinline__ int walk_tile(const double* __restrict__ prof, int co
     return pos;
 }
 
+// The same tile of the same walk along column `col` of rows that lie `stride` doubles apart: a trajectory's rows (PQP_TRAJ_STRIDE's
+// columns, s at 4), which have their own stride where the profile's is PQP_SPEED_STRIDE.
+__device__ __forceinline__ int walk_tile(const double* __restrict__ rows, int stride, int col, int c, int w, double carry, double bound, int lane,
+                                         double* last) {
+#pragma clang fp contract(off)
+    const int i = w * 64 + lane;
+    const int nv = min(64, c - w * 64);
+    const double neg = i < c ? -rows[(size_t)i * stride + col] : INFINITY;
+    const double M = fmax(carry, -wave_prefix_min(neg));
+    int pos = 0;
+#pragma unroll
+    for (int step = 64; step >= 1; step >>= 1) {
+        const int at = pos + step - 1;
+        const double Mv = __shfl(M, at & 63);
+        if (at < nv && Mv <= bound) pos += step;
+    }
+    *last = wave_read<63>(M);
+    return pos;
+}
+
 struct PathPose { double x, y, heading, k; };
 
 // a waypoint itself: the last driven one, where there is no chord to stand on
@@ -59,6 +79,17 @@ __device__ __forceinline__ PathPose chord_pose(const double* r0, int stride, dou
     const double e = fmin(fmax(want, 0.0), d);
     const double lam = d > 0.0 ? e / d : 0.0;
     *e_out = e;
+    return {x0 + lam * dx, y0 + lam * dy, constrain_angle(h0 + lam * constrain_angle(h1 - h0)), c0 + lam * (c1 - c0)};
+}
+
+// the same chord expressions between trajectory row r0 (x, y, heading, k, s at 0 .. 4) and the row behind it, the place on the chord
+// given by the station: lam = (sigma - s0) / (s1 - s0) inside [0, 1], and 0 where s does not grow along the segment
+__device__ __forceinline__ PathPose chord_pose_at_station(const double* r0, int stride, double sigma) {
+#pragma clang fp contract(off)
+    const double* r1 = r0 + stride;
+    const double x0 = r0[0], y0 = r0[1], h0 = r0[2], c0 = r0[3], s0 = r0[4], x1 = r1[0], y1 = r1[1], h1 = r1[2], c1 = r1[3], s1 = r1[4];
+    const double dx = x1 - x0, dy = y1 - y0, ds = s1 - s0;
+    const double lam = ds > 0.0 ? fmin(fmax((sigma - s0) / ds, 0.0), 1.0) : 0.0;
     return {x0 + lam * dx, y0 + lam * dy, constrain_angle(h0 + lam * constrain_angle(h1 - h0)), c0 + lam * (c1 - c0)};
 }
 

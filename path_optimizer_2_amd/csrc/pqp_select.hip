@@ -1,8 +1,10 @@
 // pqp_select.hip — the entry points of include/pqp.h that choose: scores of candidate paths and each group's best
 // (pqp_select_kernels.inc), scores of the finished trajectories and each group's best (pqp_rank_kernels.inc), and the start of the next
-// cycle on the winner a cycle left (pqp_stitch_kernels.inc).  Their kernels, launchers and entry points.
+// cycle on the winner a cycle left (pqp_stitch_kernels.inc), and the braking plans of a group that ends without a winner
+// (pqp_fallback_kernels.inc).  Their kernels, launchers and entry points.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 
 #include "pqp_defaults.hpp"
@@ -13,6 +15,7 @@ using namespace pqp_internal;
 #include "pqp_select_kernels.inc"
 #include "pqp_rank_kernels.inc"
 #include "pqp_stitch_kernels.inc"
+#include "pqp_fallback_kernels.inc"
 
 extern "C" {
 
@@ -253,6 +256,138 @@ int pqp_stitch_trajectory(pqp_handle* h, const double* prm, int keep, int prefix
     return st.run([&]() -> int {
         return pqp_stitch_trajectory_device(h, prm, keep, prefix_max, groups, m, stride, d_prev, d_m_of, d_meas, d_t_now, batch, d_start_of, d_state,
                                             d_flags, d_dev, d_idx, d_prefix, d_prefix_n, d_start, d_start_k, d_v_start);
+    });
+}
+
+// ---- a plan for every group: braking fallbacks where no candidate wins ------------------------------------------------------------------------
+void pqp_fallback_default_params(double* prm, double* levels, int* n_levels) {
+    pqp_speed_params sp;
+    pqp_speed_default_params(&sp);
+    if (prm) prm[PQP_FALLBACK_A_CAP] = sp.a_max;
+    if (levels) {
+        // this library's choice (include/pqp.h cites it): half of d_max, d_max, twice d_max
+        levels[0] = 0.5 * sp.d_max; levels[1] = 2.5;
+        levels[2] = sp.d_max;       levels[3] = 5.0;
+        levels[4] = 2.0 * sp.d_max; levels[5] = 15.0;
+    }
+    if (n_levels) *n_levels = PQP_FALLBACK_DEFAULT_LEVELS;
+}
+
+static const char* const kFallbackRowsRefusal =
+    "pqp_fallback_rows: bad argument (groups >= 1; 1 <= n_levels <= 8 and groups * n_levels within an int; every level's d and j finite and > 0, "
+    "d ascending; a_cap >= 0; dt finite and > 0; r >= 1; m >= 1; (m - 1) r + 1 <= INT_MAX - 64; with prev mp >= 1 and stride >= 8; prev_m only with prev)";
+
+static bool fallback_rows_ok(pqp_handle* h, const double* prm, int n_levels, const double* levels, double dt, int r, int m, int groups, int mp,
+                             int stride, const double* prev, const int32_t* prev_m, const double* state, const double* rows, const double* stop,
+                             const int32_t* stop_row, const int32_t* flags) {
+    if (!(h && prm && levels && state && rows && stop && stop_row && flags)) return false;
+    if (!(groups >= 1 && n_levels >= 1 && n_levels <= PQP_FALLBACK_MAX_LEVELS && (long long)groups * n_levels <= INT_MAX)) return false;
+    if (!(std::isfinite(dt) && dt > 0.0 && r >= 1 && m >= 1 && ((long long)m - 1) * r + 1 <= pqp::kFallbackMaxRows)) return false;
+    if (prev ? !(mp >= 1 && stride >= PQP_TRAJ_STRIDE) : prev_m != nullptr) return false;
+    if (!(prm[PQP_FALLBACK_A_CAP] >= 0.0)) return false;                       // (a NaN fails it too)
+    for (int l = 0; l < n_levels; ++l) {
+        const double d = levels[2 * l], j = levels[2 * l + 1];
+        if (!(std::isfinite(d) && std::isfinite(j) && d > 0.0 && j > 0.0) || (l > 0 && !(d >= levels[2 * l - 2]))) return false;
+    }
+    return true;
+}
+
+int pqp_fallback_rows_device(pqp_handle* h, const double* prm, int n_levels, const double* levels, double dt, int r, int m, int groups, int mp,
+                             int stride, const double* prev, const int32_t* prev_m, const double* state, const int32_t* stitch_flags, double* rows,
+                             double* stop, int32_t* stop_row, int32_t* flags) {
+    if (!fallback_rows_ok(h, prm, n_levels, levels, dt, r, m, groups, mp, stride, prev, prev_m, state, rows, stop, stop_row, flags))
+        return fail(PQP_ERR_INVALID, kFallbackRowsRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::FallbackArgs a;
+    a.groups = groups; a.levels = n_levels; a.mp = prev ? mp : 0; a.stride = prev ? stride : PQP_TRAJ_STRIDE; a.r = r; a.M = (m - 1) * r + 1;
+    a.dt = dt; a.a_cap = prm[PQP_FALLBACK_A_CAP];
+    for (int l = 0; l < PQP_FALLBACK_MAX_LEVELS; ++l) {
+        a.level[l][0] = l < n_levels ? levels[2 * l] : 0.0;
+        a.level[l][1] = l < n_levels ? levels[2 * l + 1] : 0.0;
+    }
+    a.prev = prev; a.prev_m = prev_m; a.state = state; a.stitch_flags = stitch_flags;
+    a.rows = rows; a.stop = stop; a.stop_row = stop_row; a.flags = flags;
+    return h->launch_timed([&]() -> int {
+        const long long items = (long long)groups * n_levels;
+        const long long blocks = (items + pqp::kFallbackThreads / 64 - 1) / (pqp::kFallbackThreads / 64);
+        hipLaunchKernelGGL(pqp::fallback_rows_kernel, dim3((unsigned)std::min(blocks, pqp::kFallbackMaxBlocks)), dim3(pqp::kFallbackThreads), 0,
+                           h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_fallback_rows(pqp_handle* h, const double* prm, int n_levels, const double* levels, double dt, int r, int m, int groups, int mp, int stride,
+                      const double* prev, const int32_t* prev_m, const double* state, const int32_t* stitch_flags, double* rows, double* stop,
+                      int32_t* stop_row, int32_t* flags) {
+    if (!fallback_rows_ok(h, prm, n_levels, levels, dt, r, m, groups, mp, stride, prev, prev_m, state, rows, stop, stop_row, flags))
+        return fail(PQP_ERR_INVALID, kFallbackRowsRefusal);
+    const size_t G = groups, items = G * n_levels, M = (size_t)(m - 1) * r + 1;
+    Staging st(h);
+    const double* d_prev = prev ? st.in(prev, G * mp * stride) : nullptr;
+    const int32_t* d_prev_m = st.in(prev_m, G);
+    const double* d_state = st.in(state, G * PQP_TRAJ_STRIDE);
+    const int32_t* d_sflags = st.in(stitch_flags, G);
+    double* d_rows = st.out(rows, items * M * PQP_TRAJ_STRIDE);
+    double* d_stop = st.out(stop, items * 2);
+    int32_t* d_stop_row = st.out(stop_row, items);
+    int32_t* d_flags = st.out(flags, items);
+    return st.run([&]() -> int {
+        return pqp_fallback_rows_device(h, prm, n_levels, levels, dt, r, m, groups, mp, stride, d_prev, d_prev_m, d_state, d_sflags, d_rows, d_stop,
+                                        d_stop_row, d_flags);
+    });
+}
+
+static const char* const kFallbackPickRefusal =
+    "pqp_fallback_pick: bad argument (groups >= 1; 1 <= n_levels <= 8 and groups * n_levels within an int; 1 <= m_rows <= INT_MAX - 64; best_traj and best_m both "
+    "or neither)";
+
+static bool fallback_pick_ok(pqp_handle* h, int groups, int n_levels, int m_rows, const double* best_traj, const int32_t* best_m, const double* rows,
+                             const int32_t* row_flags, const double* final_traj, const int32_t* final_m, const int32_t* level, const int32_t* flags) {
+    return h && rows && row_flags && final_traj && final_m && level && flags && groups >= 1 && n_levels >= 1 && n_levels <= PQP_FALLBACK_MAX_LEVELS &&
+           (long long)groups * n_levels <= INT_MAX && m_rows >= 1 && m_rows <= pqp::kFallbackMaxRows && (best_traj != nullptr) == (best_m != nullptr);
+}
+
+int pqp_fallback_pick_device(pqp_handle* h, int groups, int n_levels, int m_rows, const int32_t* best, const double* best_traj, const int32_t* best_m,
+                             const double* rows, const int32_t* row_flags, const int32_t* first_hit, const int32_t* first_collision,
+                             double* final_traj, int32_t* final_m, int32_t* level, int32_t* flags) {
+    if (!fallback_pick_ok(h, groups, n_levels, m_rows, best_traj, best_m, rows, row_flags, final_traj, final_m, level, flags))
+        return fail(PQP_ERR_INVALID, kFallbackPickRefusal);
+    PQP_HIP(hipSetDevice(h->device));
+    pqp::FallbackPickArgs a;
+    a.groups = groups; a.levels = n_levels; a.M = m_rows; a.best = best; a.best_traj = best_traj; a.best_m = best_m; a.rows = rows;
+    a.row_flags = row_flags; a.first_hit = first_hit; a.first_collision = first_collision; a.final_traj = final_traj; a.final_m = final_m;
+    a.level = level; a.flags = flags;
+    return h->launch_timed([&]() -> int {
+        const long long blocks = ((long long)groups + pqp::kFallbackThreads / 64 - 1) / (pqp::kFallbackThreads / 64);
+        hipLaunchKernelGGL(pqp::fallback_pick_kernel, dim3((unsigned)std::min(blocks, pqp::kFallbackMaxBlocks)), dim3(pqp::kFallbackThreads), 0,
+                           h->stream, a);
+        PQP_HIP(hipGetLastError());
+        return PQP_OK;
+    });
+}
+
+int pqp_fallback_pick(pqp_handle* h, int groups, int n_levels, int m_rows, const int32_t* best, const double* best_traj, const int32_t* best_m,
+                      const double* rows, const int32_t* row_flags, const int32_t* first_hit, const int32_t* first_collision, double* final_traj,
+                      int32_t* final_m, int32_t* level, int32_t* flags) {
+    if (!fallback_pick_ok(h, groups, n_levels, m_rows, best_traj, best_m, rows, row_flags, final_traj, final_m, level, flags))
+        return fail(PQP_ERR_INVALID, kFallbackPickRefusal);
+    const size_t G = groups, items = G * n_levels, cells = (size_t)m_rows * PQP_TRAJ_STRIDE;
+    Staging st(h);
+    const int32_t* d_best = st.in(best, G);
+    const double* d_best_traj = st.in(best_traj, G * cells);
+    const int32_t* d_best_m = st.in(best_m, G);
+    const double* d_rows = st.in(rows, items * cells);
+    const int32_t* d_rflags = st.in(row_flags, items);
+    const int32_t* d_hit = st.in(first_hit, items);
+    const int32_t* d_col = st.in(first_collision, items);
+    double* d_final = st.out(final_traj, G * cells);
+    int32_t* d_final_m = st.out(final_m, G);
+    int32_t* d_level = st.out(level, G);
+    int32_t* d_flags = st.out(flags, G);
+    return st.run([&]() -> int {
+        return pqp_fallback_pick_device(h, groups, n_levels, m_rows, d_best, d_best_traj, d_best_m, d_rows, d_rflags, d_hit, d_col, d_final, d_final_m,
+                                        d_level, d_flags);
     });
 }
 
