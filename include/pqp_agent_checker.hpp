@@ -10,7 +10,6 @@
 //
 // Not copyable, not thread-safe, no exceptions; check() returns false on a GPU error or a bad argument (pqp_last_error()).
 #pragma once
-#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -18,14 +17,9 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"          // PredictedAgent
 
 namespace PathOptimizationNS {
-
-// an agent at one time step: a rectangle of half_length x half_width around (x, y), turned by heading and rounded by radius (a disc:
-// half_length = half_width = 0).  half_length < 0 or half_width < 0: not there at that step
-struct PredictedAgent {
-    double x{}, y{}, heading{}, half_length{}, half_width{}, radius{};
-};
 
 class AgentChecker {
  public:
@@ -53,34 +47,15 @@ class AgentChecker {
         if (!first_hit || !hit_agent || trajectories.empty() || scenes.empty()) return false;
         const size_t B = trajectories.size(), S = scenes.size();
         if (scene_of && scene_of->size() != B) return false;
-        size_t m = 1, a_max = 0;
-        for (const auto& t : trajectories) m = std::max(m, t.size());
-        for (const auto& s : scenes) a_max = std::max(a_max, s.size());
-        std::vector<double> traj(B * m * 3, 0.0), agents(S * a_max * m * PQP_AGENT_STRIDE, 0.0), clear(clearance ? B * m : 0);
-        std::vector<int32_t> m_of(B), a_of(S), scene, first(B), who(B);
-        for (size_t b = 0; b < B; ++b) {
-            m_of[b] = (int32_t)trajectories[b].size();
-            for (size_t k = 0; k < trajectories[b].size(); ++k) {
-                double* r = &traj[(b * m + k) * 3];
-                r[0] = trajectories[b][k].x; r[1] = trajectories[b][k].y; r[2] = trajectories[b][k].heading;
-            }
-        }
-        for (size_t s = 0; s < S; ++s) {
-            a_of[s] = (int32_t)scenes[s].size();
-            for (size_t a = 0; a < scenes[s].size(); ++a)
-                for (size_t k = 0; k < m; ++k) {
-                    double* r = &agents[((s * a_max + a) * m + k) * PQP_AGENT_STRIDE];
-                    if (k < scenes[s][a].size()) {
-                        const PredictedAgent& p = scenes[s][a][k];
-                        r[0] = p.x; r[1] = p.y; r[2] = p.heading; r[3] = p.half_length; r[4] = p.half_width; r[5] = p.radius;
-                    } else {
-                        r[3] = -1.0;
-                    }
-                }
-        }
+        const detail::Packed traj = detail::pack(trajectories, 3, detail::PoseRow());
+        const size_t m = traj.n;
+        const detail::AgentRows ag = detail::pack_agents(scenes, m);
+        std::vector<double> clear(clearance ? B * m : 0);
+        std::vector<int32_t> scene, first(B), who(B);
         if (scene_of) scene.assign(scene_of->begin(), scene_of->end());
-        if (pqp_agents_check(&h_, prm_.margin, &car_, (int)B, (int)m, 3, traj.data(), m_of.data(), (int)S, (int)a_max, a_max ? agents.data() : nullptr,
-                             a_of.data(), scene_of ? scene.data() : nullptr, first.data(), who.data(), clearance ? clear.data() : nullptr) != PQP_OK)
+        if (pqp_agents_check(&h_, prm_.margin, &car_, (int)B, (int)m, 3, traj.rows.data(), traj.count.data(), (int)S, (int)ag.a_max,
+                             ag.a_max ? ag.rows.data() : nullptr, ag.a_of.data(), scene_of ? scene.data() : nullptr, first.data(), who.data(),
+                             clearance ? clear.data() : nullptr) != PQP_OK)
             return false;
         first_hit->assign(first.begin(), first.end());
         hit_agent->assign(who.begin(), who.end());

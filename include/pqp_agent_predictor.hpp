@@ -50,40 +50,27 @@ class AgentPredictor {
                  std::vector<std::vector<std::vector<PredictedAgent>>>* out, std::vector<std::vector<int>>* flags = nullptr) {
         if (!out || scenes.empty() || m < 1 || r < 1) return false;
         const size_t S = scenes.size(), M = (size_t)(m - 1) * r + 1;
-        size_t a_max = 0;
-        for (const auto& s : scenes) a_max = std::max(a_max, s.size());
         const int n_lanes = (int)lane_length_.size();
-        std::vector<double> tracks(S * a_max * PQP_TRACK_STRIDE, 0.0), rows(S * a_max * M * PQP_AGENT_STRIDE);
-        std::vector<int32_t> a_of(S), lane_of(S * a_max, -1), fl(S * a_max);
-        for (size_t s = 0; s < S; ++s) {
-            a_of[s] = (int32_t)scenes[s].size();
+        const detail::Packed tracks = detail::pack(scenes, PQP_TRACK_STRIDE, [](const TrackedAgent& t, size_t, double* q) {
+            const double row[PQP_TRACK_STRIDE] = {t.x, t.y, t.heading, t.v, t.a, t.yaw_rate, t.half_length, t.half_width, t.radius};
+            std::copy(row, row + PQP_TRACK_STRIDE, q);
+        }, 0);
+        const size_t a_max = tracks.n;
+        std::vector<double> rows(S * a_max * M * PQP_AGENT_STRIDE);
+        std::vector<int32_t> lane_of(S * a_max, -1), fl(S * a_max);
+        for (size_t s = 0; s < S; ++s)
             for (size_t a = 0; a < scenes[s].size(); ++a) {
-                const TrackedAgent& t = scenes[s][a];
-                if (t.lane >= n_lanes) return false;
-                double* q = &tracks[(s * a_max + a) * PQP_TRACK_STRIDE];
-                q[0] = t.x; q[1] = t.y; q[2] = t.heading; q[3] = t.v; q[4] = t.a; q[5] = t.yaw_rate;
-                q[6] = t.half_length; q[7] = t.half_width; q[8] = t.radius;
-                lane_of[s * a_max + a] = t.lane;
+                if (scenes[s][a].lane >= n_lanes) return false;
+                lane_of[s * a_max + a] = scenes[s][a].lane;
             }
-        }
         const double prm[PQP_PREDICT_PARAMS] = {prm_.v_cap, prm_.grow, prm_.l_max};
-        if (pqp_predict_agents(&h_, prm, t0, dt, m, r, (int)S, (int)a_max, tracks.data(), a_of.data(), lane_of.data(), n_lanes, lane_m_,
+        if (pqp_predict_agents(&h_, prm, t0, dt, m, r, (int)S, (int)a_max, tracks.rows.data(), tracks.count.data(), lane_of.data(), n_lanes, lane_m_,
                                n_lanes ? lane_spline_.data() : nullptr, n_lanes ? lane_ext_.data() : nullptr,
                                n_lanes ? lane_length_.data() : nullptr, rows.data(), nullptr, fl.data()) != PQP_OK)
             return false;
-        out->assign(S, {});
+        detail::unpack_agents(rows, tracks.count, a_max, M, out);
         if (flags) flags->assign(S, {});
-        for (size_t s = 0; s < S; ++s) {
-            (*out)[s].resize(scenes[s].size());
-            if (flags) (*flags)[s].assign(fl.begin() + s * a_max, fl.begin() + s * a_max + scenes[s].size());
-            for (size_t a = 0; a < scenes[s].size(); ++a) {
-                (*out)[s][a].resize(M);
-                for (size_t f = 0; f < M; ++f) {
-                    const double* q = &rows[((s * a_max + a) * M + f) * PQP_AGENT_STRIDE];
-                    (*out)[s][a][f] = PredictedAgent{q[0], q[1], q[2], q[3], q[4], q[5]};
-                }
-            }
-        }
+        for (size_t s = 0; flags && s < S; ++s) (*flags)[s].assign(fl.begin() + s * a_max, fl.begin() + s * a_max + scenes[s].size());
         return true;
     }
 

@@ -19,22 +19,19 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
 class FallbackPlanner {
  public:
-    explicit FallbackPlanner(int device = 0) {
+    explicit FallbackPlanner(int device = 0) : h_(device) {
         int n = 0;
         levels_.assign(2 * PQP_FALLBACK_DEFAULT_LEVELS, 0.0);
         pqp_fallback_default_params(prm_, levels_.data(), &n);
         levels_.resize(2 * (size_t)n);
-        ok_ = pqp_create(&h_, nullptr, device, 1, 2) == PQP_OK;
     }
-    FallbackPlanner(const FallbackPlanner&) = delete;
-    FallbackPlanner& operator=(const FallbackPlanner&) = delete;
-    ~FallbackPlanner() { if (h_) pqp_destroy(h_); }
-    bool ok() const { return ok_; }
+    bool ok() const { return h_.ok(); }
     std::vector<double>& levels() { return levels_; }          // d0, j0, d1, j1, ...: d ascending, at most PQP_FALLBACK_MAX_LEVELS pairs
     double& a_cap() { return prm_[PQP_FALLBACK_A_CAP]; }
 
@@ -64,19 +61,12 @@ class FallbackPlanner {
     template <class StateT>
     bool brake(const std::vector<std::vector<StateT>>& previous, const std::vector<Start>& starts, double dt, int r, int m, Plans* plans) {
         const size_t G = previous.size(), L = levels_.size() / 2;
-        if (!ok_ || !plans || G == 0 || starts.size() != G || L == 0 || r < 1 || m < 1) return false;
-        size_t mp = 1;
-        for (const auto& t : previous) mp = t.size() > mp ? t.size() : mp;
-        const size_t M = (size_t)(m - 1) * r + 1;
-        std::vector<double> prev(G * mp * PQP_TRAJ_STRIDE, 0.0), state(G * PQP_TRAJ_STRIDE);
-        std::vector<int32_t> prev_m(G), sflags(G);
+        if (!ok() || !plans || G == 0 || starts.size() != G || L == 0 || r < 1 || m < 1) return false;
+        const detail::Packed prev = detail::pack(previous, PQP_TRAJ_STRIDE, detail::TrajRow());
+        const size_t mp = prev.n, M = (size_t)(m - 1) * r + 1;
+        std::vector<double> state(G * PQP_TRAJ_STRIDE);
+        std::vector<int32_t> sflags(G);
         for (size_t g = 0; g < G; ++g) {
-            prev_m[g] = (int32_t)previous[g].size();
-            for (size_t f = 0; f < previous[g].size(); ++f) {
-                const StateT& s = previous[g][f];
-                double* q = &prev[(g * mp + f) * PQP_TRAJ_STRIDE];
-                q[0] = s.x; q[1] = s.y; q[2] = s.heading; q[3] = s.k; q[4] = s.s; q[5] = s.v; q[6] = s.a;
-            }
             for (int c = 0; c < PQP_TRAJ_STRIDE; ++c) state[g * PQP_TRAJ_STRIDE + c] = starts[g].row[c];
             sflags[g] = starts[g].stitch_flags;
         }
@@ -85,8 +75,8 @@ class FallbackPlanner {
         plans->stop.assign(G * L * 2, 0.0);
         plans->stop_row.assign(G * L, 0);
         plans->flags.assign(G * L, 0);
-        return pqp_fallback_rows(h_, prm_, (int)L, levels_.data(), dt, r, m, (int)G, (int)mp, PQP_TRAJ_STRIDE, prev.data(), prev_m.data(), state.data(),
-                                 sflags.data(), plans->rows.data(), plans->stop.data(), plans->stop_row.data(), plans->flags.data()) == PQP_OK;
+        return pqp_fallback_rows(h_.get(), prm_, (int)L, levels_.data(), dt, r, m, (int)G, (int)mp, PQP_TRAJ_STRIDE, prev.rows.data(), prev.count.data(),
+                                 state.data(), sflags.data(), plans->rows.data(), plans->stop.data(), plans->stop_row.data(), plans->flags.data()) == PQP_OK;
     }
 
     // first_hit / first_collision: AgentChecker's and FootprintChecker's verdicts on the vehicles * levels plans of `plans`, or nullptr
@@ -94,10 +84,10 @@ class FallbackPlanner {
     template <class StateT>
     bool pick(const Plans& plans, const std::vector<int32_t>* first_hit, const std::vector<int32_t>* first_collision, std::vector<Result<StateT>>* results) {
         const size_t G = plans.vehicles, L = plans.levels, M = plans.rows_per_plan;
-        if (!ok_ || !results || G == 0 || (first_hit && first_hit->size() != G * L) || (first_collision && first_collision->size() != G * L)) return false;
+        if (!ok() || !results || G == 0 || (first_hit && first_hit->size() != G * L) || (first_collision && first_collision->size() != G * L)) return false;
         std::vector<double> final_traj(G * M * PQP_TRAJ_STRIDE);
         std::vector<int32_t> final_m(G), level(G), flags(G);
-        if (pqp_fallback_pick(h_, (int)G, (int)L, (int)M, nullptr, nullptr, nullptr, plans.rows.data(), plans.flags.data(),
+        if (pqp_fallback_pick(h_.get(), (int)G, (int)L, (int)M, nullptr, nullptr, nullptr, plans.rows.data(), plans.flags.data(),
                               first_hit ? first_hit->data() : nullptr, first_collision ? first_collision->data() : nullptr, final_traj.data(),
                               final_m.data(), level.data(), flags.data()) != PQP_OK)
             return false;
@@ -108,9 +98,7 @@ class FallbackPlanner {
             out.flags = flags[g];
             for (int f = 0; f < final_m[g]; ++f) {
                 const double* q = &final_traj[(g * M + f) * PQP_TRAJ_STRIDE];
-                StateT st{};
-                st.x = q[0]; st.y = q[1]; st.heading = q[2]; st.k = q[3]; st.s = q[4]; st.v = q[5]; st.a = q[6];
-                out.plan.push_back(st);
+                out.plan.push_back(detail::TrajRow::read<StateT>(q));
                 out.t.push_back(q[7]);
             }
         }
@@ -118,10 +106,9 @@ class FallbackPlanner {
     }
 
  private:
-    pqp_handle* h_ = nullptr;
+    detail::OwnedHandle h_;
     double prm_[PQP_FALLBACK_PARAMS];
     std::vector<double> levels_;
-    bool ok_ = false;
 };
 
 }  // namespace PathOptimizationNS

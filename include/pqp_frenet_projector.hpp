@@ -18,6 +18,7 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
@@ -46,23 +47,22 @@ class FrenetProjector {
     // out[i]: s, l (positive to the left), d_heading = constrainAngle(points[i].heading - heading) and the line's x, y, heading, k at s.
     // flags (optional): PQP_PROJ_* of every point - a point that is not finite comes back as NaNs with PQP_PROJ_NOT_FINITE.
     // along (optional): the distance along the tangent, non-zero only where the projection was clipped at the line's end.
-    bool project(const std::vector<State>& points, std::vector<SlState>* out, std::vector<int>* flags = nullptr,
-                 std::vector<double>* along = nullptr) {
+    bool project(const std::vector<State>& points, std::vector<SlState>* out, std::vector<int>* flags = nullptr, std::vector<double>* along = nullptr) {
         if (!out || tab_.empty() || points.empty()) return false;
-        const int q = (int)points.size();
-        std::vector<double> in((size_t)q * 3), proj((size_t)q * PQP_PROJ_STRIDE);
+        const size_t q = points.size();
+        std::vector<double> in(q * 3), proj(q * PQP_PROJ_STRIDE);
         std::vector<int32_t> fl(q);
-        for (int i = 0; i < q; ++i) { in[3 * i] = points[i].x; in[3 * i + 1] = points[i].y; in[3 * i + 2] = points[i].heading; }
-        if (pqp_project_points(&h_, 1, (int)(tab_.size() / 9), tab_.data(), ext_.data(), &length_, q, 3, 1, in.data(), nullptr, proj.data(),
+        for (size_t i = 0; i < q; ++i) detail::PoseRow()(points[i], i, &in[i * 3]);
+        if (pqp_project_points(&h_, 1, (int)(tab_.size() / 9), tab_.data(), ext_.data(), &length_, (int)q, 3, 1, in.data(), nullptr, proj.data(),
                                fl.data()) != PQP_OK)
             return false;
         out->assign(q, SlState());
         if (along) along->resize(q);
-        for (int i = 0; i < q; ++i) {
-            const double* r = &proj[(size_t)i * PQP_PROJ_STRIDE];
+        for (size_t i = 0; i < q; ++i) {
+            const double* p = &proj[i * PQP_PROJ_STRIDE];           // s, l, along, d_heading, then the line's x, y, heading, k at s
             SlState& o = (*out)[i];
-            o.s = r[0]; o.l = r[1]; o.d_heading = r[3]; o.x = r[4]; o.y = r[5]; o.heading = r[6]; o.k = r[7];
-            if (along) (*along)[i] = r[2];
+            o.s = p[0]; o.l = p[1]; o.d_heading = p[3]; o.x = p[4]; o.y = p[5]; o.heading = p[6]; o.k = p[7];
+            if (along) (*along)[i] = p[2];
         }
         if (flags) flags->assign(fl.begin(), fl.end());
         return true;

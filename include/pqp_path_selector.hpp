@@ -14,20 +14,17 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
 class PathSelector {
  public:
     // prm == nullptr: pqp_select_default_params
-    explicit PathSelector(const pqp_select_params* prm = nullptr, int device = 0) {
+    explicit PathSelector(const pqp_select_params* prm = nullptr, int device = 0) : h_(device) {
         if (prm) prm_ = *prm; else pqp_select_default_params(&prm_);
-        ok_ = pqp_create(&h_, nullptr, device, 1, 2) == PQP_OK;
     }
-    PathSelector(const PathSelector&) = delete;
-    PathSelector& operator=(const PathSelector&) = delete;
-    ~PathSelector() { if (h_) pqp_destroy(h_); }
-    bool ok() const { return ok_; }
+    bool ok() const { return h_.ok(); }
     pqp_select_params& params() { return prm_; }
 
     // candidates of group g: group_start[g] .. group_start[g + 1] - 1 (ascending from 0 to candidates.size()).  best[g]: the index of the
@@ -36,37 +33,30 @@ class PathSelector {
     // a candidate that collides cannot win while params().require_free is set.  false: a GPU error or a bad argument (pqp_last_error()).
     bool selectBest(const std::vector<std::vector<SlState>>& candidates, const std::vector<int>& group_start, std::vector<int>* best,
                     std::vector<double>* score = nullptr, const std::vector<int>* first_collision = nullptr) {
-        if (!ok_ || !best || candidates.empty() || group_start.empty() || (first_collision && first_collision->size() != candidates.size()))
+        if (!ok() || !best || candidates.empty() || group_start.empty() || (first_collision && first_collision->size() != candidates.size()))
             return false;
-        const int batch = (int)candidates.size(), groups = (int)group_start.size() - 1;
-        int n = 1;
-        for (const auto& c : candidates) n = (int)c.size() > n ? (int)c.size() : n;
-        std::vector<double> paths((size_t)batch * n * PQP_OUT_STRIDE, 0.0), terms((size_t)batch * PQP_SCORE_STRIDE, 0.0);
-        std::vector<int32_t> n_of(batch), starts(group_start.begin(), group_start.end()), first, won(groups > 0 ? groups : 1, -1);
-        for (int b = 0; b < batch; ++b) {
-            n_of[b] = (int32_t)candidates[b].size();
-            for (size_t i = 0; i < candidates[b].size(); ++i) {
-                const SlState& s = candidates[b][i];
-                double* r = &paths[((size_t)b * n + i) * PQP_OUT_STRIDE];
-                r[0] = s.x; r[1] = s.y; r[2] = s.heading; r[3] = s.l; r[4] = s.d_heading; r[5] = s.k; r[6] = s.d_k;
-            }
-        }
+        const size_t B = candidates.size();
+        const int groups = (int)group_start.size() - 1;
+        const detail::Packed paths = detail::pack(candidates, PQP_OUT_STRIDE, [](const SlState& s, size_t, double* r) {          // the chain's output row
+            r[0] = s.x; r[1] = s.y; r[2] = s.heading; r[3] = s.l; r[4] = s.d_heading; r[5] = s.k; r[6] = s.d_k;
+        });
+        std::vector<double> terms(B * PQP_SCORE_STRIDE, 0.0);
+        std::vector<int32_t> starts(group_start.begin(), group_start.end()), first, won(groups > 0 ? groups : 1, -1);
         if (first_collision) first.assign(first_collision->begin(), first_collision->end());
-        if (pqp_select_paths(h_, &prm_, batch, n, PQP_OUT_STRIDE, paths.data(), n_of.data(), nullptr, nullptr, first_collision ? first.data() : nullptr,
-                             nullptr, groups, starts.data(), terms.data(), won.data(), nullptr, nullptr) != PQP_OK)
+        if (pqp_select_paths(h_.get(), &prm_, (int)B, (int)paths.n, PQP_OUT_STRIDE, paths.rows.data(), paths.count.data(), nullptr, nullptr,
+                             first_collision ? first.data() : nullptr, nullptr, groups, starts.data(), terms.data(), won.data(), nullptr, nullptr) != PQP_OK)
             return false;
         best->assign(won.begin(), won.begin() + groups);
         if (score) {
-            score->resize(batch);
-            for (int b = 0; b < batch; ++b) (*score)[b] = terms[(size_t)b * PQP_SCORE_STRIDE];
+            score->resize(B);
+            for (size_t b = 0; b < B; ++b) (*score)[b] = terms[b * PQP_SCORE_STRIDE];
         }
         return true;
     }
 
  private:
-    pqp_handle* h_ = nullptr;
+    detail::OwnedHandle h_;
     pqp_select_params prm_;
-    bool ok_ = false;
 };
 
 }  // namespace PathOptimizationNS

@@ -61,17 +61,11 @@ class PlanSampler {
                             flags.data()) != PQP_OK)
             return false;
         results->assign(B, Result());
-        states->assign(B, std::vector<StateT>());
+        detail::read_trajectories(fine, M, m_of, states);
         for (size_t b = 0; b < B; ++b) {
             Result& r = (*results)[b];
             r.flags = flags[b]; r.refine_flags = raw.flags[b]; r.search_flags = se.flags[b]; r.layers = se.reached[b]; r.dt = dt / (double)r_;
             r.defect = defect[b]; r.excess = excess[b];
-            for (int f = 0; f < m_of[b]; ++f) {
-                const double* row = &fine[(b * M + f) * PQP_TRAJ_STRIDE];
-                StateT st{};
-                st.x = row[0]; st.y = row[1]; st.heading = row[2]; st.k = row[3]; st.s = row[4]; st.v = row[5]; st.a = row[6];
-                (*states)[b].push_back(st);
-            }
         }
         return true;
     }

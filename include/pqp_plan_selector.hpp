@@ -17,19 +17,14 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
 class PlanSelector {
  public:
-    explicit PlanSelector(int device = 0) {
-        pqp_rank_default_params(prm_, &require_free_);
-        ok_ = pqp_create(&h_, nullptr, device, 1, 2) == PQP_OK;
-    }
-    PlanSelector(const PlanSelector&) = delete;
-    PlanSelector& operator=(const PlanSelector&) = delete;
-    ~PlanSelector() { if (h_) pqp_destroy(h_); }
-    bool ok() const { return ok_; }
+    explicit PlanSelector(int device = 0) : h_(device) { pqp_rank_default_params(prm_, &require_free_); }
+    bool ok() const { return h_.ok(); }
     double* weights() { return prm_; }
     int& require_free() { return require_free_; }
 
@@ -48,53 +43,36 @@ class PlanSelector {
     bool selectBest(const std::vector<std::vector<StateT>>& trajectories, double dt, const std::vector<int>& group_start, std::vector<int>* best,
                     std::vector<double>* terms = nullptr, std::vector<std::vector<StateT>>* winners = nullptr, const Optional& opt = Optional()) {
         const size_t B = trajectories.size();
-        if (!ok_ || !best || B == 0 || group_start.empty() || (opt.path_score && opt.path_score->size() != B) ||
+        if (!ok() || !best || B == 0 || group_start.empty() || (opt.path_score && opt.path_score->size() != B) ||
             (opt.search_flags && opt.search_flags->size() != B) || (opt.first_hit && opt.first_hit->size() != B))
             return false;
         const int batch = (int)B, groups = (int)group_start.size() - 1;
-        size_t m = 1;
-        for (const auto& t : trajectories) m = t.size() > m ? t.size() : m;
-        const size_t G = groups > 0 ? groups : 1;
-        std::vector<double> traj(B * m * PQP_TRAJ_STRIDE, 0.0), rec(B * PQP_PLAN_SCORE_STRIDE, 0.0), path_terms, won_rows(G * m * PQP_TRAJ_STRIDE, 0.0);
-        std::vector<int32_t> m_of(B), starts(group_start.begin(), group_start.end()), sflags, first, won(G, -1), won_m(G, 0);
-        for (size_t b = 0; b < B; ++b) {
-            m_of[b] = (int32_t)trajectories[b].size();
-            for (size_t f = 0; f < trajectories[b].size(); ++f) {
-                const StateT& s = trajectories[b][f];
-                double* r = &traj[(b * m + f) * PQP_TRAJ_STRIDE];
-                r[0] = s.x; r[1] = s.y; r[2] = s.heading; r[3] = s.k; r[4] = s.s; r[5] = s.v; r[6] = s.a; r[7] = (double)f * dt;
-            }
-        }
+        const detail::Packed traj = detail::pack(trajectories, PQP_TRAJ_STRIDE, detail::TimedTrajRow{dt});
+        const size_t m = traj.n, G = groups > 0 ? groups : 1;
+        std::vector<double> rec(B * PQP_PLAN_SCORE_STRIDE, 0.0), path_terms, won_rows(G * m * PQP_TRAJ_STRIDE, 0.0);
+        std::vector<int32_t> starts(group_start.begin(), group_start.end()), sflags, first, won(G, -1), won_m(G, 0);
         if (opt.path_score) {
             path_terms.assign(B * PQP_SCORE_STRIDE, 0.0);
             for (size_t b = 0; b < B; ++b) { path_terms[b * PQP_SCORE_STRIDE] = (*opt.path_score)[b]; path_terms[b * PQP_SCORE_STRIDE + 7] = 1.0; }
         }
         if (opt.search_flags) sflags.assign(opt.search_flags->begin(), opt.search_flags->end());
         if (opt.first_hit) first.assign(opt.first_hit->begin(), opt.first_hit->end());
-        if (pqp_select_plans(h_, prm_, require_free_, batch, (int)m, PQP_TRAJ_STRIDE, traj.data(), m_of.data(), opt.path_score ? path_terms.data() : nullptr,
-                             opt.search_flags ? sflags.data() : nullptr, opt.first_hit ? first.data() : nullptr, nullptr, 0, 0, nullptr, nullptr, groups,
-                             starts.data(), rec.data(), won.data(), won_rows.data(), won_m.data(), nullptr, nullptr) != PQP_OK)
+        if (pqp_select_plans(h_.get(), prm_, require_free_, batch, (int)m, PQP_TRAJ_STRIDE, traj.rows.data(), traj.count.data(),
+                             opt.path_score ? path_terms.data() : nullptr, opt.search_flags ? sflags.data() : nullptr, opt.first_hit ? first.data() : nullptr,
+                             nullptr, 0, 0, nullptr, nullptr, groups, starts.data(), rec.data(), won.data(), won_rows.data(), won_m.data(), nullptr,
+                             nullptr) != PQP_OK)
             return false;
         best->assign(won.begin(), won.begin() + groups);
         if (terms) *terms = rec;
-        if (winners) {
-            winners->assign(groups, std::vector<StateT>());
-            for (int g = 0; g < groups; ++g)
-                for (int f = 0; f < won_m[g]; ++f) {
-                    const double* r = &won_rows[((size_t)g * m + f) * PQP_TRAJ_STRIDE];
-                    StateT st{};
-                    st.x = r[0]; st.y = r[1]; st.heading = r[2]; st.k = r[3]; st.s = r[4]; st.v = r[5]; st.a = r[6];
-                    (*winners)[g].push_back(st);
-                }
-        }
+        won_m.resize(groups);
+        if (winners) detail::read_trajectories(won_rows, m, won_m, winners);
         return true;
     }
 
  private:
-    pqp_handle* h_ = nullptr;
+    detail::OwnedHandle h_;
     double prm_[PQP_RANK_PARAMS];
     int require_free_ = 1;
-    bool ok_ = false;
 };
 
 }  // namespace PathOptimizationNS

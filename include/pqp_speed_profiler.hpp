@@ -17,6 +17,7 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
@@ -44,24 +45,17 @@ class SpeedProfiler {
         const size_t B = paths->size();
         if (v_start.size() != B || (stop_before && stop_before->size() != B) || (v_end && v_end->size() != B) || (v_limit && v_limit->size() != B))
             return false;
-        size_t n = 1;
-        for (const auto& p : *paths) n = std::max(n, p.size());
-        std::vector<double> in(B * n * 6, 0.0), lim, prof(B * n * PQP_SPEED_STRIDE);
-        std::vector<int32_t> n_of(B), stop, fl(B);
-        if (v_limit) lim.assign(B * n, 0.0);
-        for (size_t b = 0; b < B; ++b) {
-            const auto& p = (*paths)[b];
-            n_of[b] = (int32_t)p.size();
-            if (v_limit && (*v_limit)[b].size() != p.size()) return false;
-            for (size_t i = 0; i < p.size(); ++i) {
-                double* r = &in[(b * n + i) * 6];
-                r[0] = p[i].x; r[1] = p[i].y; r[5] = p[i].k;
-                if (v_limit) lim[b * n + i] = (*v_limit)[b][i];
-            }
-        }
+        for (size_t b = 0; v_limit && b < B; ++b)
+            if ((*v_limit)[b].size() != (*paths)[b].size()) return false;
+        const detail::Packed in = detail::pack(*paths, 6, detail::PathRow{false});
+        const size_t n = in.n;
+        detail::Packed lim;
+        if (v_limit) lim = detail::pack(*v_limit, 1, [](double v, size_t, double* r) { *r = v; });
+        std::vector<double> prof(B * n * PQP_SPEED_STRIDE);
+        std::vector<int32_t> stop, fl(B);
         if (stop_before) stop.assign(stop_before->begin(), stop_before->end());
-        if (pqp_speed_profile(&h_, &prm_, (int)B, (int)n, 6, in.data(), n_of.data(), stop_before ? stop.data() : nullptr,
-                              v_limit ? lim.data() : nullptr, v_start.data(), v_end ? v_end->data() : nullptr, prof.data(), fl.data()) != PQP_OK)
+        if (pqp_speed_profile(&h_, &prm_, (int)B, (int)n, 6, in.rows.data(), in.count.data(), stop_before ? stop.data() : nullptr,
+                              v_limit ? lim.rows.data() : nullptr, v_start.data(), v_end ? v_end->data() : nullptr, prof.data(), fl.data()) != PQP_OK)
             return false;
         if (times) times->assign(B, std::vector<double>());
         for (size_t b = 0; b < B; ++b) {
@@ -71,7 +65,7 @@ class SpeedProfiler {
             if (times) (*times)[b].assign(p.size(), 0.0);
             for (size_t i = 0; i < driven; ++i) {
                 const double* r = &prof[(b * n + i) * PQP_SPEED_STRIDE];
-                p[i].s = r[0]; p[i].v = r[1]; p[i].a = r[2];
+                detail::ProfileRow::read(r, &p[i]);
                 if (times) (*times)[b][i] = r[3];
             }
         }

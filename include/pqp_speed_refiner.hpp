@@ -54,19 +54,13 @@ class SpeedRefiner {
         if (!results || !states || !refine_raw(paths, v_start, scenes, scene_of, layers, &raw)) return false;
         const size_t B = raw.search.B, m = raw.search.m;
         results->assign(B, Result());
-        states->assign(B, std::vector<StateT>());
+        detail::read_trajectories(raw.traj, m, raw.search.reached, states);
         for (size_t b = 0; b < B; ++b) {
             Result& r = (*results)[b];
             r.flags = raw.flags[b]; r.status = raw.status[b]; r.search_flags = raw.search.flags[b]; r.cost = raw.cost[b]; r.excess = raw.excess[b];
             for (size_t k = 0; k < m; ++k) {
                 const double* c = &raw.bounds[(b * m + k) * 3];
                 r.lo.push_back(c[0]); r.hi.push_back(c[1]); r.vcap.push_back(c[2]);
-            }
-            for (int k = 0; k < raw.search.reached[b]; ++k) {
-                const double* row = &raw.traj[(b * m + k) * PQP_TRAJ_STRIDE];
-                StateT st{};
-                st.x = row[0]; st.y = row[1]; st.heading = row[2]; st.k = row[3]; st.s = row[4]; st.v = row[5]; st.a = row[6];
-                (*states)[b].push_back(st);
             }
         }
         return true;

@@ -14,6 +14,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 #include "pqp.h"
@@ -61,7 +62,7 @@ class SpeedSearcher {
         if (!plans || !search_raw(paths, v_start, scenes, scene_of, layers, false, &raw)) return false;
         const size_t B = raw.B, m = raw.m;
         plans->assign(B, Plan());
-        if (states) states->assign(B, std::vector<StateT>());
+        if (states) detail::read_trajectories(raw.traj, m, raw.reached, states);
         for (size_t b = 0; b < B; ++b) {
             Plan& p = (*plans)[b];
             p.flags = raw.flags[b];
@@ -69,12 +70,6 @@ class SpeedSearcher {
             for (int k = 0; k < raw.reached[b]; ++k) {
                 p.station.push_back(raw.steps[(b * m + k) * 2]);
                 p.step.push_back(raw.steps[(b * m + k) * 2 + 1]);
-                if (states) {
-                    const double* r = &raw.traj[(b * m + k) * PQP_TRAJ_STRIDE];
-                    StateT st{};
-                    st.x = r[0]; st.y = r[1]; st.heading = r[2]; st.k = r[3]; st.s = r[4]; st.v = r[5]; st.a = r[6];
-                    (*states)[b].push_back(st);
-                }
             }
         }
         return true;
@@ -88,47 +83,23 @@ class SpeedSearcher {
         if (!raw || paths.empty() || scenes.empty() || v_start.size() != paths.size()) return false;
         const size_t B = paths.size(), S = scenes.size();
         if (scene_of && scene_of->size() != B) return false;
-        size_t n = 1, m = (size_t)std::max(layers, 1), a_max = 0;
-        for (const auto& p : paths) n = std::max(n, p.size());
-        for (const auto& s : scenes) {
-            a_max = std::max(a_max, s.size());
-            for (const auto& a : s) m = std::max(m, a.size());
-        }
+        size_t m = (size_t)std::max(layers, 1);
+        for (const auto& s : scenes) m = detail::longest(s, m);
+        detail::Packed rows = detail::pack(paths, 6, detail::PathRow());
+        const detail::AgentRows ag = detail::pack_agents(scenes, m);
+        const size_t n = rows.n;
         raw->B = B; raw->n = n; raw->m = m;
-        raw->rows.assign(B * n * 6, 0.0);
-        raw->profile.assign(B * n * PQP_SPEED_STRIDE, 0.0);
+        raw->rows = std::move(rows.rows);
+        raw->n_of = std::move(rows.count);
+        raw->profile = detail::pack(paths, PQP_SPEED_STRIDE, detail::ProfileRow()).rows;
         raw->traj.assign(B * m * PQP_TRAJ_STRIDE, 0.0);
         raw->cost.assign(B, 0.0);
-        raw->n_of.assign(B, 0); raw->steps.assign(B * m * 2, 0); raw->reached.assign(B, 0); raw->flags.assign(B, 0);
+        raw->steps.assign(B * m * 2, 0); raw->reached.assign(B, 0); raw->flags.assign(B, 0);
         raw->blocked.assign(with_blocked ? B * m * (size_t)((std::max(prm_.stations, 0) + 31) / 32) : 0, 0);
-        std::vector<double> agents(S * a_max * m * PQP_AGENT_STRIDE, 0.0);
-        std::vector<int32_t> a_of(S), scene;
-        for (size_t b = 0; b < B; ++b) {
-            raw->n_of[b] = (int32_t)paths[b].size();
-            for (size_t i = 0; i < paths[b].size(); ++i) {
-                const StateT& st = paths[b][i];
-                double* r = &raw->rows[(b * n + i) * 6];
-                double* o = &raw->profile[(b * n + i) * PQP_SPEED_STRIDE];
-                r[0] = st.x; r[1] = st.y; r[2] = st.heading; r[5] = st.k;
-                o[0] = st.s; o[1] = st.v; o[2] = st.a;
-            }
-        }
-        for (size_t s = 0; s < S; ++s) {
-            a_of[s] = (int32_t)scenes[s].size();
-            for (size_t a = 0; a < scenes[s].size(); ++a)
-                for (size_t k = 0; k < m; ++k) {
-                    double* r = &agents[((s * a_max + a) * m + k) * PQP_AGENT_STRIDE];
-                    if (k < scenes[s][a].size()) {
-                        const PredictedAgent& p = scenes[s][a][k];
-                        r[0] = p.x; r[1] = p.y; r[2] = p.heading; r[3] = p.half_length; r[4] = p.half_width; r[5] = p.radius;
-                    } else {
-                        r[3] = -1.0;
-                    }
-                }
-        }
+        std::vector<int32_t> scene;
         if (scene_of) scene.assign(scene_of->begin(), scene_of->end());
         return pqp_speed_search(&h_, &prm_, &car_, (int)B, (int)n, 6, raw->rows.data(), raw->n_of.data(), nullptr, raw->profile.data(), v_start.data(),
-                                (int)m, (int)S, (int)a_max, a_max ? agents.data() : nullptr, a_of.data(), scene_of ? scene.data() : nullptr,
+                                (int)m, (int)S, (int)ag.a_max, ag.a_max ? ag.rows.data() : nullptr, ag.a_of.data(), scene_of ? scene.data() : nullptr,
                                 with_blocked ? raw->blocked.data() : nullptr, raw->steps.data(), raw->traj.data(), raw->cost.data(),
                                 raw->reached.data(), raw->flags.data()) == PQP_OK;
     }

@@ -9,7 +9,6 @@
 //
 // Not copyable, not thread-safe, no exceptions; sample() returns false on a GPU error or a bad argument (pqp_last_error()).
 #pragma once
-#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -17,6 +16,7 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
@@ -44,23 +44,17 @@ class TrajectorySampler {
         if (!samples || paths.empty() || m < 1) return false;
         const size_t B = paths.size();
         if (times.size() != B || (stop_before && stop_before->size() != B) || (t0 && t0->size() != B)) return false;
-        size_t n = 1;
-        for (const auto& p : paths) n = std::max(n, p.size());
-        std::vector<double> in(B * n * 6, 0.0), prof(B * n * PQP_SPEED_STRIDE, 0.0), traj(B * (size_t)m * PQP_TRAJ_STRIDE);
-        std::vector<int32_t> n_of(B), stop, m_of(B), fl(B);
-        for (size_t b = 0; b < B; ++b) {
-            const auto& p = paths[b];
-            if (times[b].size() != p.size()) return false;
-            n_of[b] = (int32_t)p.size();
-            for (size_t i = 0; i < p.size(); ++i) {
-                double* r = &in[(b * n + i) * 6];
-                r[0] = p[i].x; r[1] = p[i].y; r[2] = p[i].heading; r[5] = p[i].k;
-                double* o = &prof[(b * n + i) * PQP_SPEED_STRIDE];
-                o[0] = p[i].s; o[1] = p[i].v; o[2] = p[i].a; o[3] = times[b][i];
-            }
-        }
+        for (size_t b = 0; b < B; ++b)
+            if (times[b].size() != paths[b].size()) return false;
+        const detail::Packed in = detail::pack(paths, 6, detail::PathRow());
+        detail::Packed prof = detail::pack(paths, PQP_SPEED_STRIDE, detail::ProfileRow());
+        const size_t n = in.n;
+        for (size_t b = 0; b < B; ++b)
+            for (size_t i = 0; i < times[b].size(); ++i) prof.rows[(b * n + i) * PQP_SPEED_STRIDE + 3] = times[b][i];
+        std::vector<double> traj(B * (size_t)m * PQP_TRAJ_STRIDE);
+        std::vector<int32_t> stop, m_of(B), fl(B);
         if (stop_before) stop.assign(stop_before->begin(), stop_before->end());
-        if (pqp_sample_trajectory(&h_, &prm_, (int)B, (int)n, 6, in.data(), n_of.data(), stop_before ? stop.data() : nullptr, prof.data(),
+        if (pqp_sample_trajectory(&h_, &prm_, (int)B, (int)n, 6, in.rows.data(), in.count.data(), stop_before ? stop.data() : nullptr, prof.rows.data(),
                                   t0 ? t0->data() : nullptr, m, traj.data(), m_of.data(), fl.data()) != PQP_OK)
             return false;
         samples->assign(B, std::vector<State>());
@@ -72,8 +66,7 @@ class TrajectorySampler {
             if (sample_times) (*sample_times)[b].resize(rows);
             for (size_t k = 0; k < rows; ++k) {
                 const double* r = &traj[(b * (size_t)m + k) * PQP_TRAJ_STRIDE];
-                State& q = (*samples)[b][k];
-                q.x = r[0]; q.y = r[1]; q.heading = r[2]; q.k = r[3]; q.s = r[4]; q.v = r[5]; q.a = r[6];
+                (*samples)[b][k] = detail::TrajRow::read<State>(r);
                 if (sample_times) (*sample_times)[b][k] = r[7];
             }
         }

@@ -18,19 +18,14 @@
 #ifndef PQP_USE_REFERENCE_TYPES
 #include "pqp_types.hpp"
 #endif
+#include "pqp_wrapper_detail.hpp"
 
 namespace PathOptimizationNS {
 
 class TrajectoryStitcher {
  public:
-    explicit TrajectoryStitcher(int device = 0) {
-        pqp_stitch_default_params(prm_, &keep_);
-        ok_ = pqp_create(&h_, nullptr, device, 1, 2) == PQP_OK;
-    }
-    TrajectoryStitcher(const TrajectoryStitcher&) = delete;
-    TrajectoryStitcher& operator=(const TrajectoryStitcher&) = delete;
-    ~TrajectoryStitcher() { if (h_) pqp_destroy(h_); }
-    bool ok() const { return ok_; }
+    explicit TrajectoryStitcher(int device = 0) : h_(device) { pqp_stitch_default_params(prm_, &keep_); }
+    bool ok() const { return h_.ok(); }
     double* params() { return prm_; }
     int& keep() { return keep_; }
 
@@ -58,44 +53,33 @@ class TrajectoryStitcher {
     template <class StateT>
     bool stitch(const std::vector<std::vector<StateT>>& previous, double dt, const std::vector<Measured>& measured, std::vector<Result<StateT>>* results) {
         const size_t G = previous.size();
-        if (!ok_ || !results || G == 0 || measured.size() != G) return false;
-        size_t m = 1;
-        for (const auto& t : previous) m = t.size() > m ? t.size() : m;
-        std::vector<double> prev(G * m * PQP_TRAJ_STRIDE, 0.0), meas(G * 6), t_now(G), state(G * PQP_TRAJ_STRIDE), dev(G * 3), prefix(G * m * PQP_TRAJ_STRIDE);
-        std::vector<int32_t> m_of(G), flags(G), idx(G * 3), prefix_n(G);
+        if (!ok() || !results || G == 0 || measured.size() != G) return false;
+        const detail::Packed prev = detail::pack(previous, PQP_TRAJ_STRIDE, detail::TimedTrajRow{dt});
+        const size_t m = prev.n;
+        std::vector<double> meas(G * 6), t_now(G), state(G * PQP_TRAJ_STRIDE), dev(G * 3), prefix(G * m * PQP_TRAJ_STRIDE);
+        std::vector<int32_t> flags(G), idx(G * 3), prefix_n(G);
         for (size_t g = 0; g < G; ++g) {
-            m_of[g] = (int32_t)previous[g].size();
-            for (size_t f = 0; f < previous[g].size(); ++f) {
-                const StateT& s = previous[g][f];
-                double* r = &prev[(g * m + f) * PQP_TRAJ_STRIDE];
-                r[0] = s.x; r[1] = s.y; r[2] = s.heading; r[3] = s.k; r[4] = s.s; r[5] = s.v; r[6] = s.a; r[7] = (double)f * dt;
-            }
             const Measured& c = measured[g];
             double* q = &meas[g * 6];
             q[0] = c.x; q[1] = c.y; q[2] = c.heading; q[3] = c.v; q[4] = c.a; q[5] = c.yaw_rate;
             t_now[g] = c.t;
         }
-        if (pqp_stitch_trajectory(h_, prm_, keep_, (int)m, (int)G, (int)m, PQP_TRAJ_STRIDE, prev.data(), m_of.data(), meas.data(), t_now.data(), (int)G,
-                                  nullptr, state.data(), flags.data(), dev.data(), idx.data(), prefix.data(), prefix_n.data(), nullptr, nullptr,
-                                  nullptr) != PQP_OK)
+        if (pqp_stitch_trajectory(h_.get(), prm_, keep_, (int)m, (int)G, (int)m, PQP_TRAJ_STRIDE, prev.rows.data(), prev.count.data(),
+                                  meas.data(), t_now.data(), (int)G, nullptr, state.data(), flags.data(), dev.data(), idx.data(), prefix.data(),
+                                  prefix_n.data(), nullptr, nullptr, nullptr) != PQP_OK)
             return false;
         results->assign(G, Result<StateT>());
-        const auto to_state = [](const double* r) {
-            StateT st{};
-            st.x = r[0]; st.y = r[1]; st.heading = r[2]; st.k = r[3]; st.s = r[4]; st.v = r[5]; st.a = r[6];
-            return st;
-        };
         for (size_t g = 0; g < G; ++g) {
             Result<StateT>& out = (*results)[g];
             const double* r = &state[g * PQP_TRAJ_STRIDE];
             for (int c = 0; c < PQP_TRAJ_STRIDE; ++c) out.row[c] = r[c];
-            out.start = to_state(r);
+            out.start = detail::TrajRow::read<StateT>(r);
             out.t_start = r[7];
             out.flags = flags[g];
             out.lon = dev[g * 3]; out.lat = dev[g * 3 + 1]; out.dh = dev[g * 3 + 2];
             for (int j = 0; j < prefix_n[g]; ++j) {
                 const double* p = &prefix[(g * m + j) * PQP_TRAJ_STRIDE];
-                out.prefix.push_back(to_state(p));
+                out.prefix.push_back(detail::TrajRow::read<StateT>(p));
                 out.prefix_t.push_back(p[7]);
             }
         }
@@ -103,10 +87,9 @@ class TrajectoryStitcher {
     }
 
  private:
-    pqp_handle* h_ = nullptr;
+    detail::OwnedHandle h_;
     double prm_[PQP_STITCH_PARAMS];
     int keep_ = 20;
-    bool ok_ = false;
 };
 
 }  // namespace PathOptimizationNS

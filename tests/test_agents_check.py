@@ -110,21 +110,6 @@ def test_checker_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
     assert r.returncode == 1 and "no checker" in r.stderr
 
 
-def test_checker_compiles_against_the_reference_headers():
-    """with PQP_USE_REFERENCE_TYPES the checker reads the reference's own State (include/data_struct/data_struct.hpp:14-26)"""
-    if not os.path.isdir(cpp_demo.REF_INCLUDE):
-        pytest.skip("the reference tree is not on this box")
-    src = ("#include \"pqp_agent_checker.hpp\"\n"
-           "using namespace PathOptimizationNS;\n"
-           "bool f(AgentChecker& c, const std::vector<std::vector<State>>& a, const std::vector<std::vector<SlState>>& b,\n"
-           "       const std::vector<std::vector<std::vector<PredictedAgent>>>& s, std::vector<int>* o) { return c.check(a, s, o, o) && c.check(b, s, o, o); }\n")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
-           "-include", "data_struct/data_struct.hpp", "-"]
-    r = subprocess.run(cmd, input=src, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert "error" not in r.stderr
-
-
 @pytest.mark.parametrize("name,tag,vgprs,occupancy", [("agent_frames_kernel", "", 40, 8), ("agents_check_kernel", "ILb1E", 96, 5),
                                                        ("agents_check_kernel", "ILb0E", 112, 4)])
 def test_the_kernels_use_no_scratch_and_no_lds(hip_lib, name, tag, vgprs, occupancy):

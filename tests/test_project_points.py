@@ -6,7 +6,6 @@ import re
 import subprocess
 
 import numpy as np
-import pytest
 
 import build_util
 import corridor_oracle as K
@@ -55,16 +54,6 @@ def test_projector_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
     P.write_case(path, s, s, np.zeros(11), np.array([[2.5, 1.0, 0.1]]))
     r = subprocess.run([exe, str(path)], capture_output=True, text=True)
     assert r.returncode == 1 and "no projector" in r.stderr
-
-
-@pytest.mark.skipif(not os.path.isdir(cpp_demo.REF_INCLUDE), reason="the reference tree is not on this box")
-def test_projector_compiles_against_the_reference_headers():
-    """with PQP_USE_REFERENCE_TYPES the projector takes the reference's own State / SlState (include/data_struct/data_struct.hpp)"""
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
-           "-include", "data_struct/data_struct.hpp", os.path.join(ROOT, "include", "pqp_frenet_projector.hpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert "error" not in r.stderr
 
 
 def test_the_kernel_uses_no_scratch_and_one_tile_of_lds(hip_lib):

@@ -94,21 +94,6 @@ def test_sampler_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
     assert r.returncode == 1 and "no sampler" in r.stderr
 
 
-def test_sampler_compiles_against_the_reference_headers():
-    """with PQP_USE_REFERENCE_TYPES the sampler reads and returns the reference's own State (include/data_struct/data_struct.hpp:14-26)"""
-    if not os.path.isdir(cpp_demo.REF_INCLUDE):
-        pytest.skip("the reference tree is not on this box")
-    src = ("#include \"pqp_trajectory_sampler.hpp\"\n"
-           "using namespace PathOptimizationNS;\n"
-           "bool f(TrajectorySampler& t, const std::vector<std::vector<State>>& a, const std::vector<std::vector<SlState>>& b,\n"
-           "       const std::vector<std::vector<double>>& tt, std::vector<std::vector<State>>* o) { return t.sample(a, tt, 5, o) && t.sample(b, tt, 5, o); }\n")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
-           "-include", "data_struct/data_struct.hpp", "-"]
-    r = subprocess.run(cmd, input=src, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert "error" not in r.stderr
-
-
 def test_the_kernel_uses_no_scratch_and_a_constant_lds(hip_lib):
     r = build_util.find_kernel(build_util.kernel_report(), "sample_trajectory_kernel")
     assert r["ScratchSize"] == 0, r

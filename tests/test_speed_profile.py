@@ -88,17 +88,6 @@ def test_profiler_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
     assert r.returncode == 1 and "no profiler" in r.stderr
 
 
-def test_profiler_compiles_against_the_reference_headers():
-    """with PQP_USE_REFERENCE_TYPES the profiler fills the reference's own State::s, v, a (include/data_struct/data_struct.hpp:14-26)"""
-    if not os.path.isdir(cpp_demo.REF_INCLUDE):
-        pytest.skip("the reference tree is not on this box")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
-           "-include", "data_struct/data_struct.hpp", os.path.join(ROOT, "include", "pqp_speed_profiler.hpp")]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert "error" not in r.stderr
-
-
 def test_the_kernel_uses_no_scratch_and_no_lds(hip_lib):
     r = build_util.find_kernel(build_util.kernel_report(), "speed_profile_kernel")
     assert r["ScratchSize"] == 0, r

@@ -160,23 +160,6 @@ def test_searcher_builds_and_fails_cleanly_without_gpu(hip_lib, tmp_path):
     assert r.returncode == 2 and "short or bad file" in r.stderr
 
 
-def test_searcher_compiles_against_the_reference_headers():
-    """with PQP_USE_REFERENCE_TYPES the searcher reads the reference's own State (include/data_struct/data_struct.hpp:14-26)"""
-    if not os.path.isdir(cpp_demo.REF_INCLUDE):
-        pytest.skip("the reference tree is not on this box")
-    src = ("#include \"pqp_speed_searcher.hpp\"\n"
-           "using namespace PathOptimizationNS;\n"
-           "bool f(SpeedSearcher& c, const std::vector<std::vector<State>>& a, const std::vector<std::vector<SlState>>& b, const std::vector<double>& v,\n"
-           "       const std::vector<std::vector<std::vector<PredictedAgent>>>& s, std::vector<SpeedSearcher::Plan>* o) {\n"
-           "    std::vector<std::vector<State>> x; std::vector<std::vector<SlState>> y;\n"
-           "    return c.search(a, v, s, o, &x) && c.search(b, v, s, o, &y); }\n")
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-x", "c++", "-DPQP_USE_REFERENCE_TYPES", "-I" + cpp_demo.REF_INCLUDE, "-I" + os.path.join(ROOT, "include"),
-           "-include", "data_struct/data_struct.hpp", "-"]
-    r = subprocess.run(cmd, input=src, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    assert "error" not in r.stderr
-
-
 @pytest.mark.parametrize("name,vgprs,occupancy,lds", [("st_occupancy_kernel", 88, 5, 0), ("st_search_kernel", 64, 2, 65536)])
 def test_the_kernels_use_no_scratch_and_spill_nothing(hip_lib, name, vgprs, occupancy, lds):
     """what the build gives today: 84 VGPRs for the occupancy (the six centres, the bounding centre and the circle test's operands) and 60 for
